@@ -2,7 +2,7 @@
 """Headline benchmark: forward tokens/s of the GPT-2-shaped stack (d=1024, H=16, L=24, S=4096, B=8 per GPU,
 bf16, causal FA3 + FusedMLP) on N MI355X, plus the roofline of the dominant kernel and the CPU baseline.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
         N = 1: runs in this process.  N > 1 without a launcher (WORLD_SIZE unset): this process touches no GPU, starts
         N child processes (one rank per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) and relays rank 0's line.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -11,7 +11,9 @@ bf16, causal FA3 + FusedMLP) on N MI355X, plus the roofline of the dominant kern
 One "step" = one forward of the whole stack over one synthetic batch resident in HBM.  tokens/s =
 B*S / avg latency (reference benchmarks/runners.py:356-358).  N > 1: one process per GPU over RCCL, the batch
 dimension is sharded (independent sequences, no data-path collective) -> weak scaling; `ranks_seen` is an all-reduce
-of ones over the job.  After the timed region, under "extra" (never inside it, never part of `value`):
+of ones over the job.  --dump-outputs DIR: rank 0 writes the hidden states its last timed step returned (float32; a fixed,
+seeded sample of token rows when the whole would exceed 64 MB) as DIR/*.npy, so that two builds can be compared output for
+output on the same seeded inputs.  After the timed region, under "extra" (never inside it, never part of `value`):
   N = 1: paged decode (HBM roofline), the C5 workload (non-causal cross attention d 1280 / Dh 80 + FusedMLP-GELU);
   N > 1: BASELINE configs 3 and 4 -- the tensor-parallel stack (tp 2 and 4: RCCL all-reduce over xGMI, overlapped
          with the row-parallel GEMM vs not) and ring attention at S 65 536 over the N ranks (K/V exchange overlapped
@@ -358,6 +360,35 @@ def cpu_baseline_c1():
                       "(hidden states in / out: no embedding or LM head)", "avg_latency_ms": r["avg_latency_s"] * 1e3}
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, y, seed=0):
+    """What the timed path returned in its last step -> dirname/<name>.npy (float32), at most DUMP_MAX_BYTES in all.  The stack
+    returns hidden states [B, S, d]; when they do not fit, a fixed set of token rows is written, drawn with `seed` on the host so
+    that two builds of the project dump the same rows of the same inputs.  Returns the description that goes into the result line."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    B, S, d = y.shape
+    flat = y.reshape(B * S, d)
+    rows = (DUMP_MAX_BYTES - 8 * B * S - 4096) // (4 * d)  # room left beside the index file and the two .npy headers
+    if rows >= B * S:
+        idx = torch.arange(B * S)
+        sample = "all rows"
+    else:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randperm(B * S, generator=g)[:rows].sort().values
+        sample = f"{rows} of {B * S} token rows (randperm, seed {seed}, sorted)"
+    files = {"hidden_states": flat[idx.to(flat.device)].float().cpu().numpy(),
+             "hidden_states_rows": idx.double().numpy()}  # flat token index b * S + s of every dumped row
+    for name, arr in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+    return {"dir": dirname, "sample": sample,
+            "files": {name + ".npy": {"shape": list(arr.shape), "dtype": str(arr.dtype)} for name, arr in files.items()}}
+
+
 class Watchdog:
     """If a fenced leg does not finish in `seconds`, rank 0 prints the line it has (with the leg marked) and every rank
     leaves: a hung collective cannot be cancelled from Python."""
@@ -397,7 +428,11 @@ def main():
     ap.add_argument("--layers", type=int, default=24)
     ap.add_argument("--no-extra", action="store_true", help="only the headline line: no roofline / cpu / extra legs")
     ap.add_argument("--ring-seq", type=int, default=65536, help="N > 1: total sequence length of the ring-attention leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(self_launch(a.gpus))
@@ -453,8 +488,9 @@ def main():
             model(x)
         sync_all()
         t0 = time.perf_counter()
-        for _ in range(a.steps):
+        for _ in range(a.steps - 1):
             model(x)
+        y = model(x)  # only the last step's result outlives its step (--dump-outputs)
         sync_all()
         elapsed = time.perf_counter() - t0
     if N > 1:
@@ -485,6 +521,9 @@ def main():
         "model_tflops_per_gpu": flops_step / (ms_per_step * 1e-3) / 1e12,
         "mfma_roofline_frac_end_to_end": flops_step / (ms_per_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS,
     }
+    if a.dump_outputs and rank == 0:
+        res["dump_outputs"] = dump_outputs(a.dump_outputs, y)
+    del y
     dog = Watchdog(rank, res)
 
     if not a.no_extra and rank == 0 and N == 1:
