@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MIO_VERSION 105 /* 0.1.0 */
+#define MIO_VERSION 106 /* 0.1.0 */
 
 typedef enum { MIO_BF16 = 0, MIO_FP16 = 1 } mio_dtype_t;
 
@@ -39,7 +39,7 @@ typedef enum {
 typedef enum {
   MIO_MASK_NONE = 0,
   MIO_MASK_KEEP_U8 = 1, /* 1 = attend, 0 -> score := -1e9  (flash_attention_kernels.py:257-273) */
-  MIO_MASK_ADD_F32 = 2  /* score += mask                   (attention_kernels.py:1565-1566)      */
+  MIO_MASK_ADD_F32 = 2  /* score += max(mask, -1e30)       (attention_kernels.py:1565-1566)      */
 } mio_mask_kind_t;
 
 int mio_version(void);
@@ -60,13 +60,20 @@ const char* mio_last_error(void);
  * causal: key position (k_offset + j) > query position (q_offset + i) is excluded.  Without a
  *   user mask excluded blocks are skipped (exact: the reference's -1e9 fill underflows to 0).
  * mask: kind KEEP_U8 (uint8) or ADD_F32 (float), addressed with 4 element strides
- *   (b, h, q, k); 0 strides broadcast.
+ *   (b, h, q, k); 0 strides broadcast.  With a user mask, causal-excluded keys get the
+ *   reference's finite -1e9 fill (not -inf).  ADD_F32 entries below -1e30 (-inf,
+ *   finfo(float32).min, finfo(bfloat16).min) count as -1e30: a key at the floor gets weight 0
+ *   next to any key above it, and a row whose every key is at the floor -- also a row of
+ *   -inf only -- gets the uniform average of its keys, as a finite fill gives in
+ *   softmax(scores + mask); never NaN.  A keep-mask row with no kept key likewise averages
+ *   every key (-1e9 fill).
  * lse (nullable): [B,H,Sq] fp32, natural-log softmax denominator (m + log l of
  *   flash_attention_kernels.py:308-325).  Rows with no visible key get lse=-inf, o=0.
  * Ring carry (nullable o_acc): fp32 [B,Sq,H,D] contiguous running output state.
  *   carry_in != 0: start from (o_acc, lse) instead of empty;  o_acc != NULL: the normalised
  *   fp32 output is also written to o_acc (and lse must be non-NULL).  `o` may be NULL when
  *   o_acc is given (intermediate ring steps).
+ * Sk == 0: no key is read; o = 0, lse = -inf (carry_in: the carried state is written back).
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   const void* q;
@@ -97,8 +104,28 @@ typedef struct {
 } mio_fa3_fwd_params_t;
 
 int mio_fa3_fwd(const mio_fa3_fwd_params_t* p, void* stream);
-/* 1 iff a launch with these parameters (k_prescaled ignored) may set k_prescaled = 1: no user mask, Sq > 128, K / V rows
- * within 4 GiB of their (batch, head) base, head dim <= 96; with the (o_acc, lse) ring carry (o_acc and lse given,
+/* Which kernel mio_fa3_fwd launches for these parameters (nothing is launched or dereferenced; no device needed).
+ * Returns a mio_fa3_route_t, or < 0 (mio_last_error()) where mio_fa3_fwd would refuse the arguments.  The rule: without a
+ * user mask, Sq > 128, Sk > 0 and K / V rows within 4 GiB of their (batch, head) base, the pipelined kernels --
+ * fa3_fwd5_kernel at padded head dim 64 (plain output; k_prescaled also with the ring carry or a blocked output),
+ * fa3_fwd3_kernel otherwise (k_prescaled at padded head dim 96, plain output only); every other launch goes to
+ * fa3_fwd_kernel, templated on the mask kind. */
+typedef enum {
+  MIO_FA3_ROUTE_INVALID = -1,
+  MIO_FA3_ROUTE_EMPTY = 0,            /* Sq == 0: nothing to launch */
+  MIO_FA3_ROUTE_FWD5 = 1,             /* fa3_fwd5_kernel, plain K (scale applied in fp32) */
+  MIO_FA3_ROUTE_FWD5_KPRE = 2,        /* fa3_fwd5_kernel, k_prescaled */
+  MIO_FA3_ROUTE_FWD5_KPRE_CARRY = 3,  /* fa3_fwd5_kernel, k_prescaled, (o_acc, lse) carry */
+  MIO_FA3_ROUTE_FWD5_KPRE_OBLK = 4,   /* fa3_fwd5_kernel, k_prescaled, blocked output */
+  MIO_FA3_ROUTE_FWD3 = 5,             /* fa3_fwd3_kernel, plain K (with or without the carry) */
+  MIO_FA3_ROUTE_FWD3_KPRE = 6,        /* fa3_fwd3_kernel, k_prescaled */
+  MIO_FA3_ROUTE_FWD1 = 7,             /* fa3_fwd_kernel, no user mask (Sq <= 128, Sk == 0, K / V spans >= 4 GiB) */
+  MIO_FA3_ROUTE_FWD1_KEEP = 8,        /* fa3_fwd_kernel, KEEP_U8 mask */
+  MIO_FA3_ROUTE_FWD1_ADD = 9          /* fa3_fwd_kernel, ADD_F32 mask */
+} mio_fa3_route_t;
+int32_t mio_fa3_route(const mio_fa3_fwd_params_t* p);
+/* 1 iff a launch with these parameters (k_prescaled ignored) may set k_prescaled = 1: no user mask, Sq > 128, Sk > 0, K / V
+ * rows within 4 GiB of their (batch, head) base, head dim <= 96; with the (o_acc, lse) ring carry (o_acc and lse given,
  * carry_in 0 / 1, o optional) only at head dim <= 64. */
 int32_t mio_fa3_k_prescaled_ok(const mio_fa3_fwd_params_t* p);
 /* 1 iff a launch with these parameters (o_blocked ignored) may set o_blocked = 1: a k_prescaled launch without the ring

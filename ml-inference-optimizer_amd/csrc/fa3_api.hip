@@ -2,6 +2,7 @@
 #include <cmath>
 
 #include "fa3_fwd_kernel.h"
+#include "fa3_route.h"
 
 extern template int fa3_launch<__bf16, 64>(const FaDev&, int, int, hipStream_t);
 extern template int fa3_launch<__bf16, 96>(const FaDev&, int, int, hipStream_t);
@@ -15,7 +16,7 @@ static bool strides_ok(const int64_t s[3]) { return (s[0] % 8 == 0) && (s[1] % 8
 extern "C" int32_t mio_fa3_k_prescaled_ok(const mio_fa3_fwd_params_t* a) {
   if (a == nullptr) return 0;
   const bool span32 = (int64_t)a->Sk * a->k_stride[1] * 2 < (1ll << 32) && (int64_t)a->Sk * a->v_stride[1] * 2 < (1ll << 32);
-  if (!(a->D <= 96 && a->mask_kind == MIO_MASK_NONE && a->Sq > 128 && span32)) return 0;
+  if (!(a->D <= 96 && a->mask_kind == MIO_MASK_NONE && a->Sq > 128 && a->Sk > 0 && span32)) return 0;
   const bool plain = a->o != nullptr && a->o_acc == nullptr && !a->carry_in;
   // the (o_acc, lse) ring carry: fa3_fwd5_kernel only (head dim <= 64)
   return (plain || (a->D <= 64 && a->o_acc != nullptr && a->lse != nullptr)) ? 1 : 0;
@@ -27,7 +28,8 @@ extern "C" int32_t mio_fa3_o_blocked_ok(const mio_fa3_fwd_params_t* a) {
   return (plain && a->D <= 64 && ((int64_t)a->H * a->D) % 32 == 0) ? 1 : 0;
 }
 
-extern "C" int mio_fa3_fwd(const mio_fa3_fwd_params_t* a, void* stream) {
+// every argument check of mio_fa3_fwd (0 or -1 with the message set); mio_fa3_route runs the same checks
+static int fa3_validate(const mio_fa3_fwd_params_t* a) {
   MIO_CHECK(a != nullptr, "mio_fa3_fwd: null params");
   MIO_CHECK(a->q && a->k && a->v, "mio_fa3_fwd: q/k/v must be non-null");
   MIO_CHECK(a->o != nullptr || a->o_acc != nullptr, "mio_fa3_fwd: o or o_acc must be given");
@@ -46,6 +48,42 @@ extern "C" int mio_fa3_fwd(const mio_fa3_fwd_params_t* a, void* stream) {
             "mio_fa3_fwd: pointers must be 16-byte aligned");
   MIO_CHECK(!a->carry_in || (a->o_acc && a->lse), "mio_fa3_fwd: carry_in needs o_acc and lse");
   MIO_CHECK(a->o_acc == nullptr || a->lse != nullptr, "mio_fa3_fwd: o_acc needs lse");
+  if (a->Sq == 0) return 0;  // nothing is launched
+  MIO_CHECK(!a->o_blocked || (a->k_prescaled && mio_fa3_o_blocked_ok(a)), "mio_fa3_fwd: o_blocked is not supported for this launch "
+                                                                          "(needs k_prescaled and mio_fa3_o_blocked_ok != 0)");
+  MIO_CHECK(!a->k_prescaled || mio_fa3_k_prescaled_ok(a), "mio_fa3_fwd: k_prescaled is not supported for this launch "
+                                                          "(mio_fa3_k_prescaled_ok == 0)");
+  return 0;
+}
+
+static int dpad_of(int D) { return D <= 64 ? 64 : (D <= 96 ? 96 : 128); }
+
+static int route_of(const mio_fa3_fwd_params_t* a) {
+  Fa3RouteArgs r;
+  r.dpad = dpad_of(a->D);
+  r.mask_kind = a->mask_kind;
+  r.Sq = a->Sq;
+  r.Sk = a->Sk;
+  r.ks_s = a->k_stride[1];
+  r.vs_s = a->v_stride[1];
+  r.o = a->o != nullptr;
+  r.o_acc = a->o_acc != nullptr;
+  r.carry_in = a->carry_in != 0;
+  r.k_prescaled = a->k_prescaled != 0;
+  r.o_blocked = a->o_blocked != 0;
+  return fa3_pick_route(r);
+}
+
+extern "C" int32_t mio_fa3_route(const mio_fa3_fwd_params_t* a) {
+  if (fa3_validate(a) != 0) return MIO_FA3_ROUTE_INVALID;
+  if (a->Sq == 0) return MIO_FA3_ROUTE_EMPTY;
+  const int r = route_of(a);
+  if (r == MIO_FA3_ROUTE_INVALID) return mio_fail("fa3_fwd: k_prescaled launch outside the kernels that support it");
+  return r;
+}
+
+extern "C" int mio_fa3_fwd(const mio_fa3_fwd_params_t* a, void* stream) {
+  if (fa3_validate(a) != 0) return -1;
   if (a->Sq == 0) return 0;
 
   FaDev p;
@@ -63,19 +101,16 @@ extern "C" int mio_fa3_fwd(const mio_fa3_fwd_params_t* a, void* stream) {
   p.scale_log2e = a->softmax_scale * FA_LOG2E;
   p.k_prescaled = a->k_prescaled ? 1 : 0;
   p.o_blk = a->o_blocked ? 1 : 0;
-  MIO_CHECK(!p.o_blk || (p.k_prescaled && mio_fa3_o_blocked_ok(a)), "mio_fa3_fwd: o_blocked is not supported for this launch "
-                                                                     "(needs k_prescaled and mio_fa3_o_blocked_ok != 0)");
-  MIO_CHECK(!p.k_prescaled || mio_fa3_k_prescaled_ok(a), "mio_fa3_fwd: k_prescaled is not supported for this launch "
-                                                         "(mio_fa3_k_prescaled_ok == 0)");
 
   hipStream_t st = (hipStream_t)stream;
-  const int dpad = a->D <= 64 ? 64 : (a->D <= 96 ? 96 : 128);
+  const int dpad = dpad_of(a->D);
+  const int route = route_of(a);
   if (a->dtype == MIO_BF16) {
-    if (dpad == 64) return fa3_launch<__bf16, 64>(p, a->causal, a->mask_kind, st);
-    if (dpad == 96) return fa3_launch<__bf16, 96>(p, a->causal, a->mask_kind, st);
-    return fa3_launch<__bf16, 128>(p, a->causal, a->mask_kind, st);
+    if (dpad == 64) return fa3_launch<__bf16, 64>(p, a->causal, route, st);
+    if (dpad == 96) return fa3_launch<__bf16, 96>(p, a->causal, route, st);
+    return fa3_launch<__bf16, 128>(p, a->causal, route, st);
   }
-  if (dpad == 64) return fa3_launch<_Float16, 64>(p, a->causal, a->mask_kind, st);
-  if (dpad == 96) return fa3_launch<_Float16, 96>(p, a->causal, a->mask_kind, st);
-  return fa3_launch<_Float16, 128>(p, a->causal, a->mask_kind, st);
+  if (dpad == 64) return fa3_launch<_Float16, 64>(p, a->causal, route, st);
+  if (dpad == 96) return fa3_launch<_Float16, 96>(p, a->causal, route, st);
+  return fa3_launch<_Float16, 128>(p, a->causal, route, st);
 }

@@ -6,6 +6,7 @@
 
 #include "fa3_fwd2_kernel.h"
 #include "fa3_fwd3_kernel.h"
+#include "fa3_route.h"
 #if FA_D == 64
 #include "fa3_fwd4_kernel.h"
 #include "fa3_fwd5_kernel.h"
@@ -223,74 +224,80 @@ static int fa_impl() {  // MIO_FA_IMPL=1 / 2 / 3 force one structure for A/B run
 static constexpr int fa_impl() { return 0; }
 #endif
 
+#ifdef MIO_DIAG
+// A/B overrides of the diagnostic build on top of the route (MIO_FA_IMPL=1 / 2 / 3 / 4, mio_dbg_set(1, 3 | 4)).  Returns 1
+// with *rc set when it took the launch.
+static int diag_launch(int route, const FaDev& p, int causal, hipStream_t stream, int* rc) {
+  const int impl = fa_impl(), dbg1 = mio_dbg_get(1);
+#if FA_D == 64
+  if ((route == MIO_FA3_ROUTE_FWD5_KPRE || route == MIO_FA3_ROUTE_FWD5_KPRE_OBLK) && (dbg1 == 3 || dbg1 == 4)) {
+    if (dbg1 == 4) *rc = causal ? launch_four<true, true>(p, stream) : launch_four<false, true>(p, stream);
+    else *rc = causal ? launch_three<true, true>(p, stream) : launch_three<false, true>(p, stream);
+    return 1;
+  }
+  if (route == MIO_FA3_ROUTE_FWD5 && (impl != 0 || dbg1 != 0)) {
+    if (impl == 4 || dbg1 == 4) *rc = causal ? launch_four<true>(p, stream) : launch_four<false>(p, stream);
+    else if (impl == 3 || impl == 0) *rc = causal ? launch_three<true>(p, stream) : launch_three<false>(p, stream);
+    else if (impl == 2) *rc = causal ? launch_two<true>(p, stream) : launch_two<false>(p, stream);
+    else *rc = causal ? launch_one<true, 0>(p, stream) : launch_one<false, 0>(p, stream);
+    return 1;
+  }
+#endif
+  if ((route == MIO_FA3_ROUTE_FWD3 || route == MIO_FA3_ROUTE_FWD1) && impl == 2 && p.Sq > 128) {
+    *rc = causal ? launch_two<true>(p, stream) : launch_two<false>(p, stream);
+    return 1;
+  }
+  if (route == MIO_FA3_ROUTE_FWD3 && impl != 0 && impl != 3) {
+    *rc = causal ? launch_one<true, 0>(p, stream) : launch_one<false, 0>(p, stream);
+    return 1;
+  }
+  return 0;
+}
+#endif
+
 template <>
-int fa3_launch<FaT, FA_D>(const FaDev& p, int causal, int mask_kind, hipStream_t stream) {
-  // Structure choice (measured on MI355X, B8 S4096, random data; MIO_FA_IMPL=1 / 2 / 3 forces one for A/B runs):
-  //   no user mask, Sq > 128: the software-pipelined kernel at every head dim --
+int fa3_launch<FaT, FA_D>(const FaDev& p, int causal, int route, hipStream_t stream) {
+  // The route is fa3_pick_route's (fa3_route.h), the rule mio_fa3_route reports.  Measured on MI355X, B8 S4096, random data:
+  //   no user mask, Sq > 128: the software-pipelined kernels --
   //     D64 causal 0.359 ms (766 TFLOP/s) vs 0.442 two-waves-per-SIMD / 0.52 sequential one-wave; non-causal 0.626 vs 0.79;
   //     D128 causal 0.284 ms (967 TFLOP/s) vs 0.361 sequential one-wave; D80 non-causal 0.828 ms (830) vs 1.158;
-  //   user masks and Sq <= 128: the two-waves-per-SIMD kernel.
-  // (the pipelined kernel addresses K / V tiles with 32-bit byte offsets from the (batch, head) base)
-  const bool span32 = (int64_t)p.Sk * p.ks_s * 2 < (1ll << 32) && (int64_t)p.Sk * p.vs_s * 2 < (1ll << 32);
-#if FA_D == 64
-  // head dim <= 64, causal, plain output: the two-waves-per-SIMD kernel (0.325 vs 0.336 ms at B8 S4096 H16 interleaved on
-  // one box; non-causal it is 1 % behind fa3_fwd3 and stays there).  Diagnostic build: MIO_FA_IMPL=3 / mio_dbg_set(1, 3)
-  // keep fa3_fwd3, = 4 force fa3_fwd4 for non-causal launches too.
+  //   head dim <= 64, plain output: fa3_fwd5 (16x16x32 MFMA tiles).  Same box, interleaved, B8 S4096 H16 bf16, k_prescaled:
+  //     causal 0.3047 ms vs 0.3305 fa3_fwd4 KPRE / 0.3401 fa3_fwd3 KPRE / 0.3570 fa3_fwd3; non-causal 0.5494 vs 0.6162 /
+  //     0.5862 / 0.6273; with plain K the same structure applies the scale in fp32 on the way into exp2;
+  //   k_prescaled at head dim 65 .. 96: fa3_fwd3's KPRE form (not at 128: the two reference tuples (32 VGPRs) do not fit
+  //     beside the score / P / fragment registers there -- hipcc parks values in accumulator registers the kernel owns,
+  //     tools/check_agpr.py catches it);
+  //   user masks, Sq <= 128, Sk == 0 and K / V spans of 4 GiB or more: the sequential one-wave kernel.
+#ifdef MIO_DIAG
   {
-    const bool plain = mask_kind == MIO_MASK_NONE && p.Sq > 128 && span32 && p.o != nullptr && p.o_acc == nullptr && !p.carry_in;
-    // k_prescaled (mio_fa3_fwd has checked mio_fa3_k_prescaled_ok), head dim <= 64: fa3_fwd5 (16x16x32 MFMA tiles).  Same
-    // box, interleaved, B8 S4096 H16 bf16: causal 0.3047 ms vs 0.3305 fa3_fwd4 KPRE / 0.3401 fa3_fwd3 KPRE / 0.3570 fa3_fwd3;
-    // non-causal 0.5494 vs 0.6162 / 0.5862 / 0.6273.  Diagnostic build: mio_dbg_set(1, 3 | 4) select the other KPRE forms.
-    // ... and its ring form: (o_acc, lse) carried in / written back, bf16 output optional
-    if (p.k_prescaled && !plain && mask_kind == MIO_MASK_NONE && p.Sq > 128 && span32 && p.o_acc != nullptr)
-      return causal ? launch_five<true, true>(p, stream) : launch_five<false, true>(p, stream);
-    if (p.k_prescaled && plain) {
-      int which = 5;
-#ifdef MIO_DIAG
-      if (mio_dbg_get(1) == 3 || mio_dbg_get(1) == 4) which = mio_dbg_get(1);
-#endif
-      if (which == 5 && p.o_blk) return causal ? launch_five<true, false, true>(p, stream) : launch_five<false, false, true>(p, stream);
-      if (which == 5) return causal ? launch_five<true>(p, stream) : launch_five<false>(p, stream);
-#ifdef MIO_DIAG
-      if (which == 4) return causal ? launch_four<true, true>(p, stream) : launch_four<false, true>(p, stream);
-#endif
-    }
-    // plain K (the functional entry point and every module that does not own the K projection's epilogue): the same
-    // structure with the scale applied in fp32 on the way into exp2
-    if (!p.k_prescaled && plain && fa_impl() == 0
-#ifdef MIO_DIAG
-        && mio_dbg_get(1) == 0
-#endif
-    )
-      return causal ? launch_five<true, false, false, false>(p, stream) : launch_five<false, false, false, false>(p, stream);
-#ifdef MIO_DIAG
-    bool four = false;
-    if (plain && (fa_impl() == 4 || mio_dbg_get(1) == 4)) four = true;
-    if (four) return causal ? launch_four<true>(p, stream) : launch_four<false>(p, stream);
-#endif
+    int rc = 0;
+    if (diag_launch(route, p, causal, stream, &rc)) return rc;
   }
 #endif
-  if (p.k_prescaled) {  // head dim 65 .. 96 (and the diagnostic A/B at 64): fa3_fwd3's KPRE form.  Not at 128: the two
-                         // reference tuples (32 VGPRs) do not fit beside the score / P / fragment registers there -- hipcc
-                         // parks values in accumulator registers the kernel owns (tools/check_agpr.py catches it)
+  switch (route) {
+#if FA_D == 64
+    case MIO_FA3_ROUTE_FWD5:
+      return causal ? launch_five<true, false, false, false>(p, stream) : launch_five<false, false, false, false>(p, stream);
+    case MIO_FA3_ROUTE_FWD5_KPRE:
+      return causal ? launch_five<true>(p, stream) : launch_five<false>(p, stream);
+    case MIO_FA3_ROUTE_FWD5_KPRE_CARRY:
+      return causal ? launch_five<true, true>(p, stream) : launch_five<false, true>(p, stream);
+    case MIO_FA3_ROUTE_FWD5_KPRE_OBLK:
+      return causal ? launch_five<true, false, true>(p, stream) : launch_five<false, false, true>(p, stream);
+#endif
 #if FA_D < 128
-    if (mask_kind == MIO_MASK_NONE && p.Sq > 128 && span32 && p.o != nullptr && p.o_acc == nullptr && !p.carry_in)
+    case MIO_FA3_ROUTE_FWD3_KPRE:
       return causal ? launch_three<true, true>(p, stream) : launch_three<false, true>(p, stream);
 #endif
-    return mio_fail("fa3_fwd: k_prescaled launch outside the kernels that support it");
+    case MIO_FA3_ROUTE_FWD3:
+      return causal ? launch_three<true>(p, stream) : launch_three<false>(p, stream);
+    case MIO_FA3_ROUTE_FWD1:
+      return causal ? launch_one<true, 0>(p, stream) : launch_one<false, 0>(p, stream);
+    case MIO_FA3_ROUTE_FWD1_KEEP:
+      return causal ? launch_one<true, 1>(p, stream) : launch_one<false, 1>(p, stream);
+    case MIO_FA3_ROUTE_FWD1_ADD:
+      return causal ? launch_one<true, 2>(p, stream) : launch_one<false, 2>(p, stream);
+    default:
+      return mio_fail("fa3_fwd: k_prescaled launch outside the kernels that support it");
   }
-  if ((fa_impl() == 3 || fa_impl() == 0) && mask_kind == MIO_MASK_NONE && p.Sq > 128 && span32)
-    return causal ? launch_three<true>(p, stream) : launch_three<false>(p, stream);
-#ifdef MIO_DIAG
-  if (mask_kind == MIO_MASK_NONE && fa_impl() == 2 && p.Sq > 128)
-    return causal ? launch_two<true>(p, stream) : launch_two<false>(p, stream);
-#endif
-  if (causal) {
-    if (mask_kind == MIO_MASK_NONE) return launch_one<true, 0>(p, stream);
-    if (mask_kind == MIO_MASK_KEEP_U8) return launch_one<true, 1>(p, stream);
-    return launch_one<true, 2>(p, stream);
-  }
-  if (mask_kind == MIO_MASK_NONE) return launch_one<false, 0>(p, stream);
-  if (mask_kind == MIO_MASK_KEEP_U8) return launch_one<false, 1>(p, stream);
-  return launch_one<false, 2>(p, stream);
 }

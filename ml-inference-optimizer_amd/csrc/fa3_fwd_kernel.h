@@ -51,6 +51,7 @@ constexpr float FA_LOG2E = 1.4426950408889634f;
 constexpr float FA_LN2 = 0.6931471805599453f;
 constexpr float FA_NEG_FILL_LOG2 = -1.0e9f * FA_LOG2E;
 constexpr float FA_RESCALE_THR = 6.0f;  // exp2 domain: P <= 64 between rescales
+constexpr float FA_ADD_MASK_FLOOR = -1.0e30f;  // MIO_MASK_ADD_F32 entries below count as this (finite after * log2(e))
 
 template <int D>
 struct FaSmem {
@@ -184,10 +185,21 @@ __global__ __launch_bounds__(256) void fa3_fwd_kernel(const FaDev p) {
       int kv = kv0 + row;
       kv = kv < p.Sk ? kv : p.Sk - 1;
       const int cc = c < d_chunks ? c : d_chunks - 1;
-      // asm loads: invisible to hipcc's s_waitcnt insertion, which would otherwise drain them (vmcnt(0)) at the
-      // first basic-block join of the tile body, i.e. before the first MFMA.  Retired by fa_wait_loads() below.
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(kreg[j]) : "v"(kbase + (int64_t)kv * p.ks_s + 8 * cc) : "memory");
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(vreg[j]) : "v"(vbase + (int64_t)kv * p.vs_s + 8 * cc) : "memory");
+      const T* kp = kbase + (int64_t)kv * p.ks_s + 8 * cc;
+      const T* vp = vbase + (int64_t)kv * p.vs_s + 8 * cc;
+      if constexpr (D == 128) {
+        // compiler-visible loads: at D = 128 the tile body needs more than 256 VGPRs and hipcc parks live registers in
+        // AGPRs -- an asm load's destination included, copied while the load is still in flight (it cannot know), so
+        // the tile was staged from stale registers.  hipcc waits for its own loads before any such copy.
+        kreg[j] = *(const u32x4_t*)kp;
+        vreg[j] = *(const u32x4_t*)vp;
+      } else {
+        // asm loads: invisible to hipcc's s_waitcnt insertion, which would otherwise drain them (vmcnt(0)) at the
+        // first basic-block join of the tile body, i.e. before the first MFMA.  Retired by wait_loads() below.  Sound
+        // only while hipcc never moves the destination registers before that wait (tests/test_host_logic.py checks it).
+        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(kreg[j]) : "v"(kp) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(vreg[j]) : "v"(vp) : "memory");
+      }
     }
   };
   auto wait_loads = [&]() {  // every staged register is an in/out operand: no consumer can be scheduled above this
@@ -295,7 +307,9 @@ __global__ __launch_bounds__(256) void fa3_fwd_kernel(const FaDev p) {
                 const uint8_t keep = ((const uint8_t*)p.mask)[mrow + (int64_t)kv * p.ms_k];
                 if (!keep) tv = FA_NEG_FILL_LOG2;
               } else if (MASK == MIO_MASK_ADD_F32) {
-                tv += ((const float*)p.mask)[mrow + (int64_t)kv * p.ms_k] * FA_LOG2E;
+                // floored at -1e30 (include/mio_hip.h): -inf / finfo(fp32).min scaled by log2(e) would make every score
+                // of a fully masked tile -inf, and exp2(-inf - -inf) below NaN
+                tv += fmaxf(((const float*)p.mask)[mrow + (int64_t)kv * p.ms_k], FA_ADD_MASK_FLOOR) * FA_LOG2E;
               }
             } else {
               tv = -INFINITY;
@@ -323,7 +337,8 @@ __global__ __launch_bounds__(256) void fa3_fwd_kernel(const FaDev p) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) oacc[dt][i] *= alpha;
     } else {
-      m_sub = m_i;  // finite here: a row with m_i == -inf always takes the branch above
+      // m_i == -inf here only if no row of the wave has a finite score yet (every score -inf): 0 keeps exp2 at 0, not NaN
+      m_sub = (m_i == -INFINITY) ? 0.f : m_i;
     }
     // P = exp2(score - m), row sum, and the P^T fragments: k-step s (16 keys) = registers 8(s&1)..+7 of tile s>>1
     float rs0 = 0.f, rs1 = 0.f;
@@ -406,6 +421,7 @@ __global__ __launch_bounds__(256) void fa3_fwd_kernel(const FaDev p) {
   }
 }
 
-// Host launcher for one (dtype, padded D); defined per translation unit (fa3_fwd_inst.hip).
+// Host launcher for one (dtype, padded D); defined per translation unit (fa3_fwd_inst.hip).  route: fa3_pick_route's
+// mio_fa3_route_t for the launch (fa3_route.h).
 template <typename T, int D>
-int fa3_launch(const FaDev& p, int causal, int mask_kind, hipStream_t stream);
+int fa3_launch(const FaDev& p, int causal, int route, hipStream_t stream);

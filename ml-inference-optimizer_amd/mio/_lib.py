@@ -22,6 +22,19 @@ LIB_PATH = os.path.join(_HERE, "libmio_hip_dbg.so" if os.environ.get("MIO_LIB_DB
 MIO_BF16, MIO_FP16 = 0, 1
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_RELU, ACT_SILU, ACT_SWIGLU = range(6)
 MASK_NONE, MASK_KEEP_U8, MASK_ADD_F32 = range(3)
+# mio_fa3_route_t: the kernel mio_fa3_fwd launches (include/mio_hip.h)
+FA3_ROUTES = {
+    0: "empty",
+    1: "fwd5",
+    2: "fwd5_kpre",
+    3: "fwd5_kpre_carry",
+    4: "fwd5_kpre_oblk",
+    5: "fwd3",
+    6: "fwd3_kpre",
+    7: "fwd1",
+    8: "fwd1_keep",
+    9: "fwd1_add",
+}
 
 # every symbol include/mio_hip.h declares
 EXPORTS = (
@@ -30,6 +43,7 @@ EXPORTS = (
     "mio_fa3_fwd",
     "mio_fa3_k_prescaled_ok",
     "mio_fa3_o_blocked_ok",
+    "mio_fa3_route",
     "mio_attn_merge",
     "mio_gemm_bias_act",
     "mio_fused_mlp_workspace_bytes",
@@ -111,6 +125,8 @@ def _load() -> C.CDLL:
     lib.mio_fa3_k_prescaled_ok.restype = i32
     lib.mio_fa3_o_blocked_ok.argtypes = [C.POINTER(FaParams)]
     lib.mio_fa3_o_blocked_ok.restype = i32
+    lib.mio_fa3_route.argtypes = [C.POINTER(FaParams)]
+    lib.mio_fa3_route.restype = i32
     lib.mio_attn_merge.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mio_attn_merge.restype = i32
     lib.mio_gemm_bias_act.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]

@@ -126,6 +126,33 @@ def fa3_fwd(
     Returns out (same layout as q) or (out, lse) if return_lse.
     """
     _need_cuda(q, k, v)
+    p, out, lse, _keep = _fa3_params(q, k, v, layout=layout, causal=causal, softmax_scale=softmax_scale,
+                                     keep_mask=keep_mask, additive_mask=additive_mask, return_lse=return_lse, out=out,
+                                     o_acc=o_acc, lse=lse, carry_in=carry_in, write_out=write_out, q_offset=q_offset,
+                                     k_offset=k_offset, k_prescaled=k_prescaled, out_blocked=out_blocked)
+    check(lib.mio_fa3_fwd(C.byref(p), _stream()))
+    if return_lse:
+        return out, lse
+    return out
+
+
+def fa3_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, **kwargs) -> str:
+    """The kernel fa3_fwd(q, k, v, **kwargs) would launch (mio_fa3_route; a name of _lib.FA3_ROUTES), without launching.
+    Takes fa3_fwd's arguments; tensors may live on any device (only their shapes, strides and addresses are read).
+    Arguments fa3_fwd refuses raise the same ValueError / RuntimeError."""
+    p, _out, _lse, _keep = _fa3_params(q, k, v, **kwargs)
+    r = lib.mio_fa3_route(C.byref(p))
+    if r < 0:
+        raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
+    return _lib.FA3_ROUTES[r]
+
+
+def _fa3_params(q, k, v, *, layout="bshd", causal=False, softmax_scale=None, keep_mask=None, additive_mask=None,
+                return_lse=False, out=None, o_acc=None, lse=None, carry_in=False, write_out=True, q_offset=0, k_offset=0,
+                k_prescaled=False, out_blocked=False):
+    """fa3_fwd's argument checks and mio_fa3_fwd_params_t; returns (params, out, lse, keep): out / lse are allocated here
+    when not given, and keep holds every other tensor the params point into (q / k / v / mask as converted here), which
+    must stay alive until the launch is queued."""
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError(f"Expected 4D tensors for q, k, v but got shapes: q={q.shape}, k={k.shape}, v={v.shape}")
     if layout not in ("bshd", "bhsd"):
@@ -183,7 +210,8 @@ def fa3_fwd(
     elif additive_mask is not None:
         mask, kind = additive_mask.to(torch.float32), _lib.MASK_ADD_F32
     if mask is not None:
-        _need_cuda(mask)
+        if q.is_cuda:
+            _need_cuda(mask)
         if mask.dim() != 4:
             raise ValueError(f"Unsupported mask shape: {tuple(mask.shape)}")
         for dim, full in zip(mask.shape, (B, H, Sq, Sk)):
@@ -202,6 +230,10 @@ def fa3_fwd(
         _st(p.o_stride, out)
     p.q, p.k, p.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
     p.o, p.lse, p.o_acc, p.mask = _ptr(out), _ptr(lse), _ptr(o_acc), _ptr(mask)
+    if Sk == 0:  # torch gives empty tensors a null address; no key (or mask entry) is read then (include/mio_hip.h)
+        p.k = p.v = p.q
+        if mask is not None:
+            p.mask = p.q
     p.B, p.Sq, p.Sk, p.H, p.Hkv, p.D = B, Sq, Sk, H, Hkv, D
     p.dtype, p.causal, p.mask_kind, p.carry_in = dt, int(bool(causal)), kind, int(bool(carry_in))
     p.q_offset, p.k_offset, p.softmax_scale = int(q_offset), int(k_offset), scale
@@ -215,17 +247,14 @@ def fa3_fwd(
             raise ValueError("out_blocked is only supported for k_prescaled launches without carry, head_dim <= 64, "
                              "(H * D) % 32 == 0")
         p.o_blocked = 1
-    check(lib.mio_fa3_fwd(C.byref(p), _stream()))
-    if return_lse:
-        return out, lse
-    return out
+    return p, out, lse, (q, k, v, mask)
 
 
 def fa3_k_prescaled_ok(B: int, Sq: int, Sk: int, H: int, D: int, k_row_stride: int, v_row_stride: int,
                        carry: bool = False) -> bool:
     """True iff fa3_fwd(..., k_prescaled=True) is available for a launch of this geometry without a mask (carry: with the
     (o_acc, lse) ring carry)."""
-    return (D <= (64 if carry else 96) and Sq > 128 and Sk * k_row_stride * 2 < (1 << 32)
+    return (D <= (64 if carry else 96) and Sq > 128 and Sk > 0 and Sk * k_row_stride * 2 < (1 << 32)
             and Sk * v_row_stride * 2 < (1 << 32))
 
 

@@ -11,14 +11,17 @@ import torch.nn as nn
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_cabi_exports_match_header():
+def test_cabi_exports_and_version_match_header():
+    """Every symbol include/mio_hip.h declares is exported and bound, and the library reports the header's ABI version:
+    106, the version that added mio_fa3_route."""
     from mio import _lib
     hdr = open(os.path.join(ROOT, "include", "mio_hip.h")).read()
     declared = set(re.findall(r"\b(mio_[a-z0-9_]+)\s*\(", hdr))
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     for name in declared:
         assert hasattr(_lib.lib, name), name
-    assert _lib.lib.mio_version() == 105
+    assert int(re.search(r"#define MIO_VERSION (\d+)", hdr).group(1)) == 106
+    assert _lib.lib.mio_version() == 106
     assert _lib.lib.mio_last_error() is not None  # callable without a GPU
 
 
@@ -55,6 +58,126 @@ def test_layernorm_fold_eligibility_without_gpu():
     assert b"mio_ln_stats_reduce" in lib.mio_last_error()               # 16 slots handed over unreduced
     assert lib.mio_ln_fold_weight(one, 16384, one, None, None, one, one, 1024, 16384, 0, None) != 0 and b"8192" in lib.mio_last_error()
     assert lib.mio_ln_stats_reduce(one, 16, one, 5, M, None) != 0
+
+
+def _fa_params(*, D=64, Sq=300, Sk=300, H=4, Hkv=4, dtype=0, causal=0, mask_kind=0, row=None, vrow=None, o=True,
+               o_acc=False, carry_in=0, kpre=0, oblk=0):
+    """mio_fa3_fwd_params_t for a [B,S,H,D] launch with fake 16-byte aligned pointers (nothing is dereferenced)."""
+    from mio import _lib
+    p = _lib.FaParams()
+    one = 16
+    p.q = p.k = p.v = one
+    p.o = one if o else None
+    p.o_acc = one if o_acc else None
+    p.lse = one if (o_acc or carry_in) else None
+    p.mask = one if mask_kind else None
+    krow = H * D if row is None else row
+    for st, r in ((p.q_stride, H * D), (p.k_stride, krow), (p.v_stride, krow if vrow is None else vrow), (p.o_stride, H * D)):
+        st[0], st[1], st[2] = max(Sq, Sk, 1) * r, r, D
+    p.B, p.Sq, p.Sk, p.H, p.Hkv, p.D = 1, Sq, Sk, H, Hkv, D
+    p.dtype, p.causal, p.mask_kind, p.carry_in = dtype, causal, mask_kind, carry_in
+    p.softmax_scale, p.k_prescaled, p.o_blocked = 0.125, kpre, oblk
+    return p
+
+
+# (geometry, route): every boundary of fa3_pick_route (csrc/fa3_route.h); None = refused (mio_fa3_route < 0)
+_ROUTE_TABLE = [
+    (dict(), "fwd5"),
+    (dict(Sq=129), "fwd5"),
+    (dict(Sq=128), "fwd1"),
+    (dict(Sq=1), "fwd1"),
+    (dict(Sq=0), "empty"),
+    (dict(D=8), "fwd5"),
+    (dict(D=72), "fwd3"),
+    (dict(D=96), "fwd3"),
+    (dict(D=104), "fwd3"),
+    (dict(D=128), "fwd3"),
+    (dict(D=128, Sq=128), "fwd1"),
+    (dict(Sk=0), "fwd1"),
+    (dict(Sk=1), "fwd5"),
+    (dict(D=96, Sk=0), "fwd1"),
+    # 32-bit K / V span: Sk * row_stride * 2 just under / at 2^32 (either operand)
+    (dict(Sk=(1 << 15) - 1, row=1 << 16), "fwd5"),
+    (dict(Sk=1 << 15, row=1 << 16), "fwd1"),
+    (dict(Sk=(1 << 15) - 1, row=256, vrow=1 << 16), "fwd5"),
+    (dict(Sk=1 << 15, row=256, vrow=1 << 16), "fwd1"),
+    (dict(D=96, Sk=1 << 15, row=1 << 16), "fwd1"),
+    (dict(D=96, Sk=(1 << 15) - 1, row=1 << 16), "fwd3"),
+    # k_prescaled
+    (dict(kpre=1), "fwd5_kpre"),
+    (dict(kpre=1, D=72), "fwd3_kpre"),
+    (dict(kpre=1, D=96), "fwd3_kpre"),
+    (dict(kpre=1, D=104), None),
+    (dict(kpre=1, Sq=128), None),
+    (dict(kpre=1, Sk=0), None),
+    (dict(kpre=1, Sk=1 << 15, row=1 << 16), None),
+    (dict(kpre=1, mask_kind=1), None),
+    (dict(kpre=1, oblk=1), "fwd5_kpre_oblk"),
+    (dict(kpre=1, oblk=1, D=40, H=4), "fwd5_kpre_oblk"),
+    (dict(kpre=1, oblk=1, D=8, H=3), None),            # (H * D) % 32 != 0
+    (dict(kpre=1, oblk=1, D=72), None),
+    (dict(oblk=1), None),                              # o_blocked needs k_prescaled
+    # the (o_acc, lse) carry
+    (dict(o_acc=True), "fwd3"),
+    (dict(o_acc=True, o=False), "fwd3"),
+    (dict(o_acc=True, carry_in=1, kpre=1), "fwd5_kpre_carry"),
+    (dict(o_acc=True, o=False, kpre=1), "fwd5_kpre_carry"),
+    (dict(o_acc=True, kpre=1, D=72), None),
+    (dict(o_acc=True, kpre=1, oblk=1), None),
+    (dict(o_acc=True, D=128, carry_in=1), "fwd3"),
+    (dict(o_acc=True, Sq=128, carry_in=1), "fwd1"),
+    (dict(o_acc=True, kpre=1, Sq=128), None),
+    # user masks: the sequential kernel at every Sq and head dim
+    (dict(mask_kind=1), "fwd1_keep"),
+    (dict(mask_kind=2), "fwd1_add"),
+    (dict(mask_kind=1, Sq=64, D=128), "fwd1_keep"),
+    (dict(mask_kind=2, Sq=64, D=96), "fwd1_add"),
+    (dict(mask_kind=2, o_acc=True, carry_in=1), "fwd1_add"),
+    (dict(mask_kind=2, Sk=0), "fwd1_add"),
+    (dict(mask_kind=3), None),
+]
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+@pytest.mark.parametrize("causal", [0, 1])
+def test_fa3_route_table_without_gpu(dtype, causal):
+    """mio_fa3_route reports the kernel mio_fa3_fwd launches, through the same rule (fa3_pick_route); every route of
+    mio_fa3_route_t appears in the table."""
+    import ctypes as C
+    from mio import _lib
+    seen = set()
+    for geom, want in _ROUTE_TABLE:
+        r = _lib.lib.mio_fa3_route(C.byref(_fa_params(dtype=dtype, causal=causal, **geom)))
+        got = _lib.FA3_ROUTES.get(r) if r >= 0 else None
+        assert got == want, f"{geom}: route {got} ({r}), expected {want}"
+        if r < 0:
+            assert _lib.lib.mio_last_error()
+        seen.add(got)
+    assert seen == set(_lib.FA3_ROUTES.values()) | {None}
+    # invalid arguments are refused like mio_fa3_fwd refuses them
+    p = _fa_params(D=60)
+    assert _lib.lib.mio_fa3_route(C.byref(p)) < 0 and b"head_dim" in _lib.lib.mio_last_error()
+    assert _lib.lib.mio_fa3_route(None) < 0
+
+
+def test_fa3_route_python_wrapper_without_gpu():
+    """ops.fa3_route builds fa3_fwd's parameters (strides of views, mask conversion, k_prescaled / out_blocked checks)
+    from tensors on any device and launches nothing."""
+    from mio import ops
+    q = torch.zeros(1, 300, 2, 64, dtype=torch.bfloat16)
+    assert ops.fa3_route(q, q, q) == "fwd5"
+    assert ops.fa3_route(q, q, q, k_prescaled=True, out_blocked=True) == "fwd5_kpre_oblk"
+    assert ops.fa3_route(q[:, :128], q, q, causal=True) == "fwd1"
+    assert ops.fa3_route(q, q, q, additive_mask=torch.zeros(1, 1, 300, 300)) == "fwd1_add"
+    assert ops.fa3_route(q, q, q, keep_mask=torch.ones(1, 1, 1, 300, dtype=torch.bool)) == "fwd1_keep"
+    acc, lse = torch.zeros(1, 300, 2, 64), torch.zeros(1, 2, 300)
+    assert ops.fa3_route(q, q, q, o_acc=acc, lse=lse, write_out=False, k_prescaled=True) == "fwd5_kpre_carry"
+    qkv = torch.zeros(1, 300, 3 * 2 * 96, dtype=torch.float16)  # strided views of one fused projection
+    qv, kv, vv = (qkv[..., i * 192:(i + 1) * 192].view(1, 300, 2, 96) for i in range(3))
+    assert ops.fa3_route(qv, kv, vv) == "fwd3" and ops.fa3_route(qv, kv, vv, k_prescaled=True) == "fwd3_kpre"
+    assert ops.fa3_route(q, q[:, :0], q[:, :0]) == "fwd1"
+    with pytest.raises(ValueError):
+        ops.fa3_route(q, q, q, additive_mask=torch.zeros(1, 1, 300, 300), k_prescaled=True)
 
 
 def test_cabi_argument_errors_without_gpu():
@@ -351,6 +474,61 @@ def test_fwd4_two_waves_per_simd_fits_without_spills(tmp_path):
             assert re.search(r"\.private_segment_fixed_size:\s+0\b", blk), blk
             assert re.search(r"\.vgpr_spill_count:\s+0\b", blk), blk
             assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= 256, blk
+
+
+def _inflight_load_reads(body):
+    """Instructions that read (or copy) a register a global_load_dwordx4 is still filling, in a straight-line listing:
+    vector-memory operations retire in order, and s_waitcnt vmcnt(N) leaves only the N most recent outstanding.  hipcc
+    waits for its own loads before their first use; a hit is a load it cannot see (inline asm) used too early."""
+    def regs(tok):
+        m = re.fullmatch(r"v\[(\d+):(\d+)\]", tok)
+        if m:
+            return set(range(int(m.group(1)), int(m.group(2)) + 1))
+        m = re.fullmatch(r"v(\d+)", tok)
+        return {int(m.group(1))} if m else set()
+    queue, hits = [], []  # destination registers of the outstanding vector-memory operations, oldest first
+    for line in body:
+        s = line.strip()
+        if not s or s.startswith((".", ";")):
+            continue
+        ops = [t.rstrip(",") for t in s.split()[1:]]
+        m = re.search(r"vmcnt\((\d+)\)", s) if s.startswith("s_waitcnt") else None
+        if m:
+            n = int(m.group(1))
+            queue = queue[len(queue) - n:] if n else []
+            continue
+        live = set().union(*queue) if queue else set()
+        if live and any(regs(t) & live for t in ops[1:]):
+            hits.append(s)
+        if re.match(r"(global|buffer|flat)_(load|store|atomic)", s):
+            queue.append(regs(ops[0]) if "_load" in s.split()[0] else set())
+    return hits
+
+
+@pytest.mark.parametrize("type_id", [0, 1])
+@pytest.mark.parametrize("D", [64, 96, 128])
+def test_fwd1_staging_registers_not_moved_in_flight(tmp_path, type_id, D):
+    """fa3_fwd_kernel stages K / V tiles with asm loads the compiler cannot see (no s_waitcnt of its own); they are sound
+    only while hipcc leaves their destination registers alone until wait_loads().  At D = 128 hipcc copied them into AGPRs
+    right after issue (every output of the Sq <= 128 launches wrong); that path now uses compiler-visible loads."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    csrc = os.path.join(ROOT, "ml-inference-optimizer_amd", "csrc")
+    isa = tmp_path / "fa.s"
+    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I../../include", "-I.", "-Wno-unused-value",
+                    "-Wno-inline-asm", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", f"-DFA_TYPE_ID={type_id}",
+                    f"-DFA_D={D}", "-S", "--cuda-device-only", "fa3_fwd_inst.hip", "-o", str(isa)], cwd=csrc, check=True,
+                   capture_output=True)
+    text = isa.read_text().splitlines()
+    starts = [i for i, l in enumerate(text) if re.match(r"^_Z14fa3_fwd_kernel\w+:", l)]
+    assert len(starts) == 6  # causal x mask kind
+    for a in starts:
+        b = next(i for i in range(a, len(text)) if "s_endpgm" in text[i])
+        hits = _inflight_load_reads(text[a:b + 1])
+        assert not hits, text[a] + "\n" + "\n".join(hits[:8])
 
 
 @pytest.mark.parametrize("D", [64, 96, 128])
