@@ -132,6 +132,55 @@ int32_t mio_fa3_k_prescaled_ok(const mio_fa3_fwd_params_t* p);
  * carry at head dim <= 64 with (H * D) % 32 == 0. */
 int32_t mio_fa3_o_blocked_ok(const mio_fa3_fwd_params_t* p);
 
+/* ------------------------------------------------------------------------------------------
+ * Packed variable-length attention forward (prefill of sequences of different lengths; the
+ * form of flash-attn's flash_attn_varlen_func), on the pipelined kernels of routes FWD5 / FWD3.
+ *
+ * q [total_q,H,D], k/v [total_k,Hkv,D], o [total_q,H,D] given by (token, head) strides (d
+ * stride is 1; k/v may be strided views into a fused QKV buffer).  Sequence b (0 <= b < B)
+ * owns rows cu_seqlens_q[b] .. cu_seqlens_q[b+1]-1 of q / o and rows cu_seqlens_k[b] ..
+ * cu_seqlens_k[b+1]-1 of k / v; cu_seqlens_* are int32 DEVICE arrays of B+1 entries, never
+ * read on the host.  The kernel clamps every sequence into [0,total_q) / [0,total_k) and to
+ * max_seqlen_q / max_seqlen_k: offsets that disagree with the totals give wrong numbers, never
+ * an access outside the buffers.  Rows of o outside every sequence are not written.
+ * causal: bottom-right aligned per sequence -- query i of sequence b sees key j iff
+ *   j <= i + Lk_b - Lq_b (a dense mio_fa3_fwd call on that sequence with q_offset = Lk_b - Lq_b,
+ *   k_offset = 0; chunked prefill against a contiguous prefix).  Rows with no visible key, and
+ *   every row of a sequence with Lk_b == 0, get o = 0, lse = -inf.
+ * lse (nullable): fp32 [H,total_q], natural-log softmax denominator.
+ * H % Hkv == 0; D in [8,128], D % 8 == 0 (padded head dim 64: fa3_fwd5_kernel, 96 / 128:
+ * fa3_fwd3_kernel); plain K, softmax_scale applied in fp32.  K / V rows of one sequence must span
+ * less than 4 GiB: max_seqlen_k * k/v token stride * 2 < 2^32.  No host sync; graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void* q;
+  const void* k;
+  const void* v;
+  void* o;
+  float* lse;                  /* nullable, fp32 [H, total_q] */
+  const int32_t* cu_seqlens_q; /* device, B+1 entries */
+  const int32_t* cu_seqlens_k; /* device, B+1 entries */
+  int64_t q_stride[2];         /* token, head */
+  int64_t k_stride[2];
+  int64_t v_stride[2];
+  int64_t o_stride[2];
+  int32_t B, total_q, total_k, max_seqlen_q, max_seqlen_k, H, Hkv, D;
+  int32_t dtype;       /* mio_dtype_t */
+  int32_t causal;      /* 0/1 */
+  float softmax_scale; /* > 0 */
+} mio_fa3_varlen_params_t;
+
+int mio_fa3_fwd_varlen(const mio_fa3_varlen_params_t* p, void* stream);
+/* Which kernel mio_fa3_fwd_varlen launches (nothing is launched or dereferenced; no device needed).  Returns a
+ * mio_fa3_varlen_route_t, or < 0 (mio_last_error()) where mio_fa3_fwd_varlen would refuse the arguments. */
+typedef enum {
+  MIO_FA3_VARLEN_ROUTE_INVALID = -1,
+  MIO_FA3_VARLEN_ROUTE_EMPTY = 0, /* B == 0 or total_q == 0: nothing to launch */
+  MIO_FA3_VARLEN_ROUTE_FWD5 = 1,  /* fa3_fwd5_kernel's varlen form (padded head dim 64), plain K */
+  MIO_FA3_VARLEN_ROUTE_FWD3 = 2   /* fa3_fwd3_kernel's varlen form (padded head dim 96 / 128), plain K */
+} mio_fa3_varlen_route_t;
+int32_t mio_fa3_varlen_route(const mio_fa3_varlen_params_t* p);
+
 /* Merge two normalised partial attention states over disjoint key sets (ring / split-KV):
  * o = w_a*o_a + w_b*o_b, lse = logaddexp(lse_a, lse_b), w_x = exp(lse_x - lse).
  * Restates the (alpha, beta) update of kernels/triton/attention_kernels.py:1573-1585.

@@ -3,6 +3,7 @@
 
 #include "fa3_fwd_kernel.h"
 #include "fa3_route.h"
+#include "fa3_varlen.h"
 
 extern template int fa3_launch<__bf16, 64>(const FaDev&, int, int, hipStream_t);
 extern template int fa3_launch<__bf16, 96>(const FaDev&, int, int, hipStream_t);
@@ -10,6 +11,12 @@ extern template int fa3_launch<__bf16, 128>(const FaDev&, int, int, hipStream_t)
 extern template int fa3_launch<_Float16, 64>(const FaDev&, int, int, hipStream_t);
 extern template int fa3_launch<_Float16, 96>(const FaDev&, int, int, hipStream_t);
 extern template int fa3_launch<_Float16, 128>(const FaDev&, int, int, hipStream_t);
+extern template int fa3_varlen_launch<__bf16, 64>(const FaDev&, const FaVarlen&, int, hipStream_t);
+extern template int fa3_varlen_launch<__bf16, 96>(const FaDev&, const FaVarlen&, int, hipStream_t);
+extern template int fa3_varlen_launch<__bf16, 128>(const FaDev&, const FaVarlen&, int, hipStream_t);
+extern template int fa3_varlen_launch<_Float16, 64>(const FaDev&, const FaVarlen&, int, hipStream_t);
+extern template int fa3_varlen_launch<_Float16, 96>(const FaDev&, const FaVarlen&, int, hipStream_t);
+extern template int fa3_varlen_launch<_Float16, 128>(const FaDev&, const FaVarlen&, int, hipStream_t);
 
 static bool strides_ok(const int64_t s[3]) { return (s[0] % 8 == 0) && (s[1] % 8 == 0) && (s[2] % 8 == 0); }
 
@@ -113,4 +120,70 @@ extern "C" int mio_fa3_fwd(const mio_fa3_fwd_params_t* a, void* stream) {
   if (dpad == 64) return fa3_launch<_Float16, 64>(p, a->causal, route, st);
   if (dpad == 96) return fa3_launch<_Float16, 96>(p, a->causal, route, st);
   return fa3_launch<_Float16, 128>(p, a->causal, route, st);
+}
+
+// ---- packed variable-length form (mio_fa3_fwd_varlen)
+
+// every argument check of mio_fa3_fwd_varlen (0 or -1 with the message set); mio_fa3_varlen_route runs the same checks.
+// Nothing here reads device memory: the sequence bounds are clamped in the kernel (fa3_varlen.h).
+static int fa3_varlen_validate(const mio_fa3_varlen_params_t* a) {
+  MIO_CHECK(a != nullptr, "mio_fa3_fwd_varlen: null params");
+  MIO_CHECK(a->B >= 0 && a->total_q >= 0 && a->total_k >= 0 && a->max_seqlen_q >= 0 && a->max_seqlen_k >= 0 && a->H > 0 &&
+                a->Hkv > 0,
+            "mio_fa3_fwd_varlen: bad sizes");
+  MIO_CHECK(a->H % a->Hkv == 0, "mio_fa3_fwd_varlen: H must be a multiple of Hkv");
+  MIO_CHECK(a->D >= 8 && a->D <= 128 && a->D % 8 == 0, "mio_fa3_fwd_varlen: head_dim must be a multiple of 8 in [8,128]");
+  MIO_CHECK(a->dtype == MIO_BF16 || a->dtype == MIO_FP16, "mio_fa3_fwd_varlen: dtype must be bf16 or fp16");
+  MIO_CHECK(a->softmax_scale > 0.f && std::isfinite(a->softmax_scale), "mio_fa3_fwd_varlen: softmax_scale must be > 0");
+  MIO_CHECK(a->q && a->k && a->v && a->o, "mio_fa3_fwd_varlen: q/k/v/o must be non-null");
+  MIO_CHECK(a->B == 0 || (a->cu_seqlens_q != nullptr && a->cu_seqlens_k != nullptr),
+            "mio_fa3_fwd_varlen: cu_seqlens_q / cu_seqlens_k must be non-null");
+  for (const int64_t* s : {a->q_stride, a->k_stride, a->v_stride, a->o_stride})
+    MIO_CHECK(s[0] >= 0 && s[1] >= 0 && s[0] % 8 == 0 && s[1] % 8 == 0,
+              "mio_fa3_fwd_varlen: strides must be non-negative multiples of 8 elements (16-byte rows)");
+  MIO_CHECK(mio_aligned16(a->q) && mio_aligned16(a->k) && mio_aligned16(a->v) && mio_aligned16(a->o),
+            "mio_fa3_fwd_varlen: pointers must be 16-byte aligned");
+  MIO_CHECK(a->total_q == 0 || a->max_seqlen_q >= 1, "mio_fa3_fwd_varlen: max_seqlen_q must be >= 1 when total_q > 0");
+  MIO_CHECK(a->total_k == 0 || a->max_seqlen_k >= 1, "mio_fa3_fwd_varlen: max_seqlen_k must be >= 1 when total_k > 0");
+  // the pipelined kernels address K / V tiles with 32-bit byte offsets from the sequence's first row
+  MIO_CHECK((int64_t)a->max_seqlen_k * a->k_stride[0] * 2 < (1ll << 32) &&
+                (int64_t)a->max_seqlen_k * a->v_stride[0] * 2 < (1ll << 32),
+            "mio_fa3_fwd_varlen: K / V rows of one sequence must span less than 4 GiB (max_seqlen_k * token stride * 2)");
+  return 0;
+}
+
+extern "C" int32_t mio_fa3_varlen_route(const mio_fa3_varlen_params_t* a) {
+  if (fa3_varlen_validate(a) != 0) return MIO_FA3_VARLEN_ROUTE_INVALID;
+  if (a->B == 0 || a->total_q == 0) return MIO_FA3_VARLEN_ROUTE_EMPTY;
+  return dpad_of(a->D) == 64 ? MIO_FA3_VARLEN_ROUTE_FWD5 : MIO_FA3_VARLEN_ROUTE_FWD3;
+}
+
+extern "C" int mio_fa3_fwd_varlen(const mio_fa3_varlen_params_t* a, void* stream) {
+  if (fa3_varlen_validate(a) != 0) return -1;
+  if (a->B == 0 || a->total_q == 0) return 0;
+
+  FaDev p = {};
+  p.q = a->q; p.k = a->k; p.v = a->v; p.o = a->o; p.lse = a->lse; p.o_acc = nullptr; p.mask = nullptr;
+  p.qs_s = a->q_stride[0]; p.qs_h = a->q_stride[1];
+  p.ks_s = a->k_stride[0]; p.ks_h = a->k_stride[1];
+  p.vs_s = a->v_stride[0]; p.vs_h = a->v_stride[1];
+  p.os_s = a->o_stride[0]; p.os_h = a->o_stride[1];
+  p.B = a->B; p.H = a->H; p.Hkv = a->Hkv; p.D = a->D;
+  p.xcd_remap = ((a->B * a->H) % 8 == 0) ? 1 : 0;
+  p.scale_log2e = a->softmax_scale * FA_LOG2E;
+  FaVarlen vl;
+  vl.cu_q = a->cu_seqlens_q; vl.cu_k = a->cu_seqlens_k;
+  vl.total_q = a->total_q; vl.total_k = a->total_k;
+  vl.max_q = a->max_seqlen_q; vl.max_k = a->max_seqlen_k;
+
+  hipStream_t st = (hipStream_t)stream;
+  const int dpad = dpad_of(a->D);
+  if (a->dtype == MIO_BF16) {
+    if (dpad == 64) return fa3_varlen_launch<__bf16, 64>(p, vl, a->causal, st);
+    if (dpad == 96) return fa3_varlen_launch<__bf16, 96>(p, vl, a->causal, st);
+    return fa3_varlen_launch<__bf16, 128>(p, vl, a->causal, st);
+  }
+  if (dpad == 64) return fa3_varlen_launch<_Float16, 64>(p, vl, a->causal, st);
+  if (dpad == 96) return fa3_varlen_launch<_Float16, 96>(p, vl, a->causal, st);
+  return fa3_varlen_launch<_Float16, 128>(p, vl, a->causal, st);
 }

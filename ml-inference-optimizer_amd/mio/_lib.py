@@ -35,6 +35,12 @@ FA3_ROUTES = {
     8: "fwd1_keep",
     9: "fwd1_add",
 }
+# mio_fa3_varlen_route_t: the kernel mio_fa3_fwd_varlen launches (a table of its own: FA3_ROUTES is mio_fa3_fwd's)
+FA3_VARLEN_ROUTES = {
+    0: "empty",
+    1: "fwd5",
+    2: "fwd3",
+}
 
 # every symbol include/mio_hip.h declares
 EXPORTS = (
@@ -44,6 +50,8 @@ EXPORTS = (
     "mio_fa3_k_prescaled_ok",
     "mio_fa3_o_blocked_ok",
     "mio_fa3_route",
+    "mio_fa3_fwd_varlen",
+    "mio_fa3_varlen_route",
     "mio_attn_merge",
     "mio_gemm_bias_act",
     "mio_fused_mlp_workspace_bytes",
@@ -106,6 +114,35 @@ class FaParams(C.Structure):
     ]
 
 
+class FaVarlenParams(C.Structure):
+    """mio_fa3_varlen_params_t"""
+
+    _fields_ = [
+        ("q", C.c_void_p),
+        ("k", C.c_void_p),
+        ("v", C.c_void_p),
+        ("o", C.c_void_p),
+        ("lse", C.c_void_p),
+        ("cu_seqlens_q", C.c_void_p),
+        ("cu_seqlens_k", C.c_void_p),
+        ("q_stride", C.c_int64 * 2),
+        ("k_stride", C.c_int64 * 2),
+        ("v_stride", C.c_int64 * 2),
+        ("o_stride", C.c_int64 * 2),
+        ("B", C.c_int32),
+        ("total_q", C.c_int32),
+        ("total_k", C.c_int32),
+        ("max_seqlen_q", C.c_int32),
+        ("max_seqlen_k", C.c_int32),
+        ("H", C.c_int32),
+        ("Hkv", C.c_int32),
+        ("D", C.c_int32),
+        ("dtype", C.c_int32),
+        ("causal", C.c_int32),
+        ("softmax_scale", C.c_float),
+    ]
+
+
 def _load() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -127,6 +164,10 @@ def _load() -> C.CDLL:
     lib.mio_fa3_o_blocked_ok.restype = i32
     lib.mio_fa3_route.argtypes = [C.POINTER(FaParams)]
     lib.mio_fa3_route.restype = i32
+    lib.mio_fa3_fwd_varlen.argtypes = [C.POINTER(FaVarlenParams), vp]
+    lib.mio_fa3_fwd_varlen.restype = i32
+    lib.mio_fa3_varlen_route.argtypes = [C.POINTER(FaVarlenParams)]
+    lib.mio_fa3_varlen_route.restype = i32
     lib.mio_attn_merge.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mio_attn_merge.restype = i32
     lib.mio_gemm_bias_act.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]

@@ -3,6 +3,8 @@
 These mirror the reference's functional launch wrappers (same positional/keyword signatures,
 same exception types for the same conditions):
   flash_attention           <- triton_flash_attention        (kernels/triton/flash_attention_kernels.py:1150-1358)
+  flash_attention_varlen       packed variable-length attention (cu_seqlens; not in the reference), with unpad_input /
+                               pad_input for padded batches under a [B, S] keep-mask
   ring_attention_forward    <- triton_ring_attention_forward (kernels/triton/attention_kernels.py:909-1005)
   fused_mlp                 <- triton_fused_mlp              (kernels/triton/mlp_kernels.py:648-756)
   layernorm                 <- triton_layernorm              (kernels/triton/layernorm_kernels.py:191-276)
@@ -303,6 +305,121 @@ def flash_attention(
     if mask is not None:
         keep = _canon_mask4(mask.to(q.device))
     return fa3_fwd(q, k, v, layout="bshd", causal=causal, softmax_scale=softmax_scale, keep_mask=keep)
+
+
+def _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=False, softmax_scale=None,
+                   return_lse=False, out=None):
+    """flash_attention_varlen's argument checks and mio_fa3_varlen_params_t; returns (params, out, lse, keep) as
+    _fa3_params does.  Reads no device memory."""
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise ValueError(f"Expected 3D tensors [tokens, heads, head_dim] for q, k, v but got shapes: q={q.shape}, "
+                         f"k={k.shape}, v={v.shape}")
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError("q, k, v must have the same dtype")
+    dt = _dtype_id(q)
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 1 or not cu.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 1-D int32 tensor of B+1 offsets")
+        if cu.device != q.device:
+            raise ValueError(f"{name} must be on the device of q")
+    if cu_seqlens_k.numel() != cu_seqlens_q.numel():
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must have the same length (B+1)")
+    q, k, v = _rows16(q), _rows16(k), _rows16(v)
+    Tq, H, D = q.shape
+    Tk, Hkv = k.shape[0], k.shape[1]
+    if v.shape != k.shape or k.shape[2] != D:
+        raise ValueError(f"incompatible q/k/v shapes: q={q.shape}, k={k.shape}, v={v.shape}")
+    if H % Hkv != 0:
+        raise ValueError(f"num_heads {H} must be a multiple of num_kv_heads {Hkv}")
+    if D % 8 != 0 or D > 128:
+        raise ValueError(f"head_dim must be a multiple of 8 and <= 128, got {D}")
+    scale = (1.0 / math.sqrt(D)) if softmax_scale is None else float(softmax_scale)
+    if not (scale > 0.0):
+        raise ValueError("softmax_scale must be positive")
+    if out is None:
+        out = torch.empty_like(q, memory_format=torch.contiguous_format)
+    elif out.shape != q.shape or out.dtype != q.dtype or out.stride(-1) != 1:
+        raise ValueError("out must match q in shape/dtype with a contiguous last dim")
+    lse = torch.empty(H, Tq, dtype=torch.float32, device=q.device) if return_lse else None
+
+    p = _lib.FaVarlenParams()
+    for dst, t in ((p.q_stride, q), (p.k_stride, k), (p.v_stride, v), (p.o_stride, out)):
+        dst[0], dst[1] = t.stride(0), t.stride(1)
+    p.q, p.k, p.v, p.o, p.lse = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse)
+    # torch gives empty tensors a null address; nothing is read or written through them then (include/mio_hip.h)
+    for f in ("q", "k", "v", "o"):
+        if not getattr(p, f):
+            setattr(p, f, cu_seqlens_q.data_ptr())
+    p.cu_seqlens_q, p.cu_seqlens_k = cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr()
+    p.B, p.total_q, p.total_k = cu_seqlens_q.numel() - 1, Tq, Tk
+    p.max_seqlen_q, p.max_seqlen_k = int(max_seqlen_q), int(max_seqlen_k)
+    p.H, p.Hkv, p.D = H, Hkv, D
+    p.dtype, p.causal, p.softmax_scale = dt, int(bool(causal)), scale
+    return p, out, lse, (q, k, v, cu_seqlens_q, cu_seqlens_k)
+
+
+def flash_attention_varlen(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    cu_seqlens_k: torch.Tensor,
+    max_seqlen_q: int,
+    max_seqlen_k: int,
+    causal: bool = False,
+    softmax_scale: Optional[float] = None,
+    return_lse: bool = False,
+    out: Optional[torch.Tensor] = None,
+):
+    """Packed variable-length attention forward (the form of flash-attn's flash_attn_varlen_func), mio_fa3_fwd_varlen.
+
+    q [total_q, H, D], k / v [total_k, Hkv, D] (bf16 / fp16; k / v may be strided views into a fused QKV buffer);
+    cu_seqlens_q / cu_seqlens_k: int32 [B+1] offsets on q's device -- sequence b is rows cu_seqlens_q[b] .. [b+1]-1 of q
+    and cu_seqlens_k[b] .. [b+1]-1 of k / v.  max_seqlen_q / max_seqlen_k bound every sequence's length (longer ones are
+    cut there).  causal is bottom-right aligned per sequence: query i sees key j iff j <= i + Lk - Lq.  Rows with no
+    visible key get 0 (lse -inf).  Returns out [total_q, H, D] or (out, lse fp32 [H, total_q]) if return_lse.
+    Queued on the current stream with no host sync (graph-capturable): the offsets are never read on the host.
+    """
+    _need_cuda(q, k, v, cu_seqlens_q, cu_seqlens_k)
+    p, out, lse, _keep = _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal,
+                                        softmax_scale=softmax_scale, return_lse=return_lse, out=out)
+    check(lib.mio_fa3_fwd_varlen(C.byref(p), _stream()))
+    if return_lse:
+        return out, lse
+    return out
+
+
+def fa3_varlen_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor,
+                     cu_seqlens_k: torch.Tensor, max_seqlen_q: int, max_seqlen_k: int, **kwargs) -> str:
+    """The kernel flash_attention_varlen(...) would launch (mio_fa3_varlen_route): "empty", "fwd5" or "fwd3", without
+    launching.  Tensors may live on any device; arguments flash_attention_varlen refuses raise the same errors."""
+    p, _out, _lse, _keep = _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, **kwargs)
+    r = lib.mio_fa3_varlen_route(C.byref(p))
+    if r < 0:
+        raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
+    return _lib.FA3_VARLEN_ROUTES[r]
+
+
+def unpad_input(x: torch.Tensor, keep: torch.Tensor):
+    """x [B, S, ...] and a keep-mask [B, S] (nonzero = a real token, any left / right padding) -> (x_packed [total, ...],
+    indices [total] int64 into the flattened [B*S], cu_seqlens int32 [B+1], max_seqlen int).  Syncs with the host (the
+    packed size and max_seqlen are read back)."""
+    if keep.dim() != 2 or x.shape[:2] != keep.shape:
+        raise ValueError(f"keep must be [B, S] matching x's first two dims, got x={tuple(x.shape)}, keep={tuple(keep.shape)}")
+    keep = keep.to(x.device) != 0
+    lens = keep.sum(dim=1, dtype=torch.int32)
+    indices = torch.nonzero(keep.flatten(), as_tuple=False).flatten()
+    cu = torch.zeros(keep.shape[0] + 1, dtype=torch.int32, device=x.device)
+    cu[1:] = torch.cumsum(lens, dim=0, dtype=torch.int32)
+    max_seqlen = int(lens.max().item()) if lens.numel() else 0
+    return x.reshape(-1, *x.shape[2:])[indices], indices, cu, max_seqlen
+
+
+def pad_input(x_packed: torch.Tensor, indices: torch.Tensor, B: int, S: int) -> torch.Tensor:
+    """Inverse of unpad_input: [total, ...] -> [B, S, ...] with zeros at the padding positions."""
+    out = torch.zeros(B * S, *x_packed.shape[1:], dtype=x_packed.dtype, device=x_packed.device)
+    out[indices] = x_packed
+    return out.view(B, S, *x_packed.shape[1:])
 
 
 def ring_attention_forward(
