@@ -1,8 +1,8 @@
 // FlashAttention forward, third structure (head dim 64, no user mask): software-pipelined across KV tiles.
 //
-// fa3_fwd2_kernel (one wave per SIMD, 64 query rows per wave) runs each tile as QK^T -> softmax -> PV in sequence, so
-// the matrix core idles during the softmax and the vector ALU idles during the MFMAs: 2375 cycles per tile against
-// 1024 of MFMA work (tools/fa_ab.py, rocprofv3 SQ counters).  Here, per wave and tile t:
+// The retired sequential structure (fa3_fwd2_kernel: one wave per SIMD, 64 query rows per wave) ran each tile as
+// QK^T -> softmax -> PV in sequence, so the matrix core idled during the softmax and the vector ALU during the MFMAs:
+// 2375 cycles per tile against 1024 of MFMA work (rocprofv3 SQ counters).  Here, per wave and tile t:
 //   phase 1   S(t+1) = K(t+1) . Q^T                  16 MFMAs   ||   P(t) = exp2(S(t))                  64 v_exp + 32 v_cvt_pk
 //   phase 2   O^T += V(t)^T . P(t)^T, L += ones . P(t)^T  24 MFMAs   ||   S(t+1) := S(t+1)*c - ref, row max    64 v_fma + 32 v_max3, DMA issue
 // with S double-buffered in VGPRs.  What makes the two sides balance:
@@ -21,8 +21,96 @@
 // ring (K(t+1) and V(t) are read while tiles t+2 and t+3 are in flight: a tile has two iterations to land), one
 // barrier per tile.
 #pragma once
-#include "fa3_fwd2_kernel.h"
 #include "fa3_varlen.h"
+
+// Accumulator tile k (16 registers) = a[16k : 16k+15], asm-owned: every statement names its registers as clobbers, so
+// hipcc allocates them in the kernel descriptor and never touches them itself.
+template <typename T, int K>
+struct Fa2Acc;
+#define FA2_CL(B) "a" #B
+#define FA2_DEF(K, R0, R1, R2, R3, R4, R5, R6, R7, R8, R9, R10, R11, R12, R13, R14, R15)                          \
+  template <>                                                                                                     \
+  struct Fa2Acc<__bf16, K> {                                                                                      \
+    static __device__ __forceinline__ void mfma(bf16x8_t a, bf16x8_t b) {                                         \
+      asm volatile("v_mfma_f32_32x32x16_bf16 a[" #R0 ":" #R15 "], %0, %1, a[" #R0 ":" #R15 "]"                     \
+                   :                                                                                              \
+                   : "v"(a), "v"(b)                                                                               \
+                   : FA2_CL(R0), FA2_CL(R1), FA2_CL(R2), FA2_CL(R3), FA2_CL(R4), FA2_CL(R5), FA2_CL(R6), FA2_CL(R7), \
+                     FA2_CL(R8), FA2_CL(R9), FA2_CL(R10), FA2_CL(R11), FA2_CL(R12), FA2_CL(R13), FA2_CL(R14),      \
+                     FA2_CL(R15));                                                                                \
+    }                                                                                                             \
+  };                                                                                                              \
+  template <>                                                                                                     \
+  struct Fa2Acc<_Float16, K> {                                                                                    \
+    static __device__ __forceinline__ void mfma(f16x8_t a, f16x8_t b) {                                           \
+      asm volatile("v_mfma_f32_32x32x16_f16 a[" #R0 ":" #R15 "], %0, %1, a[" #R0 ":" #R15 "]"                      \
+                   :                                                                                              \
+                   : "v"(a), "v"(b)                                                                               \
+                   : FA2_CL(R0), FA2_CL(R1), FA2_CL(R2), FA2_CL(R3), FA2_CL(R4), FA2_CL(R5), FA2_CL(R6), FA2_CL(R7), \
+                     FA2_CL(R8), FA2_CL(R9), FA2_CL(R10), FA2_CL(R11), FA2_CL(R12), FA2_CL(R13), FA2_CL(R14),      \
+                     FA2_CL(R15));                                                                                \
+    }                                                                                                             \
+  };                                                                                                              \
+  template <>                                                                                                     \
+  struct Fa2AccIO<K> {                                                                                            \
+    template <int G>                                                                                              \
+    static __device__ __forceinline__ f32x4_t read4() { /* registers 4G..4G+3 of the tile */                      \
+      float x0, x1, x2, x3;                                                                                       \
+      if constexpr (G == 0)                                                                                       \
+        asm volatile("v_accvgpr_read_b32 %0, a" #R0 "\n\tv_accvgpr_read_b32 %1, a" #R1 "\n\tv_accvgpr_read_b32 %2, a" #R2 \
+                     "\n\tv_accvgpr_read_b32 %3, a" #R3 : "=v"(x0), "=v"(x1), "=v"(x2), "=v"(x3));                    \
+      else if constexpr (G == 1)                                                                                  \
+        asm volatile("v_accvgpr_read_b32 %0, a" #R4 "\n\tv_accvgpr_read_b32 %1, a" #R5 "\n\tv_accvgpr_read_b32 %2, a" #R6 \
+                     "\n\tv_accvgpr_read_b32 %3, a" #R7 : "=v"(x0), "=v"(x1), "=v"(x2), "=v"(x3));                    \
+      else if constexpr (G == 2)                                                                                  \
+        asm volatile("v_accvgpr_read_b32 %0, a" #R8 "\n\tv_accvgpr_read_b32 %1, a" #R9 "\n\tv_accvgpr_read_b32 %2, a" #R10 \
+                     "\n\tv_accvgpr_read_b32 %3, a" #R11 : "=v"(x0), "=v"(x1), "=v"(x2), "=v"(x3));                   \
+      else                                                                                                        \
+        asm volatile("v_accvgpr_read_b32 %0, a" #R12 "\n\tv_accvgpr_read_b32 %1, a" #R13 "\n\tv_accvgpr_read_b32 %2, a" #R14 \
+                     "\n\tv_accvgpr_read_b32 %3, a" #R15 : "=v"(x0), "=v"(x1), "=v"(x2), "=v"(x3));                   \
+      return (f32x4_t){x0, x1, x2, x3};                                                                           \
+    }                                                                                                             \
+    template <int G>                                                                                              \
+    static __device__ __forceinline__ void write4(f32x4_t v) {                                                    \
+      if constexpr (G == 0)                                                                                       \
+        asm volatile("v_accvgpr_write_b32 a" #R0 ", %0\n\tv_accvgpr_write_b32 a" #R1 ", %1\n\tv_accvgpr_write_b32 a" #R2 \
+                     ", %2\n\tv_accvgpr_write_b32 a" #R3 ", %3" : : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3])          \
+                     : FA2_CL(R0), FA2_CL(R1), FA2_CL(R2), FA2_CL(R3));                                            \
+      else if constexpr (G == 1)                                                                                  \
+        asm volatile("v_accvgpr_write_b32 a" #R4 ", %0\n\tv_accvgpr_write_b32 a" #R5 ", %1\n\tv_accvgpr_write_b32 a" #R6 \
+                     ", %2\n\tv_accvgpr_write_b32 a" #R7 ", %3" : : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3])          \
+                     : FA2_CL(R4), FA2_CL(R5), FA2_CL(R6), FA2_CL(R7));                                            \
+      else if constexpr (G == 2)                                                                                  \
+        asm volatile("v_accvgpr_write_b32 a" #R8 ", %0\n\tv_accvgpr_write_b32 a" #R9 ", %1\n\tv_accvgpr_write_b32 a" #R10 \
+                     ", %2\n\tv_accvgpr_write_b32 a" #R11 ", %3" : : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3])         \
+                     : FA2_CL(R8), FA2_CL(R9), FA2_CL(R10), FA2_CL(R11));                                          \
+      else                                                                                                        \
+        asm volatile("v_accvgpr_write_b32 a" #R12 ", %0\n\tv_accvgpr_write_b32 a" #R13 ", %1\n\tv_accvgpr_write_b32 a" #R14 \
+                     ", %2\n\tv_accvgpr_write_b32 a" #R15 ", %3" : : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3])         \
+                     : FA2_CL(R12), FA2_CL(R13), FA2_CL(R14), FA2_CL(R15));                                        \
+    }                                                                                                             \
+  };
+template <int K>
+struct Fa2AccIO;
+FA2_DEF(0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
+FA2_DEF(1, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31)
+FA2_DEF(2, 32, 33, 34, 35, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47)
+FA2_DEF(3, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63)
+FA2_DEF(4, 64, 65, 66, 67, 68, 69, 70, 71, 72, 73, 74, 75, 76, 77, 78, 79)
+FA2_DEF(5, 80, 81, 82, 83, 84, 85, 86, 87, 88, 89, 90, 91, 92, 93, 94, 95)
+FA2_DEF(6, 96, 97, 98, 99, 100, 101, 102, 103, 104, 105, 106, 107, 108, 109, 110, 111)
+FA2_DEF(7, 112, 113, 114, 115, 116, 117, 118, 119, 120, 121, 122, 123, 124, 125, 126, 127)
+// tiles 8..15 = a[128:255]: the top of the accumulator file, where fa3_fwd3 keeps its accumulators, out of
+// the way of the low registers the allocator hands out first
+FA2_DEF(8, 128, 129, 130, 131, 132, 133, 134, 135, 136, 137, 138, 139, 140, 141, 142, 143)
+FA2_DEF(9, 144, 145, 146, 147, 148, 149, 150, 151, 152, 153, 154, 155, 156, 157, 158, 159)
+FA2_DEF(10, 160, 161, 162, 163, 164, 165, 166, 167, 168, 169, 170, 171, 172, 173, 174, 175)
+FA2_DEF(11, 176, 177, 178, 179, 180, 181, 182, 183, 184, 185, 186, 187, 188, 189, 190, 191)
+FA2_DEF(12, 192, 193, 194, 195, 196, 197, 198, 199, 200, 201, 202, 203, 204, 205, 206, 207)
+FA2_DEF(13, 208, 209, 210, 211, 212, 213, 214, 215, 216, 217, 218, 219, 220, 221, 222, 223)
+FA2_DEF(14, 224, 225, 226, 227, 228, 229, 230, 231, 232, 233, 234, 235, 236, 237, 238, 239)
+FA2_DEF(15, 240, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250, 251, 252, 253, 254, 255)
+#undef FA2_DEF
 
 constexpr int FA3_BM = 256;     // query rows per workgroup (4 waves x 64)
 constexpr int FA3_STAGES = 4;
@@ -129,7 +217,7 @@ struct Fa3P2Role {
 // ABL (diagnostic build only, timing-only ablations with WRONG results -- what each piece of the tile loop costs):
 //   1 no scale-and-subtract / max in phase 2     2 no exp (P = converted S)     4 no row-sum MFMAs
 //   8 no DMA issue in the tile loop              16 no reference test / update  32 no edge masks
-// KPRE (FaDev::k_prescaled; see fa3_fwd4_kernel.h): K carries softmax_scale * log2(e).  The reference enters the QK^T
+// KPRE (FaDev::k_prescaled; see fa3_fwd5_kernel.h): K carries softmax_scale * log2(e).  The reference enters the QK^T
 // product as the C operand of its first k-step (one 16-register tuple per query sub-tile), phase 2 loses its 64 v_fma +
 // 32 v_max3 per tile, and the rescale test is bit 14 of the OR of the tile's packed P words (move_ref below).
 template <typename T>

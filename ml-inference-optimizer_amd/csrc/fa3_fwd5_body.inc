@@ -38,7 +38,7 @@
   {
     const int q = c16 >> 2, p2 = c16 & 3, x = ((4 * g + q) >> 1) & 3;
 #pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) v_rd[dt] = FA4_KBYTES + (4 * g + q) * 128 + ((dt ^ x) * 32) + 8 * p2;
+    for (int dt = 0; dt < NDT; ++dt) v_rd[dt] = FA5_KBYTES + (4 * g + q) * 128 + ((dt ^ x) * 32) + 8 * p2;
   }
 
   const T* kbase = (const T*)p.k + b * p.ks_b + kvh * p.ks_h;
@@ -67,11 +67,11 @@
 
   const int npass = (CAUSAL && (p.nqblk - 1 - qi) != qi) ? 2 : 1;
   auto pass_q0 = [&](int pass) __attribute__((always_inline)) -> int {
-    return (CAUSAL ? (pass == 0 ? p.nqblk - 1 - qi : qi) : qi) * FA4_BM;
+    return (CAUSAL ? (pass == 0 ? p.nqblk - 1 - qi : qi) : qi) * FA5_BM;
   };
   auto pass_tiles = [&](int pass) __attribute__((always_inline)) -> int {  // KV tiles the workgroup walks in that pass
     if (!CAUSAL) return (p.Sk + FA_BN - 1) / FA_BN;
-    int kmax = pass_q0(pass) + FA4_BM - 1 + p.q_offset - p.k_offset;
+    int kmax = pass_q0(pass) + FA5_BM - 1 + p.q_offset - p.k_offset;
     if (kmax > p.Sk - 1) kmax = p.Sk - 1;
     return kmax < 0 ? 0 : kmax / FA_BN + 1;
   };
@@ -157,12 +157,12 @@
       const char* kb = (const char*)kbase + ko;
       const char* vb = (const char*)vbase + vo;
       const bool lastt = (tile == last_tile);
-      const uint32_t lds = (uint32_t)(size_t)((MIO_LDS char*)(smem + (tile_ & (FA5_STAGES - 1)) * FA4_STAGE)) + 1024 * wave;
+      const uint32_t lds = (uint32_t)(size_t)((MIO_LDS char*)(smem + (tile_ & (FA5_STAGES - 1)) * FA5_STAGE)) + 1024 * wave;
       const int ok_ = lastt ? offkl : offk, ov_ = lastt ? offvl : offv;
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(lds), "v"(ok_), "s"(kb) : "memory", "m0");
       asm volatile("s_add_i32 m0, %0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3"
                    :
-                   : "s"(lds), "n"(FA4_KBYTES), "v"(ov_), "s"(vb)
+                   : "s"(lds), "n"(FA5_KBYTES), "v"(ov_), "s"(vb)
                    : "memory", "m0", "scc");
     };
 
@@ -313,7 +313,7 @@
             if (16 * kt + i > thr) S[nb][kt][qg][i] = -INFINITY;
       }
     };
-    // move the reference of rows that need it for the tile whose scores sit in S[cb] at the OLD reference (fa3_fwd4 KPRE).
+    // move the reference of rows that need it for the tile whose scores sit in S[cb] at the OLD reference (KPRE, fa3_fwd5_kernel.h).
     // WHEN = 0: tile 0 of a pass; 1: after phase 1 -- also shift S[cb ^ 1] and recompute the tile's P.  Rare.
     auto move_ref = [&](auto CB_, auto WHEN_) __attribute__((always_inline)) {
       constexpr int cb = decltype(CB_)::value;
@@ -328,7 +328,7 @@
         mxl = fmaxf(mxl, __shfl_xor(mxl, 16, 64));  // the four lanes c16 + 16 g of a query hold its 64 keys
         const float mxr = fmaxf(mxl, __shfl_xor(mxl, 32, 64));
         const bool need = fresh[qg] ? (mxr != -INFINITY) : (mxr >= ics);  // some P >= 2
-        const float delta = need ? mxr + Fa4Margin<T>::value * ics : 0.f;
+        const float delta = need ? mxr + Fa5Margin<T>::value * ics : 0.f;
         const float alpha = (need && !fresh[qg]) ? fast_exp2(-delta * cs) : 1.f;
         if (need) fresh[qg] = false;
         ref[qg] += delta;
@@ -374,7 +374,7 @@
         }
       }
     };
-    auto stg = [&](int tile) __attribute__((always_inline)) -> const char* { return smem + ((tbase + tile) & (FA5_STAGES - 1)) * FA4_STAGE; };
+    auto stg = [&](int tile) __attribute__((always_inline)) -> const char* { return smem + ((tbase + tile) & (FA5_STAGES - 1)) * FA5_STAGE; };
 
     if constexpr (STAMP) pt1 = __builtin_amdgcn_s_memtime();
     int t = 0;

@@ -4,11 +4,9 @@
 #include <cstdlib>
 #include <mutex>
 
-#include "fa3_fwd2_kernel.h"
 #include "fa3_fwd3_kernel.h"
 #include "fa3_route.h"
 #if FA_D == 64
-#include "fa3_fwd4_kernel.h"
 #include "fa3_fwd5_kernel.h"
 #endif
 
@@ -34,31 +32,6 @@ static int launch_one(const FaDev& p, hipStream_t stream) {
   if (e != hipSuccess) return mio_fail(std::string("fa3_fwd launch: ") + hipGetErrorString(e));
   return 0;
 }
-
-#ifdef MIO_DIAG
-// second structure (one wave per SIMD, 64 query rows per wave): no user mask, D % 32 == 0 instantiations
-template <bool CAUSAL>
-static int launch_two(FaDev p, hipStream_t stream) {
-  p.nqblk = (p.Sq + FA2_BM - 1) / FA2_BM;
-  // causal: a workgroup takes query blocks i and nqblk-1-i back to back -> every workgroup does the same work
-  p.qgrid = CAUSAL ? (p.nqblk + 1) / 2 : p.nqblk;
-  static const int order = [] { const char* e = std::getenv("MIO_FA_ORDER"); return e ? std::atoi(e) : 0; }();
-  p.xcd_remap |= order;  // tuning aid: 2 = light-first, 4 = block-major
-  const int grid = p.qgrid * p.B * p.H;
-  const size_t smem = FaSmem<FA_D>::TOTAL;
-  auto kern = fa3_fwd2_kernel<FaT, FA_D, CAUSAL>;
-  if (smem > 48 * 1024) {
-    static std::once_flag once;
-    static hipError_t ea = hipSuccess;
-    std::call_once(once, [&] { ea = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
-    if (ea != hipSuccess) return mio_fail(std::string("fa3_fwd2: hipFuncSetAttribute: ") + hipGetErrorString(ea));
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("fa3_fwd2 launch: ") + hipGetErrorString(e));
-  return 0;
-}
-#endif
 
 // third structure (software-pipelined across KV tiles): no user mask
 template <bool CAUSAL, bool KPRE = false>
@@ -118,55 +91,11 @@ static int launch_three(FaDev p, hipStream_t stream) {
   return 0;
 }
 
-// fourth structure (two waves per SIMD, 8 waves x 32 query rows, 32x32x16 tiles): head dim <= 64, no user mask, plain output.
-// Diagnostic library only since round 3: fa3_fwd5_kernel takes every launch it used to (with and without pre-scaled K).
-#if FA_D == 64 && defined(MIO_DIAG)
-template <bool CAUSAL, bool KPRE = false>
-static int launch_four(FaDev p, hipStream_t stream) {
-  p.nqblk = (p.Sq + FA4_BM - 1) / FA4_BM;
-  p.qgrid = CAUSAL ? (p.nqblk + 1) / 2 : p.nqblk;
-  const int grid = p.qgrid * p.B * p.H;
-  void (*kern)(const FaDev) = fa3_fwd4_kernel<FaT, CAUSAL, 0, KPRE>;
-#if defined(MIO_DIAG) && FA_TYPE_ID == 0
-  if constexpr (CAUSAL && !KPRE) {  // timing-only ablations (tools/fa4_ablate.py)
-    void (*ka)(const FaDev) = nullptr;
-    switch (mio_dbg_get(0)) {
-      case 1: ka = fa3_fwd4_kernel<FaT, CAUSAL, 1>; break;
-      case 2: ka = fa3_fwd4_kernel<FaT, CAUSAL, 2>; break;
-      case 4: ka = fa3_fwd4_kernel<FaT, CAUSAL, 4>; break;
-      case 8: ka = fa3_fwd4_kernel<FaT, CAUSAL, 8>; break;
-      case 12: ka = fa3_fwd4_kernel<FaT, CAUSAL, 12>; break;
-      case 16: ka = fa3_fwd4_kernel<FaT, CAUSAL, 16>; break;
-      case 32: ka = fa3_fwd4_kernel<FaT, CAUSAL, 32>; break;
-      case 35: ka = fa3_fwd4_kernel<FaT, CAUSAL, 35>; break;
-      case 47: ka = fa3_fwd4_kernel<FaT, CAUSAL, 47>; break;
-      case 64: ka = fa3_fwd4_kernel<FaT, CAUSAL, 64>; break;
-      default: break;
-    }
-    if (ka != nullptr) {
-      hipError_t ed = hipFuncSetAttribute((const void*)ka, hipFuncAttributeMaxDynamicSharedMemorySize, FA4_SMEM);
-      if (ed != hipSuccess) return mio_fail(std::string("fa3_fwd4 (ablation): hipFuncSetAttribute: ") + hipGetErrorString(ed));
-      hipLaunchKernelGGL(ka, dim3(grid), dim3(512), FA4_SMEM, stream, p);
-      return 0;
-    }
-  }
-#endif
-  static std::once_flag once;
-  static hipError_t ea = hipSuccess;
-  std::call_once(once, [&] { ea = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, FA4_SMEM); });
-  if (ea != hipSuccess) return mio_fail(std::string("fa3_fwd4: hipFuncSetAttribute: ") + hipGetErrorString(ea));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), FA4_SMEM, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("fa3_fwd4 launch: ") + hipGetErrorString(e));
-  return 0;
-}
-#endif
-
-// fifth structure (fa3_fwd4's skeleton on 16x16x32 MFMA tiles): k_prescaled launches, head dim <= 64
+// fifth structure (two waves per SIMD on 16x16x32 MFMA tiles): head dim <= 64, no user mask
 #if FA_D == 64
 template <bool CAUSAL, bool CARRY = false, bool OBLK = false, bool KPRE = true>
 static int launch_five(FaDev p, hipStream_t stream) {
-  p.nqblk = (p.Sq + FA4_BM - 1) / FA4_BM;
+  p.nqblk = (p.Sq + FA5_BM - 1) / FA5_BM;
   p.qgrid = CAUSAL ? (p.nqblk + 1) / 2 : p.nqblk;
   const int grid = p.qgrid * p.B * p.H;
   void (*kern)(const FaDev) = fa3_fwd5_kernel<FaT, CAUSAL, false, 0, CARRY, OBLK, KPRE>;
@@ -213,44 +142,28 @@ static int launch_five(FaDev p, hipStream_t stream) {
 #endif
 
 #ifdef MIO_DIAG
-static int fa_impl() {  // MIO_FA_IMPL=1 / 2 / 3 force one structure for A/B runs (0 = the rule in fa3_launch)
-  static const int v = [] {
+// A/B overrides of the diagnostic build on top of the route (plain-K launches without a user mask): MIO_FA_IMPL=1 forces
+// the sequential kernel, MIO_FA_IMPL=3 or mio_dbg_set(1, 3) fwd3 where the route takes fwd5 (mio_dbg_set(1, 3) also for
+// pre-scaled K).  Returns 1 with *rc set when it took the launch.
+static int diag_launch(int route, const FaDev& p, int causal, hipStream_t stream, int* rc) {
+  static const int impl = [] {
     const char* e = std::getenv("MIO_FA_IMPL");
     return e ? std::atoi(e) : 0;
   }();
-  return v;
-}
-#else
-static constexpr int fa_impl() { return 0; }
-#endif
-
-#ifdef MIO_DIAG
-// A/B overrides of the diagnostic build on top of the route (MIO_FA_IMPL=1 / 2 / 3 / 4, mio_dbg_set(1, 3 | 4)).  Returns 1
-// with *rc set when it took the launch.
-static int diag_launch(int route, const FaDev& p, int causal, hipStream_t stream, int* rc) {
-  const int impl = fa_impl(), dbg1 = mio_dbg_get(1);
-#if FA_D == 64
-  if ((route == MIO_FA3_ROUTE_FWD5_KPRE || route == MIO_FA3_ROUTE_FWD5_KPRE_OBLK) && (dbg1 == 3 || dbg1 == 4)) {
-    if (dbg1 == 4) *rc = causal ? launch_four<true, true>(p, stream) : launch_four<false, true>(p, stream);
-    else *rc = causal ? launch_three<true, true>(p, stream) : launch_three<false, true>(p, stream);
-    return 1;
-  }
-  if (route == MIO_FA3_ROUTE_FWD5 && (impl != 0 || dbg1 != 0)) {
-    if (impl == 4 || dbg1 == 4) *rc = causal ? launch_four<true>(p, stream) : launch_four<false>(p, stream);
-    else if (impl == 3 || impl == 0) *rc = causal ? launch_three<true>(p, stream) : launch_three<false>(p, stream);
-    else if (impl == 2) *rc = causal ? launch_two<true>(p, stream) : launch_two<false>(p, stream);
-    else *rc = causal ? launch_one<true, 0>(p, stream) : launch_one<false, 0>(p, stream);
-    return 1;
-  }
-#endif
-  if ((route == MIO_FA3_ROUTE_FWD3 || route == MIO_FA3_ROUTE_FWD1) && impl == 2 && p.Sq > 128) {
-    *rc = causal ? launch_two<true>(p, stream) : launch_two<false>(p, stream);
-    return 1;
-  }
-  if (route == MIO_FA3_ROUTE_FWD3 && impl != 0 && impl != 3) {
+  if ((route == MIO_FA3_ROUTE_FWD5 || route == MIO_FA3_ROUTE_FWD3) && impl == 1) {
     *rc = causal ? launch_one<true, 0>(p, stream) : launch_one<false, 0>(p, stream);
     return 1;
   }
+#if FA_D == 64
+  if (route == MIO_FA3_ROUTE_FWD5 && (impl == 3 || mio_dbg_get(1) == 3)) {
+    *rc = causal ? launch_three<true>(p, stream) : launch_three<false>(p, stream);
+    return 1;
+  }
+  if ((route == MIO_FA3_ROUTE_FWD5_KPRE || route == MIO_FA3_ROUTE_FWD5_KPRE_OBLK) && mio_dbg_get(1) == 3) {
+    *rc = causal ? launch_three<true, true>(p, stream) : launch_three<false, true>(p, stream);
+    return 1;
+  }
+#endif
   return 0;
 }
 #endif

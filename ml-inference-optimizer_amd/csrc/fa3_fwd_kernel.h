@@ -39,10 +39,10 @@ struct FaDev {
   int B, Sq, Sk, H, Hkv, D;
   int carry_in, q_offset, k_offset;
   int nqblk, xcd_remap;
-  int qgrid;  // workgroups per (batch, head): nqblk, or ceil(nqblk/2) when causal blocks are paired (fa3_fwd2)
+  int qgrid;  // workgroups per (batch, head): nqblk, or ceil(nqblk/2) when causal blocks are paired (fwd3 / fwd5)
   float scale_log2e;  // softmax_scale * log2(e)
   int o_blk;          // o is the [B*Sq, H*D] output in the blocked activation layout (mio_fa3_o_blocked_ok)
-  int k_prescaled;    // K already carries softmax_scale * log2(e) (fa3_fwd4_kernel KPRE; mio_fa3_k_prescaled_ok)
+  int k_prescaled;    // K already carries softmax_scale * log2(e) (fa3_fwd5_kernel.h KPRE; mio_fa3_k_prescaled_ok)
 };
 
 constexpr int FA_BM = 128;
@@ -61,6 +61,15 @@ struct FaSmem {
   static constexpr int STAGE = K_BYTES + V_BYTES;
   static constexpr int TOTAL = 2 * STAGE;
 };
+
+// compile-time loop helper: f(integral_constant<int, I>) for I in [0, N)
+template <int N, typename F>
+__device__ __forceinline__ void fa2_for(F&& f) {
+  if constexpr (N > 0) {
+    fa2_for<N - 1>(f);
+    f(std::integral_constant<int, N - 1>{});
+  }
+}
 
 template <typename T, int D, bool CAUSAL, int MASK>
 __global__ __launch_bounds__(256) void fa3_fwd_kernel(const FaDev p) {

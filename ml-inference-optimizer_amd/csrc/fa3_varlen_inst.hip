@@ -19,7 +19,7 @@ using FaT = _Float16;
 template <bool CAUSAL>
 static int launch(FaDev p, const FaVarlen& vl, hipStream_t stream) {
 #if FA_D == 64
-  constexpr int BM = FA4_BM, NT = 512;
+  constexpr int BM = FA5_BM, NT = 512;
   constexpr size_t smem = FA5_SMEM;
   auto kern = fa3_fwd5_varlen_kernel<FaT, CAUSAL>;
 #else

@@ -3,8 +3,8 @@
 // K-tile three ahead (cdna_hip_programming.md, "The 256^2 8-phase template"; MI355X_MICROARCH.md, "Two waves per SIMD").
 // Persistent: a workgroup walks its output tiles and the load stream runs on across tiles.
 //
-// Why (round-3 measurements, tools/gemm8_ksweep.py, M 32768 x N 3072, blocked operands): the one-wave-per-SIMD kernels pay
-// issue time for everything that is not an MFMA.  Per K-tile of 32 and workgroup, zero operands (clock 2.39 GHz) / random:
+// Why (round-3 measurements, M 32768 x N 3072, blocked operands): the one-wave-per-SIMD kernels of rounds 1-2 (retired,
+// DESIGN.md section 4.2) pay issue time for everything that is not an MFMA.  Per K-tile of 32 and workgroup, zero operands (clock 2.39 GHz) / random:
 //   gemm4w16_kernel  555 / 696 ns     gemm4w16p_kernel (stores trickled through the K loop)  618 / 750 ns
 //   this loop        520 / 678 ns     (1024 matrix-pipe cycles = 428 ns)
 // and timing-only ablations of this loop: without its LDS-DMA requests 436 ns, without its fragment reads unchanged, with
@@ -13,8 +13,8 @@
 // 1-KiB) pieces are fetched 17 % faster than 64-byte row pieces.  Per tile the one-tile kernels lose another 5.6 - 7.6 us
 // (workgroup launch, first tiles' latency, read-out, store drain): at K = 1024 that is 25 % of the time, hence persistent.
 //
-// Structure (operand formats are gemm4w16_kernel's: K-tile = 32, four 32-KiB LDS stages X[256][32] + W[256][32], 64-byte
-// rows with the g6_swz chunk swizzle on the DMA source address, blocked or row-major operands):
+// Structure (K-tile = 32, four 32-KiB LDS stages X[256][32] + W[256][32], 64-byte rows with the g8_swz chunk swizzle on
+// the DMA source address, blocked or row-major operands):
 //   * wave w: group = w >> 2 (waves w and w + 4 share a SIMD), column quarter = w & 3; wave tile = 128 rows (the
 //     group's half of the tile) x 64 columns = 8 x 4 accumulator tiles of 16x16 (128 registers).  Weight tile = MFMA A
 //     operand, activation tile = B operand: a lane holds ONE output row and 4 consecutive columns (lane-local epilogue).
@@ -53,11 +53,22 @@
 #pragma once
 #include <type_traits>
 
-#include "gemm4w16_kernel.h"
+#include "gemm_kernel.h"
+
+// Operand ring: K-tile = 32 = one MFMA k-step, four LDS stages X[256][32] + W[256][32] (128 KiB).  Bank swizzle for the
+// 16x16x32 fragment read (lane -> row l&15, 16-byte chunk l>>4): chunk c of row r is stored at c ^ f((r>>2)&3),
+// f = {0,2,3,1}, applied to the per-lane SOURCE address (LDS-DMA writes lane-linear).
+constexpr int G8_BK = 32;
+constexpr int G8_STAGES = 4;
+constexpr int G8_XT = 256 * G8_BK * 2;       // 16 KiB: one operand tile (256 rows x 64 B)
+constexpr int G8_BUF = 2 * G8_XT;            // X + W
+constexpr int G8_RING = G8_STAGES * G8_BUF;  // 128 KiB
+
+__device__ __forceinline__ int g8_swz(int row) { return (0x78 >> (((row >> 2) & 3) * 2)) & 3; }
 
 constexpr int G8_THREADS = 512;
-constexpr int G8_BIAS_OFF = G6_SMEM;  // 8 waves x 256 B: each wave's slice of the bias row(s)
-constexpr int G8_SMEM = G6_SMEM + 8 * 256;
+constexpr int G8_BIAS_OFF = G8_RING;  // 8 waves x 256 B: each wave's slice of the bias row(s)
+constexpr int G8_SMEM = G8_RING + 8 * 256;
 // LayerNorm fold (FOLD != 0): per-wave rstd table, the row-statistics region (consumer: [group][slot <= 8][128 rows]
 // (sum, sum of squares); producer: [group][column quarter][128 rows]) and the producer's arrival counters
 constexpr int G8_RS_OFF = G8_SMEM;  // consumer: per wave, rstd of its group's 128 rows (512 B)
@@ -91,17 +102,17 @@ __global__ __launch_bounds__(G8_THREADS) void gemm8w_kernel(const GemmDev p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave >> 2, wn = wave & 3;
   const int c16 = lane & 15, g = lane >> 4;
-  const int nk = p.K / G6_BK;
+  const int nk = p.K / G8_BK;
   const int ntiles = p.tiles_m * p.tiles_n;
 
-  // ---- operand addressing of the tile being computed / prefetched (gemm4w16p_kernel's, 2 + 2 pieces per wave)
+  // ---- operand addressing of the tile being computed / prefetched (2 + 2 pieces per wave)
   int xvo[2], wvo[2];
   __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, 0, 0x00020000);
   __amdgpu_buffer_rsrc_t wrs = xrs;
   int64_t m0 = 0, mrem = 0;
   int n0 = 0, nrem = 0;  // in OUTPUT columns
   // lane id recomputed from an opaque instruction wherever lane-constant addresses are built inside the tile loop: hoisted
-  // out of it (LICM) they are kept live and spilled (gemm4w16p_kernel.h)
+  // out of it (LICM) they are kept live and spilled
   auto lane_now = [&]() {
     int l;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
@@ -119,7 +130,7 @@ __global__ __launch_bounds__(G8_THREADS) void gemm8w_kernel(const GemmDev p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int row = (wave * 2 + i) * 16 + prow;  // 0..255: waves 0..3 request rows 0..127, waves 4..7 rows 128..255
-      const int kch = pcs ^ g6_swz(row);
+      const int kch = pcs ^ g8_swz(row);
       const int xr = (row < mrem) ? row : (int)(mrem - 1);
       const int wrw = (row < wrows) ? row : (wrows - 1);
       xvo[i] = (p.x_blk ? xr * 64 : xr * (int)p.ldx * 2) + 16 * kch;
@@ -132,15 +143,15 @@ __global__ __launch_bounds__(G8_THREADS) void gemm8w_kernel(const GemmDev p) {
         p.w_blk ? (void*)((const char*)p.w + ((int64_t)tn * nk << 14)) : (void*)((const T*)p.w + (int64_t)n0 * p.ldw), 0,
         0x7fffffff, 0x00020000);
   };
-  const int xkstep = p.x_blk ? 16384 : G6_BK * 2;
-  const int wkstep = p.w_blk ? 16384 : G6_BK * 2;
+  const int xkstep = p.x_blk ? 16384 : G8_BK * 2;
+  const int wkstep = p.w_blk ? 16384 : G8_BK * 2;
 
 #define IC(N) std::integral_constant<int, N>{}
   int sbase = 0;  // LDS stage of the current tile's K-tile 0 (the stage index runs on across tiles)
   // piece i (0 / 1) of X (which = 0) or W (which = 1): K-tile `kl` of the tile `setup` describes into stage (sbase + ks) & 3
   auto issue_one = [&](int ks, int kl, auto I, auto WHICH) {
     constexpr int i = decltype(I)::value, which = decltype(WHICH)::value;
-    char* dst = smem + ((sbase + ks) & (G6_STAGES - 1)) * G6_BUF + which * G6_XT + (wave * 2 + i) * 1024;
+    char* dst = smem + ((sbase + ks) & (G8_STAGES - 1)) * G8_BUF + which * G8_XT + (wave * 2 + i) * 1024;
     int koff = kl * (which ? wkstep : xkstep);
     if constexpr ((VAR & 64) != 0) koff = 0;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(which ? wrs : xrs, (MIO_LDS void*)dst, 16, which ? wvo[i] : xvo[i], koff, 0, 0);
@@ -152,9 +163,9 @@ __global__ __launch_bounds__(G8_THREADS) void gemm8w_kernel(const GemmDev p) {
     issue_one(ks, kl, IC(1), IC(1));
   };
 
-  const int co = (g ^ g6_swz(c16)) * 16;
+  const int co = (g ^ g8_swz(c16)) * 16;
   const int xbase = (grp * 128 + c16) * 64 + co;
-  const int wbase = G6_XT + (wn * 64 + c16) * 64 + co;
+  const int wbase = G8_XT + (wn * 64 + c16) * 64 + co;
 
   constexpr bool ROT = (VAR & 2048) == 0;  // (ablation 2048: all eight activation fragments read in the read segment)
   X8 fx[ROT ? 4 : 8];
@@ -190,7 +201,7 @@ __global__ __launch_bounds__(G8_THREADS) void gemm8w_kernel(const GemmDev p) {
   };
   // EXTRA (FOLD 1): 1 = request the row statistics behind this K-tile's operand requests, 1 / 2 = count them in the wait
   auto ktile = [&](int kt, int kl, auto FIRST, auto WAIT, auto EXTRA) {
-    const char* buf = smem + ((sbase + kt) & (G6_STAGES - 1)) * G6_BUF;
+    const char* buf = smem + ((sbase + kt) & (G8_STAGES - 1)) * G8_BUF;
     // -- read segment
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) fw[nt] = __builtin_bit_cast(X8, *(const u32x4_t*)(buf + wbase + nt * 1024));
@@ -296,7 +307,7 @@ __global__ __launch_bounds__(G8_THREADS) void gemm8w_kernel(const GemmDev p) {
     ktile(nk - 3, 0, IC(0), IC(8), IC(0));
     ktile(nk - 2, 1, IC(0), IC(8), IC(0));
     ktile(nk - 1, 2, IC(0), IC(4), IC(0));
-    sbase = (sbase + nk) & (G6_STAGES - 1);
+    sbase = (sbase + nk) & (G8_STAGES - 1);
     if constexpr ((VAR & 128) != 0) st[4] = __builtin_amdgcn_s_memtime();
 
     // ---- read-out: bias / activation / column scale (/ residual), row-pair exchange, 16-byte stores.

@@ -7,7 +7,7 @@
 extern template int gemm_launch<__bf16>(GemmDev, int, hipStream_t);
 extern template int gemm_launch<_Float16>(GemmDev, int, hipStream_t);
 
-// Diagnostic build only: MIO_GEMM_IMPL=v1|4wp|4w16 forces one pipeline for A/B comparisons (read once).  The product
+// Diagnostic build only: MIO_GEMM_IMPL=v1|8w1 forces one pipeline for A/B comparisons (read once).  The product
 // library always takes the default dispatch (0) and reads no environment variable.
 int mio_gemm_impl() {
 #ifdef MIO_DIAG
@@ -17,8 +17,6 @@ int mio_gemm_impl() {
     if (e == nullptr) return 0;
     const std::string s(e);
     if (s == "v1") return 1;
-    if (s == "4wp") return 5;
-    if (s == "4w16") return 6;
     if (s == "8w1") return 9;   // gemm8w_kernel, one workgroup per tile
     return 0;
   }();
@@ -66,7 +64,7 @@ extern "C" int mio_gemm_bias_act(const void* x, const void* w, const void* bias,
 // then the intermediate can use the blocked layout (GemmDev::x_blk / y_blk).
 static bool mlp_blocked_ok(int64_t M, int32_t d, int32_t I, int32_t act, bool residual) {
   (void)residual;
-  if (mio_gemm_impl() != 0 && mio_gemm_impl() < 5) return false;
+  if (mio_gemm_impl() == 1) return false;
   const int64_t tm = (M + 255) / 256;
   // (SwiGLU: stage 1 computes 256 x 128 output tiles from 256 interleaved gate / up weight rows, gemm8w_kernel.h)
   const bool big1 = tm * ((I + 255) / 256) >= 256, big2 = tm * ((d + 255) / 256) >= 256;
@@ -127,7 +125,7 @@ extern "C" int mio_fused_mlp_fwd(const void* x, const void* w1, const void* b1, 
 
 // ---- blocked weights -----------------------------------------------------------------------------------------------
 static bool gemm_blocked_w_ok(int64_t M, int32_t N, int32_t K, int32_t act) {
-  if (act == MIO_ACT_SWIGLU || (mio_gemm_impl() != 0 && mio_gemm_impl() < 5)) return false;
+  if (act == MIO_ACT_SWIGLU || mio_gemm_impl() == 1) return false;
   const bool big = ((M + 255) / 256) * (int64_t)((N + 255) / 256) >= 256;
   return big && K % 32 == 0 && K >= 128 && (int64_t)K * 512 < 0x7fffffff && (int64_t)N * 512 < 0x7fffffff;
 }
@@ -198,7 +196,7 @@ extern "C" int mio_gemm_bias_act_bw(const void* x, const void* wb, const void* b
 // column scale: the launch must end in the persistent kernel (gemm_inst.hip launch_act): blocked weight shape, no residual,
 // K >= 256, K % 64 == 0
 extern "C" int32_t mio_gemm_col_scale_ok(int64_t M, int32_t N, int32_t K, int32_t act) {
-  return (gemm_blocked_w_ok(M, N, K, act) && (mio_gemm_impl() == 0 || mio_gemm_impl() >= 5) && K >= 256 && K % 64 == 0 && N % 8 == 0) ? 1 : 0;
+  return (gemm_blocked_w_ok(M, N, K, act) && K >= 256 && K % 64 == 0 && N % 8 == 0) ? 1 : 0;
 }
 
 extern "C" int mio_gemm_bias_act_bw_cs(const void* x, const void* wb, const void* bias, void* y, int64_t M, int32_t N,

@@ -3,8 +3,6 @@
 #include <cstdlib>
 #include <mutex>
 
-#include "gemm4w16_kernel.h"
-#include "gemm4w16p_kernel.h"
 #include "gemm8w_kernel.h"
 
 #if GEMM_TYPE_ID == 0
@@ -29,92 +27,6 @@ static int launch_cfg(GemmDev p, hipStream_t stream) {
   if (e != hipSuccess) return mio_fail(std::string("gemm launch: ") + hipGetErrorString(e));
   return 0;
 }
-
-#ifdef MIO_DIAG
-static int gemm_var() {  // MIO_GEMM_VAR=<bits>: timing-only ablations of the ACT_NONE one-tile kernel (tuning aid)
-  static const int v = [] {
-    const char* e = std::getenv("MIO_GEMM_VAR");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
-}
-#endif
-
-#ifdef MIO_DIAG  // the one-wave-per-SIMD kernels of rounds 1-2: kept in the diagnostic library for A/B runs only
-template <int ACT, int VAR = 0>
-static int launch_4w16(GemmDev p, hipStream_t stream) {
-#ifdef MIO_DIAG
-  if constexpr (ACT == MIO_ACT_NONE && VAR == 0) {
-    if (p.dbg != nullptr) {
-      switch (gemm_var()) {
-        case 4: return launch_4w16<ACT, 36>(p, stream);
-        case 8: return launch_4w16<ACT, 40>(p, stream);
-        case 12: return launch_4w16<ACT, 44>(p, stream);
-        case 16: return launch_4w16<ACT, 48>(p, stream);
-        case 28: return launch_4w16<ACT, 60>(p, stream);
-        default: return launch_4w16<ACT, 32>(p, stream);
-      }
-    }
-    if (gemm_var() == 16) return launch_4w16<ACT, 16>(p, stream);
-  }
-#endif
-  p.tiles_m = (int)((p.M + 255) / 256);
-  p.tiles_n = (p.N + 255) / 256;
-  auto kern = gemm4w16_kernel<GT, ACT, VAR>;
-  static std::once_flag once;
-  static hipError_t ea = hipSuccess;
-  std::call_once(once, [&] { ea = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G6_SMEM); });
-  if (ea != hipSuccess) return mio_fail(std::string("gemm4w16: hipFuncSetAttribute: ") + hipGetErrorString(ea));
-  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(256), G6_SMEM, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("gemm4w16 launch: ") + hipGetErrorString(e));
-  return 0;
-}
-
-// persistent variant with the overlapped epilogue (no residual operand, K >= 128)
-template <int ACT, int SPK = 0>
-static int launch_4w16p(GemmDev p, hipStream_t stream) {
-  if constexpr (SPK == 0) {  // stores per K-tile so that all 32 chunks of a tile leave during the next one
-    const int nk = p.K / 32;
-    if (nk >= 32) return launch_4w16p<ACT, 1>(p, stream);
-    if (nk >= 16) return launch_4w16p<ACT, 2>(p, stream);
-    return launch_4w16p<ACT, 4>(p, stream);
-  }
-  p.tiles_m = (int)((p.M + 255) / 256);
-  p.tiles_n = (p.N + 255) / 256;
-  auto kern = gemm4w16p_kernel<GT, ACT, (SPK == 0 ? 1 : SPK)>;
-  static std::once_flag once;
-  static hipError_t ea = hipSuccess;
-  static int ncu = 256;
-  std::call_once(once, [&] {
-    ea = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G6P_SMEM);
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      ncu = n & ~7;  // whole XCD groups, so tile % 8 keeps naming the XCD
-  });
-  if (ea != hipSuccess) return mio_fail(std::string("gemm4w16p: hipFuncSetAttribute: ") + hipGetErrorString(ea));
-  const int tiles = p.tiles_m * p.tiles_n;
-#ifdef MIO_DIAG
-  if constexpr (ACT == MIO_ACT_NONE && SPK == 1) {
-    if (p.dbg != nullptr) {  // in-kernel stamps (tools/gemm_stamps_p.py)
-      auto kd = gemm4w16p_kernel<GT, ACT, 1, true>;
-      hipError_t ed = hipFuncSetAttribute((const void*)kd, hipFuncAttributeMaxDynamicSharedMemorySize, G6P_SMEM);
-      if (ed != hipSuccess) return mio_fail(std::string("gemm4w16p (stamps): hipFuncSetAttribute: ") + hipGetErrorString(ed));
-      hipLaunchKernelGGL(kd, dim3(tiles < ncu ? tiles : ncu), dim3(256), G6P_SMEM, stream, p);
-      hipError_t e2 = hipGetLastError();
-      if (e2 != hipSuccess) return mio_fail(std::string("gemm4w16p (stamps) launch: ") + hipGetErrorString(e2));
-      return 0;
-    }
-  }
-#endif
-  hipLaunchKernelGGL(kern, dim3(tiles < ncu ? tiles : ncu), dim3(256), G6P_SMEM, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("gemm4w16p launch: ") + hipGetErrorString(e));
-  return 0;
-}
-
-#endif  // MIO_DIAG
 
 // eight-wave ping-pong kernel (gemm8w_kernel.h), persistent; `one_tile`: one workgroup per tile instead (A/B only)
 template <int ACT, bool RES, int VAR = 0, int FOLD = 0>
@@ -195,10 +107,6 @@ static int launch_act(const GemmDev& p, hipStream_t stream) {
         if (gemm_impl() == 20) return launch_8w<ACT, false, 256>(p, stream);  // scalar activation math
       }
       if (gemm_impl() == 9) return launch_8w_res<ACT>(p, stream, true);  // one workgroup per tile
-      if (gemm_impl() == 5 || gemm_impl() == 6) {  // rounds 1-2: persistent where it applied, else one tile per workgroup
-        if (gemm_impl() == 5 && p.res == nullptr && p.K >= 256 && p.K % 64 == 0) return launch_4w16p<ACT>(p, stream);
-        return launch_4w16<ACT>(p, stream);
-      }
 #endif
       return launch_8w_res<ACT>(p, stream);
     }

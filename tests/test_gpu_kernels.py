@@ -104,7 +104,7 @@ def test_fa3_benchmark_length(dtype, causal, D, S, H):
     cannot finish this size in seconds, so the checker is plain fp32 torch on the GPU (softmax(q k^T / sqrt(D)) v) on
     the same 16-bit inputs; lse against logsumexp.  Scores are scaled up (q * 3) so that rows really outgrow their
     running reference by more than the rescale threshold several times (the rare path that rescales the asm-owned
-    accumulators).  Head dims 128 and 80 take the one-wave-per-SIMD kernel (fa3_fwd2)."""
+    accumulators).  Head dims 128 and 80 take the one-wave-per-SIMD pipelined kernel (fa3_fwd3), head dim 64 fa3_fwd5."""
     ops = _ops()
     torch.manual_seed(17)
     B = 1

@@ -451,8 +451,8 @@ def test_fwd3_accumulator_registers_untouched_by_compiler(tmp_path, type_id, D):
         assert not any("scratch_" in l for l in text[a:b + 1]), "register spills in " + text[a]
 
 
-def test_fwd4_two_waves_per_simd_fits_without_spills(tmp_path):
-    """fa3_fwd4_kernel / fa3_fwd5_kernel run two waves per SIMD: 256 registers per wave.  It must fit them without scratch (a staggered
+def test_fwd5_two_waves_per_simd_fits_without_spills(tmp_path):
+    """fa3_fwd5_kernel runs two waves per SIMD: 256 registers per wave.  It must fit them without scratch (a staggered
     variant that did not fit ran 60 % slower) -- check the ISA metadata of both dtypes' causal instantiation."""
     import shutil
     import subprocess
@@ -467,8 +467,7 @@ def test_fwd4_two_waves_per_simd_fits_without_spills(tmp_path):
                         "-DFA_D=64", "-S", "--cuda-device-only", "fa3_fwd_inst.hip", "-o", str(isa)], cwd=csrc, check=True,
                        capture_output=True)
         text = isa.read_text()
-        blocks = re.findall(r"\.name:\s+_Z15fa3_fwd[45]_kernel\w+\n(?:.*\n){0,12}", text)
-        assert not any("fa3_fwd4" in b for b in blocks), "fa3_fwd4_kernel is diagnostic-only since round 3"
+        blocks = re.findall(r"\.name:\s+_Z15fa3_fwd5_kernel\w+\n(?:.*\n){0,12}", text)
         assert len(blocks) >= 8, "fa3_fwd5_kernel: causal / full x {pre-scaled, plain K, ring carry, blocked output}"
         for blk in blocks:
             assert re.search(r"\.private_segment_fixed_size:\s+0\b", blk), blk
@@ -531,39 +530,10 @@ def test_fwd1_staging_registers_not_moved_in_flight(tmp_path, type_id, D):
         assert not hits, text[a] + "\n" + "\n".join(hits[:8])
 
 
-@pytest.mark.parametrize("D", [64, 96, 128])
-def test_fwd2_accumulator_registers_untouched_by_compiler(tmp_path, D):
-    """fa3_fwd2_kernel keeps its 2*D/32 O^T tiles in the top accumulator registers a[256 - 32*D/32*... : 255] through
-    inline asm only; same soundness condition as for fwd3 (a version with the tiles at a0.. had the compiler park
-    temporaries in a0-a2 inside the rescale path at D = 96 / 128)."""
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "ml-inference-optimizer_amd", "csrc")
-    isa = tmp_path / "fa.s"
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I../../include", "-I.", "-Wno-unused-value",
-                    "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", "-DFA_TYPE_ID=0", f"-DFA_D={D}", "-DMIO_DIAG", "-S",
-                    "--cuda-device-only", "fa3_fwd_inst.hip", "-o", str(isa)], cwd=csrc, check=True, capture_output=True)
-    text = isa.read_text().splitlines()  # (fa3_fwd2 is instantiated in the diagnostic build only: A/B runs)
-    starts = [i for i, l in enumerate(text) if re.match(r"^_Z15fa3_fwd2_kernel\w+:", l)]
-    assert len(starts) == 2
-    floor = 256 - 16 * (2 * D // 32)
-    for a in starts:
-        b = next(i for i in range(a, len(text)) if "s_endpgm" in text[i])
-        part = tmp_path / "k.s"
-        part.write_text("\n".join(text[a:b + 1]))
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_agpr.py"), str(part), str(floor)],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, text[a] + "\n" + r.stdout
-
-
-def test_gemm_kernels_isa_soundness(tmp_path):
+def test_gemm8w_kernel_isa_soundness(tmp_path):
     """(a) gemm8w_kernel (the product's 256x256-tile GEMM, two waves per SIMD, compiler-managed registers): every shipped
     instantiation fits 256 registers without scratch -- a spill inside its K loop would put a vmcnt(0) in front of the
-    counted waits.  (b) gemm4w16_kernel / gemm4w16p_kernel (diagnostic library, A/B runs) own the WHOLE accumulator file
-    through inline asm: no compiler-generated instruction may touch any accumulator register, and nothing may spill."""
+    counted waits."""
     import shutil
     import subprocess
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -575,7 +545,6 @@ def test_gemm_kernels_isa_soundness(tmp_path):
                     "-Wno-inline-asm", "-DGEMM_TYPE_ID=0", "-DMIO_DIAG", "-S", "--cuda-device-only", "gemm_inst.hip", "-o", str(isa)],
                    cwd=csrc, check=True, capture_output=True)
     full = isa.read_text()
-    text = full.splitlines()
     blocks = re.findall(r"\.name:\s+_Z13gemm8w_kernel\w+Li0EEv7GemmDev\n(?:.*\n){0,12}", full)  # VAR = 0: what the product launches
     assert len(blocks) >= 9, "gemm8w_kernel: 5 plain + 4 residual instantiations (+ SwiGLU) expected"
     for blk in blocks:
@@ -584,25 +553,11 @@ def test_gemm_kernels_isa_soundness(tmp_path):
             assert re.search(r"\.private_segment_fixed_size:\s+0\b", blk), blk
             assert re.search(r"\.vgpr_spill_count:\s+0\b", blk), blk
         assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= 256, blk
-    # (c) no store whose data registers are rewritten by the very next instruction (tools/check_store_war.py: the hazard
+    # (b) no store whose data registers are rewritten by the very next instruction (tools/check_store_war.py: the hazard
     # behind round 3's wrong lanes -- hipcc leaves no wait state behind a buffer_store with a register soffset)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_store_war.py"), str(isa), "gemm8w_kernel", "1"],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stdout
-    starts = [i for i, l in enumerate(text) if re.match(r"^_Z1[56]gemm4w16p?_kernel\w+:", l)]
-    assert len(starts) >= 10
-    for a in starts:
-        b = next(i for i in range(a, len(text)) if "s_endpgm" in text[i])
-        part = tmp_path / "k.s"
-        part.write_text("\n".join(text[a:b + 1]))
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_agpr.py"), str(part), "0"],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, text[a] + "\n" + r.stdout
-        production = re.match(r"^_Z16gemm4w16p_kernel\w+Lb0EEv7GemmDev:", text[a]) or \
-            re.match(r"^_Z15gemm4w16_kernel\w+ELi0EEv7GemmDev:", text[a])  # not the stamp / ablation builds
-        erf = "DF16bLi2E" in text[a]
-        if production and not erf:
-            assert not any("scratch_" in l for l in text[a:b + 1]), "register spills in " + text[a]
 
 
 @pytest.mark.parametrize("n1,n2", [(64, 4), (13, 4), (4, 4), (5, 1), (1, 0), (3, 0), (12, 8), (2, 1), (7, 3), (0, 0)])

@@ -19,8 +19,8 @@ def run(q, k, v, n):
 rnd = [torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16) for _ in range(3)]
 zero = [torch.zeros_like(t) for t in rnd]
 ones = [torch.ones_like(t) for t in rnd]
-for impl in (3, 4):
-    _lib.lib.mio_dbg_set(1, impl)
+for impl in (5, 3):  # fa3_fwd5_kernel (the route), fa3_fwd3_kernel (mio_dbg_set(1, 3))
+    _lib.lib.mio_dbg_set(1, 3 if impl == 3 else 0)
     for name, (q, k, v) in (("random", rnd), ("zeros", zero), ("ones", ones), ("random q,k / zero v", (rnd[0], rnd[1], zero[2])),
                             ("zero q,k / random v", (zero[0], zero[1], rnd[2]))):
         print(f"fwd{impl} {name:24s} {run(q, k, v, 300):.4f} ms", flush=True)

@@ -11,4 +11,4 @@ q, k, v = (torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16) for _ in
 t1 = timeit(lambda: ops.fa3_fwd(q, k, v, causal=True), 20)
 t2 = timeit(lambda: ops.fa3_fwd(q, k, v, causal=True, q_offset=S), 20)
 t3 = timeit(lambda: ops.fa3_fwd(q, k, v, causal=False), 20)
-print(os.environ.get("MIO_FA_IMPL", "2"), os.environ.get("MIO_FA_ORDER", "0"), f"causal {t1*1e3:.3f} ms | causal-all-visible {t2*1e3:.3f} | noncausal {t3*1e3:.3f}")
+print(os.environ.get("MIO_FA_IMPL", "route"), f"causal {t1*1e3:.3f} ms | causal-all-visible {t2*1e3:.3f} | noncausal {t3*1e3:.3f}")

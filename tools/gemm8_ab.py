@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Same-process A/B of the GEMM pipelines on the C2 layer shapes (diagnostic library: mio_dbg_set(4, impl)).
-impl 0 = shipped dispatch, 6 = gemm4w16 one-tile, 8 / 9 = gemm8w (two / one phase per K-tile), ...
+impl 0 = shipped dispatch (persistent gemm8w), 1 = gemm_bias_act_kernel 256x256, 9 = gemm8w one workgroup per tile, ...
 Checks every variant against an fp32 matmul first, then times them interleaved (rounds x variants)."""
 import os, sys
 os.environ["MIO_LIB_DBG"] = "1"
@@ -11,7 +11,7 @@ from mio import ops, _lib
 sys.path.insert(0, ROOT)
 from tools.kbench import timeit
 
-impls = [int(a) for a in sys.argv[1].split(",")] if len(sys.argv) > 1 else [0, 8, 9]
+impls = [int(a) for a in sys.argv[1].split(",")] if len(sys.argv) > 1 else [0, 9]
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 xblk = len(sys.argv) > 3 and sys.argv[3] == "xblk"  # activation operand in the blocked layout (as on the main path)
 M, d, I, dt, dev = 32768, 1024, 4096, torch.bfloat16, "cuda"

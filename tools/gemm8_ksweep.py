@@ -9,7 +9,7 @@ sys.path.insert(0, os.path.join(ROOT, "ml-inference-optimizer_amd"))
 sys.path.insert(0, ROOT)
 from mio import ops, _lib
 from tools.kbench import timeit
-impls = [int(a) for a in sys.argv[1].split(",")] if len(sys.argv) > 1 else [6, 8, 9]
+impls = [int(a) for a in sys.argv[1].split(",")] if len(sys.argv) > 1 else [0, 9]
 scale = float(sys.argv[2]) if len(sys.argv) > 2 else 1.0
 xblk = len(sys.argv) > 3 and sys.argv[3] == "xblk"  # activation operand in the blocked layout too
 M, N, dt, dev = 32768, 3072, torch.bfloat16, "cuda"

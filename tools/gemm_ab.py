@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B timing of GEMM shapes (C2 layer) for the current MIO_GEMM_VAR / MIO_GEMM_IMPL environment."""
+"""A/B timing of GEMM shapes (C2 layer) for the current MIO_GEMM_IMPL environment."""
 import os, sys
 os.environ.setdefault("MIO_LIB_DBG", "1")  # A/B switches and stamp kernels live in libmio_hip_dbg.so (make dbg)
 import torch
@@ -23,4 +23,4 @@ b = (torch.randn(I, device=dev) * 0.02).to(dt)
 out = torch.empty(M, I, device=dev, dtype=dt)
 t = timeit(lambda: ops.gemm_bias_act(x, w, b, "gelu", out=out), 20)
 res.append(f"fc1+gelu {t*1e3:.3f}ms {2*M*I*d/t/1e12:.0f}TF")
-print(os.environ.get("MIO_GEMM_VAR", "0"), os.environ.get("MIO_GEMM_IMPL", "default"), " | ".join(res))
+print(os.environ.get("MIO_GEMM_IMPL", "default"), " | ".join(res))

@@ -18,4 +18,4 @@ for K in (32, 64, 512, 1024, 2048, 4096, 8192):
     t = timeit(lambda: ops.gemm_bias_act(x, w, None, out=out), 20)
     tt = timeit(lambda: torch.nn.functional.linear(x, w), 20)
     res.append(f"K{K}: {t*1e6:.1f}us (blaslt {tt*1e6:.1f}us)")
-print(os.environ.get("MIO_GEMM_IMPL", "4w"), os.environ.get("MIO_GEMM_VAR", "0"), " | ".join(res))
+print(os.environ.get("MIO_GEMM_IMPL", "default"), " | ".join(res))

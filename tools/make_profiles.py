@@ -25,27 +25,21 @@ def short(name):
         dt = "bf16" if rest.startswith("DF16b") else ("fp16" if rest.startswith("DF16_") else "?")
         ints = re.findall(r"L([ib])(\d+)E", rest)
         vals = [v for _, v in ints]
-        if k in ("gemm4w16_kernel", "gemm4w16p_kernel"):
-            return f"{k}<{dt},{ACT.get(vals[0], vals[0])}>"
         if k == "gemm8w_kernel":  # <T, ACT, RES, VAR, FOLD>: FOLD 1 = LayerNorm applied in the read-out, 2 = row statistics written
             fold = {"1": ",ln-fold", "2": ",ln-stats"}.get(vals[3] if len(vals) > 3 else "0", "")
             return f"{k}<{dt},{ACT.get(vals[0], vals[0])}{',residual' if vals[1] == '1' else ''}{fold}>"
         if k == "gemm_bias_act_kernel":
             return f"{k}<{dt},{ACT.get(vals[-1], vals[-1])}>"
-        if k in ("fa3_fwd_kernel", "fa3_fwd2_kernel"):
+        if k == "fa3_fwd_kernel":
             return f"{k}<{dt},D{vals[0]},{'causal' if vals[1] == '1' else 'full'}>"
         if k == "fa3_fwd5_kernel":  # <T, CAUSAL>
             return f"{k}<{dt},{'causal' if vals[0] == '1' else 'full'}>"
-        if k == "fa3_fwd4_kernel":  # <T, CAUSAL, ABL, KPRE>
-            return f"{k}<{dt},{'causal' if vals[0] == '1' else 'full'}{',k_prescaled' if vals[-1] == '1' and len(vals) >= 3 else ''}>"
         if k == "fa3_fwd3_kernel":  # <T, D, CAUSAL, STAMP>; the benchmark's head dim 64 keeps the short name bench.py uses
             tag = "" if vals[0] == "64" else f"D{vals[0]},"
             return f"{k}<{dt},{tag}{'causal' if vals[1] == '1' else 'full'}>"
         return f"{k}<{dt}>"
     if re.match(r"(?:void )?fa3_fwd3_kernel<bool _Accum, bool, E", name):  # <__bf16, true, false> mis-demangled
         return "fa3_fwd3_kernel<bf16,causal>"
-    if re.match(r"(?:void )?fa3_fwd4_kernel<", name):  # <__bf16, true, 0, true>
-        return "fa3_fwd4_kernel<bf16,causal,k_prescaled>"
     if re.match(r"(?:void )?fa3_fwd5_kernel<", name):  # the benchmark launches <__bf16, true>
         return "fa3_fwd5_kernel<bf16,causal>"
     m = re.match(r"(?:void )?gemm8w_kernel<bool _Accum, int, E(Lb0E)?(?:, (true|false))?, (\d+), (\d+)>", name)
