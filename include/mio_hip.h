@@ -181,6 +181,54 @@ typedef enum {
 } mio_fa3_varlen_route_t;
 int32_t mio_fa3_varlen_route(const mio_fa3_varlen_params_t* p);
 
+/* ------------------------------------------------------------------------------------------
+ * Attention forward over the paged KV cache (chunked prefill, shared prefixes, multi-token
+ * verify against a cached context), on the pipelined kernels of routes FWD5 / FWD3.
+ *
+ * q/o [total_q,H,D] packed as in mio_fa3_fwd_varlen (cu_seqlens_q, (token, head) strides, d
+ * stride 1).  k_cache/v_cache [num_blocks, num_layers, block_size, Hkv, D] contiguous (the
+ * layout of mio_fa3_decode_paged), read at layer_idx.  Sequence b sees keys 0 .. Lk_b-1,
+ * Lk_b = min(seqused_k[b], max_seqlen_k, max_blocks_per_seq * block_size); key j lives in page
+ * block_tables[b, j / block_size] at slot j % block_size.  cu_seqlens_q [B+1], seqused_k [B]
+ * and block_tables [B, max_blocks_per_seq] are int32 DEVICE arrays, never read on the host.
+ * The kernel clamps cu_seqlens_q as mio_fa3_fwd_varlen does, every logical block into
+ * [0, max_blocks_per_seq) and every page into [0, num_blocks): a bad table gives wrong numbers,
+ * never an access outside the buffers.  Rows of o outside every sequence are not written.
+ * causal: bottom-right aligned per sequence (query i sees key j iff j <= i + Lk_b - Lq_b).  Rows
+ * with no visible key, and every row of a sequence with Lk_b == 0, get o = 0, lse = -inf.
+ * lse (nullable): fp32 [H,total_q].  block_size must be a multiple of 64 (a 64-key tile never
+ * spans two pages); num_blocks * num_layers * block_size < 2^32.  H % Hkv == 0; D in [8,128],
+ * D % 8 == 0; plain K, softmax_scale applied in fp32.  No host sync; graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void* q;
+  const void* k_cache;
+  const void* v_cache;
+  void* o;
+  float* lse;                  /* nullable, fp32 [H, total_q] */
+  const int32_t* cu_seqlens_q; /* device, B+1 entries */
+  const int32_t* seqused_k;    /* device, B entries: keys of each sequence in the cache */
+  const int32_t* block_tables; /* device, [B, max_blocks_per_seq] */
+  int64_t q_stride[2];         /* token, head */
+  int64_t o_stride[2];
+  int32_t B, total_q, max_seqlen_q, max_seqlen_k, H, Hkv, D;
+  int32_t num_blocks, num_layers, layer_idx, block_size, max_blocks_per_seq;
+  int32_t dtype;       /* mio_dtype_t */
+  int32_t causal;      /* 0/1 */
+  float softmax_scale; /* > 0 */
+} mio_fa3_paged_params_t;
+
+int mio_fa3_fwd_paged(const mio_fa3_paged_params_t* p, void* stream);
+/* Which kernel mio_fa3_fwd_paged launches (nothing is launched or dereferenced; no device needed).  Returns a
+ * mio_fa3_paged_route_t, or < 0 (mio_last_error()) where mio_fa3_fwd_paged would refuse the arguments. */
+typedef enum {
+  MIO_FA3_PAGED_ROUTE_INVALID = -1,
+  MIO_FA3_PAGED_ROUTE_EMPTY = 0, /* B == 0 or total_q == 0: nothing to launch */
+  MIO_FA3_PAGED_ROUTE_FWD5 = 1,  /* fa3_fwd5_paged_kernel (padded head dim 64) */
+  MIO_FA3_PAGED_ROUTE_FWD3 = 2   /* fa3_fwd3_paged_kernel (padded head dim 96 / 128) */
+} mio_fa3_paged_route_t;
+int32_t mio_fa3_paged_route(const mio_fa3_paged_params_t* p);
+
 /* Merge two normalised partial attention states over disjoint key sets (ring / split-KV):
  * o = w_a*o_a + w_b*o_b, lse = logaddexp(lse_a, lse_b), w_x = exp(lse_x - lse).
  * Restates the (alpha, beta) update of kernels/triton/attention_kernels.py:1573-1585.
@@ -324,6 +372,22 @@ int mio_reshape_and_cache(const void* key, const void* value, void* k_cache, voi
                           const int64_t k_stride[2], const int64_t v_stride[2], /* b, h */
                           int32_t B, int32_t Hkv, int32_t D, int32_t num_layers, int32_t layer_idx,
                           int32_t block_size, int32_t max_blocks_per_seq, int32_t dtype, void* stream);
+
+/* Scatter many new tokens per sequence into the paged cache (prompt chunks, multi-token appends).
+ * key/value [total_new,Hkv,D] packed, given by (token, head) strides (d stride 1); sequence b's
+ * tokens are rows cu_seqlens_new[b] .. cu_seqlens_new[b+1]-1 (clamped into [0,total_new)), and
+ * context_lengths[b] is its length AFTER the append: token i of n_b goes to position
+ * context_lengths[b] - n_b + i.  Both are int32 DEVICE arrays [B+1] / [B], never read on the host.
+ * Positions that are negative or past the block-table row, and table entries outside
+ * [0,num_blocks), are skipped.  Caches as in mio_fa3_decode_paged.  Byte-exact 16-byte copies;
+ * no host sync; graph-capturable. */
+int mio_reshape_and_cache_varlen(const void* key, const void* value, void* k_cache, void* v_cache,
+                                 const int32_t* block_tables, const int32_t* cu_seqlens_new,
+                                 const int32_t* context_lengths, const int64_t k_stride[2],
+                                 const int64_t v_stride[2], /* token, head */
+                                 int32_t B, int32_t total_new, int32_t Hkv, int32_t D, int32_t num_blocks,
+                                 int32_t num_layers, int32_t layer_idx, int32_t block_size,
+                                 int32_t max_blocks_per_seq, int32_t dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -628,3 +628,65 @@ extern "C" int mio_reshape_and_cache(const void* key, const void* value, void* k
   if (e != hipSuccess) return mio_fail(std::string("reshape_and_cache launch: ") + hipGetErrorString(e));
   return 0;
 }
+
+// ---- reshape_and_cache_varlen: many new tokens per sequence; one thread per 16-byte chunk of K and of V ------------------
+// Thread i of the grid owns chunk i % (Hkv * D / 8) of packed token i / (Hkv * D / 8).  The token's sequence is the last b
+// with cu[b] <= token (binary search over the clamped offsets, then checked: a token outside its sequence's clamped range is
+// skipped, so offsets that disagree with total_new write nothing out of place).
+__global__ __launch_bounds__(256) void reshape_and_cache_varlen_kernel(
+    const uint16_t* __restrict__ key, const uint16_t* __restrict__ value, uint16_t* __restrict__ kc,
+    uint16_t* __restrict__ vc, const int32_t* __restrict__ bt, const int32_t* __restrict__ cu,
+    const int32_t* __restrict__ cl, int64_t ks_t, int64_t ks_h, int64_t vs_t, int64_t vs_h, int B, int total, int Hkv, int D,
+    int num_blocks, int L, int layer, int bs, int max_blocks) {
+  const int cpr = D >> 3, cpt = Hkv * cpr;  // 16-byte chunks per head row / per token
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)total * cpt) return;
+  const int t = (int)(i / cpt), c = (int)(i % cpt), hh = c / cpr, cc = c % cpr;
+  auto cu_at = [&](int b) { const int x = cu[b]; return x < 0 ? 0 : (x > total ? total : x); };
+  int lo = 0, hi = B;  // the sequence: last b in [0, B) with cu[b] <= t
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (cu_at(mid) <= t) lo = mid; else hi = mid;
+  }
+  const int b = lo, s0 = cu_at(b), s1e = cu_at(b + 1), s1 = s1e > s0 ? s1e : s0;
+  if (t < s0 || t >= s1) return;
+  const int pos = cl[b] - (s1 - s0) + (t - s0);
+  if (pos < 0 || pos / bs >= max_blocks) return;  // before the sequence / past its block-table row
+  const int pb = bt[(int64_t)b * max_blocks + pos / bs];
+  if (pb < 0 || pb >= num_blocks) return;
+  const int64_t tok_stride = (int64_t)Hkv * D;
+  const int64_t dst = (((int64_t)pb * L + layer) * bs + pos % bs) * tok_stride + (int64_t)hh * D + 8 * cc;
+  *(u32x4_t*)(kc + dst) = *(const u32x4_t*)(key + t * ks_t + hh * ks_h + 8 * cc);
+  *(u32x4_t*)(vc + dst) = *(const u32x4_t*)(value + t * vs_t + hh * vs_h + 8 * cc);
+}
+
+extern "C" int mio_reshape_and_cache_varlen(const void* key, const void* value, void* k_cache, void* v_cache,
+                                            const int32_t* block_tables, const int32_t* cu_seqlens_new,
+                                            const int32_t* context_lengths, const int64_t k_stride[2],
+                                            const int64_t v_stride[2], int32_t B, int32_t total_new, int32_t Hkv,
+                                            int32_t D, int32_t num_blocks, int32_t num_layers, int32_t layer_idx,
+                                            int32_t block_size, int32_t max_blocks_per_seq, int32_t dtype,
+                                            void* stream) {
+  MIO_CHECK(k_stride != nullptr && v_stride != nullptr, "mio_reshape_and_cache_varlen: null strides");
+  MIO_CHECK(B >= 0 && total_new >= 0 && Hkv > 0 && D >= 8 && D % 8 == 0, "mio_reshape_and_cache_varlen: bad sizes");
+  MIO_CHECK(num_blocks > 0 && num_layers > 0 && layer_idx >= 0 && layer_idx < num_layers && block_size > 0 &&
+                max_blocks_per_seq > 0,
+            "mio_reshape_and_cache_varlen: bad cache geometry");
+  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_reshape_and_cache_varlen: dtype must be bf16 or fp16");
+  if (B == 0 || total_new == 0) return 0;
+  MIO_CHECK(key && value && k_cache && v_cache && block_tables && cu_seqlens_new && context_lengths,
+            "mio_reshape_and_cache_varlen: null pointer");
+  MIO_CHECK(k_stride[0] >= 0 && k_stride[1] >= 0 && v_stride[0] >= 0 && v_stride[1] >= 0 && k_stride[0] % 8 == 0 &&
+                k_stride[1] % 8 == 0 && v_stride[0] % 8 == 0 && v_stride[1] % 8 == 0 && mio_aligned16(key) &&
+                mio_aligned16(value) && mio_aligned16(k_cache) && mio_aligned16(v_cache),
+            "mio_reshape_and_cache_varlen: 16-byte alignment");
+  const int64_t blocks = ((int64_t)total_new * Hkv * (D / 8) + 255) / 256;
+  MIO_CHECK(blocks <= 0x7fffffff, "mio_reshape_and_cache_varlen: too many tokens");
+  hipLaunchKernelGGL(reshape_and_cache_varlen_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                     (const uint16_t*)key, (const uint16_t*)value, (uint16_t*)k_cache, (uint16_t*)v_cache, block_tables,
+                     cu_seqlens_new, context_lengths, k_stride[0], k_stride[1], v_stride[0], v_stride[1], B, total_new,
+                     Hkv, D, num_blocks, num_layers, layer_idx, block_size, max_blocks_per_seq);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return mio_fail(std::string("reshape_and_cache_varlen launch: ") + hipGetErrorString(e));
+  return 0;
+}

@@ -1,8 +1,10 @@
 // C-ABI entry point mio_fa3_fwd: argument validation + dispatch (see include/mio_hip.h).
+#include <algorithm>
 #include <cmath>
 
 #include "fa3_fwd_kernel.h"
 #include "fa3_route.h"
+#include "fa3_paged.h"
 #include "fa3_varlen.h"
 
 extern template int fa3_launch<__bf16, 64>(const FaDev&, int, int, hipStream_t);
@@ -17,6 +19,12 @@ extern template int fa3_varlen_launch<__bf16, 128>(const FaDev&, const FaVarlen&
 extern template int fa3_varlen_launch<_Float16, 64>(const FaDev&, const FaVarlen&, int, hipStream_t);
 extern template int fa3_varlen_launch<_Float16, 96>(const FaDev&, const FaVarlen&, int, hipStream_t);
 extern template int fa3_varlen_launch<_Float16, 128>(const FaDev&, const FaVarlen&, int, hipStream_t);
+extern template int fa3_paged_launch<__bf16, 64>(const FaDev&, const FaPaged&, int, hipStream_t);
+extern template int fa3_paged_launch<__bf16, 96>(const FaDev&, const FaPaged&, int, hipStream_t);
+extern template int fa3_paged_launch<__bf16, 128>(const FaDev&, const FaPaged&, int, hipStream_t);
+extern template int fa3_paged_launch<_Float16, 64>(const FaDev&, const FaPaged&, int, hipStream_t);
+extern template int fa3_paged_launch<_Float16, 96>(const FaDev&, const FaPaged&, int, hipStream_t);
+extern template int fa3_paged_launch<_Float16, 128>(const FaDev&, const FaPaged&, int, hipStream_t);
 
 static bool strides_ok(const int64_t s[3]) { return (s[0] % 8 == 0) && (s[1] % 8 == 0) && (s[2] % 8 == 0); }
 
@@ -186,4 +194,78 @@ extern "C" int mio_fa3_fwd_varlen(const mio_fa3_varlen_params_t* a, void* stream
   if (dpad == 64) return fa3_varlen_launch<_Float16, 64>(p, vl, a->causal, st);
   if (dpad == 96) return fa3_varlen_launch<_Float16, 96>(p, vl, a->causal, st);
   return fa3_varlen_launch<_Float16, 128>(p, vl, a->causal, st);
+}
+
+// ---- attention forward over the paged KV cache (mio_fa3_fwd_paged)
+
+// every argument check of mio_fa3_fwd_paged (0 or -1 with the message set); mio_fa3_paged_route runs the same checks.
+// Nothing here reads device memory: sequence bounds, block indices and pages are clamped in the kernel (fa3_paged.h).
+static int fa3_paged_validate(const mio_fa3_paged_params_t* a) {
+  MIO_CHECK(a != nullptr, "mio_fa3_fwd_paged: null params");
+  MIO_CHECK(a->B >= 0 && a->total_q >= 0 && a->max_seqlen_q >= 0 && a->max_seqlen_k >= 0 && a->H > 0 && a->Hkv > 0,
+            "mio_fa3_fwd_paged: bad sizes");
+  MIO_CHECK(a->H % a->Hkv == 0, "mio_fa3_fwd_paged: H must be a multiple of Hkv");
+  MIO_CHECK(a->D >= 8 && a->D <= 128 && a->D % 8 == 0, "mio_fa3_fwd_paged: head_dim must be a multiple of 8 in [8,128]");
+  MIO_CHECK(a->dtype == MIO_BF16 || a->dtype == MIO_FP16, "mio_fa3_fwd_paged: dtype must be bf16 or fp16");
+  MIO_CHECK(a->softmax_scale > 0.f && std::isfinite(a->softmax_scale), "mio_fa3_fwd_paged: softmax_scale must be > 0");
+  MIO_CHECK(a->q && a->k_cache && a->v_cache && a->o, "mio_fa3_fwd_paged: q/k_cache/v_cache/o must be non-null");
+  MIO_CHECK(a->B == 0 || (a->cu_seqlens_q != nullptr && a->seqused_k != nullptr && a->block_tables != nullptr),
+            "mio_fa3_fwd_paged: cu_seqlens_q / seqused_k / block_tables must be non-null");
+  MIO_CHECK(a->num_blocks > 0 && a->num_layers > 0 && a->max_blocks_per_seq > 0, "mio_fa3_fwd_paged: bad cache geometry");
+  MIO_CHECK(a->layer_idx >= 0 && a->layer_idx < a->num_layers, "mio_fa3_fwd_paged: layer_idx must be in [0, num_layers)");
+  MIO_CHECK(a->block_size > 0 && a->block_size % 64 == 0,
+            "mio_fa3_fwd_paged: block_size must be a multiple of 64 (a 64-key tile may not span two pages)");
+  for (const int64_t* s : {a->q_stride, a->o_stride})
+    MIO_CHECK(s[0] >= 0 && s[1] >= 0 && s[0] % 8 == 0 && s[1] % 8 == 0,
+              "mio_fa3_fwd_paged: strides must be non-negative multiples of 8 elements (16-byte rows)");
+  MIO_CHECK(mio_aligned16(a->q) && mio_aligned16(a->k_cache) && mio_aligned16(a->v_cache) && mio_aligned16(a->o),
+            "mio_fa3_fwd_paged: pointers must be 16-byte aligned");
+  MIO_CHECK(a->total_q == 0 || a->max_seqlen_q >= 1, "mio_fa3_fwd_paged: max_seqlen_q must be >= 1 when total_q > 0");
+  // the kernels index the cache by a 32-bit row (page, layer, slot) and divide tile indices by a 31-bit reciprocal
+  MIO_CHECK((int64_t)a->num_blocks * a->num_layers * a->block_size < (1ll << 32),
+            "mio_fa3_fwd_paged: the cache must hold fewer than 2^32 token rows (num_blocks * num_layers * block_size)");
+  const int64_t tpb = a->block_size / 64;
+  MIO_CHECK((int64_t)a->max_blocks_per_seq * tpb * tpb < (1ll << 31),
+            "mio_fa3_fwd_paged: max_blocks_per_seq * (block_size / 64)^2 must be below 2^31");
+  return 0;
+}
+
+extern "C" int32_t mio_fa3_paged_route(const mio_fa3_paged_params_t* a) {
+  if (fa3_paged_validate(a) != 0) return MIO_FA3_PAGED_ROUTE_INVALID;
+  if (a->B == 0 || a->total_q == 0) return MIO_FA3_PAGED_ROUTE_EMPTY;
+  return dpad_of(a->D) == 64 ? MIO_FA3_PAGED_ROUTE_FWD5 : MIO_FA3_PAGED_ROUTE_FWD3;
+}
+
+extern "C" int mio_fa3_fwd_paged(const mio_fa3_paged_params_t* a, void* stream) {
+  if (fa3_paged_validate(a) != 0) return -1;
+  if (a->B == 0 || a->total_q == 0) return 0;
+
+  FaDev p = {};
+  p.q = a->q; p.k = a->k_cache; p.v = a->v_cache; p.o = a->o; p.lse = a->lse; p.o_acc = nullptr; p.mask = nullptr;
+  p.qs_s = a->q_stride[0]; p.qs_h = a->q_stride[1];
+  p.ks_s = p.vs_s = (int64_t)a->Hkv * a->D;  // the cache's token stride; pages and layers come from the walk
+  p.ks_h = p.vs_h = a->D;
+  p.os_s = a->o_stride[0]; p.os_h = a->o_stride[1];
+  p.B = a->B; p.H = a->H; p.Hkv = a->Hkv; p.D = a->D;
+  p.xcd_remap = ((a->B * a->H) % 8 == 0) ? 1 : 0;
+  p.scale_log2e = a->softmax_scale * FA_LOG2E;
+  FaPaged pg;
+  pg.cu_q = a->cu_seqlens_q; pg.seqused_k = a->seqused_k; pg.block_tables = a->block_tables;
+  pg.total_q = a->total_q; pg.max_q = a->max_seqlen_q;
+  pg.max_k = (int)std::min<int64_t>(a->max_seqlen_k, (int64_t)a->max_blocks_per_seq * a->block_size);
+  pg.num_blocks = a->num_blocks; pg.num_layers = a->num_layers; pg.layer = a->layer_idx;
+  pg.block_size = a->block_size; pg.max_blocks = a->max_blocks_per_seq;
+  pg.tpb = a->block_size / 64;
+  pg.tpb_magic = (uint32_t)(((1ull << 31) + pg.tpb - 1) / pg.tpb);
+
+  hipStream_t st = (hipStream_t)stream;
+  const int dpad = dpad_of(a->D);
+  if (a->dtype == MIO_BF16) {
+    if (dpad == 64) return fa3_paged_launch<__bf16, 64>(p, pg, a->causal, st);
+    if (dpad == 96) return fa3_paged_launch<__bf16, 96>(p, pg, a->causal, st);
+    return fa3_paged_launch<__bf16, 128>(p, pg, a->causal, st);
+  }
+  if (dpad == 64) return fa3_paged_launch<_Float16, 64>(p, pg, a->causal, st);
+  if (dpad == 96) return fa3_paged_launch<_Float16, 96>(p, pg, a->causal, st);
+  return fa3_paged_launch<_Float16, 128>(p, pg, a->causal, st);
 }

@@ -1,6 +1,8 @@
-// Body of fa3_fwd3_kernel and fa3_fwd3_varlen_kernel (fa3_fwd3_kernel.h), included inside each: T, D, CAUSAL, STAMP, ABL,
-// KPRE and the FaDev `p` come from the including kernel, FA_LSE_INDEX(b, head, row) is the element of lse that query row
-// `row` of (batch b, head) owns.
+// Body of fa3_fwd3_kernel, fa3_fwd3_varlen_kernel (fa3_fwd3_kernel.h) and fa3_fwd3_paged_kernel (fa3_paged.h), included
+// inside each: T, D, CAUSAL, STAMP, ABL, KPRE and the FaDev `p` come from the including kernel, FA_LSE_INDEX(b, head, row)
+// is the element of lse that query row `row` of (batch b, head) owns, FA_KV_TILE(tile, kb, vb) sets kb / vb to the scalar
+// addresses of the first K / V row of this pass' KV tile `tile` (for this lane's head; the per-lane DMA offsets are added
+// to them).
   using X8 = typename DT<T>::x8;
   using X4 = typename DT<T>::x4;
   using OPS = Fa3Ops<T>;
@@ -175,13 +177,7 @@
     uint32_t dma_lds = 0;          // LDS address of this wave's first unit in the stage being filled
     auto dma_tile_base = [&](int tile_) {
       const int tile = tile_ < n_tiles_dma ? tile_ : n_tiles_dma - 1;
-      const int kv0 = tile * FA_BN;
-      // (32-bit offsets: the launcher sends sequences whose K / V rows span 4 GiB or more to fa3_fwd_kernel; 8
-      //  scalar instructions per 64-bit multiply-add otherwise, and scalar instructions are issue time here)
-      const uint32_t ko = __builtin_amdgcn_readfirstlane((uint32_t)kv0 * (uint32_t)ks2);
-      const uint32_t vo = __builtin_amdgcn_readfirstlane((uint32_t)kv0 * (uint32_t)vs2);
-      dma_kb = (const char*)kbase + ko;
-      dma_vb = (const char*)vbase + vo;
+      FA_KV_TILE(tile, dma_kb, dma_vb);
       dma_is_last = (tile == last_tile);
       dma_lds = (uint32_t)(size_t)((MIO_LDS char*)(smem + (tile_ & (FA3_STAGES - 1)) * SM::STAGE)) + 1024 * wave;
     };

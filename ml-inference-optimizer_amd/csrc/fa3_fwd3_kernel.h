@@ -227,9 +227,11 @@ struct Fa3Margin<_Float16> { static constexpr float value = 2.0f; };
 
 template <typename T, int D, bool CAUSAL, bool STAMP = false, int ABL = 0, bool KPRE = false>
 __global__ __launch_bounds__(256) void fa3_fwd3_kernel(const FaDev p) {
+#define FA_KV_TILE FA_KV_TILE_STRIDED
 #define FA_LSE_INDEX(b, head, row) (((int64_t)(b) * p.H + (head)) * p.Sq + (row))
 #include "fa3_fwd3_body.inc"
 #undef FA_LSE_INDEX
+#undef FA_KV_TILE
 }
 
 // packed variable-length form (mio_fa3_fwd_varlen, fa3_varlen.h), plain K and output: the dense body on this workgroup's
@@ -240,7 +242,9 @@ __global__ __launch_bounds__(256) void fa3_fwd3_varlen_kernel(const FaDev pl, co
   constexpr int ABL = 0;
   FaDev p = pl;
   if (!fa_varlen_prepare<FA3_BM, 256, CAUSAL>(p, vl)) return;
+#define FA_KV_TILE FA_KV_TILE_STRIDED
 #define FA_LSE_INDEX(b, head, row) ((int64_t)(head) * vl.total_q + (row))
 #include "fa3_fwd3_body.inc"
 #undef FA_LSE_INDEX
+#undef FA_KV_TILE
 }

@@ -1,6 +1,8 @@
-// Body of fa3_fwd5_kernel and fa3_fwd5_varlen_kernel (fa3_fwd5_kernel.h), included inside each: T, CAUSAL, STAMP, ABL, CARRY,
-// OBLK, KPRE and the FaDev `p` come from the including kernel, FA_LSE_INDEX(b, head, row) is the element of lse that query row
-// `row` of (batch b, head) owns.
+// Body of fa3_fwd5_kernel, fa3_fwd5_varlen_kernel (fa3_fwd5_kernel.h) and fa3_fwd5_paged_kernel (fa3_paged.h), included
+// inside each: T, CAUSAL, STAMP, ABL, CARRY, OBLK, KPRE and the FaDev `p` come from the including kernel,
+// FA_LSE_INDEX(b, head, row) is the element of lse that query row `row` of (batch b, head) owns, FA_KV_TILE(tile, kb, vb)
+// sets kb / vb to the scalar addresses of the first K / V row of this pass' KV tile `tile` (for this lane's head; the
+// per-lane DMA offsets are added to them).
   using X8 = typename DT<T>::x8;
   using X4 = typename DT<T>::x4;
   constexpr int NKT = 4, NQG = 2, NDS = 2, NDT = 4, NS = 2;
@@ -152,10 +154,9 @@
       int tile = tile_ - tbase;
       if (tile >= n_tiles) tile = (tile - n_tiles < n_tiles_next) ? tile - n_tiles : -1;  // the next pass' tile, or none
       if (tile < 0) return;
-      const uint32_t ko = __builtin_amdgcn_readfirstlane((uint32_t)(tile * FA_BN) * (uint32_t)ks2);
-      const uint32_t vo = __builtin_amdgcn_readfirstlane((uint32_t)(tile * FA_BN) * (uint32_t)vs2);
-      const char* kb = (const char*)kbase + ko;
-      const char* vb = (const char*)vbase + vo;
+      const char* kb;
+      const char* vb;
+      FA_KV_TILE(tile, kb, vb);
       const bool lastt = (tile == last_tile);
       const uint32_t lds = (uint32_t)(size_t)((MIO_LDS char*)(smem + (tile_ & (FA5_STAGES - 1)) * FA5_STAGE)) + 1024 * wave;
       const int ok_ = lastt ? offkl : offk, ov_ = lastt ? offvl : offv;

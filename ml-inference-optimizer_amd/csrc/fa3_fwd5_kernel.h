@@ -70,9 +70,11 @@ struct Fa5Margin<_Float16> { static constexpr float value = 2.0f; };  // fp16: k
 // pre-scaled form, no extra rounding of Q or K).
 template <typename T, bool CAUSAL, bool STAMP = false, int ABL = 0, bool CARRY = false, bool OBLK = false, bool KPRE = true>  // ABL: timing-only ablations (diagnostic build)
 __global__ __launch_bounds__(512) void fa3_fwd5_kernel(const FaDev p) {
+#define FA_KV_TILE FA_KV_TILE_STRIDED
 #define FA_LSE_INDEX(b, head, row) (((int64_t)(b) * p.H + (head)) * p.Sq + (row))
 #include "fa3_fwd5_body.inc"
 #undef FA_LSE_INDEX
+#undef FA_KV_TILE
 }
 
 // packed variable-length form (mio_fa3_fwd_varlen, fa3_varlen.h), plain K and output: the dense body on this workgroup's
@@ -83,7 +85,9 @@ __global__ __launch_bounds__(512) void fa3_fwd5_varlen_kernel(const FaDev pl, co
   constexpr int ABL = 0;
   FaDev p = pl;
   if (!fa_varlen_prepare<FA5_BM, 512, CAUSAL>(p, vl)) return;
+#define FA_KV_TILE FA_KV_TILE_STRIDED
 #define FA_LSE_INDEX(b, head, row) ((int64_t)(head) * vl.total_q + (row))
 #include "fa3_fwd5_body.inc"
 #undef FA_LSE_INDEX
+#undef FA_KV_TILE
 }

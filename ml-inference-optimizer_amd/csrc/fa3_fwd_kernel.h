@@ -53,6 +53,17 @@ constexpr float FA_NEG_FILL_LOG2 = -1.0e9f * FA_LOG2E;
 constexpr float FA_RESCALE_THR = 6.0f;  // exp2 domain: P <= 64 between rescales
 constexpr float FA_ADD_MASK_FLOOR = -1.0e30f;  // MIO_MASK_ADD_F32 entries below count as this (finite after * log2(e))
 
+// FA_KV_TILE of the pipelined bodies (fa3_fwd5_body.inc, fa3_fwd3_body.inc) for K / V rows at a fixed stride from kbase /
+// vbase: the dense and varlen kernels.  32-bit offsets: the launchers send sequences whose K / V rows span 4 GiB or more to
+// fa3_fwd_kernel; 8 scalar instructions per 64-bit multiply-add otherwise, and scalar instructions are issue time in fwd3.
+#define FA_KV_TILE_STRIDED(tile, kb, vb)                                                               \
+  do {                                                                                                 \
+    const uint32_t ko = __builtin_amdgcn_readfirstlane((uint32_t)((tile) * FA_BN) * (uint32_t)ks2); \
+    const uint32_t vo = __builtin_amdgcn_readfirstlane((uint32_t)((tile) * FA_BN) * (uint32_t)vs2); \
+    kb = (const char*)kbase + ko;                                                                      \
+    vb = (const char*)vbase + vo;                                                                      \
+  } while (0)
+
 template <int D>
 struct FaSmem {
   static constexpr int KROW = D * 2 + 16;       // bytes per K row (padded)

@@ -47,11 +47,13 @@ __device__ __forceinline__ FaSeq fa_varlen_seq(const FaVarlen& v, int b) {
   return s;
 }
 
+__device__ __forceinline__ FaSeq fa_seq_of(const FaVarlen& v, int b) { return fa_varlen_seq(v, b); }
+
 // A sequence with no keys: o = 0 and lse = -inf for the rows of query blocks blk0 and blk1 (blk1 < 0: none) that lie below
 // Lq.  No K / V load, no barrier -- the pipelined prologue fetches its
 // first tile before it looks at the tile count.
-template <int BM, int NT>
-__device__ __forceinline__ void fa_varlen_write_empty(const FaDev& p, const FaVarlen& v, const FaSeq& s, int head, int blk0,
+template <int BM, int NT, typename V>
+__device__ __forceinline__ void fa_varlen_write_empty(const FaDev& p, const V& v, const FaSeq& s, int head, int blk0,
                                                       int blk1) {
   // No lane-dependent branch: lanes past the rows store the same value to the sequence's last row (Lq >= 1 here).  A branch
   // on the lane makes the compiler treat what follows the join as divergent, and the pipelined body behind this needs its
@@ -75,11 +77,13 @@ __device__ __forceinline__ void fa_varlen_write_empty(const FaDev& p, const FaVa
   }
 }
 
-// Turns the launch's FaDev into this workgroup's dense problem (one sequence, p.B and the grid fields unchanged).  Returns
-// false when the workgroup has nothing (more) to do: no query block of its sequence, or a sequence without keys (its rows
-// are written here).  Every wave of the workgroup takes the same exit.
-template <int BM, int NT, bool CAUSAL>
-__device__ __forceinline__ bool fa_varlen_prepare(FaDev& p, const FaVarlen& v) {
+// Turns the launch's FaDev into this workgroup's dense problem (one sequence, p.B and the grid fields unchanged).  V is the
+// launch's sequence description (FaVarlen, FaPaged in fa3_paged.h): fa_seq_of(v, b) gives batch entry b's FaSeq (clamped),
+// v.total_q is the packed row count (the lse row stride); b_out receives the workgroup's batch entry.  Returns false when
+// the workgroup has nothing (more) to do: no query block of its sequence, or a sequence without keys (its rows are written
+// here).  Every wave of the workgroup takes the same exit.
+template <int BM, int NT, bool CAUSAL, typename V>
+__device__ __forceinline__ bool fa_seq_prepare(FaDev& p, const V& v, int& b_out) {
   int bh, qi;
   {  // the dense kernels' workgroup -> (batch, head, query block) map
     const int id = blockIdx.x;
@@ -93,7 +97,8 @@ __device__ __forceinline__ bool fa_varlen_prepare(FaDev& p, const FaVarlen& v) {
     }
   }
   const int b = bh / p.H, head = bh % p.H;
-  const FaSeq s = fa_varlen_seq(v, b);
+  b_out = b;
+  const FaSeq s = fa_seq_of(v, b);
   const int nqblk = (s.Lq + BM - 1) / BM;
   if (qi >= (CAUSAL ? (nqblk + 1) / 2 : nqblk)) return false;
   if (s.Lk == 0) {
@@ -114,6 +119,12 @@ __device__ __forceinline__ bool fa_varlen_prepare(FaDev& p, const FaVarlen& v) {
   p.k_offset = 0;
   p.nqblk = nqblk;
   return true;
+}
+
+template <int BM, int NT, bool CAUSAL>
+__device__ __forceinline__ bool fa_varlen_prepare(FaDev& p, const FaVarlen& v) {
+  int b;
+  return fa_seq_prepare<BM, NT, CAUSAL>(p, v, b);
 }
 
 // Host launcher for one (dtype, padded D); defined per translation unit (fa3_varlen_inst.hip).  p carries the launch's

@@ -41,6 +41,12 @@ FA3_VARLEN_ROUTES = {
     1: "fwd5",
     2: "fwd3",
 }
+# mio_fa3_paged_route_t: the kernel mio_fa3_fwd_paged launches
+FA3_PAGED_ROUTES = {
+    0: "empty",
+    1: "fwd5",
+    2: "fwd3",
+}
 
 # every symbol include/mio_hip.h declares
 EXPORTS = (
@@ -52,6 +58,8 @@ EXPORTS = (
     "mio_fa3_route",
     "mio_fa3_fwd_varlen",
     "mio_fa3_varlen_route",
+    "mio_fa3_fwd_paged",
+    "mio_fa3_paged_route",
     "mio_attn_merge",
     "mio_gemm_bias_act",
     "mio_fused_mlp_workspace_bytes",
@@ -77,6 +85,7 @@ EXPORTS = (
     "mio_fa3_decode_workspace_bytes",
     "mio_fa3_decode_paged",
     "mio_reshape_and_cache",
+    "mio_reshape_and_cache_varlen",
 )
 
 
@@ -143,6 +152,38 @@ class FaVarlenParams(C.Structure):
     ]
 
 
+class FaPagedParams(C.Structure):
+    """mio_fa3_paged_params_t"""
+
+    _fields_ = [
+        ("q", C.c_void_p),
+        ("k_cache", C.c_void_p),
+        ("v_cache", C.c_void_p),
+        ("o", C.c_void_p),
+        ("lse", C.c_void_p),
+        ("cu_seqlens_q", C.c_void_p),
+        ("seqused_k", C.c_void_p),
+        ("block_tables", C.c_void_p),
+        ("q_stride", C.c_int64 * 2),
+        ("o_stride", C.c_int64 * 2),
+        ("B", C.c_int32),
+        ("total_q", C.c_int32),
+        ("max_seqlen_q", C.c_int32),
+        ("max_seqlen_k", C.c_int32),
+        ("H", C.c_int32),
+        ("Hkv", C.c_int32),
+        ("D", C.c_int32),
+        ("num_blocks", C.c_int32),
+        ("num_layers", C.c_int32),
+        ("layer_idx", C.c_int32),
+        ("block_size", C.c_int32),
+        ("max_blocks_per_seq", C.c_int32),
+        ("dtype", C.c_int32),
+        ("causal", C.c_int32),
+        ("softmax_scale", C.c_float),
+    ]
+
+
 def _load() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -168,6 +209,10 @@ def _load() -> C.CDLL:
     lib.mio_fa3_fwd_varlen.restype = i32
     lib.mio_fa3_varlen_route.argtypes = [C.POINTER(FaVarlenParams)]
     lib.mio_fa3_varlen_route.restype = i32
+    lib.mio_fa3_fwd_paged.argtypes = [C.POINTER(FaPagedParams), vp]
+    lib.mio_fa3_fwd_paged.restype = i32
+    lib.mio_fa3_paged_route.argtypes = [C.POINTER(FaPagedParams)]
+    lib.mio_fa3_paged_route.restype = i32
     lib.mio_attn_merge.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mio_attn_merge.restype = i32
     lib.mio_gemm_bias_act.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
@@ -220,6 +265,9 @@ def _load() -> C.CDLL:
     lib.mio_reshape_and_cache.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32, i32, i32,
                                           i32, i32, i32, i32, vp]
     lib.mio_reshape_and_cache.restype = i32
+    lib.mio_reshape_and_cache_varlen.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32,
+                                                 i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.mio_reshape_and_cache_varlen.restype = i32
     return lib
 
 

@@ -842,6 +842,123 @@ def layernorm(x, weight, bias=None, eps: float = 1e-5, residual=None, residual_a
 # ------------------------------------------------------------------------------------------------
 # paged decode
 # ------------------------------------------------------------------------------------------------
+def _i32_dev(t: torch.Tensor, name: str, dim: int, what: str, device) -> None:
+    if t.dtype != torch.int32 or t.dim() != dim or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dim}-D int32 tensor {what}")
+    if t.device != device:
+        raise ValueError(f"{name} must be on the device of q")
+
+
+def _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q, max_seqlen_k, layer_idx=0,
+                  causal=False, softmax_scale=None, return_lse=False, out=None):
+    """flash_attention_varlen_paged's argument checks and mio_fa3_paged_params_t; returns (params, out, lse, keep) as
+    _varlen_params does.  Reads no device memory."""
+    if q.dim() != 3:
+        raise ValueError(f"Expected a 3D tensor [tokens, heads, head_dim] for q but got shape {q.shape}")
+    if k_cache.dim() != 5 or v_cache.shape != k_cache.shape:
+        raise ValueError("caches must be [num_blocks, num_layers, block_size, num_kv_heads, head_dim] with equal shapes")
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise ValueError("q, k_cache, v_cache must have the same dtype")
+    dt = _dtype_id(q)
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("caches must be contiguous")
+    _i32_dev(cu_seqlens_q, "cu_seqlens_q", 1, "of B+1 offsets", q.device)
+    if cu_seqlens_q.numel() < 1:
+        raise ValueError("cu_seqlens_q must be a contiguous 1-D int32 tensor of B+1 offsets")
+    B = cu_seqlens_q.numel() - 1
+    _i32_dev(seqused_k, "seqused_k", 1, "of B key counts", q.device)
+    _i32_dev(block_tables, "block_tables", 2, "[B, max_blocks_per_seq]", q.device)
+    if seqused_k.numel() != B or block_tables.shape[0] != B:
+        raise ValueError(f"seqused_k and block_tables must have B = {B} rows (cu_seqlens_q has B+1 entries)")
+    q = _rows16(q)
+    Tq, H, D = q.shape
+    nb, L, bs, Hkv, Dc = k_cache.shape
+    if Dc != D:
+        raise ValueError(f"incompatible q/cache shapes: q={q.shape}, k_cache={k_cache.shape}")
+    if H % Hkv != 0:
+        raise ValueError(f"num_heads {H} must be a multiple of num_kv_heads {Hkv}")
+    if D % 8 != 0 or D > 128:
+        raise ValueError(f"head_dim must be a multiple of 8 and <= 128, got {D}")
+    if bs % 64 != 0:
+        raise ValueError(f"block_size must be a multiple of 64 for the paged attention kernels, got {bs}")
+    if not 0 <= int(layer_idx) < L:
+        raise ValueError(f"layer_idx {layer_idx} out of range for a {L}-layer cache")
+    scale = (1.0 / math.sqrt(D)) if softmax_scale is None else float(softmax_scale)
+    if not (scale > 0.0):
+        raise ValueError("softmax_scale must be positive")
+    if out is None:
+        out = torch.empty_like(q, memory_format=torch.contiguous_format)
+    elif out.shape != q.shape or out.dtype != q.dtype or out.stride(-1) != 1:
+        raise ValueError("out must match q in shape/dtype with a contiguous last dim")
+    lse = torch.empty(H, Tq, dtype=torch.float32, device=q.device) if return_lse else None
+
+    p = _lib.FaPagedParams()
+    for dst, t in ((p.q_stride, q), (p.o_stride, out)):
+        dst[0], dst[1] = t.stride(0), t.stride(1)
+    p.q, p.k_cache, p.v_cache, p.o, p.lse = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), _ptr(lse)
+    # torch gives empty tensors a null address; nothing is read or written through them then (include/mio_hip.h)
+    for f in ("q", "k_cache", "v_cache", "o"):
+        if not getattr(p, f):
+            setattr(p, f, cu_seqlens_q.data_ptr())
+    p.cu_seqlens_q, p.seqused_k, p.block_tables = cu_seqlens_q.data_ptr(), seqused_k.data_ptr(), block_tables.data_ptr()
+    p.B, p.total_q = B, Tq
+    p.max_seqlen_q, p.max_seqlen_k = int(max_seqlen_q), int(max_seqlen_k)
+    p.H, p.Hkv, p.D = H, Hkv, D
+    p.num_blocks, p.num_layers, p.layer_idx, p.block_size = nb, L, int(layer_idx), bs
+    p.max_blocks_per_seq = block_tables.shape[1]
+    p.dtype, p.causal, p.softmax_scale = dt, int(bool(causal)), scale
+    return p, out, lse, (q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k)
+
+
+def flash_attention_varlen_paged(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    block_tables: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    seqused_k: torch.Tensor,
+    max_seqlen_q: int,
+    max_seqlen_k: int,
+    layer_idx: int = 0,
+    causal: bool = False,
+    softmax_scale: Optional[float] = None,
+    return_lse: bool = False,
+    out: Optional[torch.Tensor] = None,
+):
+    """Packed variable-length attention forward over the paged KV cache (chunked prefill), mio_fa3_fwd_paged.
+
+    q [total_q, H, D] packed by cu_seqlens_q (int32 [B+1]) as in flash_attention_varlen.  k_cache / v_cache
+    [num_blocks, num_layers, block_size, Hkv, D] contiguous (PagedKVCache's layout), read at layer_idx; block_size must
+    be a multiple of 64.  Sequence b attends keys 0 .. min(seqused_k[b], max_seqlen_k) - 1, key j in page
+    block_tables[b, j // block_size] (int32 [B, max_blocks_per_seq]) at slot j % block_size.  causal is bottom-right
+    aligned: query i of a sequence sees key j iff j <= i + Lk - Lq.  Rows with no visible key get 0 (lse -inf).
+    Returns out [total_q, H, D] or (out, lse fp32 [H, total_q]) if return_lse.  Queued on the current stream with no host
+    sync (graph-capturable): the offsets and tables are never read on the host.
+    """
+    _need_cuda(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k)
+    p, out, lse, _keep = _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
+                                       max_seqlen_k, layer_idx=layer_idx, causal=causal, softmax_scale=softmax_scale,
+                                       return_lse=return_lse, out=out)
+    check(lib.mio_fa3_fwd_paged(C.byref(p), _stream()))
+    if return_lse:
+        return out, lse
+    return out
+
+
+def fa3_paged_route(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
+                    cu_seqlens_q: torch.Tensor, seqused_k: torch.Tensor, max_seqlen_q: int, max_seqlen_k: int,
+                    **kwargs) -> str:
+    """The kernel flash_attention_varlen_paged(...) would launch (mio_fa3_paged_route): "empty", "fwd5" or "fwd3",
+    without launching.  Tensors may live on any device; arguments flash_attention_varlen_paged refuses raise the same
+    errors."""
+    p, _out, _lse, _keep = _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
+                                         max_seqlen_k, **kwargs)
+    r = lib.mio_fa3_paged_route(C.byref(p))
+    if r < 0:
+        raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
+    return _lib.FA3_PAGED_ROUTES[r]
+
+
 def paged_attention_forward(query, output, k_cache, v_cache, block_tables, context_lengths, block_size: int,
                             max_seq_len: int, layer_idx: int, scale: Optional[float] = None) -> torch.Tensor:
     """Drop-in for triton_paged_attention_forward (attention_kernels.py:1206-1311).
@@ -895,6 +1012,50 @@ def reshape_and_cache(key, value, k_cache, v_cache, block_tables, context_length
     check(lib.mio_reshape_and_cache(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                                     bt.data_ptr(), cl.data_ptr(), ks, vs, B, Hkv, D, L, int(layer_idx), bs,
                                     bt.shape[1], dt, _stream()))
+
+
+def reshape_and_cache_varlen(key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths,
+                             block_size: int, layer_idx: int):
+    """Write many new tokens per sequence into the paged cache (mio_reshape_and_cache_varlen).
+
+    key / value [total_new, Hkv, D] packed by cu_seqlens_new (int32 [B+1]); context_lengths (int32 [B]) holds each
+    sequence's length AFTER the append, so token i of the n_b new ones goes to position context_lengths[b] - n_b + i of
+    the pages in block_tables (int32 [B, max_blocks_per_seq]).  Positions that are negative or past the table row are
+    skipped.  Byte-exact copies, queued on the current stream with no host sync (graph-capturable)."""
+    _need_cuda(key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths)
+    if key.dim() != 3 or value.shape != key.shape:
+        raise ValueError(f"key/value must be [total_new, num_kv_heads, head_dim] with equal shapes, got "
+                         f"key={tuple(key.shape)}, value={tuple(value.shape)}")
+    dt = _dtype_id(key)
+    if value.dtype != key.dtype or k_cache.dtype != key.dtype or v_cache.dtype != key.dtype:
+        raise ValueError("key, value and caches must share a dtype")
+    if k_cache.dim() != 5 or v_cache.shape != k_cache.shape:
+        raise ValueError("caches must be [num_blocks, num_layers, block_size, num_kv_heads, head_dim] with equal shapes")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("caches must be contiguous")
+    T, Hkv, D = key.shape
+    nb, L, bs, Hc, Dc = k_cache.shape
+    if (Hc, Dc, bs) != (Hkv, D, block_size):
+        raise ValueError("cache geometry mismatch")
+    if D % 8 != 0:
+        raise ValueError(f"head_dim must be a multiple of 8, got {D}")
+    if not 0 <= int(layer_idx) < L:
+        raise ValueError(f"layer_idx {layer_idx} out of range for a {L}-layer cache")
+    _i32_dev(cu_seqlens_new, "cu_seqlens_new", 1, "of B+1 offsets", key.device)
+    if cu_seqlens_new.numel() < 1:
+        raise ValueError("cu_seqlens_new must be a contiguous 1-D int32 tensor of B+1 offsets")
+    B = cu_seqlens_new.numel() - 1
+    _i32_dev(context_lengths, "context_lengths", 1, "of B lengths", key.device)
+    _i32_dev(block_tables, "block_tables", 2, "[B, max_blocks_per_seq]", key.device)
+    if context_lengths.numel() != B or block_tables.shape[0] != B:
+        raise ValueError(f"context_lengths and block_tables must have B = {B} rows (cu_seqlens_new has B+1 entries)")
+    key, value = _rows16(key), _rows16(value)
+    ks = (C.c_int64 * 2)(key.stride(0), key.stride(1))
+    vs = (C.c_int64 * 2)(value.stride(0), value.stride(1))
+    check(lib.mio_reshape_and_cache_varlen(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                           block_tables.data_ptr(), cu_seqlens_new.data_ptr(),
+                                           context_lengths.data_ptr(), ks, vs, B, T, Hkv, D, nb, L, int(layer_idx),
+                                           bs, block_tables.shape[1], dt, _stream()))
 
 
 # ------------------------------------------------------------------------------------------------

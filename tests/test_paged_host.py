@@ -1,0 +1,222 @@
+"""CPU-only tests of the attention forward over the paged KV cache (mio_fa3_fwd_paged) and of the many-token cache write
+(mio_reshape_and_cache_varlen): the C-ABI symbols are bound, the route table and every refusal are reported without a GPU,
+ops raises on bad arguments before it calls the library, and the paged kernels pass the ISA soundness checks of the dense
+pipelined kernels."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ml-inference-optimizer_amd", "csrc")
+ALIGNED = 1 << 20  # a fake 16-byte aligned device address: nothing is dereferenced by the route query
+
+
+def _params(B=3, total_q=600, max_q=300, max_k=1000, H=4, Hkv=4, D=64, dtype=0, causal=1, tables=True, num_blocks=64,
+            num_layers=2, layer_idx=0, block_size=64, max_blocks=16, tok_stride=None, head_stride=None, ptr_off=0):
+    from mio import _lib
+    p = _lib.FaPagedParams()
+    p.q = ALIGNED + ptr_off
+    p.k_cache, p.v_cache, p.o = ALIGNED, ALIGNED, ALIGNED
+    p.cu_seqlens_q = p.seqused_k = p.block_tables = (ALIGNED if tables else None)
+    for st in (p.q_stride, p.o_stride):
+        st[0], st[1] = (H * D if tok_stride is None else tok_stride), (D if head_stride is None else head_stride)
+    p.B, p.total_q, p.max_seqlen_q, p.max_seqlen_k = B, total_q, max_q, max_k
+    p.H, p.Hkv, p.D, p.dtype, p.causal, p.softmax_scale = H, Hkv, D, dtype, causal, 0.125
+    p.num_blocks, p.num_layers, p.layer_idx, p.block_size, p.max_blocks_per_seq = (num_blocks, num_layers, layer_idx,
+                                                                                 block_size, max_blocks)
+    return p
+
+
+def _route(**kw):
+    from mio import _lib
+    r = _lib.lib.mio_fa3_paged_route(C.byref(_params(**kw)))
+    return _lib.FA3_PAGED_ROUTES.get(r) if r >= 0 else None
+
+
+def test_paged_symbols_bound():
+    from mio import _lib, ops
+    for name in ("mio_fa3_fwd_paged", "mio_fa3_paged_route", "mio_reshape_and_cache_varlen"):
+        assert name in _lib.EXPORTS and hasattr(_lib.lib, name)
+    assert _lib.lib.mio_fa3_paged_route.argtypes == [C.POINTER(_lib.FaPagedParams)]
+    assert _lib.lib.mio_fa3_fwd_paged.argtypes[0] == C.POINTER(_lib.FaPagedParams)
+    assert len(_lib.lib.mio_reshape_and_cache_varlen.argtypes) == 20
+    assert set(_lib.FA3_PAGED_ROUTES.values()) == {"empty", "fwd5", "fwd3"}
+    for f in ("flash_attention_varlen_paged", "fa3_paged_route", "reshape_and_cache_varlen"):
+        assert callable(getattr(ops, f))
+
+
+# (geometry, expected route or None = refused, substring of the error)
+_PAGED_TABLE = [
+    (dict(D=8), "fwd5", None),
+    (dict(D=32), "fwd5", None),
+    (dict(D=64), "fwd5", None),
+    (dict(D=72), "fwd3", None),
+    (dict(D=96), "fwd3", None),
+    (dict(D=128), "fwd3", None),
+    (dict(D=128, causal=0, dtype=1), "fwd3", None),
+    (dict(H=32, Hkv=4), "fwd5", None),
+    (dict(block_size=128), "fwd5", None),
+    (dict(block_size=256, D=128), "fwd3", None),
+    (dict(block_size=192), "fwd5", None),
+    (dict(layer_idx=1), "fwd5", None),
+    (dict(total_q=0, max_q=0), "empty", None),
+    (dict(B=0, tables=False), "empty", None),
+    (dict(max_k=0), "fwd5", None),                     # every sequence without keys: launched, writes the empty rows
+    (dict(block_size=16), None, b"multiple of 64"),
+    (dict(block_size=96), None, b"multiple of 64"),
+    (dict(block_size=0), None, b"multiple of 64"),
+    (dict(H=6, Hkv=4), None, b"multiple of Hkv"),
+    (dict(D=136), None, b"head_dim"),
+    (dict(D=60), None, b"head_dim"),
+    (dict(layer_idx=2), None, b"layer_idx"),
+    (dict(layer_idx=-1), None, b"layer_idx"),
+    (dict(tables=False), None, b"block_tables"),
+    (dict(num_blocks=0), None, b"cache geometry"),
+    (dict(num_blocks=-3), None, b"cache geometry"),
+    (dict(max_blocks=0), None, b"cache geometry"),
+    (dict(dtype=2), None, b"dtype"),
+    (dict(ptr_off=8), None, b"aligned"),
+    (dict(tok_stride=4 * 64 + 4), None, b"strides"),
+    (dict(head_stride=68), None, b"strides"),
+    (dict(max_q=0), None, b"max_seqlen_q"),
+    (dict(B=-1), None, b"sizes"),
+    # 32-bit cache rows: num_blocks * num_layers * block_size < 2^32
+    (dict(num_blocks=(1 << 31) // 64 - 1, num_layers=2), "fwd5", None),
+    (dict(num_blocks=(1 << 31) // 64, num_layers=2), None, b"2^32"),
+]
+
+
+@pytest.mark.parametrize("geom,want,err", _PAGED_TABLE)
+def test_paged_route_table_without_gpu(geom, want, err):
+    from mio import _lib
+    got = _route(**geom)
+    assert got == want, f"{geom}: route {got}, expected {want}"
+    if want is None:
+        assert err in _lib.lib.mio_last_error(), _lib.lib.mio_last_error()
+
+
+def _cache(nb=8, L=2, bs=64, Hkv=2, D=64, dtype=torch.bfloat16):
+    return torch.zeros(nb, L, bs, Hkv, D, dtype=dtype)
+
+
+def test_paged_argument_errors_without_gpu():
+    """mio_fa3_fwd_paged refuses what the route query refuses, before any launch; ops raises before it calls the library."""
+    from mio import _lib, ops
+    assert _lib.lib.mio_fa3_fwd_paged(None, None) != 0 and b"null" in _lib.lib.mio_last_error()
+    assert _lib.lib.mio_fa3_paged_route(None) < 0
+    assert _lib.lib.mio_fa3_fwd_paged(C.byref(_params(block_size=32)), None) != 0
+    assert b"multiple of 64" in _lib.lib.mio_last_error()
+    assert _lib.lib.mio_fa3_fwd_paged(C.byref(_params(tables=False)), None) != 0
+    assert _lib.lib.mio_fa3_fwd_paged(C.byref(_params(total_q=0, max_q=0)), None) == 0  # nothing to do: no launch
+
+    q = torch.zeros(600, 4, 64, dtype=torch.bfloat16)
+    kc, vc = _cache(), _cache()
+    bt = torch.zeros(2, 8, dtype=torch.int32)
+    cu = torch.tensor([0, 300, 600], dtype=torch.int32)
+    used = torch.tensor([400, 512], dtype=torch.int32)
+    assert ops.fa3_paged_route(q, kc, vc, bt, cu, used, 300, 512, causal=True) == "fwd5"
+    assert ops.fa3_paged_route(q, kc, vc, bt, cu, used, 300, 512, layer_idx=1) == "fwd5"
+    kc128 = _cache(bs=128, D=128, dtype=torch.float16)
+    assert ops.fa3_paged_route(torch.zeros(600, 8, 128, dtype=torch.float16), kc128, kc128, bt, cu, used, 300,
+                               512) == "fwd3"
+    assert ops.fa3_paged_route(q[:0], kc, vc, bt[:0], cu[:1], used[:0], 0, 512) == "empty"
+    with pytest.raises(ValueError):  # CPU tensors: no fallback
+        ops.flash_attention_varlen_paged(q, kc, vc, bt, cu, used, 300, 512)
+    with pytest.raises(ValueError, match="multiple of 64"):
+        ops.fa3_paged_route(q, _cache(bs=16), _cache(bs=16), bt, cu, used, 300, 512)
+    with pytest.raises(ValueError, match="layer_idx"):
+        ops.fa3_paged_route(q, kc, vc, bt, cu, used, 300, 512, layer_idx=2)
+    with pytest.raises(ValueError, match="multiple of num_kv_heads"):
+        ops.fa3_paged_route(torch.zeros(600, 3, 64, dtype=torch.bfloat16), kc, vc, bt, cu, used, 300, 512)
+    with pytest.raises(ValueError, match="head_dim"):
+        ops.fa3_paged_route(q[:, :, :60], _cache(D=60), _cache(D=60), bt, cu, used, 300, 512)
+    with pytest.raises(ValueError):
+        ops.fa3_paged_route(q, kc, vc, bt.long(), cu, used, 300, 512)
+    with pytest.raises(ValueError):
+        ops.fa3_paged_route(q, kc, vc, bt, cu.long(), used, 300, 512)
+    with pytest.raises(ValueError):
+        ops.fa3_paged_route(q, kc, vc, bt, cu, used[:1], 300, 512)
+    with pytest.raises(ValueError):
+        ops.fa3_paged_route(q, kc, vc[:4], bt, cu, used, 300, 512)
+    with pytest.raises(ValueError):
+        ops.fa3_paged_route(q[None], kc, vc, bt, cu, used, 300, 512)
+    with pytest.raises(ValueError):
+        ops.fa3_paged_route(q.float(), kc.float(), vc.float(), bt, cu, used, 300, 512)
+    with pytest.raises(ValueError):
+        ops.fa3_paged_route(q, kc.transpose(3, 4), vc.transpose(3, 4), bt, cu, used, 300, 512)
+    with pytest.raises(RuntimeError):
+        ops.fa3_paged_route(q, kc, vc, bt, cu, used, 0, 512)
+
+
+def test_reshape_and_cache_varlen_errors_without_gpu():
+    from mio import _lib, ops
+    k = torch.zeros(10, 2, 64, dtype=torch.bfloat16)
+    kc, vc = _cache(), _cache()
+    bt = torch.zeros(2, 8, dtype=torch.int32)
+    cu = torch.tensor([0, 4, 10], dtype=torch.int32)
+    cl = torch.tensor([4, 6], dtype=torch.int32)
+    with pytest.raises(ValueError):  # CPU tensors: no fallback
+        ops.reshape_and_cache_varlen(k, k, kc, vc, bt, cu, cl, 64, 0)
+    ks = (C.c_int64 * 2)(128, 64)
+    f = _lib.lib.mio_reshape_and_cache_varlen
+    args = dict(B=2, T=10, Hkv=2, D=64, nb=8, L=2, layer=0, bs=64, mb=8, dt=0)
+
+    def call(**kw):
+        a = dict(args, **kw)
+        return f(ALIGNED, ALIGNED, ALIGNED, ALIGNED, ALIGNED, ALIGNED, ALIGNED, ks, ks, a["B"], a["T"], a["Hkv"], a["D"],
+                 a["nb"], a["L"], a["layer"], a["bs"], a["mb"], a["dt"], None)
+
+    assert call(layer=2) != 0 and b"geometry" in _lib.lib.mio_last_error()
+    assert call(nb=0) != 0 and b"geometry" in _lib.lib.mio_last_error()
+    assert call(D=60) != 0 and b"sizes" in _lib.lib.mio_last_error()
+    assert call(dt=3) != 0 and b"dtype" in _lib.lib.mio_last_error()
+    assert call(T=0) == 0 and call(B=0) == 0  # nothing to write: no launch
+
+
+def _isa(tmp_path, type_id, D):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    isa = tmp_path / f"paged_{type_id}_{D}.s"
+    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I../../include", "-I.", "-Wno-unused-value",
+                    "-Wno-inline-asm", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", f"-DFA_TYPE_ID={type_id}",
+                    f"-DFA_D={D}", "-S", "--cuda-device-only", "fa3_paged_inst.hip", "-o", str(isa)], cwd=CSRC, check=True,
+                   capture_output=True)
+    return isa.read_text()
+
+
+@pytest.mark.parametrize("type_id", [0, 1])
+def test_fwd5_paged_fits_without_spills(tmp_path, type_id):
+    """The paged form of fa3_fwd5_kernel runs two waves per SIMD like the dense one: no scratch, at most 256 VGPRs."""
+    text = _isa(tmp_path, type_id, 64)
+    blocks = re.findall(r"\.name:\s+_Z21fa3_fwd5_paged_kernel\w+\n(?:.*\n){0,12}", text)
+    assert len(blocks) == 2, "causal and full instantiations expected"
+    for blk in blocks:
+        assert re.search(r"\.private_segment_fixed_size:\s+0\b", blk), blk
+        assert re.search(r"\.vgpr_spill_count:\s+0\b", blk), blk
+        assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= 256, blk
+    assert "scratch_" not in text
+
+
+@pytest.mark.parametrize("type_id,D", [(0, 96), (1, 96), (0, 128), (1, 128)])
+def test_fwd3_paged_accumulator_registers_untouched_by_compiler(tmp_path, type_id, D):
+    """The paged form of fa3_fwd3_kernel owns the same accumulator registers (Fa3Map<D>::A_Q and up) through inline asm:
+    no compiler-generated instruction may touch them (tools/check_agpr.py), and nothing spills."""
+    text = _isa(tmp_path, type_id, D).splitlines()
+    starts = [i for i, l in enumerate(text) if re.match(r"^_Z21fa3_fwd3_paged_kernel\w+:", l)]
+    assert len(starts) == 2, "causal and full instantiations expected"
+    floor = 16 * (14 - 2 * (D // 32)) - 4 - 8 * (D // 16)  # Fa3Map<D>::A_Q
+    for a in starts:
+        b = next(i for i in range(a, len(text)) if "s_endpgm" in text[i])
+        part = tmp_path / "k.s"
+        part.write_text("\n".join(text[a:b + 1]))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_agpr.py"), str(part), str(floor)],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, text[a] + "\n" + r.stdout
+        assert not any("scratch_" in l for l in text[a:b + 1]), "register spills in " + text[a]
