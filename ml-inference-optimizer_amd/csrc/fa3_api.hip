@@ -1,32 +1,74 @@
-// C-ABI entry point mio_fa3_fwd: argument validation + dispatch (see include/mio_hip.h).
+// C-ABI entry points of the attention forward, dense (mio_fa3_fwd), packed varlen (mio_fa3_fwd_varlen) and paged
+// (mio_fa3_fwd_paged): argument validation + dispatch (see include/mio_hip.h).
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 
 #include "fa3_fwd_kernel.h"
 #include "fa3_route.h"
 #include "fa3_paged.h"
 #include "fa3_varlen.h"
 
-extern template int fa3_launch<__bf16, 64>(const FaDev&, int, int, hipStream_t);
-extern template int fa3_launch<__bf16, 96>(const FaDev&, int, int, hipStream_t);
-extern template int fa3_launch<__bf16, 128>(const FaDev&, int, int, hipStream_t);
-extern template int fa3_launch<_Float16, 64>(const FaDev&, int, int, hipStream_t);
-extern template int fa3_launch<_Float16, 96>(const FaDev&, int, int, hipStream_t);
-extern template int fa3_launch<_Float16, 128>(const FaDev&, int, int, hipStream_t);
-extern template int fa3_varlen_launch<__bf16, 64>(const FaDev&, const FaVarlen&, int, hipStream_t);
-extern template int fa3_varlen_launch<__bf16, 96>(const FaDev&, const FaVarlen&, int, hipStream_t);
-extern template int fa3_varlen_launch<__bf16, 128>(const FaDev&, const FaVarlen&, int, hipStream_t);
-extern template int fa3_varlen_launch<_Float16, 64>(const FaDev&, const FaVarlen&, int, hipStream_t);
-extern template int fa3_varlen_launch<_Float16, 96>(const FaDev&, const FaVarlen&, int, hipStream_t);
-extern template int fa3_varlen_launch<_Float16, 128>(const FaDev&, const FaVarlen&, int, hipStream_t);
-extern template int fa3_paged_launch<__bf16, 64>(const FaDev&, const FaPaged&, int, hipStream_t);
-extern template int fa3_paged_launch<__bf16, 96>(const FaDev&, const FaPaged&, int, hipStream_t);
-extern template int fa3_paged_launch<__bf16, 128>(const FaDev&, const FaPaged&, int, hipStream_t);
-extern template int fa3_paged_launch<_Float16, 64>(const FaDev&, const FaPaged&, int, hipStream_t);
-extern template int fa3_paged_launch<_Float16, 96>(const FaDev&, const FaPaged&, int, hipStream_t);
-extern template int fa3_paged_launch<_Float16, 128>(const FaDev&, const FaPaged&, int, hipStream_t);
-
 static bool strides_ok(const int64_t s[3]) { return (s[0] % 8 == 0) && (s[1] % 8 == 0) && (s[2] % 8 == 0); }
+
+static bool aligned16(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (!mio_aligned16(p)) return false;
+  return true;
+}
+
+// The checks all three entry points make alike, in this order; fn (the entry point's name) prefixes the messages.
+static int fa_check_common(const char* fn, int H, int Hkv, int D, int dtype, float softmax_scale) {
+  MIO_CHECK(H % Hkv == 0, std::string(fn) + ": H must be a multiple of Hkv");
+  MIO_CHECK(D >= 8 && D <= 128 && D % 8 == 0, std::string(fn) + ": head_dim must be a multiple of 8 in [8,128]");
+  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, std::string(fn) + ": dtype must be bf16 or fp16");
+  MIO_CHECK(softmax_scale > 0.f && std::isfinite(softmax_scale), std::string(fn) + ": softmax_scale must be > 0");
+  return 0;
+}
+
+// The packed-row checks of the per-sequence forms (varlen, paged): [token, head] strides, pointers, max_seqlen_q.
+static int fa_check_packed(const char* fn, std::initializer_list<const int64_t*> strides,
+                           std::initializer_list<const void*> ptrs, int total_q, int max_seqlen_q) {
+  for (const int64_t* s : strides)
+    MIO_CHECK(s[0] >= 0 && s[1] >= 0 && s[0] % 8 == 0 && s[1] % 8 == 0,
+              std::string(fn) + ": strides must be non-negative multiples of 8 elements (16-byte rows)");
+  MIO_CHECK(aligned16(ptrs), std::string(fn) + ": pointers must be 16-byte aligned");
+  MIO_CHECK(total_q == 0 || max_seqlen_q >= 1, std::string(fn) + ": max_seqlen_q must be >= 1 when total_q > 0");
+  return 0;
+}
+
+// The FaDev fields all three entry points fill alike; each adds its strides and its own fields.
+static FaDev fa_dev(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv, int D,
+                    float softmax_scale) {
+  FaDev p = {};
+  p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
+  p.B = B; p.H = H; p.Hkv = Hkv; p.D = D;
+  p.xcd_remap = ((B * H) % 8 == 0) ? 1 : 0;
+  p.scale_log2e = softmax_scale * FA_LOG2E;
+  return p;
+}
+
+static int dpad_of(int D) { return D <= 64 ? 64 : (D <= 96 ? 96 : 128); }
+
+template <typename T_, int D_>
+struct FaInst {  // one (dtype, padded head dim) instantiation of the launchers
+  using T = T_;
+  static constexpr int D = D_;
+};
+
+// f(FaInst<T, D>{}) for the launch's dtype and padded head dim: the one list of the instantiations the library holds
+template <typename F>
+static int fa_dispatch(int dtype, int D, F&& f) {
+  const int dpad = dpad_of(D);
+  if (dtype == MIO_BF16) {
+    if (dpad == 64) return f(FaInst<__bf16, 64>{});
+    if (dpad == 96) return f(FaInst<__bf16, 96>{});
+    return f(FaInst<__bf16, 128>{});
+  }
+  if (dpad == 64) return f(FaInst<_Float16, 64>{});
+  if (dpad == 96) return f(FaInst<_Float16, 96>{});
+  return f(FaInst<_Float16, 128>{});
+}
 
 extern "C" int32_t mio_fa3_k_prescaled_ok(const mio_fa3_fwd_params_t* a) {
   if (a == nullptr) return 0;
@@ -49,18 +91,13 @@ static int fa3_validate(const mio_fa3_fwd_params_t* a) {
   MIO_CHECK(a->q && a->k && a->v, "mio_fa3_fwd: q/k/v must be non-null");
   MIO_CHECK(a->o != nullptr || a->o_acc != nullptr, "mio_fa3_fwd: o or o_acc must be given");
   MIO_CHECK(a->B > 0 && a->H > 0 && a->Hkv > 0 && a->Sq >= 0 && a->Sk >= 0, "mio_fa3_fwd: bad sizes");
-  MIO_CHECK(a->H % a->Hkv == 0, "mio_fa3_fwd: H must be a multiple of Hkv");
-  MIO_CHECK(a->D >= 8 && a->D <= 128 && a->D % 8 == 0, "mio_fa3_fwd: head_dim must be a multiple of 8 in [8,128]");
-  MIO_CHECK(a->dtype == MIO_BF16 || a->dtype == MIO_FP16, "mio_fa3_fwd: dtype must be bf16 or fp16");
-  MIO_CHECK(a->softmax_scale > 0.f && std::isfinite(a->softmax_scale), "mio_fa3_fwd: softmax_scale must be > 0");
+  if (fa_check_common("mio_fa3_fwd", a->H, a->Hkv, a->D, a->dtype, a->softmax_scale) != 0) return -1;
   MIO_CHECK(a->mask_kind >= 0 && a->mask_kind <= 2, "mio_fa3_fwd: bad mask_kind");
   MIO_CHECK((a->mask_kind == MIO_MASK_NONE) == (a->mask == nullptr), "mio_fa3_fwd: mask pointer / mask_kind mismatch");
   MIO_CHECK(strides_ok(a->q_stride) && strides_ok(a->k_stride) && strides_ok(a->v_stride) &&
                 (a->o == nullptr || a->o_blocked || strides_ok(a->o_stride)),
             "mio_fa3_fwd: strides must be multiples of 8 elements (16-byte rows)");
-  MIO_CHECK(mio_aligned16(a->q) && mio_aligned16(a->k) && mio_aligned16(a->v) && mio_aligned16(a->o) &&
-                mio_aligned16(a->o_acc),
-            "mio_fa3_fwd: pointers must be 16-byte aligned");
+  MIO_CHECK(aligned16({a->q, a->k, a->v, a->o, a->o_acc}), "mio_fa3_fwd: pointers must be 16-byte aligned");
   MIO_CHECK(!a->carry_in || (a->o_acc && a->lse), "mio_fa3_fwd: carry_in needs o_acc and lse");
   MIO_CHECK(a->o_acc == nullptr || a->lse != nullptr, "mio_fa3_fwd: o_acc needs lse");
   if (a->Sq == 0) return 0;  // nothing is launched
@@ -70,8 +107,6 @@ static int fa3_validate(const mio_fa3_fwd_params_t* a) {
                                                           "(mio_fa3_k_prescaled_ok == 0)");
   return 0;
 }
-
-static int dpad_of(int D) { return D <= 64 ? 64 : (D <= 96 ? 96 : 128); }
 
 static int route_of(const mio_fa3_fwd_params_t* a) {
   Fa3RouteArgs r;
@@ -101,36 +136,39 @@ extern "C" int mio_fa3_fwd(const mio_fa3_fwd_params_t* a, void* stream) {
   if (fa3_validate(a) != 0) return -1;
   if (a->Sq == 0) return 0;
 
-  FaDev p;
-  p.q = a->q; p.k = a->k; p.v = a->v; p.o = a->o; p.lse = a->lse; p.o_acc = a->o_acc; p.mask = a->mask;
+  FaDev p = fa_dev(a->q, a->k, a->v, a->o, a->lse, a->B, a->H, a->Hkv, a->D, a->softmax_scale);
+  p.o_acc = a->o_acc; p.mask = a->mask;
   p.qs_b = a->q_stride[0]; p.qs_s = a->q_stride[1]; p.qs_h = a->q_stride[2];
   p.ks_b = a->k_stride[0]; p.ks_s = a->k_stride[1]; p.ks_h = a->k_stride[2];
   p.vs_b = a->v_stride[0]; p.vs_s = a->v_stride[1]; p.vs_h = a->v_stride[2];
   p.os_b = a->o_stride[0]; p.os_s = a->o_stride[1]; p.os_h = a->o_stride[2];
   p.ms_b = a->mask_stride[0]; p.ms_h = a->mask_stride[1]; p.ms_q = a->mask_stride[2]; p.ms_k = a->mask_stride[3];
-  p.B = a->B; p.Sq = a->Sq; p.Sk = a->Sk; p.H = a->H; p.Hkv = a->Hkv; p.D = a->D;
+  p.Sq = a->Sq; p.Sk = a->Sk;
   p.carry_in = a->carry_in; p.q_offset = a->q_offset; p.k_offset = a->k_offset;
   p.nqblk = (a->Sq + FA_BM - 1) / FA_BM;
   p.qgrid = p.nqblk;
-  p.xcd_remap = ((a->B * a->H) % 8 == 0) ? 1 : 0;
-  p.scale_log2e = a->softmax_scale * FA_LOG2E;
   p.k_prescaled = a->k_prescaled ? 1 : 0;
   p.o_blk = a->o_blocked ? 1 : 0;
 
-  hipStream_t st = (hipStream_t)stream;
-  const int dpad = dpad_of(a->D);
   const int route = route_of(a);
-  if (a->dtype == MIO_BF16) {
-    if (dpad == 64) return fa3_launch<__bf16, 64>(p, a->causal, route, st);
-    if (dpad == 96) return fa3_launch<__bf16, 96>(p, a->causal, route, st);
-    return fa3_launch<__bf16, 128>(p, a->causal, route, st);
-  }
-  if (dpad == 64) return fa3_launch<_Float16, 64>(p, a->causal, route, st);
-  if (dpad == 96) return fa3_launch<_Float16, 96>(p, a->causal, route, st);
-  return fa3_launch<_Float16, 128>(p, a->causal, route, st);
+  return fa_dispatch(a->dtype, a->D, [&](auto i) {
+    return fa3_launch<typename decltype(i)::T, decltype(i)::D>(p, a->causal, route, (hipStream_t)stream);
+  });
 }
 
-// ---- packed variable-length form (mio_fa3_fwd_varlen)
+// ---- the per-sequence forms: packed variable-length (mio_fa3_fwd_varlen) and over the paged KV cache (mio_fa3_fwd_paged)
+
+// mio_fa3_varlen_route / mio_fa3_paged_route: the same kernels for the same head dims (the two enums have equal values)
+template <typename P>
+static int32_t fa_seq_route(const P* a, int (*validate)(const P*)) {
+  static_assert((int)MIO_FA3_PAGED_ROUTE_INVALID == MIO_FA3_VARLEN_ROUTE_INVALID &&
+                (int)MIO_FA3_PAGED_ROUTE_EMPTY == MIO_FA3_VARLEN_ROUTE_EMPTY &&
+                (int)MIO_FA3_PAGED_ROUTE_FWD5 == MIO_FA3_VARLEN_ROUTE_FWD5 &&
+                (int)MIO_FA3_PAGED_ROUTE_FWD3 == MIO_FA3_VARLEN_ROUTE_FWD3);
+  if (validate(a) != 0) return MIO_FA3_VARLEN_ROUTE_INVALID;
+  if (a->B == 0 || a->total_q == 0) return MIO_FA3_VARLEN_ROUTE_EMPTY;
+  return dpad_of(a->D) == 64 ? MIO_FA3_VARLEN_ROUTE_FWD5 : MIO_FA3_VARLEN_ROUTE_FWD3;
+}
 
 // every argument check of mio_fa3_fwd_varlen (0 or -1 with the message set); mio_fa3_varlen_route runs the same checks.
 // Nothing here reads device memory: the sequence bounds are clamped in the kernel (fa3_varlen.h).
@@ -139,19 +177,13 @@ static int fa3_varlen_validate(const mio_fa3_varlen_params_t* a) {
   MIO_CHECK(a->B >= 0 && a->total_q >= 0 && a->total_k >= 0 && a->max_seqlen_q >= 0 && a->max_seqlen_k >= 0 && a->H > 0 &&
                 a->Hkv > 0,
             "mio_fa3_fwd_varlen: bad sizes");
-  MIO_CHECK(a->H % a->Hkv == 0, "mio_fa3_fwd_varlen: H must be a multiple of Hkv");
-  MIO_CHECK(a->D >= 8 && a->D <= 128 && a->D % 8 == 0, "mio_fa3_fwd_varlen: head_dim must be a multiple of 8 in [8,128]");
-  MIO_CHECK(a->dtype == MIO_BF16 || a->dtype == MIO_FP16, "mio_fa3_fwd_varlen: dtype must be bf16 or fp16");
-  MIO_CHECK(a->softmax_scale > 0.f && std::isfinite(a->softmax_scale), "mio_fa3_fwd_varlen: softmax_scale must be > 0");
+  if (fa_check_common("mio_fa3_fwd_varlen", a->H, a->Hkv, a->D, a->dtype, a->softmax_scale) != 0) return -1;
   MIO_CHECK(a->q && a->k && a->v && a->o, "mio_fa3_fwd_varlen: q/k/v/o must be non-null");
   MIO_CHECK(a->B == 0 || (a->cu_seqlens_q != nullptr && a->cu_seqlens_k != nullptr),
             "mio_fa3_fwd_varlen: cu_seqlens_q / cu_seqlens_k must be non-null");
-  for (const int64_t* s : {a->q_stride, a->k_stride, a->v_stride, a->o_stride})
-    MIO_CHECK(s[0] >= 0 && s[1] >= 0 && s[0] % 8 == 0 && s[1] % 8 == 0,
-              "mio_fa3_fwd_varlen: strides must be non-negative multiples of 8 elements (16-byte rows)");
-  MIO_CHECK(mio_aligned16(a->q) && mio_aligned16(a->k) && mio_aligned16(a->v) && mio_aligned16(a->o),
-            "mio_fa3_fwd_varlen: pointers must be 16-byte aligned");
-  MIO_CHECK(a->total_q == 0 || a->max_seqlen_q >= 1, "mio_fa3_fwd_varlen: max_seqlen_q must be >= 1 when total_q > 0");
+  if (fa_check_packed("mio_fa3_fwd_varlen", {a->q_stride, a->k_stride, a->v_stride, a->o_stride}, {a->q, a->k, a->v, a->o},
+                      a->total_q, a->max_seqlen_q) != 0)
+    return -1;
   MIO_CHECK(a->total_k == 0 || a->max_seqlen_k >= 1, "mio_fa3_fwd_varlen: max_seqlen_k must be >= 1 when total_k > 0");
   // the pipelined kernels address K / V tiles with 32-bit byte offsets from the sequence's first row
   MIO_CHECK((int64_t)a->max_seqlen_k * a->k_stride[0] * 2 < (1ll << 32) &&
@@ -160,43 +192,26 @@ static int fa3_varlen_validate(const mio_fa3_varlen_params_t* a) {
   return 0;
 }
 
-extern "C" int32_t mio_fa3_varlen_route(const mio_fa3_varlen_params_t* a) {
-  if (fa3_varlen_validate(a) != 0) return MIO_FA3_VARLEN_ROUTE_INVALID;
-  if (a->B == 0 || a->total_q == 0) return MIO_FA3_VARLEN_ROUTE_EMPTY;
-  return dpad_of(a->D) == 64 ? MIO_FA3_VARLEN_ROUTE_FWD5 : MIO_FA3_VARLEN_ROUTE_FWD3;
-}
+extern "C" int32_t mio_fa3_varlen_route(const mio_fa3_varlen_params_t* a) { return fa_seq_route(a, fa3_varlen_validate); }
 
 extern "C" int mio_fa3_fwd_varlen(const mio_fa3_varlen_params_t* a, void* stream) {
   if (fa3_varlen_validate(a) != 0) return -1;
   if (a->B == 0 || a->total_q == 0) return 0;
 
-  FaDev p = {};
-  p.q = a->q; p.k = a->k; p.v = a->v; p.o = a->o; p.lse = a->lse; p.o_acc = nullptr; p.mask = nullptr;
+  FaDev p = fa_dev(a->q, a->k, a->v, a->o, a->lse, a->B, a->H, a->Hkv, a->D, a->softmax_scale);
   p.qs_s = a->q_stride[0]; p.qs_h = a->q_stride[1];
   p.ks_s = a->k_stride[0]; p.ks_h = a->k_stride[1];
   p.vs_s = a->v_stride[0]; p.vs_h = a->v_stride[1];
   p.os_s = a->o_stride[0]; p.os_h = a->o_stride[1];
-  p.B = a->B; p.H = a->H; p.Hkv = a->Hkv; p.D = a->D;
-  p.xcd_remap = ((a->B * a->H) % 8 == 0) ? 1 : 0;
-  p.scale_log2e = a->softmax_scale * FA_LOG2E;
   FaVarlen vl;
   vl.cu_q = a->cu_seqlens_q; vl.cu_k = a->cu_seqlens_k;
   vl.total_q = a->total_q; vl.total_k = a->total_k;
   vl.max_q = a->max_seqlen_q; vl.max_k = a->max_seqlen_k;
 
-  hipStream_t st = (hipStream_t)stream;
-  const int dpad = dpad_of(a->D);
-  if (a->dtype == MIO_BF16) {
-    if (dpad == 64) return fa3_varlen_launch<__bf16, 64>(p, vl, a->causal, st);
-    if (dpad == 96) return fa3_varlen_launch<__bf16, 96>(p, vl, a->causal, st);
-    return fa3_varlen_launch<__bf16, 128>(p, vl, a->causal, st);
-  }
-  if (dpad == 64) return fa3_varlen_launch<_Float16, 64>(p, vl, a->causal, st);
-  if (dpad == 96) return fa3_varlen_launch<_Float16, 96>(p, vl, a->causal, st);
-  return fa3_varlen_launch<_Float16, 128>(p, vl, a->causal, st);
+  return fa_dispatch(a->dtype, a->D, [&](auto i) {
+    return fa3_seq_launch<typename decltype(i)::T, decltype(i)::D>(p, vl, a->causal, (hipStream_t)stream);
+  });
 }
-
-// ---- attention forward over the paged KV cache (mio_fa3_fwd_paged)
 
 // every argument check of mio_fa3_fwd_paged (0 or -1 with the message set); mio_fa3_paged_route runs the same checks.
 // Nothing here reads device memory: sequence bounds, block indices and pages are clamped in the kernel (fa3_paged.h).
@@ -204,10 +219,7 @@ static int fa3_paged_validate(const mio_fa3_paged_params_t* a) {
   MIO_CHECK(a != nullptr, "mio_fa3_fwd_paged: null params");
   MIO_CHECK(a->B >= 0 && a->total_q >= 0 && a->max_seqlen_q >= 0 && a->max_seqlen_k >= 0 && a->H > 0 && a->Hkv > 0,
             "mio_fa3_fwd_paged: bad sizes");
-  MIO_CHECK(a->H % a->Hkv == 0, "mio_fa3_fwd_paged: H must be a multiple of Hkv");
-  MIO_CHECK(a->D >= 8 && a->D <= 128 && a->D % 8 == 0, "mio_fa3_fwd_paged: head_dim must be a multiple of 8 in [8,128]");
-  MIO_CHECK(a->dtype == MIO_BF16 || a->dtype == MIO_FP16, "mio_fa3_fwd_paged: dtype must be bf16 or fp16");
-  MIO_CHECK(a->softmax_scale > 0.f && std::isfinite(a->softmax_scale), "mio_fa3_fwd_paged: softmax_scale must be > 0");
+  if (fa_check_common("mio_fa3_fwd_paged", a->H, a->Hkv, a->D, a->dtype, a->softmax_scale) != 0) return -1;
   MIO_CHECK(a->q && a->k_cache && a->v_cache && a->o, "mio_fa3_fwd_paged: q/k_cache/v_cache/o must be non-null");
   MIO_CHECK(a->B == 0 || (a->cu_seqlens_q != nullptr && a->seqused_k != nullptr && a->block_tables != nullptr),
             "mio_fa3_fwd_paged: cu_seqlens_q / seqused_k / block_tables must be non-null");
@@ -215,12 +227,9 @@ static int fa3_paged_validate(const mio_fa3_paged_params_t* a) {
   MIO_CHECK(a->layer_idx >= 0 && a->layer_idx < a->num_layers, "mio_fa3_fwd_paged: layer_idx must be in [0, num_layers)");
   MIO_CHECK(a->block_size > 0 && a->block_size % 64 == 0,
             "mio_fa3_fwd_paged: block_size must be a multiple of 64 (a 64-key tile may not span two pages)");
-  for (const int64_t* s : {a->q_stride, a->o_stride})
-    MIO_CHECK(s[0] >= 0 && s[1] >= 0 && s[0] % 8 == 0 && s[1] % 8 == 0,
-              "mio_fa3_fwd_paged: strides must be non-negative multiples of 8 elements (16-byte rows)");
-  MIO_CHECK(mio_aligned16(a->q) && mio_aligned16(a->k_cache) && mio_aligned16(a->v_cache) && mio_aligned16(a->o),
-            "mio_fa3_fwd_paged: pointers must be 16-byte aligned");
-  MIO_CHECK(a->total_q == 0 || a->max_seqlen_q >= 1, "mio_fa3_fwd_paged: max_seqlen_q must be >= 1 when total_q > 0");
+  if (fa_check_packed("mio_fa3_fwd_paged", {a->q_stride, a->o_stride}, {a->q, a->k_cache, a->v_cache, a->o}, a->total_q,
+                      a->max_seqlen_q) != 0)
+    return -1;
   // the kernels index the cache by a 32-bit row (page, layer, slot) and divide tile indices by a 31-bit reciprocal
   MIO_CHECK((int64_t)a->num_blocks * a->num_layers * a->block_size < (1ll << 32),
             "mio_fa3_fwd_paged: the cache must hold fewer than 2^32 token rows (num_blocks * num_layers * block_size)");
@@ -230,25 +239,17 @@ static int fa3_paged_validate(const mio_fa3_paged_params_t* a) {
   return 0;
 }
 
-extern "C" int32_t mio_fa3_paged_route(const mio_fa3_paged_params_t* a) {
-  if (fa3_paged_validate(a) != 0) return MIO_FA3_PAGED_ROUTE_INVALID;
-  if (a->B == 0 || a->total_q == 0) return MIO_FA3_PAGED_ROUTE_EMPTY;
-  return dpad_of(a->D) == 64 ? MIO_FA3_PAGED_ROUTE_FWD5 : MIO_FA3_PAGED_ROUTE_FWD3;
-}
+extern "C" int32_t mio_fa3_paged_route(const mio_fa3_paged_params_t* a) { return fa_seq_route(a, fa3_paged_validate); }
 
 extern "C" int mio_fa3_fwd_paged(const mio_fa3_paged_params_t* a, void* stream) {
   if (fa3_paged_validate(a) != 0) return -1;
   if (a->B == 0 || a->total_q == 0) return 0;
 
-  FaDev p = {};
-  p.q = a->q; p.k = a->k_cache; p.v = a->v_cache; p.o = a->o; p.lse = a->lse; p.o_acc = nullptr; p.mask = nullptr;
+  FaDev p = fa_dev(a->q, a->k_cache, a->v_cache, a->o, a->lse, a->B, a->H, a->Hkv, a->D, a->softmax_scale);
   p.qs_s = a->q_stride[0]; p.qs_h = a->q_stride[1];
   p.ks_s = p.vs_s = (int64_t)a->Hkv * a->D;  // the cache's token stride; pages and layers come from the walk
   p.ks_h = p.vs_h = a->D;
   p.os_s = a->o_stride[0]; p.os_h = a->o_stride[1];
-  p.B = a->B; p.H = a->H; p.Hkv = a->Hkv; p.D = a->D;
-  p.xcd_remap = ((a->B * a->H) % 8 == 0) ? 1 : 0;
-  p.scale_log2e = a->softmax_scale * FA_LOG2E;
   FaPaged pg;
   pg.cu_q = a->cu_seqlens_q; pg.seqused_k = a->seqused_k; pg.block_tables = a->block_tables;
   pg.total_q = a->total_q; pg.max_q = a->max_seqlen_q;
@@ -258,14 +259,7 @@ extern "C" int mio_fa3_fwd_paged(const mio_fa3_paged_params_t* a, void* stream) 
   pg.tpb = a->block_size / 64;
   pg.tpb_magic = (uint32_t)(((1ull << 31) + pg.tpb - 1) / pg.tpb);
 
-  hipStream_t st = (hipStream_t)stream;
-  const int dpad = dpad_of(a->D);
-  if (a->dtype == MIO_BF16) {
-    if (dpad == 64) return fa3_paged_launch<__bf16, 64>(p, pg, a->causal, st);
-    if (dpad == 96) return fa3_paged_launch<__bf16, 96>(p, pg, a->causal, st);
-    return fa3_paged_launch<__bf16, 128>(p, pg, a->causal, st);
-  }
-  if (dpad == 64) return fa3_paged_launch<_Float16, 64>(p, pg, a->causal, st);
-  if (dpad == 96) return fa3_paged_launch<_Float16, 96>(p, pg, a->causal, st);
-  return fa3_paged_launch<_Float16, 128>(p, pg, a->causal, st);
+  return fa_dispatch(a->dtype, a->D, [&](auto i) {
+    return fa3_seq_launch<typename decltype(i)::T, decltype(i)::D>(p, pg, a->causal, (hipStream_t)stream);
+  });
 }

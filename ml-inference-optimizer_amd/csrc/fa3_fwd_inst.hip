@@ -2,7 +2,6 @@
 // The product library reads no environment variable and keeps no unsynchronised mutable state; the A/B switches and the
 // in-kernel stamp instantiations exist only in the diagnostic build (make dbg: -DMIO_DIAG -> libmio_hip_dbg.so).
 #include <cstdlib>
-#include <mutex>
 
 #include "fa3_fwd3_kernel.h"
 #include "fa3_route.h"
@@ -18,19 +17,8 @@ using FaT = _Float16;
 
 template <bool CAUSAL, int MASK>
 static int launch_one(const FaDev& p, hipStream_t stream) {
-  const int grid = p.nqblk * p.B * p.H;
-  const size_t smem = FaSmem<FA_D>::TOTAL;
-  auto kern = fa3_fwd_kernel<FaT, FA_D, CAUSAL, MASK>;
-  if (smem > 48 * 1024) {  // > 64 KiB dynamic LDS (D = 128) needs the opt-in once per kernel
-    static std::once_flag once;
-    static hipError_t ea = hipSuccess;
-    std::call_once(once, [&] { ea = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
-    if (ea != hipSuccess) return mio_fail(std::string("fa3_fwd: hipFuncSetAttribute: ") + hipGetErrorString(ea));
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("fa3_fwd launch: ") + hipGetErrorString(e));
-  return 0;
+  return fa_launch<fa3_fwd_kernel<FaT, FA_D, CAUSAL, MASK>>("fa3_fwd", p.nqblk * p.B * p.H, 256, FaSmem<FA_D>::TOTAL,
+                                                            stream, p);
 }
 
 // third structure (software-pipelined across KV tiles): no user mask
@@ -40,55 +28,33 @@ static int launch_three(FaDev p, hipStream_t stream) {
   p.qgrid = CAUSAL ? (p.nqblk + 1) / 2 : p.nqblk;
   const int grid = p.qgrid * p.B * p.H;
   const size_t smem = FA3_STAGES * FaSmem<FA_D>::STAGE;
-  auto kern = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 0, KPRE>;
 #ifdef MIO_DIAG
 #if FA_D == 64 && FA_TYPE_ID == 0
   if constexpr (CAUSAL && !KPRE) {  // timing-only ablations (tools/fa_ablate.py): mio_dbg_set(0, bits)
-    void (*ka)(const FaDev) = nullptr;
+    const char* abl = "fa3_fwd3 (ablation)";
     switch (mio_dbg_get(0)) {
-      case 1: ka = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 1>; break;
-      case 2: ka = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 2>; break;
-      case 3: ka = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 3>; break;
-      case 4: ka = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 4>; break;
-      case 8: ka = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 8>; break;
-      case 16: ka = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 16>; break;
-      case 32: ka = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 32>; break;
-      case 48: ka = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 48>; break;
-      case 57: ka = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 57>; break;
-      case 59: ka = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 59>; break;
-      case 63: ka = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 63>; break;
+      case 1: return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 1>>(abl, grid, 256, smem, stream, p);
+      case 2: return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 2>>(abl, grid, 256, smem, stream, p);
+      case 3: return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 3>>(abl, grid, 256, smem, stream, p);
+      case 4: return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 4>>(abl, grid, 256, smem, stream, p);
+      case 8: return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 8>>(abl, grid, 256, smem, stream, p);
+      case 16: return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 16>>(abl, grid, 256, smem, stream, p);
+      case 32: return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 32>>(abl, grid, 256, smem, stream, p);
+      case 48: return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 48>>(abl, grid, 256, smem, stream, p);
+      case 57: return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 57>>(abl, grid, 256, smem, stream, p);
+      case 59: return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 59>>(abl, grid, 256, smem, stream, p);
+      case 63: return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 63>>(abl, grid, 256, smem, stream, p);
       default: break;
-    }
-    if (ka != nullptr) {
-      hipError_t ed = hipFuncSetAttribute((const void*)ka, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (ed != hipSuccess) return mio_fail(std::string("fa3_fwd3 (ablation): hipFuncSetAttribute: ") + hipGetErrorString(ed));
-      hipLaunchKernelGGL(ka, dim3(grid), dim3(256), smem, stream, p);
-      return 0;
     }
   }
 #endif
   static const char* dbg_ptr = std::getenv("MIO_FA_DBG_PTR");  // in-kernel phase stamps (tools/fa_stamps.py)
   if (dbg_ptr != nullptr && !KPRE) {
-    auto kd = fa3_fwd3_kernel<FaT, FA_D, CAUSAL, true>;
     p.mask = (const void*)std::strtoull(dbg_ptr, nullptr, 0);
-    hipError_t ed = hipFuncSetAttribute((const void*)kd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (ed != hipSuccess) return mio_fail(std::string("fa3_fwd3 (stamps): hipFuncSetAttribute: ") + hipGetErrorString(ed));
-    hipLaunchKernelGGL(kd, dim3(grid), dim3(256), smem, stream, p);
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) return mio_fail(std::string("fa3_fwd3 (stamps) launch: ") + hipGetErrorString(e2));
-    return 0;
+    return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, true>>("fa3_fwd3 (stamps)", grid, 256, smem, stream, p);
   }
 #endif
-  {
-    static std::once_flag once;
-    static hipError_t ea = hipSuccess;
-    std::call_once(once, [&] { ea = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
-    if (ea != hipSuccess) return mio_fail(std::string("fa3_fwd3: hipFuncSetAttribute: ") + hipGetErrorString(ea));
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("fa3_fwd3 launch: ") + hipGetErrorString(e));
-  return 0;
+  return fa_launch<fa3_fwd3_kernel<FaT, FA_D, CAUSAL, false, 0, KPRE>>("fa3_fwd3", grid, 256, smem, stream, p);
 }
 
 // fifth structure (two waves per SIMD on 16x16x32 MFMA tiles): head dim <= 64, no user mask
@@ -98,46 +64,28 @@ static int launch_five(FaDev p, hipStream_t stream) {
   p.nqblk = (p.Sq + FA5_BM - 1) / FA5_BM;
   p.qgrid = CAUSAL ? (p.nqblk + 1) / 2 : p.nqblk;
   const int grid = p.qgrid * p.B * p.H;
-  void (*kern)(const FaDev) = fa3_fwd5_kernel<FaT, CAUSAL, false, 0, CARRY, OBLK, KPRE>;
 #if defined(MIO_DIAG) && FA_TYPE_ID == 0
   if constexpr (!CARRY && !OBLK && KPRE) {
   p.xcd_remap |= (mio_dbg_get(3) & 7) << 4;  // wave-priority probe (tools/fa5_ablate.py)
   static const char* dbg_ptr = std::getenv("MIO_FA_DBG_PTR");  // in-kernel phase stamps (tools/fa5_stamps.py)
   if (dbg_ptr != nullptr) {
-    auto kd = fa3_fwd5_kernel<FaT, CAUSAL, true>;
     p.mask = (const void*)std::strtoull(dbg_ptr, nullptr, 0);
-    hipError_t ed = hipFuncSetAttribute((const void*)kd, hipFuncAttributeMaxDynamicSharedMemorySize, FA5_SMEM);
-    if (ed != hipSuccess) return mio_fail(std::string("fa3_fwd5 (stamps): hipFuncSetAttribute: ") + hipGetErrorString(ed));
-    hipLaunchKernelGGL(kd, dim3(grid), dim3(512), FA5_SMEM, stream, p);
-    return 0;
+    return fa_launch<fa3_fwd5_kernel<FaT, CAUSAL, true>>("fa3_fwd5 (stamps)", grid, 512, FA5_SMEM, stream, p);
   }
   if constexpr (CAUSAL) {  // timing-only ablations (tools/fa5_ablate.py): mio_dbg_set(0, bits)
-    void (*ka)(const FaDev) = nullptr;
+    const char* abl = "fa3_fwd5 (ablation)";
     switch (mio_dbg_get(0)) {
-      case 1: ka = fa3_fwd5_kernel<FaT, CAUSAL, false, 1>; break;
-      case 2: ka = fa3_fwd5_kernel<FaT, CAUSAL, false, 2>; break;
-      case 4: ka = fa3_fwd5_kernel<FaT, CAUSAL, false, 4>; break;
-      case 8: ka = fa3_fwd5_kernel<FaT, CAUSAL, false, 8>; break;
-      case 15: ka = fa3_fwd5_kernel<FaT, CAUSAL, false, 15>; break;
+      case 1: return fa_launch<fa3_fwd5_kernel<FaT, CAUSAL, false, 1>>(abl, grid, 512, FA5_SMEM, stream, p);
+      case 2: return fa_launch<fa3_fwd5_kernel<FaT, CAUSAL, false, 2>>(abl, grid, 512, FA5_SMEM, stream, p);
+      case 4: return fa_launch<fa3_fwd5_kernel<FaT, CAUSAL, false, 4>>(abl, grid, 512, FA5_SMEM, stream, p);
+      case 8: return fa_launch<fa3_fwd5_kernel<FaT, CAUSAL, false, 8>>(abl, grid, 512, FA5_SMEM, stream, p);
+      case 15: return fa_launch<fa3_fwd5_kernel<FaT, CAUSAL, false, 15>>(abl, grid, 512, FA5_SMEM, stream, p);
       default: break;
-    }
-    if (ka != nullptr) {
-      hipError_t ed = hipFuncSetAttribute((const void*)ka, hipFuncAttributeMaxDynamicSharedMemorySize, FA5_SMEM);
-      if (ed != hipSuccess) return mio_fail(std::string("fa3_fwd5 (ablation): hipFuncSetAttribute: ") + hipGetErrorString(ed));
-      hipLaunchKernelGGL(ka, dim3(grid), dim3(512), FA5_SMEM, stream, p);
-      return 0;
     }
   }
   }
 #endif
-  static std::once_flag once;
-  static hipError_t ea = hipSuccess;
-  std::call_once(once, [&] { ea = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, FA5_SMEM); });
-  if (ea != hipSuccess) return mio_fail(std::string("fa3_fwd5: hipFuncSetAttribute: ") + hipGetErrorString(ea));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), FA5_SMEM, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("fa3_fwd5 launch: ") + hipGetErrorString(e));
-  return 0;
+  return fa_launch<fa3_fwd5_kernel<FaT, CAUSAL, false, 0, CARRY, OBLK, KPRE>>("fa3_fwd5", grid, 512, FA5_SMEM, stream, p);
 }
 #endif
 

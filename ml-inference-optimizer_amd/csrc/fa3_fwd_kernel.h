@@ -19,6 +19,7 @@
 //   * LDS images: K rows padded by 16 B (conflict-free ds_read_b128 for any D), V as
 //     [key/8][d/32][8][32] sub-tiles (each half-wave's transposed read covers one 256-B bank row).
 #pragma once
+#include <mutex>
 #include <type_traits>
 
 #include "mio_common.h"
@@ -445,3 +446,20 @@ __global__ __launch_bounds__(256) void fa3_fwd_kernel(const FaDev p) {
 // mio_fa3_route_t for the launch (fa3_route.h).
 template <typename T, int D>
 int fa3_launch(const FaDev& p, int causal, int route, hipStream_t stream);
+
+// One launch of attention kernel KERN (every attention launch goes through here).  More than 48 KiB of dynamic LDS needs
+// an opt-in, requested once per kernel (std::call_once: the library keeps no unsynchronised mutable state).  Failures
+// return mio_fail("<family>: hipFuncSetAttribute: ...") or mio_fail("<family> launch: ...").
+template <auto KERN, typename... A>
+static int fa_launch(const char* family, unsigned grid, int threads, size_t smem, hipStream_t stream, const A&... args) {
+  if (smem > 48 * 1024) {
+    static std::once_flag once;
+    static hipError_t ea = hipSuccess;
+    std::call_once(once, [&] { ea = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
+    if (ea != hipSuccess) return mio_fail(std::string(family) + ": hipFuncSetAttribute: " + hipGetErrorString(ea));
+  }
+  hipLaunchKernelGGL(KERN, dim3(grid), dim3(threads), smem, stream, args...);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return mio_fail(std::string(family) + " launch: " + hipGetErrorString(e));
+  return 0;
+}

@@ -141,9 +141,3 @@ __global__ __launch_bounds__(256) void fa3_fwd3_paged_kernel(const FaDev pl, con
 #undef FA_LSE_INDEX
 #undef FA_KV_TILE
 }
-
-// Host launcher for one (dtype, padded D); defined per translation unit (fa3_paged_inst.hip).  p carries the launch's
-// sizes, q / o strides and pointers (k / v: the caches; ks_s = vs_s = Hkv * D, ks_h = vs_h = D); the grid fields are set by
-// the launcher.
-template <typename T, int D>
-int fa3_paged_launch(const FaDev& p, const FaPaged& pg, int causal, hipStream_t stream);

@@ -127,7 +127,9 @@ __device__ __forceinline__ bool fa_varlen_prepare(FaDev& p, const FaVarlen& v) {
   return fa_seq_prepare<BM, NT, CAUSAL>(p, v, b);
 }
 
-// Host launcher for one (dtype, padded D); defined per translation unit (fa3_varlen_inst.hip).  p carries the launch's
-// sizes, strides (batch strides unused) and pointers; the grid fields are set by the launcher.
-template <typename T, int D>
-int fa3_varlen_launch(const FaDev& p, const FaVarlen& vl, int causal, hipStream_t stream);
+// Host launcher of the per-sequence forms for one (dtype, padded D) and sequence description V (FaVarlen, FaPaged in
+// fa3_paged.h); defined per translation unit (fa3_seq_inst.hip).  p carries the launch's sizes, strides (batch strides
+// unused) and pointers (paged: k / v are the caches, ks_s = vs_s = Hkv * D, ks_h = vs_h = D); the grid fields are set by
+// the launcher.
+template <typename T, int D, typename V>
+int fa3_seq_launch(const FaDev& p, const V& seq, int causal, hipStream_t stream);

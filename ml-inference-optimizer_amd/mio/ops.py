@@ -94,6 +94,59 @@ def _rows16(t: torch.Tensor) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------------
+def _qkv_dtype(q, k, v, names="q, k, v") -> int:
+    """The dtype id of q, which k and v must share."""
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"{names} must have the same dtype")
+    return _dtype_id(q)
+
+
+def _check_heads(H: int, Hkv: int, D: int) -> None:
+    if H % Hkv != 0:
+        raise ValueError(f"num_heads {H} must be a multiple of num_kv_heads {Hkv}")
+    if D % 8 != 0 or D > 128:
+        raise ValueError(f"head_dim must be a multiple of 8 and <= 128, got {D}")
+
+
+def _softmax_scale(D: int, softmax_scale: Optional[float]) -> float:
+    scale = (1.0 / math.sqrt(D)) if softmax_scale is None else float(softmax_scale)
+    if not (scale > 0.0):
+        raise ValueError("softmax_scale must be positive")
+    return scale
+
+
+def _out_like(q: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    if out is None:
+        return torch.empty_like(q, memory_format=torch.contiguous_format)
+    if out.shape != q.shape or out.dtype != q.dtype or out.stride(-1) != 1:
+        raise ValueError("out must match q in shape/dtype with a contiguous last dim")
+    return out
+
+
+def _packed_lse(q: torch.Tensor, return_lse: bool) -> Optional[torch.Tensor]:
+    """The packed forms' lse, fp32 [H, total_q] for q [total_q, H, D], when return_lse."""
+    return torch.empty(q.shape[1], q.shape[0], dtype=torch.float32, device=q.device) if return_lse else None
+
+
+def _fill_null(p, fields, addr: int) -> None:
+    """torch gives empty tensors a null address; nothing is read or written through them (include/mio_hip.h): use addr."""
+    for f in fields:
+        if not getattr(p, f):
+            setattr(p, f, addr)
+
+
+def _route(query, p, names) -> str:
+    r = query(C.byref(p))
+    if r < 0:
+        raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
+    return names[r]
+
+
+def _launch(fwd, p, out, lse, return_lse: bool):  # queued on the current stream; RuntimeError on failure
+    check(fwd(C.byref(p), _stream()))
+    return (out, lse) if return_lse else out
+
+
 def fa3_fwd(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -132,10 +185,7 @@ def fa3_fwd(
                                      keep_mask=keep_mask, additive_mask=additive_mask, return_lse=return_lse, out=out,
                                      o_acc=o_acc, lse=lse, carry_in=carry_in, write_out=write_out, q_offset=q_offset,
                                      k_offset=k_offset, k_prescaled=k_prescaled, out_blocked=out_blocked)
-    check(lib.mio_fa3_fwd(C.byref(p), _stream()))
-    if return_lse:
-        return out, lse
-    return out
+    return _launch(lib.mio_fa3_fwd, p, out, lse, return_lse)
 
 
 def fa3_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, **kwargs) -> str:
@@ -143,10 +193,7 @@ def fa3_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, **kwargs) -> st
     Takes fa3_fwd's arguments; tensors may live on any device (only their shapes, strides and addresses are read).
     Arguments fa3_fwd refuses raise the same ValueError / RuntimeError."""
     p, _out, _lse, _keep = _fa3_params(q, k, v, **kwargs)
-    r = lib.mio_fa3_route(C.byref(p))
-    if r < 0:
-        raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
-    return _lib.FA3_ROUTES[r]
+    return _route(lib.mio_fa3_route, p, _lib.FA3_ROUTES)
 
 
 def _fa3_params(q, k, v, *, layout="bshd", causal=False, softmax_scale=None, keep_mask=None, additive_mask=None,
@@ -159,22 +206,15 @@ def _fa3_params(q, k, v, *, layout="bshd", causal=False, softmax_scale=None, kee
         raise ValueError(f"Expected 4D tensors for q, k, v but got shapes: q={q.shape}, k={k.shape}, v={v.shape}")
     if layout not in ("bshd", "bhsd"):
         raise ValueError(f"unknown layout {layout}")
-    if k.dtype != q.dtype or v.dtype != q.dtype:
-        raise ValueError("q, k, v must have the same dtype")
-    dt = _dtype_id(q)
+    dt = _qkv_dtype(q, k, v)
     q, k, v = _rows16(q), _rows16(k), _rows16(v)
     si, hi = (1, 2) if layout == "bshd" else (2, 1)
     B, Sq, H, D = q.shape[0], q.shape[si], q.shape[hi], q.shape[3]
     Sk, Hkv = k.shape[si], k.shape[hi]
     if k.shape[0] != B or v.shape != k.shape or k.shape[3] != D:
         raise ValueError(f"incompatible q/k/v shapes: q={q.shape}, k={k.shape}, v={v.shape}")
-    if H % Hkv != 0:
-        raise ValueError(f"num_heads {H} must be a multiple of num_kv_heads {Hkv}")
-    if D % 8 != 0 or D > 128:
-        raise ValueError(f"head_dim must be a multiple of 8 and <= 128, got {D}")
-    scale = (1.0 / math.sqrt(D)) if softmax_scale is None else float(softmax_scale)
-    if not (scale > 0.0):
-        raise ValueError("softmax_scale must be positive")
+    _check_heads(H, Hkv, D)
+    scale = _softmax_scale(D, softmax_scale)
     if keep_mask is not None and additive_mask is not None:
         raise ValueError("give either keep_mask or additive_mask, not both")
 
@@ -184,10 +224,7 @@ def _fa3_params(q, k, v, *, layout="bshd", causal=False, softmax_scale=None, kee
             raise ValueError("out_blocked needs layout 'bshd', k_prescaled, write_out and no out= tensor")
         out = torch.empty((B * Sq + 255) // 256 * 256, H * D, dtype=q.dtype, device=q.device)
     elif write_out:
-        if out is None:
-            out = torch.empty_like(q, memory_format=torch.contiguous_format)
-        elif out.shape != q.shape or out.dtype != q.dtype or out.stride(-1) != 1:
-            raise ValueError("out must match q in shape/dtype with a contiguous last dim")
+        out = _out_like(q, out)
     else:
         out = None
         if o_acc is None:
@@ -314,9 +351,7 @@ def _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen
     if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
         raise ValueError(f"Expected 3D tensors [tokens, heads, head_dim] for q, k, v but got shapes: q={q.shape}, "
                          f"k={k.shape}, v={v.shape}")
-    if k.dtype != q.dtype or v.dtype != q.dtype:
-        raise ValueError("q, k, v must have the same dtype")
-    dt = _dtype_id(q)
+    dt = _qkv_dtype(q, k, v)
     for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
         if cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 1 or not cu.is_contiguous():
             raise ValueError(f"{name} must be a contiguous 1-D int32 tensor of B+1 offsets")
@@ -329,27 +364,16 @@ def _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen
     Tk, Hkv = k.shape[0], k.shape[1]
     if v.shape != k.shape or k.shape[2] != D:
         raise ValueError(f"incompatible q/k/v shapes: q={q.shape}, k={k.shape}, v={v.shape}")
-    if H % Hkv != 0:
-        raise ValueError(f"num_heads {H} must be a multiple of num_kv_heads {Hkv}")
-    if D % 8 != 0 or D > 128:
-        raise ValueError(f"head_dim must be a multiple of 8 and <= 128, got {D}")
-    scale = (1.0 / math.sqrt(D)) if softmax_scale is None else float(softmax_scale)
-    if not (scale > 0.0):
-        raise ValueError("softmax_scale must be positive")
-    if out is None:
-        out = torch.empty_like(q, memory_format=torch.contiguous_format)
-    elif out.shape != q.shape or out.dtype != q.dtype or out.stride(-1) != 1:
-        raise ValueError("out must match q in shape/dtype with a contiguous last dim")
-    lse = torch.empty(H, Tq, dtype=torch.float32, device=q.device) if return_lse else None
+    _check_heads(H, Hkv, D)
+    scale = _softmax_scale(D, softmax_scale)
+    out = _out_like(q, out)
+    lse = _packed_lse(q, return_lse)
 
     p = _lib.FaVarlenParams()
     for dst, t in ((p.q_stride, q), (p.k_stride, k), (p.v_stride, v), (p.o_stride, out)):
         dst[0], dst[1] = t.stride(0), t.stride(1)
     p.q, p.k, p.v, p.o, p.lse = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse)
-    # torch gives empty tensors a null address; nothing is read or written through them then (include/mio_hip.h)
-    for f in ("q", "k", "v", "o"):
-        if not getattr(p, f):
-            setattr(p, f, cu_seqlens_q.data_ptr())
+    _fill_null(p, ("q", "k", "v", "o"), cu_seqlens_q.data_ptr())
     p.cu_seqlens_q, p.cu_seqlens_k = cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr()
     p.B, p.total_q, p.total_k = cu_seqlens_q.numel() - 1, Tq, Tk
     p.max_seqlen_q, p.max_seqlen_k = int(max_seqlen_q), int(max_seqlen_k)
@@ -383,10 +407,7 @@ def flash_attention_varlen(
     _need_cuda(q, k, v, cu_seqlens_q, cu_seqlens_k)
     p, out, lse, _keep = _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal,
                                         softmax_scale=softmax_scale, return_lse=return_lse, out=out)
-    check(lib.mio_fa3_fwd_varlen(C.byref(p), _stream()))
-    if return_lse:
-        return out, lse
-    return out
+    return _launch(lib.mio_fa3_fwd_varlen, p, out, lse, return_lse)
 
 
 def fa3_varlen_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor,
@@ -394,10 +415,7 @@ def fa3_varlen_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqle
     """The kernel flash_attention_varlen(...) would launch (mio_fa3_varlen_route): "empty", "fwd5" or "fwd3", without
     launching.  Tensors may live on any device; arguments flash_attention_varlen refuses raise the same errors."""
     p, _out, _lse, _keep = _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, **kwargs)
-    r = lib.mio_fa3_varlen_route(C.byref(p))
-    if r < 0:
-        raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
-    return _lib.FA3_VARLEN_ROUTES[r]
+    return _route(lib.mio_fa3_varlen_route, p, _lib.FA3_VARLEN_ROUTES)
 
 
 def unpad_input(x: torch.Tensor, keep: torch.Tensor):
@@ -857,9 +875,7 @@ def _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, ma
         raise ValueError(f"Expected a 3D tensor [tokens, heads, head_dim] for q but got shape {q.shape}")
     if k_cache.dim() != 5 or v_cache.shape != k_cache.shape:
         raise ValueError("caches must be [num_blocks, num_layers, block_size, num_kv_heads, head_dim] with equal shapes")
-    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise ValueError("q, k_cache, v_cache must have the same dtype")
-    dt = _dtype_id(q)
+    dt = _qkv_dtype(q, k_cache, v_cache, "q, k_cache, v_cache")
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("caches must be contiguous")
     _i32_dev(cu_seqlens_q, "cu_seqlens_q", 1, "of B+1 offsets", q.device)
@@ -875,31 +891,20 @@ def _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, ma
     nb, L, bs, Hkv, Dc = k_cache.shape
     if Dc != D:
         raise ValueError(f"incompatible q/cache shapes: q={q.shape}, k_cache={k_cache.shape}")
-    if H % Hkv != 0:
-        raise ValueError(f"num_heads {H} must be a multiple of num_kv_heads {Hkv}")
-    if D % 8 != 0 or D > 128:
-        raise ValueError(f"head_dim must be a multiple of 8 and <= 128, got {D}")
+    _check_heads(H, Hkv, D)
     if bs % 64 != 0:
         raise ValueError(f"block_size must be a multiple of 64 for the paged attention kernels, got {bs}")
     if not 0 <= int(layer_idx) < L:
         raise ValueError(f"layer_idx {layer_idx} out of range for a {L}-layer cache")
-    scale = (1.0 / math.sqrt(D)) if softmax_scale is None else float(softmax_scale)
-    if not (scale > 0.0):
-        raise ValueError("softmax_scale must be positive")
-    if out is None:
-        out = torch.empty_like(q, memory_format=torch.contiguous_format)
-    elif out.shape != q.shape or out.dtype != q.dtype or out.stride(-1) != 1:
-        raise ValueError("out must match q in shape/dtype with a contiguous last dim")
-    lse = torch.empty(H, Tq, dtype=torch.float32, device=q.device) if return_lse else None
+    scale = _softmax_scale(D, softmax_scale)
+    out = _out_like(q, out)
+    lse = _packed_lse(q, return_lse)
 
     p = _lib.FaPagedParams()
     for dst, t in ((p.q_stride, q), (p.o_stride, out)):
         dst[0], dst[1] = t.stride(0), t.stride(1)
     p.q, p.k_cache, p.v_cache, p.o, p.lse = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), _ptr(lse)
-    # torch gives empty tensors a null address; nothing is read or written through them then (include/mio_hip.h)
-    for f in ("q", "k_cache", "v_cache", "o"):
-        if not getattr(p, f):
-            setattr(p, f, cu_seqlens_q.data_ptr())
+    _fill_null(p, ("q", "k_cache", "v_cache", "o"), cu_seqlens_q.data_ptr())
     p.cu_seqlens_q, p.seqused_k, p.block_tables = cu_seqlens_q.data_ptr(), seqused_k.data_ptr(), block_tables.data_ptr()
     p.B, p.total_q = B, Tq
     p.max_seqlen_q, p.max_seqlen_k = int(max_seqlen_q), int(max_seqlen_k)
@@ -939,10 +944,7 @@ def flash_attention_varlen_paged(
     p, out, lse, _keep = _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
                                        max_seqlen_k, layer_idx=layer_idx, causal=causal, softmax_scale=softmax_scale,
                                        return_lse=return_lse, out=out)
-    check(lib.mio_fa3_fwd_paged(C.byref(p), _stream()))
-    if return_lse:
-        return out, lse
-    return out
+    return _launch(lib.mio_fa3_fwd_paged, p, out, lse, return_lse)
 
 
 def fa3_paged_route(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
@@ -953,10 +955,7 @@ def fa3_paged_route(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
     errors."""
     p, _out, _lse, _keep = _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
                                          max_seqlen_k, **kwargs)
-    r = lib.mio_fa3_paged_route(C.byref(p))
-    if r < 0:
-        raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
-    return _lib.FA3_PAGED_ROUTES[r]
+    return _route(lib.mio_fa3_paged_route, p, _lib.FA3_PAGED_ROUTES)
 
 
 def paged_attention_forward(query, output, k_cache, v_cache, block_tables, context_lengths, block_size: int,

@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn as nn
 
+import _isa
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -427,52 +429,22 @@ def test_fwd3_accumulator_registers_untouched_by_compiler(tmp_path, type_id, D):
     """fa3_fwd3_kernel keeps O^T, L, Q and the ones operand in accumulator registers Fa3Map<D>::A_Q .. a255 that only
     its inline asm names.  The allocator does not know they are live between asm statements, so the build is only sound
     if no compiler-generated instruction touches them: check the ISA of every instantiation (tools/check_agpr.py)."""
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "ml-inference-optimizer_amd", "csrc")
-    isa = tmp_path / "fa.s"
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I../../include", "-I.", "-Wno-unused-value",
-                    "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", f"-DFA_TYPE_ID={type_id}", f"-DFA_D={D}", "-S",
-                    "--cuda-device-only", "fa3_fwd_inst.hip", "-o", str(isa)], cwd=csrc, check=True, capture_output=True)
-    text = isa.read_text().splitlines()
-    starts = [i for i, l in enumerate(text) if re.match(r"^_Z15fa3_fwd3_kernel\w+:", l)]
-    assert len(starts) >= 2, "causal and full instantiations expected"
-    floor = 16 * (14 - 2 * (D // 32)) - 4 - 8 * (D // 16)  # Fa3Map<D>::A_Q
-    for a in starts:
-        b = next(i for i in range(a, len(text)) if "s_endpgm" in text[i])
-        part = tmp_path / "k.s"
-        part.write_text("\n".join(text[a:b + 1]))
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_agpr.py"), str(part), str(floor)],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, text[a] + "\n" + r.stdout
-        assert not any("scratch_" in l for l in text[a:b + 1]), "register spills in " + text[a]
+    text = _isa.fa_isa(tmp_path, "fa3_fwd_inst.hip", type_id, D)
+    bodies = _isa.kernels(text, "_Z15fa3_fwd3_kernel")
+    assert len(bodies) >= 2, "causal and full instantiations expected"
+    for body in bodies:
+        _isa.check_agpr(tmp_path, body, _isa.fa3_agpr_floor(D))
 
 
 def test_fwd5_two_waves_per_simd_fits_without_spills(tmp_path):
     """fa3_fwd5_kernel runs two waves per SIMD: 256 registers per wave.  It must fit them without scratch (a staggered
     variant that did not fit ran 60 % slower) -- check the ISA metadata of both dtypes' causal instantiation."""
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "ml-inference-optimizer_amd", "csrc")
     for type_id in (0, 1):
-        isa = tmp_path / f"fa{type_id}.s"
-        subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I../../include", "-I.", "-Wno-unused-value",
-                        "-Wno-inline-asm", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", f"-DFA_TYPE_ID={type_id}",
-                        "-DFA_D=64", "-S", "--cuda-device-only", "fa3_fwd_inst.hip", "-o", str(isa)], cwd=csrc, check=True,
-                       capture_output=True)
-        text = isa.read_text()
-        blocks = re.findall(r"\.name:\s+_Z15fa3_fwd5_kernel\w+\n(?:.*\n){0,12}", text)
+        text = _isa.fa_isa(tmp_path, "fa3_fwd_inst.hip", type_id, 64)
+        blocks = _isa.metadata(text, r"_Z15fa3_fwd5_kernel\w+")
         assert len(blocks) >= 8, "fa3_fwd5_kernel: causal / full x {pre-scaled, plain K, ring carry, blocked output}"
         for blk in blocks:
-            assert re.search(r"\.private_segment_fixed_size:\s+0\b", blk), blk
-            assert re.search(r"\.vgpr_spill_count:\s+0\b", blk), blk
-            assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= 256, blk
+            _isa.check_fits_256(blk)
 
 
 def _inflight_load_reads(body):
@@ -510,49 +482,25 @@ def test_fwd1_staging_registers_not_moved_in_flight(tmp_path, type_id, D):
     """fa3_fwd_kernel stages K / V tiles with asm loads the compiler cannot see (no s_waitcnt of its own); they are sound
     only while hipcc leaves their destination registers alone until wait_loads().  At D = 128 hipcc copied them into AGPRs
     right after issue (every output of the Sq <= 128 launches wrong); that path now uses compiler-visible loads."""
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "ml-inference-optimizer_amd", "csrc")
-    isa = tmp_path / "fa.s"
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I../../include", "-I.", "-Wno-unused-value",
-                    "-Wno-inline-asm", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", f"-DFA_TYPE_ID={type_id}",
-                    f"-DFA_D={D}", "-S", "--cuda-device-only", "fa3_fwd_inst.hip", "-o", str(isa)], cwd=csrc, check=True,
-                   capture_output=True)
-    text = isa.read_text().splitlines()
-    starts = [i for i, l in enumerate(text) if re.match(r"^_Z14fa3_fwd_kernel\w+:", l)]
-    assert len(starts) == 6  # causal x mask kind
-    for a in starts:
-        b = next(i for i in range(a, len(text)) if "s_endpgm" in text[i])
-        hits = _inflight_load_reads(text[a:b + 1])
-        assert not hits, text[a] + "\n" + "\n".join(hits[:8])
+    bodies = _isa.kernels(_isa.fa_isa(tmp_path, "fa3_fwd_inst.hip", type_id, D), "_Z14fa3_fwd_kernel")
+    assert len(bodies) == 6  # causal x mask kind
+    for body in bodies:
+        hits = _inflight_load_reads(body)
+        assert not hits, body[0] + "\n" + "\n".join(hits[:8])
 
 
 def test_gemm8w_kernel_isa_soundness(tmp_path):
     """(a) gemm8w_kernel (the product's 256x256-tile GEMM, two waves per SIMD, compiler-managed registers): every shipped
     instantiation fits 256 registers without scratch -- a spill inside its K loop would put a vmcnt(0) in front of the
     counted waits."""
-    import shutil
     import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "ml-inference-optimizer_amd", "csrc")
-    isa = tmp_path / "gemm.s"
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I../../include", "-I.", "-Wno-unused-value",
-                    "-Wno-inline-asm", "-DGEMM_TYPE_ID=0", "-DMIO_DIAG", "-S", "--cuda-device-only", "gemm_inst.hip", "-o", str(isa)],
-                   cwd=csrc, check=True, capture_output=True)
+    isa = _isa.device_isa(tmp_path, "gemm_inst.hip", ["GEMM_TYPE_ID=0", "MIO_DIAG"], attention=False)
     full = isa.read_text()
-    blocks = re.findall(r"\.name:\s+_Z13gemm8w_kernel\w+Li0EEv7GemmDev\n(?:.*\n){0,12}", full)  # VAR = 0: what the product launches
+    blocks = _isa.metadata(full, r"_Z13gemm8w_kernel\w+Li0EEv7GemmDev")  # VAR = 0: what the product launches
     assert len(blocks) >= 9, "gemm8w_kernel: 5 plain + 4 residual instantiations (+ SwiGLU) expected"
     for blk in blocks:
         erf = "DF16bLi2E" in blk  # exact-erf GELU: erff() in the read-out may spill a few registers (slow, still correct)
-        if not erf:
-            assert re.search(r"\.private_segment_fixed_size:\s+0\b", blk), blk
-            assert re.search(r"\.vgpr_spill_count:\s+0\b", blk), blk
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= 256, blk
+        _isa.check_fits_256(blk, no_spill=not erf)
     # (b) no store whose data registers are rewritten by the very next instruction (tools/check_store_war.py: the hazard
     # behind round 3's wrong lanes -- hipcc leaves no wait state behind a buffer_store with a register soffset)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_store_war.py"), str(isa), "gemm8w_kernel", "1"],

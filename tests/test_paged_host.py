@@ -3,17 +3,12 @@
 ops raises on bad arguments before it calls the library, and the paged kernels pass the ISA soundness checks of the dense
 pipelined kernels."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
-import sys
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ml-inference-optimizer_amd", "csrc")
+import _isa
+
 ALIGNED = 1 << 20  # a fake 16-byte aligned device address: nothing is dereferenced by the route query
 
 
@@ -179,28 +174,14 @@ def test_reshape_and_cache_varlen_errors_without_gpu():
     assert call(T=0) == 0 and call(B=0) == 0  # nothing to write: no launch
 
 
-def _isa(tmp_path, type_id, D):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    isa = tmp_path / f"paged_{type_id}_{D}.s"
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I../../include", "-I.", "-Wno-unused-value",
-                    "-Wno-inline-asm", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", f"-DFA_TYPE_ID={type_id}",
-                    f"-DFA_D={D}", "-S", "--cuda-device-only", "fa3_paged_inst.hip", "-o", str(isa)], cwd=CSRC, check=True,
-                   capture_output=True)
-    return isa.read_text()
-
-
 @pytest.mark.parametrize("type_id", [0, 1])
 def test_fwd5_paged_fits_without_spills(tmp_path, type_id):
     """The paged form of fa3_fwd5_kernel runs two waves per SIMD like the dense one: no scratch, at most 256 VGPRs."""
-    text = _isa(tmp_path, type_id, 64)
-    blocks = re.findall(r"\.name:\s+_Z21fa3_fwd5_paged_kernel\w+\n(?:.*\n){0,12}", text)
+    text = _isa.fa_isa(tmp_path, "fa3_seq_inst.hip", type_id, 64)
+    blocks = _isa.metadata(text, r"_Z21fa3_fwd5_paged_kernel\w+")
     assert len(blocks) == 2, "causal and full instantiations expected"
     for blk in blocks:
-        assert re.search(r"\.private_segment_fixed_size:\s+0\b", blk), blk
-        assert re.search(r"\.vgpr_spill_count:\s+0\b", blk), blk
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= 256, blk
+        _isa.check_fits_256(blk)
     assert "scratch_" not in text
 
 
@@ -208,15 +189,7 @@ def test_fwd5_paged_fits_without_spills(tmp_path, type_id):
 def test_fwd3_paged_accumulator_registers_untouched_by_compiler(tmp_path, type_id, D):
     """The paged form of fa3_fwd3_kernel owns the same accumulator registers (Fa3Map<D>::A_Q and up) through inline asm:
     no compiler-generated instruction may touch them (tools/check_agpr.py), and nothing spills."""
-    text = _isa(tmp_path, type_id, D).splitlines()
-    starts = [i for i, l in enumerate(text) if re.match(r"^_Z21fa3_fwd3_paged_kernel\w+:", l)]
-    assert len(starts) == 2, "causal and full instantiations expected"
-    floor = 16 * (14 - 2 * (D // 32)) - 4 - 8 * (D // 16)  # Fa3Map<D>::A_Q
-    for a in starts:
-        b = next(i for i in range(a, len(text)) if "s_endpgm" in text[i])
-        part = tmp_path / "k.s"
-        part.write_text("\n".join(text[a:b + 1]))
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_agpr.py"), str(part), str(floor)],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, text[a] + "\n" + r.stdout
-        assert not any("scratch_" in l for l in text[a:b + 1]), "register spills in " + text[a]
+    bodies = _isa.kernels(_isa.fa_isa(tmp_path, "fa3_seq_inst.hip", type_id, D), "_Z21fa3_fwd3_paged_kernel")
+    assert len(bodies) == 2, "causal and full instantiations expected"
+    for body in bodies:
+        _isa.check_agpr(tmp_path, body, _isa.fa3_agpr_floor(D))
