@@ -350,6 +350,30 @@ int mio_layernorm_fwd(const void* x, const void* residual, const void* weight, c
                       int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sliding-window attention forward (flash-attn's window_size = (left, right)): the params of
+ * mio_fa3_fwd / mio_fa3_fwd_varlen / mio_fa3_fwd_paged unchanged, plus the window.  Each value is -1
+ * (unbounded) or >= 0; query row i sees key j iff j >= i + off - window_left (left >= 0) and
+ * j <= i + off + window_right (right >= 0) and the causal / length rules allow it, with
+ * off = q_offset - k_offset (dense) or Lk_b - Lq_b (varlen, paged: bottom-right per sequence).
+ * causal means window_right = 0 (-1 or 0 accepted).  Rows with no visible key get o = 0, lse = -inf.
+ * (-1, -1) is the existing entry point exactly (same route, same output).  Any other window runs the
+ * windowed fwd5 (head dim <= 64) / fwd3 kernels, which walk only the KV tiles inside each query
+ * block's window; the routes report MIO_FA3_ROUTE_FWD5 / FWD3 / EMPTY for them (a dense launch with
+ * Sk = 0 has no key to window and takes the unwindowed route).  Refused under a window: a window
+ * value below -1, causal with window_right > 0, and for the dense form a mask, the ring carry
+ * (o_acc / carry_in), k_prescaled, o_blocked, K / V spans of 4 GiB or more; lengths and offsets of
+ * 2^28 or more.
+ * ------------------------------------------------------------------------------------------ */
+int mio_fa3_fwd_window(const mio_fa3_fwd_params_t* p, int32_t window_left, int32_t window_right, void* stream);
+int32_t mio_fa3_route_window(const mio_fa3_fwd_params_t* p, int32_t window_left, int32_t window_right);
+int mio_fa3_fwd_varlen_window(const mio_fa3_varlen_params_t* p, int32_t window_left, int32_t window_right,
+                              void* stream);
+int32_t mio_fa3_varlen_route_window(const mio_fa3_varlen_params_t* p, int32_t window_left, int32_t window_right);
+int mio_fa3_fwd_paged_window(const mio_fa3_paged_params_t* p, int32_t window_left, int32_t window_right,
+                             void* stream);
+int32_t mio_fa3_paged_route_window(const mio_fa3_paged_params_t* p, int32_t window_left, int32_t window_right);
+
+/* ------------------------------------------------------------------------------------------
  * Paged-KV decode attention.  Replaces triton_paged_attention_forward ->
  * _paged_attention_fwd_kernel (kernels/triton/attention_kernels.py:1206-1311; kernel :628-808).
  * q/o [B,H,q_len,D] (strides b,h,s; d contiguous); caches [num_blocks, L, block_size, Hkv, D]
@@ -363,6 +387,39 @@ int mio_fa3_decode_paged(const void* q, void* o, const void* k_cache, const void
                          int32_t Hkv, int32_t q_len, int32_t D, int32_t num_layers, int32_t layer_idx,
                          int32_t block_size, int32_t max_blocks_per_seq, int32_t max_ctx, float scale,
                          int32_t dtype, void* workspace, void* stream);
+
+/* Sliding-window decode (flash-attn's window_size = (left, right), decode form).  The arguments of
+ * mio_fa3_decode_paged plus the window: row qi of q_len sees the cached keys j < ctx_b with
+ * j >= ctx_b - q_len + qi - window_left; rows with no visible key get o = 0.  window_left is -1
+ * (unbounded) or >= 0; window_right must be -1 (decode has no upper bound).  (-1, -1) is
+ * mio_fa3_decode_paged exactly.  The splits cover [max(0, ctx_b - q_len - window_left), ctx_b) and
+ * their count is sized from min(max_ctx, window_left + q_len), so mio_fa3_decode_workspace_bytes
+ * for max_ctx covers every windowed launch as well.  Refused: a window value below -1, and
+ * window_right != -1. */
+int mio_fa3_decode_paged_window(const void* q, void* o, const void* k_cache, const void* v_cache,
+                                const int32_t* block_tables, const int32_t* context_lengths,
+                                const int64_t q_stride[3], const int64_t o_stride[3], int32_t B, int32_t H,
+                                int32_t Hkv, int32_t q_len, int32_t D, int32_t num_layers, int32_t layer_idx,
+                                int32_t block_size, int32_t max_blocks_per_seq, int32_t max_ctx, float scale,
+                                int32_t window_left, int32_t window_right, int32_t dtype, void* workspace,
+                                void* stream);
+
+/* Which decode kernel a mio_fa3_decode_paged_window launch with these arguments takes (host-only: no
+ * pointer is dereferenced, no stream is touched; the same argument checks).  Returns a
+ * mio_decode_route_t, or <0 with mio_last_error() set when the launch would be refused.  The kernel
+ * heuristics see the window span min(max_ctx, window_left + q_len) as the context length. */
+typedef enum {
+  MIO_DEC_ROUTE_HEAD = 0, /* decode_paged_kernel: one workgroup per (query row, split)              */
+  MIO_DEC_ROUTE_ROWS = 1, /* decode_rows_kernel: whole token rows, one workgroup per (sequence, split) */
+  MIO_DEC_ROUTE_GQA = 2   /* decode_gqa_kernel: matrix-core, one workgroup per (sequence, kv head, split) */
+} mio_decode_route_t;
+int mio_fa3_decode_window_route(const void* q, void* o, const void* k_cache, const void* v_cache,
+                                const int32_t* block_tables, const int32_t* context_lengths,
+                                const int64_t q_stride[3], const int64_t o_stride[3], int32_t B, int32_t H,
+                                int32_t Hkv, int32_t q_len, int32_t D, int32_t num_layers, int32_t layer_idx,
+                                int32_t block_size, int32_t max_blocks_per_seq, int32_t max_ctx, float scale,
+                                int32_t window_left, int32_t window_right, int32_t dtype, void* workspace,
+                                void* stream);
 
 /* Scatter the current token's K/V into the paged cache at position context_len-1.
  * Replaces triton_reshape_and_cache -> _reshape_and_cache_kernel

@@ -6,6 +6,7 @@
 // :1206-1311) and _reshape_and_cache_kernel (:811-905, wrapper :1314-1407).
 // Cache layout [num_blocks, num_layers, block_size, Hkv, D]; token t of sequence b lives in physical
 // block block_tables[b, t / block_size] at slot t % block_size (:728-751).
+#include <algorithm>
 #include <cstdlib>
 #include <mutex>
 
@@ -106,163 +107,21 @@ static inline bool dec_rows_ok(int B, int H, int Hkv, int q_len, int D, int max_
   return cpt >= 16 && cpt <= 256 && (cpt & (cpt - 1)) == 0 && qn == 1;  // 2 .. 16 query vectors per key: decode_gqa_kernel
 }
 
-// CPRP = chunks-per-row padded to a power of two (8 for D <= 64, 16 for D <= 128)
+// CPRP = chunks-per-row padded to a power of two (8 for D <= 64, 16 for D <= 128).  The body (decode_paged_body.inc) is shared
+// with the sliding-window form decode_paged_win_kernel (WIN, `wleft` keys to the left): row qi of sequence b sees keys
+// max(0, ctx - q_len + qi - wleft) .. ctx - 1, the splits cover [max(0, ctx - q_len - wleft), ctx) and each row (one per
+// workgroup here) starts its walk at its own first key.  WIN = false compiles to the kernel as it was before the window.
 template <typename T, int CPRP, int U>
 __global__ __launch_bounds__(256) void decode_paged_kernel(const DecDev p) {
-  constexpr int TPI = 64 / CPRP;  // tokens per wave-iteration
-  constexpr int NSTATE = 4 * TPI;
-  __shared__ float s_o[NSTATE][CPRP * 8 + 1];
-  __shared__ float s_m[NSTATE], s_l[NSTATE];
+  constexpr bool WIN = false;
+  [[maybe_unused]] constexpr int wleft = 0;
+#include "decode_paged_body.inc"
+}
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int t = lane / CPRP, c = lane % CPRP;
-  const int row = blockIdx.x;  // (b, h, qi)
-  const int split = blockIdx.y;
-  const int qi = row % p.q_len;
-  const int h = (row / p.q_len) % p.H;
-  const int b = row / (p.q_len * p.H);
-  const int kvh = h / (p.H / p.Hkv);
-  const int ctx = p.cl[b];
-  const int begin = split * p.split_len;
-  int end = begin + p.split_len;
-  if (end > ctx) end = ctx;
-  const bool c_ok = (8 * c < p.D);
-
-  float qf[8];
-  {
-    u32x4_t raw = {0, 0, 0, 0};
-    if (c_ok) raw = *(const u32x4_t*)((const T*)p.q + b * p.qs_b + h * p.qs_h + (int64_t)qi * p.qs_s + 8 * c);
-    const typename DT<T>::x8 v = __builtin_bit_cast(typename DT<T>::x8, raw);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) qf[i] = (float)v[i] * p.scale;
-  }
-
-  float m = -INFINITY, l = 0.f, o[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = 0.f;
-
-  const int64_t tok_stride = (int64_t)p.Hkv * p.D;
-  const int64_t blk_stride = (int64_t)p.L * p.bs * tok_stride;
-
-  // U wave-iterations (U * TPI tokens per wave) per batch, two batches in flight: the K/V rows of batch i+1 and the
-  // block-table entries of batch i+2 are requested before batch i is reduced, and one max / rescale serves the U
-  // tokens of a batch.  Measured (tools/dbg/dec_sweep.sh): U = 1 .. 4 are within 2 % of each other, U = 8 is 3-5 %
-  // slower -- the kernel is bound by the 128-byte-pieces-at-token-stride access pattern (5.2-5.4 TB/s at B 64), not
-  // by loads in flight.
-  constexpr int STEP = 4 * TPI;  // tokens the workgroup's four waves cover per iteration
-  // Loads are unconditional (addresses clamped to the split's last token / the row's first chunk, values masked in
-  // `reduce`): predicated loads become branches, and hipcc drains vmcnt at every join, which serialises the batches.
-  const int last = end - 1;  // >= begin here: empty splits skip the loop
-  const int coff = c_ok ? 8 * c : 0;
-  const int64_t lay_off = (int64_t)p.layer * p.bs * tok_stride + (int64_t)kvh * p.D + coff;
-  const int32_t* btrow = p.bt + (int64_t)b * p.max_blocks;
-  auto load_pb = [&](int pos0, int (&pb)[U]) {
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const int pos = min(pos0 + j * STEP + t, last);
-      pb[j] = btrow[min(pos / p.bs, p.max_blocks - 1)];
-    }
-  };
-  auto load_kv = [&](int pos0, const int (&pb)[U], u32x4_t (&kr)[U], u32x4_t (&vr)[U]) {
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const int pos = min(pos0 + j * STEP + t, last);
-      const int64_t off = (int64_t)pb[j] * blk_stride + lay_off + (int64_t)(pos % p.bs) * tok_stride;
-      kr[j] = *(const u32x4_t*)((const T*)p.kc + off);
-      vr[j] = *(const u32x4_t*)((const T*)p.vc + off);
-    }
-  };
-  auto reduce = [&](int pos0, const int (&pb)[U], const u32x4_t (&kr)[U], const u32x4_t (&vr)[U]) {
-    float sc[U];
-    float m_new = m;
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const typename DT<T>::x8 kv = __builtin_bit_cast(typename DT<T>::x8, kr[j]);
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s += qf[i] * (float)kv[i];  // qf = 0 in the padding chunks (c_ok false)
-#pragma unroll
-      for (int x = 1; x < CPRP; x <<= 1) s += __shfl_xor(s, x, 64);
-      const int pos = pos0 + j * STEP + t;
-      sc[j] = (pos < end && pos / p.bs < p.max_blocks) ? s : -INFINITY;  // uniform within the token's lane group
-      m_new = fmaxf(m_new, sc[j]);
-    }
-    const float m_ref = (m_new == -INFINITY) ? 0.f : m_new;  // nothing seen yet: every weight below is exp(-inf) = 0
-    const float alpha = __expf(m - m_ref);
-    l *= alpha;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] *= alpha;
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const typename DT<T>::x8 vv = __builtin_bit_cast(typename DT<T>::x8, vr[j]);
-      const float pe = __expf(sc[j] - m_ref);
-      l += pe;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] += pe * (float)vv[i];
-    }
-    m = m_new;
-  };
-  {
-    constexpr int BATCH = U * STEP;
-    int pbA[U], pbB[U], pbC[U];  // block ids of the batch being reduced, the next one, and the one after
-    u32x4_t kA[U], vA[U], kB[U], vB[U];
-    auto shift = [&]() {
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        pbA[j] = pbB[j];
-        pbB[j] = pbC[j];
-      }
-    };
-    int pos0 = begin + wave * TPI;
-    if (begin >= end) pos0 = end;  // empty split: no loads at all
-    else {
-    load_pb(pos0, pbA);
-    load_pb(pos0 + BATCH, pbB);
-    load_kv(pos0, pbA, kA, vA);
-    }
-    while (pos0 < end) {
-      load_pb(pos0 + 2 * BATCH, pbC);
-      load_kv(pos0 + BATCH, pbB, kB, vB);
-      reduce(pos0, pbA, kA, vA);
-      pos0 += BATCH;
-      if (pos0 >= end) break;
-      shift();
-      load_pb(pos0 + 2 * BATCH, pbC);
-      load_kv(pos0 + BATCH, pbB, kA, vA);
-      reduce(pos0, pbA, kB, vB);
-      pos0 += BATCH;
-      shift();
-    }
-  }
-
-  // ---- merge the NSTATE per-(wave, token-slot) states
-  const int g = wave * TPI + t;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s_o[g][8 * c + i] = o[i];
-  if (c == 0) {
-    s_m[g] = m;
-    s_l[g] = l;
-  }
-  __syncthreads();
-  if (tid < p.D) {
-    float M = -INFINITY;
-    for (int j = 0; j < NSTATE; ++j) M = fmaxf(M, s_m[j]);
-    float Lsum = 0.f, acc = 0.f;
-    if (M != -INFINITY) {
-      for (int j = 0; j < NSTATE; ++j) {
-        const float w = __expf(s_m[j] - M);
-        Lsum += s_l[j] * w;
-        acc += s_o[j][tid] * w;
-      }
-    }
-    const float val = (Lsum > 0.f) ? acc / Lsum : 0.f;  // empty context -> 0 (attention_kernels.py:802)
-    if (p.nsplit == 1) {
-      ((T*)p.o)[b * p.os_b + h * p.os_h + (int64_t)qi * p.os_s + tid] = (T)val;
-    } else {
-      p.ws_o[((int64_t)row * p.nsplit + split) * p.D + tid] = val;
-      if (tid == 0) p.ws_lse[(int64_t)row * p.nsplit + split] = (Lsum > 0.f) ? M + __logf(Lsum) : -INFINITY;
-    }
-  }
+template <typename T, int CPRP, int U>
+__global__ __launch_bounds__(256) void decode_paged_win_kernel(const DecDev p, int wleft) {
+  constexpr bool WIN = true;
+#include "decode_paged_body.inc"
 }
 
 // ---- whole-token-row variant -------------------------------------------------------------------------------------------
@@ -276,176 +135,19 @@ __global__ __launch_bounds__(256) void decode_paged_kernel(const DecDev p) {
 //   CPT >= 64: the row is NPART = CPT / 64 wave-loads; wave w takes part w % NPART of tokens (w / NPART) + k * (4 / NPART)
 //   CPT <  64: one wave-load holds TPL = 64 / CPT tokens; wave w takes token slots 4 k + w
 // Same clamped-address / masked-score loop as decode_paged_kernel, batches of U token slots, double-buffered.
+// The body (decode_rows_body.inc) is shared with the sliding-window form decode_rows_win_kernel: splits as in
+// decode_paged_win_kernel, and query q's keys below its own first key are masked per score.
 template <typename T, int CPR, int QN>
 __global__ __launch_bounds__(256) void decode_rows_kernel(const DecDev p) {
-  constexpr int U = 2;  // token slots per batch (U = 4 measured the same within 2 %)
-  __shared__ float s_st[4][64][QN][10];  // per (wave, lane, query): o[8], m, l
+  constexpr bool WIN = false;
+  [[maybe_unused]] constexpr int wleft = 0;
+#include "decode_rows_body.inc"
+}
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x, split = blockIdx.y;
-  const int CPT = p.Hkv * CPR;
-  const int npart = CPT >= 64 ? CPT / 64 : 1;
-  const int tpl = CPT >= 64 ? 1 : 64 / CPT;             // tokens per wave-load
-  const int part = wave % npart, tslot = wave / npart;  // this wave's slice of the row / token slot
-  const int wpp = 4 / npart;                            // waves per part
-  const int tl = CPT >= 64 ? 0 : lane / CPT;            // token inside the wave-load
-  const int cidx = CPT >= 64 ? part * 64 + lane : lane % CPT;  // 16-byte chunk of the token row
-  const int kvh = cidx / CPR, c = cidx % CPR;
-  const int rep = p.H / p.Hkv;
-  const int ctx = p.cl[b];
-  const int begin = split * p.split_len;
-  int end = begin + p.split_len;
-  if (end > ctx) end = ctx;
-
-  float qf[QN][8];
-#pragma unroll
-  for (int j = 0; j < QN; ++j) {
-    const int h = kvh * rep + j / p.q_len, qi = j % p.q_len;
-    const u32x4_t raw = *(const u32x4_t*)((const T*)p.q + b * p.qs_b + h * p.qs_h + (int64_t)qi * p.qs_s + 8 * c);
-    const typename DT<T>::x8 v = __builtin_bit_cast(typename DT<T>::x8, raw);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) qf[j][i] = (float)v[i] * p.scale;
-  }
-  float m[QN], l[QN], o[QN][8];
-#pragma unroll
-  for (int j = 0; j < QN; ++j) {
-    m[j] = -INFINITY;
-    l[j] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[j][i] = 0.f;
-  }
-
-  const int64_t tok_stride = (int64_t)p.Hkv * p.D;
-  const int64_t blk_stride = (int64_t)p.L * p.bs * tok_stride;
-  const int64_t lay_off = (int64_t)p.layer * p.bs * tok_stride + (int64_t)cidx * 8;
-  const int32_t* btrow = p.bt + (int64_t)b * p.max_blocks;
-  const int step = wpp * tpl;  // tokens the workgroup covers per slot
-  const int last = end - 1;
-  auto tok = [&](int pos0, int j) { return pos0 + j * step + tl; };
-  auto load_pb = [&](int pos0, int (&pb)[U]) {
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const int pos = min(tok(pos0, j), last);
-      pb[j] = btrow[min(pos / p.bs, p.max_blocks - 1)];
-    }
-  };
-  auto load_kv = [&](int pos0, const int (&pb)[U], u32x4_t (&kr)[U], u32x4_t (&vr)[U]) {
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const int pos = min(tok(pos0, j), last);
-      const int64_t off = (int64_t)pb[j] * blk_stride + lay_off + (int64_t)(pos % p.bs) * tok_stride;
-      kr[j] = *(const u32x4_t*)((const T*)p.kc + off);
-      vr[j] = *(const u32x4_t*)((const T*)p.vc + off);
-    }
-  };
-  auto reduce = [&](int pos0, const u32x4_t (&kr)[U], const u32x4_t (&vr)[U]) {
-#pragma unroll
-    for (int q = 0; q < QN; ++q) {
-      float sc[U];
-      float m_new = m[q];
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        const typename DT<T>::x8 kv = __builtin_bit_cast(typename DT<T>::x8, kr[j]);
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += qf[q][i] * (float)kv[i];
-#pragma unroll
-        for (int x = 1; x < CPR; x <<= 1) s += __shfl_xor(s, x, 64);
-        const int pos = tok(pos0, j);
-        sc[j] = (pos < end && pos / p.bs < p.max_blocks) ? s : -INFINITY;
-        m_new = fmaxf(m_new, sc[j]);
-      }
-      const float m_ref = (m_new == -INFINITY) ? 0.f : m_new;
-      const float alpha = __expf(m[q] - m_ref);
-      l[q] *= alpha;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[q][i] *= alpha;
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        const typename DT<T>::x8 vv = __builtin_bit_cast(typename DT<T>::x8, vr[j]);
-        const float pe = __expf(sc[j] - m_ref);
-        l[q] += pe;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[q][i] += pe * (float)vv[i];
-      }
-      m[q] = m_new;
-    }
-  };
-  {
-    const int BATCH = U * step;
-    int pbA[U], pbB[U], pbC[U];
-    u32x4_t kA[U], vA[U], kB[U], vB[U];
-    auto shift = [&]() {
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        pbA[j] = pbB[j];
-        pbB[j] = pbC[j];
-      }
-    };
-    int pos0 = begin + tslot * tpl;
-    if (begin >= end) pos0 = end;  // empty split: no loads at all
-    else {
-      load_pb(pos0, pbA);
-      load_pb(pos0 + BATCH, pbB);
-      load_kv(pos0, pbA, kA, vA);
-    }
-    while (pos0 < end) {
-      load_pb(pos0 + 2 * BATCH, pbC);
-      load_kv(pos0 + BATCH, pbB, kB, vB);
-      reduce(pos0, kA, vA);
-      pos0 += BATCH;
-      if (pos0 >= end) break;
-      shift();
-      load_pb(pos0 + 2 * BATCH, pbC);
-      load_kv(pos0 + BATCH, pbB, kA, vA);
-      reduce(pos0, kB, vB);
-      pos0 += BATCH;
-      shift();
-    }
-  }
-  // ---- merge the states of one (chunk of the row, query) held by several waves / token slots
-#pragma unroll
-  for (int q = 0; q < QN; ++q) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s_st[wave][lane][q][i] = o[q][i];
-    s_st[wave][lane][q][8] = m[q];
-    s_st[wave][lane][q][9] = l[q];
-  }
-  __syncthreads();
-  if (tslot == 0 && tl == 0) {  // one lane per chunk of the row: its own state first, then the others'
-#pragma unroll
-    for (int q = 0; q < QN; ++q) {
-      float M = -INFINITY;
-      for (int w = part; w < 4; w += npart)
-        for (int t2 = 0; t2 < tpl; ++t2) M = fmaxf(M, s_st[w][(CPT >= 64 ? lane : t2 * CPT + cidx)][q][8]);
-      float Ls = 0.f, acc[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-      if (M != -INFINITY) {
-        for (int w = part; w < 4; w += npart)
-          for (int t2 = 0; t2 < tpl; ++t2) {
-            const float* st = s_st[w][(CPT >= 64 ? lane : t2 * CPT + cidx)][q];
-            const float wgt = __expf(st[8] - M);
-            Ls += st[9] * wgt;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[i] += st[i] * wgt;
-          }
-      }
-      const float inv = (Ls > 0.f) ? 1.f / Ls : 0.f;  // empty context -> 0 (attention_kernels.py:802)
-      const int h = kvh * rep + q / p.q_len, qi = q % p.q_len;
-      const int64_t row = ((int64_t)b * p.H + h) * p.q_len + qi;
-      if (p.nsplit == 1) {
-        T* op = (T*)p.o + b * p.os_b + h * p.os_h + (int64_t)qi * p.os_s + 8 * c;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) op[i] = (T)(acc[i] * inv);
-      } else {
-        float* wo = p.ws_o + (row * p.nsplit + split) * p.D + 8 * c;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wo[i] = acc[i] * inv;
-        if (c == 0) p.ws_lse[row * p.nsplit + split] = (Ls > 0.f) ? M + __logf(Ls) : -INFINITY;
-      }
-    }
-  }
+template <typename T, int CPR, int QN>
+__global__ __launch_bounds__(256) void decode_rows_win_kernel(const DecDev p, int wleft) {
+  constexpr bool WIN = true;
+#include "decode_rows_body.inc"
 }
 
 template <typename T>
@@ -527,29 +229,34 @@ extern "C" size_t mio_fa3_decode_workspace_bytes(int32_t B, int32_t H, int32_t q
   return (size_t)B * H * q_len * ns * (size_t)(D + 1) * sizeof(float) + 256;
 }
 
-extern "C" int mio_fa3_decode_paged(const void* q, void* o, const void* k_cache, const void* v_cache,
-                                    const int32_t* block_tables, const int32_t* context_lengths,
-                                    const int64_t q_stride[3], const int64_t o_stride[3], int32_t B, int32_t H,
-                                    int32_t Hkv, int32_t q_len, int32_t D, int32_t num_layers, int32_t layer_idx,
-                                    int32_t block_size, int32_t max_blocks_per_seq, int32_t max_ctx, float scale,
-                                    int32_t dtype, void* workspace, void* stream) {
-  MIO_CHECK(q && o && k_cache && v_cache && block_tables && context_lengths, "mio_fa3_decode_paged: null pointer");
-  MIO_CHECK(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && q_len > 0, "mio_fa3_decode_paged: bad sizes");
-  MIO_CHECK(D >= 8 && D <= 128 && D % 8 == 0, "mio_fa3_decode_paged: head_dim must be a multiple of 8 in [8,128]");
-  MIO_CHECK(layer_idx >= 0 && layer_idx < num_layers, "mio_fa3_decode_paged: layer_idx out of range");
-  MIO_CHECK(block_size > 0 && max_blocks_per_seq > 0 && max_ctx >= 0, "mio_fa3_decode_paged: bad cache geometry");
-  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_fa3_decode_paged: dtype must be bf16 or fp16");
+// The checks, kernel choice and split geometry of a decode launch, shared by mio_fa3_decode_paged (wleft = -1), its windowed
+// form and the host-only route query; fn prefixes the messages.  route: a mio_decode_route_t.  With a window the kernel
+// heuristics and the split count see the span min(max_ctx, wleft + q_len) as the context length: no split lies past the
+// window, and the split count is at most the one of max_ctx (every dec_nsplit* grows with the context length), so
+// mio_fa3_decode_workspace_bytes(max_ctx) covers it.
+static int dec_plan(DecDev& p, int& route, const std::string& fn, const void* q, void* o, const void* k_cache,
+                    const void* v_cache, const int32_t* block_tables, const int32_t* context_lengths,
+                    const int64_t q_stride[3], const int64_t o_stride[3], int32_t B, int32_t H, int32_t Hkv,
+                    int32_t q_len, int32_t D, int32_t num_layers, int32_t layer_idx, int32_t block_size,
+                    int32_t max_blocks_per_seq, int32_t max_ctx, float scale, int32_t dtype, int32_t wleft) {
+  MIO_CHECK(q && o && k_cache && v_cache && block_tables && context_lengths, fn + ": null pointer");
+  MIO_CHECK(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && q_len > 0, fn + ": bad sizes");
+  MIO_CHECK(D >= 8 && D <= 128 && D % 8 == 0, fn + ": head_dim must be a multiple of 8 in [8,128]");
+  MIO_CHECK(layer_idx >= 0 && layer_idx < num_layers, fn + ": layer_idx out of range");
+  MIO_CHECK(block_size > 0 && max_blocks_per_seq > 0 && max_ctx >= 0, fn + ": bad cache geometry");
+  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, fn + ": dtype must be bf16 or fp16");
   MIO_CHECK(q_stride[0] % 8 == 0 && q_stride[1] % 8 == 0 && q_stride[2] % 8 == 0 && mio_aligned16(q) &&
                 mio_aligned16(k_cache) && mio_aligned16(v_cache),
-            "mio_fa3_decode_paged: q/cache rows must be 16-byte aligned");
-  DecDev p;
+            fn + ": q/cache rows must be 16-byte aligned");
   p.q = q; p.o = o; p.kc = k_cache; p.vc = v_cache; p.bt = block_tables; p.cl = context_lengths;
   p.qs_b = q_stride[0]; p.qs_h = q_stride[1]; p.qs_s = q_stride[2];
   p.os_b = o_stride[0]; p.os_h = o_stride[1]; p.os_s = o_stride[2];
   p.B = B; p.H = H; p.Hkv = Hkv; p.q_len = q_len; p.D = D; p.L = num_layers; p.layer = layer_idx;
   p.bs = block_size; p.max_blocks = max_blocks_per_seq; p.scale = scale;
-  bool rows_kernel = dec_rows_ok(B, H, Hkv, q_len, D, max_ctx);
-  bool gqa_kernel = dec_gqa_ok(B, H, Hkv, q_len, D, max_ctx, block_size, o_stride, o);
+  // the keys a sequence's splits cover: all of max_ctx, or the window span
+  const int span = (wleft >= 0 && (int64_t)wleft + q_len < max_ctx) ? wleft + q_len : max_ctx;
+  bool rows_kernel = dec_rows_ok(B, H, Hkv, q_len, D, span);
+  bool gqa_kernel = dec_gqa_ok(B, H, Hkv, q_len, D, span, block_size, o_stride, o);
 #ifdef MIO_DIAG
   if (mio_dbg_get(6) == 1) rows_kernel = gqa_kernel = false;  // A/B: the per-head kernel (tools/dbg/dec_rows_ab.py)
   if (mio_dbg_get(6) == 2) gqa_kernel = false;                // A/B: rows kernel where it applies
@@ -558,30 +265,133 @@ extern "C" int mio_fa3_decode_paged(const void* q, void* o, const void* k_cache,
                  o_stride[2] % 8 == 0 && mio_aligned16(o);
 #endif
   if (gqa_kernel) rows_kernel = false;
-  p.nsplit = gqa_kernel ? dec_nsplit_gqa((int64_t)B * Hkv, max_ctx, block_size, D)
-                        : rows_kernel ? dec_nsplit_rows(B, max_ctx) : dec_nsplit(B, H, q_len, max_ctx);
-  int sl = (max_ctx + p.nsplit - 1) / p.nsplit;
+  route = gqa_kernel ? MIO_DEC_ROUTE_GQA : rows_kernel ? MIO_DEC_ROUTE_ROWS : MIO_DEC_ROUTE_HEAD;
+  p.nsplit = gqa_kernel ? dec_nsplit_gqa((int64_t)B * Hkv, span, block_size, D)
+                        : rows_kernel ? dec_nsplit_rows(B, span) : dec_nsplit(B, H, q_len, span);
+  int sl = (span + p.nsplit - 1) / p.nsplit;
   const int gran = gqa_kernel ? 128 : 32;
   sl = (sl + gran - 1) / gran * gran;
   if (sl < gran) sl = gran;
   p.split_len = sl;
-  MIO_CHECK(p.nsplit == 1 || workspace != nullptr, "mio_fa3_decode_paged: workspace required");
+  return 0;
+}
+
+// the launches of one route; wleft >= 0 takes the windowed form of its kernel
+template <typename T>
+static int dec_run(const DecDev& p, int route, int wleft, hipStream_t st) {
+  const int64_t rows = (int64_t)p.B * p.H * p.q_len;
+  if (wleft < 0) {
+    if (route == MIO_DEC_ROUTE_GQA) return dec_launch_gqa<T>(p, (unsigned)rows, st);
+    if (route == MIO_DEC_ROUTE_ROWS) dec_launch_rows<T>(p, (p.H / p.Hkv) * p.q_len, (unsigned)rows, st);
+    else dec_launch<T>(p, dim3((unsigned)rows, (unsigned)p.nsplit), st);
+    return 0;
+  }
+  if (route == MIO_DEC_ROUTE_GQA) {
+    static std::once_flag once;
+    static hipError_t ea = hipSuccess;
+    std::call_once(once, [&] {
+      ea = hipFuncSetAttribute((const void*)decode_gqa_win_kernel<T, 128>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               dg_smem_bytes<128>());
+      if (ea == hipSuccess)
+        ea = hipFuncSetAttribute((const void*)decode_gqa_win_kernel<T, 64>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 dg_smem_bytes<64>());
+    });
+    if (ea != hipSuccess) return mio_fail(std::string("decode_gqa_win: hipFuncSetAttribute: ") + hipGetErrorString(ea));
+    const dim3 grid((unsigned)(p.B * p.Hkv), (unsigned)p.nsplit);
+    if (p.D == 128) hipLaunchKernelGGL((decode_gqa_win_kernel<T, 128>), grid, dim3(256), dg_smem_bytes<128>(), st, p, wleft);
+    else hipLaunchKernelGGL((decode_gqa_win_kernel<T, 64>), grid, dim3(256), dg_smem_bytes<64>(), st, p, wleft);
+  } else if (route == MIO_DEC_ROUTE_ROWS) {  // one query vector per key (dec_rows_ok)
+    const dim3 grid((unsigned)p.B, (unsigned)p.nsplit);
+    if (p.D == 64) hipLaunchKernelGGL((decode_rows_win_kernel<T, 8, 1>), grid, dim3(256), 0, st, p, wleft);
+    else hipLaunchKernelGGL((decode_rows_win_kernel<T, 16, 1>), grid, dim3(256), 0, st, p, wleft);
+  } else {
+    const dim3 grid((unsigned)rows, (unsigned)p.nsplit);
+    if (p.D <= 64) hipLaunchKernelGGL((decode_paged_win_kernel<T, 8, 2>), grid, dim3(256), 0, st, p, wleft);
+    else hipLaunchKernelGGL((decode_paged_win_kernel<T, 16, 2>), grid, dim3(256), 0, st, p, wleft);
+  }
+  if (p.nsplit > 1) hipLaunchKernelGGL(decode_reduce_kernel<T>, dim3((unsigned)rows), dim3(128), 0, st, p);
+  return 0;
+}
+
+static int dec_forward(const std::string& fn, const void* q, void* o, const void* k_cache, const void* v_cache,
+                       const int32_t* block_tables, const int32_t* context_lengths, const int64_t q_stride[3],
+                       const int64_t o_stride[3], int32_t B, int32_t H, int32_t Hkv, int32_t q_len, int32_t D,
+                       int32_t num_layers, int32_t layer_idx, int32_t block_size, int32_t max_blocks_per_seq,
+                       int32_t max_ctx, float scale, int32_t dtype, int32_t wleft, void* workspace, void* stream) {
+  DecDev p;
+  int route = 0;
+  const int rc = dec_plan(p, route, fn, q, o, k_cache, v_cache, block_tables, context_lengths, q_stride, o_stride, B, H,
+                          Hkv, q_len, D, num_layers, layer_idx, block_size, max_blocks_per_seq, max_ctx, scale, dtype, wleft);
+  if (rc != 0) return rc;
+  MIO_CHECK(p.nsplit == 1 || workspace != nullptr, fn + ": workspace required");
   const int64_t rows = (int64_t)B * H * q_len;
   p.ws_o = (float*)workspace;
   p.ws_lse = p.ws_o ? p.ws_o + rows * p.nsplit * D : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)rows, (unsigned)p.nsplit), block(256);
-  if (gqa_kernel) {
-    const int rc = (dtype == MIO_BF16) ? dec_launch_gqa<__bf16>(p, (unsigned)rows, st) : dec_launch_gqa<_Float16>(p, (unsigned)rows, st);
-    if (rc != 0) return rc;
-  } else if (rows_kernel) {
-    if (dtype == MIO_BF16) dec_launch_rows<__bf16>(p, (H / Hkv) * q_len, (unsigned)rows, st);
-    else dec_launch_rows<_Float16>(p, (H / Hkv) * q_len, (unsigned)rows, st);
-  } else if (dtype == MIO_BF16) dec_launch<__bf16>(p, grid, st);
-  else dec_launch<_Float16>(p, grid, st);
+  const int rl = (dtype == MIO_BF16) ? dec_run<__bf16>(p, route, wleft, st) : dec_run<_Float16>(p, route, wleft, st);
+  if (rl != 0) return rl;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mio_fail(std::string("decode_paged launch: ") + hipGetErrorString(e));
   return 0;
+}
+
+extern "C" int mio_fa3_decode_paged(const void* q, void* o, const void* k_cache, const void* v_cache,
+                                    const int32_t* block_tables, const int32_t* context_lengths,
+                                    const int64_t q_stride[3], const int64_t o_stride[3], int32_t B, int32_t H,
+                                    int32_t Hkv, int32_t q_len, int32_t D, int32_t num_layers, int32_t layer_idx,
+                                    int32_t block_size, int32_t max_blocks_per_seq, int32_t max_ctx, float scale,
+                                    int32_t dtype, void* workspace, void* stream) {
+  return dec_forward("mio_fa3_decode_paged", q, o, k_cache, v_cache, block_tables, context_lengths, q_stride, o_stride, B,
+                     H, Hkv, q_len, D, num_layers, layer_idx, block_size, max_blocks_per_seq, max_ctx, scale, dtype, -1,
+                     workspace, stream);
+}
+
+static int dec_window_check(const char* fn, int32_t window_left, int32_t window_right) {
+  MIO_CHECK(window_left >= -1 && window_right >= -1, std::string(fn) + ": window values must be -1 (unbounded) or >= 0");
+  MIO_CHECK(window_right == -1, std::string(fn) + ": decode takes no right window (window_right must be -1)");
+  return 0;
+}
+
+extern "C" int mio_fa3_decode_paged_window(const void* q, void* o, const void* k_cache, const void* v_cache,
+                                           const int32_t* block_tables, const int32_t* context_lengths,
+                                           const int64_t q_stride[3], const int64_t o_stride[3], int32_t B, int32_t H,
+                                           int32_t Hkv, int32_t q_len, int32_t D, int32_t num_layers, int32_t layer_idx,
+                                           int32_t block_size, int32_t max_blocks_per_seq, int32_t max_ctx, float scale,
+                                           int32_t window_left, int32_t window_right, int32_t dtype, void* workspace,
+                                           void* stream) {
+  const char* fn = "mio_fa3_decode_paged_window";
+  if (dec_window_check(fn, window_left, window_right) != 0) return -1;
+  MIO_CHECK(window_left < 0 || q_len < (1 << 29), std::string(fn) + ": q_len must be below 2^29 under a window");
+  // a window no shorter than max_ctx + q_len is the unbounded one: clamped, so the kernels' bounds stay in int
+  if (window_left >= 0) window_left = (int32_t)std::min<int64_t>(std::min<int64_t>(window_left, (int64_t)max_ctx + q_len), 1 << 29);
+  if (window_left < 0)  // no window: exactly mio_fa3_decode_paged
+    return mio_fa3_decode_paged(q, o, k_cache, v_cache, block_tables, context_lengths, q_stride, o_stride, B, H, Hkv,
+                                q_len, D, num_layers, layer_idx, block_size, max_blocks_per_seq, max_ctx, scale, dtype,
+                                workspace, stream);
+  return dec_forward(fn, q, o, k_cache, v_cache, block_tables, context_lengths, q_stride, o_stride, B, H, Hkv, q_len, D,
+                     num_layers, layer_idx, block_size, max_blocks_per_seq, max_ctx, scale, dtype, window_left, workspace,
+                     stream);
+}
+
+extern "C" int mio_fa3_decode_window_route(const void* q, void* o, const void* k_cache, const void* v_cache,
+                                           const int32_t* block_tables, const int32_t* context_lengths,
+                                           const int64_t q_stride[3], const int64_t o_stride[3], int32_t B, int32_t H,
+                                           int32_t Hkv, int32_t q_len, int32_t D, int32_t num_layers, int32_t layer_idx,
+                                           int32_t block_size, int32_t max_blocks_per_seq, int32_t max_ctx, float scale,
+                                           int32_t window_left, int32_t window_right, int32_t dtype, void* workspace,
+                                           void* stream) {
+  (void)workspace;
+  (void)stream;
+  const char* fn = "mio_fa3_decode_window_route";
+  if (dec_window_check(fn, window_left, window_right) != 0) return -1;
+  MIO_CHECK(window_left < 0 || q_len < (1 << 29), std::string(fn) + ": q_len must be below 2^29 under a window");
+  if (window_left >= 0) window_left = (int32_t)std::min<int64_t>(std::min<int64_t>(window_left, (int64_t)max_ctx + q_len), 1 << 29);
+  DecDev p;
+  int route = 0;
+  const int rc = dec_plan(p, route, fn, q, o, k_cache, v_cache, block_tables, context_lengths, q_stride, o_stride, B, H,
+                          Hkv, q_len, D, num_layers, layer_idx, block_size, max_blocks_per_seq, max_ctx, scale, dtype,
+                          window_left);
+  return rc != 0 ? rc : route;
 }
 
 // ---- reshape_and_cache: one workgroup per sequence, 16-byte chunks over (Hkv, D) --------------------

@@ -263,3 +263,135 @@ extern "C" int mio_fa3_fwd_paged(const mio_fa3_paged_params_t* a, void* stream) 
     return fa3_seq_launch<typename decltype(i)::T, decltype(i)::D>(p, pg, a->causal, (hipStream_t)stream);
   });
 }
+
+// ---- sliding windows (flash-attn's window_size = (left, right)): mio_fa3_*_window.  (-1, -1) is the existing entry point
+// exactly; any other window takes the windowed fwd5 / fwd3 kernels (fa3_win_inst.hip) for every launch with keys.
+
+constexpr int64_t FA_WIN_LEN_MAX = 1 << 28;  // lengths and offsets of a windowed launch (the kernels' bounds stay in int)
+constexpr int32_t FA_WIN_CLAMP = 1 << 29;    // a window wider than every length is the unbounded one: clamped to this
+
+static int fa_window_check(const char* fn, int32_t left, int32_t right, int causal) {
+  MIO_CHECK(left >= -1 && right >= -1, std::string(fn) + ": window values must be -1 (unbounded) or >= 0");
+  MIO_CHECK(!causal || right <= 0, std::string(fn) + ": causal means window_right = 0 (give -1 or 0)");
+  return 0;
+}
+
+static int32_t fa_window_clamp(int32_t w) { return w > FA_WIN_CLAMP ? FA_WIN_CLAMP : w; }
+
+static bool fa_windowed(int32_t left, int32_t right) { return left != -1 || right != -1; }
+
+// the checks a windowed dense launch adds to mio_fa3_fwd's
+static int fa3_window_validate(const mio_fa3_fwd_params_t* a, int32_t left, int32_t right) {
+  const char* fn = "mio_fa3_fwd_window";
+  if (fa3_validate(a) != 0) return -1;
+  if (fa_window_check(fn, left, right, a->causal) != 0) return -1;
+  MIO_CHECK(a->mask_kind == MIO_MASK_NONE, std::string(fn) + ": a window cannot be combined with a mask");
+  MIO_CHECK(a->o_acc == nullptr && !a->carry_in, std::string(fn) + ": a window cannot be combined with the ring carry");
+  MIO_CHECK(!a->k_prescaled, std::string(fn) + ": a window cannot be combined with k_prescaled");
+  MIO_CHECK(!a->o_blocked, std::string(fn) + ": a window cannot be combined with o_blocked");
+  MIO_CHECK((int64_t)a->Sk * a->k_stride[1] * 2 < (1ll << 32) && (int64_t)a->Sk * a->v_stride[1] * 2 < (1ll << 32),
+            std::string(fn) + ": K / V rows of one (batch, head) must span less than 4 GiB under a window");
+  MIO_CHECK(a->Sq < FA_WIN_LEN_MAX && a->Sk < FA_WIN_LEN_MAX && std::abs((int64_t)a->q_offset - a->k_offset) < FA_WIN_LEN_MAX,
+            std::string(fn) + ": Sq, Sk and |q_offset - k_offset| must be below 2^28 under a window");
+  return 0;
+}
+
+extern "C" int32_t mio_fa3_route_window(const mio_fa3_fwd_params_t* a, int32_t window_left, int32_t window_right) {
+  if (!fa_windowed(window_left, window_right)) return mio_fa3_route(a);
+  if (fa3_window_validate(a, window_left, window_right) != 0) return MIO_FA3_ROUTE_INVALID;
+  if (a->Sq == 0) return MIO_FA3_ROUTE_EMPTY;
+  if (a->Sk == 0) return route_of(a);  // no key to window: the unwindowed launch writes the empty rows
+  return dpad_of(a->D) == 64 ? MIO_FA3_ROUTE_FWD5 : MIO_FA3_ROUTE_FWD3;
+}
+
+extern "C" int mio_fa3_fwd_window(const mio_fa3_fwd_params_t* a, int32_t window_left, int32_t window_right, void* stream) {
+  if (!fa_windowed(window_left, window_right)) return mio_fa3_fwd(a, stream);
+  if (fa3_window_validate(a, window_left, window_right) != 0) return -1;
+  if (a->Sq == 0) return 0;
+  if (a->Sk == 0) return mio_fa3_fwd(a, stream);
+  FaDev p = fa_dev(a->q, a->k, a->v, a->o, a->lse, a->B, a->H, a->Hkv, a->D, a->softmax_scale);
+  p.qs_b = a->q_stride[0]; p.qs_s = a->q_stride[1]; p.qs_h = a->q_stride[2];
+  p.ks_b = a->k_stride[0]; p.ks_s = a->k_stride[1]; p.ks_h = a->k_stride[2];
+  p.vs_b = a->v_stride[0]; p.vs_s = a->v_stride[1]; p.vs_h = a->v_stride[2];
+  p.os_b = a->o_stride[0]; p.os_s = a->o_stride[1]; p.os_h = a->o_stride[2];
+  p.Sq = a->Sq; p.Sk = a->Sk;
+  p.q_offset = a->q_offset; p.k_offset = a->k_offset;
+  const int wl = fa_window_clamp(window_left), wr = fa_window_clamp(window_right);
+  return fa_dispatch(a->dtype, a->D, [&](auto i) {
+    return fa3_win_launch<typename decltype(i)::T, decltype(i)::D>(p, a->causal, wl, wr, (hipStream_t)stream);
+  });
+}
+
+static int fa3_varlen_window_validate(const mio_fa3_varlen_params_t* a, int32_t left, int32_t right) {
+  const char* fn = "mio_fa3_fwd_varlen_window";
+  if (fa3_varlen_validate(a) != 0) return -1;
+  if (fa_window_check(fn, left, right, a->causal) != 0) return -1;
+  MIO_CHECK(a->max_seqlen_q < FA_WIN_LEN_MAX && a->max_seqlen_k < FA_WIN_LEN_MAX,
+            std::string(fn) + ": max_seqlen_q / max_seqlen_k must be below 2^28 under a window");
+  return 0;
+}
+
+extern "C" int32_t mio_fa3_varlen_route_window(const mio_fa3_varlen_params_t* a, int32_t window_left, int32_t window_right) {
+  if (!fa_windowed(window_left, window_right)) return mio_fa3_varlen_route(a);
+  if (fa3_varlen_window_validate(a, window_left, window_right) != 0) return MIO_FA3_VARLEN_ROUTE_INVALID;
+  return mio_fa3_varlen_route(a);  // the same kernel family, in its windowed form
+}
+
+extern "C" int mio_fa3_fwd_varlen_window(const mio_fa3_varlen_params_t* a, int32_t window_left, int32_t window_right,
+                                         void* stream) {
+  if (!fa_windowed(window_left, window_right)) return mio_fa3_fwd_varlen(a, stream);
+  if (fa3_varlen_window_validate(a, window_left, window_right) != 0) return -1;
+  if (a->B == 0 || a->total_q == 0) return 0;
+  FaDev p = fa_dev(a->q, a->k, a->v, a->o, a->lse, a->B, a->H, a->Hkv, a->D, a->softmax_scale);
+  p.qs_s = a->q_stride[0]; p.qs_h = a->q_stride[1];
+  p.ks_s = a->k_stride[0]; p.ks_h = a->k_stride[1];
+  p.vs_s = a->v_stride[0]; p.vs_h = a->v_stride[1];
+  p.os_s = a->o_stride[0]; p.os_h = a->o_stride[1];
+  FaVarlen vl;
+  vl.cu_q = a->cu_seqlens_q; vl.cu_k = a->cu_seqlens_k;
+  vl.total_q = a->total_q; vl.total_k = a->total_k;
+  vl.max_q = a->max_seqlen_q; vl.max_k = a->max_seqlen_k;
+  const int wl = fa_window_clamp(window_left), wr = fa_window_clamp(window_right);
+  return fa_dispatch(a->dtype, a->D, [&](auto i) {
+    return fa3_win_seq_launch<typename decltype(i)::T, decltype(i)::D>(p, vl, a->causal, wl, wr, (hipStream_t)stream);
+  });
+}
+
+static int fa3_paged_window_validate(const mio_fa3_paged_params_t* a, int32_t left, int32_t right) {
+  const char* fn = "mio_fa3_fwd_paged_window";
+  if (fa3_paged_validate(a) != 0) return -1;
+  if (fa_window_check(fn, left, right, a->causal) != 0) return -1;
+  MIO_CHECK(a->max_seqlen_q < FA_WIN_LEN_MAX && a->max_seqlen_k < FA_WIN_LEN_MAX,
+            std::string(fn) + ": max_seqlen_q / max_seqlen_k must be below 2^28 under a window");
+  return 0;
+}
+
+extern "C" int32_t mio_fa3_paged_route_window(const mio_fa3_paged_params_t* a, int32_t window_left, int32_t window_right) {
+  if (!fa_windowed(window_left, window_right)) return mio_fa3_paged_route(a);
+  if (fa3_paged_window_validate(a, window_left, window_right) != 0) return MIO_FA3_PAGED_ROUTE_INVALID;
+  return mio_fa3_paged_route(a);
+}
+
+extern "C" int mio_fa3_fwd_paged_window(const mio_fa3_paged_params_t* a, int32_t window_left, int32_t window_right,
+                                        void* stream) {
+  if (!fa_windowed(window_left, window_right)) return mio_fa3_fwd_paged(a, stream);
+  if (fa3_paged_window_validate(a, window_left, window_right) != 0) return -1;
+  if (a->B == 0 || a->total_q == 0) return 0;
+  FaDev p = fa_dev(a->q, a->k_cache, a->v_cache, a->o, a->lse, a->B, a->H, a->Hkv, a->D, a->softmax_scale);
+  p.qs_s = a->q_stride[0]; p.qs_h = a->q_stride[1];
+  p.ks_s = p.vs_s = (int64_t)a->Hkv * a->D;
+  p.ks_h = p.vs_h = a->D;
+  p.os_s = a->o_stride[0]; p.os_h = a->o_stride[1];
+  FaPaged pg;
+  pg.cu_q = a->cu_seqlens_q; pg.seqused_k = a->seqused_k; pg.block_tables = a->block_tables;
+  pg.total_q = a->total_q; pg.max_q = a->max_seqlen_q;
+  pg.max_k = (int)std::min<int64_t>(a->max_seqlen_k, (int64_t)a->max_blocks_per_seq * a->block_size);
+  pg.num_blocks = a->num_blocks; pg.num_layers = a->num_layers; pg.layer = a->layer_idx;
+  pg.block_size = a->block_size; pg.max_blocks = a->max_blocks_per_seq;
+  pg.tpb = a->block_size / 64;
+  pg.tpb_magic = (uint32_t)(((1ull << 31) + pg.tpb - 1) / pg.tpb);
+  const int wl = fa_window_clamp(window_left), wr = fa_window_clamp(window_right);
+  return fa_dispatch(a->dtype, a->D, [&](auto i) {
+    return fa3_win_seq_launch<typename decltype(i)::T, decltype(i)::D>(p, pg, a->causal, wl, wr, (hipStream_t)stream);
+  });
+}

@@ -3,6 +3,9 @@
 // is the element of lse that query row `row` of (batch b, head) owns, FA_KV_TILE(tile, kb, vb) sets kb / vb to the scalar
 // addresses of the first K / V row of this pass' KV tile `tile` (for this lane's head; the per-lane DMA offsets are added
 // to them).
+// FA_WINDOW (the sliding-window kernels, fa3_win_inst.hip): as in fa3_fwd5_body.inc -- rows bounded to keys
+// i + q_offset - k_offset - wl .. i + q_offset - k_offset + wr, each pass walks tiles t_lo .. t_lo + n_tiles - 1 (the
+// loop and the LDS stages relative to the walk, FA_KV_TILE absolute), left-edge tiles get a lower-limit compare.
   using X8 = typename DT<T>::x8;
   using X4 = typename DT<T>::x4;
   using OPS = Fa3Ops<T>;
@@ -97,6 +100,28 @@
     }
     // ---- tiles: the workgroup walks n_tiles (barriers, staging); this wave computes the first n_w of them
     int n_tiles, n_w;
+#ifdef FA_WINDOW
+    const int win_off = p.q_offset - p.k_offset, win_r = CAUSAL ? 0 : wr;
+    auto win_tlo = [&](int qb0) -> int {  // first (absolute) tile of the pass whose first row is qb0
+      const int k = qb0 + win_off - wl;
+      return (wl < 0 || k <= 0) ? 0 : k / FA_BN;
+    };
+    const int t_lo = win_tlo(q0);
+    {
+      int kmax = p.Sk - 1, kw = p.Sk - 1;
+      if (win_r >= 0) {
+        const int c = q0 + FA3_BM - 1 + win_off + win_r, cw = wrow0 + 32 * QT - 1 + win_off + win_r;
+        kmax = c < kmax ? c : kmax;
+        kw = cw < kw ? cw : kw;
+      }
+      n_tiles = kmax < 0 ? 0 : kmax / FA_BN + 1 - t_lo;
+      n_tiles = n_tiles > 0 ? n_tiles : 0;
+      n_w = kw < 0 ? 0 : kw / FA_BN + 1 - t_lo;
+      n_w = n_w < 0 ? 0 : (n_w > n_tiles ? n_tiles : n_w);
+    }
+    FA_WIN_PASS(t_lo, t_lo + n_tiles,
+                pass + 1 < npass ? win_tlo((CAUSAL ? qi : qblk) * FA3_BM) : t_lo, pass == 0);
+#else
     if (CAUSAL) {
       int kmax = q0 + FA3_BM - 1 + p.q_offset - p.k_offset;
       if (kmax > p.Sk - 1) kmax = p.Sk - 1;
@@ -108,8 +133,31 @@
       n_tiles = (p.Sk + FA_BN - 1) / FA_BN;
       n_w = n_tiles;
     }
+#endif
     const int n_tiles_dma = n_tiles > 0 ? n_tiles : 1;
     // last key visible to each query row of this lane, and the first tile of this wave that needs masks
+#ifdef FA_WINDOW
+    int klim[QT], kmin[QT];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+      klim[qt] = p.Sk - 1;
+      if (win_r >= 0) {
+        const int c = qrow[qt] + win_off + win_r;
+        klim[qt] = c < klim[qt] ? c : klim[qt];
+      }
+      kmin[qt] = wl >= 0 ? qrow[qt] + win_off - wl : -FA_BN;
+    }
+    int lim0 = p.Sk - 1;
+    if (win_r >= 0) {
+      const int c = wrow0 + win_off + win_r;
+      lim0 = c < lim0 ? c : lim0;
+    }
+    const int first_edge = (lim0 + 1) / FA_BN;
+    // tiles below first_inner hold a key left of the window of the wave's last row (lower limits grow with the row)
+    const int kmin_w = wl >= 0 ? wrow0 + 32 * QT - 1 + win_off - wl : 0;
+    const int first_inner = kmin_w > 0 ? (kmin_w + FA_BN - 1) / FA_BN : 0;
+    auto is_edge = [&](int t) -> bool { return t + t_lo >= first_edge || t + t_lo < first_inner; };
+#else
     int klim[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
@@ -128,6 +176,7 @@
     const int first_edge = (lim0 + 1) / FA_BN;  // tiles t >= first_edge contain a key > lim0  (lim0 + 1 >= 0 here
                                                 // whenever n_w > 0 ... negative limits give first_edge <= 0: all edge)
     auto is_edge = [&](int t) -> bool { return t >= first_edge; };
+#endif
 
     // ---- K/V staging: global -> LDS by DMA (global_load_lds_dwordx4: 64 lanes x 16 B = 1 KiB of lane-linear LDS per
     // wave-instruction, no staging registers).  A stage is 17 such units: 0..8 the K tile (64 rows x 144 B: 9 chunks
@@ -176,7 +225,12 @@
     bool dma_is_last = false;      // that tile is the (possibly partial) last one of the sequence
     uint32_t dma_lds = 0;          // LDS address of this wave's first unit in the stage being filled
     auto dma_tile_base = [&](int tile_) {
+#ifdef FA_WINDOW
+      int tile = t_lo + (tile_ < n_tiles_dma ? tile_ : n_tiles_dma - 1);  // absolute; an empty pass re-fetches valid rows
+      tile = tile < last_tile ? tile : last_tile;
+#else
       const int tile = tile_ < n_tiles_dma ? tile_ : n_tiles_dma - 1;
+#endif
       FA_KV_TILE(tile, dma_kb, dma_vb);
       dma_is_last = (tile == last_tile);
       dma_lds = (uint32_t)(size_t)((MIO_LDS char*)(smem + (tile_ & (FA3_STAGES - 1)) * SM::STAGE)) + 1024 * wave;
@@ -340,12 +394,19 @@
       fa2_for<QT>([&](auto QTI) {
         constexpr int qt = decltype(QTI)::value;
         const int thr = klim[qt] - kv0n - 4 * h;
+#ifdef FA_WINDOW
+        const int thl = kmin[qt] - kv0n - 4 * h;  // and keys left of the row's window
+#endif
         fa2_for<4>([&](auto G_) {
           constexpr int tt = decltype(G_)::value >> 1, i0 = 8 * (decltype(G_)::value & 1);
 #pragma unroll
           for (int i = i0; i < i0 + 8; ++i) {
             const int c = 32 * tt + (i & 3) + 8 * (i >> 2);
+#ifdef FA_WINDOW
+            if (c > thr || c < thl) S[nb][qt][tt][i] = -INFINITY;
+#else
             if (c > thr) S[nb][qt][tt][i] = -INFINITY;
+#endif
           }
           __builtin_amdgcn_sched_barrier(0);
         });
@@ -521,7 +582,11 @@
     // ---- scores, masks, maximum and reference of tile 0
     if (n_w > 0) {
       phase1(IC(1), IC(0), smem, smem);
+#ifdef FA_WINDOW
+      if (is_edge(0)) mask_tile(IC(0), t_lo * FA_BN);
+#else
       if (is_edge(0)) mask_tile(IC(0), 0);
+#endif
       else asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
       if constexpr (KPRE) {
         move_ref(IC(0), IC(0));
@@ -553,7 +618,11 @@
       }
       if constexpr (STAMP) c2 = __builtin_amdgcn_s_memtime();
       if constexpr (!(ABL & 32))
+#ifdef FA_WINDOW
+        if (has_next && is_edge(t + 1)) mask_tile(IC(cb ^ 1), (t_lo + t + 1) * FA_BN);
+#else
         if (has_next && is_edge(t + 1)) mask_tile(IC(cb ^ 1), (t + 1) * FA_BN);
+#endif
       // (P words written by the vector ALU late in phase 1 are first read by an MFMA many steps into phase 2)
       if constexpr (STAMP) c2b = __builtin_amdgcn_s_memtime();
       dma_tile_base(t + 3);

@@ -3,6 +3,11 @@
 // FA_LSE_INDEX(b, head, row) is the element of lse that query row `row` of (batch b, head) owns, FA_KV_TILE(tile, kb, vb)
 // sets kb / vb to the scalar addresses of the first K / V row of this pass' KV tile `tile` (for this lane's head; the
 // per-lane DMA offsets are added to them).
+// FA_WINDOW (defined by the sliding-window kernels, fa3_win_inst.hip): `wl` / `wr` (ints from the kernel, -1 = unbounded)
+// bound query row i to keys i + q_offset - k_offset - wl .. i + q_offset - k_offset + wr (CAUSAL: wr = 0).  Each pass then
+// walks the tiles t_lo .. t_lo + n_tiles - 1: the loop, the virtual-tile stream and the LDS stages stay relative to the
+// walk, FA_KV_TILE receives the absolute tile, and tiles at the left edge get a per-row lower-limit compare.  Without
+// FA_WINDOW the text below is what it was before the window.
   using X8 = typename DT<T>::x8;
   using X4 = typename DT<T>::x4;
   constexpr int NKT = 4, NQG = 2, NDS = 2, NDT = 4, NS = 2;
@@ -71,12 +76,29 @@
   auto pass_q0 = [&](int pass) __attribute__((always_inline)) -> int {
     return (CAUSAL ? (pass == 0 ? p.nqblk - 1 - qi : qi) : qi) * FA5_BM;
   };
+#ifdef FA_WINDOW
+  const int win_off = p.q_offset - p.k_offset, win_r = CAUSAL ? 0 : wr;
+  auto pass_tlo = [&](int pass) __attribute__((always_inline)) -> int {  // first (absolute) KV tile of that pass
+    const int k = pass_q0(pass) + win_off - wl;
+    return (wl < 0 || k <= 0) ? 0 : k / FA_BN;
+  };
+  auto pass_tiles = [&](int pass) __attribute__((always_inline)) -> int {  // KV tiles the workgroup walks in that pass
+    int kmax = p.Sk - 1;
+    if (win_r >= 0) {
+      const int c = pass_q0(pass) + FA5_BM - 1 + win_off + win_r;
+      kmax = c < kmax ? c : kmax;
+    }
+    const int n = kmax < 0 ? 0 : kmax / FA_BN + 1 - pass_tlo(pass);
+    return n > 0 ? n : 0;
+  };
+#else
   auto pass_tiles = [&](int pass) __attribute__((always_inline)) -> int {  // KV tiles the workgroup walks in that pass
     if (!CAUSAL) return (p.Sk + FA_BN - 1) / FA_BN;
     int kmax = pass_q0(pass) + FA5_BM - 1 + p.q_offset - p.k_offset;
     if (kmax > p.Sk - 1) kmax = p.Sk - 1;
     return kmax < 0 ? 0 : kmax / FA_BN + 1;
   };
+#endif
   // Q fragments (B operand: lane (c16, g) holds Q[row][32 ds + 8 g .. +7]); rows past Sq / chunks past D are zero
   auto load_q = [&](int pass, X8 (&dst)[NQG][NDS]) __attribute__((always_inline)) {
 #pragma unroll
@@ -128,6 +150,35 @@
 
     const int n_tiles = pass_tiles(pass);
     const int n_tiles_next = pass + 1 < npass ? pass_tiles(pass + 1) : 0;
+#ifdef FA_WINDOW
+    const int t_lo = pass_tlo(pass), t_lo_next = pass + 1 < npass ? pass_tlo(pass + 1) : t_lo;
+    FA_WIN_PASS(t_lo, t_lo + n_tiles, t_lo_next, pass == 0);
+    int n_w = n_tiles;
+    if (win_r >= 0) {
+      int kw = wrow0 + 31 + win_off + win_r;
+      if (kw > p.Sk - 1) kw = p.Sk - 1;
+      n_w = kw < 0 ? 0 : kw / FA_BN + 1 - t_lo;
+      n_w = n_w < 0 ? 0 : (n_w > n_tiles ? n_tiles : n_w);
+    }
+    int klim[NQG], kmin[NQG], lim0 = p.Sk - 1;
+#pragma unroll
+    for (int qg = 0; qg < NQG; ++qg) {
+      klim[qg] = p.Sk - 1;
+      if (win_r >= 0) {
+        const int c = qrow[qg] + win_off + win_r;
+        klim[qg] = c < klim[qg] ? c : klim[qg];
+      }
+      kmin[qg] = wl >= 0 ? qrow[qg] + win_off - wl : -FA_BN;
+    }
+    if (win_r >= 0) {
+      const int c0 = wrow0 + win_off + win_r;
+      lim0 = c0 < lim0 ? c0 : lim0;
+    }
+    const int first_edge = (lim0 + 1) / FA_BN;
+    // tiles below first_inner hold a key left of the window of the wave's last row (lower limits grow with the row)
+    const int kmin_w = wl >= 0 ? wrow0 + 31 + win_off - wl : 0;
+    const int first_inner = kmin_w > 0 ? (kmin_w + FA_BN - 1) / FA_BN : 0;
+#else
     int n_w = n_tiles;
     if (CAUSAL) {
       int kw = wrow0 + 31 + p.q_offset - p.k_offset;
@@ -148,11 +199,18 @@
       lim0 = c0 < lim0 ? c0 : lim0;
     }
     const int first_edge = (lim0 + 1) / FA_BN;
+#endif
     const bool late = wave >= 4;
 
     auto stage_dma = [&](int tile_) __attribute__((always_inline)) {  // tile_: virtual index
+#ifdef FA_WINDOW
+      int tile = tile_ - tbase;  // (absolute: + this pass' or the next pass' first tile)
+      if (tile >= n_tiles) tile = (tile - n_tiles < n_tiles_next) ? tile - n_tiles + t_lo_next : -1;  // the next pass' tile, or none
+      else tile += t_lo;
+#else
       int tile = tile_ - tbase;
       if (tile >= n_tiles) tile = (tile - n_tiles < n_tiles_next) ? tile - n_tiles : -1;  // the next pass' tile, or none
+#endif
       if (tile < 0) return;
       const char* kb;
       const char* vb;
@@ -307,11 +365,20 @@
 #pragma unroll
       for (int qg = 0; qg < NQG; ++qg) {
         const int thr = klim[qg] - kv0n - 4 * g;
+#ifdef FA_WINDOW
+        const int thl = kmin[qg] - kv0n - 4 * g;  // and keys left of the row's window
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (16 * kt + i > thr || 16 * kt + i < thl) S[nb][kt][qg][i] = -INFINITY;
+#else
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
           for (int i = 0; i < 4; ++i)
             if (16 * kt + i > thr) S[nb][kt][qg][i] = -INFINITY;
+#endif
       }
     };
     // move the reference of rows that need it for the tile whose scores sit in S[cb] at the OLD reference (KPRE, fa3_fwd5_kernel.h).
@@ -356,7 +423,11 @@
       }
       fresh_any = __builtin_amdgcn_ballot_w64(fresh[0] || fresh[1]) != 0;
     };
+#ifdef FA_WINDOW
+    auto is_edge = [&](int t) __attribute__((always_inline)) -> bool { return t + t_lo >= first_edge || t + t_lo < first_inner; };
+#else
     auto is_edge = [&](int t) __attribute__((always_inline)) -> bool { return t >= first_edge; };
+#endif
     // every second iteration (t even) a wave waits for its DMA shares, meets the other waves (every virtual tile requested
     // so far is then visible: pass-local tiles up to t + 3) and requests the next two tiles
     auto sync_and_dma = [&](int t, auto EVEN_) __attribute__((always_inline)) {  // EVEN_: 1 / 0 = t is even / odd, 2 = look
@@ -384,7 +455,11 @@
       fa2_for<8>([&](auto F_) __attribute__((always_inline)) { read_k(stg(0), F_); });
       phase1(IC(1), IC(0), stg(0));
       fa2_for<8>([&](auto F_) __attribute__((always_inline)) { read_k(stg(1), F_); });  // (land under the reference set-up)
+#ifdef FA_WINDOW
+      if (is_edge(0)) mask_tile(IC(0), t_lo * FA_BN);
+#else
       if (is_edge(0)) mask_tile(IC(0), 0);
+#endif
       move_ref(IC(0), IC(0));
     }
     unsigned long long st_sum[6] = {0, 0, 0, 0, 0, 0};
@@ -403,7 +478,11 @@
       else if (__builtin_expect(__builtin_amdgcn_ballot_w64((orw & 0x40004000u) != 0u) != 0 || fresh_any, 0)) move_ref(CB_, IC(1));
       // one register home for the C-operand tuples on both paths (hipcc otherwise copies them on the COMMON path)
       asm volatile("" : "+v"(nref4[0]), "+v"(nref4[1]));
+#ifdef FA_WINDOW
+      if (__builtin_expect(has_next && is_edge(t + 1), 0)) mask_tile(IC(cb ^ 1), (t_lo + t + 1) * FA_BN);
+#else
       if (__builtin_expect(has_next && is_edge(t + 1), 0)) mask_tile(IC(cb ^ 1), (t + 1) * FA_BN);
+#endif
       if constexpr (STAMP) c3 = __builtin_amdgcn_s_memtime();
       if constexpr (FA5_STAGGER) {
         if (!late) sync_and_dma(t, IC(cb ^ 1));

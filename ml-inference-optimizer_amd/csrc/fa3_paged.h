@@ -98,6 +98,52 @@ struct FaPageWalk {
   }
 };
 
+// The walk of a windowed pass (fa3_win_inst.hip): tiles are absolute, a pass covers tiles t_lo .. t_end - 1, and the
+// window requested when one runs past the pass' end is the first block of the NEXT pass' range (t_next), not block 0.
+// The first pass starts the walk at its own first block.
+struct FaPageWalkWin : FaPageWalk {
+  int t_end, next_lb;
+  __device__ __forceinline__ void begin_pass(const FaPaged& g, int t_lo, int t_end_, int t_next, bool first) {
+    t_end = t_end_;
+    next_lb = (int)__umulhi(2u * (uint32_t)t_next, g.tpb_magic);
+    if (first) {
+      w0 = (int)__umulhi(2u * (uint32_t)t_lo, g.tpb_magic);
+      wp0 = entry(g, w0);
+      wp1 = entry(g, w0 + 1);
+      n0 = (w0 + 2) * g.tpb < t_end ? w0 + 2 : next_lb;
+      np0 = entry(g, n0);
+      np1 = entry(g, n0 + 1);
+    }
+  }
+  __device__ __forceinline__ void tile_base(const FaPaged& g, int tile, const void* kbase, const void* vbase, int ks2,
+                                            int vs2, const char*& kb, const char*& vb) {
+    int lb = (int)__umulhi(2u * (uint32_t)tile, g.tpb_magic);
+    lb = lb < g.max_blocks - 1 ? lb : g.max_blocks - 1;
+    int slot = tile - lb * g.tpb;
+    slot = slot < g.tpb - 1 ? slot : g.tpb - 1;
+    if ((uint32_t)(lb - w0) >= 2u) {
+      if ((uint32_t)(lb - n0) < 2u) {
+        w0 = n0;
+        wp0 = np0;
+        wp1 = np1;
+      } else {  // off the walk: load the window now
+        w0 = lb;
+        wp0 = entry(g, lb);
+        wp1 = entry(g, lb + 1);
+      }
+      n0 = (w0 + 2) * g.tpb < t_end ? w0 + 2 : next_lb;  // the rest of this pass, or the next pass' first tiles
+      np0 = entry(g, n0);
+      np1 = entry(g, n0 + 1);
+    }
+    int page = lb == w0 ? wp0 : wp1;
+    page = page < 0 ? 0 : (page < g.num_blocks - 1 ? page : g.num_blocks - 1);
+    const uint32_t r = ((uint32_t)page * (uint32_t)g.num_layers + (uint32_t)g.layer) * (uint32_t)g.block_size +
+                       (uint32_t)slot * FA_BN;
+    kb = (const char*)kbase + (uint64_t)r * (uint32_t)ks2;
+    vb = (const char*)vbase + (uint64_t)r * (uint32_t)vs2;
+  }
+};
+
 // Turns the launch's FaDev into this workgroup's dense problem over its sequence's pages and starts the walk (see
 // fa_seq_prepare for the exits).  p.k / p.v stay at the cache base: the tile bases come from the walk.
 template <int BM, int NT, bool CAUSAL>
@@ -141,3 +187,10 @@ __global__ __launch_bounds__(256) void fa3_fwd3_paged_kernel(const FaDev pl, con
 #undef FA_LSE_INDEX
 #undef FA_KV_TILE
 }
+
+// Host launchers of the sliding-window forms (fa3_win_inst.hip) for one (dtype, padded D): the dense launch (p as
+// mio_fa3_fwd fills it) and the per-sequence launches (p, seq as for fa3_seq_launch).  left / right: -1 = unbounded.
+template <typename T, int D>
+int fa3_win_launch(const FaDev& p, int causal, int left, int right, hipStream_t stream);
+template <typename T, int D, typename V>
+int fa3_win_seq_launch(const FaDev& p, const V& seq, int causal, int left, int right, hipStream_t stream);

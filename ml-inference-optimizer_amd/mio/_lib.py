@@ -47,6 +47,12 @@ FA3_PAGED_ROUTES = {
     1: "fwd5",
     2: "fwd3",
 }
+# mio_decode_route_t: the kernel mio_fa3_decode_paged(_window) launches
+DECODE_ROUTES = {
+    0: "head",
+    1: "rows",
+    2: "gqa",
+}
 
 # every symbol include/mio_hip.h declares
 EXPORTS = (
@@ -60,6 +66,12 @@ EXPORTS = (
     "mio_fa3_varlen_route",
     "mio_fa3_fwd_paged",
     "mio_fa3_paged_route",
+    "mio_fa3_fwd_window",
+    "mio_fa3_route_window",
+    "mio_fa3_fwd_varlen_window",
+    "mio_fa3_varlen_route_window",
+    "mio_fa3_fwd_paged_window",
+    "mio_fa3_paged_route_window",
     "mio_attn_merge",
     "mio_gemm_bias_act",
     "mio_fused_mlp_workspace_bytes",
@@ -84,6 +96,8 @@ EXPORTS = (
     "mio_layernorm_fwd",
     "mio_fa3_decode_workspace_bytes",
     "mio_fa3_decode_paged",
+    "mio_fa3_decode_paged_window",
+    "mio_fa3_decode_window_route",
     "mio_reshape_and_cache",
     "mio_reshape_and_cache_varlen",
 )
@@ -213,6 +227,14 @@ def _load() -> C.CDLL:
     lib.mio_fa3_fwd_paged.restype = i32
     lib.mio_fa3_paged_route.argtypes = [C.POINTER(FaPagedParams)]
     lib.mio_fa3_paged_route.restype = i32
+    for name, params in (("mio_fa3_fwd_window", FaParams), ("mio_fa3_fwd_varlen_window", FaVarlenParams),
+                         ("mio_fa3_fwd_paged_window", FaPagedParams)):
+        getattr(lib, name).argtypes = [C.POINTER(params), i32, i32, vp]
+        getattr(lib, name).restype = i32
+    for name, params in (("mio_fa3_route_window", FaParams), ("mio_fa3_varlen_route_window", FaVarlenParams),
+                         ("mio_fa3_paged_route_window", FaPagedParams)):
+        getattr(lib, name).argtypes = [C.POINTER(params), i32, i32]
+        getattr(lib, name).restype = i32
     lib.mio_attn_merge.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mio_attn_merge.restype = i32
     lib.mio_gemm_bias_act.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
@@ -262,6 +284,10 @@ def _load() -> C.CDLL:
     lib.mio_fa3_decode_paged.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32, i32, i32,
                                          i32, i32, i32, i32, i32, i32, f32, i32, vp, vp]
     lib.mio_fa3_decode_paged.restype = i32
+    for name in ("mio_fa3_decode_paged_window", "mio_fa3_decode_window_route"):
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32, i32, i32, i32,
+                                       i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, vp]
+        getattr(lib, name).restype = i32
     lib.mio_reshape_and_cache.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32, i32, i32,
                                           i32, i32, i32, i32, vp]
     lib.mio_reshape_and_cache.restype = i32

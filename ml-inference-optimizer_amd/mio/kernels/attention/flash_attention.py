@@ -36,6 +36,9 @@ class FlashAttentionConfig:
     precision: str = "fp16"
     normalize_query: bool = False
     fp8_ortho_matrix: Optional[torch.Tensor] = None
+    # sliding window (flash-attn's window_size = (left, right), -1 = unbounded): prefill through ops.flash_attention,
+    # decode through ops.paged_attention_forward with (left, -1); windowed modules take the plain attention path
+    window_size: Tuple[int, int] = (-1, -1)
 
     @property
     def allowed_precisions(self) -> Set[str]:
@@ -76,8 +79,26 @@ class FlashAttention3(nn.Module):
         if cfg.normalize_query:
             q = F.normalize(q, dim=-1)
         out = ops.flash_attention(q, k, v, mask=mask, causal=cfg.causal, softmax_scale=cfg.softmax_scale,
-                                  dropout_p=0.0, return_softmax=False, block_size=cfg.block_size)
+                                  dropout_p=0.0, return_softmax=False, block_size=cfg.block_size,
+                                  **_window_kw(cfg))
         return out if out.dtype == orig_dtype else out.to(orig_dtype)
+
+
+def _window_kw(cfg) -> dict:
+    """window_size for ops.flash_attention when the config sets one (nothing otherwise: the unwindowed call exactly)."""
+    return {} if tuple(cfg.window_size) == (-1, -1) else {"window_size": tuple(cfg.window_size)}
+
+
+def _decode_window_kw(cfg) -> dict:
+    """The config's window for ops.paged_attention_forward: a decode row has no key right of itself (right -1)."""
+    if tuple(cfg.window_size) == (-1, -1):
+        return {}
+    left, right = cfg.window_size
+    return {"window_size": (left, -1 if right in (-1, 0) else right)}
+
+
+def _windowed(cfg) -> bool:
+    return tuple(cfg.window_size) != (-1, -1)
 
 
 _PAGED_KEYS = ("physical_kv_cache_k", "physical_kv_cache_v", "block_tables", "context_lengths",
@@ -110,7 +131,8 @@ class _AttentionBase(nn.Module):
         k_cache, v_cache, bt, cl, bs, max_seq_len, layer_idx = _paged_args(kwargs, who)
         q = q2d.view(B, q_len, self.num_attention_heads, self.head_dim).permute(0, 2, 1, 3)
         out = torch.empty(B, q_len, self.num_attention_heads, self.head_dim, dtype=dt, device=q2d.device)
-        ops.paged_attention_forward(q, out.permute(0, 2, 1, 3), k_cache, v_cache, bt, cl, bs, max_seq_len, layer_idx)
+        ops.paged_attention_forward(q, out.permute(0, 2, 1, 3), k_cache, v_cache, bt, cl, bs, max_seq_len, layer_idx,
+                                    **_decode_window_kw(self.config))
         return linear(out.view(B, q_len, self.hidden_size), self.o_proj, self._cast, dt, residual=residual)
 
     def _attend(self, q, k, v, attention_mask):
@@ -122,7 +144,7 @@ class _AttentionBase(nn.Module):
         if cfg.normalize_query:
             q = F.normalize(q, dim=-1)
         return ops.flash_attention(q, k, v, mask=attention_mask, causal=cfg.causal,
-                                   softmax_scale=cfg.softmax_scale, block_size=cfg.block_size)
+                                   softmax_scale=cfg.softmax_scale, block_size=cfg.block_size, **_window_kw(cfg))
 
 
 class FlashAttentionLayer(_AttentionBase):
@@ -164,7 +186,8 @@ class FlashAttentionLayer(_AttentionBase):
         # (scaled in fp32, rounded once) and the attention launch is told so (ops.fa3_fwd k_prescaled)
         cfg = self.config
         kv_dim = self.num_kv_heads * self.head_dim
-        kpre = (attention_mask is None and not cfg.normalize_query and not cfg.return_softmax and kv_dim % 128 == 0
+        kpre = (attention_mask is None and not cfg.normalize_query and not cfg.return_softmax and not _windowed(cfg)
+                and kv_dim % 128 == 0
                 and self.k_proj.in_features % 32 == 0
                 and ops.fa3_k_prescaled_ok(B, S, S, self.num_attention_heads, self.head_dim, kv_dim, kv_dim)
                 and ops.blocked_weight_ok(B * S, kv_dim, self.k_proj.in_features)
@@ -213,6 +236,8 @@ class FlashSelfAttention(_AttentionBase):
         n_tot, M = q_dim + 2 * kv_dim, B * S
         if dtype not in (torch.float16, torch.bfloat16) or pre_norm is None or pre_norm.weight is None or ops.NO_BLOCKED_X:
             return False
+        if _windowed(cfg):  # the stream form's attention is the pre-scaled-K / blocked-output kernel: no window there
+            return False
         if compute_dtype(cfg.precision, torch.empty(0, dtype=dtype)) != dtype:
             return False  # the stream form runs in the stream's dtype
         if tuple(pre_norm.normalized_shape) != (d,) or self.o_proj.out_features != d or q_dim != d:
@@ -226,7 +251,7 @@ class FlashSelfAttention(_AttentionBase):
         """The QKV epilogue may hand the attention kernel K * softmax_scale * log2(e) (ops.fa3_fwd k_prescaled)."""
         q_dim, kv_dim = self.hidden_size, self.num_kv_heads * self.head_dim
         n_tot = q_dim + 2 * kv_dim
-        return (q_dim % 128 == 0 and kv_dim % 128 == 0 and ops.col_scale_ok(B * S, n_tot, self.qkv_proj.in_features)
+        return (not _windowed(self.config) and q_dim % 128 == 0 and kv_dim % 128 == 0 and ops.col_scale_ok(B * S, n_tot, self.qkv_proj.in_features)
                 and ops.fa3_k_prescaled_ok(B, S, S, self.num_attention_heads, self.head_dim, n_tot, n_tot))
 
     def _forward_stream(self, x, pre_norm: nn.LayerNorm, stream_out: bool):
@@ -306,7 +331,8 @@ class FlashSelfAttention(_AttentionBase):
         # reference through the MFMA's C operand and drops its per-score multiply-subtract / max pass (ops.fa3_fwd k_prescaled)
         n_tot = q_dim + 2 * kv_dim
         cfg = self.config
-        kpre = (attention_mask is None and not cfg.normalize_query and not cfg.return_softmax and q_dim % 128 == 0
+        kpre = (attention_mask is None and not cfg.normalize_query and not cfg.return_softmax and not _windowed(cfg)
+                and q_dim % 128 == 0
                 and kv_dim % 128 == 0 and self.qkv_proj.in_features % 32 == 0
                 and ops.fa3_k_prescaled_ok(B, S, S, self.num_attention_heads, self.head_dim, n_tot, n_tot)
                 and ops.blocked_weight_ok(B * S, n_tot, self.qkv_proj.in_features)

@@ -18,6 +18,7 @@ import os
 
 import ctypes as C
 import math
+import operator
 from typing import Optional, Tuple
 
 import torch
@@ -147,6 +148,49 @@ def _launch(fwd, p, out, lse, return_lse: bool):  # queued on the current stream
     return (out, lse) if return_lse else out
 
 
+_WINDOW_MAX = (1 << 31) - 1  # the C ABI's int32: larger values would arrive truncated
+
+
+def _window(window_size, causal: bool = False):
+    """window_size = (left, right) checked (flash-attn's convention): two ints, each -1 (unbounded) or in
+    [0, 2^31 - 1]; causal allows right -1 or 0 (causal is right = 0).  Returns (left, right); ValueError otherwise."""
+    try:
+        left, right = (operator.index(w) for w in window_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"window_size must be a pair of ints (left, right), got {window_size!r}") from None
+    if not (-1 <= left <= _WINDOW_MAX and -1 <= right <= _WINDOW_MAX):
+        raise ValueError(f"window_size values must be -1 (unbounded) or in [0, 2^31 - 1], got {tuple(window_size)}")
+    if causal and right > 0:
+        raise ValueError(f"causal attention has window_size[1] = 0: give -1 or 0, got {right}")
+    return left, right
+
+
+def _launch_window(fwd, p, window, out, lse, return_lse: bool):
+    check(fwd(C.byref(p), window[0], window[1], _stream()))
+    return (out, lse) if return_lse else out
+
+
+def _route_window(query, p, window, names) -> str:
+    r = query(C.byref(p), window[0], window[1])
+    if r < 0:
+        raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
+    return names[r]
+
+
+def _dense_window(window_size, causal=False, keep_mask=None, additive_mask=None, o_acc=None, carry_in=False,
+                  k_prescaled=False, out_blocked=False, **_):
+    """The window of a dense launch, with the combinations the windowed kernels do not take refused."""
+    w = _window(window_size, causal)
+    if w != (-1, -1):
+        if keep_mask is not None or additive_mask is not None:
+            raise ValueError("window_size cannot be combined with a mask")
+        if o_acc is not None or carry_in:
+            raise ValueError("window_size cannot be combined with the ring carry (o_acc / carry_in)")
+        if k_prescaled or out_blocked:
+            raise ValueError("window_size cannot be combined with k_prescaled / out_blocked")
+    return w
+
+
 def fa3_fwd(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -167,6 +211,7 @@ def fa3_fwd(
     k_offset: int = 0,
     k_prescaled: bool = False,
     out_blocked: bool = False,
+    window_size=(-1, -1),
 ):
     """One launch of the tiled attention kernel.
 
@@ -178,13 +223,20 @@ def fa3_fwd(
     out_blocked (k_prescaled launches, layout "bshd", where fa3_o_blocked_ok() says so): the output is returned as a
     [ceil(B*Sq/256)*256, H*D] tensor in the blocked activation layout (include/mio_hip.h) for a following
     gemm_bias_act(..., x_blocked_shape=(B, Sq, H*D)) -- the output projection then fetches contiguous K-tiles.
+    window_size = (left, right): sliding window (flash-attn's convention, -1 = unbounded): query i sees key j iff
+    i + q_offset - k_offset - left <= j <= i + q_offset - k_offset + right; not with masks, the ring carry, k_prescaled
+    or out_blocked (ValueError).  (-1, -1) is the launch without a window.
     Returns out (same layout as q) or (out, lse) if return_lse.
     """
+    w = _dense_window(window_size, causal, keep_mask=keep_mask, additive_mask=additive_mask, o_acc=o_acc,
+                      carry_in=carry_in, k_prescaled=k_prescaled, out_blocked=out_blocked)
     _need_cuda(q, k, v)
     p, out, lse, _keep = _fa3_params(q, k, v, layout=layout, causal=causal, softmax_scale=softmax_scale,
                                      keep_mask=keep_mask, additive_mask=additive_mask, return_lse=return_lse, out=out,
                                      o_acc=o_acc, lse=lse, carry_in=carry_in, write_out=write_out, q_offset=q_offset,
                                      k_offset=k_offset, k_prescaled=k_prescaled, out_blocked=out_blocked)
+    if w != (-1, -1):
+        return _launch_window(lib.mio_fa3_fwd_window, p, w, out, lse, return_lse)
     return _launch(lib.mio_fa3_fwd, p, out, lse, return_lse)
 
 
@@ -192,7 +244,11 @@ def fa3_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, **kwargs) -> st
     """The kernel fa3_fwd(q, k, v, **kwargs) would launch (mio_fa3_route; a name of _lib.FA3_ROUTES), without launching.
     Takes fa3_fwd's arguments; tensors may live on any device (only their shapes, strides and addresses are read).
     Arguments fa3_fwd refuses raise the same ValueError / RuntimeError."""
+    window_size = kwargs.pop("window_size", (-1, -1))
+    w = _dense_window(window_size, **kwargs)
     p, _out, _lse, _keep = _fa3_params(q, k, v, **kwargs)
+    if w != (-1, -1):
+        return _route_window(lib.mio_fa3_route_window, p, w, _lib.FA3_ROUTES)
     return _route(lib.mio_fa3_route, p, _lib.FA3_ROUTES)
 
 
@@ -324,6 +380,8 @@ def flash_attention(
     dropout_p: float = 0.0,
     return_softmax: bool = False,
     block_size: int = 128,
+    *,
+    window_size=(-1, -1),
 ):
     """Drop-in for triton_flash_attention (flash_attention_kernels.py:1150-1358), q/k/v [B,S,H,D].
 
@@ -331,6 +389,7 @@ def flash_attention(
     [B,S,S] or 4-D.  block_size is accepted for signature compatibility; the HIP kernel's tile
     (128 queries x 64 keys) is fixed.  return_softmax / dropout_p > 0 are not computed by the
     fused kernel: NotImplementedError (the reference's autograd path punts the same way, :1044-1046).
+    window_size = (left, right): sliding window as in fa3_fwd (not together with mask).
     """
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError(f"Expected 4D tensors for q, k, v but got shapes: q={q.shape}, k={k.shape}, v={v.shape}")
@@ -341,7 +400,10 @@ def flash_attention(
     keep = None
     if mask is not None:
         keep = _canon_mask4(mask.to(q.device))
-    return fa3_fwd(q, k, v, layout="bshd", causal=causal, softmax_scale=softmax_scale, keep_mask=keep)
+    if tuple(window_size) == (-1, -1):
+        return fa3_fwd(q, k, v, layout="bshd", causal=causal, softmax_scale=softmax_scale, keep_mask=keep)
+    return fa3_fwd(q, k, v, layout="bshd", causal=causal, softmax_scale=softmax_scale, keep_mask=keep,
+                   window_size=window_size)
 
 
 def _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=False, softmax_scale=None,
@@ -394,6 +456,8 @@ def flash_attention_varlen(
     softmax_scale: Optional[float] = None,
     return_lse: bool = False,
     out: Optional[torch.Tensor] = None,
+    *,
+    window_size=(-1, -1),
 ):
     """Packed variable-length attention forward (the form of flash-attn's flash_attn_varlen_func), mio_fa3_fwd_varlen.
 
@@ -403,10 +467,15 @@ def flash_attention_varlen(
     cut there).  causal is bottom-right aligned per sequence: query i sees key j iff j <= i + Lk - Lq.  Rows with no
     visible key get 0 (lse -inf).  Returns out [total_q, H, D] or (out, lse fp32 [H, total_q]) if return_lse.
     Queued on the current stream with no host sync (graph-capturable): the offsets are never read on the host.
+    window_size = (left, right): sliding window, bottom-right per sequence: query i also needs
+    i + Lk - Lq - left <= j <= i + Lk - Lq + right (-1 = unbounded; causal is right = 0).
     """
+    w = _window(window_size, causal)
     _need_cuda(q, k, v, cu_seqlens_q, cu_seqlens_k)
     p, out, lse, _keep = _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal,
                                         softmax_scale=softmax_scale, return_lse=return_lse, out=out)
+    if w != (-1, -1):
+        return _launch_window(lib.mio_fa3_fwd_varlen_window, p, w, out, lse, return_lse)
     return _launch(lib.mio_fa3_fwd_varlen, p, out, lse, return_lse)
 
 
@@ -414,7 +483,10 @@ def fa3_varlen_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqle
                      cu_seqlens_k: torch.Tensor, max_seqlen_q: int, max_seqlen_k: int, **kwargs) -> str:
     """The kernel flash_attention_varlen(...) would launch (mio_fa3_varlen_route): "empty", "fwd5" or "fwd3", without
     launching.  Tensors may live on any device; arguments flash_attention_varlen refuses raise the same errors."""
+    w = _window(kwargs.pop("window_size", (-1, -1)), kwargs.get("causal", False))
     p, _out, _lse, _keep = _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, **kwargs)
+    if w != (-1, -1):
+        return _route_window(lib.mio_fa3_varlen_route_window, p, w, _lib.FA3_VARLEN_ROUTES)
     return _route(lib.mio_fa3_varlen_route, p, _lib.FA3_VARLEN_ROUTES)
 
 
@@ -929,6 +1001,8 @@ def flash_attention_varlen_paged(
     softmax_scale: Optional[float] = None,
     return_lse: bool = False,
     out: Optional[torch.Tensor] = None,
+    *,
+    window_size=(-1, -1),
 ):
     """Packed variable-length attention forward over the paged KV cache (chunked prefill), mio_fa3_fwd_paged.
 
@@ -939,11 +1013,16 @@ def flash_attention_varlen_paged(
     aligned: query i of a sequence sees key j iff j <= i + Lk - Lq.  Rows with no visible key get 0 (lse -inf).
     Returns out [total_q, H, D] or (out, lse fp32 [H, total_q]) if return_lse.  Queued on the current stream with no host
     sync (graph-capturable): the offsets and tables are never read on the host.
+    window_size = (left, right): sliding window as in flash_attention_varlen; only the pages inside each query block's
+    window are read.
     """
+    w = _window(window_size, causal)
     _need_cuda(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k)
     p, out, lse, _keep = _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
                                        max_seqlen_k, layer_idx=layer_idx, causal=causal, softmax_scale=softmax_scale,
                                        return_lse=return_lse, out=out)
+    if w != (-1, -1):
+        return _launch_window(lib.mio_fa3_fwd_paged_window, p, w, out, lse, return_lse)
     return _launch(lib.mio_fa3_fwd_paged, p, out, lse, return_lse)
 
 
@@ -953,16 +1032,26 @@ def fa3_paged_route(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
     """The kernel flash_attention_varlen_paged(...) would launch (mio_fa3_paged_route): "empty", "fwd5" or "fwd3",
     without launching.  Tensors may live on any device; arguments flash_attention_varlen_paged refuses raise the same
     errors."""
+    w = _window(kwargs.pop("window_size", (-1, -1)), kwargs.get("causal", False))
     p, _out, _lse, _keep = _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
                                          max_seqlen_k, **kwargs)
+    if w != (-1, -1):
+        return _route_window(lib.mio_fa3_paged_route_window, p, w, _lib.FA3_PAGED_ROUTES)
     return _route(lib.mio_fa3_paged_route, p, _lib.FA3_PAGED_ROUTES)
 
 
-def paged_attention_forward(query, output, k_cache, v_cache, block_tables, context_lengths, block_size: int,
-                            max_seq_len: int, layer_idx: int, scale: Optional[float] = None) -> torch.Tensor:
-    """Drop-in for triton_paged_attention_forward (attention_kernels.py:1206-1311).
-    query/output [B,H,q_len,D] (output caller-preallocated, :1208,1286); caches
-    [num_blocks, L, block_size, Hkv, D]; block_tables [B,max_blocks] int32; context_lengths [B] int32."""
+def _decode_window(window_size) -> int:
+    """The left bound of a decode window_size = (left, right): each -1 (unbounded) or >= 0, and right must be -1 (a
+    decode row sees every cached key up to its own position).  Raises ValueError otherwise."""
+    left, right = _window(window_size)
+    if right != -1:
+        raise ValueError(f"paged decode takes no right window: window_size[1] must be -1, got {right}")
+    return left
+
+
+def _decode_args(query, output, k_cache, v_cache, block_tables, context_lengths, block_size, max_seq_len, layer_idx,
+                 scale):
+    """The checked arguments of mio_fa3_decode_paged(_window) up to the window, and the tensors they point into."""
     _need_cuda(query, output, k_cache, v_cache, block_tables, context_lengths)
     if query.dim() != 4 or output.shape != query.shape:
         raise ValueError("query/output must be [B,H,q_len,D] with equal shapes")
@@ -983,14 +1072,50 @@ def paged_attention_forward(query, output, k_cache, v_cache, block_tables, conte
     bt = block_tables.to(torch.int32).contiguous()
     cl = context_lengths.to(torch.int32).contiguous()
     sc = (1.0 / math.sqrt(D)) if scale is None else float(scale)
-    nbytes = lib.mio_fa3_decode_workspace_bytes(B, H, q_len, D, int(max_seq_len))
-    work = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
     qs = (C.c_int64 * 3)(q.stride(0), q.stride(1), q.stride(2))
     os_ = (C.c_int64 * 3)(output.stride(0), output.stride(1), output.stride(2))
-    check(lib.mio_fa3_decode_paged(q.data_ptr(), output.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                   bt.data_ptr(), cl.data_ptr(), qs, os_, B, H, Hkv, q_len, D, L, int(layer_idx), bs,
-                                   bt.shape[1], int(max_seq_len), sc, dt, work.data_ptr(), _stream()))
+    args = (q.data_ptr(), output.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), bt.data_ptr(), cl.data_ptr(), qs,
+            os_, B, H, Hkv, q_len, D, L, int(layer_idx), bs, bt.shape[1], int(max_seq_len), sc)
+    return args, dt, (q, bt, cl)
+
+
+def paged_attention_forward(query, output, k_cache, v_cache, block_tables, context_lengths, block_size: int,
+                            max_seq_len: int, layer_idx: int, scale: Optional[float] = None, *,
+                            window_size=(-1, -1)) -> torch.Tensor:
+    """Drop-in for triton_paged_attention_forward (attention_kernels.py:1206-1311).
+    query/output [B,H,q_len,D] (output caller-preallocated, :1208,1286); caches
+    [num_blocks, L, block_size, Hkv, D]; block_tables [B,max_blocks] int32; context_lengths [B] int32.
+
+    window_size = (left, -1): sliding-window decode (flash-attn's convention): row qi of q_len sees the cached keys
+    j < ctx with j >= ctx - q_len + qi - left; only the window's keys are read.  (-1, -1) (the default) is the
+    unwindowed launch exactly."""
+    left = _decode_window(window_size)
+    args, dt, keep = _decode_args(query, output, k_cache, v_cache, block_tables, context_lengths, block_size,
+                                  max_seq_len, layer_idx, scale)
+    B, H, q_len, D = query.shape
+    nbytes = lib.mio_fa3_decode_workspace_bytes(B, H, q_len, D, int(max_seq_len))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
+    if left < 0:
+        check(lib.mio_fa3_decode_paged(*args, dt, work.data_ptr(), _stream()))
+    else:
+        check(lib.mio_fa3_decode_paged_window(*args, left, -1, dt, work.data_ptr(), _stream()))
+    del keep
     return output
+
+
+def paged_attention_route(query, output, k_cache, v_cache, block_tables, context_lengths, block_size: int,
+                          max_seq_len: int, layer_idx: int, scale: Optional[float] = None, *,
+                          window_size=(-1, -1)) -> str:
+    """The decode kernel paged_attention_forward takes for these arguments ("head", "rows" or "gqa",
+    mio_fa3_decode_window_route); nothing is launched."""
+    left = _decode_window(window_size)
+    args, dt, keep = _decode_args(query, output, k_cache, v_cache, block_tables, context_lengths, block_size,
+                                  max_seq_len, layer_idx, scale)
+    r = lib.mio_fa3_decode_window_route(*args, left, -1, dt, None, None)
+    del keep
+    if r < 0:
+        check(r)
+    return _lib.DECODE_ROUTES[r]
 
 
 def reshape_and_cache(key, value, k_cache, v_cache, block_tables, context_lengths, block_size: int, layer_idx: int):
