@@ -446,6 +446,46 @@ int mio_reshape_and_cache_varlen(const void* key, const void* value, void* k_cac
                                  int32_t num_layers, int32_t layer_idx, int32_t block_size,
                                  int32_t max_blocks_per_seq, int32_t dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * FP8 paged KV cache (OCP e4m3fn, torch.float8_e4m3fn).  The caches are the layout above at one byte
+ * per element; key/value, q and o stay bf16 / fp16 (dtype).  A cached byte x8 stands for
+ * x8 * scale: k_scale / v_scale are DEVICE pointers to the fp32 scale of layer_idx's K and V, read
+ * by the kernels (no host sync, graph-capturable; a scale may change between replays).  Both are
+ * required (null is refused) and 4-byte aligned.  head_dim must be a multiple of 16.
+ * Writes quantise: q = e4m3(clamp(float(x) * (1.0f / scale), -448, 448)), round to nearest even,
+ * NaN stays NaN; otherwise as mio_reshape_and_cache / mio_reshape_and_cache_varlen (same skipping
+ * rules, positions skipped leave the cache bytes untouched).
+ * Decode is mio_fa3_decode_paged_window over K = x8 * k_scale, V = x8 * v_scale: window_left -1
+ * (unbounded) or >= 0, the same routes (head / rows / gqa), the same workspace
+ * (mio_fa3_decode_workspace_bytes); mio_fa3_decode_kv8_route is its host-only route query.
+ * ------------------------------------------------------------------------------------------ */
+int mio_reshape_and_cache_kv8(const void* key, const void* value, void* k_cache, void* v_cache,
+                              const float* k_scale, const float* v_scale, const int32_t* block_tables,
+                              const int32_t* context_lengths, const int64_t k_stride[2],
+                              const int64_t v_stride[2], int32_t B, int32_t Hkv, int32_t D, int32_t num_layers,
+                              int32_t layer_idx, int32_t block_size, int32_t max_blocks_per_seq, int32_t dtype,
+                              void* stream);
+int mio_reshape_and_cache_varlen_kv8(const void* key, const void* value, void* k_cache, void* v_cache,
+                                     const float* k_scale, const float* v_scale, const int32_t* block_tables,
+                                     const int32_t* cu_seqlens_new, const int32_t* context_lengths,
+                                     const int64_t k_stride[2], const int64_t v_stride[2], int32_t B,
+                                     int32_t total_new, int32_t Hkv, int32_t D, int32_t num_blocks,
+                                     int32_t num_layers, int32_t layer_idx, int32_t block_size,
+                                     int32_t max_blocks_per_seq, int32_t dtype, void* stream);
+int mio_fa3_decode_paged_kv8(const void* q, void* o, const void* k_cache, const void* v_cache,
+                             const float* k_scale, const float* v_scale, const int32_t* block_tables,
+                             const int32_t* context_lengths, const int64_t q_stride[3], const int64_t o_stride[3],
+                             int32_t B, int32_t H, int32_t Hkv, int32_t q_len, int32_t D, int32_t num_layers,
+                             int32_t layer_idx, int32_t block_size, int32_t max_blocks_per_seq, int32_t max_ctx,
+                             float scale, int32_t window_left, int32_t dtype, void* workspace, void* stream);
+/* a mio_decode_route_t, or <0 with mio_last_error() set where mio_fa3_decode_paged_kv8 would refuse */
+int mio_fa3_decode_kv8_route(const void* q, void* o, const void* k_cache, const void* v_cache,
+                             const float* k_scale, const float* v_scale, const int32_t* block_tables,
+                             const int32_t* context_lengths, const int64_t q_stride[3], const int64_t o_stride[3],
+                             int32_t B, int32_t H, int32_t Hkv, int32_t q_len, int32_t D, int32_t num_layers,
+                             int32_t layer_idx, int32_t block_size, int32_t max_blocks_per_seq, int32_t max_ctx,
+                             float scale, int32_t window_left, int32_t dtype, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

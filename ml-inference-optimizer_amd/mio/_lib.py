@@ -100,6 +100,10 @@ EXPORTS = (
     "mio_fa3_decode_window_route",
     "mio_reshape_and_cache",
     "mio_reshape_and_cache_varlen",
+    "mio_reshape_and_cache_kv8",
+    "mio_reshape_and_cache_varlen_kv8",
+    "mio_fa3_decode_paged_kv8",
+    "mio_fa3_decode_kv8_route",
 )
 
 
@@ -294,6 +298,18 @@ def _load() -> C.CDLL:
     lib.mio_reshape_and_cache_varlen.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32,
                                                  i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.mio_reshape_and_cache_varlen.restype = i32
+    # fp8 (e4m3fn) cache: the 16-bit forms' arguments with the two scale pointers after v_cache
+    lib.mio_reshape_and_cache_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32,
+                                              i32, i32, i32, i32, i32, i32, vp]
+    lib.mio_reshape_and_cache_kv8.restype = i32
+    lib.mio_reshape_and_cache_varlen_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64),
+                                                     C.POINTER(i64), i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                                     vp]
+    lib.mio_reshape_and_cache_varlen_kv8.restype = i32
+    for name in ("mio_fa3_decode_paged_kv8", "mio_fa3_decode_kv8_route"):
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32, i32,
+                                       i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp]
+        getattr(lib, name).restype = i32
     return lib
 
 

@@ -176,7 +176,9 @@ class BlockManager:
     """Physical block pool with reference counts (inference.py:1045-1126).  Cache layout
     [num_blocks, num_layers, block_size, num_heads, head_dim] -- what mio_fa3_decode_paged / mio_reshape_and_cache
     read and write.  Reference counts live on the host (the reference keeps them in a device tensor and pays a
-    device->host sync per allocate/free)."""
+    device->host sync per allocate/free).
+    dtype torch.float8_e4m3fn stores the cache in one byte per element; the per-layer dequantisation scales k_scale /
+    v_scale (fp32 [num_layers] on the device, initialised to 1.0) are what the cache writes and the decode read."""
 
     def __init__(self, num_blocks: int, block_size: int, num_layers: int, num_heads: int, head_dim: int,
                  dtype: torch.dtype, device: str):
@@ -187,6 +189,11 @@ class BlockManager:
         shape = (num_blocks, num_layers, block_size, num_heads, head_dim)
         self.gpu_cache_k = torch.zeros(shape, dtype=dtype, device=device)
         self.gpu_cache_v = torch.zeros(shape, dtype=dtype, device=device)
+        self.k_scale: Optional[torch.Tensor] = None
+        self.v_scale: Optional[torch.Tensor] = None
+        if dtype == torch.float8_e4m3fn:
+            self.k_scale = torch.ones(num_layers, dtype=torch.float32, device=device)
+            self.v_scale = torch.ones(num_layers, dtype=torch.float32, device=device)
         self.is_initialized = True
 
     def allocate_block(self) -> int:
@@ -217,6 +224,10 @@ class BlockManager:
 
     def get_physical_caches(self) -> Tuple[torch.Tensor, torch.Tensor]:
         return self.gpu_cache_k, self.gpu_cache_v
+
+    def get_kv_scales(self) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """(k_scale, v_scale) of an fp8 cache, fp32 [num_layers] device tensors; (None, None) for a 16-bit cache."""
+        return self.k_scale, self.v_scale
 
 
 class SequenceMetadata:
@@ -301,6 +312,11 @@ class PagedKVCache:
 
     def get_physical_caches(self) -> Tuple[torch.Tensor, torch.Tensor]:
         return self.block_manager.get_physical_caches()
+
+    def get_kv_scales(self) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """(k_scale, v_scale) for the k_scale= / v_scale= arguments of the paged ops and modules: fp32 [num_layers]
+        device tensors (1.0 until the caller sets them) for a torch.float8_e4m3fn cache, (None, None) otherwise."""
+        return self.block_manager.get_kv_scales()
 
     def kernel_metadata(self, seq_ids: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor, int]:
         """(block_tables int32 [B, max_blocks], context_lengths int32 [B], max_seq_len) for a batch of sequences --

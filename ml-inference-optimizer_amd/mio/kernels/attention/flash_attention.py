@@ -127,12 +127,18 @@ class _AttentionBase(nn.Module):
 
     def _paged(self, q2d, B, q_len, dt, kwargs, who, residual=None):
         """q [B,q_len,H*D] already projected; attention over the paged cache, then o_proj
-        (reference :572-621: K/V are NOT recomputed, they are read from the cache)."""
+        (reference :572-621: K/V are NOT recomputed, they are read from the cache).  An fp8 cache takes the k_scale /
+        v_scale kwargs next to physical_kv_cache_k / _v."""
         k_cache, v_cache, bt, cl, bs, max_seq_len, layer_idx = _paged_args(kwargs, who)
+        k_scale, v_scale = kwargs.get("k_scale"), kwargs.get("v_scale")
+        if k_cache.dtype == torch.float8_e4m3fn and (k_scale is None or v_scale is None):
+            raise ValueError(f"{who}: an fp8 (float8_e4m3fn) KV cache needs k_scale and v_scale "
+                             "(PagedKVCache.get_kv_scales())")
+        scales = {} if k_scale is None and v_scale is None else {"k_scale": k_scale, "v_scale": v_scale}
         q = q2d.view(B, q_len, self.num_attention_heads, self.head_dim).permute(0, 2, 1, 3)
         out = torch.empty(B, q_len, self.num_attention_heads, self.head_dim, dtype=dt, device=q2d.device)
         ops.paged_attention_forward(q, out.permute(0, 2, 1, 3), k_cache, v_cache, bt, cl, bs, max_seq_len, layer_idx,
-                                    **_decode_window_kw(self.config))
+                                    **_decode_window_kw(self.config), **scales)
         return linear(out.view(B, q_len, self.hidden_size), self.o_proj, self._cast, dt, residual=residual)
 
     def _attend(self, q, k, v, attention_mask):

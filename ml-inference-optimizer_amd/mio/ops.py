@@ -947,6 +947,9 @@ def _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, ma
         raise ValueError(f"Expected a 3D tensor [tokens, heads, head_dim] for q but got shape {q.shape}")
     if k_cache.dim() != 5 or v_cache.shape != k_cache.shape:
         raise ValueError("caches must be [num_blocks, num_layers, block_size, num_kv_heads, head_dim] with equal shapes")
+    if k_cache.dtype == _KV8 or v_cache.dtype == _KV8:
+        raise ValueError("flash_attention_varlen_paged does not read an fp8 (float8_e4m3fn) KV cache; paged decode "
+                         "(paged_attention_forward) does")
     dt = _qkv_dtype(q, k_cache, v_cache, "q, k_cache, v_cache")
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("caches must be contiguous")
@@ -1049,16 +1052,58 @@ def _decode_window(window_size) -> int:
     return left
 
 
+# the fp8 KV cache: OCP e4m3fn only (MI300's e4m3fnuz is another encoding)
+_KV8 = torch.float8_e4m3fn
+
+
+def _kv8_kind(k_cache, v_cache) -> None:
+    """One-byte caches must be float8_e4m3fn (not e5m2, e4m3fnuz or an integer type): ValueError otherwise."""
+    for c in (k_cache, v_cache):
+        if c.element_size() == 1 and c.dtype != _KV8:
+            raise ValueError(f"an 8-bit KV cache must be torch.float8_e4m3fn (OCP e4m3), got {c.dtype}")
+
+
+def _kv_scales(cache_dtype, k_scale, v_scale, L: int, layer_idx: int, device, who: str):
+    """None for a 16-bit cache (which takes no scales); for a float8_e4m3fn cache, the device addresses of the fp32
+    scales the kernels read for layer_idx (1 element shared by all layers, or num_layers elements).  ValueError for any
+    other cache dtype or scale misuse."""
+    if cache_dtype in (torch.bfloat16, torch.float16):
+        if k_scale is not None or v_scale is not None:
+            raise ValueError(f"{who}: k_scale / v_scale apply to an fp8 (float8_e4m3fn) cache only, got a "
+                             f"{cache_dtype} cache")
+        return None
+    if cache_dtype != _KV8:
+        raise ValueError(f"{who}: the KV cache must be bf16, fp16 or float8_e4m3fn, got {cache_dtype}")
+    if k_scale is None or v_scale is None:
+        raise ValueError(f"{who}: an fp8 (float8_e4m3fn) cache requires k_scale and v_scale")
+    ptrs = []
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if not isinstance(s, torch.Tensor) or s.dtype != torch.float32 or not s.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous float32 tensor")
+        if s.numel() not in (1, L):
+            raise ValueError(f"{who}: {name} must hold 1 or num_layers = {L} elements, got {s.numel()}")
+        if s.device != device:
+            raise ValueError(f"{who}: {name} must be on the device of the cache")
+        if s.numel() > 1 and not 0 <= int(layer_idx) < L:
+            raise ValueError(f"{who}: layer_idx {layer_idx} out of range for a {L}-layer cache")
+        ptrs.append(s.data_ptr() + (4 * int(layer_idx) if s.numel() > 1 else 0))
+    return tuple(ptrs)
+
+
 def _decode_args(query, output, k_cache, v_cache, block_tables, context_lengths, block_size, max_seq_len, layer_idx,
-                 scale):
-    """The checked arguments of mio_fa3_decode_paged(_window) up to the window, and the tensors they point into."""
+                 scale, k_scale=None, v_scale=None):
+    """The checked arguments of mio_fa3_decode_paged(_window / _kv8) up to the window, the scale addresses (None for a
+    16-bit cache) and the tensors they point into."""
     _need_cuda(query, output, k_cache, v_cache, block_tables, context_lengths)
     if query.dim() != 4 or output.shape != query.shape:
         raise ValueError("query/output must be [B,H,q_len,D] with equal shapes")
     if k_cache.dim() != 5 or v_cache.shape != k_cache.shape:
         raise ValueError("caches must be [num_blocks, num_layers, block_size, num_kv_heads, head_dim]")
     dt = _dtype_id(query)
-    if k_cache.dtype != query.dtype or v_cache.dtype != query.dtype or output.dtype != query.dtype:
+    _kv8_kind(k_cache, v_cache)
+    if output.dtype != query.dtype or v_cache.dtype != k_cache.dtype:
+        raise ValueError("query, output and caches must share a dtype")
+    if k_cache.dtype != _KV8 and k_cache.dtype != query.dtype:
         raise ValueError("query, output and caches must share a dtype")
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("caches must be contiguous")
@@ -1066,6 +1111,9 @@ def _decode_args(query, output, k_cache, v_cache, block_tables, context_lengths,
     nb, L, bs, Hkv, Dc = k_cache.shape
     if bs != block_size or Dc != D:
         raise ValueError("cache geometry does not match block_size/head_dim")
+    scales = _kv_scales(k_cache.dtype, k_scale, v_scale, L, layer_idx, k_cache.device, "paged_attention_forward")
+    if scales is not None and D % 16 != 0:
+        raise ValueError(f"an fp8 KV cache needs head_dim to be a multiple of 16, got head_dim {D}")
     q = _rows16(query)
     if output.stride(-1) != 1:
         raise ValueError("output last dim must be contiguous")
@@ -1074,28 +1122,38 @@ def _decode_args(query, output, k_cache, v_cache, block_tables, context_lengths,
     sc = (1.0 / math.sqrt(D)) if scale is None else float(scale)
     qs = (C.c_int64 * 3)(q.stride(0), q.stride(1), q.stride(2))
     os_ = (C.c_int64 * 3)(output.stride(0), output.stride(1), output.stride(2))
-    args = (q.data_ptr(), output.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), bt.data_ptr(), cl.data_ptr(), qs,
-            os_, B, H, Hkv, q_len, D, L, int(layer_idx), bs, bt.shape[1], int(max_seq_len), sc)
-    return args, dt, (q, bt, cl)
+    if scales is None:
+        args = (q.data_ptr(), output.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), bt.data_ptr(), cl.data_ptr(),
+                qs, os_, B, H, Hkv, q_len, D, L, int(layer_idx), bs, bt.shape[1], int(max_seq_len), sc)
+    else:
+        args = (q.data_ptr(), output.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), *scales, bt.data_ptr(),
+                cl.data_ptr(), qs, os_, B, H, Hkv, q_len, D, L, int(layer_idx), bs, bt.shape[1], int(max_seq_len), sc)
+    return args, dt, scales is not None, (q, bt, cl, k_scale, v_scale)
 
 
 def paged_attention_forward(query, output, k_cache, v_cache, block_tables, context_lengths, block_size: int,
                             max_seq_len: int, layer_idx: int, scale: Optional[float] = None, *,
-                            window_size=(-1, -1)) -> torch.Tensor:
+                            window_size=(-1, -1), k_scale=None, v_scale=None) -> torch.Tensor:
     """Drop-in for triton_paged_attention_forward (attention_kernels.py:1206-1311).
     query/output [B,H,q_len,D] (output caller-preallocated, :1208,1286); caches
     [num_blocks, L, block_size, Hkv, D]; block_tables [B,max_blocks] int32; context_lengths [B] int32.
 
     window_size = (left, -1): sliding-window decode (flash-attn's convention): row qi of q_len sees the cached keys
     j < ctx with j >= ctx - q_len + qi - left; only the window's keys are read.  (-1, -1) (the default) is the
-    unwindowed launch exactly."""
+    unwindowed launch exactly.
+
+    FP8 cache: k_cache / v_cache torch.float8_e4m3fn (query / output bf16 or fp16, head_dim a multiple of 16) with
+    k_scale / v_scale, fp32 device tensors of 1 or num_layers elements: attention over K = k_cache * k_scale,
+    V = v_cache * v_scale (mio_fa3_decode_paged_kv8).  The scales are read on the device, never on the host."""
     left = _decode_window(window_size)
-    args, dt, keep = _decode_args(query, output, k_cache, v_cache, block_tables, context_lengths, block_size,
-                                  max_seq_len, layer_idx, scale)
+    args, dt, kv8, keep = _decode_args(query, output, k_cache, v_cache, block_tables, context_lengths, block_size,
+                                       max_seq_len, layer_idx, scale, k_scale, v_scale)
     B, H, q_len, D = query.shape
     nbytes = lib.mio_fa3_decode_workspace_bytes(B, H, q_len, D, int(max_seq_len))
     work = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
-    if left < 0:
+    if kv8:
+        check(lib.mio_fa3_decode_paged_kv8(*args, left, dt, work.data_ptr(), _stream()))
+    elif left < 0:
         check(lib.mio_fa3_decode_paged(*args, dt, work.data_ptr(), _stream()))
     else:
         check(lib.mio_fa3_decode_paged_window(*args, left, -1, dt, work.data_ptr(), _stream()))
@@ -1105,25 +1163,50 @@ def paged_attention_forward(query, output, k_cache, v_cache, block_tables, conte
 
 def paged_attention_route(query, output, k_cache, v_cache, block_tables, context_lengths, block_size: int,
                           max_seq_len: int, layer_idx: int, scale: Optional[float] = None, *,
-                          window_size=(-1, -1)) -> str:
+                          window_size=(-1, -1), k_scale=None, v_scale=None) -> str:
     """The decode kernel paged_attention_forward takes for these arguments ("head", "rows" or "gqa",
-    mio_fa3_decode_window_route); nothing is launched."""
+    mio_fa3_decode_window_route / mio_fa3_decode_kv8_route); nothing is launched."""
     left = _decode_window(window_size)
-    args, dt, keep = _decode_args(query, output, k_cache, v_cache, block_tables, context_lengths, block_size,
-                                  max_seq_len, layer_idx, scale)
-    r = lib.mio_fa3_decode_window_route(*args, left, -1, dt, None, None)
+    args, dt, kv8, keep = _decode_args(query, output, k_cache, v_cache, block_tables, context_lengths, block_size,
+                                       max_seq_len, layer_idx, scale, k_scale, v_scale)
+    if kv8:
+        r = lib.mio_fa3_decode_kv8_route(*args, left, dt, None, None)
+    else:
+        r = lib.mio_fa3_decode_window_route(*args, left, -1, dt, None, None)
     del keep
     if r < 0:
         check(r)
     return _lib.DECODE_ROUTES[r]
 
 
-def reshape_and_cache(key, value, k_cache, v_cache, block_tables, context_lengths, block_size: int, layer_idx: int):
-    """Drop-in for triton_reshape_and_cache (attention_kernels.py:1314-1407): key/value [B,1,Hkv,D]."""
+def _write_caches(key, value, k_cache, v_cache, layer_idx, k_scale, v_scale, who):
+    """The cache checks the two cache writes share: value shares key's dtype; the caches are 5-D, equal, contiguous,
+    and either of key's dtype or float8_e4m3fn with scales.  Returns the scale addresses (None for a 16-bit cache)."""
+    if value.dtype != key.dtype:
+        raise ValueError("key, value and caches must share a dtype")
+    _kv8_kind(k_cache, v_cache)
+    if k_cache.dim() != 5 or v_cache.shape != k_cache.shape:
+        raise ValueError("caches must be [num_blocks, num_layers, block_size, num_kv_heads, head_dim] with equal shapes")
+    if v_cache.dtype != k_cache.dtype or (k_cache.dtype != _KV8 and k_cache.dtype != key.dtype):
+        raise ValueError("key, value and caches must share a dtype")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("caches must be contiguous")
+    scales = _kv_scales(k_cache.dtype, k_scale, v_scale, k_cache.shape[1], layer_idx, k_cache.device, who)
+    if scales is not None and key.shape[-1] % 16 != 0:
+        raise ValueError(f"an fp8 KV cache needs head_dim to be a multiple of 16, got head_dim {key.shape[-1]}")
+    return scales
+
+
+def reshape_and_cache(key, value, k_cache, v_cache, block_tables, context_lengths, block_size: int, layer_idx: int, *,
+                      k_scale=None, v_scale=None):
+    """Drop-in for triton_reshape_and_cache (attention_kernels.py:1314-1407): key/value [B,1,Hkv,D].
+    The caches share key's dtype, or are torch.float8_e4m3fn with k_scale / v_scale (fp32 device tensors of 1 or
+    num_layers elements): the written bytes are e4m3(clamp(x * (1 / scale), -448, 448)) (mio_reshape_and_cache_kv8)."""
     _need_cuda(key, value, k_cache, v_cache)
     if key.dim() != 4 or key.shape[1] != 1:
         raise ValueError("reshape_and_cache supports q_seq_len == 1 only (attention_kernels.py:1363-1365)")
     dt = _dtype_id(key)
+    scales = _write_caches(key, value, k_cache, v_cache, layer_idx, k_scale, v_scale, "reshape_and_cache")
     B, _, Hkv, D = key.shape
     nb, L, bs, Hc, Dc = k_cache.shape
     if (Hc, Dc, bs) != (Hkv, D, block_size):
@@ -1133,30 +1216,31 @@ def reshape_and_cache(key, value, k_cache, v_cache, block_tables, context_length
     cl = context_lengths.to(torch.int32).contiguous()
     ks = (C.c_int64 * 2)(key.stride(0), key.stride(2))
     vs = (C.c_int64 * 2)(value.stride(0), value.stride(2))
+    if scales is not None:
+        check(lib.mio_reshape_and_cache_kv8(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                            *scales, bt.data_ptr(), cl.data_ptr(), ks, vs, B, Hkv, D, L,
+                                            int(layer_idx), bs, bt.shape[1], dt, _stream()))
+        return
     check(lib.mio_reshape_and_cache(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                                     bt.data_ptr(), cl.data_ptr(), ks, vs, B, Hkv, D, L, int(layer_idx), bs,
                                     bt.shape[1], dt, _stream()))
 
 
 def reshape_and_cache_varlen(key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths,
-                             block_size: int, layer_idx: int):
+                             block_size: int, layer_idx: int, *, k_scale=None, v_scale=None):
     """Write many new tokens per sequence into the paged cache (mio_reshape_and_cache_varlen).
 
     key / value [total_new, Hkv, D] packed by cu_seqlens_new (int32 [B+1]); context_lengths (int32 [B]) holds each
     sequence's length AFTER the append, so token i of the n_b new ones goes to position context_lengths[b] - n_b + i of
     the pages in block_tables (int32 [B, max_blocks_per_seq]).  Positions that are negative or past the table row are
-    skipped.  Byte-exact copies, queued on the current stream with no host sync (graph-capturable)."""
+    skipped.  Byte-exact copies, queued on the current stream with no host sync (graph-capturable).
+    FP8 cache: as reshape_and_cache, torch.float8_e4m3fn caches with k_scale / v_scale (mio_reshape_and_cache_varlen_kv8)."""
     _need_cuda(key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths)
     if key.dim() != 3 or value.shape != key.shape:
         raise ValueError(f"key/value must be [total_new, num_kv_heads, head_dim] with equal shapes, got "
                          f"key={tuple(key.shape)}, value={tuple(value.shape)}")
     dt = _dtype_id(key)
-    if value.dtype != key.dtype or k_cache.dtype != key.dtype or v_cache.dtype != key.dtype:
-        raise ValueError("key, value and caches must share a dtype")
-    if k_cache.dim() != 5 or v_cache.shape != k_cache.shape:
-        raise ValueError("caches must be [num_blocks, num_layers, block_size, num_kv_heads, head_dim] with equal shapes")
-    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
-        raise ValueError("caches must be contiguous")
+    scales = _write_caches(key, value, k_cache, v_cache, layer_idx, k_scale, v_scale, "reshape_and_cache_varlen")
     T, Hkv, D = key.shape
     nb, L, bs, Hc, Dc = k_cache.shape
     if (Hc, Dc, bs) != (Hkv, D, block_size):
@@ -1176,6 +1260,13 @@ def reshape_and_cache_varlen(key, value, k_cache, v_cache, block_tables, cu_seql
     key, value = _rows16(key), _rows16(value)
     ks = (C.c_int64 * 2)(key.stride(0), key.stride(1))
     vs = (C.c_int64 * 2)(value.stride(0), value.stride(1))
+    if scales is not None:
+        check(lib.mio_reshape_and_cache_varlen_kv8(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(),
+                                                   v_cache.data_ptr(), *scales, block_tables.data_ptr(),
+                                                   cu_seqlens_new.data_ptr(), context_lengths.data_ptr(), ks, vs, B, T,
+                                                   Hkv, D, nb, L, int(layer_idx), bs, block_tables.shape[1], dt,
+                                                   _stream()))
+        return
     check(lib.mio_reshape_and_cache_varlen(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                                            block_tables.data_ptr(), cu_seqlens_new.data_ptr(),
                                            context_lengths.data_ptr(), ks, vs, B, T, Hkv, D, nb, L, int(layer_idx),
