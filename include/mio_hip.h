@@ -301,6 +301,28 @@ int mio_weight_block_glu(const void* w_gate, const void* w_up, int64_t ldw, void
 int mio_fused_mlp_glu_fwd_bw(const void* x, const void* wgu_b, const void* b_up, const void* b_gate, const void* w2b,
                              const void* b2, const void* residual, void* y, void* workspace, int64_t M, int32_t d, int32_t I,
                              int32_t dtype, int32_t x_blocked, void* stream);
+/* Which GEMM kernel a launch with these arguments takes (host-only: no pointer is dereferenced).  The same rule the launch
+ * switches on (csrc/gemm_route.h), for every entry point that ends in a GEMM (mio_gemm_bias_act, *_bw, *_bw_cs, mio_gemm_ln_bw
+ * and both stages of the FusedMLP forwards).  ld*: row strides in elements (a blocked operand: its row length, K or N);
+ * has_residual: a residual is added; w_layout: 0 row-major, 1 blocked (mio_weight_block), 2 gate / up interleaved
+ * (mio_weight_block_glu); fold_in / stats_out: the LayerNorm consumer / producer forms of mio_gemm_ln_bw.  The column scale
+ * is an argument of the persistent kernel, not a route.  Returns a mio_gemm_route_t, or < 0 (mio_last_error()) for
+ * arguments no entry point takes (sizes, strides, an activation or weight layout the form does not have). */
+typedef enum {
+  MIO_GEMM_ROUTE_EMPTY = 0,         /* M == 0: nothing is launched                                                 */
+  MIO_GEMM_ROUTE_T128 = 1,          /* gemm_bias_act_kernel, 128x128 tiles (fewer than 256 tiles of 256x256)       */
+  MIO_GEMM_ROUTE_T256 = 2,          /* gemm_bias_act_kernel, 256x256 tiles (K % 32 != 0, K < 128 or a long stride)  */
+  MIO_GEMM_ROUTE_P8W = 3,           /* gemm8w_kernel, persistent, no residual (column scale here)                  */
+  MIO_GEMM_ROUTE_P8W_RES = 4,       /* gemm8w_kernel with the residual epilogue                                   */
+  MIO_GEMM_ROUTE_P8W_FOLD = 5,      /* gemm8w_kernel, LayerNorm consumer (fold_in)                                */
+  MIO_GEMM_ROUTE_P8W_STATS = 6,     /* gemm8w_kernel, residual epilogue + row statistics (stats_out)              */
+  MIO_GEMM_ROUTE_GLU_T128X64 = 7,   /* gemm_bias_act_kernel SwiGLU, 128x64 tiles                                  */
+  MIO_GEMM_ROUTE_GLU_T256X128 = 8,  /* gemm_bias_act_kernel SwiGLU, 256x128 tiles (>= 256 of them)                */
+  MIO_GEMM_ROUTE_P8W_GLU = 9,       /* gemm8w_kernel SwiGLU on the interleaved blocked weight                     */
+  MIO_GEMM_ROUTE_P8W_GLU_FOLD = 10  /* the same, LayerNorm consumer                                               */
+} mio_gemm_route_t;
+int32_t mio_gemm_route(int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
+                       int32_t has_residual, int32_t w_layout, int32_t fold_in, int32_t stats_out);
 /* x_blocked != 0: the activation operand x is in the same blocked layout (m in the place of n; ceil(M/256)*256 x K
  * elements, ldx ignored) -- what mio_layernorm_fwd_bx writes, so that LayerNorm -> GEMM hands over contiguous K-tiles. */
 int mio_layernorm_fwd_bx(const void* x, const void* residual, const void* weight, const void* bias, void* yb,
@@ -321,8 +343,8 @@ int mio_layernorm_fwd_bx(const void* x, const void* residual, const void* weight
  *     for streams whose row mean is up to 4x their deviation.
  * flags: the operands in the blocked activation layout ((256-row, 32-column) blocks of 16 KiB, rows padded to 256; ld* ignored
  * for a blocked operand): x (as mio_gemm_bias_act_bw's x_blocked), y (what the next GEMM takes as blocked x), residual.
- * Shapes: mio_gemm_ln_ok(M, N, K, act, fold_in, stats_out) != 0 (blocked-weight shapes; fold_in: K % 256 == 0, act none /
- * gelu_tanh / swiglu; stats_out: N % 256 == 0, act none).  Without ln_stats and stats_out it is
+ * Shapes: mio_gemm_ln_ok(M, N, K, act, fold_in, stats_out) != 0 (blocked-weight shapes; fold_in: K % 256 == 0, K <= 8192 (the
+ * rows mio_ln_fold_weight prepares), act none / gelu_tanh / swiglu; stats_out: N % 256 == 0, act none).  Without ln_stats and stats_out it is
  * mio_gemm_bias_act_bw (+ column scale) with blocked y / residual.  act == MIO_ACT_SWIGLU: wb is mio_weight_block_glu of the two
  * folded weights (gate, up), bias the up bias, bias_gate the gate bias, N the number of OUTPUT columns (I). */
 #define MIO_GEMM_X_BLOCKED 1

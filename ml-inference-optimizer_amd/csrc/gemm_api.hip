@@ -3,6 +3,7 @@
 #include <string>
 
 #include "gemm_kernel.h"
+#include "gemm_route.h"
 
 extern template int gemm_launch<__bf16>(GemmDev, int, hipStream_t);
 extern template int gemm_launch<_Float16>(GemmDev, int, hipStream_t);
@@ -35,7 +36,8 @@ extern "C" int mio_gemm_bias_act(const void* x, const void* w, const void* bias,
                                  const void* bias_gate, const void* residual, void* y, int64_t M, int32_t N,
                                  int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
                                  int32_t dtype, void* stream) {
-  MIO_CHECK(x && w && y, "mio_gemm_bias_act: x, w, y must be non-null");
+  // (M == 0: x and y hold no element, and an empty allocation may be a null pointer)
+  MIO_CHECK(w && (M == 0 || (x && y)), "mio_gemm_bias_act: x, w, y must be non-null");
   MIO_CHECK(M >= 0 && N > 0 && K > 0, "mio_gemm_bias_act: bad sizes");
   MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_gemm_bias_act: dtype must be bf16 or fp16");
   MIO_CHECK(act >= MIO_ACT_NONE && act <= MIO_ACT_SWIGLU, "mio_gemm_bias_act: unknown activation");
@@ -295,8 +297,13 @@ extern "C" size_t mio_ln_stats_bytes(int64_t M, int32_t width) {
   return (size_t)((width + 255) / 256) * (size_t)((M + 255) / 256 * 256) * 2 * sizeof(float);
 }
 
+// the longest weight rows mio_ln_fold_weight prepares (ln_fold_weight_kernel: 256 threads x 32 elements), so the widest stream a
+// consumer (fold_in) takes
+constexpr int32_t GEMM_LN_FOLD_K_MAX = 8192;
+
 extern "C" int32_t mio_gemm_ln_ok(int64_t M, int32_t N, int32_t K, int32_t act, int32_t fold_in, int32_t stats_out) {
   if (mio_gemm_impl() != 0) return 0;
+  if (fold_in && K > GEMM_LN_FOLD_K_MAX) return 0;
   if (act == MIO_ACT_SWIGLU) {  // the gated stage (interleaved gate / up blocked weight, 256 x 128 output tiles): consumer form only
     const bool big = ((M + 255) / 256) * (int64_t)((N + 127) / 128) >= 256;
     return (big && !stats_out && N % 128 == 0 && K >= 128 && (int64_t)K * 512 < 0x7fffffff && (int64_t)N * 512 < 0x7fffffff &&
@@ -425,7 +432,7 @@ extern "C" int mio_ln_fold_weight(const void* w, int64_t ldw, const void* gamma,
                                   void* w_scaled, void* bias_out, int32_t N, int32_t K, int32_t dtype, void* stream) {
   MIO_CHECK(w && gamma && w_scaled && bias_out, "mio_ln_fold_weight: w, gamma, w_scaled, bias_out must be non-null");
   MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_ln_fold_weight: dtype must be bf16 or fp16");
-  MIO_CHECK(N > 0 && K > 0 && K <= 8192 && ldw >= K, "mio_ln_fold_weight: bad sizes (K <= 8192)");
+  MIO_CHECK(N > 0 && K > 0 && K <= GEMM_LN_FOLD_K_MAX && ldw >= K, "mio_ln_fold_weight: bad sizes (K <= 8192)");
 #define MIO_LNFW(T_, E_)                                                                                                       \
   hipLaunchKernelGGL((ln_fold_weight_kernel<T_, E_>), dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, (const T_*)w, ldw, \
                      (const T_*)gamma, (const T_*)beta, (const T_*)bias, (T_*)w_scaled, (T_*)bias_out, K)
@@ -507,4 +514,37 @@ extern "C" int mio_gemm_ln_bw(const void* x, const void* wb, const void* bias, c
   p.ln_stats = ln_stats; p.ln_eps = ln_eps; p.ln_slots = ln_stats ? ln_slots : 0;
   p.stats_out = stats_out;
   return gemm_dispatch(p, act, dtype, (hipStream_t)stream);
+}
+
+// ---- route query ------------------------------------------------------------------------------------------------------
+extern "C" int32_t mio_gemm_route(int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
+                                  int32_t has_residual, int32_t w_layout, int32_t fold_in, int32_t stats_out) {
+  MIO_CHECK(M >= 0 && N > 0 && K > 0, "mio_gemm_route: bad sizes");
+  MIO_CHECK(act >= MIO_ACT_NONE && act <= MIO_ACT_SWIGLU, "mio_gemm_route: unknown activation");
+  MIO_CHECK(w_layout >= 0 && w_layout <= 2, "mio_gemm_route: w_layout must be 0 (row-major), 1 (blocked) or 2 (gate / up interleaved)");
+  MIO_CHECK((w_layout == 2) == (act == MIO_ACT_SWIGLU) || w_layout == 0,
+            "mio_gemm_route: the interleaved weight belongs to act == SWIGLU, and SWIGLU has no plain blocked weight");
+  MIO_CHECK(K % 8 == 0 && N % 8 == 0, "mio_gemm_route: N and K must be multiples of 8");
+  MIO_CHECK(ldx % 8 == 0 && ldw % 8 == 0 && ldy % 8 == 0 && (!has_residual || ldr % 8 == 0) && ldx >= K && ldw >= K && ldy >= N,
+            "mio_gemm_route: bad strides");
+  MIO_CHECK(w_layout != 0 || (!fold_in && !stats_out), "mio_gemm_route: the LayerNorm forms take a blocked weight");
+  if (M == 0) return MIO_GEMM_ROUTE_EMPTY;
+  if (w_layout != 0) {
+    MIO_CHECK(ldx * 512 < (int64_t)0x7fffffff && ldy * 512 < (int64_t)0x7fffffff && (!has_residual || ldr * 512 < (int64_t)0x7fffffff),
+              "mio_gemm_route: row stride too large for the blocked-weight kernels");
+    if (fold_in || stats_out || act == MIO_ACT_SWIGLU) {
+      MIO_CHECK(mio_gemm_ln_ok(M, N, K, act, fold_in, stats_out),
+                "mio_gemm_route: this shape / activation does not take the folded kernels (mio_gemm_ln_ok == 0)");
+      MIO_CHECK(!(fold_in || act == MIO_ACT_SWIGLU) || !has_residual, "mio_gemm_route: the consumer and gated forms take no residual");
+      MIO_CHECK(!stats_out || has_residual, "mio_gemm_route: the producer form is the residual epilogue");
+    } else {
+      MIO_CHECK(gemm_blocked_w_ok(M, N, K, act), "mio_gemm_route: this shape does not take the blocked-weight kernels "
+                                                 "(mio_gemm_blocked_weight_ok == 0)");
+    }
+  }
+  GemmRouteArgs ra;
+  ra.M = M; ra.ldx = ldx; ra.ldw = w_layout != 0 ? K : ldw; ra.ldy = ldy; ra.ldr = ldr;
+  ra.N = N; ra.K = K; ra.act = act;
+  ra.res = has_residual != 0; ra.w_blk = w_layout; ra.ln_stats = fold_in != 0; ra.stats_out = stats_out != 0;
+  return gemm_pick_route(ra);
 }

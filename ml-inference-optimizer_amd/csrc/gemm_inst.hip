@@ -2,8 +2,10 @@
 // The product library reads no environment variable; A/B switches and stamp instantiations: -DMIO_DIAG (make dbg).
 #include <cstdlib>
 #include <mutex>
+#include <string>
 
 #include "gemm8w_kernel.h"
+#include "gemm_route.h"
 
 #if GEMM_TYPE_ID == 0
 using GT = __bf16;
@@ -65,53 +67,58 @@ static int launch_8w_res(const GemmDev& p, hipStream_t stream, bool one_tile = f
   return launch_8w<ACT, false, VAR>(p, stream, one_tile);
 }
 
+#ifdef MIO_DIAG
 static int gemm_impl() { return mio_gemm_impl(); }  // MIO_GEMM_IMPL (gemm_api.hip)
+#endif
 
 template <int ACT>
 static int launch_act(const GemmDev& p, hipStream_t stream) {
-  // Big tiles when they still fill the chip (>= 256 workgroups), else 128x128.
-  constexpr bool GATE = (ACT == MIO_ACT_SWIGLU);
-  if constexpr (GATE) {
-    if (p.w_blk == 2) {  // interleaved blocked gate / up weight (gemm_api.hip checked the shape)
-      if (p.ln_stats != nullptr) return launch_8w<ACT, false, 0, 1>(p, stream);  // LayerNorm applied in the read-out
-      return launch_8w<ACT, false>(p, stream);
+  // the kernel is named by gemm_pick_route (gemm_route.h), the same rule mio_gemm_route reports
+  GemmRouteArgs ra;
+  ra.M = p.M; ra.ldx = p.ldx; ra.ldw = p.ldw; ra.ldy = p.ldy; ra.ldr = p.ldr;
+  ra.N = p.N; ra.K = p.K; ra.act = ACT;
+  ra.res = p.res != nullptr; ra.w_blk = p.w_blk; ra.ln_stats = p.ln_stats != nullptr; ra.stats_out = p.stats_out != nullptr;
+  const int route = gemm_pick_route(ra);
+  if constexpr (ACT == MIO_ACT_SWIGLU) {
+    switch (route) {
+      case MIO_GEMM_ROUTE_P8W_GLU_FOLD: return launch_8w<ACT, false, 0, 1>(p, stream);  // LayerNorm applied in the read-out
+      case MIO_GEMM_ROUTE_P8W_GLU: return launch_8w<ACT, false>(p, stream);
+      case MIO_GEMM_ROUTE_GLU_T256X128: return launch_cfg<256, 128, 2, 4, ACT>(p, stream);
+      case MIO_GEMM_ROUTE_GLU_T128X64: return launch_cfg<128, 64, 2, 2, ACT>(p, stream);
     }
-    const int64_t big = ((p.M + 255) / 256) * ((p.N + 127) / 128);
-    if (big >= 256) return launch_cfg<256, 128, 2, 4, ACT>(p, stream);
-    return launch_cfg<128, 64, 2, 2, ACT>(p, stream);
   } else {
-    const int64_t big = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-    if (big >= 256) {
-      if (gemm_impl() == 1) return launch_cfg<256, 256, 2, 4, ACT>(p, stream);
-      // the 16x16x32 kernels address operands with 32-bit per-tile byte offsets and need whole K-tiles (>= 4 of them)
-      const bool fits = (p.K % 32 == 0) && p.K >= 128 && (p.ldx * 512 < (int64_t)0x7fffffff) &&
-                        (p.ldw * 512 < (int64_t)0x7fffffff) && (p.ldy * 512 < (int64_t)0x7fffffff) &&
-                        (p.res == nullptr || p.ldr * 512 < (int64_t)0x7fffffff);
-      if (!fits) return launch_cfg<256, 256, 2, 4, ACT>(p, stream);
-      // LayerNorm fold (mio_gemm_ln_bw checked the shape): consumer = projection behind the LayerNorm, producer = residual GEMM
-      if constexpr (ACT == MIO_ACT_NONE || ACT == MIO_ACT_GELU_TANH) {
-        if (p.ln_stats != nullptr) return launch_8w<ACT, false, 0, 1>(p, stream);
-      }
-      if constexpr (ACT == MIO_ACT_NONE) {
-        if (p.stats_out != nullptr) return launch_8w<ACT, true, 0, 2>(p, stream);
-      }
 #ifdef MIO_DIAG
-      if constexpr (ACT == MIO_ACT_NONE) {
-        if (gemm_impl() == 8 && p.dbg != nullptr) return launch_8w<ACT, false, 128>(p, stream);  // stamps
-        if (gemm_impl() == 24) return launch_8w_res<ACT, 2048>(p, stream);
-        if (gemm_impl() == 10) return launch_8w_res<ACT, 4>(p, stream);
-        if (gemm_impl() == 13) return launch_8w_res<ACT, 16>(p, stream);
-        if (gemm_impl() == 16) return launch_8w_res<ACT, 64>(p, stream);
-      }
-      if constexpr (ACT == MIO_ACT_GELU_TANH) {
-        if (gemm_impl() == 20) return launch_8w<ACT, false, 256>(p, stream);  // scalar activation math
-      }
-      if (gemm_impl() == 9) return launch_8w_res<ACT>(p, stream, true);  // one workgroup per tile
+    // A/B: the generic 256x256 kernel in place of the persistent one
+    if (gemm_impl() == 1 && route != MIO_GEMM_ROUTE_T128) return launch_cfg<256, 256, 2, 4, ACT>(p, stream);
 #endif
-      return launch_8w_res<ACT>(p, stream);
+    switch (route) {
+      case MIO_GEMM_ROUTE_T128: return launch_cfg<128, 128, 2, 2, ACT>(p, stream);
+      case MIO_GEMM_ROUTE_T256: return launch_cfg<256, 256, 2, 4, ACT>(p, stream);
+      case MIO_GEMM_ROUTE_P8W_FOLD:
+        if constexpr (ACT == MIO_ACT_NONE || ACT == MIO_ACT_GELU_TANH) return launch_8w<ACT, false, 0, 1>(p, stream);
+        break;
+      case MIO_GEMM_ROUTE_P8W_STATS:
+        if constexpr (ACT == MIO_ACT_NONE) return launch_8w<ACT, true, 0, 2>(p, stream);
+        break;
+      case MIO_GEMM_ROUTE_P8W:
+      case MIO_GEMM_ROUTE_P8W_RES:
+#ifdef MIO_DIAG
+        if constexpr (ACT == MIO_ACT_NONE) {
+          if (gemm_impl() == 8 && p.dbg != nullptr) return launch_8w<ACT, false, 128>(p, stream);  // stamps
+          if (gemm_impl() == 24) return launch_8w_res<ACT, 2048>(p, stream);
+          if (gemm_impl() == 10) return launch_8w_res<ACT, 4>(p, stream);
+          if (gemm_impl() == 13) return launch_8w_res<ACT, 16>(p, stream);
+          if (gemm_impl() == 16) return launch_8w_res<ACT, 64>(p, stream);
+        }
+        if constexpr (ACT == MIO_ACT_GELU_TANH) {
+          if (gemm_impl() == 20) return launch_8w<ACT, false, 256>(p, stream);  // scalar activation math
+        }
+        if (gemm_impl() == 9) return launch_8w_res<ACT>(p, stream, true);  // one workgroup per tile
+#endif
+        return launch_8w_res<ACT>(p, stream);
     }
-    return launch_cfg<128, 128, 2, 2, ACT>(p, stream);
   }
+  return mio_fail("gemm: no kernel for route " + std::to_string(route));
 }
 
 template <>

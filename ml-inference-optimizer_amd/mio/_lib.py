@@ -54,6 +54,23 @@ DECODE_ROUTES = {
     2: "gqa",
 }
 
+# mio_gemm_route_t: the kernel a GEMM launch takes (include/mio_hip.h, csrc/gemm_route.h)
+GEMM_ROUTES = {
+    0: "empty",
+    1: "t128",
+    2: "t256",
+    3: "p8w",
+    4: "p8w_res",
+    5: "p8w_fold",
+    6: "p8w_stats",
+    7: "glu_t128x64",
+    8: "glu_t256x128",
+    9: "p8w_glu",
+    10: "p8w_glu_fold",
+}
+# weight layouts mio_gemm_route takes
+W_PLAIN, W_BLOCKED, W_GLU = range(3)
+
 # every symbol include/mio_hip.h declares
 EXPORTS = (
     "mio_version",
@@ -87,6 +104,7 @@ EXPORTS = (
     "mio_weight_blocked_glu_bytes",
     "mio_weight_block_glu",
     "mio_fused_mlp_glu_fwd_bw",
+    "mio_gemm_route",
     "mio_layernorm_fwd_bx",
     "mio_ln_stats_bytes",
     "mio_gemm_ln_ok",
@@ -269,6 +287,8 @@ def _load() -> C.CDLL:
     lib.mio_weight_block_glu.restype = i32
     lib.mio_fused_mlp_glu_fwd_bw.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]
     lib.mio_fused_mlp_glu_fwd_bw.restype = i32
+    lib.mio_gemm_route.argtypes = [i64, i32, i32, i64, i64, i64, i64, i32, i32, i32, i32, i32]
+    lib.mio_gemm_route.restype = i32
     lib.mio_ln_stats_bytes.argtypes = [i64, i32]
     lib.mio_ln_stats_bytes.restype = C.c_size_t
     lib.mio_gemm_ln_ok.argtypes = [i64, i32, i32, i32, i32, i32]

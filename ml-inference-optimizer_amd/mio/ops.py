@@ -600,6 +600,55 @@ def col_scale_ok(M: int, N: int, K: int, activation: str = "none") -> bool:
     return not _NO_BLOCKED_W and bool(lib.mio_gemm_col_scale_ok(M, N, K, _ACT.get(activation, _lib.ACT_NONE)))
 
 
+def _bw_ok(M: int, N: int, K: int, act: int, ldx: int, w_blocked) -> bool:
+    """gemm_bias_act with a row-major x: True iff it calls the blocked-weight entry point (else the plain one)."""
+    return w_blocked is not None and act != _lib.ACT_SWIGLU and bool(lib.mio_gemm_blocked_weight_ok(M, N, K, act)) and \
+        ldx * 512 < 0x7fffffff
+
+
+def _gemm_route(M, N, K, ldx, ldw, ldy, ldr, act, residual: bool, w_layout, fold_in=False, stats_out=False) -> str:
+    r = lib.mio_gemm_route(M, N, K, ldx, ldw, ldy, ldr, act, int(residual), w_layout, int(fold_in), int(stats_out))
+    if r < 0:
+        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
+    return _lib.GEMM_ROUTES[r]
+
+
+def gemm_route(x, w, bias=None, activation: str = "none", **kwargs) -> str:
+    """The kernel (a name of mio._lib.GEMM_ROUTES) that gemm_bias_act(x, w, bias, activation, **kwargs) -- or, with the
+    keyword-only M / N / K of that signature, gemm_ln(x, w, bias, **kwargs) -- launches.  Host-only (mio_gemm_route): it reads
+    shapes, strides and which operands are given, never the data.  ValueError where the call would be refused."""
+    if activation not in _ACT:
+        raise ValueError(f"Unsupported activation function: {activation}")
+    act = _ACT[activation]
+    if "M" in kwargs:  # gemm_ln
+        M, N, K = int(kwargs["M"]), int(kwargs["N"]), int(kwargs["K"])
+        ldx = K if kwargs.get("x_blocked") else _rows16(x.reshape(-1, K)).stride(0)
+        residual = kwargs.get("residual")
+        ldr = 0
+        if residual is not None:
+            ldr = N if kwargs.get("res_blocked") else _rows16(residual.reshape(-1, N)).stride(0)
+        return _gemm_route(M, N, K, ldx, K, N, ldr, act, residual is not None,
+                           _lib.W_GLU if act == _lib.ACT_SWIGLU else _lib.W_BLOCKED,
+                           kwargs.get("ln_stats") is not None, bool(kwargs.get("stats_out", False)))
+    unknown = set(kwargs) - {"w_gate", "bias_gate", "residual", "out", "w_blocked", "x_blocked_shape", "col_scale"}
+    if unknown:
+        raise TypeError(f"gemm_route: unexpected arguments {sorted(unknown)}")
+    K, N = x.shape[-1], w.shape[0]
+    out, residual, w_blocked = kwargs.get("out"), kwargs.get("residual"), kwargs.get("w_blocked")
+    xbs = kwargs.get("x_blocked_shape")
+    ldy = N if out is None else out.view(-1, N).stride(0)
+    ldr = 0 if residual is None else _rows16(residual.reshape(-1, N)).stride(0)
+    if xbs is not None or kwargs.get("col_scale") is not None:
+        M = int(math.prod(xbs[:-1])) if xbs is not None else x.numel() // K
+        ldx = K if xbs is not None else _rows16(x.reshape(-1, K)).stride(0)
+        return _gemm_route(M, N, K, ldx, K, ldy, ldr, act, residual is not None, _lib.W_BLOCKED)
+    x2 = _rows16(x.reshape(-1, K))
+    M = x2.shape[0]
+    if _bw_ok(M, N, K, act, x2.stride(0), w_blocked):
+        return _gemm_route(M, N, K, x2.stride(0), K, ldy, ldr, act, residual is not None, _lib.W_BLOCKED)
+    return _gemm_route(M, N, K, x2.stride(0), _rows16(w).stride(0), ldy, ldr, act, residual is not None, _lib.W_PLAIN)
+
+
 def gemm_bias_act(x, w, bias=None, activation: str = "none", w_gate=None, bias_gate=None, residual=None, out=None,
                   w_blocked=None, x_blocked_shape=None, col_scale=None):
     """y = act(x @ w^T + bias) (+ residual); x [..., K], w [N, K].  F.linear with a fused epilogue.
@@ -674,8 +723,7 @@ def gemm_bias_act(x, w, bias=None, activation: str = "none", w_gate=None, bias_g
     if residual is not None:
         _res_ok(residual, M * N, x.dtype)
         r2 = _rows16(residual.reshape(-1, N))
-    if w_blocked is not None and act != _lib.ACT_SWIGLU and lib.mio_gemm_blocked_weight_ok(M, N, K, act) and \
-            x2.stride(0) * 512 < 0x7fffffff:
+    if _bw_ok(M, N, K, act, x2.stride(0), w_blocked):
         check(lib.mio_gemm_bias_act_bw(x2.data_ptr(), w_blocked.data_ptr(), _ptr(bias), _ptr(r2), y2.data_ptr(), M, N, K,
                                        x2.stride(0), y2.stride(0), 0 if r2 is None else r2.stride(0), act, dt, 0, _stream()))
         return out
@@ -799,6 +847,39 @@ def _blocked_sizes_ok(fc1_blocked, fc2_blocked, x, d, I, act):
                              f"(swiglu: block_weight_glu(gate, up)); repack after converting the module")
 
 
+def _mlp_bw_entry(M: int, d: int, I: int, act: int, fc1_blocked, fc2_blocked) -> bool:
+    """fused_mlp with a row-major input: True iff it calls the blocked-weight entry points (else mio_fused_mlp_fwd)."""
+    return fc1_blocked is not None and fc2_blocked is not None and bool(lib.mio_fused_mlp_blocked_weight_ok(M, d, I, act))
+
+
+def fused_mlp_route(hidden_states, fc1_weight, fc1_bias=None, fc2_weight=None, fc2_bias=None, activation: str = "gelu",
+                    fc1_gate_weight=None, fc1_gate_bias=None, residual=None, fc1_blocked=None, fc2_blocked=None,
+                    x_blocked_shape=None) -> dict:
+    """How fused_mlp(...) with these arguments runs (host-only): {"path": "blocked" (both stages on the 256x256-tile kernels,
+    the intermediate in the blocked layout) or "two_launch" (two gemm_bias_act launches, row-major intermediate),
+    "stage1": route, "stage2": route} with route names of mio._lib.GEMM_ROUTES."""
+    if activation not in _ACT or _ACT[activation] == _lib.ACT_NONE:
+        raise ValueError(f"Unsupported activation function: {activation}")
+    act = _ACT[activation]
+    if x_blocked_shape is not None:
+        d, M = x_blocked_shape[-1], int(math.prod(x_blocked_shape[:-1]))
+    else:
+        d, M = hidden_states.shape[-1], hidden_states.numel() // hidden_states.shape[-1]
+    I = fc1_weight.shape[0]
+    has_res = residual is not None
+    wblk = 1 if (x_blocked_shape is not None or _mlp_bw_entry(M, d, I, act, fc1_blocked, fc2_blocked)) else 0
+    # mio_fused_mlp_fwd* (gemm_api.hip fused_mlp_impl): the blocked two-stage form wherever mio_fused_mlp_blocked_weight_ok,
+    # SwiGLU only with its interleaved blocked weight
+    if M > 0 and lib.mio_fused_mlp_blocked_weight_ok(M, d, I, act) and (act != _lib.ACT_SWIGLU or wblk):
+        w1 = _lib.W_GLU if act == _lib.ACT_SWIGLU else wblk
+        return {"path": "blocked",
+                "stage1": _gemm_route(M, I, d, d, d, I, 0, act, False, w1),
+                "stage2": _gemm_route(M, d, I, I, I, d, d, _lib.ACT_NONE, has_res, wblk)}
+    return {"path": "two_launch",
+            "stage1": _gemm_route(M, I, d, d, d, I, 0, act, False, _lib.W_PLAIN),
+            "stage2": _gemm_route(M, d, I, I, I, d, d, _lib.ACT_NONE, has_res, _lib.W_PLAIN)}
+
+
 def fused_mlp(
     hidden_states: torch.Tensor,
     fc1_weight: torch.Tensor,
@@ -876,7 +957,7 @@ def fused_mlp(
             r2 = r2.contiguous()
     gate_w = fc1_gate_weight if act == _lib.ACT_SWIGLU else None
     gate_b = fc1_gate_bias if act == _lib.ACT_SWIGLU else None
-    if fc1_blocked is not None and fc2_blocked is not None and lib.mio_fused_mlp_blocked_weight_ok(M, d, I, act):
+    if _mlp_bw_entry(M, d, I, act, fc1_blocked, fc2_blocked):
         _blocked_sizes_ok(fc1_blocked, fc2_blocked, hidden_states, d, I, act)
         if act == _lib.ACT_SWIGLU:
             check(lib.mio_fused_mlp_glu_fwd_bw(x2.data_ptr(), fc1_blocked.data_ptr(), _ptr(fc1_bias), _ptr(gate_b),
