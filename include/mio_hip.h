@@ -480,6 +480,12 @@ int mio_reshape_and_cache_varlen(const void* key, const void* value, void* k_cac
  * Decode is mio_fa3_decode_paged_window over K = x8 * k_scale, V = x8 * v_scale: window_left -1
  * (unbounded) or >= 0, the same routes (head / rows / gqa), the same workspace
  * (mio_fa3_decode_workspace_bytes); mio_fa3_decode_kv8_route is its host-only route query.
+ * Paged prefill (chunked prefill, shared prefixes, multi-token verify) is mio_fa3_fwd_paged_kv8:
+ * mio_fa3_fwd_paged_window over K = x8 * k_scale, V = x8 * v_scale (window (-1, -1) = none), the
+ * same kernels (fwd5 at padded head dim 64, fwd3 at 96 / 128) widening the bytes exactly to 16 bits
+ * in LDS; p->dtype is that of q / o, p->k_cache / p->v_cache address bytes.  Refused besides what
+ * mio_fa3_fwd_paged(_window) refuses: null or misaligned scales, head_dim % 16 != 0.
+ * mio_fa3_paged_kv8_route is its host-only route query (a mio_fa3_paged_route_t).
  * ------------------------------------------------------------------------------------------ */
 int mio_reshape_and_cache_kv8(const void* key, const void* value, void* k_cache, void* v_cache,
                               const float* k_scale, const float* v_scale, const int32_t* block_tables,
@@ -507,6 +513,10 @@ int mio_fa3_decode_kv8_route(const void* q, void* o, const void* k_cache, const 
                              int32_t B, int32_t H, int32_t Hkv, int32_t q_len, int32_t D, int32_t num_layers,
                              int32_t layer_idx, int32_t block_size, int32_t max_blocks_per_seq, int32_t max_ctx,
                              float scale, int32_t window_left, int32_t dtype, void* workspace, void* stream);
+int mio_fa3_fwd_paged_kv8(const mio_fa3_paged_params_t* p, const float* k_scale, const float* v_scale,
+                          int32_t window_left, int32_t window_right, void* stream);
+int32_t mio_fa3_paged_kv8_route(const mio_fa3_paged_params_t* p, const float* k_scale, const float* v_scale,
+                                int32_t window_left, int32_t window_right);
 
 #ifdef __cplusplus
 }

@@ -241,6 +241,19 @@ static int fa3_paged_validate(const mio_fa3_paged_params_t* a) {
 
 extern "C" int32_t mio_fa3_paged_route(const mio_fa3_paged_params_t* a) { return fa_seq_route(a, fa3_paged_validate); }
 
+// the kernels' description of the paged launch a (validated)
+static FaPaged fa_paged_of(const mio_fa3_paged_params_t* a) {
+  FaPaged pg;
+  pg.cu_q = a->cu_seqlens_q; pg.seqused_k = a->seqused_k; pg.block_tables = a->block_tables;
+  pg.total_q = a->total_q; pg.max_q = a->max_seqlen_q;
+  pg.max_k = (int)std::min<int64_t>(a->max_seqlen_k, (int64_t)a->max_blocks_per_seq * a->block_size);
+  pg.num_blocks = a->num_blocks; pg.num_layers = a->num_layers; pg.layer = a->layer_idx;
+  pg.block_size = a->block_size; pg.max_blocks = a->max_blocks_per_seq;
+  pg.tpb = a->block_size / 64;
+  pg.tpb_magic = (uint32_t)(((1ull << 31) + pg.tpb - 1) / pg.tpb);
+  return pg;
+}
+
 extern "C" int mio_fa3_fwd_paged(const mio_fa3_paged_params_t* a, void* stream) {
   if (fa3_paged_validate(a) != 0) return -1;
   if (a->B == 0 || a->total_q == 0) return 0;
@@ -250,14 +263,7 @@ extern "C" int mio_fa3_fwd_paged(const mio_fa3_paged_params_t* a, void* stream) 
   p.ks_s = p.vs_s = (int64_t)a->Hkv * a->D;  // the cache's token stride; pages and layers come from the walk
   p.ks_h = p.vs_h = a->D;
   p.os_s = a->o_stride[0]; p.os_h = a->o_stride[1];
-  FaPaged pg;
-  pg.cu_q = a->cu_seqlens_q; pg.seqused_k = a->seqused_k; pg.block_tables = a->block_tables;
-  pg.total_q = a->total_q; pg.max_q = a->max_seqlen_q;
-  pg.max_k = (int)std::min<int64_t>(a->max_seqlen_k, (int64_t)a->max_blocks_per_seq * a->block_size);
-  pg.num_blocks = a->num_blocks; pg.num_layers = a->num_layers; pg.layer = a->layer_idx;
-  pg.block_size = a->block_size; pg.max_blocks = a->max_blocks_per_seq;
-  pg.tpb = a->block_size / 64;
-  pg.tpb_magic = (uint32_t)(((1ull << 31) + pg.tpb - 1) / pg.tpb);
+  const FaPaged pg = fa_paged_of(a);
 
   return fa_dispatch(a->dtype, a->D, [&](auto i) {
     return fa3_seq_launch<typename decltype(i)::T, decltype(i)::D>(p, pg, a->causal, (hipStream_t)stream);
@@ -382,16 +388,48 @@ extern "C" int mio_fa3_fwd_paged_window(const mio_fa3_paged_params_t* a, int32_t
   p.ks_s = p.vs_s = (int64_t)a->Hkv * a->D;
   p.ks_h = p.vs_h = a->D;
   p.os_s = a->o_stride[0]; p.os_h = a->o_stride[1];
-  FaPaged pg;
-  pg.cu_q = a->cu_seqlens_q; pg.seqused_k = a->seqused_k; pg.block_tables = a->block_tables;
-  pg.total_q = a->total_q; pg.max_q = a->max_seqlen_q;
-  pg.max_k = (int)std::min<int64_t>(a->max_seqlen_k, (int64_t)a->max_blocks_per_seq * a->block_size);
-  pg.num_blocks = a->num_blocks; pg.num_layers = a->num_layers; pg.layer = a->layer_idx;
-  pg.block_size = a->block_size; pg.max_blocks = a->max_blocks_per_seq;
-  pg.tpb = a->block_size / 64;
-  pg.tpb_magic = (uint32_t)(((1ull << 31) + pg.tpb - 1) / pg.tpb);
+  const FaPaged pg = fa_paged_of(a);
   const int wl = fa_window_clamp(window_left), wr = fa_window_clamp(window_right);
   return fa_dispatch(a->dtype, a->D, [&](auto i) {
     return fa3_win_seq_launch<typename decltype(i)::T, decltype(i)::D>(p, pg, a->causal, wl, wr, (hipStream_t)stream);
+  });
+}
+
+// ---- the fp8 (e4m3fn) KV cache: mio_fa3_fwd_paged_kv8 (fa3_kv8_inst.hip).  The checks of mio_fa3_fwd_paged (and of
+// mio_fa3_fwd_paged_window when windowed), then the scales and head_dim % 16; the cache pointers address bytes.
+
+static int fa3_paged_kv8_validate(const mio_fa3_paged_params_t* a, const float* k_scale, const float* v_scale,
+                                  int32_t left, int32_t right) {
+  const char* fn = "mio_fa3_fwd_paged_kv8";
+  if (fa_windowed(left, right) ? fa3_paged_window_validate(a, left, right) != 0 : fa3_paged_validate(a) != 0) return -1;
+  MIO_CHECK(k_scale != nullptr && v_scale != nullptr,
+            std::string(fn) + ": k_scale and v_scale are required with an fp8 cache (null scale pointer)");
+  MIO_CHECK(((uintptr_t)k_scale & 3) == 0 && ((uintptr_t)v_scale & 3) == 0, std::string(fn) + ": scales must be 4-byte aligned fp32");
+  MIO_CHECK(a->D % 16 == 0, std::string(fn) + ": head_dim must be a multiple of 16 in [16,128] for an fp8 cache");
+  return 0;
+}
+
+extern "C" int32_t mio_fa3_paged_kv8_route(const mio_fa3_paged_params_t* a, const float* k_scale, const float* v_scale,
+                                           int32_t window_left, int32_t window_right) {
+  if (fa3_paged_kv8_validate(a, k_scale, v_scale, window_left, window_right) != 0) return MIO_FA3_PAGED_ROUTE_INVALID;
+  if (a->B == 0 || a->total_q == 0) return MIO_FA3_PAGED_ROUTE_EMPTY;
+  return dpad_of(a->D) == 64 ? MIO_FA3_PAGED_ROUTE_FWD5 : MIO_FA3_PAGED_ROUTE_FWD3;
+}
+
+extern "C" int mio_fa3_fwd_paged_kv8(const mio_fa3_paged_params_t* a, const float* k_scale, const float* v_scale,
+                                     int32_t window_left, int32_t window_right, void* stream) {
+  if (fa3_paged_kv8_validate(a, k_scale, v_scale, window_left, window_right) != 0) return -1;
+  if (a->B == 0 || a->total_q == 0) return 0;
+  FaDev p = fa_dev(a->q, a->k_cache, a->v_cache, a->o, a->lse, a->B, a->H, a->Hkv, a->D, a->softmax_scale);
+  p.qs_s = a->q_stride[0]; p.qs_h = a->q_stride[1];
+  p.ks_s = p.vs_s = (int64_t)a->Hkv * a->D / 2;  // the bodies count 16-bit units: half the one-byte row
+  p.ks_h = p.vs_h = a->D / 2;
+  p.os_s = a->o_stride[0]; p.os_h = a->o_stride[1];
+  const FaPaged pg = fa_paged_of(a);
+  const bool win = fa_windowed(window_left, window_right);
+  const int wl = win ? fa_window_clamp(window_left) : -1, wr = win ? fa_window_clamp(window_right) : -1;
+  return fa_dispatch(a->dtype, a->D, [&](auto i) {
+    return fa3_kv8_launch<typename decltype(i)::T, decltype(i)::D>(p, pg, k_scale, v_scale, a->causal, wl, wr,
+                                                                    (hipStream_t)stream);
   });
 }

@@ -6,11 +6,20 @@
 // FA_WINDOW (the sliding-window kernels, fa3_win_inst.hip): as in fa3_fwd5_body.inc -- rows bounded to keys
 // i + q_offset - k_offset - wl .. i + q_offset - k_offset + wr, each pass walks tiles t_lo .. t_lo + n_tiles - 1 (the
 // loop and the LDS stages relative to the walk, FA_KV_TILE absolute), left-edge tiles get a lower-limit compare.
+// FA_KV8 (the fp8 KV-cache kernels, fa3_kv8_inst.hip): K / V arrive one byte per element (e4m3fn; p.ks_s / p.vs_s in
+// 16-bit units, so ks2 / vs2 are the byte strides of the one-byte rows), `kv8_vs` (a float from the kernel) multiplies
+// the output.  Wave w DMAs K rows and V rows 16 w .. 16 w + 15 (two 1-KiB units each) to the start of the 16-bit images
+// of those rows, and widens them in place in front of the barrier that publishes the tile (land).  Without FA_KV8 the
+// text below is what it was before it.
   using X8 = typename DT<T>::x8;
   using X4 = typename DT<T>::x4;
   using OPS = Fa3Ops<T>;
   using MAP = Fa3Map<D>;
+#ifdef FA_KV8
+  constexpr int QT = 2, KS = MAP::KS, DT_ = MAP::DT, UPW = 4;  // units per wave: K rows 16 w .. + 15, then the V rows
+#else
   constexpr int QT = 2, KS = MAP::KS, DT_ = MAP::DT, UPW = MAP::UPW;
+#endif
   constexpr int FA3_T_O = MAP::T_O, FA3_T_L = MAP::T_L, FA3_A_Q = MAP::A_Q, FA3_A_ONES = MAP::A_ONES;
   using SM = FaSmem<D>;
 #define IC(N) std::integral_constant<int, (N)> {}
@@ -198,6 +207,52 @@
     const int ks2 = (int)p.ks_s * 2, vs2 = (int)p.vs_s * 2;  // row strides in bytes
     const int last_tile = (p.Sk - 1) >> 6, last_row = (p.Sk - 1) & (FA_BN - 1);
     int st_off[UPW], st_offl[UPW];  // per slot: byte offset of this lane's 16-B chunk from the tile's first row (full / last tile)
+#ifdef FA_KV8
+    // fp8 slot i (0, 1: K, 2, 3: V), lane l: element e = 64 (i & 1) + l of the wave's rows in row-major 16-element chunks
+    // (D / 16 per row); lanes past the 16 rows (padded D 96: e >= 96) repeat the last chunk into bytes the widening
+    // overwrites.  kv8_w[i]: where the chunk's 32 bytes of 16-bit image go, relative to the stage (-1: nowhere)
+    constexpr int C8 = D / 16;
+    const int kv8_k = 16 * wave * SM::KROW, kv8_v = SM::K_BYTES + 32 * D * wave;  // the wave's K / V image regions
+    int kv8_w[UPW];
+#pragma unroll
+    for (int i = 0; i < UPW; ++i) {
+      const int e = 64 * (i & 1) + lane;
+      const bool live = e < 16 * C8;
+      const int rw = live ? e / C8 : 15, j = live ? e % C8 : C8 - 1, row = 16 * wave + rw;
+      const int c = j < (p.D >> 4) ? j : (p.D >> 4) - 1;
+      const int rowl = row < last_row ? row : last_row;
+      st_off[i] = row * (i < 2 ? ks2 : vs2) + 16 * c;
+      st_offl[i] = rowl * (i < 2 ? ks2 : vs2) + 16 * c;
+      // K: row-major rows of KROW bytes; V: [key / 8][d / 32][8][32] sub-tiles of 512 bytes
+      const int w = i < 2 ? kv8_k + rw * SM::KROW + 32 * j
+                          : kv8_v + ((rw >> 3) * DT_ + (j >> 1)) * 512 + (rw & 7) * 64 + (j & 1) * 32;
+      kv8_w[i] = live ? w : -1;
+    }
+    // widen this wave's four fp8 KiB of the tile in stage `st` (all four read before the first write: in place)
+    auto kv8_expand = [&](int st) {
+      char* sb = smem + st * SM::STAGE;
+      u32x4_t x[UPW];
+#pragma unroll
+      for (int i = 0; i < UPW; ++i) x[i] = *(const u32x4_t*)(sb + (i < 2 ? kv8_k : kv8_v) + 1024 * (i & 1) + 16 * lane);
+      asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]) : : "memory");
+#pragma unroll
+      for (int i = 0; i < UPW; ++i) {
+        u32x4_t lo, hi;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          lo[2 * k] = kv8_cvt2<T, false>(x[i][k]);
+          lo[2 * k + 1] = kv8_cvt2<T, true>(x[i][k]);
+          hi[2 * k] = kv8_cvt2<T, false>(x[i][k + 2]);
+          hi[2 * k + 1] = kv8_cvt2<T, true>(x[i][k + 2]);
+        }
+        if (kv8_w[i] >= 0) {
+          *(u32x4_t*)(sb + kv8_w[i]) = lo;
+          *(u32x4_t*)(sb + kv8_w[i] + 16) = hi;
+        }
+      }
+    };
+    int kv8_next = 2;  // the tile the next land() widens
+#else
 #pragma unroll
     for (int i = 0; i < UPW; ++i) {
       int u, row, c;
@@ -217,6 +272,7 @@
       st_off[i] = row * (i < KSL ? ks2 : vs2) + 16 * c;
       st_offl[i] = rowl * (i < KSL ? ks2 : vs2) + 16 * c;
     }
+#endif
     const int kl_imm = (wave + 4 * (KSL - 1) < MAP::KU) ? 4096 * (KSL - 1) : 0;  // LDS offset of the last K slot's unit
     // one DMA unit of tile `tile` (clamped to the last tile: a run past the end re-fetches valid data into a dead
     // stage, which keeps the number of loads per iteration -- and the counted waits -- the same for every iteration)
@@ -238,6 +294,11 @@
     auto dma_unit = [&](auto I_, int) {
       constexpr int i = decltype(I_)::value;
       const int off = dma_is_last ? st_offl[i] : st_off[i];
+#ifdef FA_KV8
+      const char* base = (i < 2) ? dma_kb : dma_vb;
+      const uint32_t lds = dma_lds - 1024 * wave + (i < 2 ? kv8_k : kv8_v) + 1024 * (i & 1);
+      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(lds), "v"(off), "s"(base) : "memory", "m0");
+#else
       const char* base = (i < KSL) ? dma_kb : dma_vb;
       // asm: invisible to the compiler's wait-count insertion, which otherwise drains the DMA (vmcnt(0)) in front of
       // the next LDS read it cannot prove disjoint -- the V fragments of the tile being computed
@@ -253,6 +314,7 @@
                      : "s"(dma_lds), "n"(imm), "v"(off), "s"(base)
                      : "memory", "m0", "scc");  // s_add writes SCC
       }
+#endif
     };
     auto stage_dma = [&](int tile) {
       dma_tile_base(tile);
@@ -315,6 +377,11 @@
     });
     asm volatile("s_nop 7" ::: "memory");  // accumulator-file writes settle before the first MFMA reads them
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(UPW) : "memory");  // tiles 0 and 1 have landed, tile 2 may still fly
+#ifdef FA_KV8
+    kv8_expand(0);
+    kv8_expand(1);
+    kv8_next = 2;
+#endif
     __syncthreads();
     if constexpr (STAMP) pt2 = __builtin_amdgcn_s_memtime();
 
@@ -600,6 +667,10 @@
     // move (other waves of the workgroup still need them: causal, this wave's rows end earlier)
     auto land = [&]() {  // end of an iteration: this wave's share of tile t + 2 has landed (tile t + 3 may still fly)
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(UPW) : "memory");
+#ifdef FA_KV8
+      kv8_expand(kv8_next & (FA3_STAGES - 1));
+      ++kv8_next;
+#endif
       __syncthreads();
     };
     unsigned long long st_sum[5] = {0, 0, 0, 0, 0};  // diagnostic build: cycles in phase 1 / mask / phase 2 / update / land
@@ -670,7 +741,11 @@
     fa2_for<QT>([&](auto QTI) {
       constexpr int qt = decltype(QTI)::value;
       const float l_tot = Fa2AccIO<FA3_T_L + qt>::template read4<0>()[0];
+#ifdef FA_KV8
+      const float inv = (l_tot > 0.f) ? fast_rcp(l_tot) * kv8_vs : 0.f;  // V = x8 * v_scale
+#else
       const float inv = (l_tot > 0.f) ? fast_rcp(l_tot) : 0.f;
+#endif
       if (q_ok[qt]) {
         if (p.lse != nullptr && h == 0) {
           const float lse = (l_tot > 0.f) ? ((KPRE ? ref[qt] : m_i[qt]) + fast_log2(l_tot)) * FA_LN2 : -INFINITY;

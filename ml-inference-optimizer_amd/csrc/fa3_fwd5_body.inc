@@ -8,6 +8,12 @@
 // walks the tiles t_lo .. t_lo + n_tiles - 1: the loop, the virtual-tile stream and the LDS stages stay relative to the
 // walk, FA_KV_TILE receives the absolute tile, and tiles at the left edge get a per-row lower-limit compare.  Without
 // FA_WINDOW the text below is what it was before the window.
+// FA_KV8 (the fp8 KV-cache kernels, fa3_kv8_inst.hip): K / V arrive one byte per element (e4m3fn; p.ks_s / p.vs_s are
+// given in 16-bit units, so ks2 / vs2 are the byte strides of the one-byte rows) and `kv8_vs` (a float from the kernel)
+// multiplies the output.  Waves 0..3 DMA K rows 16 w .. 16 w + 15, waves 4..7 the same V rows, into the first KiB of
+// the 2-KiB 16-bit image of those rows; at the wait in front of the barrier that publishes a tile, each wave widens its
+// own KiB in place (v_cvt_scalef32_pk_*_fp8, scale 1: exact) into the swizzled image the fragment reads expect.
+// Without FA_KV8 the text below is what it was before it.
   using X8 = typename DT<T>::x8;
   using X4 = typename DT<T>::x4;
   constexpr int NKT = 4, NQG = 2, NDS = 2, NDT = 4, NS = 2;
@@ -54,6 +60,28 @@
   const int ks2 = (int)p.ks_s * 2, vs2 = (int)p.vs_s * 2;
   const int last_tile = (p.Sk - 1) >> 6, last_row = (p.Sk - 1) & (FA_BN - 1);
   // DMA: wave w moves rows 8 w .. 8 w + 7 of the K tile and of the V tile (one 1-KiB unit each)
+#ifdef FA_KV8
+  // fp8: lane l of wave w moves row 16 (w & 3) + l / 4, 16-element chunk l % 4 (clamped into D) of K (w < 4) or V, to
+  // byte 16 l of the wave's image region; kv8_w0 / kv8_w1: where its two 16-bit halves go, relative to that region
+  int off8, off8l, kv8_w0, kv8_w1;
+  const int kv8_reg = wave < 4 ? 2048 * wave : FA5_KBYTES + 2048 * (wave - 4);
+  {
+    const int rw = lane >> 2, row = 16 * (wave & 3) + rw, j = lane & 3, c8 = p.D >> 4;
+    const int rowl = row < last_row ? row : last_row;
+    const int c = j < c8 ? j : c8 - 1;
+    const int rs = wave < 4 ? ks2 : vs2;
+    off8 = row * rs + 16 * c;
+    off8l = rowl * rs + 16 * c;
+    if (wave < 4) {  // K: 16-bit chunks 2 j, 2 j + 1 at positions (2 j) ^ x, (2 j + 1) ^ x, x = (row >> 1) & 7
+      const int x = (row >> 1) & 7;
+      kv8_w0 = rw * 128 + 16 * ((2 * j) ^ x);
+      kv8_w1 = rw * 128 + 16 * ((2 * j + 1) ^ x);
+    } else {         // V: 32-byte block j at position j ^ ((row >> 1) & 3)
+      kv8_w0 = rw * 128 + 32 * (j ^ ((row >> 1) & 3));
+      kv8_w1 = kv8_w0 + 16;
+    }
+  }
+#else
   int offk, offkl, offv, offvl;
   {
     const int row = 8 * wave + (lane >> 3), pos = lane & 7;
@@ -67,6 +95,7 @@
     offv = row * vs2 + 16 * vc;
     offvl = rowl * vs2 + 16 * vc;
   }
+#endif
 
   // diagnostic build (STAMP): cycles per region summed over both passes, p.mask doubles as the record buffer
   unsigned long long st_all[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -132,6 +161,25 @@
   if (wave < 4) __builtin_amdgcn_s_setprio(1);
 #endif
   int tbase = 0, vnext = 0, vseen = 0;
+#ifdef FA_KV8
+  // widen this wave's fp8 KiB of every virtual tile requested since the last barrier (its DMA has landed: vmcnt(0))
+  auto kv8_expand = [&]() __attribute__((always_inline)) {
+    for (int v = vseen; v < vnext; ++v) {
+      char* img = smem + (v & (FA5_STAGES - 1)) * FA5_STAGE + kv8_reg;
+      const u32x4_t x = *(const u32x4_t*)(img + 16 * lane);
+      u32x4_t lo, hi;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        lo[2 * i] = kv8_cvt2<T, false>(x[i]);
+        lo[2 * i + 1] = kv8_cvt2<T, true>(x[i]);
+        hi[2 * i] = kv8_cvt2<T, false>(x[i + 2]);
+        hi[2 * i + 1] = kv8_cvt2<T, true>(x[i + 2]);
+      }
+      *(u32x4_t*)(img + kv8_w0) = lo;
+      *(u32x4_t*)(img + kv8_w1) = hi;
+    }
+  };
+#endif
   X8 qf_next[NQG][NDS];
   load_q(0, qf_next);
 
@@ -216,6 +264,12 @@
       const char* vb;
       FA_KV_TILE(tile, kb, vb);
       const bool lastt = (tile == last_tile);
+#ifdef FA_KV8
+      const uint32_t lds = (uint32_t)(size_t)((MIO_LDS char*)(smem + (tile_ & (FA5_STAGES - 1)) * FA5_STAGE)) + kv8_reg;
+      const int o8 = lastt ? off8l : off8;
+      const char* b8 = wave < 4 ? kb : vb;
+      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(lds), "v"(o8), "s"(b8) : "memory", "m0");
+#else
       const uint32_t lds = (uint32_t)(size_t)((MIO_LDS char*)(smem + (tile_ & (FA5_STAGES - 1)) * FA5_STAGE)) + 1024 * wave;
       const int ok_ = lastt ? offkl : offk, ov_ = lastt ? offvl : offv;
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(lds), "v"(ok_), "s"(kb) : "memory", "m0");
@@ -223,6 +277,7 @@
                    :
                    : "s"(lds), "n"(FA5_KBYTES), "v"(ov_), "s"(vb)
                    : "memory", "m0", "scc");
+#endif
     };
 
     X8 qf[NQG][NDS];
@@ -236,7 +291,13 @@
       ++vnext;
     }
     if (vseen < tbase + 2) {
+#ifdef FA_KV8
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      kv8_expand();
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#else
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+#endif
       vseen = vnext;
     }
 
@@ -436,7 +497,15 @@
         if (EVEN == 1 || !(t & 1)) {
           if constexpr (ABL & 4) asm volatile("s_barrier" ::: "memory");
           else if constexpr (ABL & 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef FA_KV8
+          else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            kv8_expand();
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+          }
+#else
           else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+#endif
           vseen = vnext;
           if constexpr (!(ABL & 8)) {
             stage_dma(vnext);
@@ -529,6 +598,9 @@
     for (int qg = 0; qg < NQG; ++qg) {
       const float l_tot = L[qg][0];
       inv2[qg] = (l_tot > 0.f) ? fast_rcp(l_tot) : 0.f;
+#ifdef FA_KV8
+      inv2[qg] *= kv8_vs;  // V = x8 * v_scale
+#endif
       if (q_ok[qg] && p.lse != nullptr && g == 0) {
         const float lse = (l_tot > 0.f) ? (ref[qg] * cs + fast_log2(l_tot)) * FA_LN2 : -INFINITY;
         p.lse[FA_LSE_INDEX(b, head, qrow[qg])] = lse;

@@ -194,3 +194,9 @@ template <typename T, int D>
 int fa3_win_launch(const FaDev& p, int causal, int left, int right, hipStream_t stream);
 template <typename T, int D, typename V>
 int fa3_win_seq_launch(const FaDev& p, const V& seq, int causal, int left, int right, hipStream_t stream);
+// Host launcher of the fp8 (e4m3fn) KV-cache forms (fa3_kv8_inst.hip) for one (dtype of q / o, padded D): p and pg as for
+// the paged launch, with the cache strides in 16-bit units of the one-byte rows; k_scale / v_scale: device pointers to the
+// layer's fp32 scales; left / right: the window, (-1, -1) = none.
+template <typename T, int D>
+int fa3_kv8_launch(const FaDev& p, const FaPaged& pg, const float* k_scale, const float* v_scale, int causal, int left,
+                   int right, hipStream_t stream);

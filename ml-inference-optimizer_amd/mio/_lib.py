@@ -122,6 +122,8 @@ EXPORTS = (
     "mio_reshape_and_cache_varlen_kv8",
     "mio_fa3_decode_paged_kv8",
     "mio_fa3_decode_kv8_route",
+    "mio_fa3_fwd_paged_kv8",
+    "mio_fa3_paged_kv8_route",
 )
 
 
@@ -330,6 +332,10 @@ def _load() -> C.CDLL:
         getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32, i32,
                                        i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp]
         getattr(lib, name).restype = i32
+    lib.mio_fa3_fwd_paged_kv8.argtypes = [C.POINTER(FaPagedParams), vp, vp, i32, i32, vp]
+    lib.mio_fa3_fwd_paged_kv8.restype = i32
+    lib.mio_fa3_paged_kv8_route.argtypes = [C.POINTER(FaPagedParams), vp, vp, i32, i32]
+    lib.mio_fa3_paged_kv8_route.restype = i32
     return lib
 
 

@@ -1022,16 +1022,33 @@ def _i32_dev(t: torch.Tensor, name: str, dim: int, what: str, device) -> None:
 
 def _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q, max_seqlen_k, layer_idx=0,
                   causal=False, softmax_scale=None, return_lse=False, out=None):
-    """flash_attention_varlen_paged's argument checks and mio_fa3_paged_params_t; returns (params, out, lse, keep) as
-    _varlen_params does.  Reads no device memory."""
+    """flash_attention_varlen_paged's argument checks and mio_fa3_paged_params_t for a 16-bit cache; returns (params,
+    out, lse, keep) as _varlen_params does.  Reads no device memory."""
+    p, out, lse, keep, _scales = _paged_args(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
+                                             max_seqlen_k, layer_idx, causal, softmax_scale, return_lse, out)
+    return p, out, lse, keep
+
+
+def _paged_args(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q, max_seqlen_k, layer_idx=0,
+                causal=False, softmax_scale=None, return_lse=False, out=None, k_scale=None, v_scale=None):
+    """_paged_params for either cache: also returns the scale addresses of an fp8 (float8_e4m3fn) cache (None for a
+    16-bit one), checked as paged decode checks them (_kv8_kind, _kv_scales)."""
     if q.dim() != 3:
         raise ValueError(f"Expected a 3D tensor [tokens, heads, head_dim] for q but got shape {q.shape}")
     if k_cache.dim() != 5 or v_cache.shape != k_cache.shape:
         raise ValueError("caches must be [num_blocks, num_layers, block_size, num_kv_heads, head_dim] with equal shapes")
-    if k_cache.dtype == _KV8 or v_cache.dtype == _KV8:
-        raise ValueError("flash_attention_varlen_paged does not read an fp8 (float8_e4m3fn) KV cache; paged decode "
-                         "(paged_attention_forward) does")
-    dt = _qkv_dtype(q, k_cache, v_cache, "q, k_cache, v_cache")
+    scales = None
+    if k_cache.element_size() == 1 or v_cache.element_size() == 1 or k_scale is not None or v_scale is not None:
+        _kv8_kind(k_cache, v_cache)
+        scales = _kv_scales(k_cache.dtype, k_scale, v_scale, k_cache.shape[1], layer_idx, k_cache.device,
+                            "flash_attention_varlen_paged")
+        if v_cache.dtype != k_cache.dtype:
+            raise ValueError("k_cache and v_cache must share a dtype")
+        dt = _dtype_id(q)
+        if q.shape[-1] % 16 != 0:
+            raise ValueError(f"an fp8 KV cache needs head_dim to be a multiple of 16, got head_dim {q.shape[-1]}")
+    else:
+        dt = _qkv_dtype(q, k_cache, v_cache, "q, k_cache, v_cache")
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("caches must be contiguous")
     _i32_dev(cu_seqlens_q, "cu_seqlens_q", 1, "of B+1 offsets", q.device)
@@ -1068,7 +1085,7 @@ def _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, ma
     p.num_blocks, p.num_layers, p.layer_idx, p.block_size = nb, L, int(layer_idx), bs
     p.max_blocks_per_seq = block_tables.shape[1]
     p.dtype, p.causal, p.softmax_scale = dt, int(bool(causal)), scale
-    return p, out, lse, (q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k)
+    return p, out, lse, (q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, k_scale, v_scale), scales
 
 
 def flash_attention_varlen_paged(
@@ -1087,6 +1104,8 @@ def flash_attention_varlen_paged(
     out: Optional[torch.Tensor] = None,
     *,
     window_size=(-1, -1),
+    k_scale: Optional[torch.Tensor] = None,
+    v_scale: Optional[torch.Tensor] = None,
 ):
     """Packed variable-length attention forward over the paged KV cache (chunked prefill), mio_fa3_fwd_paged.
 
@@ -1099,12 +1118,20 @@ def flash_attention_varlen_paged(
     sync (graph-capturable): the offsets and tables are never read on the host.
     window_size = (left, right): sliding window as in flash_attention_varlen; only the pages inside each query block's
     window are read.
+    FP8 cache: k_cache / v_cache torch.float8_e4m3fn (q / out bf16 or fp16, head_dim a multiple of 16) with k_scale /
+    v_scale, fp32 device tensors of 1 or num_layers elements (PagedKVCache.get_kv_scales()): attention over
+    K = k_cache * k_scale, V = v_cache * v_scale (mio_fa3_fwd_paged_kv8), everything else as above.  The scales are read
+    on the device, never on the host.
     """
     w = _window(window_size, causal)
     _need_cuda(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k)
-    p, out, lse, _keep = _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
-                                       max_seqlen_k, layer_idx=layer_idx, causal=causal, softmax_scale=softmax_scale,
-                                       return_lse=return_lse, out=out)
+    p, out, lse, _keep, scales = _paged_args(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
+                                             max_seqlen_k, layer_idx=layer_idx, causal=causal,
+                                             softmax_scale=softmax_scale, return_lse=return_lse, out=out,
+                                             k_scale=k_scale, v_scale=v_scale)
+    if scales is not None:
+        check(lib.mio_fa3_fwd_paged_kv8(C.byref(p), scales[0], scales[1], w[0], w[1], _stream()))
+        return (out, lse) if return_lse else out
     if w != (-1, -1):
         return _launch_window(lib.mio_fa3_fwd_paged_window, p, w, out, lse, return_lse)
     return _launch(lib.mio_fa3_fwd_paged, p, out, lse, return_lse)
@@ -1117,8 +1144,13 @@ def fa3_paged_route(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
     without launching.  Tensors may live on any device; arguments flash_attention_varlen_paged refuses raise the same
     errors."""
     w = _window(kwargs.pop("window_size", (-1, -1)), kwargs.get("causal", False))
-    p, _out, _lse, _keep = _paged_params(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
-                                         max_seqlen_k, **kwargs)
+    p, _out, _lse, _keep, scales = _paged_args(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
+                                               max_seqlen_k, **kwargs)
+    if scales is not None:
+        r = lib.mio_fa3_paged_kv8_route(C.byref(p), scales[0], scales[1], w[0], w[1])
+        if r < 0:
+            raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
+        return _lib.FA3_PAGED_ROUTES[r]
     if w != (-1, -1):
         return _route_window(lib.mio_fa3_paged_route_window, p, w, _lib.FA3_PAGED_ROUTES)
     return _route(lib.mio_fa3_paged_route, p, _lib.FA3_PAGED_ROUTES)
