@@ -1,15 +1,19 @@
-// Body of decode_gqa_kernel and decode_gqa_win_kernel (decode_gqa_kernel.h), included inside each: T, D, the DecDev
-// `p`, WIN and `wleft` come from the including kernel.
+// Body of decode_gqa_kernel, decode_gqa_win_kernel (decode_gqa_kernel.h) and their fp8-cache forms decode_gqa_kv8_kernel,
+// decode_gqa_kv8_win_kernel (decode_kv8.hip), included inside each: T, D, the DecDev `p`, WIN, `wleft`, KV8 and the scale
+// pointers `ksc`, `vsc` come from the including kernel.  KV8: the LDS image holds the cache's own bytes (one per element,
+// with the swizzle dg_kv8_sw), the K / V^T fragments are widened to 16 bits after their LDS reads, k_scale joins the score
+// scale and v_scale the split's own output.
   using X8 = typename DT<T>::x8;
   using X4 = typename DT<T>::x4;
+  constexpr int ESZ = KV8 ? 1 : 2;   // bytes per cached element
   constexpr int NDS = D / 32;        // 32-wide d steps of q . k
   constexpr int NDT = D / 16;        // 16-row d tiles of O^T
-  constexpr int ROWB = D * 2;        // bytes per cached head row
+  constexpr int ROWB = D * ESZ;      // bytes per cached head row
   constexpr int HALF = 32 * ROWB;    // bytes of a 32-key K (or V) image
   constexpr int STAGE = 2 * HALF;
-  constexpr int LPR = ROWB / 16;     // lanes (16-byte chunks) per row: 16 / 8
-  constexpr int RPI = 64 / LPR;      // rows per DMA instruction: 4 / 8
-  constexpr int NDMA = 32 / RPI;     // DMA instructions per image: 8 / 4
+  constexpr int LPR = ROWB / 16;     // lanes (16-byte chunks) per row: 16 / 8 (KV8: 8 / 4)
+  constexpr int RPI = 64 / LPR;      // rows per DMA instruction: 4 / 8 (KV8: 8 / 16)
+  constexpr int NDMA = 32 / RPI;     // DMA instructions per image: 8 / 4 (KV8: 4 / 2)
   constexpr int NL = 2 * NDMA;       // vector-memory instructions per chunk
   constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
@@ -56,13 +60,15 @@
       qf[ds] = __builtin_bit_cast(X8, raw);
     }
   }
+  // KV8: the scales are read here, in front of the wait below
+  const float ks = KV8 ? ksc[0] : 1.f, vs = KV8 ? vsc[0] : 1.f;
   __syncthreads();  // bt_s visible
   // the compiler's own vector loads end here: it must not wait for "its" loads inside the loop (its vmcnt(0) would drain the DMA)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
   for (int ds = 0; ds < NDS; ++ds) asm volatile("" : "+v"(qf[ds]));
 
-  const int64_t tok_bytes = (int64_t)p.Hkv * D * 2;
+  const int64_t tok_bytes = (int64_t)p.Hkv * D * ESZ;
   const char* kbase = (const char*)p.kc + (int64_t)kvh * ROWB;
   const char* vbase = (const char*)p.vc + (int64_t)kvh * ROWB;
   char* ring = smem + wave * (DG_NST * STAGE);
@@ -80,7 +86,9 @@
       const int blk = bt_s[pos / p.bs - blk0];
       const int64_t row = ((int64_t)blk * p.L + p.layer) * p.bs + pos % p.bs;
       int kc, vc;
-      if constexpr (D == 128) {
+      if constexpr (KV8) {
+        kc = vc = dpos ^ dg_kv8_sw<D>(key);
+      } else if constexpr (D == 128) {
         kc = dpos ^ (key & 15);
         vc = (((dpos >> 1) ^ (key & 7)) << 1) | (dpos & 1);
       } else {
@@ -95,14 +103,25 @@
     }
   };
 
-  // per-lane LDS read offsets
-  int k_rd[NDS], v_rd[NDT];
-  {
+  // per-lane LDS read offsets (KV8: one K table per 16-key tile, as the swizzle of a row depends on its bit 4)
+  int k_rd[KV8 ? 2 : 1][NDS], v_rd[NDT];
+  if constexpr (KV8) {
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt) {
+      const int r = 16 * kt + c16;
+#pragma unroll
+      for (int ds = 0; ds < NDS; ++ds) k_rd[kt][ds] = r * ROWB + 16 * ((2 * ds + (g >> 1)) ^ dg_kv8_sw<D>(r)) + 8 * (g & 1);
+    }
+    const int q8 = c16 >> 1, p8 = c16 & 1;
+    const int vkey = q8 < 4 ? 4 * g + q8 : 16 + 4 * g + q8 - 4;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) v_rd[dt] = HALF + vkey * ROWB + 16 * (dt ^ dg_kv8_sw<D>(vkey)) + 8 * p8;
+  } else {
     const int q4 = c16 >> 2, p2 = c16 & 3, vrow = 4 * g + q4;
 #pragma unroll
     for (int ds = 0; ds < NDS; ++ds) {
-      if constexpr (D == 128) k_rd[ds] = c16 * ROWB + 16 * ((4 * ds + g) ^ c16);
-      else k_rd[ds] = c16 * ROWB + 16 * ((4 * ds + g) ^ ((c16 >> 1) & 7));
+      if constexpr (D == 128) k_rd[0][ds] = c16 * ROWB + 16 * ((4 * ds + g) ^ c16);
+      else k_rd[0][ds] = c16 * ROWB + 16 * ((4 * ds + g) ^ ((c16 >> 1) & 7));
     }
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) {
@@ -113,7 +132,7 @@
 
   int qlo = 0;  // WIN: the first key query c16 sees
   if constexpr (WIN) qlo = ctx - p.q_len + c16 % p.q_len - wleft;
-  const float sl2 = p.scale * LOG2E;
+  const float sl2 = p.scale * ks * LOG2E;  // KV8: k_scale folded into the score scale
   float m = -INFINITY, l = 0.f;  // m: running maximum of the query's scaled scores (log2 units), the same on its 4 lanes
   f32x4_t o[NDT];
 #pragma unroll
@@ -133,7 +152,9 @@
       f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ds = 0; ds < NDS; ++ds) {
-        const X8 kf = __builtin_bit_cast(X8, *(const MIO_LDS u32x4_t*)(sb + kt * 16 * ROWB + k_rd[ds]));
+        X8 kf;
+        if constexpr (KV8) kf = kv8_to_x8<T>(*(const MIO_LDS u32x2_t*)(sb + k_rd[kt][ds]));
+        else kf = __builtin_bit_cast(X8, *(const MIO_LDS u32x4_t*)(sb + kt * 16 * ROWB + k_rd[0][ds]));
         acc = DT<T>::mfma16(kf, qf[ds], acc);
       }
       s2[kt] = acc;
@@ -174,9 +195,15 @@
     // ---- O^T = O^T * alpha + V^T . P^T
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) {
-      const X4 lo = DT<T>::ds_read_tr(sb + v_rd[dt]);
-      const X4 hi = DT<T>::ds_read_tr(sb + 16 * ROWB + v_rd[dt]);
-      const X8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      X8 vf;
+      if constexpr (KV8) {
+        typedef __attribute__((ext_vector_type(2))) int i32x2_t;
+        vf = kv8_to_x8<T>(__builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr8_b64_v2i32((MIO_LDS i32x2_t*)(sb + v_rd[dt]))));
+      } else {
+        const X4 lo = DT<T>::ds_read_tr(sb + v_rd[dt]);
+        const X4 hi = DT<T>::ds_read_tr(sb + 16 * ROWB + v_rd[dt]);
+        vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      }
       f32x4_t acc = o[dt];
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc[i] *= alpha;
@@ -219,7 +246,7 @@
           for (int i = 0; i < 8; ++i) acc[i] += src[i] * wgt;
         }
       }
-      const float inv = (Ls > 0.f) ? 1.f / Ls : 0.f;  // empty context -> 0 (attention_kernels.py:802)
+      const float inv = (Ls > 0.f) ? vs / Ls : 0.f;  // empty context -> 0 (attention_kernels.py:802)
       const int h = kvh * rep + qj / p.q_len, qi = qj % p.q_len;
       const int64_t row = ((int64_t)b * p.H + h) * p.q_len + qi;
       if (p.nsplit == 1) {

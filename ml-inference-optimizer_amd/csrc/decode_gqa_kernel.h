@@ -31,9 +31,26 @@ __device__ __forceinline__ int dec_win_begin(int ctx, int q_len, int wleft) {
 constexpr int DG_BT_MAX = 2048;  // block-table entries a split may span (8 KiB of LDS)
 constexpr int DG_NST = 2;        // (K, V) stages per wave
 
-template <int D>
+// ESZ: bytes per cached element (2, or 1 for the fp8 cache: 72 KiB at D 128)
+template <int D, int ESZ = 2>
 constexpr int dg_smem_bytes() {
-  return 4 * DG_NST * (2 * 32 * D * 2) + DG_BT_MAX * 4;
+  return 4 * DG_NST * (2 * 32 * D * ESZ) + DG_BT_MAX * 4;
+}
+
+// The fp8 cache's LDS image (KV8): 32 rows x D bytes per 32-key half, 16-byte chunk `ch` of row r stored at chunk
+// ch ^ dg_kv8_sw(r) (applied on the DMA's source address).  The swizzle makes both fragment reads conflict-free within each
+// 32-lane half: the K read takes one chunk of 16 consecutive rows (keys 0-15 or 16-31), the V^T read one chunk of the 16
+// rows 4g .. 4g+3, 16+4g .. 16+4g+3 for g in {0, 1} (or {2, 3}); with b the row's bits, sw = [b3^b4, b2, b1] (D 128, 8
+// chunks, rows 2 apart share a 256-byte bank row) and [b3^b4, b2] (D 64, 4 chunks, rows 4 apart share it).
+//   K fragment (A of S^T = K . Q^T): lane (c16, g) = K[key 16 kt + c16][32 ds + 8 g .. +7]: one ds_read_b64 + 4 conversions.
+//   V^T fragment (A of O^T += V^T . P^T): lane (c16, g) = V[key(k)][16 dt + c16] for k = 8 g .. 8 g + 7, key(8 g + j) =
+//   4 g + j (j < 4), 16 + 4 g + j - 4 (j >= 4): one ds_read_b64_tr_b8 (lane 2 q + p of a 16-lane group addresses row q's
+//   bytes 8 p .. 8 p + 7; lane i receives byte i of the 8 rows) + 4 conversions.
+template <int D>
+__device__ __forceinline__ int dg_kv8_sw(int r) {
+  const int x = ((r >> 3) ^ (r >> 4)) & 1;
+  if constexpr (D == 128) return (x << 2) | ((r >> 1) & 3);
+  else return (x << 1) | ((r >> 2) & 1);
 }
 
 // The body (decode_gqa_body.inc) is shared with the sliding-window form decode_gqa_win_kernel (WIN, `wleft` keys to the left):
@@ -41,13 +58,15 @@ constexpr int dg_smem_bytes() {
 // below ctx - q_len + j % q_len - wleft are masked like the split's tail.
 template <typename T, int D>
 __global__ __launch_bounds__(256) void decode_gqa_kernel(const DecDev p) {
-  constexpr bool WIN = false;
+  constexpr bool WIN = false, KV8 = false;
   [[maybe_unused]] constexpr int wleft = 0;
+  [[maybe_unused]] constexpr const float *ksc = nullptr, *vsc = nullptr;
 #include "decode_gqa_body.inc"
 }
 
 template <typename T, int D>
 __global__ __launch_bounds__(256) void decode_gqa_win_kernel(const DecDev p, int wleft) {
-  constexpr bool WIN = true;
+  constexpr bool WIN = true, KV8 = false;
+  [[maybe_unused]] constexpr const float *ksc = nullptr, *vsc = nullptr;
 #include "decode_gqa_body.inc"
 }

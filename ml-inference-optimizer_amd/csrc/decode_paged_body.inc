@@ -1,8 +1,13 @@
-// Body of decode_paged_kernel and decode_paged_win_kernel (decode_paged.hip), included inside each: T, CPRP, U, the
-// DecDev `p`, WIN and `wleft` come from the including kernel.
+// Body of decode_paged_kernel, decode_paged_win_kernel (decode_paged.hip) and their fp8-cache forms decode_paged_kv8_kernel,
+// decode_paged_kv8_win_kernel (decode_kv8.hip), included inside each: T, CPRP, U, the DecDev `p`, WIN, `wleft`, KV8 and the
+// scale pointers `ksc`, `vsc` come from the including kernel.  KV8: a cached element is one e4m3fn byte, so a lane's 16-byte
+// chunk holds 16 elements instead of 8; k_scale joins the score scale and v_scale the split's own output (only the fp8
+// kernels read ksc / vsc).
+  constexpr int EPC = KV8 ? 16 : 8;  // elements per 16-byte chunk
+  using KT = std::conditional_t<KV8, uint8_t, T>;  // a cached element
   constexpr int TPI = 64 / CPRP;  // tokens per wave-iteration
   constexpr int NSTATE = 4 * TPI;
-  __shared__ float s_o[NSTATE][CPRP * 8 + 1];
+  __shared__ float s_o[NSTATE][CPRP * EPC + 1];
   __shared__ float s_m[NSTATE], s_l[NSTATE];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -22,20 +27,28 @@
     const int lo = ctx - p.q_len + qi - wleft;  // this row's first visible key
     if (begin < lo) begin = lo;
   }
-  const bool c_ok = (8 * c < p.D);
+  const bool c_ok = (EPC * c < p.D);
 
-  float qf[8];
+  float qf[EPC];
   {
-    u32x4_t raw = {0, 0, 0, 0};
-    if (c_ok) raw = *(const u32x4_t*)((const T*)p.q + b * p.qs_b + h * p.qs_h + (int64_t)qi * p.qs_s + 8 * c);
-    const typename DT<T>::x8 v = __builtin_bit_cast(typename DT<T>::x8, raw);
+    const float qs = KV8 ? p.scale * ksc[0] : p.scale;
+    u32x4_t raw[EPC / 8] = {};
+    if (c_ok) {
+      const T* qp = (const T*)p.q + b * p.qs_b + h * p.qs_h + (int64_t)qi * p.qs_s + EPC * c;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) qf[i] = (float)v[i] * p.scale;
+      for (int hh = 0; hh < EPC / 8; ++hh) raw[hh] = *(const u32x4_t*)(qp + 8 * hh);
+    }
+#pragma unroll
+    for (int hh = 0; hh < EPC / 8; ++hh) {
+      const typename DT<T>::x8 v = __builtin_bit_cast(typename DT<T>::x8, raw[hh]);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) qf[8 * hh + i] = (float)v[i] * qs;
+    }
   }
 
-  float m = -INFINITY, l = 0.f, o[8];
+  float m = -INFINITY, l = 0.f, o[EPC];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = 0.f;
+  for (int i = 0; i < EPC; ++i) o[i] = 0.f;
 
   const int64_t tok_stride = (int64_t)p.Hkv * p.D;
   const int64_t blk_stride = (int64_t)p.L * p.bs * tok_stride;
@@ -49,7 +62,7 @@
   // Loads are unconditional (addresses clamped to the split's last token / the row's first chunk, values masked in
   // `reduce`): predicated loads become branches, and hipcc drains vmcnt at every join, which serialises the batches.
   const int last = end - 1;  // >= begin here: empty splits skip the loop
-  const int coff = c_ok ? 8 * c : 0;
+  const int coff = c_ok ? EPC * c : 0;
   const int64_t lay_off = (int64_t)p.layer * p.bs * tok_stride + (int64_t)kvh * p.D + coff;
   const int32_t* btrow = p.bt + (int64_t)b * p.max_blocks;
   auto load_pb = [&](int pos0, int (&pb)[U]) {
@@ -64,19 +77,17 @@
     for (int j = 0; j < U; ++j) {
       const int pos = min(pos0 + j * STEP + t, last);
       const int64_t off = (int64_t)pb[j] * blk_stride + lay_off + (int64_t)(pos % p.bs) * tok_stride;
-      kr[j] = *(const u32x4_t*)((const T*)p.kc + off);
-      vr[j] = *(const u32x4_t*)((const T*)p.vc + off);
+      kr[j] = *(const u32x4_t*)((const KT*)p.kc + off);
+      vr[j] = *(const u32x4_t*)((const KT*)p.vc + off);
     }
   };
-  auto reduce = [&](int pos0, const int (&pb)[U], const u32x4_t (&kr)[U], const u32x4_t (&vr)[U]) {
+  auto reduce = [&](int pos0, const u32x4_t (&kr)[U], const u32x4_t (&vr)[U]) {
     float sc[U];
     float m_new = m;
 #pragma unroll
     for (int j = 0; j < U; ++j) {
-      const typename DT<T>::x8 kv = __builtin_bit_cast(typename DT<T>::x8, kr[j]);
       float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s += qf[i] * (float)kv[i];  // qf = 0 in the padding chunks (c_ok false)
+      dec_chunk_each<T, KV8>(kr[j], [&](int i, float k) { s += qf[i] * k; });  // qf = 0 in the padding chunks (c_ok false)
 #pragma unroll
       for (int x = 1; x < CPRP; x <<= 1) s += __shfl_xor(s, x, 64);
       const int pos = pos0 + j * STEP + t;
@@ -87,14 +98,12 @@
     const float alpha = __expf(m - m_ref);
     l *= alpha;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] *= alpha;
+    for (int i = 0; i < EPC; ++i) o[i] *= alpha;
 #pragma unroll
     for (int j = 0; j < U; ++j) {
-      const typename DT<T>::x8 vv = __builtin_bit_cast(typename DT<T>::x8, vr[j]);
       const float pe = __expf(sc[j] - m_ref);
       l += pe;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] += pe * (float)vv[i];
+      dec_chunk_each<T, KV8>(vr[j], [&](int i, float v) { o[i] += pe * v; });
     }
     m = m_new;
   };
@@ -112,20 +121,20 @@
     int pos0 = begin + wave * TPI;
     if (begin >= end) pos0 = end;  // empty split: no loads at all
     else {
-    load_pb(pos0, pbA);
-    load_pb(pos0 + BATCH, pbB);
-    load_kv(pos0, pbA, kA, vA);
+      load_pb(pos0, pbA);
+      load_pb(pos0 + BATCH, pbB);
+      load_kv(pos0, pbA, kA, vA);
     }
     while (pos0 < end) {
       load_pb(pos0 + 2 * BATCH, pbC);
       load_kv(pos0 + BATCH, pbB, kB, vB);
-      reduce(pos0, pbA, kA, vA);
+      reduce(pos0, kA, vA);
       pos0 += BATCH;
       if (pos0 >= end) break;
       shift();
       load_pb(pos0 + 2 * BATCH, pbC);
       load_kv(pos0 + BATCH, pbB, kA, vA);
-      reduce(pos0, pbA, kB, vB);
+      reduce(pos0, kB, vB);
       pos0 += BATCH;
       shift();
     }
@@ -134,7 +143,7 @@
   // ---- merge the NSTATE per-(wave, token-slot) states
   const int g = wave * TPI + t;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) s_o[g][8 * c + i] = o[i];
+  for (int i = 0; i < EPC; ++i) s_o[g][EPC * c + i] = o[i];
   if (c == 0) {
     s_m[g] = m;
     s_l[g] = l;
@@ -151,7 +160,8 @@
         acc += s_o[j][tid] * w;
       }
     }
-    const float val = (Lsum > 0.f) ? acc / Lsum : 0.f;  // empty context -> 0 (attention_kernels.py:802)
+    // empty context -> 0 (attention_kernels.py:802); KV8: v_scale on the split's own output
+    const float val = (Lsum > 0.f) ? (KV8 ? acc / Lsum * vsc[0] : acc / Lsum) : 0.f;
     if (p.nsplit == 1) {
       ((T*)p.o)[b * p.os_b + h * p.os_h + (int64_t)qi * p.os_s + tid] = (T)val;
     } else {

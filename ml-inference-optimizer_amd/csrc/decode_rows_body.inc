@@ -1,7 +1,11 @@
-// Body of decode_rows_kernel and decode_rows_win_kernel (decode_paged.hip), included inside each: T, CPR, QN, the
-// DecDev `p`, WIN and `wleft` come from the including kernel.
+// Body of decode_rows_kernel, decode_rows_win_kernel (decode_paged.hip) and their fp8-cache forms decode_rows_kv8_kernel,
+// decode_rows_kv8_win_kernel (decode_kv8.hip), included inside each: T, CPR, QN, the DecDev `p`, WIN, `wleft`, KV8 and the
+// scale pointers `ksc`, `vsc` come from the including kernel.  KV8: 16 one-byte elements per 16-byte chunk, k_scale in the
+// score scale, v_scale on the split's own output.
+  constexpr int EPC = KV8 ? 16 : 8;  // elements per 16-byte chunk
+  using KT = std::conditional_t<KV8, uint8_t, T>;  // a cached element
   constexpr int U = 2;  // token slots per batch (U = 4 measured the same within 2 %)
-  __shared__ float s_st[4][64][QN][10];  // per (wave, lane, query): o[8], m, l
+  __shared__ float s_st[4][64][QN][EPC + 2];  // per (wave, lane, query): o[EPC], m, l
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x, split = blockIdx.y;
@@ -13,34 +17,39 @@
   const int tl = CPT >= 64 ? 0 : lane / CPT;            // token inside the wave-load
   const int cidx = CPT >= 64 ? part * 64 + lane : lane % CPT;  // 16-byte chunk of the token row
   const int kvh = cidx / CPR, c = cidx % CPR;
-  const int rep = p.H / p.Hkv;
+  // the fp8 kernel has QN = 1 with the query indexing folded: H == Hkv and q_len == 1 (dec_rows_ok)
+  const int rep = KV8 ? 1 : p.H / p.Hkv, q_len = KV8 ? 1 : p.q_len;
   const int ctx = p.cl[b];
   int begin = split * p.split_len;
   if constexpr (WIN) begin += dec_win_begin(ctx, p.q_len, wleft);
   int end = begin + p.split_len;
   if (end > ctx) end = ctx;
 
-  float qf[QN][8];
+  float qf[QN][EPC];
 #pragma unroll
   for (int j = 0; j < QN; ++j) {
-    const int h = kvh * rep + j / p.q_len, qi = j % p.q_len;
-    const u32x4_t raw = *(const u32x4_t*)((const T*)p.q + b * p.qs_b + h * p.qs_h + (int64_t)qi * p.qs_s + 8 * c);
-    const typename DT<T>::x8 v = __builtin_bit_cast(typename DT<T>::x8, raw);
+    const float qs = KV8 ? p.scale * ksc[0] : p.scale;
+    const int h = kvh * rep + j / q_len, qi = j % q_len;
+    const T* qp = (const T*)p.q + b * p.qs_b + h * p.qs_h + (int64_t)qi * p.qs_s + EPC * c;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) qf[j][i] = (float)v[i] * p.scale;
+    for (int hh = 0; hh < EPC / 8; ++hh) {
+      const typename DT<T>::x8 v = __builtin_bit_cast(typename DT<T>::x8, *(const u32x4_t*)(qp + 8 * hh));
+#pragma unroll
+      for (int i = 0; i < 8; ++i) qf[j][8 * hh + i] = (float)v[i] * qs;
+    }
   }
-  float m[QN], l[QN], o[QN][8];
+  float m[QN], l[QN], o[QN][EPC];
 #pragma unroll
   for (int j = 0; j < QN; ++j) {
     m[j] = -INFINITY;
     l[j] = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o[j][i] = 0.f;
+    for (int i = 0; i < EPC; ++i) o[j][i] = 0.f;
   }
 
   const int64_t tok_stride = (int64_t)p.Hkv * p.D;
   const int64_t blk_stride = (int64_t)p.L * p.bs * tok_stride;
-  const int64_t lay_off = (int64_t)p.layer * p.bs * tok_stride + (int64_t)cidx * 8;
+  const int64_t lay_off = (int64_t)p.layer * p.bs * tok_stride + (int64_t)cidx * EPC;
   const int32_t* btrow = p.bt + (int64_t)b * p.max_blocks;
   const int step = wpp * tpl;  // tokens the workgroup covers per slot
   const int last = end - 1;
@@ -57,8 +66,8 @@
     for (int j = 0; j < U; ++j) {
       const int pos = min(tok(pos0, j), last);
       const int64_t off = (int64_t)pb[j] * blk_stride + lay_off + (int64_t)(pos % p.bs) * tok_stride;
-      kr[j] = *(const u32x4_t*)((const T*)p.kc + off);
-      vr[j] = *(const u32x4_t*)((const T*)p.vc + off);
+      kr[j] = *(const u32x4_t*)((const KT*)p.kc + off);
+      vr[j] = *(const u32x4_t*)((const KT*)p.vc + off);
     }
   };
   auto reduce = [&](int pos0, const u32x4_t (&kr)[U], const u32x4_t (&vr)[U]) {
@@ -68,16 +77,14 @@
       float m_new = m[q];
 #pragma unroll
       for (int j = 0; j < U; ++j) {
-        const typename DT<T>::x8 kv = __builtin_bit_cast(typename DT<T>::x8, kr[j]);
         float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += qf[q][i] * (float)kv[i];
+        dec_chunk_each<T, KV8>(kr[j], [&](int i, float k) { s += qf[q][i] * k; });
 #pragma unroll
         for (int x = 1; x < CPR; x <<= 1) s += __shfl_xor(s, x, 64);
         const int pos = tok(pos0, j);
         sc[j] = (pos < end && pos / p.bs < p.max_blocks) ? s : -INFINITY;
         if constexpr (WIN) {
-          if (pos < ctx - p.q_len + q % p.q_len - wleft) sc[j] = -INFINITY;
+          if (pos < ctx - q_len + q % q_len - wleft) sc[j] = -INFINITY;
         }
         m_new = fmaxf(m_new, sc[j]);
       }
@@ -85,14 +92,12 @@
       const float alpha = __expf(m[q] - m_ref);
       l[q] *= alpha;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[q][i] *= alpha;
+      for (int i = 0; i < EPC; ++i) o[q][i] *= alpha;
 #pragma unroll
       for (int j = 0; j < U; ++j) {
-        const typename DT<T>::x8 vv = __builtin_bit_cast(typename DT<T>::x8, vr[j]);
         const float pe = __expf(sc[j] - m_ref);
         l[q] += pe;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[q][i] += pe * (float)vv[i];
+        dec_chunk_each<T, KV8>(vr[j], [&](int i, float v) { o[q][i] += pe * v; });
       }
       m[q] = m_new;
     }
@@ -133,9 +138,9 @@
 #pragma unroll
   for (int q = 0; q < QN; ++q) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) s_st[wave][lane][q][i] = o[q][i];
-    s_st[wave][lane][q][8] = m[q];
-    s_st[wave][lane][q][9] = l[q];
+    for (int i = 0; i < EPC; ++i) s_st[wave][lane][q][i] = o[q][i];
+    s_st[wave][lane][q][EPC] = m[q];
+    s_st[wave][lane][q][EPC + 1] = l[q];
   }
   __syncthreads();
   if (tslot == 0 && tl == 0) {  // one lane per chunk of the row: its own state first, then the others'
@@ -143,31 +148,32 @@
     for (int q = 0; q < QN; ++q) {
       float M = -INFINITY;
       for (int w = part; w < 4; w += npart)
-        for (int t2 = 0; t2 < tpl; ++t2) M = fmaxf(M, s_st[w][(CPT >= 64 ? lane : t2 * CPT + cidx)][q][8]);
-      float Ls = 0.f, acc[8];
+        for (int t2 = 0; t2 < tpl; ++t2) M = fmaxf(M, s_st[w][(CPT >= 64 ? lane : t2 * CPT + cidx)][q][EPC]);
+      float Ls = 0.f, acc[EPC];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+      for (int i = 0; i < EPC; ++i) acc[i] = 0.f;
       if (M != -INFINITY) {
         for (int w = part; w < 4; w += npart)
           for (int t2 = 0; t2 < tpl; ++t2) {
             const float* st = s_st[w][(CPT >= 64 ? lane : t2 * CPT + cidx)][q];
-            const float wgt = __expf(st[8] - M);
-            Ls += st[9] * wgt;
+            const float wgt = __expf(st[EPC] - M);
+            Ls += st[EPC + 1] * wgt;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) acc[i] += st[i] * wgt;
+            for (int i = 0; i < EPC; ++i) acc[i] += st[i] * wgt;
           }
       }
-      const float inv = (Ls > 0.f) ? 1.f / Ls : 0.f;  // empty context -> 0 (attention_kernels.py:802)
-      const int h = kvh * rep + q / p.q_len, qi = q % p.q_len;
-      const int64_t row = ((int64_t)b * p.H + h) * p.q_len + qi;
+      // empty context -> 0 (attention_kernels.py:802); KV8: v_scale on the split's own output
+      const float inv = (Ls > 0.f) ? (KV8 ? vsc[0] : 1.f) / Ls : 0.f;
+      const int h = kvh * rep + q / q_len, qi = q % q_len;
+      const int64_t row = ((int64_t)b * p.H + h) * q_len + qi;
       if (p.nsplit == 1) {
-        T* op = (T*)p.o + b * p.os_b + h * p.os_h + (int64_t)qi * p.os_s + 8 * c;
+        T* op = (T*)p.o + b * p.os_b + h * p.os_h + (int64_t)qi * p.os_s + EPC * c;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) op[i] = (T)(acc[i] * inv);
+        for (int i = 0; i < EPC; ++i) op[i] = (T)(acc[i] * inv);
       } else {
-        float* wo = p.ws_o + (row * p.nsplit + split) * p.D + 8 * c;
+        float* wo = p.ws_o + (row * p.nsplit + split) * p.D + EPC * c;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) wo[i] = acc[i] * inv;
+        for (int i = 0; i < EPC; ++i) wo[i] = acc[i] * inv;
         if (c == 0) p.ws_lse[row * p.nsplit + split] = (Ls > 0.f) ? M + __logf(Ls) : -INFINITY;
       }
     }

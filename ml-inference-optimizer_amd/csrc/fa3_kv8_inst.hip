@@ -5,26 +5,18 @@
 //
 // K = x8 * k_scale, V = x8 * v_scale with the fp32 scales of the layer read here from device memory (no host sync: a scale
 // may change between replays of a captured graph).  The bytes are widened exactly to 16 bits in LDS (fa3_fwd5_body.inc,
-// fa3_fwd3_body.inc: FA_KV8) and the MFMAs see x8 itself; k_scale joins softmax_scale * log2(e) in the fp32 score scale,
-// v_scale the epilogue's 1 / l.  The per-lane strides of the bodies count 16-bit units (ks2 = 2 * ks_s bytes), so the
+// fa3_fwd3_body.inc: FA_KV8, with kv8_cvt2 of kv8_cvt.h) and the MFMAs see x8 itself; k_scale joins softmax_scale *
+// log2(e) in the fp32 score scale, v_scale the epilogue's 1 / l.  The per-lane strides of the bodies count 16-bit units (ks2 = 2 * ks_s bytes), so the
 // launcher gives the one-byte cache's strides halved.  No extra LDS: a wave's fp8 rows land inside the 16-bit image of
 // the same rows, which that wave alone widens, so the stage sizes are those of the 16-bit kernels.
-#include <type_traits>
-
 #include "fa3_paged.h"
+#include "kv8_cvt.h"
 
 #if FA_TYPE_ID == 0
 using FaT = __bf16;
 #else
 using FaT = _Float16;
 #endif
-
-// two e4m3fn bytes (the low / high half of w) -> two packed T (exact, scale 1)
-template <typename T, bool HI>
-__device__ __forceinline__ uint32_t kv8_cvt2(uint32_t w) {
-  if constexpr (std::is_same_v<T, __bf16>) return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
-  else return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, HI));
-}
 
 struct FaKv8Args {
   FaDev p;
