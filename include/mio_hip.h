@@ -401,6 +401,9 @@ int32_t mio_fa3_paged_route_window(const mio_fa3_paged_params_t* p, int32_t wind
  * q/o [B,H,q_len,D] (strides b,h,s; d contiguous); caches [num_blocks, L, block_size, Hkv, D]
  * contiguous; block_tables [B,max_blocks] int32; context_lengths [B] int32.  No causal mask
  * (the reference's is commented out, :774-776).  workspace: mio_fa3_decode_workspace_bytes().
+ * Keys at positions >= max_blocks * block_size (a context longer than its block-table row) are
+ * ignored.  No cache slot at or past context_lengths[b], and no table entry past the last needed
+ * block, influences the result: such slots and entries may hold anything (NaN bit patterns too).
  * ------------------------------------------------------------------------------------------ */
 size_t mio_fa3_decode_workspace_bytes(int32_t B, int32_t H, int32_t q_len, int32_t D, int32_t max_ctx);
 int mio_fa3_decode_paged(const void* q, void* o, const void* k_cache, const void* v_cache,

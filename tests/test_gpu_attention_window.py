@@ -8,6 +8,8 @@ windowed kernel on the unwindowed splits and must be bitwise equal to the unwind
 import pytest
 import torch
 
+import _decode_check as dc
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -19,30 +21,13 @@ def _ops():
     return ops
 
 
-def _ref(q, kc, vc, bt, ctx, bs, layer, left, scale):
-    """fp64 windowed decode on the CPU: q [B, H, q_len, D], caches [nb, L, bs, Hkv, D]."""
-    B, H, q_len, D = q.shape
-    Hkv = kc.shape[3]
-    out = torch.zeros(B, H, q_len, D, dtype=torch.float64)
-    for b in range(B):
-        n = int(ctx[b])
-        if n == 0:
-            continue
-        pos = torch.arange(n)
-        pages = bt[b, pos // bs].long()
-        k = kc[pages, layer, pos % bs].double()  # [n, Hkv, D]
-        v = vc[pages, layer, pos % bs].double()
-        k = k.repeat_interleave(H // Hkv, dim=1).permute(1, 0, 2)  # [H, n, D]
-        v = v.repeat_interleave(H // Hkv, dim=1).permute(1, 0, 2)
-        s = torch.einsum("hqd,hkd->hqk", q[b].double(), k) * scale
-        qi = torch.arange(q_len).view(q_len, 1)
-        lo = n - q_len + qi - left if left >= 0 else torch.full_like(qi, -(1 << 40))
-        vis = pos.view(1, n) >= lo
-        s = s.masked_fill(~vis.view(1, q_len, n), float("-inf"))
-        any_vis = vis.any(-1).view(1, q_len, 1)
-        p = torch.softmax(torch.where(any_vis, s, torch.zeros_like(s)), dim=-1) * any_vis
-        out[b] = torch.einsum("hqk,hkd->hqd", p, v)
-    return out
+def _judge(out, q, kc, vc, bt, ctx, bs, layer, left, dtype, route, what):
+    """The decode result against _decode_check's fp64 windowed reference: the whole-tensor bars of the unwindowed decode
+    tests, then the per-row check against the fp32 model."""
+    ref, lse = dc.reference(q, kc, vc, bt, ctx, bs, layer, left=left)
+    _cmp(out, ref, dtype, what)
+    model_o = dc.model(q, kc, vc, bt, ctx, bs, layer, dtype=dtype, p16=route == "gqa", left=left)
+    dc.check(out, ref, lse, dtype, (dtype, route, "kv16"), model_o, what, win=left >= 0)
 
 
 def _cmp(got, ref, dtype, what):
@@ -86,14 +71,12 @@ def test_decode_window_matches_reference(kernel, q_len, bs):
     ctx = torch.tensor(ctxs, dtype=torch.int32)
     args = (kc.to(DEV), vc.to(DEV), bt.to(DEV), ctx.to(DEV), bs, max_ctx, layer)
     qd = q.to(DEV)
-    scale = D ** -0.5
     for left in _LEFTS:
         out = torch.full((B, H, q_len, D), float("nan"), dtype=dtype, device=DEV)
         ws = (left, -1)
         assert ops.paged_attention_route(qd, out, *args, window_size=ws) == kernel, (kernel, left, q_len)
         ops.paged_attention_forward(qd, out, *args, window_size=ws)
-        ref = _ref(q, kc, vc, bt, ctx, bs, layer, left, scale)
-        _cmp(out, ref, dtype, f"{kernel} q_len={q_len} bs={bs} left={left}")
+        _judge(out, q, kc, vc, bt, ctx, bs, layer, left, dtype, kernel, f"{kernel} q_len={q_len} bs={bs} left={left}")
         assert out[2].abs().max() == 0  # empty context -> zeros
         if left >= max_ctx + q_len:  # the window covers every context: the unwindowed launch, bit for bit
             plain = torch.full_like(out, float("nan"))
@@ -136,7 +119,7 @@ def test_decode_window_long_context(kernel):
     args = (kc.to(DEV), vc.to(DEV), bt.to(DEV), ctx.to(DEV), bs, 12000, 0)
     assert ops.paged_attention_route(q.to(DEV), out, *args, window_size=(left, -1)) == kernel
     ops.paged_attention_forward(q.to(DEV), out, *args, window_size=(left, -1))
-    _cmp(out, _ref(q, kc, vc, bt, ctx, bs, 0, left, D ** -0.5), dtype, f"{kernel} long window")
+    _judge(out, q, kc, vc, bt, ctx, bs, 0, left, dtype, kernel, f"{kernel} long window")
 
 
 def test_decode_window_graph_capture():
@@ -182,5 +165,5 @@ def test_decode_window_graph_capture():
     step()
     torch.cuda.synchronize()
     assert torch.equal(o_graph, out)
-    ref = _ref(q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(), cl.cpu(), bs, 0, 100, D ** -0.5)
-    _cmp(out, ref, dtype, "graph")
+    assert ops.paged_attention_route(q, out, kc, vc, bt, cl, bs, 701, 0, window_size=(100, -1)) == "gqa"
+    _judge(out, q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(), cl.cpu(), bs, 0, 100, dtype, "gqa", "graph")

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import oracle
+import _decode_check as dc
 
 pytestmark = pytest.mark.gpu
 
@@ -593,6 +594,14 @@ def test_layernorm(golden_dir, dtype):
         _cmp(ops.layernorm(xx.to(DEV), ww.to(DEV)), oracle.layernorm(xx, ww), dtype, f"ln{cols}")
 
 
+def _decode_rows(out, q, kc, vc, bt, ctx, bs, layer, dtype, route, what):
+    """The per-row check of tests/_decode_check.py next to _cmp's whole-tensor one (which lets a defect in one long
+    sequence of a mixed batch pass): bars from the fp32 model of the same inputs."""
+    ref, lse = dc.reference(q, kc, vc, bt, ctx, bs, layer)
+    model_o = dc.model(q, kc, vc, bt, ctx, bs, layer, dtype=dtype, p16=route == "gqa")
+    dc.check(out, ref, lse, dtype, (dtype, route, "kv16"), model_o, what)
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("D,H,Hkv,q_len", [
     (64, 4, 4, 1), (128, 8, 2, 1), (80, 2, 2, 3),
@@ -610,6 +619,9 @@ def test_paged_decode_and_cache(dtype, D, H, Hkv, q_len):
     ops = _ops()
     torch.manual_seed(D + H)
     B, bs, L, maxb = (3 if H < 8 else 18), 16, 2, 20   # B >= 16 takes the whole-token-row kernel where the geometry fits
+    # the kernel each geometry takes: per head at B 3 with one query vector per key at D 64, and at D 80; whole token rows
+    # at B 18 with one vector per key at D 64; the matrix core with 2 .. 16 vectors per key, or one at D 128
+    route = {(64, 4, 4, 1): "head", (80, 2, 2, 3): "head", (64, 16, 16, 1): "rows"}.get((D, H, Hkv, q_len), "gqa")
     nblk = B * maxb + 4
     ctx = torch.tensor(([300, 17, 0] * 6)[:B], dtype=torch.int32)
     kc = torch.randn(nblk, L, bs, Hkv, D).to(dtype)
@@ -618,14 +630,17 @@ def test_paged_decode_and_cache(dtype, D, H, Hkv, q_len):
     q = torch.randn(B, H, q_len, D).to(dtype)
     out = torch.empty(B, H, q_len, D, dtype=dtype, device=DEV)
     kcd, vcd = kc.to(DEV), vc.to(DEV)
+    assert ops.paged_attention_route(q.to(DEV), out, kcd, vcd, bt.to(DEV), ctx.to(DEV), bs, 320, 1) == route
     ops.paged_attention_forward(q.to(DEV), out, kcd, vcd, bt.to(DEV), ctx.to(DEV), bs, 320, 1)
     ref = oracle.paged_attention_forward(q, kc, vc, bt, ctx, bs, 1)
     _cmp(out, ref, dtype, "paged")
+    _decode_rows(out, q, kc, vc, bt, ctx, bs, 1, dtype, route, "paged")
     assert out[2].abs().max() == 0  # empty context -> zeros (attention_kernels.py:802)
     if B > 3:
         ctx[3:] = torch.tensor([319, 256, 1, 64, 129, 255, 318, 16, 15, 33, 100, 200, 7, 303, 48][:B - 3], dtype=torch.int32)
         ops.paged_attention_forward(q.to(DEV), out, kcd, vcd, bt.to(DEV), ctx.to(DEV), bs, 320, 1)
         _cmp(out, oracle.paged_attention_forward(q, kc, vc, bt, ctx, bs, 1), dtype, "paged ragged")
+        _decode_rows(out, q, kc, vc, bt, ctx, bs, 1, dtype, route, "paged ragged")
     # cache write for the next token, then decode again: must equal the oracle on the updated cache
     knew, vnew = torch.randn(B, 1, Hkv, D).to(dtype), torch.randn(B, 1, Hkv, D).to(dtype)
     ctx2 = ctx + 1
@@ -634,6 +649,7 @@ def test_paged_decode_and_cache(dtype, D, H, Hkv, q_len):
     assert torch.equal(kcd.cpu(), kc) and torch.equal(vcd.cpu(), vc)  # byte-exact scatter
     ops.paged_attention_forward(q.to(DEV), out, kcd, vcd, bt.to(DEV), ctx2.to(DEV), bs, 320, 1)
     _cmp(out, oracle.paged_attention_forward(q, kc, vc, bt, ctx2, bs, 1), dtype, "paged+1")
+    _decode_rows(out, q, kc, vc, bt, ctx2, bs, 1, dtype, route, "paged+1")
 
 
 def test_paged_decode_pipelined_batches():
@@ -643,7 +659,7 @@ def test_paged_decode_pipelined_batches():
     unroll = "2"
     torch.manual_seed(7)
     dtype = torch.bfloat16
-    for D, H, Hkv in ((64, 4, 4), (128, 4, 2)):
+    for D, H, Hkv, route in ((64, 4, 4, "head"), (128, 4, 2, "gqa")):   # B 6: per head; two query heads per key: matrix core
         B, bs, L, maxb = 6, 16, 1, 80
         nblk = B * maxb
         ctx = torch.tensor([1280, 1023, 513, 257, 1, 0], dtype=torch.int32)
@@ -652,8 +668,10 @@ def test_paged_decode_pipelined_batches():
         bt = torch.randperm(nblk).view(B, maxb).to(torch.int32)
         q = torch.randn(B, H, 1, D).to(dtype)
         out = torch.empty(B, H, 1, D, dtype=dtype, device=DEV)
+        assert ops.paged_attention_route(q.to(DEV), out, kc.to(DEV), vc.to(DEV), bt.to(DEV), ctx.to(DEV), bs, 1280, 0) == route
         ops.paged_attention_forward(q.to(DEV), out, kc.to(DEV), vc.to(DEV), bt.to(DEV), ctx.to(DEV), bs, 1280, 0)
         _cmp(out, oracle.paged_attention_forward(q, kc, vc, bt, ctx, bs, 0), dtype, f"paged U={unroll} D={D}")
+        _decode_rows(out, q, kc, vc, bt, ctx, bs, 0, dtype, route, f"paged U={unroll} D={D}")
         assert out[5].abs().max() == 0
 
 
@@ -675,8 +693,10 @@ def test_paged_decode_gqa_long_contexts(dtype, D, H, Hkv, q_len, bs):
     bt = torch.randperm(nblk).view(B, maxb).to(torch.int32)
     q = (torch.randn(B, H, q_len, D) * 1.5).to(dtype)
     out = torch.full((B, H, q_len, D), float("nan"), dtype=dtype, device=DEV)
+    assert ops.paged_attention_route(q.to(DEV), out, kc.to(DEV), vc.to(DEV), bt.to(DEV), ctx.to(DEV), bs, 5000, 1) == "gqa"
     ops.paged_attention_forward(q.to(DEV), out, kc.to(DEV), vc.to(DEV), bt.to(DEV), ctx.to(DEV), bs, 5000, 1)
     _cmp(out, oracle.paged_attention_forward(q, kc, vc, bt, ctx, bs, 1), dtype, f"gqa decode D={D} H={H}/{Hkv} q_len={q_len} bs={bs}")
+    _decode_rows(out, q, kc, vc, bt, ctx, bs, 1, dtype, "gqa", f"gqa decode D={D} H={H}/{Hkv} q_len={q_len} bs={bs}")
     assert out[-1].abs().max() == 0
     # a strided (non-contiguous in H) output tensor still lands in the right rows
     big = torch.zeros(B, H, q_len, 2 * D, dtype=dtype, device=DEV)

@@ -9,6 +9,8 @@ entry points every test fails at the symbol check, before an fp8 cache reaches a
 import pytest
 import torch
 
+import _decode_check as dc
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -124,30 +126,14 @@ def test_kv8_write_one_token_byte_exact(dtype, per_layer):
 
 
 # ---- decode -----------------------------------------------------------------------------------------------------------------
-def _ref(q, kc, vc, ks, vs, bt, ctx, bs, layer, left, scale):
-    """fp64 decode over the dequantised cache (windowed when left >= 0)."""
-    B, H, q_len, D = q.shape
-    Hkv = kc.shape[3]
-    out = torch.zeros(B, H, q_len, D, dtype=torch.float64)
-    for b in range(B):
-        n = int(ctx[b])
-        if n == 0:
-            continue
-        pos = torch.arange(n)
-        pages = bt[b, pos // bs].long()
-        k = kc[pages, layer, pos % bs].double() * ks
-        v = vc[pages, layer, pos % bs].double() * vs
-        k = k.repeat_interleave(H // Hkv, dim=1).permute(1, 0, 2)
-        v = v.repeat_interleave(H // Hkv, dim=1).permute(1, 0, 2)
-        s = torch.einsum("hqd,hkd->hqk", q[b].double(), k) * scale
-        qi = torch.arange(q_len).view(q_len, 1)
-        lo = n - q_len + qi - left if left >= 0 else torch.full_like(qi, -(1 << 40))
-        vis = pos.view(1, n) >= lo
-        s = s.masked_fill(~vis.view(1, q_len, n), float("-inf"))
-        any_vis = vis.any(-1).view(1, q_len, 1)
-        p = torch.softmax(torch.where(any_vis, s, torch.zeros_like(s)), dim=-1) * any_vis
-        out[b] = torch.einsum("hqk,hkd->hqd", p, v)
-    return out
+def _judge(out, q, kc, vc, ks, vs, bt, ctx, bs, layer, left, dtype, route, what):
+    """The decode result against _decode_check's fp64 reference over the dequantised cache (windowed when left >= 0):
+    the whole-tensor bars of the 16-bit decode tests, then the per-row check against the fp32 model."""
+    kw = dict(left=left, k_scale=ks, v_scale=vs)
+    ref, lse = dc.reference(q, kc, vc, bt, ctx, bs, layer, **kw)
+    _cmp(out, ref, dtype, what)
+    model_o = dc.model(q, kc, vc, bt, ctx, bs, layer, dtype=dtype, p16=route == "gqa", **kw)
+    dc.check(out, ref, lse, dtype, (dtype, route, "fp8"), model_o, what, win=left >= 0)
 
 
 def _cmp(got, ref, dtype, what, tol=None):
@@ -202,8 +188,8 @@ def test_kv8_decode_matches_reference(route, D, q_len, bs, left):
     kw = dict(window_size=(left, -1), k_scale=ks.to(DEV), v_scale=vs.to(DEV))
     assert ops.paged_attention_route(*args, **kw) == want
     ops.paged_attention_forward(*args, **kw)
-    ref = _ref(q, kc.float(), vc.float(), float(ks[layer]), float(vs[layer]), bt, ctx, bs, layer, left, D ** -0.5)
-    _cmp(out, ref, dtype, f"{want} D{D} q_len{q_len} bs{bs} left{left}")
+    _judge(out, q, kc, vc, float(ks[layer]), float(vs[layer]), bt, ctx, bs, layer, left, dtype, want,
+           f"{want} D{D} q_len{q_len} bs{bs} left{left}")
 
 
 @pytest.mark.parametrize("route", ["head", "rows", "gqa"])
@@ -223,8 +209,7 @@ def test_kv8_decode_shared_scale_and_splits(route):
     kw = dict(k_scale=ks.to(DEV), v_scale=vs.to(DEV))
     assert ops.paged_attention_route(*args, **kw) == route
     ops.paged_attention_forward(*args, **kw)
-    ref = _ref(q, kc.float(), vc.float(), 0.33, 2.0, bt, ctx, bs, layer, -1, D ** -0.5)
-    _cmp(out, ref, torch.bfloat16, route)
+    _judge(out, q, kc, vc, float(ks[0]), float(vs[0]), bt, ctx, bs, layer, -1, torch.bfloat16, route, route)
 
 
 @pytest.mark.parametrize("route", ["head", "rows", "gqa"])
