@@ -1,19 +1,10 @@
-// One translation unit per (dtype, padded head dim): compiled with -DFA_TYPE_ID={0,1} -DFA_D={64,96,128}.
+// The dense attention forward (mio_fa3_fwd): one translation unit per (dtype, padded head dim), see fa3_inst.h.
 // The product library reads no environment variable and keeps no unsynchronised mutable state; the A/B switches and the
 // in-kernel stamp instantiations exist only in the diagnostic build (make dbg: -DMIO_DIAG -> libmio_hip_dbg.so).
 #include <cstdlib>
 
-#include "fa3_fwd3_kernel.h"
+#include "fa3_inst.h"
 #include "fa3_route.h"
-#if FA_D == 64
-#include "fa3_fwd5_kernel.h"
-#endif
-
-#if FA_TYPE_ID == 0
-using FaT = __bf16;
-#else
-using FaT = _Float16;
-#endif
 
 template <bool CAUSAL, int MASK>
 static int launch_one(const FaDev& p, hipStream_t stream) {
@@ -24,9 +15,7 @@ static int launch_one(const FaDev& p, hipStream_t stream) {
 // third structure (software-pipelined across KV tiles): no user mask
 template <bool CAUSAL, bool KPRE = false>
 static int launch_three(FaDev p, hipStream_t stream) {
-  p.nqblk = (p.Sq + FA3_BM - 1) / FA3_BM;
-  p.qgrid = CAUSAL ? (p.nqblk + 1) / 2 : p.nqblk;
-  const int grid = p.qgrid * p.B * p.H;
+  const int grid = (int)fa_grid<CAUSAL>(p, p.Sq, FA3_BM);
   const size_t smem = FA3_STAGES * FaSmem<FA_D>::STAGE;
 #ifdef MIO_DIAG
 #if FA_D == 64 && FA_TYPE_ID == 0
@@ -61,9 +50,7 @@ static int launch_three(FaDev p, hipStream_t stream) {
 #if FA_D == 64
 template <bool CAUSAL, bool CARRY = false, bool OBLK = false, bool KPRE = true>
 static int launch_five(FaDev p, hipStream_t stream) {
-  p.nqblk = (p.Sq + FA5_BM - 1) / FA5_BM;
-  p.qgrid = CAUSAL ? (p.nqblk + 1) / 2 : p.nqblk;
-  const int grid = p.qgrid * p.B * p.H;
+  const int grid = (int)fa_grid<CAUSAL>(p, p.Sq, FA5_BM);
 #if defined(MIO_DIAG) && FA_TYPE_ID == 0
   if constexpr (!CARRY && !OBLK && KPRE) {
   p.xcd_remap |= (mio_dbg_get(3) & 7) << 4;  // wave-priority probe (tools/fa5_ablate.py)

@@ -1,33 +1,26 @@
 // The paged attention forward over an fp8 (OCP e4m3fn) KV cache (mio_fa3_fwd_paged_kv8): the paged kernels of
 // fa3_seq_inst.hip and their windowed forms of fa3_win_inst.hip with FA_KV8 defined.  One translation unit per (dtype,
-// padded head dim), compiled with -DFA_TYPE_ID={0,1} -DFA_D={64,96,128} like fa3_fwd_inst.hip.  Padded head dim 64: the
-// fwd5 body; 96 / 128: the fwd3 body.
+// padded head dim), see fa3_inst.h.  Padded head dim 64: the fwd5 body; 96 / 128: the fwd3 body.
 //
 // K = x8 * k_scale, V = x8 * v_scale with the fp32 scales of the layer read here from device memory (no host sync: a scale
 // may change between replays of a captured graph).  The bytes are widened exactly to 16 bits in LDS (fa3_fwd5_body.inc,
 // fa3_fwd3_body.inc: FA_KV8, with kv8_cvt2 of kv8_cvt.h) and the MFMAs see x8 itself; k_scale joins softmax_scale *
-// log2(e) in the fp32 score scale, v_scale the epilogue's 1 / l.  The per-lane strides of the bodies count 16-bit units (ks2 = 2 * ks_s bytes), so the
-// launcher gives the one-byte cache's strides halved.  No extra LDS: a wave's fp8 rows land inside the 16-bit image of
-// the same rows, which that wave alone widens, so the stage sizes are those of the 16-bit kernels.
+// log2(e) in the fp32 score scale, v_scale the epilogue's 1 / l.  The per-lane strides of the bodies count 16-bit units
+// (ks2 = 2 * ks_s bytes), so the paged plan (fa3_api.hip) gives the one-byte cache's strides halved.  No extra LDS: a
+// wave's fp8 rows land inside the 16-bit image of the same rows, which that wave alone widens, so the stage sizes are
+// those of the 16-bit kernels.
+#include "fa3_inst.h"
 #include "fa3_paged.h"
 #include "kv8_cvt.h"
-
-#if FA_TYPE_ID == 0
-using FaT = __bf16;
-#else
-using FaT = _Float16;
-#endif
 
 struct FaKv8Args {
   FaDev p;
   const float* k_scale;  // device: the layer's fp32 scales
   const float* v_scale;
-  int left, right;       // window; -1 = unbounded (the launcher clamps both below 2^30)
+  int left, right;       // window; -1 = unbounded (the plan clamps both to 2^29: fa3_api.hip, fa_plan_window)
 };
 
 #define FA_KV8 1
-#define FA_WIN_PASS_PAGED(t_lo, t_end, t_next, first) walk.begin_pass(pg, (t_lo), (t_end), (t_next), (first))
-#define FA_KV_TILE_PAGED_WIN(tile, kb, vb) walk.tile_base(pg, (tile), kbase, vbase, ks2, vs2, kb, vb)
 #define FA_LSE_INDEX(b, head, row) ((int64_t)(head) * pg.total_q + (row))
 
 // ---- head dim <= 64: the fwd5 body
@@ -38,8 +31,7 @@ __global__ __launch_bounds__(512) void fa3_fwd5_paged_kv8_kernel(const FaKv8Args
   FaDev p = a.p;
   FaPageWalk walk;
   if (!fa_paged_prepare<FA5_BM, 512, CAUSAL>(p, pg, walk)) return;
-  p.scale_log2e *= *a.k_scale;
-  const float kv8_vs = *a.v_scale;
+  const float kv8_vs = fa_kv8_scales(p, a.k_scale, a.v_scale);
 #define FA_KV_TILE FA_KV_TILE_PAGED
 #include "fa3_fwd5_body.inc"
 #undef FA_KV_TILE
@@ -56,8 +48,7 @@ __global__ __launch_bounds__(512) void fa3_fwd5_paged_kv8_win_kernel(const FaKv8
   int bseq;
   if (!fa_seq_prepare<FA5_BM, 512, CAUSAL>(p, pg, bseq)) return;
   walk.row = (fa_cint32*)(pg.block_tables + (int64_t)bseq * pg.max_blocks);
-  p.scale_log2e *= *a.k_scale;
-  const float kv8_vs = *a.v_scale;
+  const float kv8_vs = fa_kv8_scales(p, a.k_scale, a.v_scale);
 #define FA_KV_TILE FA_KV_TILE_PAGED_WIN
 #define FA_WIN_PASS FA_WIN_PASS_PAGED
 #include "fa3_fwd5_body.inc"
@@ -74,8 +65,7 @@ __global__ __launch_bounds__(256) void fa3_fwd3_paged_kv8_kernel(const FaKv8Args
   FaDev p = a.p;
   FaPageWalk walk;
   if (!fa_paged_prepare<FA3_BM, 256, CAUSAL>(p, pg, walk)) return;
-  p.scale_log2e *= *a.k_scale;
-  const float kv8_vs = *a.v_scale;
+  const float kv8_vs = fa_kv8_scales(p, a.k_scale, a.v_scale);
 #define FA_KV_TILE FA_KV_TILE_PAGED
 #include "fa3_fwd3_body.inc"
 #undef FA_KV_TILE
@@ -92,8 +82,7 @@ __global__ __launch_bounds__(256) void fa3_fwd3_paged_kv8_win_kernel(const FaKv8
   int bseq;
   if (!fa_seq_prepare<FA3_BM, 256, CAUSAL>(p, pg, bseq)) return;
   walk.row = (fa_cint32*)(pg.block_tables + (int64_t)bseq * pg.max_blocks);
-  p.scale_log2e *= *a.k_scale;
-  const float kv8_vs = *a.v_scale;
+  const float kv8_vs = fa_kv8_scales(p, a.k_scale, a.v_scale);
 #define FA_KV_TILE FA_KV_TILE_PAGED_WIN
 #define FA_WIN_PASS FA_WIN_PASS_PAGED
 #include "fa3_fwd3_body.inc"
@@ -117,22 +106,9 @@ constexpr auto kv8_kernel() {
 #endif
 }
 
-#if FA_D == 64
-constexpr int KV8_BM = FA5_BM, KV8_NT = 512;
-constexpr size_t KV8_SMEM = FA5_SMEM;
-#else
-constexpr int KV8_BM = FA3_BM, KV8_NT = 256;
-constexpr size_t KV8_SMEM = FA3_STAGES * FaSmem<FA_D>::STAGE;
-#endif
-static_assert(KV8_SMEM <= 160 * 1024, "fp8 paged attention: LDS above 160 KiB per workgroup");
-
 template <bool WIN, bool CAUSAL>
 static int kv8_launch(FaKv8Args a, const FaPaged& pg, hipStream_t stream) {
-  a.p.nqblk = (pg.max_q + KV8_BM - 1) / KV8_BM;
-  a.p.qgrid = CAUSAL ? (a.p.nqblk + 1) / 2 : a.p.nqblk;  // heavy / light pairing of the query blocks
-  const int64_t grid = (int64_t)a.p.qgrid * a.p.B * a.p.H;
-  if (grid > 0x7fffffff) return mio_fail("fa3_fwd_paged_kv8: grid too large");
-  return fa_launch<kv8_kernel<WIN, CAUSAL>()>("fa3_fwd_paged_kv8", (unsigned)grid, KV8_NT, KV8_SMEM, stream, a, pg);
+  return fa_grid_launch<kv8_kernel<WIN, CAUSAL>(), CAUSAL>("fa3_fwd_paged_kv8", a.p, pg.max_q, stream, a, pg);
 }
 
 template <>

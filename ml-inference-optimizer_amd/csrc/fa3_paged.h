@@ -68,9 +68,10 @@ struct FaPageWalk {
     np0 = entry(g, 2);
     np1 = entry(g, 3);
   }
-  // the scalar K / V bases of tile `tile` of a pass with n_tiles tiles; kbase / vbase: the cache plus this head's offset
-  __device__ __forceinline__ void tile_base(const FaPaged& g, int tile, int n_tiles, const void* kbase, const void* vbase,
-                                            int ks2, int vs2, const char*& kb, const char*& vb) {
+  // The scalar K / V bases of tile `tile` of a pass that ends before tile t_end; kbase / vbase: the cache plus this head's
+  // offset.  wrap_lb: the logical block requested when a window runs past the pass' end (the next pass' first block).
+  __device__ __forceinline__ void tile_base(const FaPaged& g, int tile, int t_end, int wrap_lb, const void* kbase,
+                                            const void* vbase, int ks2, int vs2, const char*& kb, const char*& vb) {
     int lb = (int)__umulhi(2u * (uint32_t)tile, g.tpb_magic);
     lb = lb < g.max_blocks - 1 ? lb : g.max_blocks - 1;
     int slot = tile - lb * g.tpb;
@@ -85,7 +86,7 @@ struct FaPageWalk {
         wp0 = entry(g, lb);
         wp1 = entry(g, lb + 1);
       }
-      n0 = (w0 + 2) * g.tpb < n_tiles ? w0 + 2 : 0;  // the rest of this pass, or the next pass' first tiles
+      n0 = (w0 + 2) * g.tpb < t_end ? w0 + 2 : wrap_lb;  // the rest of this pass, or the next pass' first tiles
       np0 = entry(g, n0);
       np1 = entry(g, n0 + 1);
     }
@@ -98,9 +99,9 @@ struct FaPageWalk {
   }
 };
 
-// The walk of a windowed pass (fa3_win_inst.hip): tiles are absolute, a pass covers tiles t_lo .. t_end - 1, and the
-// window requested when one runs past the pass' end is the first block of the NEXT pass' range (t_next), not block 0.
-// The first pass starts the walk at its own first block.
+// The walk of a windowed pass (fa3_win_inst.hip, fa3_kv8_inst.hip): tiles are absolute, a pass covers tiles t_lo ..
+// t_end - 1, and the window requested when one runs past the pass' end is the first block of the NEXT pass' range
+// (t_next), not block 0: tile_base gets (t_end, next_lb).  The first pass starts the walk at its own first block.
 struct FaPageWalkWin : FaPageWalk {
   int t_end, next_lb;
   __device__ __forceinline__ void begin_pass(const FaPaged& g, int t_lo, int t_end_, int t_next, bool first) {
@@ -115,33 +116,6 @@ struct FaPageWalkWin : FaPageWalk {
       np1 = entry(g, n0 + 1);
     }
   }
-  __device__ __forceinline__ void tile_base(const FaPaged& g, int tile, const void* kbase, const void* vbase, int ks2,
-                                            int vs2, const char*& kb, const char*& vb) {
-    int lb = (int)__umulhi(2u * (uint32_t)tile, g.tpb_magic);
-    lb = lb < g.max_blocks - 1 ? lb : g.max_blocks - 1;
-    int slot = tile - lb * g.tpb;
-    slot = slot < g.tpb - 1 ? slot : g.tpb - 1;
-    if ((uint32_t)(lb - w0) >= 2u) {
-      if ((uint32_t)(lb - n0) < 2u) {
-        w0 = n0;
-        wp0 = np0;
-        wp1 = np1;
-      } else {  // off the walk: load the window now
-        w0 = lb;
-        wp0 = entry(g, lb);
-        wp1 = entry(g, lb + 1);
-      }
-      n0 = (w0 + 2) * g.tpb < t_end ? w0 + 2 : next_lb;  // the rest of this pass, or the next pass' first tiles
-      np0 = entry(g, n0);
-      np1 = entry(g, n0 + 1);
-    }
-    int page = lb == w0 ? wp0 : wp1;
-    page = page < 0 ? 0 : (page < g.num_blocks - 1 ? page : g.num_blocks - 1);
-    const uint32_t r = ((uint32_t)page * (uint32_t)g.num_layers + (uint32_t)g.layer) * (uint32_t)g.block_size +
-                       (uint32_t)slot * FA_BN;
-    kb = (const char*)kbase + (uint64_t)r * (uint32_t)ks2;
-    vb = (const char*)vbase + (uint64_t)r * (uint32_t)vs2;
-  }
 };
 
 // Turns the launch's FaDev into this workgroup's dense problem over its sequence's pages and starts the walk (see
@@ -154,9 +128,19 @@ __device__ __forceinline__ bool fa_paged_prepare(FaDev& p, const FaPaged& g, FaP
   return true;
 }
 
+// The layer's scales of an fp8 (e4m3fn) cache, read from device memory: k_scale joins the score scale, v_scale is returned
+// for the epilogue's 1 / l (fa3_kv8_inst.hip).
+__device__ __forceinline__ float fa_kv8_scales(FaDev& p, const float* k_scale, const float* v_scale) {
+  p.scale_log2e *= *k_scale;
+  return *v_scale;
+}
+
 // FA_KV_TILE of the paged kernels: `walk`, `pg` (FaPaged) come from the kernel, n_tiles / kbase / vbase / ks2 / vs2 from
-// the body
-#define FA_KV_TILE_PAGED(tile, kb, vb) walk.tile_base(pg, (tile), n_tiles, kbase, vbase, ks2, vs2, kb, vb)
+// the body.  Windowed paged kernels: their FA_KV_TILE, and FA_WIN_PASS of a pass.
+#define FA_KV_TILE_PAGED(tile, kb, vb) walk.tile_base(pg, (tile), n_tiles, 0, kbase, vbase, ks2, vs2, kb, vb)
+#define FA_KV_TILE_PAGED_WIN(tile, kb, vb) \
+  walk.tile_base(pg, (tile), walk.t_end, walk.next_lb, kbase, vbase, ks2, vs2, kb, vb)
+#define FA_WIN_PASS_PAGED(t_lo, t_end, t_next, first) walk.begin_pass(pg, (t_lo), (t_end), (t_next), (first))
 
 // padded head dim 64: the fwd5 body (plain K and output) on this workgroup's sequence, K / V tiles through its pages
 template <typename T, bool CAUSAL>

@@ -1,16 +1,11 @@
 // The per-sequence attention forwards: packed variable-length (mio_fa3_fwd_varlen, fa3_varlen.h) and over the paged KV
-// cache (mio_fa3_fwd_paged, fa3_paged.h).  One translation unit per (dtype, padded head dim), compiled with
-// -DFA_TYPE_ID={0,1} -DFA_D={64,96,128} like fa3_fwd_inst.hip.  Padded head dim 64: the fwd5 form of the sequence's
-// kernel (route fwd5's kernel); 96 / 128: the fwd3 form (route fwd3's).  Plain K, plain output.
+// cache (mio_fa3_fwd_paged, fa3_paged.h).  One translation unit per (dtype, padded head dim), see fa3_inst.h.  Padded
+// head dim 64: the fwd5 form of the sequence's kernel (route fwd5's kernel); 96 / 128: the fwd3 form (route fwd3's).
+// Plain K, plain output.
 #include <type_traits>
 
+#include "fa3_inst.h"
 #include "fa3_paged.h"
-
-#if FA_TYPE_ID == 0
-using FaT = __bf16;
-#else
-using FaT = _Float16;
-#endif
 
 // the kernel for the sequence description V (FaVarlen / FaPaged)
 template <typename V, bool CAUSAL>
@@ -28,19 +23,7 @@ constexpr auto seq_kernel() {
 template <typename V, bool CAUSAL>
 static int launch(FaDev p, const V& s, hipStream_t stream) {
   const char* family = std::is_same_v<V, FaVarlen> ? "fa3_fwd_varlen" : "fa3_fwd_paged";
-#if FA_D == 64
-  constexpr int BM = FA5_BM, NT = 512;
-  constexpr size_t smem = FA5_SMEM;
-#else
-  constexpr int BM = FA3_BM, NT = 256;
-  constexpr size_t smem = FA3_STAGES * FaSmem<FA_D>::STAGE;
-#endif
-  // the grid of a dense [B, max_seqlen_q] launch; workgroups past their own sequence's blocks leave at once
-  p.nqblk = (s.max_q + BM - 1) / BM;
-  p.qgrid = CAUSAL ? (p.nqblk + 1) / 2 : p.nqblk;
-  const int64_t grid = (int64_t)p.qgrid * p.B * p.H;
-  if (grid > 0x7fffffff) return mio_fail(std::string(family) + ": grid too large");
-  return fa_launch<seq_kernel<V, CAUSAL>()>(family, (unsigned)grid, NT, smem, stream, p, s);
+  return fa_grid_launch<seq_kernel<V, CAUSAL>(), CAUSAL>(family, p, s.max_q, stream, p, s);
 }
 
 template <>

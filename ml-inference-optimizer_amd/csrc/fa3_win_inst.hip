@@ -1,27 +1,20 @@
 // Sliding-window forms of the pipelined attention kernels (mio_fa3_fwd_window, mio_fa3_fwd_varlen_window,
-// mio_fa3_fwd_paged_window).  One translation unit per (dtype, padded head dim), compiled with -DFA_TYPE_ID={0,1}
-// -DFA_D={64,96,128} like fa3_fwd_inst.hip.  Padded head dim 64: the fwd5 body; 96 / 128: the fwd3 body -- both with
-// FA_WINDOW defined, so that each pass walks only the KV tiles of its rows' windows (fa3_fwd5_body.inc).  Plain K, plain
-// output, no mask, no carry.  The window bounds travel beside FaDev (FaWinArgs), whose layout is unchanged.
+// mio_fa3_fwd_paged_window).  One translation unit per (dtype, padded head dim), see fa3_inst.h.  Padded head dim 64:
+// the fwd5 body; 96 / 128: the fwd3 body -- both with FA_WINDOW defined, so that each pass walks only the KV tiles of its
+// rows' windows (fa3_fwd5_body.inc).  Plain K, plain output, no mask, no carry.  The window bounds travel beside FaDev
+// (FaWinArgs), whose layout is unchanged.
 #include <type_traits>
 
+#include "fa3_inst.h"
 #include "fa3_paged.h"
-
-#if FA_TYPE_ID == 0
-using FaT = __bf16;
-#else
-using FaT = _Float16;
-#endif
 
 struct FaWinArgs {
   FaDev p;
-  int left, right;  // -1 = unbounded; the launcher clamps both below 2^30
+  int left, right;  // -1 = unbounded; the plan (fa3_api.hip, fa_plan_window) clamps both to 2^29
 };
 
 #define FA_WINDOW 1
-#define FA_WIN_PASS_NONE(t_lo, t_end, t_next, first) ((void)0)
-#define FA_WIN_PASS_PAGED(t_lo, t_end, t_next, first) walk.begin_pass(pg, (t_lo), (t_end), (t_next), (first))
-#define FA_KV_TILE_PAGED_WIN(tile, kb, vb) walk.tile_base(pg, (tile), kbase, vbase, ks2, vs2, kb, vb)
+#define FA_WIN_PASS_NONE(t_lo, t_end, t_next, first) ((void)0)  // the dense and varlen kernels keep no page walk
 
 // ---- head dim <= 64: the fwd5 body
 template <typename T, bool CAUSAL>
@@ -142,38 +135,27 @@ constexpr auto win_kernel() {
 }
 
 template <typename V, bool CAUSAL, typename... S>
-static int win_launch(FaWinArgs a, int max_q, int batches, hipStream_t stream, const S&... seq) {
+static int win_launch(FaWinArgs a, int max_q, hipStream_t stream, const S&... seq) {
   const char* family = std::is_same_v<V, void> ? "fa3_fwd_window" : std::is_same_v<V, FaVarlen> ? "fa3_fwd_varlen_window"
                                                                                                   : "fa3_fwd_paged_window";
-#if FA_D == 64
-  constexpr int BM = FA5_BM, NT = 512;
-  constexpr size_t smem = FA5_SMEM;
-#else
-  constexpr int BM = FA3_BM, NT = 256;
-  constexpr size_t smem = FA3_STAGES * FaSmem<FA_D>::STAGE;
-#endif
-  a.p.nqblk = (max_q + BM - 1) / BM;
-  a.p.qgrid = CAUSAL ? (a.p.nqblk + 1) / 2 : a.p.nqblk;  // heavy / light pairing of the query blocks, as unwindowed
-  const int64_t grid = (int64_t)a.p.qgrid * batches * a.p.H;
-  if (grid > 0x7fffffff) return mio_fail(std::string(family) + ": grid too large");
-  return fa_launch<win_kernel<V, CAUSAL>()>(family, (unsigned)grid, NT, smem, stream, a, seq...);
+  return fa_grid_launch<win_kernel<V, CAUSAL>(), CAUSAL>(family, a.p, max_q, stream, a, seq...);
 }
 
 template <>
 int fa3_win_launch<FaT, FA_D>(const FaDev& p, int causal, int left, int right, hipStream_t stream) {
   const FaWinArgs a = {p, left, right};
-  return causal ? win_launch<void, true>(a, p.Sq, p.B, stream) : win_launch<void, false>(a, p.Sq, p.B, stream);
+  return causal ? win_launch<void, true>(a, p.Sq, stream) : win_launch<void, false>(a, p.Sq, stream);
 }
 
 template <>
 int fa3_win_seq_launch<FaT, FA_D>(const FaDev& p, const FaVarlen& s, int causal, int left, int right, hipStream_t stream) {
   const FaWinArgs a = {p, left, right};
-  return causal ? win_launch<FaVarlen, true>(a, s.max_q, p.B, stream, s)
-                : win_launch<FaVarlen, false>(a, s.max_q, p.B, stream, s);
+  return causal ? win_launch<FaVarlen, true>(a, s.max_q, stream, s)
+                : win_launch<FaVarlen, false>(a, s.max_q, stream, s);
 }
 
 template <>
 int fa3_win_seq_launch<FaT, FA_D>(const FaDev& p, const FaPaged& s, int causal, int left, int right, hipStream_t stream) {
   const FaWinArgs a = {p, left, right};
-  return causal ? win_launch<FaPaged, true>(a, s.max_q, p.B, stream, s) : win_launch<FaPaged, false>(a, s.max_q, p.B, stream, s);
+  return causal ? win_launch<FaPaged, true>(a, s.max_q, stream, s) : win_launch<FaPaged, false>(a, s.max_q, stream, s);
 }

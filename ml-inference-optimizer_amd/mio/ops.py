@@ -136,15 +136,17 @@ def _fill_null(p, fields, addr: int) -> None:
             setattr(p, f, addr)
 
 
-def _route(query, p, names) -> str:
-    r = query(C.byref(p))
+def _route(query, p, window, names, *scales) -> str:
+    """The route name of a *_route_window query (window (-1, -1): exactly the query without one); scales: the fp8 form's."""
+    r = query(C.byref(p), *scales, window[0], window[1])
     if r < 0:
         raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
     return names[r]
 
 
-def _launch(fwd, p, out, lse, return_lse: bool):  # queued on the current stream; RuntimeError on failure
-    check(fwd(C.byref(p), _stream()))
+def _launch(fwd, p, window, out, lse, return_lse: bool, *scales):
+    """A *_window launch (as _route), queued on the current stream; RuntimeError on failure."""
+    check(fwd(C.byref(p), *scales, window[0], window[1], _stream()))
     return (out, lse) if return_lse else out
 
 
@@ -163,18 +165,6 @@ def _window(window_size, causal: bool = False):
     if causal and right > 0:
         raise ValueError(f"causal attention has window_size[1] = 0: give -1 or 0, got {right}")
     return left, right
-
-
-def _launch_window(fwd, p, window, out, lse, return_lse: bool):
-    check(fwd(C.byref(p), window[0], window[1], _stream()))
-    return (out, lse) if return_lse else out
-
-
-def _route_window(query, p, window, names) -> str:
-    r = query(C.byref(p), window[0], window[1])
-    if r < 0:
-        raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
-    return names[r]
 
 
 def _dense_window(window_size, causal=False, keep_mask=None, additive_mask=None, o_acc=None, carry_in=False,
@@ -235,9 +225,7 @@ def fa3_fwd(
                                      keep_mask=keep_mask, additive_mask=additive_mask, return_lse=return_lse, out=out,
                                      o_acc=o_acc, lse=lse, carry_in=carry_in, write_out=write_out, q_offset=q_offset,
                                      k_offset=k_offset, k_prescaled=k_prescaled, out_blocked=out_blocked)
-    if w != (-1, -1):
-        return _launch_window(lib.mio_fa3_fwd_window, p, w, out, lse, return_lse)
-    return _launch(lib.mio_fa3_fwd, p, out, lse, return_lse)
+    return _launch(lib.mio_fa3_fwd_window, p, w, out, lse, return_lse)
 
 
 def fa3_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, **kwargs) -> str:
@@ -247,9 +235,7 @@ def fa3_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, **kwargs) -> st
     window_size = kwargs.pop("window_size", (-1, -1))
     w = _dense_window(window_size, **kwargs)
     p, _out, _lse, _keep = _fa3_params(q, k, v, **kwargs)
-    if w != (-1, -1):
-        return _route_window(lib.mio_fa3_route_window, p, w, _lib.FA3_ROUTES)
-    return _route(lib.mio_fa3_route, p, _lib.FA3_ROUTES)
+    return _route(lib.mio_fa3_route_window, p, w, _lib.FA3_ROUTES)
 
 
 def _fa3_params(q, k, v, *, layout="bshd", causal=False, softmax_scale=None, keep_mask=None, additive_mask=None,
@@ -474,9 +460,7 @@ def flash_attention_varlen(
     _need_cuda(q, k, v, cu_seqlens_q, cu_seqlens_k)
     p, out, lse, _keep = _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal,
                                         softmax_scale=softmax_scale, return_lse=return_lse, out=out)
-    if w != (-1, -1):
-        return _launch_window(lib.mio_fa3_fwd_varlen_window, p, w, out, lse, return_lse)
-    return _launch(lib.mio_fa3_fwd_varlen, p, out, lse, return_lse)
+    return _launch(lib.mio_fa3_fwd_varlen_window, p, w, out, lse, return_lse)
 
 
 def fa3_varlen_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor,
@@ -485,9 +469,7 @@ def fa3_varlen_route(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqle
     launching.  Tensors may live on any device; arguments flash_attention_varlen refuses raise the same errors."""
     w = _window(kwargs.pop("window_size", (-1, -1)), kwargs.get("causal", False))
     p, _out, _lse, _keep = _varlen_params(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, **kwargs)
-    if w != (-1, -1):
-        return _route_window(lib.mio_fa3_varlen_route_window, p, w, _lib.FA3_VARLEN_ROUTES)
-    return _route(lib.mio_fa3_varlen_route, p, _lib.FA3_VARLEN_ROUTES)
+    return _route(lib.mio_fa3_varlen_route_window, p, w, _lib.FA3_VARLEN_ROUTES)
 
 
 def unpad_input(x: torch.Tensor, keep: torch.Tensor):
@@ -1130,11 +1112,8 @@ def flash_attention_varlen_paged(
                                              softmax_scale=softmax_scale, return_lse=return_lse, out=out,
                                              k_scale=k_scale, v_scale=v_scale)
     if scales is not None:
-        check(lib.mio_fa3_fwd_paged_kv8(C.byref(p), scales[0], scales[1], w[0], w[1], _stream()))
-        return (out, lse) if return_lse else out
-    if w != (-1, -1):
-        return _launch_window(lib.mio_fa3_fwd_paged_window, p, w, out, lse, return_lse)
-    return _launch(lib.mio_fa3_fwd_paged, p, out, lse, return_lse)
+        return _launch(lib.mio_fa3_fwd_paged_kv8, p, w, out, lse, return_lse, *scales)
+    return _launch(lib.mio_fa3_fwd_paged_window, p, w, out, lse, return_lse)
 
 
 def fa3_paged_route(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
@@ -1147,13 +1126,8 @@ def fa3_paged_route(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
     p, _out, _lse, _keep, scales = _paged_args(q, k_cache, v_cache, block_tables, cu_seqlens_q, seqused_k, max_seqlen_q,
                                                max_seqlen_k, **kwargs)
     if scales is not None:
-        r = lib.mio_fa3_paged_kv8_route(C.byref(p), scales[0], scales[1], w[0], w[1])
-        if r < 0:
-            raise RuntimeError(lib.mio_last_error().decode("utf-8", "replace"))
-        return _lib.FA3_PAGED_ROUTES[r]
-    if w != (-1, -1):
-        return _route_window(lib.mio_fa3_paged_route_window, p, w, _lib.FA3_PAGED_ROUTES)
-    return _route(lib.mio_fa3_paged_route, p, _lib.FA3_PAGED_ROUTES)
+        return _route(lib.mio_fa3_paged_kv8_route, p, w, _lib.FA3_PAGED_ROUTES, *scales)
+    return _route(lib.mio_fa3_paged_route_window, p, w, _lib.FA3_PAGED_ROUTES)
 
 
 def _decode_window(window_size) -> int:
