@@ -5,8 +5,8 @@
 #include "gemm_kernel.h"
 #include "gemm_route.h"
 
-extern template int gemm_launch<__bf16>(GemmDev, int, hipStream_t);
-extern template int gemm_launch<_Float16>(GemmDev, int, hipStream_t);
+extern template int gemm_launch<__bf16>(GemmDev, int, int, hipStream_t);
+extern template int gemm_launch<_Float16>(GemmDev, int, int, hipStream_t);
 
 // Diagnostic build only: MIO_GEMM_IMPL=v1|8w1 forces one pipeline for A/B comparisons (read once).  The product
 // library always takes the default dispatch (0) and reads no environment variable.
@@ -27,96 +27,255 @@ int mio_gemm_impl() {
 #endif
 }
 
-static int gemm_dispatch(const GemmDev& p, int act, int dtype, hipStream_t st) {
-  if (dtype == MIO_BF16) return gemm_launch<__bf16>(p, act, st);
-  return gemm_launch<_Float16>(p, act, st);
+// ---- shape queries: which launches take the 256-tile kernels (gemm_route.h gemm_tiles_ok) ---------------------------------------
+static bool gemm_blocked_w_ok(int64_t M, int32_t N, int32_t K, int32_t act) {
+  return act != MIO_ACT_SWIGLU && mio_gemm_impl() != 1 && gemm_tiles_ok(M, N, K, 256);
+}
+
+extern "C" int32_t mio_gemm_blocked_weight_ok(int64_t M, int32_t N, int32_t K, int32_t act) {
+  return gemm_blocked_w_ok(M, N, K, act) ? 1 : 0;
+}
+
+// column scale: the launch must end in the persistent kernel (gemm_inst.hip launch_act): blocked weight shape, no residual,
+// K >= 256, K % 64 == 0
+extern "C" int32_t mio_gemm_col_scale_ok(int64_t M, int32_t N, int32_t K, int32_t act) {
+  return (gemm_blocked_w_ok(M, N, K, act) && K >= 256 && K % 64 == 0 && N % 8 == 0) ? 1 : 0;
+}
+
+// Both GEMMs of the MLP take a 256x256-tile 16x16x32 kernel (gemm_inst.hip launch_act) and stage 1 the persistent one:
+// then the intermediate can use the blocked layout (GemmDev::x_blk / y_blk).
+// (SwiGLU: stage 1 computes 256 x 128 output tiles from 256 interleaved gate / up weight rows, gemm8w_kernel.h)
+static bool mlp_blocked_ok(int64_t M, int32_t d, int32_t I) {
+  return mio_gemm_impl() != 1 && gemm_tiles_ok(M, I, d, 256) && gemm_tiles_ok(M, d, I, 256) && d % 64 == 0 && d >= 256 &&
+         I % 256 == 0;
+}
+
+extern "C" int32_t mio_fused_mlp_blocked_weight_ok(int64_t M, int32_t d, int32_t I, int32_t act) {
+  (void)act;
+  return (M > 0 && mlp_blocked_ok(M, d, I)) ? 1 : 0;
+}
+
+// the longest weight rows mio_ln_fold_weight prepares (ln_fold_weight_kernel: 256 threads x 32 elements), so the widest stream a
+// consumer (fold_in) takes
+constexpr int32_t GEMM_LN_FOLD_K_MAX = 8192;
+
+extern "C" int32_t mio_gemm_ln_ok(int64_t M, int32_t N, int32_t K, int32_t act, int32_t fold_in, int32_t stats_out) {
+  if (mio_gemm_impl() != 0) return 0;
+  if (fold_in && K > GEMM_LN_FOLD_K_MAX) return 0;
+  if (act == MIO_ACT_SWIGLU)  // the gated stage (interleaved gate / up blocked weight, 256 x 128 output tiles): consumer form only
+    return (gemm_tiles_ok(M, N, K, 128) && !stats_out && N % 128 == 0 && (!fold_in || K % 256 == 0)) ? 1 : 0;
+  if (!gemm_blocked_w_ok(M, N, K, act) || N % 32 != 0) return 0;
+  if (fold_in && (K % 256 != 0 || (act != MIO_ACT_NONE && act != MIO_ACT_GELU_TANH))) return 0;
+  if (stats_out && (N % 256 != 0 || act != MIO_ACT_NONE || fold_in)) return 0;
+  return 1;
+}
+
+// ---- the host plan: every launch form and mio_gemm_route validate, fill the device struct and pick the kernel here ----------------
+// A form is an entry point's set of checks and the words of its refusals (tests/test_gemm_refusals_host.py pins both; the order
+// of the checks is not part of the contract):
+enum GemmForm {
+  GEMM_PLAIN,  // mio_gemm_bias_act: row-major weight, every shape
+  GEMM_BW,     // mio_gemm_bias_act_bw: blocked weight, gated by mio_gemm_blocked_weight_ok
+  GEMM_CS,     // mio_gemm_bias_act_bw_cs: GEMM_BW with a column range and no residual, gated by mio_gemm_col_scale_ok
+  GEMM_LN,     // mio_gemm_ln_bw: blocked / interleaved weight, LayerNorm consumer or producer, gated by mio_gemm_ln_ok
+  GEMM_STAGE,  // a stage of the blocked fused MLP on a blocked weight: mlp_blocked_ok has judged both stages
+};
+
+// A call as its entry point received it (the operands, sizes, strides and layouts sit in `dev`, everything not named at its
+// default); gemm_plan makes `dev` what the kernel reads and names the kernel in `route`.
+struct GemmCall {
+  GemmForm form;
+  int act, dtype, route;
+  GemmDev dev;
+};
+
+static GemmCall gemm_call(GemmForm form, const void* x, const void* w, const void* bias, const void* residual, void* y, int64_t M,
+                          int32_t N, int32_t K, int64_t ldx, int64_t ldy, int64_t ldr, int32_t act, int32_t dtype) {
+  GemmCall c = {form, act, dtype, MIO_GEMM_ROUTE_EMPTY, {}};
+  GemmDev& p = c.dev;
+  gemm_dev_defaults(p);
+  p.x = x; p.w = w; p.bias = bias; p.res = residual; p.y = y;
+  p.M = M; p.N = N; p.K = K; p.ldx = ldx; p.ldw = K; p.ldy = ldy; p.ldr = ldr;
+  p.w_blk = form == GEMM_PLAIN ? 0 : act == MIO_ACT_SWIGLU ? 2 : 1;  // (2: gate / up rows interleaved per wave)
+  return c;
+}
+
+// route_only (mio_gemm_route): no pointer or dtype checks; a non-null res / ln_stats / stats_out only says that the operand is
+// given.  M == 0 is answered as each entry point always has: mio_gemm_bias_act after all its checks, mio_gemm_ln_bw right after
+// the null and size checks, mio_gemm_route before the blocked forms' shape checks (all three: MIO_GEMM_ROUTE_EMPTY);
+// mio_gemm_bias_act_bw / _bw_cs refuse it through their shape query.
+static int gemm_plan(const char* who, GemmCall& c, bool route_only) {
+#define GEMM_CHECK(cond, text) MIO_CHECK(cond, std::string(who) + (text))
+  GemmDev& p = c.dev;
+  const bool launch = !route_only, plain = c.form == GEMM_PLAIN, bw = c.form == GEMM_BW, cs = c.form == GEMM_CS, ln = c.form == GEMM_LN;
+  const bool res = p.res != nullptr, fold = p.ln_stats != nullptr, stats = p.stats_out != nullptr, glu = c.act == MIO_ACT_SWIGLU;
+  const int64_t M = p.M;
+  const int N = p.N, K = p.K;
+  // (M == 0: x and y hold no element, and an empty allocation may be a null pointer)
+  if (launch && plain) GEMM_CHECK(p.w && (M == 0 || (p.x && p.y)), ": x, w, y must be non-null");
+  if (launch && !plain) GEMM_CHECK(p.x && p.w && p.y, ": x, wb, y must be non-null");
+  GEMM_CHECK(M >= 0 && N > 0 && K > 0, ": bad sizes");
+  if (launch && ln && M == 0) return 0;
+  GEMM_CHECK(route_only || c.dtype == MIO_BF16 || c.dtype == MIO_FP16, ": dtype must be bf16 or fp16");
+  if (launch && (bw || cs)) GEMM_CHECK(c.act >= MIO_ACT_NONE && c.act < MIO_ACT_SWIGLU, ": unknown / unsupported activation");
+  GEMM_CHECK(c.act >= MIO_ACT_NONE && c.act <= MIO_ACT_SWIGLU, ": unknown activation");
+  if (launch && plain) GEMM_CHECK(glu == (p.wg != nullptr), ": w_gate is required iff act == SWIGLU");
+  GEMM_CHECK(!plain || (!fold && !stats), ": the LayerNorm forms take a blocked weight");
+  // row strides: a blocked operand has none, its row length stands in (the weight's, once checked as given)
+  if (p.x_blk) p.ldx = K;
+  if (p.y_blk) p.ldy = N;
+  if (p.res_blk) p.ldr = N;
+  const bool ld8 = p.ldx % 8 == 0 && p.ldw % 8 == 0 && p.ldy % 8 == 0 && (!res || p.ldr % 8 == 0);
+  const bool ldlen = p.ldx >= K && p.ldw >= K && p.ldy >= N;
+  if (plain || route_only) GEMM_CHECK(K % 8 == 0 && N % 8 == 0, ": N and K must be multiples of 8");
+  if (launch && plain) {
+    GEMM_CHECK(ld8, ": row strides must be multiples of 8 elements");
+    GEMM_CHECK(ldlen, ": row stride smaller than row length");
+  }  // (only mio_gemm_ln_bw asks ldr >= N, and only mio_gemm_bias_act_bw N % 8: the other shape queries ask more of N)
+  GEMM_CHECK(ld8 && ldlen && (!bw || N % 8 == 0) && (!ln || route_only || !res || p.ldr >= N), ": bad strides");
+  if (!plain) p.ldw = K;
+  if (launch)
+    GEMM_CHECK(mio_aligned16(p.x) && mio_aligned16(p.w) && mio_aligned16(p.y) && mio_aligned16(p.wg) && mio_aligned16(p.res) &&
+                   mio_aligned16(p.bias) && mio_aligned16(p.bias_g) && mio_aligned16(p.ln_stats) && mio_aligned16(p.stats_out),
+               ": pointers must be 16-byte aligned");
+  if (route_only && M == 0) return 0;
+  if (!plain)
+    GEMM_CHECK(gemm_off32(p.ldx) && gemm_off32(p.ldy) && (!res || gemm_off32(p.ldr)),
+               bw || route_only ? ": row stride too large for the blocked-weight kernels" : ": row stride too large");
+  if (bw)
+    GEMM_CHECK(gemm_blocked_w_ok(M, N, K, c.act),
+               route_only ? ": this shape does not take the blocked-weight kernels (mio_gemm_blocked_weight_ok == 0)"
+                          : ": this shape does not take the blocked-weight kernels (mio_gemm_blocked_weight_ok == 0); use "
+                            "mio_gemm_bias_act with the plain weight");
+  if (cs) {
+    GEMM_CHECK(mio_gemm_col_scale_ok(M, N, K, c.act), ": this shape does not run the persistent kernel (mio_gemm_col_scale_ok == 0)");
+    GEMM_CHECK(p.cs_lo >= 0 && p.cs_hi <= N && p.cs_lo % 128 == 0 && p.cs_hi % 128 == 0 && p.cs_lo <= p.cs_hi,
+               ": [cs_lo, cs_hi) must be multiples of 128 inside [0, N]");
+  }
+  if (ln) {
+    GEMM_CHECK(glu || p.bias_g == nullptr, ": bias_gate belongs to the gated stage (act == SWIGLU)");
+    GEMM_CHECK(mio_gemm_ln_ok(M, N, K, c.act, fold, stats), ": this shape / activation does not take the folded kernels (mio_gemm_ln_ok == 0)");
+    if (route_only) GEMM_CHECK(!((fold || glu) && res), ": the consumer and gated forms take no residual");
+    GEMM_CHECK(!(glu && res), ": the gated stage takes no residual");
+    GEMM_CHECK(!(fold && res), ": the consumer form takes no residual");
+    p.ln_slots = !fold ? 0 : p.ln_slots == 0 ? K / 256 : p.ln_slots;
+    GEMM_CHECK(!fold || route_only || (p.ln_slots >= 1 && p.ln_slots <= GEMM_LN_SLOTS_MAX),
+               ": at most 8 statistic slots (rows wider than 2048 columns: mio_ln_stats_reduce first)");
+    GEMM_CHECK(!stats || res, ": the producer form is the residual epilogue");
+    GEMM_CHECK(!p.res_blk || res, ": RES_BLOCKED without a residual");
+    GEMM_CHECK(p.cs_lo >= p.cs_hi || (!res && p.cs_lo >= 0 && p.cs_hi <= N && p.cs_lo % 128 == 0 && p.cs_hi % 128 == 0),
+               ": [cs_lo, cs_hi) must be multiples of 128 inside [0, N], without a residual");
+  }
+#undef GEMM_CHECK
+  GemmRouteArgs ra;
+  ra.M = M; ra.ldx = p.ldx; ra.ldw = p.ldw; ra.ldy = p.ldy; ra.ldr = p.ldr; ra.N = N; ra.K = K; ra.act = c.act;
+  ra.res = res; ra.w_blk = p.w_blk; ra.ln_stats = fold; ra.stats_out = stats;
+  c.route = gemm_pick_route(ra);
+  return 0;
+}
+
+static int gemm_dispatch(const GemmCall& c, void* stream) {
+  if (c.route == MIO_GEMM_ROUTE_EMPTY) return 0;
+  return c.dtype == MIO_BF16 ? gemm_launch<__bf16>(c.dev, c.act, c.route, (hipStream_t)stream)
+                             : gemm_launch<_Float16>(c.dev, c.act, c.route, (hipStream_t)stream);
+}
+
+static int gemm_run(const char* who, GemmCall& c, void* stream) {
+  const int rc = gemm_plan(who, c, false);
+  return rc != 0 ? rc : gemm_dispatch(c, stream);
 }
 
 extern "C" int mio_gemm_bias_act(const void* x, const void* w, const void* bias, const void* w_gate,
                                  const void* bias_gate, const void* residual, void* y, int64_t M, int32_t N,
                                  int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
                                  int32_t dtype, void* stream) {
-  // (M == 0: x and y hold no element, and an empty allocation may be a null pointer)
-  MIO_CHECK(w && (M == 0 || (x && y)), "mio_gemm_bias_act: x, w, y must be non-null");
-  MIO_CHECK(M >= 0 && N > 0 && K > 0, "mio_gemm_bias_act: bad sizes");
-  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_gemm_bias_act: dtype must be bf16 or fp16");
-  MIO_CHECK(act >= MIO_ACT_NONE && act <= MIO_ACT_SWIGLU, "mio_gemm_bias_act: unknown activation");
-  MIO_CHECK((act == MIO_ACT_SWIGLU) == (w_gate != nullptr), "mio_gemm_bias_act: w_gate is required iff act == SWIGLU");
-  MIO_CHECK(K % 8 == 0 && N % 8 == 0, "mio_gemm_bias_act: N and K must be multiples of 8");
-  MIO_CHECK(ldx % 8 == 0 && ldw % 8 == 0 && ldy % 8 == 0 && (residual == nullptr || ldr % 8 == 0),
-            "mio_gemm_bias_act: row strides must be multiples of 8 elements");
-  MIO_CHECK(ldx >= K && ldw >= K && ldy >= N, "mio_gemm_bias_act: row stride smaller than row length");
-  MIO_CHECK(mio_aligned16(x) && mio_aligned16(w) && mio_aligned16(y) && mio_aligned16(w_gate) &&
-                mio_aligned16(residual) && mio_aligned16(bias) && mio_aligned16(bias_gate),
-            "mio_gemm_bias_act: pointers must be 16-byte aligned");
-  if (M == 0) return 0;
-  GemmDev p;
-  gemm_dev_defaults(p);
-  p.x = x; p.w = w; p.wg = w_gate; p.bias = bias; p.bias_g = bias_gate; p.res = residual; p.y = y;
-  p.M = M; p.ldx = ldx; p.ldw = ldw; p.ldy = ldy; p.ldr = ldr; p.N = N; p.K = K;
-  p.tiles_m = p.tiles_n = 0;
-  p.x_blk = p.y_blk = 0;
-  p.w_blk = 0;
-  p.dbg = nullptr;
-  p.cs_lo = p.cs_hi = 0; p.cs_val = 1.f; p.group_m = 0;
-  return gemm_dispatch(p, act, dtype, (hipStream_t)stream);
+  GemmCall c = gemm_call(GEMM_PLAIN, x, w, bias, residual, y, M, N, K, ldx, ldy, ldr, act, dtype);
+  c.dev.wg = w_gate; c.dev.bias_g = bias_gate; c.dev.ldw = ldw;
+  return gemm_run("mio_gemm_bias_act", c, stream);
 }
 
-// Both GEMMs of the MLP take a 256x256-tile 16x16x32 kernel (gemm_inst.hip launch_act) and stage 1 the persistent one:
-// then the intermediate can use the blocked layout (GemmDev::x_blk / y_blk).
-static bool mlp_blocked_ok(int64_t M, int32_t d, int32_t I, int32_t act, bool residual) {
-  (void)residual;
-  if (mio_gemm_impl() == 1) return false;
-  const int64_t tm = (M + 255) / 256;
-  // (SwiGLU: stage 1 computes 256 x 128 output tiles from 256 interleaved gate / up weight rows, gemm8w_kernel.h)
-  const bool big1 = tm * ((I + 255) / 256) >= 256, big2 = tm * ((d + 255) / 256) >= 256;
-  const bool fits = (int64_t)d * 512 < 0x7fffffff && (int64_t)I * 512 < 0x7fffffff;
-  return big1 && big2 && fits && d % 64 == 0 && d >= 256 && I % 256 == 0 && d % 8 == 0;
+extern "C" int mio_gemm_bias_act_bw(const void* x, const void* wb, const void* bias, const void* residual, void* y,
+                                    int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldy, int64_t ldr, int32_t act,
+                                    int32_t dtype, int32_t x_blocked, void* stream) {
+  GemmCall c = gemm_call(GEMM_BW, x, wb, bias, residual, y, M, N, K, ldx, ldy, ldr, act, dtype);
+  c.dev.x_blk = x_blocked ? 1 : 0;  // blocked x: ceil(M / 256) * 256 x K elements, no row stride
+  return gemm_run("mio_gemm_bias_act_bw", c, stream);
 }
 
+extern "C" int mio_gemm_bias_act_bw_cs(const void* x, const void* wb, const void* bias, void* y, int64_t M, int32_t N,
+                                       int32_t K, int64_t ldx, int64_t ldy, int32_t act, int32_t dtype, int32_t x_blocked,
+                                       int32_t cs_lo, int32_t cs_hi, float cs_val, void* stream) {
+  GemmCall c = gemm_call(GEMM_CS, x, wb, bias, nullptr, y, M, N, K, ldx, ldy, 0, act, dtype);
+  c.dev.x_blk = x_blocked ? 1 : 0;
+  c.dev.cs_lo = cs_lo; c.dev.cs_hi = cs_hi; c.dev.cs_val = cs_val;
+  return gemm_run("mio_gemm_bias_act_bw_cs", c, stream);
+}
+
+extern "C" int mio_gemm_ln_bw(const void* x, const void* wb, const void* bias, const void* bias_gate, const void* residual, void* y, int64_t M, int32_t N,
+                              int32_t K, int64_t ldx, int64_t ldy, int64_t ldr, int32_t act, int32_t dtype, int32_t flags,
+                              const float* ln_stats, int32_t ln_slots, float ln_eps, float* stats_out, int32_t cs_lo, int32_t cs_hi,
+                              float cs_val, void* stream) {
+  MIO_CHECK(M == 0 || (flags & ~7) == 0, "mio_gemm_ln_bw: unknown flag");
+  GemmCall c = gemm_call(GEMM_LN, x, wb, bias, residual, y, M, N, K, ldx, ldy, ldr, act, dtype);
+  GemmDev& p = c.dev;
+  p.bias_g = bias_gate;
+  p.x_blk = (flags & MIO_GEMM_X_BLOCKED) != 0; p.y_blk = (flags & MIO_GEMM_Y_BLOCKED) != 0; p.res_blk = (flags & MIO_GEMM_RES_BLOCKED) != 0;
+  p.cs_lo = cs_lo; p.cs_hi = cs_hi; p.cs_val = cs_val;
+  p.ln_stats = ln_stats; p.ln_slots = ln_slots; p.ln_eps = ln_eps; p.stats_out = stats_out;
+  return gemm_run("mio_gemm_ln_bw", c, stream);
+}
+
+// ---- route query ------------------------------------------------------------------------------------------------------
+extern "C" int32_t mio_gemm_route(int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
+                                  int32_t has_residual, int32_t w_layout, int32_t fold_in, int32_t stats_out) {
+  MIO_CHECK(w_layout >= 0 && w_layout <= 2, "mio_gemm_route: w_layout must be 0 (row-major), 1 (blocked) or 2 (gate / up interleaved)");
+  MIO_CHECK((w_layout == 2) == (act == MIO_ACT_SWIGLU) || w_layout == 0,
+            "mio_gemm_route: the interleaved weight belongs to act == SWIGLU, and SWIGLU has no plain blocked weight");
+  static float given[1];  // marks an operand as given: the plan reads no pointer of a route query
+  const GemmForm form = w_layout == 0 ? GEMM_PLAIN : (fold_in || stats_out || act == MIO_ACT_SWIGLU) ? GEMM_LN : GEMM_BW;
+  GemmCall c = gemm_call(form, nullptr, nullptr, nullptr, has_residual ? given : nullptr, nullptr, M, N, K, ldx, ldy, ldr, act, MIO_BF16);
+  c.dev.ldw = ldw;  // (checked as given, also where a blocked weight then counts with its row length K)
+  c.dev.w_blk = w_layout;
+  c.dev.ln_stats = fold_in ? given : nullptr;
+  c.dev.stats_out = stats_out ? given : nullptr;
+  const int rc = gemm_plan("mio_gemm_route", c, true);
+  return rc != 0 ? rc : c.route;
+}
+
+// ---- fused MLP ------------------------------------------------------------------------------------------------------------
 extern "C" size_t mio_fused_mlp_workspace_bytes(int64_t M, int32_t d, int32_t I, int32_t act) {
   (void)d; (void)act;
   const int64_t mp = (M + 255) / 256 * 256;  // whole 256-row blocks (blocked intermediate layout)
   return (size_t)mp * (size_t)I * 2;
 }
 
+// Two GEMMs.  Where mlp_blocked_ok, both run on the 256-tile kernels with the intermediate in the blocked layout (SwiGLU: only
+// with its interleaved blocked weight) and refusals come as mio_fused_mlp_fwd; elsewhere they are what two mio_gemm_bias_act
+// calls are, refusals under that name included.
 static int fused_mlp_impl(const void* x, const void* w1, const void* b1, const void* wg, const void* bg, const void* w2,
                           const void* b2, const void* residual, void* y, void* workspace, int64_t M, int32_t d, int32_t I,
                           int32_t act, int32_t dtype, void* stream, int wblk, int xblk = 0) {
   MIO_CHECK(workspace != nullptr || M == 0, "mio_fused_mlp_fwd: workspace must be non-null");
   MIO_CHECK(act != MIO_ACT_NONE, "mio_fused_mlp_fwd: an activation is required");
-  if (M > 0 && mlp_blocked_ok(M, d, I, act, residual != nullptr) && (act != MIO_ACT_SWIGLU || wblk)) {
-    MIO_CHECK(x && w1 && w2 && y, "mio_fused_mlp_fwd: x, w1, w2, y must be non-null");
-    MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_fused_mlp_fwd: dtype must be bf16 or fp16");
-    MIO_CHECK(mio_aligned16(x) && mio_aligned16(w1) && mio_aligned16(w2) && mio_aligned16(y) && mio_aligned16(b1) &&
-                  mio_aligned16(b2) && mio_aligned16(residual) && mio_aligned16(workspace),
-              "mio_fused_mlp_fwd: pointers must be 16-byte aligned");
-    MIO_CHECK(act != MIO_ACT_SWIGLU || wblk, "mio_fused_mlp_fwd: the gated 256-tile kernel takes the interleaved blocked weight "
-                                            "(mio_weight_block_glu) through mio_fused_mlp_glu_fwd_bw");
-    GemmDev p;
-    gemm_dev_defaults(p);
-    p.x = x; p.w = w1; p.wg = nullptr; p.bias = b1; p.bias_g = bg; p.res = nullptr; p.y = workspace;
-    p.M = M; p.ldx = d; p.ldw = d; p.ldy = I; p.ldr = 0; p.N = I; p.K = d;
-    p.tiles_m = p.tiles_n = 0;
-    p.x_blk = xblk; p.y_blk = 1; p.w_blk = (act == MIO_ACT_SWIGLU) ? 2 : wblk;  // 2: gate / up rows interleaved per wave
-    p.dbg = nullptr;
-    p.cs_lo = p.cs_hi = 0; p.cs_val = 1.f; p.group_m = 0;
-    int rc = gemm_dispatch(p, act, dtype, (hipStream_t)stream);
-    if (rc != 0) return rc;
-    p.x = workspace; p.w = w2; p.bias = b2; p.bias_g = nullptr; p.res = residual; p.y = y;
-    p.ldx = I; p.ldw = I; p.ldy = d; p.ldr = d; p.N = d; p.K = I;
-    p.tiles_m = p.tiles_n = 0;
-    p.x_blk = 1; p.y_blk = 0; p.w_blk = wblk;
-    return gemm_dispatch(p, MIO_ACT_NONE, dtype, (hipStream_t)stream);
-  }
-  MIO_CHECK(!wblk && !xblk, "mio_fused_mlp_fwd_bw: this shape does not take the blocked-weight kernels "
-                   "(mio_fused_mlp_blocked_weight_ok == 0); pass the plain weights to mio_fused_mlp_fwd");
+  const bool glu = act == MIO_ACT_SWIGLU;
+  const bool blocked = M > 0 && mlp_blocked_ok(M, d, I) && (!glu || wblk);
+  if (blocked) MIO_CHECK(x && w1 && w2 && y, "mio_fused_mlp_fwd: x, w1, w2, y must be non-null");
+  else MIO_CHECK(!wblk && !xblk, "mio_fused_mlp_fwd_bw: this shape does not take the blocked-weight kernels "
+                                 "(mio_fused_mlp_blocked_weight_ok == 0); pass the plain weights to mio_fused_mlp_fwd");
+  const char* who = blocked ? "mio_fused_mlp_fwd" : "mio_gemm_bias_act";
+  const GemmForm form = wblk ? GEMM_STAGE : GEMM_PLAIN;
   // stage 1: h = act(x w1^T + b1) [* silu-gate], written once in the storage dtype
-  int rc = mio_gemm_bias_act(x, w1, b1, wg, bg, nullptr, workspace, M, I, d, d, d, I, 0, act, dtype, stream);
-  if (rc != 0) return rc;
+  GemmCall s1 = gemm_call(form, x, w1, b1, nullptr, workspace, M, I, d, d, I, 0, act, dtype);
+  s1.dev.x_blk = xblk; s1.dev.y_blk = blocked;
+  if (!blocked) s1.dev.wg = wg;
+  if (!blocked || glu) s1.dev.bias_g = bg;
   // stage 2: y = h w2^T + b2 (+ residual)
-  return mio_gemm_bias_act(workspace, w2, b2, nullptr, nullptr, residual, y, M, d, I, I, I, d, d, MIO_ACT_NONE,
-                           dtype, stream);
+  GemmCall s2 = gemm_call(form, workspace, w2, b2, residual, y, M, d, I, I, d, d, MIO_ACT_NONE, dtype);
+  s2.dev.x_blk = blocked;
+  int rc = gemm_plan(who, s1, false);
+  if (rc == 0) rc = gemm_plan(who, s2, false);
+  if (rc == 0) rc = gemm_dispatch(s1, stream);
+  return rc != 0 ? rc : gemm_dispatch(s2, stream);
 }
 
 extern "C" int mio_fused_mlp_fwd(const void* x, const void* w1, const void* b1, const void* wg, const void* bg,
@@ -125,13 +284,25 @@ extern "C" int mio_fused_mlp_fwd(const void* x, const void* w1, const void* b1, 
   return fused_mlp_impl(x, w1, b1, wg, bg, w2, b2, residual, y, workspace, M, d, I, act, dtype, stream, 0);
 }
 
-// ---- blocked weights -----------------------------------------------------------------------------------------------
-static bool gemm_blocked_w_ok(int64_t M, int32_t N, int32_t K, int32_t act) {
-  if (act == MIO_ACT_SWIGLU || mio_gemm_impl() == 1) return false;
-  const bool big = ((M + 255) / 256) * (int64_t)((N + 255) / 256) >= 256;
-  return big && K % 32 == 0 && K >= 128 && (int64_t)K * 512 < 0x7fffffff && (int64_t)N * 512 < 0x7fffffff;
+extern "C" int mio_fused_mlp_fwd_bw(const void* x, const void* w1b, const void* b1, const void* w2b, const void* b2,
+                                    const void* residual, void* y, void* workspace, int64_t M, int32_t d, int32_t I,
+                                    int32_t act, int32_t dtype, int32_t x_blocked, void* stream) {
+  return fused_mlp_impl(x, w1b, b1, nullptr, nullptr, w2b, b2, residual, y, workspace, M, d, I, act, dtype, stream, 1,
+                        x_blocked ? 1 : 0);
 }
 
+extern "C" int mio_fused_mlp_glu_fwd_bw(const void* x, const void* wgu_b, const void* b_up, const void* b_gate, const void* w2b,
+                                        const void* b2, const void* residual, void* y, void* workspace, int64_t M, int32_t d,
+                                        int32_t I, int32_t dtype, int32_t x_blocked, void* stream) {
+  MIO_CHECK(mio_aligned16(b_gate), "mio_fused_mlp_glu_fwd_bw: pointers must be 16-byte aligned");
+  MIO_CHECK(M == 0 || mlp_blocked_ok(M, d, I),
+            "mio_fused_mlp_glu_fwd_bw: this shape does not take the 256-tile kernels (mio_fused_mlp_blocked_weight_ok(.., SWIGLU) == 0); "
+            "pass the plain weights to mio_fused_mlp_fwd");
+  return fused_mlp_impl(x, wgu_b, b_up, nullptr, b_gate, w2b, b2, residual, y, workspace, M, d, I, MIO_ACT_SWIGLU, dtype, stream, 1,
+                        x_blocked ? 1 : 0);
+}
+
+// ---- blocked weights -----------------------------------------------------------------------------------------------
 extern "C" size_t mio_weight_blocked_bytes(int32_t N, int32_t K) {
   return (size_t)((N + 255) / 256 * 256) * (size_t)K * 2;
 }
@@ -162,81 +333,6 @@ extern "C" int mio_weight_block(const void* w, int64_t ldw, void* wb, int32_t N,
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mio_fail(std::string("mio_weight_block launch: ") + hipGetErrorString(e));
   return 0;
-}
-
-extern "C" int32_t mio_gemm_blocked_weight_ok(int64_t M, int32_t N, int32_t K, int32_t act) {
-  return gemm_blocked_w_ok(M, N, K, act) ? 1 : 0;
-}
-
-extern "C" int mio_gemm_bias_act_bw(const void* x, const void* wb, const void* bias, const void* residual, void* y,
-                                    int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldy, int64_t ldr, int32_t act,
-                                    int32_t dtype, int32_t x_blocked, void* stream) {
-  MIO_CHECK(x && wb && y, "mio_gemm_bias_act_bw: x, wb, y must be non-null");
-  MIO_CHECK(M >= 0 && N > 0 && K > 0, "mio_gemm_bias_act_bw: bad sizes");
-  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_gemm_bias_act_bw: dtype must be bf16 or fp16");
-  MIO_CHECK(act >= MIO_ACT_NONE && act < MIO_ACT_SWIGLU, "mio_gemm_bias_act_bw: unknown / unsupported activation");
-  if (x_blocked) ldx = K;  // blocked x: ceil(M / 256) * 256 x K elements, no row stride
-  MIO_CHECK(N % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && (residual == nullptr || ldr % 8 == 0) && ldx >= K && ldy >= N,
-            "mio_gemm_bias_act_bw: bad strides");
-  MIO_CHECK(mio_aligned16(x) && mio_aligned16(wb) && mio_aligned16(y) && mio_aligned16(residual) && mio_aligned16(bias),
-            "mio_gemm_bias_act_bw: pointers must be 16-byte aligned");
-  MIO_CHECK(ldx * 512 < (int64_t)0x7fffffff && ldy * 512 < (int64_t)0x7fffffff && (residual == nullptr || ldr * 512 < (int64_t)0x7fffffff),
-            "mio_gemm_bias_act_bw: row stride too large for the blocked-weight kernels");
-  MIO_CHECK(gemm_blocked_w_ok(M, N, K, act), "mio_gemm_bias_act_bw: this shape does not take the blocked-weight kernels "
-                                             "(mio_gemm_blocked_weight_ok == 0); use mio_gemm_bias_act with the plain weight");
-  GemmDev p;
-  gemm_dev_defaults(p);
-  p.x = x; p.w = wb; p.wg = nullptr; p.bias = bias; p.bias_g = nullptr; p.res = residual; p.y = y;
-  p.M = M; p.ldx = ldx; p.ldw = K; p.ldy = ldy; p.ldr = ldr; p.N = N; p.K = K;
-  p.tiles_m = p.tiles_n = 0;
-  p.x_blk = x_blocked ? 1 : 0; p.y_blk = 0; p.w_blk = 1;
-  p.dbg = nullptr;
-  p.cs_lo = p.cs_hi = 0; p.cs_val = 1.f; p.group_m = 0;
-  return gemm_dispatch(p, act, dtype, (hipStream_t)stream);
-}
-
-// column scale: the launch must end in the persistent kernel (gemm_inst.hip launch_act): blocked weight shape, no residual,
-// K >= 256, K % 64 == 0
-extern "C" int32_t mio_gemm_col_scale_ok(int64_t M, int32_t N, int32_t K, int32_t act) {
-  return (gemm_blocked_w_ok(M, N, K, act) && K >= 256 && K % 64 == 0 && N % 8 == 0) ? 1 : 0;
-}
-
-extern "C" int mio_gemm_bias_act_bw_cs(const void* x, const void* wb, const void* bias, void* y, int64_t M, int32_t N,
-                                       int32_t K, int64_t ldx, int64_t ldy, int32_t act, int32_t dtype, int32_t x_blocked,
-                                       int32_t cs_lo, int32_t cs_hi, float cs_val, void* stream) {
-  MIO_CHECK(x && wb && y, "mio_gemm_bias_act_bw_cs: x, wb, y must be non-null");
-  MIO_CHECK(M >= 0 && N > 0 && K > 0, "mio_gemm_bias_act_bw_cs: bad sizes");
-  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_gemm_bias_act_bw_cs: dtype must be bf16 or fp16");
-  MIO_CHECK(act >= MIO_ACT_NONE && act < MIO_ACT_SWIGLU, "mio_gemm_bias_act_bw_cs: unknown / unsupported activation");
-  if (x_blocked) ldx = K;
-  MIO_CHECK(ldx % 8 == 0 && ldy % 8 == 0 && ldx >= K && ldy >= N, "mio_gemm_bias_act_bw_cs: bad strides");
-  MIO_CHECK(mio_aligned16(x) && mio_aligned16(wb) && mio_aligned16(y) && mio_aligned16(bias),
-            "mio_gemm_bias_act_bw_cs: pointers must be 16-byte aligned");
-  MIO_CHECK(ldx * 512 < (int64_t)0x7fffffff && ldy * 512 < (int64_t)0x7fffffff, "mio_gemm_bias_act_bw_cs: row stride too large");
-  MIO_CHECK(mio_gemm_col_scale_ok(M, N, K, act), "mio_gemm_bias_act_bw_cs: this shape does not run the persistent kernel "
-                                                 "(mio_gemm_col_scale_ok == 0)");
-  MIO_CHECK(cs_lo >= 0 && cs_hi <= N && cs_lo % 128 == 0 && cs_hi % 128 == 0 && cs_lo <= cs_hi,
-            "mio_gemm_bias_act_bw_cs: [cs_lo, cs_hi) must be multiples of 128 inside [0, N]");
-  GemmDev p;
-  gemm_dev_defaults(p);
-  p.x = x; p.w = wb; p.wg = nullptr; p.bias = bias; p.bias_g = nullptr; p.res = nullptr; p.y = y;
-  p.M = M; p.ldx = ldx; p.ldw = K; p.ldy = ldy; p.ldr = 0; p.N = N; p.K = K;
-  p.tiles_m = p.tiles_n = 0;
-  p.x_blk = x_blocked ? 1 : 0; p.y_blk = 0; p.w_blk = 1;
-  p.dbg = nullptr;
-  p.cs_lo = cs_lo; p.cs_hi = cs_hi; p.cs_val = cs_val; p.group_m = 0;
-  return gemm_dispatch(p, act, dtype, (hipStream_t)stream);
-}
-
-extern "C" int32_t mio_fused_mlp_blocked_weight_ok(int64_t M, int32_t d, int32_t I, int32_t act) {
-  return (M > 0 && mlp_blocked_ok(M, d, I, act, false)) ? 1 : 0;
-}
-
-extern "C" int mio_fused_mlp_fwd_bw(const void* x, const void* w1b, const void* b1, const void* w2b, const void* b2,
-                                    const void* residual, void* y, void* workspace, int64_t M, int32_t d, int32_t I,
-                                    int32_t act, int32_t dtype, int32_t x_blocked, void* stream) {
-  return fused_mlp_impl(x, w1b, b1, nullptr, nullptr, w2b, b2, residual, y, workspace, M, d, I, act, dtype, stream, 1,
-                        x_blocked ? 1 : 0);
 }
 
 // ---- SwiGLU on the 256-tile kernel: gate / up weights interleaved per wave in one blocked weight ----------------------
@@ -275,17 +371,6 @@ extern "C" int mio_weight_block_glu(const void* w_gate, const void* w_up, int64_
   return 0;
 }
 
-extern "C" int mio_fused_mlp_glu_fwd_bw(const void* x, const void* wgu_b, const void* b_up, const void* b_gate, const void* w2b,
-                                        const void* b2, const void* residual, void* y, void* workspace, int64_t M, int32_t d,
-                                        int32_t I, int32_t dtype, int32_t x_blocked, void* stream) {
-  MIO_CHECK(mio_aligned16(b_gate), "mio_fused_mlp_glu_fwd_bw: pointers must be 16-byte aligned");
-  MIO_CHECK(M == 0 || mlp_blocked_ok(M, d, I, MIO_ACT_SWIGLU, false),
-            "mio_fused_mlp_glu_fwd_bw: this shape does not take the 256-tile kernels (mio_fused_mlp_blocked_weight_ok(.., SWIGLU) == 0); "
-            "pass the plain weights to mio_fused_mlp_fwd");
-  return fused_mlp_impl(x, wgu_b, b_up, nullptr, b_gate, w2b, b2, residual, y, workspace, M, d, I, MIO_ACT_SWIGLU, dtype, stream, 1,
-                        x_blocked ? 1 : 0);
-}
-
 // ---- LayerNorm folded into the GEMMs on either side of it ------------------------------------------------
 // Reference: kernels/triton/fused_layernorm_qkv.py:37-420 (LayerNorm as the prologue of the QKV projection) and
 // layernorm_kernels.py:35-188 (residual add + LayerNorm in one pass).  Here neither a prologue nor a pass: the GEMM that
@@ -297,23 +382,6 @@ extern "C" size_t mio_ln_stats_bytes(int64_t M, int32_t width) {
   return (size_t)((width + 255) / 256) * (size_t)((M + 255) / 256 * 256) * 2 * sizeof(float);
 }
 
-// the longest weight rows mio_ln_fold_weight prepares (ln_fold_weight_kernel: 256 threads x 32 elements), so the widest stream a
-// consumer (fold_in) takes
-constexpr int32_t GEMM_LN_FOLD_K_MAX = 8192;
-
-extern "C" int32_t mio_gemm_ln_ok(int64_t M, int32_t N, int32_t K, int32_t act, int32_t fold_in, int32_t stats_out) {
-  if (mio_gemm_impl() != 0) return 0;
-  if (fold_in && K > GEMM_LN_FOLD_K_MAX) return 0;
-  if (act == MIO_ACT_SWIGLU) {  // the gated stage (interleaved gate / up blocked weight, 256 x 128 output tiles): consumer form only
-    const bool big = ((M + 255) / 256) * (int64_t)((N + 127) / 128) >= 256;
-    return (big && !stats_out && N % 128 == 0 && K >= 128 && (int64_t)K * 512 < 0x7fffffff && (int64_t)N * 512 < 0x7fffffff &&
-            (!fold_in || K % 256 == 0) && K % 32 == 0) ? 1 : 0;
-  }
-  if (!gemm_blocked_w_ok(M, N, K, act) || N % 32 != 0) return 0;
-  if (fold_in && (K % 256 != 0 || (act != MIO_ACT_NONE && act != MIO_ACT_GELU_TANH))) return 0;
-  if (stats_out && (N % 256 != 0 || act != MIO_ACT_NONE || fold_in)) return 0;
-  return 1;
-}
 
 // one workgroup per weight row: w_scaled[n][k] = T(w[n][k] * gamma[k] - mean_k(w[n][.] * gamma[.])) (the row mean is taken over
 // the unrounded products), bias_out[n] = T(bias[n] + sum_k w[n][k] * beta[k]).
@@ -468,83 +536,4 @@ extern "C" int mio_ln_stats_reduce(const float* stats_in, int32_t slots_in, floa
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mio_fail(std::string("mio_ln_stats_reduce launch: ") + hipGetErrorString(e));
   return 0;
-}
-
-extern "C" int mio_gemm_ln_bw(const void* x, const void* wb, const void* bias, const void* bias_gate, const void* residual, void* y, int64_t M, int32_t N,
-                              int32_t K, int64_t ldx, int64_t ldy, int64_t ldr, int32_t act, int32_t dtype, int32_t flags,
-                              const float* ln_stats, int32_t ln_slots, float ln_eps, float* stats_out, int32_t cs_lo, int32_t cs_hi,
-                              float cs_val, void* stream) {
-  const bool xb = (flags & MIO_GEMM_X_BLOCKED) != 0, yb = (flags & MIO_GEMM_Y_BLOCKED) != 0, rb = (flags & MIO_GEMM_RES_BLOCKED) != 0;
-  MIO_CHECK(x && wb && y, "mio_gemm_ln_bw: x, wb, y must be non-null");
-  MIO_CHECK(M >= 0 && N > 0 && K > 0, "mio_gemm_ln_bw: bad sizes");
-  if (M == 0) return 0;
-  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_gemm_ln_bw: dtype must be bf16 or fp16");
-  MIO_CHECK(act >= MIO_ACT_NONE && act <= MIO_ACT_SWIGLU, "mio_gemm_ln_bw: unknown activation");
-  MIO_CHECK((flags & ~7) == 0, "mio_gemm_ln_bw: unknown flag");
-  MIO_CHECK(act == MIO_ACT_SWIGLU || bias_gate == nullptr, "mio_gemm_ln_bw: bias_gate belongs to the gated stage (act == SWIGLU)");
-  MIO_CHECK(act != MIO_ACT_SWIGLU || residual == nullptr, "mio_gemm_ln_bw: the gated stage takes no residual");
-  MIO_CHECK(mio_aligned16(bias_gate), "mio_gemm_ln_bw: pointers must be 16-byte aligned");
-  MIO_CHECK(mio_gemm_ln_ok(M, N, K, act, ln_stats != nullptr, stats_out != nullptr),
-            "mio_gemm_ln_bw: this shape / activation does not take the folded kernels (mio_gemm_ln_ok == 0)");
-  MIO_CHECK(ln_stats == nullptr || residual == nullptr, "mio_gemm_ln_bw: the consumer form takes no residual");
-  if (ln_stats != nullptr && ln_slots == 0) ln_slots = K / 256;
-  MIO_CHECK(ln_stats == nullptr || (ln_slots >= 1 && ln_slots <= GEMM_LN_SLOTS_MAX),
-            "mio_gemm_ln_bw: at most 8 statistic slots (rows wider than 2048 columns: mio_ln_stats_reduce first)");
-  MIO_CHECK(stats_out == nullptr || residual != nullptr, "mio_gemm_ln_bw: the producer form is the residual epilogue");
-  MIO_CHECK(!rb || residual != nullptr, "mio_gemm_ln_bw: RES_BLOCKED without a residual");
-  if (xb) ldx = K;
-  if (yb) ldy = N;
-  if (rb) ldr = N;
-  MIO_CHECK(ldx % 8 == 0 && ldy % 8 == 0 && (residual == nullptr || ldr % 8 == 0) && ldx >= K && ldy >= N &&
-                (residual == nullptr || ldr >= N),
-            "mio_gemm_ln_bw: bad strides");
-  MIO_CHECK(ldx * 512 < (int64_t)0x7fffffff && ldy * 512 < (int64_t)0x7fffffff && (residual == nullptr || ldr * 512 < (int64_t)0x7fffffff),
-            "mio_gemm_ln_bw: row stride too large");
-  MIO_CHECK(mio_aligned16(x) && mio_aligned16(wb) && mio_aligned16(y) && mio_aligned16(residual) && mio_aligned16(bias) &&
-                mio_aligned16(ln_stats) && mio_aligned16(stats_out),
-            "mio_gemm_ln_bw: pointers must be 16-byte aligned");
-  MIO_CHECK(cs_lo >= cs_hi || (residual == nullptr && cs_lo >= 0 && cs_hi <= N && cs_lo % 128 == 0 && cs_hi % 128 == 0),
-            "mio_gemm_ln_bw: [cs_lo, cs_hi) must be multiples of 128 inside [0, N], without a residual");
-  GemmDev p;
-  gemm_dev_defaults(p);
-  p.x = x; p.w = wb; p.bias = bias; p.bias_g = bias_gate; p.res = residual; p.y = y;
-  p.M = M; p.ldx = ldx; p.ldw = K; p.ldy = ldy; p.ldr = ldr; p.N = N; p.K = K;
-  p.x_blk = xb ? 1 : 0; p.y_blk = yb ? 1 : 0; p.w_blk = (act == MIO_ACT_SWIGLU) ? 2 : 1; p.res_blk = rb ? 1 : 0;
-  p.cs_lo = cs_lo; p.cs_hi = cs_hi; p.cs_val = cs_val;
-  p.ln_stats = ln_stats; p.ln_eps = ln_eps; p.ln_slots = ln_stats ? ln_slots : 0;
-  p.stats_out = stats_out;
-  return gemm_dispatch(p, act, dtype, (hipStream_t)stream);
-}
-
-// ---- route query ------------------------------------------------------------------------------------------------------
-extern "C" int32_t mio_gemm_route(int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
-                                  int32_t has_residual, int32_t w_layout, int32_t fold_in, int32_t stats_out) {
-  MIO_CHECK(M >= 0 && N > 0 && K > 0, "mio_gemm_route: bad sizes");
-  MIO_CHECK(act >= MIO_ACT_NONE && act <= MIO_ACT_SWIGLU, "mio_gemm_route: unknown activation");
-  MIO_CHECK(w_layout >= 0 && w_layout <= 2, "mio_gemm_route: w_layout must be 0 (row-major), 1 (blocked) or 2 (gate / up interleaved)");
-  MIO_CHECK((w_layout == 2) == (act == MIO_ACT_SWIGLU) || w_layout == 0,
-            "mio_gemm_route: the interleaved weight belongs to act == SWIGLU, and SWIGLU has no plain blocked weight");
-  MIO_CHECK(K % 8 == 0 && N % 8 == 0, "mio_gemm_route: N and K must be multiples of 8");
-  MIO_CHECK(ldx % 8 == 0 && ldw % 8 == 0 && ldy % 8 == 0 && (!has_residual || ldr % 8 == 0) && ldx >= K && ldw >= K && ldy >= N,
-            "mio_gemm_route: bad strides");
-  MIO_CHECK(w_layout != 0 || (!fold_in && !stats_out), "mio_gemm_route: the LayerNorm forms take a blocked weight");
-  if (M == 0) return MIO_GEMM_ROUTE_EMPTY;
-  if (w_layout != 0) {
-    MIO_CHECK(ldx * 512 < (int64_t)0x7fffffff && ldy * 512 < (int64_t)0x7fffffff && (!has_residual || ldr * 512 < (int64_t)0x7fffffff),
-              "mio_gemm_route: row stride too large for the blocked-weight kernels");
-    if (fold_in || stats_out || act == MIO_ACT_SWIGLU) {
-      MIO_CHECK(mio_gemm_ln_ok(M, N, K, act, fold_in, stats_out),
-                "mio_gemm_route: this shape / activation does not take the folded kernels (mio_gemm_ln_ok == 0)");
-      MIO_CHECK(!(fold_in || act == MIO_ACT_SWIGLU) || !has_residual, "mio_gemm_route: the consumer and gated forms take no residual");
-      MIO_CHECK(!stats_out || has_residual, "mio_gemm_route: the producer form is the residual epilogue");
-    } else {
-      MIO_CHECK(gemm_blocked_w_ok(M, N, K, act), "mio_gemm_route: this shape does not take the blocked-weight kernels "
-                                                 "(mio_gemm_blocked_weight_ok == 0)");
-    }
-  }
-  GemmRouteArgs ra;
-  ra.M = M; ra.ldx = ldx; ra.ldw = w_layout != 0 ? K : ldw; ra.ldy = ldy; ra.ldr = ldr;
-  ra.N = N; ra.K = K; ra.act = act;
-  ra.res = has_residual != 0; ra.w_blk = w_layout; ra.ln_stats = fold_in != 0; ra.stats_out = stats_out != 0;
-  return gemm_pick_route(ra);
 }

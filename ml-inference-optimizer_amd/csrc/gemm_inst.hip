@@ -5,7 +5,6 @@
 #include <string>
 
 #include "gemm8w_kernel.h"
-#include "gemm_route.h"
 
 #if GEMM_TYPE_ID == 0
 using GT = __bf16;
@@ -67,18 +66,10 @@ static int launch_8w_res(const GemmDev& p, hipStream_t stream, bool one_tile = f
   return launch_8w<ACT, false, VAR>(p, stream, one_tile);
 }
 
-#ifdef MIO_DIAG
-static int gemm_impl() { return mio_gemm_impl(); }  // MIO_GEMM_IMPL (gemm_api.hip)
-#endif
-
+// `route`: the kernel gemm_plan (gemm_api.hip) chose with gemm_pick_route, the same answer mio_gemm_route reports.  The
+// diagnostic build's overrides (mio_gemm_impl: MIO_GEMM_IMPL, mio_dbg_set(4, .)) replace it here by a variant of that route.
 template <int ACT>
-static int launch_act(const GemmDev& p, hipStream_t stream) {
-  // the kernel is named by gemm_pick_route (gemm_route.h), the same rule mio_gemm_route reports
-  GemmRouteArgs ra;
-  ra.M = p.M; ra.ldx = p.ldx; ra.ldw = p.ldw; ra.ldy = p.ldy; ra.ldr = p.ldr;
-  ra.N = p.N; ra.K = p.K; ra.act = ACT;
-  ra.res = p.res != nullptr; ra.w_blk = p.w_blk; ra.ln_stats = p.ln_stats != nullptr; ra.stats_out = p.stats_out != nullptr;
-  const int route = gemm_pick_route(ra);
+static int launch_act(const GemmDev& p, int route, hipStream_t stream) {
   if constexpr (ACT == MIO_ACT_SWIGLU) {
     switch (route) {
       case MIO_GEMM_ROUTE_P8W_GLU_FOLD: return launch_8w<ACT, false, 0, 1>(p, stream);  // LayerNorm applied in the read-out
@@ -89,7 +80,7 @@ static int launch_act(const GemmDev& p, hipStream_t stream) {
   } else {
 #ifdef MIO_DIAG
     // A/B: the generic 256x256 kernel in place of the persistent one
-    if (gemm_impl() == 1 && route != MIO_GEMM_ROUTE_T128) return launch_cfg<256, 256, 2, 4, ACT>(p, stream);
+    if (mio_gemm_impl() == 1 && route != MIO_GEMM_ROUTE_T128) return launch_cfg<256, 256, 2, 4, ACT>(p, stream);
 #endif
     switch (route) {
       case MIO_GEMM_ROUTE_T128: return launch_cfg<128, 128, 2, 2, ACT>(p, stream);
@@ -104,16 +95,16 @@ static int launch_act(const GemmDev& p, hipStream_t stream) {
       case MIO_GEMM_ROUTE_P8W_RES:
 #ifdef MIO_DIAG
         if constexpr (ACT == MIO_ACT_NONE) {
-          if (gemm_impl() == 8 && p.dbg != nullptr) return launch_8w<ACT, false, 128>(p, stream);  // stamps
-          if (gemm_impl() == 24) return launch_8w_res<ACT, 2048>(p, stream);
-          if (gemm_impl() == 10) return launch_8w_res<ACT, 4>(p, stream);
-          if (gemm_impl() == 13) return launch_8w_res<ACT, 16>(p, stream);
-          if (gemm_impl() == 16) return launch_8w_res<ACT, 64>(p, stream);
+          if (mio_gemm_impl() == 8 && p.dbg != nullptr) return launch_8w<ACT, false, 128>(p, stream);  // stamps
+          if (mio_gemm_impl() == 24) return launch_8w_res<ACT, 2048>(p, stream);
+          if (mio_gemm_impl() == 10) return launch_8w_res<ACT, 4>(p, stream);
+          if (mio_gemm_impl() == 13) return launch_8w_res<ACT, 16>(p, stream);
+          if (mio_gemm_impl() == 16) return launch_8w_res<ACT, 64>(p, stream);
         }
         if constexpr (ACT == MIO_ACT_GELU_TANH) {
-          if (gemm_impl() == 20) return launch_8w<ACT, false, 256>(p, stream);  // scalar activation math
+          if (mio_gemm_impl() == 20) return launch_8w<ACT, false, 256>(p, stream);  // scalar activation math
         }
-        if (gemm_impl() == 9) return launch_8w_res<ACT>(p, stream, true);  // one workgroup per tile
+        if (mio_gemm_impl() == 9) return launch_8w_res<ACT>(p, stream, true);  // one workgroup per tile
 #endif
         return launch_8w_res<ACT>(p, stream);
     }
@@ -122,7 +113,7 @@ static int launch_act(const GemmDev& p, hipStream_t stream) {
 }
 
 template <>
-int gemm_launch<GT>(GemmDev p, int act, hipStream_t stream) {
+int gemm_launch<GT>(GemmDev p, int act, int route, hipStream_t stream) {
 #ifdef MIO_DIAG
   static const char* dbg_ptr = std::getenv("MIO_GEMM_DBG_PTR");
   if (dbg_ptr != nullptr) p.dbg = (unsigned long long*)std::strtoull(dbg_ptr, nullptr, 0);
@@ -131,12 +122,12 @@ int gemm_launch<GT>(GemmDev p, int act, hipStream_t stream) {
   if (mio_dbg_get(5) > 0) p.group_m = mio_dbg_get(5);
 #endif
   switch (act) {
-    case MIO_ACT_NONE: return launch_act<MIO_ACT_NONE>(p, stream);
-    case MIO_ACT_GELU_TANH: return launch_act<MIO_ACT_GELU_TANH>(p, stream);
-    case MIO_ACT_GELU_ERF: return launch_act<MIO_ACT_GELU_ERF>(p, stream);
-    case MIO_ACT_RELU: return launch_act<MIO_ACT_RELU>(p, stream);
-    case MIO_ACT_SILU: return launch_act<MIO_ACT_SILU>(p, stream);
-    case MIO_ACT_SWIGLU: return launch_act<MIO_ACT_SWIGLU>(p, stream);
+    case MIO_ACT_NONE: return launch_act<MIO_ACT_NONE>(p, route, stream);
+    case MIO_ACT_GELU_TANH: return launch_act<MIO_ACT_GELU_TANH>(p, route, stream);
+    case MIO_ACT_GELU_ERF: return launch_act<MIO_ACT_GELU_ERF>(p, route, stream);
+    case MIO_ACT_RELU: return launch_act<MIO_ACT_RELU>(p, route, stream);
+    case MIO_ACT_SILU: return launch_act<MIO_ACT_SILU>(p, route, stream);
+    case MIO_ACT_SWIGLU: return launch_act<MIO_ACT_SWIGLU>(p, route, stream);
   }
   return mio_fail("gemm: unknown activation");
 }

@@ -337,4 +337,4 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_bias_act_kernel(const GemmDe
 
 // Host launcher for one dtype; defined per translation unit (gemm_inst.hip).
 template <typename T>
-int gemm_launch(GemmDev p, int act, hipStream_t stream);
+int gemm_launch(GemmDev p, int act, int route, hipStream_t stream);

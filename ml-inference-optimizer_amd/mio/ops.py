@@ -582,17 +582,41 @@ def col_scale_ok(M: int, N: int, K: int, activation: str = "none") -> bool:
     return not _NO_BLOCKED_W and bool(lib.mio_gemm_col_scale_ok(M, N, K, _ACT.get(activation, _lib.ACT_NONE)))
 
 
-def _bw_ok(M: int, N: int, K: int, act: int, ldx: int, w_blocked) -> bool:
-    """gemm_bias_act with a row-major x: True iff it calls the blocked-weight entry point (else the plain one)."""
-    return w_blocked is not None and act != _lib.ACT_SWIGLU and bool(lib.mio_gemm_blocked_weight_ok(M, N, K, act)) and \
-        ldx * 512 < 0x7fffffff
-
-
 def _gemm_route(M, N, K, ldx, ldw, ldy, ldr, act, residual: bool, w_layout, fold_in=False, stats_out=False) -> str:
     r = lib.mio_gemm_route(M, N, K, ldx, ldw, ldy, ldr, act, int(residual), w_layout, int(fold_in), int(stats_out))
     if r < 0:
         raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
     return _lib.GEMM_ROUTES[r]
+
+
+def _gemm_args(x, w, act, residual=None, out=None, w_blocked=None, x_blocked_shape=None, col_scale=None, **_):
+    """A gemm_bias_act call as the launch and gemm_route both read it: (entry, M, N, K, lead, x2, ldx, w2, ldw, ldy, r2, ldr).
+    entry names the C entry point: "cs" (mio_gemm_bias_act_bw_cs), "bw" (mio_gemm_bias_act_bw) or "plain" (mio_gemm_bias_act);
+    lead is the output's leading shape, x2 / w2 / r2 the operands as 2-D views whose rows the kernels take (copies only where
+    _rows16 must make one).  Host-only: shapes and strides, no data, no allocation, so tensors may live on any device."""
+    K, N = x.shape[-1], w.shape[0]
+    if x_blocked_shape is not None:
+        # x is layernorm(..., out_blocked=True) of a tensor of shape x_blocked_shape: blocked activation layout
+        lead, x2, ldx = tuple(x_blocked_shape[:-1]), x, K
+    else:
+        lead, x2 = tuple(x.shape[:-1]), _rows16(x.reshape(-1, K))
+        ldx = x2.stride(0)
+    M = int(math.prod(lead))
+    if residual is not None and residual.numel() != M * N:
+        raise ValueError(f"residual has {residual.numel()} elements, the output has {M * N}")
+    r2 = None if residual is None else _rows16(residual.reshape(-1, N))
+    ldr = 0 if r2 is None else r2.stride(0)
+    ldy = N if out is None else out.view(-1, N).stride(0)
+    if col_scale is not None:
+        entry = "cs"
+    elif x_blocked_shape is not None:
+        entry = "bw"
+    else:  # a row-major x takes the blocked weight where mio_gemm_bias_act_bw takes the call (mio_gemm_route refuses it otherwise)
+        bw = w_blocked is not None and M > 0 and \
+            lib.mio_gemm_route(M, N, K, ldx, K, ldy, ldr, act, int(r2 is not None), _lib.W_BLOCKED, 0, 0) >= 0
+        entry = "bw" if bw else "plain"
+    w2 = _rows16(w) if entry == "plain" else w_blocked  # (a blocked weight counts with its row length K)
+    return entry, M, N, K, lead, x2, ldx, w2, w2.stride(0) if entry == "plain" else K, ldy, r2, ldr
 
 
 def gemm_route(x, w, bias=None, activation: str = "none", **kwargs) -> str:
@@ -604,31 +628,15 @@ def gemm_route(x, w, bias=None, activation: str = "none", **kwargs) -> str:
     act = _ACT[activation]
     if "M" in kwargs:  # gemm_ln
         M, N, K = int(kwargs["M"]), int(kwargs["N"]), int(kwargs["K"])
-        ldx = K if kwargs.get("x_blocked") else _rows16(x.reshape(-1, K)).stride(0)
-        residual = kwargs.get("residual")
-        ldr = 0
-        if residual is not None:
-            ldr = N if kwargs.get("res_blocked") else _rows16(residual.reshape(-1, N)).stride(0)
-        return _gemm_route(M, N, K, ldx, K, N, ldr, act, residual is not None,
+        _x2, ldx, r2, ldr = _gemm_ln_args(x, **kwargs)
+        return _gemm_route(M, N, K, ldx, K, N, ldr, act, r2 is not None,
                            _lib.W_GLU if act == _lib.ACT_SWIGLU else _lib.W_BLOCKED,
                            kwargs.get("ln_stats") is not None, bool(kwargs.get("stats_out", False)))
     unknown = set(kwargs) - {"w_gate", "bias_gate", "residual", "out", "w_blocked", "x_blocked_shape", "col_scale"}
     if unknown:
         raise TypeError(f"gemm_route: unexpected arguments {sorted(unknown)}")
-    K, N = x.shape[-1], w.shape[0]
-    out, residual, w_blocked = kwargs.get("out"), kwargs.get("residual"), kwargs.get("w_blocked")
-    xbs = kwargs.get("x_blocked_shape")
-    ldy = N if out is None else out.view(-1, N).stride(0)
-    ldr = 0 if residual is None else _rows16(residual.reshape(-1, N)).stride(0)
-    if xbs is not None or kwargs.get("col_scale") is not None:
-        M = int(math.prod(xbs[:-1])) if xbs is not None else x.numel() // K
-        ldx = K if xbs is not None else _rows16(x.reshape(-1, K)).stride(0)
-        return _gemm_route(M, N, K, ldx, K, ldy, ldr, act, residual is not None, _lib.W_BLOCKED)
-    x2 = _rows16(x.reshape(-1, K))
-    M = x2.shape[0]
-    if _bw_ok(M, N, K, act, x2.stride(0), w_blocked):
-        return _gemm_route(M, N, K, x2.stride(0), K, ldy, ldr, act, residual is not None, _lib.W_BLOCKED)
-    return _gemm_route(M, N, K, x2.stride(0), _rows16(w).stride(0), ldy, ldr, act, residual is not None, _lib.W_PLAIN)
+    entry, M, N, K, _lead, _x2, ldx, _w2, ldw, ldy, r2, ldr = _gemm_args(x, w, act, **kwargs)
+    return _gemm_route(M, N, K, ldx, ldw, ldy, ldr, act, r2 is not None, _lib.W_PLAIN if entry == "plain" else _lib.W_BLOCKED)
 
 
 def gemm_bias_act(x, w, bias=None, activation: str = "none", w_gate=None, bias_gate=None, residual=None, out=None,
@@ -643,10 +651,9 @@ def gemm_bias_act(x, w, bias=None, activation: str = "none", w_gate=None, bias_g
     dt = _dtype_id(x)
     if w.dtype != x.dtype:
         raise ValueError("x and w must have the same dtype")
-    K = x.shape[-1]
-    N = w.shape[0]
-    if w.shape[1] != K:
-        raise ValueError(f"weight shape {tuple(w.shape)} does not match input features {K}")
+    if w.shape[1] != x.shape[-1]:
+        raise ValueError(f"weight shape {tuple(w.shape)} does not match input features {x.shape[-1]}")
+    N, K = w.shape
     _vec_ok(bias, N, x.dtype, "bias")
     if act == _lib.ACT_SWIGLU:
         _vec_ok(bias_gate, N, x.dtype, "bias_gate")
@@ -656,62 +663,33 @@ def gemm_bias_act(x, w, bias=None, activation: str = "none", w_gate=None, bias_g
             raise ValueError("w_blocked must have x's dtype and device (repack after converting the module)")
         if w_blocked.numel() != (N + 255) // 256 * 256 * K or not w_blocked.is_contiguous():
             raise ValueError(f"w_blocked has {w_blocked.numel()} elements, expected ceil(N/256)*256*K = {(N + 255) // 256 * 256 * K}")
-    if col_scale is not None:
+    entry, M, N, K, lead, x2, ldx, w2, ldw, _ldy, r2, ldr = _gemm_args(x, w, act, residual, out, w_blocked, x_blocked_shape, col_scale)
+    _res_ok(residual, M * N, x.dtype)
+    if entry == "cs":
         lo, hi, val = int(col_scale[0]), int(col_scale[1]), float(col_scale[2])
-        Mcs = int(math.prod(x_blocked_shape[:-1])) if x_blocked_shape is not None else x.numel() // K
-        if w_blocked is None or residual is not None or not lib.mio_gemm_col_scale_ok(Mcs, N, K, act):
+        if w_blocked is None or residual is not None or not lib.mio_gemm_col_scale_ok(M, N, K, act):
             raise ValueError("col_scale needs a blocked weight, no residual and a shape with col_scale_ok()")
         if lo % 128 or hi % 128 or not (0 <= lo <= hi <= N):
             raise ValueError(f"col_scale range [{lo}, {hi}) must be multiples of 128 inside [0, {N}]")
-        if x_blocked_shape is not None:
-            xs, ldx, xb = x, K, 1
-            lead = tuple(x_blocked_shape[:-1])
-        else:
-            xs = _rows16(x.reshape(-1, K))
-            ldx, xb = xs.stride(0), 0
-            lead = tuple(x.shape[:-1])
-        if out is None:
-            out = torch.empty(*lead, N, dtype=x.dtype, device=x.device)
-        y2 = out.view(-1, N)
-        check(lib.mio_gemm_bias_act_bw_cs(xs.data_ptr(), w_blocked.data_ptr(), _ptr(bias), y2.data_ptr(), Mcs, N, K, ldx,
-                                          y2.stride(0), act, dt, xb, lo, hi, val, _stream()))
-        return out
-    if x_blocked_shape is not None:
-        # x is layernorm(..., out_blocked=True) of a tensor of shape x_blocked_shape: blocked activation layout
-        M = int(math.prod(x_blocked_shape[:-1]))
+    elif x_blocked_shape is not None:
         if w_blocked is None or act == _lib.ACT_SWIGLU or not lib.mio_gemm_blocked_weight_ok(M, N, K, act):
             raise ValueError("a blocked activation operand needs a blocked weight and a shape with blocked_weight_ok()")
-        if out is None:
-            out = torch.empty(*x_blocked_shape[:-1], N, dtype=x.dtype, device=x.device)
-        y2 = out.view(-1, N)
-        _res_ok(residual, M * N, x.dtype)
-        r2 = None if residual is None else _rows16(residual.reshape(-1, N))
-        check(lib.mio_gemm_bias_act_bw(x.data_ptr(), w_blocked.data_ptr(), _ptr(bias), _ptr(r2), y2.data_ptr(), M, N, K,
-                                       K, y2.stride(0), 0 if r2 is None else r2.stride(0), act, dt, 1, _stream()))
-        return out
-    x2 = x.reshape(-1, K)
-    x2, w = _rows16(x2), _rows16(w)
-    M = x2.shape[0]
-    if act == _lib.ACT_SWIGLU:
-        if w_gate is None:
-            raise ValueError("SwiGLU activation requires gate weights")
-        w_gate = _rows16(w_gate)
-    else:
-        w_gate, bias_gate = None, None
+    elif act == _lib.ACT_SWIGLU and w_gate is None:
+        raise ValueError("SwiGLU activation requires gate weights")
     if out is None:
-        out = torch.empty(*x.shape[:-1], N, dtype=x.dtype, device=x.device)
+        out = torch.empty(*lead, N, dtype=x.dtype, device=x.device)
     y2 = out.view(-1, N)
-    r2 = None
-    if residual is not None:
-        _res_ok(residual, M * N, x.dtype)
-        r2 = _rows16(residual.reshape(-1, N))
-    if _bw_ok(M, N, K, act, x2.stride(0), w_blocked):
-        check(lib.mio_gemm_bias_act_bw(x2.data_ptr(), w_blocked.data_ptr(), _ptr(bias), _ptr(r2), y2.data_ptr(), M, N, K,
-                                       x2.stride(0), y2.stride(0), 0 if r2 is None else r2.stride(0), act, dt, 0, _stream()))
-        return out
-    check(lib.mio_gemm_bias_act(x2.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(w_gate), _ptr(bias_gate), _ptr(r2),
-                                y2.data_ptr(), M, N, K, x2.stride(0), w.stride(0), y2.stride(0),
-                                0 if r2 is None else r2.stride(0), act, dt, _stream()))
+    xb = int(x_blocked_shape is not None)
+    if entry == "cs":
+        check(lib.mio_gemm_bias_act_bw_cs(x2.data_ptr(), w2.data_ptr(), _ptr(bias), y2.data_ptr(), M, N, K, ldx, y2.stride(0),
+                                          act, dt, xb, lo, hi, val, _stream()))
+    elif entry == "bw":
+        check(lib.mio_gemm_bias_act_bw(x2.data_ptr(), w2.data_ptr(), _ptr(bias), _ptr(r2), y2.data_ptr(), M, N, K, ldx,
+                                       y2.stride(0), ldr, act, dt, xb, _stream()))
+    else:
+        w_gate, bias_gate = (_rows16(w_gate), bias_gate) if act == _lib.ACT_SWIGLU else (None, None)
+        check(lib.mio_gemm_bias_act(x2.data_ptr(), w2.data_ptr(), _ptr(bias), _ptr(w_gate), _ptr(bias_gate), _ptr(r2),
+                                    y2.data_ptr(), M, N, K, ldx, ldw, y2.stride(0), ldr, act, dt, _stream()))
     return out
 
 
@@ -746,6 +724,25 @@ def ln_stats_shape(M: int, width: int):
     return ((width + 255) // 256, (M + 255) // 256 * 256, 2)
 
 
+def _gemm_ln_args(x, M, N, K, x_blocked=False, residual=None, res_blocked=False, **_):
+    """gemm_ln's x and residual as mio_gemm_ln_bw and mio_gemm_route take them: (x2, ldx, r2, ldr).  Host-only."""
+    M, N, K = int(M), int(N), int(K)
+
+    def _operand(t, cols, blocked, what):
+        if t.dtype != x.dtype or t.device != x.device:
+            raise ValueError(f"{what} must have x's dtype and device")
+        if blocked:
+            if t.numel() != (M + 255) // 256 * 256 * cols or not t.is_contiguous():
+                raise ValueError(f"{what}: a blocked operand has ceil(M/256)*256 x {cols} contiguous elements")
+            return t, cols
+        t2 = _rows16(t.reshape(-1, cols))
+        if t2.shape[0] != M:
+            raise ValueError(f"{what}: expected [{M}, {cols}]")
+        return t2, t2.stride(0)
+
+    return _operand(x, K, x_blocked, "x") + ((None, 0) if residual is None else _operand(residual, N, res_blocked, "residual"))
+
+
 def gemm_ln(x: torch.Tensor, w_blocked: torch.Tensor, bias: Optional[torch.Tensor], *, M: int, N: int, K: int,
             activation: str = "none", x_blocked: bool = False, residual: Optional[torch.Tensor] = None,
             res_blocked: bool = False, out_blocked: bool = False, ln_stats: Optional[torch.Tensor] = None,
@@ -774,26 +771,12 @@ def gemm_ln(x: torch.Tensor, w_blocked: torch.Tensor, bias: Optional[torch.Tenso
     if not lib.mio_gemm_ln_ok(M, N, K, act, int(fold), int(stats_out)):
         raise ValueError("gemm_ln: this shape / activation does not take the folded kernels (gemm_ln_ok)")
     mp = (M + 255) // 256 * 256
-
-    def _operand(t, cols, blocked, what):
-        if t.dtype != x.dtype or t.device != x.device:
-            raise ValueError(f"{what} must have x's dtype and device")
-        if blocked:
-            if t.numel() != mp * cols or not t.is_contiguous():
-                raise ValueError(f"{what}: a blocked operand has ceil(M/256)*256 x {cols} contiguous elements")
-            return t, cols
-        t2 = _rows16(t.reshape(-1, cols))
-        if t2.shape[0] != M:
-            raise ValueError(f"{what}: expected [{M}, {cols}]")
-        return t2, t2.stride(0)
-
-    x2, ldx = _operand(x, K, x_blocked, "x")
+    x2, ldx, r2, ldr = _gemm_ln_args(x, M, N, K, x_blocked, residual, res_blocked)
     wn = (N + 127) // 128 * 256 * K if glu else (N + 255) // 256 * 256 * K
     if w_blocked.dtype != x.dtype or w_blocked.device != x.device or not w_blocked.is_contiguous() or w_blocked.numel() != wn:
         raise ValueError(f"w_blocked: expected {wn} contiguous elements of x's dtype on its device (swiglu: block_weight_glu)")
     _vec_ok(bias, N, x.dtype, "bias")
     _vec_ok(bias_gate, N, x.dtype, "bias_gate")
-    r2, ldr = (None, 0) if residual is None else _operand(residual, N, res_blocked, "residual")
     slots = 0
     if fold:
         want = ln_stats_shape(M, K)
@@ -829,9 +812,19 @@ def _blocked_sizes_ok(fc1_blocked, fc2_blocked, x, d, I, act):
                              f"(swiglu: block_weight_glu(gate, up)); repack after converting the module")
 
 
-def _mlp_bw_entry(M: int, d: int, I: int, act: int, fc1_blocked, fc2_blocked) -> bool:
-    """fused_mlp with a row-major input: True iff it calls the blocked-weight entry points (else mio_fused_mlp_fwd)."""
-    return fc1_blocked is not None and fc2_blocked is not None and bool(lib.mio_fused_mlp_blocked_weight_ok(M, d, I, act))
+def _mlp_args(hidden_states, fc1_weight, act, fc1_blocked=None, fc2_blocked=None, x_blocked_shape=None):
+    """A fused_mlp call as the launch and fused_mlp_route both read it: (shape, M, d, I, bw, blocked).  shape is the logical
+    [..., d] shape of the input (x_blocked_shape: hidden_states is layernorm(..., out_blocked=True) of such a tensor, in the
+    blocked activation layout), bw says that the blocked-weight entry points take the call (else mio_fused_mlp_fwd), and
+    blocked that both stages run on the 256x256-tile kernels: the rule of gemm_api.hip fused_mlp_impl, SwiGLU only with its
+    interleaved blocked weight.  Host-only."""
+    shape = tuple(hidden_states.shape if x_blocked_shape is None else x_blocked_shape)
+    M, d, I = int(math.prod(shape[:-1])), shape[-1], fc1_weight.shape[0]
+    ok = bool(lib.mio_fused_mlp_blocked_weight_ok(M, d, I, act))
+    bw = ok and fc1_blocked is not None and fc2_blocked is not None
+    if x_blocked_shape is not None and not bw:
+        raise ValueError("a blocked activation operand needs blocked weights and fused_mlp_blocked_weight_ok()")
+    return shape, M, d, I, bw, ok and (bw or act != _lib.ACT_SWIGLU)
 
 
 def fused_mlp_route(hidden_states, fc1_weight, fc1_bias=None, fc2_weight=None, fc2_bias=None, activation: str = "gelu",
@@ -843,23 +836,12 @@ def fused_mlp_route(hidden_states, fc1_weight, fc1_bias=None, fc2_weight=None, f
     if activation not in _ACT or _ACT[activation] == _lib.ACT_NONE:
         raise ValueError(f"Unsupported activation function: {activation}")
     act = _ACT[activation]
-    if x_blocked_shape is not None:
-        d, M = x_blocked_shape[-1], int(math.prod(x_blocked_shape[:-1]))
-    else:
-        d, M = hidden_states.shape[-1], hidden_states.numel() // hidden_states.shape[-1]
-    I = fc1_weight.shape[0]
-    has_res = residual is not None
-    wblk = 1 if (x_blocked_shape is not None or _mlp_bw_entry(M, d, I, act, fc1_blocked, fc2_blocked)) else 0
-    # mio_fused_mlp_fwd* (gemm_api.hip fused_mlp_impl): the blocked two-stage form wherever mio_fused_mlp_blocked_weight_ok,
-    # SwiGLU only with its interleaved blocked weight
-    if M > 0 and lib.mio_fused_mlp_blocked_weight_ok(M, d, I, act) and (act != _lib.ACT_SWIGLU or wblk):
-        w1 = _lib.W_GLU if act == _lib.ACT_SWIGLU else wblk
-        return {"path": "blocked",
-                "stage1": _gemm_route(M, I, d, d, d, I, 0, act, False, w1),
-                "stage2": _gemm_route(M, d, I, I, I, d, d, _lib.ACT_NONE, has_res, wblk)}
-    return {"path": "two_launch",
-            "stage1": _gemm_route(M, I, d, d, d, I, 0, act, False, _lib.W_PLAIN),
-            "stage2": _gemm_route(M, d, I, I, I, d, d, _lib.ACT_NONE, has_res, _lib.W_PLAIN)}
+    _shape, M, d, I, bw, blocked = _mlp_args(hidden_states, fc1_weight, act, fc1_blocked, fc2_blocked, x_blocked_shape)
+    w2 = _lib.W_BLOCKED if blocked and bw else _lib.W_PLAIN
+    w1 = _lib.W_GLU if blocked and act == _lib.ACT_SWIGLU else w2
+    return {"path": "blocked" if blocked else "two_launch",
+            "stage1": _gemm_route(M, I, d, d, d, I, 0, act, False, w1),
+            "stage2": _gemm_route(M, d, I, I, I, d, d, _lib.ACT_NONE, residual is not None, w2)}
 
 
 def fused_mlp(
@@ -878,81 +860,52 @@ def fused_mlp(
 ) -> torch.Tensor:
     """Drop-in for triton_fused_mlp (mlp_kernels.py:648-756): fc2(act(fc1(x))), hidden [B,S,d].
     "gelu" is the tanh form like the Triton kernel (:144-161); "gelu_erf" is pytorch_fused_mlp's (:782-783)."""
-    if x_blocked_shape is None and hidden_states.dim() != 3:
+    xb = x_blocked_shape is not None
+    if not xb and hidden_states.dim() != 3:
         raise ValueError(f"Expected 3D input tensor, got shape: {hidden_states.shape}")
     _need_cuda(hidden_states)
     if activation not in _ACT or _ACT[activation] == _lib.ACT_NONE:
         raise ValueError(f"Unsupported activation function: {activation}")
     act = _ACT[activation]
-    if x_blocked_shape is not None:
-        # hidden_states is layernorm(..., out_blocked=True) of a [B,S,d] tensor: blocked activation layout
-        d, I = x_blocked_shape[-1], fc1_weight.shape[0]
-        M = int(math.prod(x_blocked_shape[:-1]))
-        _vec_ok(fc1_bias, I, hidden_states.dtype, "fc1_bias")
-        _vec_ok(fc2_bias, d, hidden_states.dtype, "fc2_bias")
-        _res_ok(residual, M * d, hidden_states.dtype)
-        if fc1_blocked is None or fc2_blocked is None or not lib.mio_fused_mlp_blocked_weight_ok(M, d, I, act):
-            raise ValueError("a blocked activation operand needs blocked weights and fused_mlp_blocked_weight_ok()")
-        _blocked_sizes_ok(fc1_blocked, fc2_blocked, hidden_states, d, I, act)
-        out = torch.empty(*x_blocked_shape, dtype=hidden_states.dtype, device=hidden_states.device)
-        work = torch.empty((M + 255) // 256 * 256, I, dtype=hidden_states.dtype, device=hidden_states.device)
-        r2 = None if residual is None else residual.reshape(-1, d)
-        if r2 is not None and not r2.is_contiguous():
-            r2 = r2.contiguous()
-        if act == _lib.ACT_SWIGLU:
-            _vec_ok(fc1_gate_bias, I, hidden_states.dtype, "fc1_gate_bias")
-            check(lib.mio_fused_mlp_glu_fwd_bw(hidden_states.data_ptr(), fc1_blocked.data_ptr(), _ptr(fc1_bias),
-                                               _ptr(fc1_gate_bias), fc2_blocked.data_ptr(), _ptr(fc2_bias), _ptr(r2),
-                                               out.data_ptr(), work.data_ptr(), M, d, I, _dtype_id(hidden_states), 1, _stream()))
-            return out
-        check(lib.mio_fused_mlp_fwd_bw(hidden_states.data_ptr(), fc1_blocked.data_ptr(), _ptr(fc1_bias),
-                                       fc2_blocked.data_ptr(), _ptr(fc2_bias), _ptr(r2), out.data_ptr(), work.data_ptr(),
-                                       M, d, I, act, _dtype_id(hidden_states), 1, _stream()))
-        return out
-    if act == _lib.ACT_SWIGLU and fc1_gate_weight is None:
+    glu = act == _lib.ACT_SWIGLU
+    if glu and not xb and fc1_gate_weight is None:
         raise ValueError("SwiGLU activation requires gate weights")
-    dt = _dtype_id(hidden_states)
-    d = hidden_states.shape[-1]
-    I = fc1_weight.shape[0]
-    if fc1_weight.shape[1] != d or tuple(fc2_weight.shape) != (d, I):
-        raise ValueError("fc1/fc2 weight shapes do not match hidden size")
-    x2 = _rows16(hidden_states.reshape(-1, d))
-    if x2.stride(0) != d:
-        x2 = x2.contiguous()
-    M = x2.shape[0]
-    _vec_ok(fc1_bias, I, hidden_states.dtype, "fc1_bias")
-    _vec_ok(fc2_bias, d, hidden_states.dtype, "fc2_bias")
-    if act == _lib.ACT_SWIGLU:
-        _vec_ok(fc1_gate_bias, I, hidden_states.dtype, "fc1_gate_bias")
-    _res_ok(residual, M * d, hidden_states.dtype)
-    ws = [fc1_weight, fc2_weight] + ([fc1_gate_weight] if act == _lib.ACT_SWIGLU else [])
-    for w_ in ws:
-        if w_.dtype != hidden_states.dtype or not w_.is_contiguous():
-            raise ValueError("weights must be contiguous and of the input dtype")
-    out = torch.empty_like(hidden_states, memory_format=torch.contiguous_format)
-    # workspace in whole 256-row blocks (mio_fused_mlp_workspace_bytes): the intermediate may use a blocked layout
-    work = torch.empty((M + 255) // 256 * 256, I, dtype=hidden_states.dtype, device=hidden_states.device)
-    r2 = None
-    if residual is not None:
-        r2 = residual.reshape(-1, d)
-        if not r2.is_contiguous():
-            r2 = r2.contiguous()
-    gate_w = fc1_gate_weight if act == _lib.ACT_SWIGLU else None
-    gate_b = fc1_gate_bias if act == _lib.ACT_SWIGLU else None
-    if _mlp_bw_entry(M, d, I, act, fc1_blocked, fc2_blocked):
+    dt, dtype = _dtype_id(hidden_states), hidden_states.dtype
+    shape, M, d, I, bw, _blocked = _mlp_args(hidden_states, fc1_weight, act, fc1_blocked, fc2_blocked, x_blocked_shape)
+    x2 = hidden_states
+    if not xb:
+        if fc1_weight.shape[1] != d or tuple(fc2_weight.shape) != (d, I):
+            raise ValueError("fc1/fc2 weight shapes do not match hidden size")
+        x2 = _rows16(hidden_states.reshape(-1, d))
+        if x2.stride(0) != d:
+            x2 = x2.contiguous()
+    _vec_ok(fc1_bias, I, dtype, "fc1_bias")
+    _vec_ok(fc2_bias, d, dtype, "fc2_bias")
+    gate_w, gate_b = (fc1_gate_weight, fc1_gate_bias) if glu else (None, None)
+    _vec_ok(gate_b, I, dtype, "fc1_gate_bias")
+    _res_ok(residual, M * d, dtype)
+    if not xb:  # (a blocked input comes with blocked weights: the plain ones are not read)
+        for w_ in (fc1_weight, fc2_weight) + ((gate_w,) if glu else ()):
+            if w_.dtype != dtype or not w_.is_contiguous():
+                raise ValueError("weights must be contiguous and of the input dtype")
+    if bw:
         _blocked_sizes_ok(fc1_blocked, fc2_blocked, hidden_states, d, I, act)
-        if act == _lib.ACT_SWIGLU:
-            check(lib.mio_fused_mlp_glu_fwd_bw(x2.data_ptr(), fc1_blocked.data_ptr(), _ptr(fc1_bias), _ptr(gate_b),
-                                               fc2_blocked.data_ptr(), _ptr(fc2_bias), _ptr(r2), out.data_ptr(),
-                                               work.data_ptr(), M, d, I, dt, 0, _stream()))
-            return out
+    out = torch.empty(shape, dtype=dtype, device=hidden_states.device)
+    # workspace in whole 256-row blocks (mio_fused_mlp_workspace_bytes): the intermediate may use a blocked layout
+    work = torch.empty((M + 255) // 256 * 256, I, dtype=dtype, device=hidden_states.device)
+    r2 = None if residual is None else residual.reshape(-1, d)
+    if r2 is not None and not r2.is_contiguous():
+        r2 = r2.contiguous()
+    tail = (_ptr(r2), out.data_ptr(), work.data_ptr(), M, d, I)
+    if bw and glu:
+        check(lib.mio_fused_mlp_glu_fwd_bw(x2.data_ptr(), fc1_blocked.data_ptr(), _ptr(fc1_bias), _ptr(gate_b),
+                                           fc2_blocked.data_ptr(), _ptr(fc2_bias), *tail, dt, int(xb), _stream()))
+    elif bw:
         check(lib.mio_fused_mlp_fwd_bw(x2.data_ptr(), fc1_blocked.data_ptr(), _ptr(fc1_bias), fc2_blocked.data_ptr(),
-                                       _ptr(fc2_bias), _ptr(r2), out.data_ptr(), work.data_ptr(), M, d, I, act, dt,
-                                       0, _stream()))
-        return out
-    check(lib.mio_fused_mlp_fwd(x2.data_ptr(), fc1_weight.data_ptr(), _ptr(fc1_bias), _ptr(gate_w), _ptr(gate_b),
-                                fc2_weight.data_ptr(), _ptr(fc2_bias), _ptr(r2), out.data_ptr(), work.data_ptr(),
-                                M, d, I, act, dt, _stream()))
+                                       _ptr(fc2_bias), *tail, act, dt, int(xb), _stream()))
+    else:
+        check(lib.mio_fused_mlp_fwd(x2.data_ptr(), fc1_weight.data_ptr(), _ptr(fc1_bias), _ptr(gate_w), _ptr(gate_b),
+                                    fc2_weight.data_ptr(), _ptr(fc2_bias), *tail, act, dt, _stream()))
     return out
 
 
