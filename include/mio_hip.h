@@ -521,6 +521,61 @@ int mio_fa3_fwd_paged_kv8(const mio_fa3_paged_params_t* p, const float* k_scale,
 int32_t mio_fa3_paged_kv8_route(const mio_fa3_paged_params_t* p, const float* k_scale, const float* v_scale,
                                 int32_t window_left, int32_t window_right);
 
+/* ------------------------------------------------------------------------------------------
+ * Rotary position embedding (csrc/rope.hip).  The first rot_dim elements of every head are rotated
+ * by the angles of the token's position: y1 = x1 c - x2 s, y2 = x2 c + x1 s, evaluated in fp32 and
+ * rounded once to the stored format.  c / s are read from the caller's tables cos / sin, fp32
+ * DEVICE arrays [max_position, rot_dim / 2] contiguous and 16-byte aligned, never computed by the
+ * kernels (a scaled, YaRN or Llama-3 frequency schedule is the caller's table).  interleaved 0 is
+ * the neox pairing (element i with i + rot_dim / 2), 1 the GPT-J one (element 2i with 2i + 1).
+ * rot_dim is a multiple of 16 in [16, D]; D a multiple of 8 (16 for an fp8 cache) and <= 128; for
+ * an fp8 cache with the neox pairing rot_dim is a multiple of 32.  Elements [rot_dim, D) pass
+ * through unchanged.
+ *
+ * mio_rope_and_cache_varlen: mio_reshape_and_cache_varlen (same packed-token form, same positions,
+ * same skipping rules, V and K's elements past rot_dim written exactly as it writes them) with K
+ * rotated on the way into the cache and the token's H query heads rotated into q_out.  q / q_out
+ * [total_new, H, D] by (token, head) strides each (d stride 1); q_out may be q.  The rotation's
+ * position is the token's cache position context_lengths[b] - n_b + i, or positions[t] where
+ * positions (int32 DEVICE [total_new], may be null) is given; the cache row does not depend on it.
+ * A token outside every sequence's clamped range, or whose rotation position is outside
+ * [0, max_position), writes nothing to the caches and its q_out row is zeros.  A token whose cache
+ * row is skipped (position before the sequence, past the table row, block id outside
+ * [0, num_blocks)) but whose rotation position is valid still gets its q_out row.
+ * mio_rope_and_cache_varlen_kv8: the same into an fp8 (e4m3fn) cache with the layer's scales as in
+ * mio_reshape_and_cache_varlen_kv8: K is e4m3(clamp(rot(k) * (1.0f / k_scale), -448, 448)), one
+ * rounding from fp32; NaN stays NaN.
+ * mio_rope_rows: the standalone form: x [tokens, heads, D] by (token, head) strides rotated at
+ * positions[token] (int32 DEVICE [tokens]) into out (own strides, may be x); a position outside
+ * [0, max_position) writes the row as zeros.
+ * All three: no host sync, graph-capturable; B == 0 / total_new == 0 / tokens == 0 return 0 without
+ * a launch.  Refused before any launch: null pointers (positions of the cache forms excepted), a
+ * pointer off 16-byte alignment, strides negative or not multiples of 8, bad geometry, dtype,
+ * rot_dim, max_position <= 0.
+ * ------------------------------------------------------------------------------------------ */
+int mio_rope_and_cache_varlen(const void* q, void* q_out, const void* key, const void* value, void* k_cache,
+                              void* v_cache, const int32_t* block_tables, const int32_t* cu_seqlens_new,
+                              const int32_t* context_lengths, const int32_t* positions, const float* cos,
+                              const float* sin, const int64_t q_stride[2], const int64_t q_out_stride[2],
+                              const int64_t k_stride[2], const int64_t v_stride[2], /* token, head */
+                              int32_t B, int32_t total_new, int32_t H, int32_t Hkv, int32_t D, int32_t rot_dim,
+                              int32_t max_position, int32_t interleaved, int32_t num_blocks, int32_t num_layers,
+                              int32_t layer_idx, int32_t block_size, int32_t max_blocks_per_seq, int32_t dtype,
+                              void* stream);
+int mio_rope_and_cache_varlen_kv8(const void* q, void* q_out, const void* key, const void* value, void* k_cache,
+                                  void* v_cache, const float* k_scale, const float* v_scale,
+                                  const int32_t* block_tables, const int32_t* cu_seqlens_new,
+                                  const int32_t* context_lengths, const int32_t* positions, const float* cos,
+                                  const float* sin, const int64_t q_stride[2], const int64_t q_out_stride[2],
+                                  const int64_t k_stride[2], const int64_t v_stride[2], int32_t B, int32_t total_new,
+                                  int32_t H, int32_t Hkv, int32_t D, int32_t rot_dim, int32_t max_position,
+                                  int32_t interleaved, int32_t num_blocks, int32_t num_layers, int32_t layer_idx,
+                                  int32_t block_size, int32_t max_blocks_per_seq, int32_t dtype, void* stream);
+int mio_rope_rows(const void* x, void* out, const int32_t* positions, const float* cos, const float* sin,
+                  const int64_t x_stride[2], const int64_t out_stride[2], /* token, head */
+                  int32_t tokens, int32_t heads, int32_t D, int32_t rot_dim, int32_t max_position,
+                  int32_t interleaved, int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

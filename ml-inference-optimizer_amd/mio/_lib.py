@@ -124,6 +124,9 @@ EXPORTS = (
     "mio_fa3_decode_kv8_route",
     "mio_fa3_fwd_paged_kv8",
     "mio_fa3_paged_kv8_route",
+    "mio_rope_and_cache_varlen",
+    "mio_rope_and_cache_varlen_kv8",
+    "mio_rope_rows",
 )
 
 
@@ -336,6 +339,15 @@ def _load() -> C.CDLL:
     lib.mio_fa3_fwd_paged_kv8.restype = i32
     lib.mio_fa3_paged_kv8_route.argtypes = [C.POINTER(FaPagedParams), vp, vp, i32, i32]
     lib.mio_fa3_paged_kv8_route.restype = i32
+    # rotary: q, q_out, key, value, caches, (fp8: the two scales,) block_tables, cu_seqlens_new, context_lengths, positions, cos,
+    # sin, four (token, head) stride pairs, then the sizes
+    p64 = C.POINTER(i64)
+    lib.mio_rope_and_cache_varlen.argtypes = [vp] * 12 + [p64] * 4 + [i32] * 14 + [vp]
+    lib.mio_rope_and_cache_varlen.restype = i32
+    lib.mio_rope_and_cache_varlen_kv8.argtypes = [vp] * 14 + [p64] * 4 + [i32] * 14 + [vp]
+    lib.mio_rope_and_cache_varlen_kv8.restype = i32
+    lib.mio_rope_rows.argtypes = [vp] * 5 + [p64] * 2 + [i32] * 7 + [vp]
+    lib.mio_rope_rows.restype = i32
     return lib
 
 

@@ -39,6 +39,13 @@ class FlashAttentionConfig:
     # sliding window (flash-attn's window_size = (left, right), -1 = unbounded): prefill through ops.flash_attention,
     # decode through ops.paged_attention_forward with (left, -1); windowed modules take the plain attention path
     window_size: Tuple[int, int] = (-1, -1)
+    # rotary position embedding in FlashAttentionLayer / FlashSelfAttention: the first rotary_dim elements of every q and k head
+    # are rotated (0: off, the layers run exactly as without these fields); the plain schedule base ** (-2 i / rotary_dim) over
+    # positions [0, max_position); neox pairing, or GPT-J's with rotary_interleaved.  A position outside the table gives a zero row.
+    rotary_dim: int = 0
+    rotary_base: float = 10000.0
+    rotary_interleaved: bool = False
+    max_position: int = 8192
 
     @property
     def allowed_precisions(self) -> Set[str]:
@@ -124,6 +131,33 @@ class _AttentionBase(nn.Module):
         if hidden_size % self.num_kv_heads != 0:
             raise ValueError(f"hidden_size {hidden_size} must be divisible by num_kv_heads {self.num_kv_heads}")
         self._cast = CastCache()
+        rd = self.config.rotary_dim
+        if rd and (rd < 0 or rd % 16 != 0 or rd > self.head_dim):
+            raise ValueError(f"rotary_dim must be 0 (off) or a multiple of 16 up to head_dim {self.head_dim}, got {rd}")
+        self._rope_key, self._rope_tabs = None, None  # plain attributes: the tables are derived, not state
+
+    def _rope_tables(self, device):
+        """(cos, sin) of the config's schedule on device: built once, and again when max_position (or the schedule) changes."""
+        cfg = self.config
+        key = (torch.device(device), int(cfg.max_position), int(cfg.rotary_dim), float(cfg.rotary_base))
+        if self._rope_key != key:
+            self._rope_tabs = ops.rope_tables(cfg.max_position, cfg.rotary_dim, cfg.rotary_base, device=device)
+            self._rope_key = key
+        return self._rope_tabs
+
+    def _rotate(self, t, positions):
+        """t [B,S,heads,D] (a fresh projection result or a view of one) rotated in place at positions int32 [B,S] or [S]."""
+        cos, sin = self._rope_tables(t.device)
+        return ops.apply_rotary(t, cos, sin, positions, interleaved=self.config.rotary_interleaved, out=t)
+
+    def _dense_positions(self, kwargs, S, device):
+        """The dense path's positions: the position_ids kwarg ([B,S] or [S]), else 0 .. S-1."""
+        ids = kwargs.get("position_ids")
+        if ids is not None:
+            return ids.to(device=device, dtype=torch.int32)
+        if S > self.config.max_position:
+            raise ValueError(f"sequence length {S} exceeds the rotary tables' max_position {self.config.max_position}")
+        return torch.arange(S, dtype=torch.int32, device=device)
 
     def _paged(self, q2d, B, q_len, dt, kwargs, who, residual=None):
         """q [B,q_len,H*D] already projected; attention over the paged cache, then o_proj
@@ -135,7 +169,18 @@ class _AttentionBase(nn.Module):
             raise ValueError(f"{who}: an fp8 (float8_e4m3fn) KV cache needs k_scale and v_scale "
                              "(PagedKVCache.get_kv_scales())")
         scales = {} if k_scale is None and v_scale is None else {"k_scale": k_scale, "v_scale": v_scale}
-        q = q2d.view(B, q_len, self.num_attention_heads, self.head_dim).permute(0, 2, 1, 3)
+        q = q2d.view(B, q_len, self.num_attention_heads, self.head_dim)
+        if self.config.rotary_dim > 0:
+            # row i of sequence b sits at position context_lengths[b] - q_len + i (the keys were rotated when they were cached:
+            # ops.rope_and_cache_varlen); computed on the device, nothing is read back
+            pos = kwargs.get("position_ids")
+            if pos is None:
+                pos = (cl.to(device=q.device, dtype=torch.int32).view(B, 1) - q_len
+                       + torch.arange(q_len, dtype=torch.int32, device=q.device).view(1, q_len))
+            else:
+                pos = pos.to(device=q.device, dtype=torch.int32)
+            q = self._rotate(q, pos)
+        q = q.permute(0, 2, 1, 3)
         out = torch.empty(B, q_len, self.num_attention_heads, self.head_dim, dtype=dt, device=q2d.device)
         ops.paged_attention_forward(q, out.permute(0, 2, 1, 3), k_cache, v_cache, bt, cl, bs, max_seq_len, layer_idx,
                                     **_decode_window_kw(self.config), **scales)
@@ -192,7 +237,9 @@ class FlashAttentionLayer(_AttentionBase):
         # (scaled in fp32, rounded once) and the attention launch is told so (ops.fa3_fwd k_prescaled)
         cfg = self.config
         kv_dim = self.num_kv_heads * self.head_dim
+        # (not with rotary: the rotation comes before any scaling of K)
         kpre = (attention_mask is None and not cfg.normalize_query and not cfg.return_softmax and not _windowed(cfg)
+                and cfg.rotary_dim == 0
                 and kv_dim % 128 == 0
                 and self.k_proj.in_features % 32 == 0
                 and ops.fa3_k_prescaled_ok(B, S, S, self.num_attention_heads, self.head_dim, kv_dim, kv_dim)
@@ -204,6 +251,9 @@ class FlashAttentionLayer(_AttentionBase):
             cs = (0, kv_dim, sc * 1.4426950408889634)
         k = linear(x, self.k_proj, c, dt, col_scale=cs).view(B, S, self.num_kv_heads, self.head_dim)
         v = linear(x, self.v_proj, c, dt).view(B, S, self.num_kv_heads, self.head_dim)
+        if cfg.rotary_dim > 0:
+            pos = self._dense_positions(kwargs, S, x.device)
+            q, k = self._rotate(q, pos), self._rotate(k, pos)
         if kpre:
             if self.training and cfg.dropout_p > 0.0:
                 raise NotImplementedError("attention dropout (training) is not supported by the inference kernel")
@@ -244,6 +294,8 @@ class FlashSelfAttention(_AttentionBase):
             return False
         if _windowed(cfg):  # the stream form's attention is the pre-scaled-K / blocked-output kernel: no window there
             return False
+        if cfg.rotary_dim > 0:  # nor rotary: the rotation comes before any scaling of K; forward() takes the ordinary route
+            return False
         if compute_dtype(cfg.precision, torch.empty(0, dtype=dtype)) != dtype:
             return False  # the stream form runs in the stream's dtype
         if tuple(pre_norm.normalized_shape) != (d,) or self.o_proj.out_features != d or q_dim != d:
@@ -257,7 +309,7 @@ class FlashSelfAttention(_AttentionBase):
         """The QKV epilogue may hand the attention kernel K * softmax_scale * log2(e) (ops.fa3_fwd k_prescaled)."""
         q_dim, kv_dim = self.hidden_size, self.num_kv_heads * self.head_dim
         n_tot = q_dim + 2 * kv_dim
-        return (not _windowed(self.config) and q_dim % 128 == 0 and kv_dim % 128 == 0 and ops.col_scale_ok(B * S, n_tot, self.qkv_proj.in_features)
+        return (not _windowed(self.config) and self.config.rotary_dim == 0 and q_dim % 128 == 0 and kv_dim % 128 == 0 and ops.col_scale_ok(B * S, n_tot, self.qkv_proj.in_features)
                 and ops.fa3_k_prescaled_ok(B, S, S, self.num_attention_heads, self.head_dim, n_tot, n_tot))
 
     def _forward_stream(self, x, pre_norm: nn.LayerNorm, stream_out: bool):
@@ -338,6 +390,7 @@ class FlashSelfAttention(_AttentionBase):
         n_tot = q_dim + 2 * kv_dim
         cfg = self.config
         kpre = (attention_mask is None and not cfg.normalize_query and not cfg.return_softmax and not _windowed(cfg)
+                and cfg.rotary_dim == 0
                 and q_dim % 128 == 0
                 and kv_dim % 128 == 0 and self.qkv_proj.in_features % 32 == 0
                 and ops.fa3_k_prescaled_ok(B, S, S, self.num_attention_heads, self.head_dim, n_tot, n_tot)
@@ -352,6 +405,9 @@ class FlashSelfAttention(_AttentionBase):
         q = qkv[:, :, :q_dim].view(B, S, self.num_attention_heads, self.head_dim)
         k = qkv[:, :, q_dim:q_dim + kv_dim].view(B, S, self.num_kv_heads, self.head_dim)
         v = qkv[:, :, q_dim + kv_dim:].view(B, S, self.num_kv_heads, self.head_dim)
+        if cfg.rotary_dim > 0:
+            pos = self._dense_positions(kwargs, S, x.device)
+            q, k = self._rotate(q, pos), self._rotate(k, pos)
         if kpre:
             if self.training and cfg.dropout_p > 0.0:
                 raise NotImplementedError("attention dropout (training) is not supported by the inference kernel")

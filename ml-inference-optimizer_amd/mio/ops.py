@@ -10,6 +10,10 @@ same exception types for the same conditions):
   layernorm                 <- triton_layernorm              (kernels/triton/layernorm_kernels.py:191-276)
   paged_attention_forward   <- triton_paged_attention_forward(kernels/triton/attention_kernels.py:1206-1311)
   reshape_and_cache         <- triton_reshape_and_cache      (kernels/triton/attention_kernels.py:1314-1407)
+  rope_tables / apply_rotary / rope_and_cache_varlen
+                               rotary position embedding (not a reference kernel: its LLaMA path rotates K in PyTorch before
+                               caching it, baseline/model_utils.py): the fp32 angle tables, the standalone rotation of the dense
+                               path, and the rotation fused into the varlen paged-cache write (16-bit and fp8 caches)
 There is no fallback path: a non-zero return from the library raises RuntimeError.
 """
 from __future__ import annotations
@@ -1311,6 +1315,166 @@ def reshape_and_cache_varlen(key, value, k_cache, v_cache, block_tables, cu_seql
                                            block_tables.data_ptr(), cu_seqlens_new.data_ptr(),
                                            context_lengths.data_ptr(), ks, vs, B, T, Hkv, D, nb, L, int(layer_idx),
                                            bs, block_tables.shape[1], dt, _stream()))
+
+
+# ------------------------------------------------------------------------------------------------
+# rotary position embedding
+# ------------------------------------------------------------------------------------------------
+def rope_tables(max_position: int, rot_dim: int, base: float = 10000.0, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The (cos, sin) tables of the plain rotary schedule, fp32 [max_position, rot_dim / 2]: entry (p, i) is the cosine /
+    sine of p * base ** (-2 i / rot_dim), the angle computed in fp64 and cast once.  Any other schedule (scaled, YaRN,
+    Llama-3) is a table of the same shape the caller builds."""
+    max_position, rot_dim = operator.index(max_position), operator.index(rot_dim)
+    if max_position <= 0:
+        raise ValueError(f"max_position must be positive, got {max_position}")
+    if rot_dim <= 0 or rot_dim % 2 != 0:
+        raise ValueError(f"rot_dim must be a positive even number, got {rot_dim}")
+    inv_freq = float(base) ** (-torch.arange(0, rot_dim, 2, dtype=torch.float64) / rot_dim)
+    ang = torch.arange(max_position, dtype=torch.float64)[:, None] * inv_freq[None, :]
+    return ang.cos().to(torch.float32).to(device), ang.sin().to(torch.float32).to(device)
+
+
+def _rope_tables_ok(cos, sin, D: int, kv8: bool, interleaved: bool, device, who: str) -> Tuple[int, int]:
+    """The checks of the (cos, sin) tables; returns (max_position, rot_dim)."""
+    for name, t in (("cos", cos), ("sin", sin)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous float32 tensor [max_position, rot_dim / 2]")
+        if t.device != device:
+            raise ValueError(f"{who}: {name} must be on the device of the rotated tensor")
+    if sin.shape != cos.shape:
+        raise ValueError(f"{who}: cos and sin must have equal shapes, got {tuple(cos.shape)} and {tuple(sin.shape)}")
+    max_position, rot_dim = cos.shape[0], 2 * cos.shape[1]
+    if max_position < 1:
+        raise ValueError(f"{who}: the tables must hold at least one position")
+    if rot_dim < 16 or rot_dim % 16 != 0 or rot_dim > D:
+        raise ValueError(f"{who}: rot_dim must be a multiple of 16 in [16, head_dim = {D}], got {rot_dim}")
+    if kv8 and not interleaved and rot_dim % 32 != 0:
+        raise ValueError(f"{who}: rot_dim must be a multiple of 32 for an fp8 cache with the neox pairing, got {rot_dim}")
+    if cos.data_ptr() % 16 or sin.data_ptr() % 16:
+        raise ValueError(f"{who}: cos and sin must be 16-byte aligned")
+    return max_position, rot_dim
+
+
+def apply_rotary(x, cos, sin, positions, *, interleaved: bool = False, out=None) -> torch.Tensor:
+    """Rotary position embedding of x (mio_rope_rows): x [tokens, heads, D] with positions int32 [tokens], or
+    [B, S, heads, D] with positions [B, S] or [S].  The first rot_dim = 2 * cos.shape[1] elements of every head are rotated by
+    the angles cos / sin hold (fp32 [max_position, rot_dim / 2], rope_tables or the caller's schedule) for the token's
+    position: y1 = x1 c - x2 s, y2 = x2 c + x1 s in fp32, rounded once; the neox pairing (i with i + rot_dim / 2) or, with
+    interleaved, GPT-J's (2 i with 2 i + 1).  Elements past rot_dim are copied.  A position outside [0, max_position) gives a
+    row of zeros.  out (x's shape and dtype, last dim contiguous, strides multiples of 8) may be x itself."""
+    who = "apply_rotary"
+    if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4):
+        raise ValueError(f"{who}: x must be [tokens, heads, head_dim] or [B, S, heads, head_dim]")
+    _need_cuda(x, cos, sin, positions, out)
+    dt = _dtype_id(x)
+    D = x.shape[-1]
+    if D % 8 != 0 or D > 128:
+        raise ValueError(f"head_dim must be a multiple of 8 and <= 128, got {D}")
+    max_position, rot_dim = _rope_tables_ok(cos, sin, D, False, interleaved, x.device, who)
+    if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32 or positions.device != x.device:
+        raise ValueError(f"{who}: positions must be an int32 tensor on the device of x")
+    if out is not None and (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device):
+        raise ValueError(f"{who}: out must have x's shape, dtype and device")
+    shape = x.shape
+    if x.dim() == 4:
+        B, S = shape[0], shape[1]
+        if tuple(positions.shape) == (S,):
+            positions = positions.expand(B, S)
+        if tuple(positions.shape) != (B, S):
+            raise ValueError(f"{who}: positions must be [B, S] = [{B}, {S}] or [S], got {tuple(positions.shape)}")
+        positions = positions.reshape(B * S)
+        # [B, S] collapse to one token axis where the strides allow it (a view of a [B, S, n] projection does)
+        x3 = x.reshape(B * S, shape[2], D) if x.stride(0) == S * x.stride(1) else x.contiguous().view(B * S, shape[2], D)
+        out3 = None
+        if out is not None:
+            if out.stride(0) != S * out.stride(1):
+                raise ValueError(f"{who}: out's batch and sequence axes must collapse to one token axis")
+            out3 = out.view(B * S, shape[2], D)
+    else:
+        if positions.dim() != 1 or positions.numel() != shape[0]:
+            raise ValueError(f"{who}: positions must be [tokens] = [{shape[0]}], got {tuple(positions.shape)}")
+        x3, out3 = x, out
+    positions = positions.contiguous()
+    x3 = _rows16(x3)
+    if out3 is None:
+        res = torch.empty(shape, dtype=x.dtype, device=x.device)
+        out3 = res.view(x3.shape)
+    else:
+        res = out
+        if out3.stride(-1) != 1 or any(s % 8 for s in out3.stride()[:-1]) or out3.data_ptr() % 16:
+            raise ValueError(f"{who}: out needs a contiguous last dim, strides that are multiples of 8 and 16-byte alignment")
+    T, Hn, _ = x3.shape
+    xs = (C.c_int64 * 2)(x3.stride(0), x3.stride(1))
+    os_ = (C.c_int64 * 2)(out3.stride(0), out3.stride(1))
+    check(lib.mio_rope_rows(x3.data_ptr(), out3.data_ptr(), positions.data_ptr(), cos.data_ptr(), sin.data_ptr(), xs, os_,
+                            T, Hn, D, rot_dim, max_position, int(bool(interleaved)), dt, _stream()))
+    return res
+
+
+def rope_and_cache_varlen(q, key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths,
+                          block_size: int, layer_idx: int, cos, sin, *, positions=None, interleaved: bool = False,
+                          q_out=None, k_scale=None, v_scale=None) -> torch.Tensor:
+    """reshape_and_cache_varlen with rotary position embedding fused in (mio_rope_and_cache_varlen / _kv8): K is rotated on
+    its way into the paged cache (rounded once, straight into the cache's format: 16 bits, or e4m3 of rot(k) / k_scale for a
+    float8_e4m3fn cache), V and K's elements past rot_dim are written exactly as reshape_and_cache_varlen writes them, and
+    the token's query heads q [total_new, H, D] are rotated into q_out (returned; q's shape, may be q itself; allocated when
+    None).  cos / sin as apply_rotary.  A token's position is its cache position context_lengths[b] - n_b + i, or
+    positions[t] (int32 [total_new]) where given -- the cache row does not depend on it.  A token outside every sequence, or
+    whose position is outside [0, max_position), writes nothing to the caches and gets a q_out row of zeros.  Queued on the
+    current stream with no host sync (graph-capturable)."""
+    who = "rope_and_cache_varlen"
+    _need_cuda(q, key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths, cos, sin, positions, q_out)
+    if key.dim() != 3 or value.shape != key.shape:
+        raise ValueError(f"key/value must be [total_new, num_kv_heads, head_dim] with equal shapes, got "
+                         f"key={tuple(key.shape)}, value={tuple(value.shape)}")
+    dt = _dtype_id(key)
+    scales = _write_caches(key, value, k_cache, v_cache, layer_idx, k_scale, v_scale, who)
+    T, Hkv, D = key.shape
+    if q.dim() != 3 or q.shape[0] != T or q.shape[2] != D or q.dtype != key.dtype:
+        raise ValueError(f"q must be [total_new, num_heads, head_dim] = [{T}, H, {D}] of key's dtype, got "
+                         f"{tuple(q.shape)} {q.dtype}")
+    H = q.shape[1]
+    nb, L, bs, Hc, Dc = k_cache.shape
+    if (Hc, Dc, bs) != (Hkv, D, block_size):
+        raise ValueError("cache geometry mismatch")
+    if D % 8 != 0:
+        raise ValueError(f"head_dim must be a multiple of 8, got {D}")
+    _check_heads(H, Hkv, D)
+    if not 0 <= int(layer_idx) < L:
+        raise ValueError(f"layer_idx {layer_idx} out of range for a {L}-layer cache")
+    _i32_dev(cu_seqlens_new, "cu_seqlens_new", 1, "of B+1 offsets", key.device)
+    if cu_seqlens_new.numel() < 1:
+        raise ValueError("cu_seqlens_new must be a contiguous 1-D int32 tensor of B+1 offsets")
+    B = cu_seqlens_new.numel() - 1
+    _i32_dev(context_lengths, "context_lengths", 1, "of B lengths", key.device)
+    _i32_dev(block_tables, "block_tables", 2, "[B, max_blocks_per_seq]", key.device)
+    if context_lengths.numel() != B or block_tables.shape[0] != B:
+        raise ValueError(f"context_lengths and block_tables must have B = {B} rows (cu_seqlens_new has B+1 entries)")
+    max_position, rot_dim = _rope_tables_ok(cos, sin, D, scales is not None, interleaved, key.device, who)
+    if positions is not None:
+        _i32_dev(positions, "positions", 1, "of total_new positions", key.device)
+        if positions.numel() != T:
+            raise ValueError(f"positions must hold total_new = {T} entries, got {positions.numel()}")
+    if q_out is None:
+        q_out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    elif q_out.shape != q.shape or q_out.dtype != q.dtype or q_out.device != q.device:
+        raise ValueError(f"{who}: q_out must have q's shape, dtype and device")
+    elif q_out.stride(-1) != 1 or any(s % 8 for s in q_out.stride()[:-1]) or q_out.data_ptr() % 16:
+        raise ValueError(f"{who}: q_out needs a contiguous last dim, strides that are multiples of 8 and 16-byte alignment")
+    q, key, value = _rows16(q), _rows16(key), _rows16(value)
+    qs = (C.c_int64 * 2)(q.stride(0), q.stride(1))
+    os_ = (C.c_int64 * 2)(q_out.stride(0), q_out.stride(1))
+    ks = (C.c_int64 * 2)(key.stride(0), key.stride(1))
+    vs = (C.c_int64 * 2)(value.stride(0), value.stride(1))
+    head = (q.data_ptr(), q_out.data_ptr(), key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr())
+    tail = (block_tables.data_ptr(), cu_seqlens_new.data_ptr(), context_lengths.data_ptr(), _ptr(positions),
+            cos.data_ptr(), sin.data_ptr(), qs, os_, ks, vs, B, T, H, Hkv, D, rot_dim, max_position,
+            int(bool(interleaved)), nb, L, int(layer_idx), bs, block_tables.shape[1], dt, _stream())
+    if scales is not None:
+        check(lib.mio_rope_and_cache_varlen_kv8(*head, *scales, *tail))
+    else:
+        check(lib.mio_rope_and_cache_varlen(*head, *tail))
+    return q_out
 
 
 # ------------------------------------------------------------------------------------------------
