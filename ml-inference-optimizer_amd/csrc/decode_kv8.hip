@@ -1,10 +1,10 @@
-// FP8 paged KV cache (OCP e4m3fn, torch.float8_e4m3fn) for CDNA4 (gfx950): the quantising cache writes and the three
-// decode kernels of decode_paged.hip over one byte per cached element.
+// FP8 paged KV cache (OCP e4m3fn, torch.float8_e4m3fn) for CDNA4 (gfx950): the three decode kernels of decode_paged.hip
+// over one byte per cached element; decode only: the quantising writes into the cache are cache_write.hip's.
 //
 // Same cache layout, one byte per element: [num_blocks, num_layers, block_size, Hkv, D].  A cached element x8 stands for
 // x8 * scale with one fp32 scale per (K or V, layer), read by the kernels from device memory (no host sync: a scale may change
 // between replays of a captured graph).  The host passes the address of the scale of layer_idx.
-//   write:  q = e4m3(clamp(float(x) * (1 / scale), -448, 448)), round to nearest even; NaN stays NaN (sign | 0x7f)
+//   write:  q = e4m3(clamp(float(x) * (1 / scale), -448, 448)), round to nearest even; NaN stays NaN (cache_write.hip)
 //   decode: every e4m3 value is exact in bf16 / fp16 / fp32, so K and V enter the products unrounded; k_scale is folded into
 //           the score scale, v_scale into the output of each split before its partial state is stored (the split merge,
 //           decode_reduce_kernel, is linear in o and is the 16-bit one).  Q and the softmax weights stay 16-bit / fp32.
@@ -148,139 +148,4 @@ extern "C" int mio_fa3_decode_kv8_route(const void* q, void* o, const void* k_ca
                           context_lengths, q_stride, o_stride, B, H, Hkv, q_len, D, num_layers, layer_idx, block_size,
                           max_blocks_per_seq, max_ctx, scale, dtype, dec_window(window_left, max_ctx, q_len));
   return rc != 0 ? rc : route;
-}
-
-// ---- quantising cache writes ---------------------------------------------------------------------------------------------
-// reshape_and_cache_kv8_kernel: one workgroup per sequence, the token at context_lengths[b] - 1; a thread owns one 16-byte
-// chunk (16 elements) of the cached row: two 16-byte loads of each of K and V, one 16-byte store of each.
-template <typename T>
-__global__ __launch_bounds__(256) void reshape_and_cache_kv8_kernel(
-    const T* __restrict__ key, const T* __restrict__ value, uint8_t* __restrict__ kc, uint8_t* __restrict__ vc,
-    const float* __restrict__ ksc, const float* __restrict__ vsc, const int32_t* __restrict__ bt,
-    const int32_t* __restrict__ cl, int64_t ks_b, int64_t ks_h, int64_t vs_b, int64_t vs_h, int Hkv, int D, int L,
-    int layer, int bs, int max_blocks) {
-  const int b = blockIdx.x;
-  const int pos = cl[b] - 1;
-  if (pos < 0 || pos / bs >= max_blocks) return;  // empty sequence / context longer than the block table row: nothing written
-  const int pb = bt[(int64_t)b * max_blocks + pos / bs];
-  const float kinv = 1.0f / ksc[0], vinv = 1.0f / vsc[0];
-  const int64_t tok_stride = (int64_t)Hkv * D;
-  const int64_t dst = ((int64_t)pb * L + layer) * bs * tok_stride + (int64_t)(pos % bs) * tok_stride;
-  const int cpr = D >> 4;
-  for (int i = threadIdx.x; i < Hkv * cpr; i += 256) {
-    const int hh = i / cpr, c = i % cpr;
-    const T* kp = key + b * ks_b + hh * ks_h + 16 * c;
-    const T* vp = value + b * vs_b + hh * vs_h + 16 * c;
-    const u32x4_t k0 = *(const u32x4_t*)kp, k1 = *(const u32x4_t*)(kp + 8);
-    const u32x4_t v0 = *(const u32x4_t*)vp, v1 = *(const u32x4_t*)(vp + 8);
-    *(u32x4_t*)(kc + dst + (int64_t)hh * D + 16 * c) = kv8_quant16<T>(k0, k1, kinv);
-    *(u32x4_t*)(vc + dst + (int64_t)hh * D + 16 * c) = kv8_quant16<T>(v0, v1, vinv);
-  }
-}
-
-// reshape_and_cache_varlen_kv8_kernel: reshape_and_cache_varlen_kernel with a thread per 16-byte chunk (16 elements) of the
-// cached row; the same token-to-row lookup (dec_varlen_row) and skipping rules.
-template <typename T>
-__global__ __launch_bounds__(256) void reshape_and_cache_varlen_kv8_kernel(
-    const T* __restrict__ key, const T* __restrict__ value, uint8_t* __restrict__ kc, uint8_t* __restrict__ vc,
-    const float* __restrict__ ksc, const float* __restrict__ vsc, const int32_t* __restrict__ bt,
-    const int32_t* __restrict__ cu, const int32_t* __restrict__ cl, int64_t ks_t, int64_t ks_h, int64_t vs_t,
-    int64_t vs_h, int B, int total, int Hkv, int D, int num_blocks, int L, int layer, int bs, int max_blocks) {
-  const int cpr = D >> 4, cpt = Hkv * cpr;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (int64_t)total * cpt) return;
-  const int t = (int)(i / cpt), c = (int)(i % cpt), hh = c / cpr, cc = c % cpr;
-  dec_varlen_row(t, bt, cu, cl, B, total, num_blocks, L, layer, bs, max_blocks, [&](int64_t row) __attribute__((always_inline)) {
-    const int64_t dst = row * ((int64_t)Hkv * D) + (int64_t)hh * D + 16 * cc;
-    const T* kp = key + t * ks_t + hh * ks_h + 16 * cc;
-    const T* vp = value + t * vs_t + hh * vs_h + 16 * cc;
-    const u32x4_t k0 = *(const u32x4_t*)kp, k1 = *(const u32x4_t*)(kp + 8);
-    const u32x4_t v0 = *(const u32x4_t*)vp, v1 = *(const u32x4_t*)(vp + 8);
-    *(u32x4_t*)(kc + dst) = kv8_quant16<T>(k0, k1, 1.0f / ksc[0]);
-    *(u32x4_t*)(vc + dst) = kv8_quant16<T>(v0, v1, 1.0f / vsc[0]);
-  });
-}
-
-static bool kv8_scales_ok(const float* k_scale, const float* v_scale) {
-  return k_scale && v_scale && ((uintptr_t)k_scale & 3) == 0 && ((uintptr_t)v_scale & 3) == 0;
-}
-
-extern "C" int mio_reshape_and_cache_kv8(const void* key, const void* value, void* k_cache, void* v_cache,
-                                         const float* k_scale, const float* v_scale, const int32_t* block_tables,
-                                         const int32_t* context_lengths, const int64_t k_stride[2],
-                                         const int64_t v_stride[2], int32_t B, int32_t Hkv, int32_t D,
-                                         int32_t num_layers, int32_t layer_idx, int32_t block_size,
-                                         int32_t max_blocks_per_seq, int32_t dtype, void* stream) {
-  const char* fn = "mio_reshape_and_cache_kv8";
-  MIO_CHECK(key && value && k_cache && v_cache && block_tables && context_lengths && k_stride && v_stride,
-            std::string(fn) + ": null pointer");
-  MIO_CHECK(kv8_scales_ok(k_scale, v_scale), std::string(fn) + ": k_scale and v_scale are required with an fp8 cache "
-                                                               "(null scale pointer or not 4-byte aligned)");
-  MIO_CHECK(B > 0 && Hkv > 0, std::string(fn) + ": bad sizes");
-  MIO_CHECK(D >= 16 && D % 16 == 0, std::string(fn) + ": head_dim must be a multiple of 16 for an fp8 cache");
-  MIO_CHECK(layer_idx >= 0 && layer_idx < num_layers && block_size > 0 && max_blocks_per_seq > 0,
-            std::string(fn) + ": bad cache geometry");
-  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, std::string(fn) + ": dtype (of key and value) must be bf16 or fp16");
-  MIO_CHECK(k_stride[0] % 8 == 0 && k_stride[1] % 8 == 0 && v_stride[0] % 8 == 0 && v_stride[1] % 8 == 0 &&
-                mio_aligned16(key) && mio_aligned16(value) && mio_aligned16(k_cache) && mio_aligned16(v_cache),
-            std::string(fn) + ": 16-byte alignment");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MIO_BF16)
-    hipLaunchKernelGGL(reshape_and_cache_kv8_kernel<__bf16>, dim3((unsigned)B), dim3(256), 0, st, (const __bf16*)key,
-                       (const __bf16*)value, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale, v_scale, block_tables,
-                       context_lengths, k_stride[0], k_stride[1], v_stride[0], v_stride[1], Hkv, D, num_layers,
-                       layer_idx, block_size, max_blocks_per_seq);
-  else
-    hipLaunchKernelGGL(reshape_and_cache_kv8_kernel<_Float16>, dim3((unsigned)B), dim3(256), 0, st, (const _Float16*)key,
-                       (const _Float16*)value, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale, v_scale, block_tables,
-                       context_lengths, k_stride[0], k_stride[1], v_stride[0], v_stride[1], Hkv, D, num_layers,
-                       layer_idx, block_size, max_blocks_per_seq);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("reshape_and_cache_kv8 launch: ") + hipGetErrorString(e));
-  return 0;
-}
-
-extern "C" int mio_reshape_and_cache_varlen_kv8(const void* key, const void* value, void* k_cache, void* v_cache,
-                                                const float* k_scale, const float* v_scale,
-                                                const int32_t* block_tables, const int32_t* cu_seqlens_new,
-                                                const int32_t* context_lengths, const int64_t k_stride[2],
-                                                const int64_t v_stride[2], int32_t B, int32_t total_new, int32_t Hkv,
-                                                int32_t D, int32_t num_blocks, int32_t num_layers, int32_t layer_idx,
-                                                int32_t block_size, int32_t max_blocks_per_seq, int32_t dtype,
-                                                void* stream) {
-  const char* fn = "mio_reshape_and_cache_varlen_kv8";
-  MIO_CHECK(k_stride != nullptr && v_stride != nullptr, std::string(fn) + ": null strides");
-  MIO_CHECK(kv8_scales_ok(k_scale, v_scale), std::string(fn) + ": k_scale and v_scale are required with an fp8 cache "
-                                                               "(null scale pointer or not 4-byte aligned)");
-  MIO_CHECK(B >= 0 && total_new >= 0 && Hkv > 0, std::string(fn) + ": bad sizes");
-  MIO_CHECK(D >= 16 && D % 16 == 0, std::string(fn) + ": head_dim must be a multiple of 16 for an fp8 cache");
-  MIO_CHECK(num_blocks > 0 && num_layers > 0 && layer_idx >= 0 && layer_idx < num_layers && block_size > 0 &&
-                max_blocks_per_seq > 0,
-            std::string(fn) + ": bad cache geometry");
-  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, std::string(fn) + ": dtype (of key and value) must be bf16 or fp16");
-  if (B == 0 || total_new == 0) return 0;
-  MIO_CHECK(key && value && k_cache && v_cache && block_tables && cu_seqlens_new && context_lengths,
-            std::string(fn) + ": null pointer");
-  MIO_CHECK(k_stride[0] >= 0 && k_stride[1] >= 0 && v_stride[0] >= 0 && v_stride[1] >= 0 && k_stride[0] % 8 == 0 &&
-                k_stride[1] % 8 == 0 && v_stride[0] % 8 == 0 && v_stride[1] % 8 == 0 && mio_aligned16(key) &&
-                mio_aligned16(value) && mio_aligned16(k_cache) && mio_aligned16(v_cache),
-            std::string(fn) + ": 16-byte alignment");
-  const int64_t blocks = ((int64_t)total_new * Hkv * (D / 16) + 255) / 256;
-  MIO_CHECK(blocks <= 0x7fffffff, std::string(fn) + ": too many tokens");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MIO_BF16)
-    hipLaunchKernelGGL(reshape_and_cache_varlen_kv8_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, st,
-                       (const __bf16*)key, (const __bf16*)value, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale, v_scale,
-                       block_tables, cu_seqlens_new, context_lengths, k_stride[0], k_stride[1], v_stride[0],
-                       v_stride[1], B, total_new, Hkv, D, num_blocks, num_layers, layer_idx, block_size,
-                       max_blocks_per_seq);
-  else
-    hipLaunchKernelGGL(reshape_and_cache_varlen_kv8_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, st,
-                       (const _Float16*)key, (const _Float16*)value, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale,
-                       v_scale, block_tables, cu_seqlens_new, context_lengths, k_stride[0], k_stride[1], v_stride[0],
-                       v_stride[1], B, total_new, Hkv, D, num_blocks, num_layers, layer_idx, block_size,
-                       max_blocks_per_seq);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("reshape_and_cache_varlen_kv8 launch: ") + hipGetErrorString(e));
-  return 0;
 }

@@ -1,9 +1,8 @@
-// Paged-KV decode attention + cache scatter for CDNA4 (gfx950).  HBM-bandwidth-bound: K/V rows go
-// straight from global memory to VGPRs (16 B per lane), no LDS staging, split over the context so
-// a small batch still fills 256 CUs; partial (o, lse) states are merged by a second tiny kernel.
+// Paged-KV decode attention for CDNA4 (gfx950); decode only: the writes into the cache are cache_write.hip's.
+// HBM-bandwidth-bound: K/V rows go straight from global memory to VGPRs (16 B per lane), no LDS staging, split over the
+// context so a small batch still fills 256 CUs; partial (o, lse) states are merged by a second tiny kernel.
 //
-// Replaces _paged_attention_fwd_kernel (reference kernels/triton/attention_kernels.py:628-808, wrapper
-// :1206-1311) and _reshape_and_cache_kernel (:811-905, wrapper :1314-1407).
+// Replaces _paged_attention_fwd_kernel (reference kernels/triton/attention_kernels.py:628-808, wrapper :1206-1311).
 // Cache layout [num_blocks, num_layers, block_size, Hkv, D]; token t of sequence b lives in physical
 // block block_tables[b, t / block_size] at slot t % block_size (:728-751).
 #include <cstdlib>
@@ -194,99 +193,4 @@ extern "C" int mio_fa3_decode_window_route(const void* q, void* o, const void* k
                           o_stride, B, H, Hkv, q_len, D, num_layers, layer_idx, block_size, max_blocks_per_seq, max_ctx,
                           scale, dtype, dec_window(window_left, max_ctx, q_len));
   return rc != 0 ? rc : route;
-}
-
-// ---- reshape_and_cache: one workgroup per sequence, 16-byte chunks over (Hkv, D) --------------------
-__global__ __launch_bounds__(256) void reshape_and_cache_kernel(const uint16_t* __restrict__ key,
-                                                                const uint16_t* __restrict__ value,
-                                                                uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
-                                                                const int32_t* __restrict__ bt,
-                                                                const int32_t* __restrict__ cl, int64_t ks_b,
-                                                                int64_t ks_h, int64_t vs_b, int64_t vs_h, int Hkv,
-                                                                int D, int L, int layer, int bs, int max_blocks) {
-  const int b = blockIdx.x;
-  const int pos = cl[b] - 1;  // write position (attention_kernels.py:858)
-  if (pos < 0 || pos / bs >= max_blocks) return;  // empty sequence / context longer than the block table row: nothing written
-  const int pb = bt[(int64_t)b * max_blocks + pos / bs];
-  const int64_t tok_stride = (int64_t)Hkv * D;
-  const int64_t dst = ((int64_t)pb * L + layer) * bs * tok_stride + (int64_t)(pos % bs) * tok_stride;
-  const int cpr = D >> 3;
-  for (int i = threadIdx.x; i < Hkv * cpr; i += 256) {
-    const int hh = i / cpr, c = i % cpr;
-    const u32x4_t kk = *(const u32x4_t*)(key + b * ks_b + hh * ks_h + 8 * c);
-    const u32x4_t vv = *(const u32x4_t*)(value + b * vs_b + hh * vs_h + 8 * c);
-    *(u32x4_t*)(kc + dst + (int64_t)hh * D + 8 * c) = kk;
-    *(u32x4_t*)(vc + dst + (int64_t)hh * D + 8 * c) = vv;
-  }
-}
-
-extern "C" int mio_reshape_and_cache(const void* key, const void* value, void* k_cache, void* v_cache,
-                                     const int32_t* block_tables, const int32_t* context_lengths,
-                                     const int64_t k_stride[2], const int64_t v_stride[2], int32_t B, int32_t Hkv,
-                                     int32_t D, int32_t num_layers, int32_t layer_idx, int32_t block_size,
-                                     int32_t max_blocks_per_seq, int32_t dtype, void* stream) {
-  MIO_CHECK(key && value && k_cache && v_cache && block_tables && context_lengths, "mio_reshape_and_cache: null pointer");
-  MIO_CHECK(B > 0 && Hkv > 0 && D >= 8 && D % 8 == 0, "mio_reshape_and_cache: bad sizes");
-  MIO_CHECK(layer_idx >= 0 && layer_idx < num_layers && block_size > 0, "mio_reshape_and_cache: bad cache geometry");
-  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_reshape_and_cache: dtype must be bf16 or fp16");
-  MIO_CHECK(k_stride[0] % 8 == 0 && k_stride[1] % 8 == 0 && v_stride[0] % 8 == 0 && v_stride[1] % 8 == 0 &&
-                mio_aligned16(key) && mio_aligned16(value) && mio_aligned16(k_cache) && mio_aligned16(v_cache),
-            "mio_reshape_and_cache: 16-byte alignment");
-  hipLaunchKernelGGL(reshape_and_cache_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream,
-                     (const uint16_t*)key, (const uint16_t*)value, (uint16_t*)k_cache, (uint16_t*)v_cache,
-                     block_tables, context_lengths, k_stride[0], k_stride[1], v_stride[0], v_stride[1], Hkv, D,
-                     num_layers, layer_idx, block_size, max_blocks_per_seq);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("reshape_and_cache launch: ") + hipGetErrorString(e));
-  return 0;
-}
-
-// ---- reshape_and_cache_varlen: many new tokens per sequence; one thread per 16-byte chunk of K and of V ------------------
-// Thread i of the grid owns chunk i % (Hkv * D / 8) of packed token i / (Hkv * D / 8); the token's cache row and the
-// skipping rules are dec_varlen_row's (decode_plan.h).
-__global__ __launch_bounds__(256) void reshape_and_cache_varlen_kernel(
-    const uint16_t* __restrict__ key, const uint16_t* __restrict__ value, uint16_t* __restrict__ kc,
-    uint16_t* __restrict__ vc, const int32_t* __restrict__ bt, const int32_t* __restrict__ cu,
-    const int32_t* __restrict__ cl, int64_t ks_t, int64_t ks_h, int64_t vs_t, int64_t vs_h, int B, int total, int Hkv, int D,
-    int num_blocks, int L, int layer, int bs, int max_blocks) {
-  const int cpr = D >> 3, cpt = Hkv * cpr;  // 16-byte chunks per head row / per token
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (int64_t)total * cpt) return;
-  const int t = (int)(i / cpt), c = (int)(i % cpt), hh = c / cpr, cc = c % cpr;
-  dec_varlen_row(t, bt, cu, cl, B, total, num_blocks, L, layer, bs, max_blocks, [&](int64_t row) __attribute__((always_inline)) {
-    const int64_t dst = row * ((int64_t)Hkv * D) + (int64_t)hh * D + 8 * cc;
-    *(u32x4_t*)(kc + dst) = *(const u32x4_t*)(key + t * ks_t + hh * ks_h + 8 * cc);
-    *(u32x4_t*)(vc + dst) = *(const u32x4_t*)(value + t * vs_t + hh * vs_h + 8 * cc);
-  });
-}
-
-extern "C" int mio_reshape_and_cache_varlen(const void* key, const void* value, void* k_cache, void* v_cache,
-                                            const int32_t* block_tables, const int32_t* cu_seqlens_new,
-                                            const int32_t* context_lengths, const int64_t k_stride[2],
-                                            const int64_t v_stride[2], int32_t B, int32_t total_new, int32_t Hkv,
-                                            int32_t D, int32_t num_blocks, int32_t num_layers, int32_t layer_idx,
-                                            int32_t block_size, int32_t max_blocks_per_seq, int32_t dtype,
-                                            void* stream) {
-  MIO_CHECK(k_stride != nullptr && v_stride != nullptr, "mio_reshape_and_cache_varlen: null strides");
-  MIO_CHECK(B >= 0 && total_new >= 0 && Hkv > 0 && D >= 8 && D % 8 == 0, "mio_reshape_and_cache_varlen: bad sizes");
-  MIO_CHECK(num_blocks > 0 && num_layers > 0 && layer_idx >= 0 && layer_idx < num_layers && block_size > 0 &&
-                max_blocks_per_seq > 0,
-            "mio_reshape_and_cache_varlen: bad cache geometry");
-  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_reshape_and_cache_varlen: dtype must be bf16 or fp16");
-  if (B == 0 || total_new == 0) return 0;
-  MIO_CHECK(key && value && k_cache && v_cache && block_tables && cu_seqlens_new && context_lengths,
-            "mio_reshape_and_cache_varlen: null pointer");
-  MIO_CHECK(k_stride[0] >= 0 && k_stride[1] >= 0 && v_stride[0] >= 0 && v_stride[1] >= 0 && k_stride[0] % 8 == 0 &&
-                k_stride[1] % 8 == 0 && v_stride[0] % 8 == 0 && v_stride[1] % 8 == 0 && mio_aligned16(key) &&
-                mio_aligned16(value) && mio_aligned16(k_cache) && mio_aligned16(v_cache),
-            "mio_reshape_and_cache_varlen: 16-byte alignment");
-  const int64_t blocks = ((int64_t)total_new * Hkv * (D / 8) + 255) / 256;
-  MIO_CHECK(blocks <= 0x7fffffff, "mio_reshape_and_cache_varlen: too many tokens");
-  hipLaunchKernelGGL(reshape_and_cache_varlen_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     (const uint16_t*)key, (const uint16_t*)value, (uint16_t*)k_cache, (uint16_t*)v_cache, block_tables,
-                     cu_seqlens_new, context_lengths, k_stride[0], k_stride[1], v_stride[0], v_stride[1], B, total_new,
-                     Hkv, D, num_blocks, num_layers, layer_idx, block_size, max_blocks_per_seq);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("reshape_and_cache_varlen launch: ") + hipGetErrorString(e));
-  return 0;
 }

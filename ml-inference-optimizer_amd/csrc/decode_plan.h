@@ -1,6 +1,5 @@
 // Decode launch state, the plan of a launch (argument checks, kernel choice, split geometry) and its rules, shared by the
-// 16-bit decode (decode_paged.hip) and the fp8-cache decode (decode_kv8.hip), with the split-merge kernel both launch and
-// the token-to-row lookup of both varlen cache writes.
+// 16-bit decode (decode_paged.hip) and the fp8-cache decode (decode_kv8.hip), with the split-merge kernel both launch.
 // The kernel bodies (decode_paged_body.inc, decode_rows_body.inc, decode_gqa_body.inc) serve both caches: each unit's
 // kernels include them with KV8 false (16-bit elements) or true (one e4m3fn byte per element, kv8_cvt.h).
 #pragma once
@@ -24,45 +23,6 @@ struct DecDev {
   int B, H, Hkv, q_len, D, L, layer, bs, max_blocks, nsplit, split_len;
   float scale;
 };
-
-// The cache row of packed token t of a varlen cache write (reshape_and_cache_varlen_kernel, its fp8 form and the rotating
-// writes of rope.hip): write(row) when the token is written.  Its sequence is the last b with cu[b] <= t (binary search over
-// the clamped offsets, then checked: a token outside its sequence's clamped range is skipped, so offsets that disagree with
-// total write nothing out of place); a position before the sequence, past its block-table row or in a block outside the
-// cache is skipped too.  The two halves are usable apart: dec_varlen_tok (the sequence and the cache position, false for a
-// token outside its sequence's range) and dec_varlen_row_at (the row of a position); dec_varlen_row is one after the other.
-__device__ __forceinline__ bool dec_varlen_tok(int t, const int32_t* cu, const int32_t* cl, int B, int total, int& b,
-                                               int& pos) {
-  auto cu_at = [&](int b) { const int x = cu[b]; return x < 0 ? 0 : (x > total ? total : x); };
-  int lo = 0, hi = B;  // the sequence: last b in [0, B) with cu[b] <= t
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (cu_at(mid) <= t) lo = mid; else hi = mid;
-  }
-  const int s0 = cu_at(lo), s1e = cu_at(lo + 1), s1 = s1e > s0 ? s1e : s0;
-  b = lo;
-  if (t < s0 || t >= s1) return false;
-  pos = cl[lo] - (s1 - s0) + (t - s0);
-  return true;
-}
-
-template <typename F>
-__device__ __forceinline__ void dec_varlen_row_at(int b, int pos, const int32_t* bt, int num_blocks, int L, int layer,
-                                                  int bs, int max_blocks, F&& write) {
-  if (pos < 0 || pos / bs >= max_blocks) return;  // before the sequence / past its block-table row
-  const int pb = bt[(int64_t)b * max_blocks + pos / bs];
-  if (pb < 0 || pb >= num_blocks) return;
-  write(((int64_t)pb * L + layer) * bs + pos % bs);
-}
-
-template <typename F>
-__device__ __forceinline__ void dec_varlen_row(int t, const int32_t* bt, const int32_t* cu, const int32_t* cl, int B,
-                                               int total, int num_blocks, int L, int layer, int bs, int max_blocks,
-                                               F&& write) {
-  int b, pos;
-  if (!dec_varlen_tok(t, cu, cl, B, total, b, pos)) return;
-  dec_varlen_row_at(b, pos, bt, num_blocks, L, layer, bs, max_blocks, write);
-}
 
 // each element of one 16-byte chunk of the cache as fp32, in order: f(i, x) for the 8 16-bit elements, or (KV8) the 16
 // e4m3fn bytes

@@ -1,5 +1,5 @@
-// The OCP e4m3fn (torch.float8_e4m3fn) conversions of the fp8 KV cache, shared by its decode and cache writes
-// (decode_kv8.hip) and its paged prefill (fa3_kv8_inst.hip).  Every e4m3 value is exact in bf16 / fp16 / fp32, so the
+// The OCP e4m3fn (torch.float8_e4m3fn) conversions of the fp8 KV cache, shared by its decode (decode_kv8.hip), its cache
+// writes (cache_write.hip) and its paged prefill (fa3_kv8_inst.hip).  Every e4m3 value is exact in bf16 / fp16 / fp32, so the
 // widening conversions run at scale 1 and round nothing; the narrowing one rounds to nearest even after an explicit clamp.
 #pragma once
 #include <type_traits>

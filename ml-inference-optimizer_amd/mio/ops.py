@@ -23,6 +23,7 @@ import os
 import ctypes as C
 import math
 import operator
+import types
 from typing import Optional, Tuple
 
 import torch
@@ -1224,7 +1225,7 @@ def paged_attention_route(query, output, k_cache, v_cache, block_tables, context
 
 
 def _write_caches(key, value, k_cache, v_cache, layer_idx, k_scale, v_scale, who):
-    """The cache checks the two cache writes share: value shares key's dtype; the caches are 5-D, equal, contiguous,
+    """The cache checks the cache writes share: value shares key's dtype; the caches are 5-D, equal, contiguous,
     and either of key's dtype or float8_e4m3fn with scales.  Returns the scale addresses (None for a 16-bit cache)."""
     if value.dtype != key.dtype:
         raise ValueError("key, value and caches must share a dtype")
@@ -1241,33 +1242,69 @@ def _write_caches(key, value, k_cache, v_cache, layer_idx, k_scale, v_scale, who
     return scales
 
 
+def _cache_write_args(key, value, k_cache, v_cache, block_tables, context_lengths, block_size, layer_idx, k_scale, v_scale,
+                      who, cu_seqlens_new=None, q=None):
+    """The argument checks the three cache writes share and what they pass to the library; host only (shapes, strides,
+    dtypes and addresses: the tensors may live on any device, the public functions call _need_cuda first).
+    cu_seqlens_new None: the single-token form, key / value [B, 1, Hkv, D], block_tables / context_lengths converted to
+    int32.  Otherwise the varlen forms: key / value [total_new, Hkv, D], strict int32 tables; q (the rotating write) is
+    checked against key.  Returns a namespace: data (key, value, cache and scale addresses, in the C order), tables
+    (block_tables, [cu_seqlens_new,] context_lengths), strides (k, v), B, T, Hkv, D, geom (num_blocks, num_layers, layer_idx,
+    block_size, max_blocks_per_seq), dt, kv8, and keep (the tensors the addresses point into)."""
+    varlen = cu_seqlens_new is not None
+    if not varlen:
+        if key.dim() != 4 or key.shape[1] != 1:
+            raise ValueError("reshape_and_cache supports q_seq_len == 1 only (attention_kernels.py:1363-1365)")
+    elif key.dim() != 3 or value.shape != key.shape:
+        raise ValueError(f"key/value must be [total_new, num_kv_heads, head_dim] with equal shapes, got "
+                         f"key={tuple(key.shape)}, value={tuple(value.shape)}")
+    dt = _dtype_id(key)
+    scales = _write_caches(key, value, k_cache, v_cache, layer_idx, k_scale, v_scale, who)
+    T, Hkv, D = key.shape[0], key.shape[-2], key.shape[-1]
+    if q is not None and (q.dim() != 3 or q.shape[0] != T or q.shape[2] != D or q.dtype != key.dtype):
+        raise ValueError(f"q must be [total_new, num_heads, head_dim] = [{T}, H, {D}] of key's dtype, got "
+                         f"{tuple(q.shape)} {q.dtype}")
+    nb, L, bs, Hc, Dc = k_cache.shape
+    if (Hc, Dc, bs) != (Hkv, D, block_size):
+        raise ValueError("cache geometry mismatch")
+    if varlen:
+        if D % 8 != 0:
+            raise ValueError(f"head_dim must be a multiple of 8, got {D}")
+        if q is not None:
+            _check_heads(q.shape[1], Hkv, D)
+        if not 0 <= int(layer_idx) < L:
+            raise ValueError(f"layer_idx {layer_idx} out of range for a {L}-layer cache")
+        _i32_dev(cu_seqlens_new, "cu_seqlens_new", 1, "of B+1 offsets", key.device)
+        if cu_seqlens_new.numel() < 1:
+            raise ValueError("cu_seqlens_new must be a contiguous 1-D int32 tensor of B+1 offsets")
+        B = cu_seqlens_new.numel() - 1
+        _i32_dev(context_lengths, "context_lengths", 1, "of B lengths", key.device)
+        _i32_dev(block_tables, "block_tables", 2, "[B, max_blocks_per_seq]", key.device)
+        if context_lengths.numel() != B or block_tables.shape[0] != B:
+            raise ValueError(f"context_lengths and block_tables must have B = {B} rows (cu_seqlens_new has B+1 entries)")
+        tables = (block_tables, cu_seqlens_new, context_lengths)
+    else:
+        B = T
+        tables = (block_tables.to(torch.int32).contiguous(), context_lengths.to(torch.int32).contiguous())
+    key, value = _rows16(key), _rows16(value)
+    strides = tuple((C.c_int64 * 2)(t.stride(0), t.stride(-2)) for t in (key, value))
+    return types.SimpleNamespace(
+        data=(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), *(scales or ())),
+        tables=tuple(t.data_ptr() for t in tables), strides=strides, B=B, T=T, Hkv=Hkv, D=D,
+        geom=(nb, L, int(layer_idx), bs, tables[0].shape[1]), dt=dt, kv8=scales is not None,
+        keep=(key, value, tables, k_scale, v_scale))
+
+
 def reshape_and_cache(key, value, k_cache, v_cache, block_tables, context_lengths, block_size: int, layer_idx: int, *,
                       k_scale=None, v_scale=None):
     """Drop-in for triton_reshape_and_cache (attention_kernels.py:1314-1407): key/value [B,1,Hkv,D].
     The caches share key's dtype, or are torch.float8_e4m3fn with k_scale / v_scale (fp32 device tensors of 1 or
     num_layers elements): the written bytes are e4m3(clamp(x * (1 / scale), -448, 448)) (mio_reshape_and_cache_kv8)."""
     _need_cuda(key, value, k_cache, v_cache)
-    if key.dim() != 4 or key.shape[1] != 1:
-        raise ValueError("reshape_and_cache supports q_seq_len == 1 only (attention_kernels.py:1363-1365)")
-    dt = _dtype_id(key)
-    scales = _write_caches(key, value, k_cache, v_cache, layer_idx, k_scale, v_scale, "reshape_and_cache")
-    B, _, Hkv, D = key.shape
-    nb, L, bs, Hc, Dc = k_cache.shape
-    if (Hc, Dc, bs) != (Hkv, D, block_size):
-        raise ValueError("cache geometry mismatch")
-    key, value = _rows16(key), _rows16(value)
-    bt = block_tables.to(torch.int32).contiguous()
-    cl = context_lengths.to(torch.int32).contiguous()
-    ks = (C.c_int64 * 2)(key.stride(0), key.stride(2))
-    vs = (C.c_int64 * 2)(value.stride(0), value.stride(2))
-    if scales is not None:
-        check(lib.mio_reshape_and_cache_kv8(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                            *scales, bt.data_ptr(), cl.data_ptr(), ks, vs, B, Hkv, D, L,
-                                            int(layer_idx), bs, bt.shape[1], dt, _stream()))
-        return
-    check(lib.mio_reshape_and_cache(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                    bt.data_ptr(), cl.data_ptr(), ks, vs, B, Hkv, D, L, int(layer_idx), bs,
-                                    bt.shape[1], dt, _stream()))
+    w = _cache_write_args(key, value, k_cache, v_cache, block_tables, context_lengths, block_size, layer_idx, k_scale,
+                          v_scale, "reshape_and_cache")
+    fn = lib.mio_reshape_and_cache_kv8 if w.kv8 else lib.mio_reshape_and_cache
+    check(fn(*w.data, *w.tables, *w.strides, w.B, w.Hkv, w.D, *w.geom[1:], w.dt, _stream()))
 
 
 def reshape_and_cache_varlen(key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths,
@@ -1280,41 +1317,10 @@ def reshape_and_cache_varlen(key, value, k_cache, v_cache, block_tables, cu_seql
     skipped.  Byte-exact copies, queued on the current stream with no host sync (graph-capturable).
     FP8 cache: as reshape_and_cache, torch.float8_e4m3fn caches with k_scale / v_scale (mio_reshape_and_cache_varlen_kv8)."""
     _need_cuda(key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths)
-    if key.dim() != 3 or value.shape != key.shape:
-        raise ValueError(f"key/value must be [total_new, num_kv_heads, head_dim] with equal shapes, got "
-                         f"key={tuple(key.shape)}, value={tuple(value.shape)}")
-    dt = _dtype_id(key)
-    scales = _write_caches(key, value, k_cache, v_cache, layer_idx, k_scale, v_scale, "reshape_and_cache_varlen")
-    T, Hkv, D = key.shape
-    nb, L, bs, Hc, Dc = k_cache.shape
-    if (Hc, Dc, bs) != (Hkv, D, block_size):
-        raise ValueError("cache geometry mismatch")
-    if D % 8 != 0:
-        raise ValueError(f"head_dim must be a multiple of 8, got {D}")
-    if not 0 <= int(layer_idx) < L:
-        raise ValueError(f"layer_idx {layer_idx} out of range for a {L}-layer cache")
-    _i32_dev(cu_seqlens_new, "cu_seqlens_new", 1, "of B+1 offsets", key.device)
-    if cu_seqlens_new.numel() < 1:
-        raise ValueError("cu_seqlens_new must be a contiguous 1-D int32 tensor of B+1 offsets")
-    B = cu_seqlens_new.numel() - 1
-    _i32_dev(context_lengths, "context_lengths", 1, "of B lengths", key.device)
-    _i32_dev(block_tables, "block_tables", 2, "[B, max_blocks_per_seq]", key.device)
-    if context_lengths.numel() != B or block_tables.shape[0] != B:
-        raise ValueError(f"context_lengths and block_tables must have B = {B} rows (cu_seqlens_new has B+1 entries)")
-    key, value = _rows16(key), _rows16(value)
-    ks = (C.c_int64 * 2)(key.stride(0), key.stride(1))
-    vs = (C.c_int64 * 2)(value.stride(0), value.stride(1))
-    if scales is not None:
-        check(lib.mio_reshape_and_cache_varlen_kv8(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(),
-                                                   v_cache.data_ptr(), *scales, block_tables.data_ptr(),
-                                                   cu_seqlens_new.data_ptr(), context_lengths.data_ptr(), ks, vs, B, T,
-                                                   Hkv, D, nb, L, int(layer_idx), bs, block_tables.shape[1], dt,
-                                                   _stream()))
-        return
-    check(lib.mio_reshape_and_cache_varlen(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                           block_tables.data_ptr(), cu_seqlens_new.data_ptr(),
-                                           context_lengths.data_ptr(), ks, vs, B, T, Hkv, D, nb, L, int(layer_idx),
-                                           bs, block_tables.shape[1], dt, _stream()))
+    w = _cache_write_args(key, value, k_cache, v_cache, block_tables, context_lengths, block_size, layer_idx, k_scale,
+                          v_scale, "reshape_and_cache_varlen", cu_seqlens_new)
+    fn = lib.mio_reshape_and_cache_varlen_kv8 if w.kv8 else lib.mio_reshape_and_cache_varlen
+    check(fn(*w.data, *w.tables, *w.strides, w.B, w.T, w.Hkv, w.D, *w.geom, w.dt, _stream()))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1424,33 +1430,10 @@ def rope_and_cache_varlen(q, key, value, k_cache, v_cache, block_tables, cu_seql
     current stream with no host sync (graph-capturable)."""
     who = "rope_and_cache_varlen"
     _need_cuda(q, key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths, cos, sin, positions, q_out)
-    if key.dim() != 3 or value.shape != key.shape:
-        raise ValueError(f"key/value must be [total_new, num_kv_heads, head_dim] with equal shapes, got "
-                         f"key={tuple(key.shape)}, value={tuple(value.shape)}")
-    dt = _dtype_id(key)
-    scales = _write_caches(key, value, k_cache, v_cache, layer_idx, k_scale, v_scale, who)
-    T, Hkv, D = key.shape
-    if q.dim() != 3 or q.shape[0] != T or q.shape[2] != D or q.dtype != key.dtype:
-        raise ValueError(f"q must be [total_new, num_heads, head_dim] = [{T}, H, {D}] of key's dtype, got "
-                         f"{tuple(q.shape)} {q.dtype}")
-    H = q.shape[1]
-    nb, L, bs, Hc, Dc = k_cache.shape
-    if (Hc, Dc, bs) != (Hkv, D, block_size):
-        raise ValueError("cache geometry mismatch")
-    if D % 8 != 0:
-        raise ValueError(f"head_dim must be a multiple of 8, got {D}")
-    _check_heads(H, Hkv, D)
-    if not 0 <= int(layer_idx) < L:
-        raise ValueError(f"layer_idx {layer_idx} out of range for a {L}-layer cache")
-    _i32_dev(cu_seqlens_new, "cu_seqlens_new", 1, "of B+1 offsets", key.device)
-    if cu_seqlens_new.numel() < 1:
-        raise ValueError("cu_seqlens_new must be a contiguous 1-D int32 tensor of B+1 offsets")
-    B = cu_seqlens_new.numel() - 1
-    _i32_dev(context_lengths, "context_lengths", 1, "of B lengths", key.device)
-    _i32_dev(block_tables, "block_tables", 2, "[B, max_blocks_per_seq]", key.device)
-    if context_lengths.numel() != B or block_tables.shape[0] != B:
-        raise ValueError(f"context_lengths and block_tables must have B = {B} rows (cu_seqlens_new has B+1 entries)")
-    max_position, rot_dim = _rope_tables_ok(cos, sin, D, scales is not None, interleaved, key.device, who)
+    w = _cache_write_args(key, value, k_cache, v_cache, block_tables, context_lengths, block_size, layer_idx, k_scale,
+                          v_scale, who, cu_seqlens_new, q)
+    T, D = w.T, w.D
+    max_position, rot_dim = _rope_tables_ok(cos, sin, D, w.kv8, interleaved, key.device, who)
     if positions is not None:
         _i32_dev(positions, "positions", 1, "of total_new positions", key.device)
         if positions.numel() != T:
@@ -1461,19 +1444,13 @@ def rope_and_cache_varlen(q, key, value, k_cache, v_cache, block_tables, cu_seql
         raise ValueError(f"{who}: q_out must have q's shape, dtype and device")
     elif q_out.stride(-1) != 1 or any(s % 8 for s in q_out.stride()[:-1]) or q_out.data_ptr() % 16:
         raise ValueError(f"{who}: q_out needs a contiguous last dim, strides that are multiples of 8 and 16-byte alignment")
-    q, key, value = _rows16(q), _rows16(key), _rows16(value)
+    q = _rows16(q)
     qs = (C.c_int64 * 2)(q.stride(0), q.stride(1))
     os_ = (C.c_int64 * 2)(q_out.stride(0), q_out.stride(1))
-    ks = (C.c_int64 * 2)(key.stride(0), key.stride(1))
-    vs = (C.c_int64 * 2)(value.stride(0), value.stride(1))
-    head = (q.data_ptr(), q_out.data_ptr(), key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr())
-    tail = (block_tables.data_ptr(), cu_seqlens_new.data_ptr(), context_lengths.data_ptr(), _ptr(positions),
-            cos.data_ptr(), sin.data_ptr(), qs, os_, ks, vs, B, T, H, Hkv, D, rot_dim, max_position,
-            int(bool(interleaved)), nb, L, int(layer_idx), bs, block_tables.shape[1], dt, _stream())
-    if scales is not None:
-        check(lib.mio_rope_and_cache_varlen_kv8(*head, *scales, *tail))
-    else:
-        check(lib.mio_rope_and_cache_varlen(*head, *tail))
+    fn = lib.mio_rope_and_cache_varlen_kv8 if w.kv8 else lib.mio_rope_and_cache_varlen
+    check(fn(q.data_ptr(), q_out.data_ptr(), *w.data, *w.tables, _ptr(positions), cos.data_ptr(), sin.data_ptr(), qs, os_,
+             *w.strides, w.B, T, q.shape[1], w.Hkv, D, rot_dim, max_position, int(bool(interleaved)), *w.geom, w.dt,
+             _stream()))
     return q_out
 
 

@@ -125,6 +125,53 @@ def test_kv8_write_one_token_byte_exact(dtype, per_layer):
     assert _bytes(kc_d)[..., 0].ne(sentinel).sum() > 0
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("kv8", [False, True])
+@pytest.mark.parametrize("Hkv,D", [(2, 16), (40, 128)])
+def test_write_forms_share_the_chunk_store(dtype, kv8, Hkv, D):
+    """The single-token write and the varlen write of one new token per sequence leave byte-identical caches, 16-bit and fp8:
+    both go through the one chunk store of csrc/cache_write.hip.  (2, 16) is the smallest fp8 chunk; (40, 128) is 640 16-bit /
+    320 fp8 chunks per token, more than one pass of the single-token kernel's 256 threads in both cache kinds.  K and V are
+    strided views into one fused projection; sequence 3 is empty and sequence 4's position is past its table row: neither
+    writes.  All comparisons are exact: the source bits for a 16-bit cache, _quant_ref for fp8."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(7)
+    B, bs, L, layer, maxb, H = 5, 16, 2, 1, 4, 2 * Hkv
+    ctx = torch.tensor([1, 16, 17, 0, 65], dtype=torch.int32)  # lengths after the append
+    qkv = (torch.randn(B, (H + 2 * Hkv) * D, generator=g) * 100).to(dtype)
+    key = qkv[:, H * D:(H + Hkv) * D].view(B, Hkv, D)
+    value = qkv[:, (H + Hkv) * D:].view(B, Hkv, D)
+    nb = B * maxb + 3
+    bt = torch.randperm(nb, generator=g)[:B * maxb].view(B, maxb).to(torch.int32)
+    cu = torch.arange(B + 1, dtype=torch.int32)
+    scales = dict(k_scale=torch.tensor([0.5, 0.37], device=DEV), v_scale=torch.tensor([2.0, 1.75], device=DEV)) if kv8 else {}
+    sentinel = torch.full((nb, L, bs, Hkv, D * (1 if kv8 else 2)), 0x5A, dtype=torch.uint8).view(F8 if kv8 else dtype)
+    qkv_d = qkv.to(DEV)
+    key_d = qkv_d[:, H * D:(H + Hkv) * D].view(B, Hkv, D)
+    value_d = qkv_d[:, (H + Hkv) * D:].view(B, Hkv, D)
+    one = [sentinel.to(DEV), sentinel.to(DEV)]
+    var = [sentinel.to(DEV), sentinel.to(DEV)]
+    ops.reshape_and_cache(key_d[:, None], value_d[:, None], *one, bt.to(DEV), ctx.to(DEV), bs, layer, **scales)
+    ops.reshape_and_cache_varlen(key_d, value_d, *var, bt.to(DEV), cu.to(DEV), ctx.to(DEV), bs, layer, **scales)
+    torch.cuda.synchronize()
+    ref = [sentinel.clone(), sentinel.clone()]
+    written = torch.zeros(nb, L, bs, dtype=torch.bool)
+    for b in range(B):
+        pos = int(ctx[b]) - 1
+        if pos < 0 or pos // bs >= maxb:
+            continue
+        row = (int(bt[b, pos // bs]), layer, pos % bs)
+        written[row] = True
+        ref[0][row] = _quant_ref(key[b], 0.37) if kv8 else key[b]
+        ref[1][row] = _quant_ref(value[b], 1.75) if kv8 else value[b]
+    assert written.sum() == 3
+    for what, a, v, r in zip("KV", one, var, ref):
+        a, v, r = _bytes(a), _bytes(v), _bytes(r)
+        assert torch.equal(a, v), (what, (a != v).nonzero()[:8])            # the two forms, byte for byte
+        assert (a[~written] == 0x5A).all() and (v[~written] == 0x5A).all(), what  # nothing outside the written rows of the layer
+        assert torch.equal(a[written], r[written]), (what, (a != r).nonzero()[:8])  # the written rows: the reference's bytes
+
+
 # ---- decode -----------------------------------------------------------------------------------------------------------------
 def _judge(out, q, kc, vc, ks, vs, bt, ctx, bs, layer, left, dtype, route, what):
     """The decode result against _decode_check's fp64 reference over the dequantised cache (windowed when left >= 0):

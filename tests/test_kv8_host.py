@@ -1,6 +1,6 @@
 """CPU-only tests of the fp8 (e4m3fn) paged KV cache's C ABI: the new symbols are bound and the ABI version is unchanged,
 the host-only route query mio_fa3_decode_kv8_route picks the named kernel for the benchmark cases, the C-level refusals
-carry their messages, and every fp8 decode and cache-write kernel of csrc/decode_kv8.hip compiles without scratch."""
+carry their messages, and every fp8 decode kernel of csrc/decode_kv8.hip compiles without scratch (the unit holds decode only)."""
 import ctypes as C
 import re
 
@@ -115,23 +115,24 @@ def test_kv8_write_refusals_c(fn):
     assert _write_rc(fn, dtype=2) < 0 and "bf16 or fp16" in _err()
 
 
+# the fp8 cache writes (cache_write_kernel / cache_write_varlen_kernel, two instantiations each) live in csrc/cache_write.hip:
+# tests/test_rope_host.py::test_rope_kernels_isa holds them to the same checks
 _KV8_KERNELS = ["decode_paged_kv8_kernel", "decode_paged_kv8_win_kernel", "decode_rows_kv8_kernel",
-                "decode_rows_kv8_win_kernel", "decode_gqa_kv8_kernel", "decode_gqa_kv8_win_kernel",
-                "reshape_and_cache_kv8_kernel", "reshape_and_cache_varlen_kv8_kernel"]
+                "decode_rows_kv8_win_kernel", "decode_gqa_kv8_kernel", "decode_gqa_kv8_win_kernel"]
 
 
 def test_kv8_kernels_isa(tmp_path):
-    """Every fp8 decode kernel (plain and windowed, bf16 / fp16, both head-dim forms) and both cache writes exist, with no
-    scratch and no spills; the matrix-core form reads V^T with the 8-bit transposed LDS read."""
+    """Every fp8 decode kernel (plain and windowed, bf16 / fp16, both head-dim forms) exists, with no scratch and no spills;
+    the matrix-core form reads V^T with the 8-bit transposed LDS read; the unit defines no cache-write kernel."""
     text = _isa.device_isa(tmp_path, "decode_kv8.hip", [], attention=False).read_text()
     for name in _KV8_KERNELS:
         blks = _isa.metadata(text, rf"_Z\d+{name}\w+")
-        want = 2 if name.startswith("reshape") else 4
-        assert len(blks) == want, name
+        assert len(blks) == 4, name
         for blk in blks:
             _isa.check_fits_256(blk)
     # the 16-bit decode kernels' names are not reused (the ISA test of decode_paged.hip counts them by name)
     assert not _isa.metadata(text, r"_Z\d+decode_(paged|rows|gqa)_(win_)?kernel\w+")
+    assert not _isa.metadata(text, r"_Z\d+(reshape_and_cache|cache_write|rope_)\w+")  # decode only: the writes are cache_write.hip's
     starts = [m.start() for m in re.finditer(r"^_Z\d+decode_gqa_kv8_kernel\w+:", text, re.M)]
     assert len(starts) == 4
     for a in starts:

@@ -1,7 +1,7 @@
 """CPU-only tests of the attention forward over the paged KV cache (mio_fa3_fwd_paged) and of the many-token cache write
 (mio_reshape_and_cache_varlen): the C-ABI symbols are bound, the route table and every refusal are reported without a GPU,
-ops raises on bad arguments before it calls the library, and the paged kernels pass the ISA soundness checks of the dense
-pipelined kernels."""
+ops raises on bad arguments before it calls the library (every ValueError of the cache writes' shared argument builder by its
+text), and the paged kernels pass the ISA soundness checks of the dense pipelined kernels."""
 import ctypes as C
 
 import pytest
@@ -172,6 +172,118 @@ def test_reshape_and_cache_varlen_errors_without_gpu():
     assert call(D=60) != 0 and b"sizes" in _lib.lib.mio_last_error()
     assert call(dt=3) != 0 and b"dtype" in _lib.lib.mio_last_error()
     assert call(T=0) == 0 and call(B=0) == 0  # nothing to write: no launch
+
+
+def _write_tensors(dtype=torch.bfloat16, T=10, Hkv=2, D=64, cache_dtype=None, L=2, bs=64):
+    """Valid CPU arguments of ops._cache_write_args for a varlen write of T tokens in 2 sequences."""
+    k = torch.zeros(T, Hkv, D, dtype=dtype)
+    c = torch.zeros(8, L, bs, Hkv, D, dtype=cache_dtype or dtype)
+    return dict(key=k, value=k.clone(), k_cache=c, v_cache=c.clone(), block_tables=torch.zeros(2, 8, dtype=torch.int32),
+                context_lengths=torch.tensor([4, 6], dtype=torch.int32), block_size=bs, layer_idx=1, k_scale=None,
+                v_scale=None, who="f", cu_seqlens_new=torch.tensor([0, 4, T], dtype=torch.int32))
+
+
+def test_cache_write_args_returns_the_c_arguments():
+    """The host-only builder of the three cache writes on CPU tensors: addresses, strides and geometry in the C order."""
+    from mio import ops
+    F8 = torch.float8_e4m3fn
+    a = _write_tensors()
+    a["key"] = torch.zeros(10, 3 * 2 * 64, dtype=torch.bfloat16)[:, 128:256].view(10, 2, 64)  # a view of a fused projection
+    w = ops._cache_write_args(**a)
+    assert w.data == (a["key"].data_ptr(), a["value"].data_ptr(), a["k_cache"].data_ptr(), a["v_cache"].data_ptr())
+    assert w.tables == (a["block_tables"].data_ptr(), a["cu_seqlens_new"].data_ptr(), a["context_lengths"].data_ptr())
+    assert [tuple(s) for s in w.strides] == [(384, 64), (128, 64)]
+    assert (w.B, w.T, w.Hkv, w.D, w.geom, w.dt, w.kv8) == (2, 10, 2, 64, (8, 2, 1, 64, 8), 0, False)
+    # fp8 cache: the scale addresses of layer_idx follow the caches'
+    a = _write_tensors(torch.float16, cache_dtype=F8)
+    a.update(k_scale=torch.ones(2), v_scale=torch.ones(1), q=torch.zeros(10, 4, 64, dtype=torch.float16))
+    w = ops._cache_write_args(**a)
+    assert w.data[4:] == (a["k_scale"].data_ptr() + 4, a["v_scale"].data_ptr()) and w.kv8 and w.dt == 1
+    # single-token form: [B, 1, Hkv, D], tables of any integer type converted to int32
+    a = _write_tensors()
+    a.update(key=a["key"][:2, None], value=a["value"][:2, None], cu_seqlens_new=None, block_tables=a["block_tables"].long())
+    w = ops._cache_write_args(**a)
+    assert (w.B, w.T, w.Hkv, w.D, w.geom) == (2, 2, 2, 64, (8, 2, 1, 64, 8)) and len(w.tables) == 2
+    assert [tuple(s) for s in w.strides] == [(128, 64), (128, 64)] and w.keep[2][0].dtype == torch.int32
+
+
+_T = _write_tensors
+_F8 = torch.float8_e4m3fn
+_SHARE = "key, value and caches must share a dtype"
+_CU = "cu_seqlens_new must be a contiguous 1-D int32 tensor of B+1 offsets"
+# (changes to the valid arguments, the ValueError's text): one case per raise of the builder and of the checks it calls
+_WRITE_ERRORS = [
+    (lambda a: a.update(key=a["key"][:2], value=a["value"][:2], cu_seqlens_new=None),
+     "reshape_and_cache supports q_seq_len == 1 only (attention_kernels.py:1363-1365)"),
+    (lambda a: a.update(key=a["key"][:2, None].expand(2, 2, 2, 64), cu_seqlens_new=None),
+     "reshape_and_cache supports q_seq_len == 1 only (attention_kernels.py:1363-1365)"),
+    (lambda a: a.update(value=a["value"][:9]), "key/value must be [total_new, num_kv_heads, head_dim] with equal shapes, got "
+                                               "key=(10, 2, 64), value=(9, 2, 64)"),
+    (lambda a: a.update(key=a["key"][0], value=a["value"][0]),
+     "key/value must be [total_new, num_kv_heads, head_dim] with equal shapes, got key=(2, 64), value=(2, 64)"),
+    (lambda a: a.update(key=a["key"].float(), value=a["value"].float()), "HIP kernels compute in bf16 or fp16, got torch.float32"),
+    (lambda a: a.update(value=a["value"].half()), _SHARE),
+    (lambda a: a.update(k_cache=a["k_cache"].to(torch.int8), v_cache=a["v_cache"].to(torch.int8)),
+     "an 8-bit KV cache must be torch.float8_e4m3fn (OCP e4m3), got torch.int8"),
+    (lambda a: a.update(k_cache=a["k_cache"][0], v_cache=a["v_cache"][0]),
+     "caches must be [num_blocks, num_layers, block_size, num_kv_heads, head_dim] with equal shapes"),
+    (lambda a: a.update(v_cache=a["v_cache"][:4]),
+     "caches must be [num_blocks, num_layers, block_size, num_kv_heads, head_dim] with equal shapes"),
+    (lambda a: a.update(v_cache=a["v_cache"].half()), _SHARE),
+    (lambda a: a.update(k_cache=a["k_cache"].half(), v_cache=a["v_cache"].half()), _SHARE),
+    (lambda a: a.update(k_cache=a["k_cache"].transpose(0, 1).contiguous().transpose(0, 1)), "caches must be contiguous"),
+    (lambda a: a.update(k_scale=torch.ones(1)),
+     "f: k_scale / v_scale apply to an fp8 (float8_e4m3fn) cache only, got a torch.bfloat16 cache"),
+    (lambda a: a.update(_T(cache_dtype=_F8), k_scale=torch.ones(1)), "f: an fp8 (float8_e4m3fn) cache requires k_scale and v_scale"),
+    (lambda a: a.update(_T(cache_dtype=_F8), k_scale=torch.ones(1), v_scale=torch.ones(1).double()),
+     "f: v_scale must be a contiguous float32 tensor"),
+    (lambda a: a.update(_T(cache_dtype=_F8), k_scale=1.0, v_scale=torch.ones(1)), "f: k_scale must be a contiguous float32 tensor"),
+    (lambda a: a.update(_T(cache_dtype=_F8), k_scale=torch.ones(3), v_scale=torch.ones(1)),
+     "f: k_scale must hold 1 or num_layers = 2 elements, got 3"),
+    (lambda a: a.update(_T(cache_dtype=_F8), k_scale=torch.ones(1), v_scale=torch.ones(1, device="meta")),
+     "f: v_scale must be on the device of the cache"),
+    (lambda a: a.update(_T(cache_dtype=_F8), k_scale=torch.ones(2), v_scale=torch.ones(2), layer_idx=2),
+     "f: layer_idx 2 out of range for a 2-layer cache"),
+    (lambda a: a.update(_T(D=72, cache_dtype=_F8), k_scale=torch.ones(1), v_scale=torch.ones(1)),
+     "an fp8 KV cache needs head_dim to be a multiple of 16, got head_dim 72"),
+    (lambda a: a.update(q=torch.zeros(9, 4, 64, dtype=torch.bfloat16)),
+     "q must be [total_new, num_heads, head_dim] = [10, H, 64] of key's dtype, got (9, 4, 64) torch.bfloat16"),
+    (lambda a: a.update(q=torch.zeros(10, 4, 64, dtype=torch.float16)),
+     "q must be [total_new, num_heads, head_dim] = [10, H, 64] of key's dtype, got (10, 4, 64) torch.float16"),
+    (lambda a: a.update(block_size=32), "cache geometry mismatch"),
+    (lambda a: a.update(key=a["key"][:, :1], value=a["value"][:, :1]), "cache geometry mismatch"),
+    (lambda a: a.update(_T(D=60)), "head_dim must be a multiple of 8, got 60"),
+    (lambda a: a.update(q=torch.zeros(10, 3, 64, dtype=torch.bfloat16)), "num_heads 3 must be a multiple of num_kv_heads 2"),
+    (lambda a: a.update(_T(D=136), q=torch.zeros(10, 4, 136, dtype=torch.bfloat16)),
+     "head_dim must be a multiple of 8 and <= 128, got 136"),
+    (lambda a: a.update(layer_idx=2), "layer_idx 2 out of range for a 2-layer cache"),
+    (lambda a: a.update(layer_idx=-1), "layer_idx -1 out of range for a 2-layer cache"),
+    (lambda a: a.update(cu_seqlens_new=a["cu_seqlens_new"].long()), _CU),
+    (lambda a: a.update(cu_seqlens_new=a["cu_seqlens_new"][None]), _CU),
+    (lambda a: a.update(cu_seqlens_new=torch.zeros(6, dtype=torch.int32)[::2]), _CU),
+    (lambda a: a.update(cu_seqlens_new=a["cu_seqlens_new"][:0]), _CU),
+    (lambda a: a.update(cu_seqlens_new=a["cu_seqlens_new"].to("meta")), "cu_seqlens_new must be on the device of q"),
+    (lambda a: a.update(context_lengths=a["context_lengths"].long()),
+     "context_lengths must be a contiguous 1-D int32 tensor of B lengths"),
+    (lambda a: a.update(block_tables=a["block_tables"][0]),
+     "block_tables must be a contiguous 2-D int32 tensor [B, max_blocks_per_seq]"),
+    (lambda a: a.update(block_tables=a["block_tables"].to("meta")), "block_tables must be on the device of q"),
+    (lambda a: a.update(context_lengths=a["context_lengths"][:1]),
+     "context_lengths and block_tables must have B = 2 rows (cu_seqlens_new has B+1 entries)"),
+    (lambda a: a.update(block_tables=torch.zeros(3, 8, dtype=torch.int32)),
+     "context_lengths and block_tables must have B = 2 rows (cu_seqlens_new has B+1 entries)"),
+]
+
+
+@pytest.mark.parametrize("change,text", _WRITE_ERRORS, ids=[f"{i}-{t[:28]}" for i, (_, t) in enumerate(_WRITE_ERRORS)])
+def test_cache_write_args_errors(change, text):
+    from mio import ops
+    a = _write_tensors()
+    assert ops._cache_write_args(**a).B == 2  # the neighbour is valid
+    change(a)
+    with pytest.raises(ValueError) as e:
+        ops._cache_write_args(**a)
+    assert str(e.value) == text
 
 
 @pytest.mark.parametrize("type_id", [0, 1])

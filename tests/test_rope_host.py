@@ -1,6 +1,6 @@
 """CPU-only tests of rotary position embedding: the three C-ABI symbols are bound, every host refusal returns before a launch
 with a message that names the function, the ops functions refuse CPU tensors and malformed arguments, rope_tables is the
-fp64 formula cast once, every kernel of csrc/rope.hip compiles for gfx950 without scratch and stores 16 bytes at a time,
+fp64 formula cast once, every kernel of csrc/cache_write.hip compiles for gfx950 without scratch and stores 16 bytes at a time,
 and a config without rotary builds the attention layers as before.  The checker's own rounding (tests/_rope_check.py) is
 tested against exhaustive and randomised cases."""
 import ctypes as C
@@ -168,29 +168,34 @@ def test_rope_table_argument_checks():
             ops._rope_tables_ok(cos, sin, D, kv8, il, dev, "f")
 
 
-_ROPE_KERNELS = {"rope_and_cache_varlen_kernel": 8, "rope_rows_kernel": 4}  # name -> instantiations
+# mangled-name pattern -> instantiations: the rotating and rotation kernels (bf16 / fp16, both pairings, 16-bit and fp8 cache), the
+# plain writes' fp8 forms per source dtype and their 16-bit forms once (over unsigned short: they move bits)
+_WRITE_UNIT_KERNELS = {r"rope_and_cache_varlen_kernel": 8, r"rope_rows_kernel": 4, r"cache_write_kernelI\w+Lb1E": 2,
+                       r"cache_write_varlen_kernelI\w+Lb1E": 2, r"cache_write_kernelItLb0E": 1, r"cache_write_varlen_kernelItLb0E": 1}
 
 
 def test_rope_kernels_isa(tmp_path):
-    """Every rotary kernel (bf16 / fp16, both pairings, 16-bit and fp8 cache) exists, with no scratch and no spills, moves
-    data with 16-byte stores only and uses no LDS; the decode units' kernel names are not reused."""
-    text = _isa.device_isa(tmp_path, "rope.hip", [], attention=False).read_text()
-    for name, want in _ROPE_KERNELS.items():
+    """Every kernel of the write unit (csrc/cache_write.hip: the rotating writes, the standalone rotation and the plain cache
+    writes) exists, with no scratch and no spills, moves data with 16-byte stores only and uses no LDS; the decode units'
+    kernel names are not reused."""
+    text = _isa.device_isa(tmp_path, "cache_write.hip", [], attention=False).read_text()
+    for name, want in _WRITE_UNIT_KERNELS.items():
         blks = _isa.metadata(text, rf"_Z\d+{name}\w+")
         assert len(blks) == want, name
         for blk in blks:
             _isa.check_fits_256(blk)
         bodies = _isa.kernels(text, rf"_Z\d+{name}")
         assert len(bodies) == want
+    total = sum(_WRITE_UNIT_KERNELS.values())
     assert not _isa.metadata(text, r"_Z\d+(decode_|reshape_and_cache)\w+")
     lds = re.findall(r"\.group_segment_fixed_size:\s+(\d+)", text)
-    assert len(lds) == 12 and set(lds) == {"0"}
+    assert len(lds) == total == 18 and set(lds) == {"0"}
     code = [l.split("//")[0].split(";")[0] for l in text.splitlines()]
     stores = [l for l in code if re.search(r"\b(global|flat|buffer|scratch)_store", l)]
     assert stores and all("global_store_dwordx4" in l for l in stores), [l for l in stores if "dwordx4" not in l][:4]
     assert not [l for l in code if re.search(r"\bscratch_|\bds_(read|write|load|store)", l)]
     # the 16-bit loads and the table reads are 16 bytes wide; narrower loads are the int32 lookups and the fp8 scales
-    assert sum("global_load_dwordx4" in l for l in code) >= 8 * 12
+    assert sum("global_load_dwordx4" in l for l in code) >= 8 * total
 
 
 def test_rotary_off_constructs_layers_as_before():

@@ -110,8 +110,10 @@ def test_decode_window_refusals_ops(ws):
 
 
 def test_windowed_decode_kernels_isa(tmp_path):
-    """The windowed decode kernels exist for every unwindowed one, under their own names, with no scratch."""
+    """The windowed decode kernels exist for every unwindowed one, under their own names, with no scratch; the unit holds
+    decode only (the cache writes are csrc/cache_write.hip's)."""
     text = _isa.device_isa(tmp_path, "decode_paged.hip", [], attention=False).read_text()
+    assert not _isa.metadata(text, r"_Z\d+(reshape_and_cache|cache_write|rope_)\w+")
     for base in ("decode_paged", "decode_rows", "decode_gqa"):
         plain = _isa.metadata(text, rf"_Z\d+{base}_kernel\w+")
         win = _isa.metadata(text, rf"_Z\d+{base}_win_kernel\w+")
