@@ -388,8 +388,13 @@ extern "C" size_t mio_ln_stats_bytes(int64_t M, int32_t width) {
 // The consumer's read-out relies on sum_k w_scaled[n][k] = 0 (that is what removes the activations' mean); after rounding to 16
 // bits the sum is off by ~sqrt(K / 12) ulp, and the product picks up mean(x) times that.  So the rounding DIRECTION of a few
 // elements is flipped (those whose exact value sits closest to the midpoint of its two neighbours: the flip leaves their own
-// error almost unchanged, weighed against how much of the sum it removes) until no flip brings the row sum closer to zero:
-// <= 64 greedy steps per row, one-time weight preparation.
+// error almost unchanged, weighed against how much of the sum it removes) until no flip brings the row sum closer to zero.
+// One-time weight preparation.  Every step strictly lowers |sum| and the loop leaves as soon as no flip does, so the step
+// count only has to be large enough: a row starts about sqrt(K / 12) ulp off and a flip takes off at most one ulp of its own
+// element, less where a gamma spread over many binades leaves the residue to the K / 13 or so elements of the top binade.
+// A fixed budget of 64 ran out there (K 8192, gamma = +-2^-6 .. 2^6: 32 ulp of the row's largest element were left), so the
+// budget is max(64, K).  Rows that 64 steps had cut short (wide rows may be among them under any gamma) now come out closer to a
+// zero sum than before; rows that were done within 64 steps are prepared bit for bit as before.
 template <typename T, int EPT>  // EPT: elements per thread (K <= 256 * EPT)
 __global__ __launch_bounds__(256) void ln_fold_weight_kernel(const T* __restrict__ w, int64_t ldw, const T* __restrict__ gamma,
                                                              const T* __restrict__ beta, const T* __restrict__ bias,
@@ -433,7 +438,8 @@ __global__ __launch_bounds__(256) void ln_fold_weight_kernel(const T* __restrict
     }
   }
   auto val = [](uint16_t b) { return (float)__builtin_bit_cast(T, b); };
-  for (int it = 0; it < 64; ++it) {
+  const int budget = K > 64 ? K : 64;
+  for (int it = 0; it < budget; ++it) {
     s_c[t] = sum;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {

@@ -729,6 +729,19 @@ def ln_stats_shape(M: int, width: int):
     return ((width + 255) // 256, (M + 255) // 256 * 256, 2)
 
 
+def ln_stats_for_launch(ln_stats: torch.Tensor, M: int) -> torch.Tensor:
+    """The statistics as gemm_ln's consumer launch reads them: up to 8 slots as they are; more (a stream wider than 2048 columns)
+    summed in equal groups of consecutive slots (mio_ln_stats_reduce) down to the largest divisor of the count that the
+    kernel's LDS region holds."""
+    slots = ln_stats.shape[0]
+    if slots <= 8:
+        return ln_stats
+    out_slots = max(s_ for s_ in range(1, 9) if slots % s_ == 0)
+    red = torch.empty((out_slots,) + tuple(ln_stats.shape[1:]), dtype=torch.float32, device=ln_stats.device)
+    check(lib.mio_ln_stats_reduce(ln_stats.data_ptr(), slots, red.data_ptr(), out_slots, M, _stream()))
+    return red
+
+
 def _gemm_ln_args(x, M, N, K, x_blocked=False, residual=None, res_blocked=False, **_):
     """gemm_ln's x and residual as mio_gemm_ln_bw and mio_gemm_route take them: (x2, ldx, r2, ldr).  Host-only."""
     M, N, K = int(M), int(N), int(K)
@@ -787,12 +800,8 @@ def gemm_ln(x: torch.Tensor, w_blocked: torch.Tensor, bias: Optional[torch.Tenso
         want = ln_stats_shape(M, K)
         if ln_stats.dtype != torch.float32 or tuple(ln_stats.shape) != want or not ln_stats.is_contiguous() or ln_stats.device != x.device:
             raise ValueError(f"ln_stats: expected a contiguous fp32 tensor of shape {want}")
-        slots = want[0]
-        if slots > 8:  # a stream wider than 2048 columns: sum the slots in groups down to what the kernel's LDS region holds
-            out_slots = max(s_ for s_ in range(1, 9) if slots % s_ == 0)
-            red = torch.empty((out_slots,) + want[1:], dtype=torch.float32, device=x.device)
-            check(lib.mio_ln_stats_reduce(ln_stats.data_ptr(), slots, red.data_ptr(), out_slots, M, _stream()))
-            ln_stats, slots = red, out_slots
+        ln_stats = ln_stats_for_launch(ln_stats, M)
+        slots = ln_stats.shape[0]
     lo = hi = 0
     val = 1.0
     if col_scale is not None:

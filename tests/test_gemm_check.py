@@ -169,3 +169,156 @@ def test_subnormal_fp16_bound():
     y2[0, 0] = (y2[0, 0].double() + 2 * 2.0 ** -24).to(torch.float16)
     with pytest.raises(AssertionError, match="rounding bound"):
         gc.check(y2, ref, torch.float16, "t128", bars=False)
+
+
+# ---- LayerNorm fold: reference_fold() against an fp32 model of the consumer, and the defects it must reject ----------------------
+FM, FN, FK = 384, 256, 512  # three 128-row groups, two statistic slots
+EPS = 1e-5
+# Limits of this self-test (no kernel route): a result within half an ulp of ref has a normwise error of at most 1 u per row and
+# per fragment; rounding errors uniform in +-ulp/2 on significands uniform in [1, 2) give a mean row of 2 / sqrt(12) / sqrt(7/3)
+# = 0.38 u.  The fp32 model adds its accumulation and rstd noise: a quarter more, and up to 5 % of the elements across a tie.  On
+# the stream with a mean of 32 deviations a real rstd error of one u' (2 m^2 + 1) / 2 = 1.2e-4 is a quarter of fp16's u, 4.9e-4:
+# up to a quarter of the elements may cross a tie there.
+FOLD_LIMITS = {1.0: (0.05, 1.25, 0.5, 1.25), 32.0: (0.25, 1.25, 0.5, 1.25)}
+
+
+def _fold_inputs(dtype, mean_over_std, glu=False, seed=0):
+    """A stream with row scales spread over 0.5 .. 2 (so that a neighbour's rstd is a wrong one), row 7 all zero; fp32 slot
+    sums of the stored stream; centred weights rounded to the dtype, folded biases."""
+    g = torch.Generator().manual_seed(seed)
+    scale = 2.0 ** (torch.rand(FM, 1, generator=g) * 2 - 1)
+    y = ((torch.randn(FM, FK, generator=g) + mean_over_std) * scale)
+    y[7] = 0
+    y = y.to(dtype)
+    yd = y.double().view(FM, FK // 256, 256)
+    stats = torch.stack([yd.sum(-1).t(), (yd * yd).sum(-1).t()], -1).float().contiguous()  # [slots, M, 2]
+    gamma = (1 + 0.2 * torch.randn(FK, generator=g)).to(dtype).double()
+    out = {"y": y, "stats": stats}
+    for nm in ("", "_gate") if glu else ("",):
+        w = (torch.randn(FN, FK, generator=g) * 0.05).to(dtype).double() * gamma
+        out["w_plain" + nm] = gc.rn16(w, dtype).to(dtype)                       # gamma o W, uncentred
+        out["ws" + nm] = gc.rn16(w - w.mean(1, keepdim=True), dtype).to(dtype)
+        out["b" + nm] = (torch.randn(FN, generator=g) * 0.3).to(dtype)
+    return out
+
+
+def _rstd32(stats, K, eps=EPS):
+    """The kernel's operation order in fp32: slots added one by one, the rounded 1 / K, mu, sq ik - mu mu, clamp, + eps, rsqrt."""
+    sm, sq = torch.zeros_like(stats[0, :, 0]), torch.zeros_like(stats[0, :, 0])
+    for s in range(stats.shape[0]):
+        sm, sq = sm + stats[s, :, 0], sq + stats[s, :, 1]
+    ik = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(K), dtype=torch.float32)
+    mu = sm * ik
+    return torch.rsqrt(torch.clamp_min(sq * ik - mu * mu, 0.0) + torch.tensor(eps, dtype=torch.float32))
+
+
+def _emulate(d, dtype, act="none", r=None, ws=None, bias_first=False, up_unscaled=False):
+    """fp32 model of the consumer: fp32 accumulation, acc * rstd + b', the activation, one rounding to the dtype."""
+    r = (_rstd32(d["stats"], FK) if r is None else r)[:, None]
+    y = d["y"].float()
+    pre = lambda w, b: (y @ w.float().t() + b.float()) * r if bias_first else (y @ w.float().t()) * r + b.float()  # noqa: E731
+    z = pre(d["ws"] if ws is None else ws, d["b"])
+    if act == "swiglu":
+        if up_unscaled:
+            z = y @ d["ws"].float().t() + d["b"].float()
+        z = torch.nn.functional.silu(pre(d["ws_gate"], d["b_gate"])) * z
+    elif act == "gelu":
+        z = torch.nn.functional.gelu(z, approximate="tanh")
+    return z.to(dtype)
+
+
+def _fold_ref(d, act="none"):
+    return gc.reference_fold(d["y"], d["stats"], d["ws"], d["b"], eps=EPS, act=act, ws_gate=d.get("ws_gate"),
+                             bias_gate=d.get("b_gate"))
+
+
+def _fold_rejected(z, ref, dtype, mean):
+    """Rejected by a judgement of the values (the element bound or a statistical limit), not by a mismatch of shape or dtype."""
+    with pytest.raises(AssertionError, match=r"outside the rounding bound|\(bar "):
+        gc.check(z, ref, dtype, "fold model", bars=FOLD_LIMITS[mean], what="planted defect")
+
+
+FOLD_PARAMS = [(dt, m) for dt in (torch.bfloat16, torch.float16) for m in (1.0, 32.0)]
+FOLD_IDS = [f"{str(dt).split('.')[-1]}-mean{int(m)}" for dt, m in FOLD_PARAMS]
+
+
+def test_reference_fold_is_layernorm_then_linear():
+    """With exact statistics and an exactly centred weight the fold reference is the oracle's LayerNorm -> linear."""
+    d = _fold_inputs(torch.bfloat16, 1.0)
+    yd = d["y"].double().view(FM, FK // 256, 256)
+    stats = torch.stack([yd.sum(-1).t(), (yd * yd).sum(-1).t()], -1)  # fp64
+    w = torch.randn(FN, FK, dtype=torch.float64, generator=torch.Generator().manual_seed(9)) * 0.05
+    gamma, beta = torch.rand(FK, dtype=torch.float64) + 0.5, torch.randn(FK, dtype=torch.float64) * 0.1
+    wg = w * gamma
+    ref = gc.reference_fold(d["y"], stats, wg - wg.mean(1, keepdim=True), d["b"].double() + w @ beta, eps=EPS)
+    want = oracle.layernorm(d["y"], gamma, beta, EPS).double() @ w.t() + d["b"].double()
+    rows = torch.arange(FM) != 7  # (the zero row: eps as fp32 in the reference, fp64 in the oracle; both give b')
+    assert torch.allclose(ref.y[rows], want[rows], rtol=0, atol=1e-9)
+
+
+def test_rstd_interval_order_of_magnitude():
+    """dr / r grows with the square of the stream's mean: about 1e-6 at 1 deviation, 8e-4 at 32 (two slots)."""
+    for m, lo, hi in ((1.0, 3e-7, 3e-6), (32.0, 3e-4, 2e-3)):
+        d = _fold_inputs(torch.float16, m)
+        r, r_lo, r_hi = gc.rstd_interval(d["stats"], FK, EPS)
+        rel = (torch.maximum(r_hi - r, r - r_lo) / r)[torch.arange(FM) != 7]
+        assert lo < rel.median().item() < hi, (m, rel.median().item())
+        assert bool((r_lo <= r).all() and (r <= r_hi).all())
+
+
+@pytest.mark.parametrize("dtype,mean", FOLD_PARAMS, ids=FOLD_IDS)
+@pytest.mark.parametrize("act", ["none", "gelu", "swiglu"])
+def test_fold_model_passes(dtype, mean, act):
+    d = _fold_inputs(dtype, mean, glu=act == "swiglu")
+    ref = _fold_ref(d, act)
+    st = gc.check(_emulate(d, dtype, act), ref, dtype, "fold model", bars=FOLD_LIMITS[mean], what="fp32 model")
+    assert ("fold model" not in {k[1] for k in gc.STATS}) and st["frag"] > 0
+    # the zero row: r = eps^-1/2 on a zero accumulator, the output is act(b') within the epilogue's own terms
+    assert ref.tol[7].max().item() <= 64 * gc.EPS32 * max(1.0, ref.y[7].abs().max().item())
+    # the rstd of the fp32 model lies inside the interval
+    r32 = _rstd32(d["stats"], FK).double()
+    _, r_lo, r_hi = gc.rstd_interval(d["stats"], FK, EPS)
+    assert bool((r_lo <= r32).all() and (r32 <= r_hi).all())
+
+
+@pytest.mark.parametrize("dtype,mean", FOLD_PARAMS, ids=FOLD_IDS)
+def test_rejects_rstd_of_the_neighbouring_16_rows(dtype, mean):
+    d = _fold_inputs(dtype, mean)
+    r = _rstd32(d["stats"], FK)
+    r[16:32] = r[0:16].clone()
+    _fold_rejected(_emulate(d, dtype, r=r), _fold_ref(d), dtype, mean)
+
+
+@pytest.mark.parametrize("dtype,mean", FOLD_PARAMS, ids=FOLD_IDS)
+def test_rejects_a_statistics_slot_left_out_for_one_group(dtype, mean):
+    d = _fold_inputs(dtype, mean)
+    r = _rstd32(d["stats"], FK)
+    r[128:256] = _rstd32(d["stats"][:1], FK)[128:256]  # the group's second slot never arrived
+    _fold_rejected(_emulate(d, dtype, "gelu", r=r), _fold_ref(d, "gelu"), dtype, mean)
+
+
+@pytest.mark.parametrize("dtype,mean", FOLD_PARAMS, ids=FOLD_IDS)
+def test_rejects_rstd_applied_after_the_bias(dtype, mean):
+    d = _fold_inputs(dtype, mean)
+    _fold_rejected(_emulate(d, dtype, bias_first=True), _fold_ref(d), dtype, mean)
+
+
+@pytest.mark.parametrize("dtype,mean", FOLD_PARAMS, ids=FOLD_IDS)
+def test_rejects_swiglu_up_half_unscaled(dtype, mean):
+    d = _fold_inputs(dtype, mean, glu=True)
+    _fold_rejected(_emulate(d, dtype, "swiglu", up_unscaled=True), _fold_ref(d, "swiglu"), dtype, mean)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_rejects_eps_left_out_on_a_zero_row(dtype):
+    d = _fold_inputs(dtype, 1.0)
+    z = _emulate(d, dtype, r=_rstd32(d["stats"], FK, eps=0.0))
+    assert not bool(torch.isfinite(z[7]).any())
+    with pytest.raises(AssertionError, match="non-finite"):
+        gc.check(z, _fold_ref(d), dtype, "fold model", bars=FOLD_LIMITS[1.0])
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_rejects_uncentred_weight_on_a_stream_with_large_mean(dtype):
+    d = _fold_inputs(dtype, 32.0)
+    _fold_rejected(_emulate(d, dtype, ws=d["w_plain"]), _fold_ref(d), dtype, 32.0)

@@ -3,8 +3,8 @@
 Each case first asserts the route its call takes (ops.gemm_route / ops.fused_mlp_route, the rule the launch switches on), then
 judges the output with _gemm_check.check: finite, guards untouched, the first-principles element bound and the per-(dtype, route)
 statistical bars.  Cases are listed per route in CASES; test_every_route_has_cases (no GPU) proves the table covers every route.
-The LayerNorm-fold routes are not faithfully rounded (the weights are re-rounded by mio_ln_fold_weight): their cases assert the
-route and judge the value with the bar of test_gpu_kernels.py's fold tests.  The cases beyond 32-bit offsets (an output over
+The LayerNorm-fold routes are judged against _gemm_check.reference_fold, built from what the consumer reads (the stream, the
+statistics handed to the launch, the folded weights and biases).  The cases beyond 32-bit offsets (an output over
 4 GiB, an x over 2 GiB, row strides at and past the per-tile offset limit) check 16-row blocks on both sides of every 2^31- and
 2^32-byte boundary and the last, ragged, row tile in fp64 on the GPU."""
 import pytest
@@ -163,51 +163,126 @@ def _glu_t256x128():
     }
 
 
-def _glu_ln(dtype, route, M, N, K, fold=False, seed=0, what=""):
-    """The gated stage through block_weight_glu + gemm_ln (plain, or the LayerNorm consumer behind a producer's statistics)."""
+def _glu_ln(dtype, route, M, N, K, seed=0, what=""):
+    """The gated stage through block_weight_glu + gemm_ln."""
     ops = _ops()
     x, wu, bu, _, wg, bg = _operands(dtype, M, N, K, "swiglu", True, False, seed, gate=True)
-    if not fold:
-        wb = ops.block_weight_glu(wg, wu)
-        assert ops.gemm_route(x, wb, bu, "swiglu", M=M, N=N, K=K, bias_gate=bg) == route
-        h, _ = ops.gemm_ln(x, wb, bu, M=M, N=N, K=K, activation="swiglu", bias_gate=bg)
-        gc.check(h, gc.reference(x, wu, bu, "swiglu", wg, bg, device=DEV), dtype, route, what=what)
-        return
-    _fold_case(dtype, route, M, N, K, "swiglu", seed)
+    wb = ops.block_weight_glu(wg, wu)
+    assert ops.gemm_route(x, wb, bu, "swiglu", M=M, N=N, K=K, bias_gate=bg) == route
+    h, _ = ops.gemm_ln(x, wb, bu, M=M, N=N, K=K, activation="swiglu", bias_gate=bg)
+    gc.check(h, gc.reference(x, wu, bu, "swiglu", wg, bg, device=DEV), dtype, route, what=what)
 
 
-def _fold_case(dtype, route, M, N, K, act, seed=0):
-    """Producer (residual GEMM + statistics) -> consumer with the LayerNorm folded into its weights: route asserted, value
-    against the fp64 LayerNorm -> linear with the bar of the fold tests in test_gpu_kernels.py (the fold re-rounds the weights)."""
-    import oracle
-    from test_gpu_kernels import _cmp
+EPS = 1e-5
+
+
+def _built_stats(y, pad):
+    """The consumer's statistics built by the test: fp64 slot sums of the stored stream rounded to fp32, rows past M = pad."""
+    M, K = y.shape
+    st = torch.full(_ops().ln_stats_shape(M, K), pad, dtype=torch.float32, device=DEV)
+    yd = y.double().view(M, K // 256, 256)
+    st[:, :M, 0] = yd.sum(-1).t().float()
+    st[:, :M, 1] = (yd * yd).sum(-1).t().float()
+    return st
+
+
+def _fold_stream(dtype, M, K, seed, mean=1.0):
+    """(y, statistics): the residual stream and its row statistics from the real producer (gemm_ln(..., residual=,
+    stats_out=True), the chain the modules run) where that GEMM [M, K, K] has the tiles for the 256-tile kernels -- with
+    M = MR from K 2048 on, at K 256 with M 65436 and at K 1024 with M 16500 -- row mean about mean / 2.2 deviations (the
+    residual's 2 and the product's 1 add to sqrt 5).  Else (MR with K 256, 768, 1024) the residual alone with statistics built
+    by the test and NaN in the rows past M: row mean mean / 2 deviations."""
     ops = _ops()
-    x0 = _rand((M, K), dtype, seed=seed)
-    r0 = _rand((M, K), dtype, 2.0, seed + 1, shift=1.0)
-    wp, bp = _rand((K, K), dtype, 0.03, seed + 2), _rand((K,), dtype, 0.1, seed + 3)
+    r0 = _rand((M, K), dtype, 2.0, seed + 1, shift=mean)
+    if ops.gemm_ln_ok(M, K, K, "none", stats_out=True):
+        x0 = _rand((M, K), dtype, seed=seed)
+        wp, bp = _rand((K, K), dtype, K ** -0.5, seed + 2), _rand((K,), dtype, 0.1, seed + 3)
+        return ops.gemm_ln(x0, ops.block_weight(wp), bp, M=M, N=K, K=K, residual=r0, stats_out=True)
+    return r0, _built_stats(r0, float("nan"))
+
+
+def _seam_rows(M):
+    """16-row blocks: the first rows, both sides of every 256-row tile seam, the whole ragged last tile."""
+    return _blocks_around([256 * k for k in range(1, (M - 1) // 256 + 1)], 1, M)
+
+
+def _fold_consumer(dtype, route, y, st, N, act, seed, col_scale=None, blocked=False, bars=True, what=""):
+    """One consumer launch on the stream y with the statistics st: the route asserted, the output judged by gc.check against
+    gc.reference_fold of what the kernel reads -- the whole output, or at K >= 4096 (where the fp64 reference is large) the
+    16-row blocks of _seam_rows.  Returns (z, folded bias, the launch's keyword arguments)."""
+    ops = _ops()
+    M, K = y.shape
     gam, bet = _rand((K,), dtype, 0.2, seed + 4, shift=1.0), _rand((K,), dtype, 0.1, seed + 5)
-    wc, bc = _rand((N, K), dtype, 0.03, seed + 6), _rand((N,), dtype, 0.1, seed + 7)
-    y, st = ops.gemm_ln(x0, ops.block_weight(wp), bp, M=M, N=K, K=K, residual=r0, stats_out=True)
-    rows = torch.cat([torch.arange(0, M, 97, device=DEV), torch.tensor([255, 256, M - 1], device=DEV)])
-    ln = oracle.layernorm(y[rows].cpu(), gam.cpu(), bet.cpu(), 1e-5).double()
+    wc, bc = _rand((N, K), dtype, K ** -0.5, seed + 6), _rand((N,), dtype, 0.1, seed + 7)
+    ws, bfold = ops.ln_fold_weight(wc, gam, bet, bc, blocked=False)
+    kw = dict(M=M, N=N, K=K, activation=act, ln_stats=st, eps=EPS)
+    rkw = {}
     if act == "swiglu":
-        wg, bg = _rand((N, K), dtype, 0.03, seed + 8), _rand((N,), dtype, 0.1, seed + 9)
-        wgf, bgf = ops.ln_fold_weight(wg, gam, bet, bg, blocked=False)
-        wuf, buf = ops.ln_fold_weight(wc, gam, bet, bc, blocked=False)
-        wb = ops.block_weight_glu(wgf, wuf)
-        assert ops.gemm_route(y, wb, buf, "swiglu", M=M, N=N, K=K, ln_stats=st, bias_gate=bgf) == route
-        z, _ = ops.gemm_ln(y, wb, buf, M=M, N=N, K=K, activation="swiglu", ln_stats=st, bias_gate=bgf)
-        want = torch.nn.functional.silu(ln @ wg.cpu().double().t() + bg.cpu().double()) * \
-            (ln @ wc.cpu().double().t() + bc.cpu().double())
+        wg, bg = _rand((N, K), dtype, K ** -0.5, seed + 8), _rand((N,), dtype, 0.1, seed + 9)
+        wgs, bgf = ops.ln_fold_weight(wg, gam, bet, bg, blocked=False)
+        wb = ops.block_weight_glu(wgs, ws)
+        kw["bias_gate"] = bgf
+        rkw = dict(ws_gate=wgs, bias_gate=bgf)
     else:
-        wfb, bfold = ops.ln_fold_weight(wc, gam, bet, bc)
-        assert ops.gemm_route(y, wfb, bfold, act, M=M, N=N, K=K, ln_stats=st) == route
-        z, _ = ops.gemm_ln(y, wfb, bfold, M=M, N=N, K=K, activation=act, ln_stats=st)
-        want = ln @ wc.cpu().double().t() + bc.cpu().double()
-        if act == "gelu":
-            want = torch.nn.functional.gelu(want, approximate="tanh")
-    assert torch.isfinite(z).all()
-    _cmp(z[rows], want, dtype, f"{route} {act}")
+        wb, bfold2 = ops.ln_fold_weight(wc, gam, bet, bc)
+        assert torch.equal(wb, ops.block_weight(ws)) and torch.equal(bfold2, bfold), "the blocked fold is not block_weight(ws)"
+    if col_scale is not None:
+        kw["col_scale"] = col_scale
+    assert ops.gemm_route(y, wb, bfold, **kw) == route, what
+    z, none = ops.gemm_ln(y, wb, bfold, **kw)
+    assert none is None and tuple(z.shape) == (M, N)
+    if blocked:  # the same launch through the blocked activation layout on both sides: bit for bit
+        from test_gpu_kernels import _block, _unblock
+        zb, _ = ops.gemm_ln(_block(y), wb, bfold, x_blocked=True, out_blocked=True, **kw)
+        assert torch.equal(_unblock(zb, M, N), z), "blocked x / blocked output differs from the row-major launch"
+    stl = ops.ln_stats_for_launch(st, M)  # what gemm_ln itself hands to the launch (the same call gives the same bits)
+    rows = _seam_rows(M) if K >= 4096 else None
+    pick = (lambda t: t) if rows is None else (lambda t: t[rows])  # noqa: E731
+    ref = gc.reference_fold(pick(y), stl[:, :M] if rows is None else stl[:, rows], ws, bfold, eps=EPS, act=act,
+                            col_scale=col_scale, device=DEV, **rkw)
+    gc.check(pick(z), ref, dtype, route, bars=bars, what=what or f"fold M {M} N {N} K {K} {act}")
+    return z, bfold, (wb, kw)
+
+
+def _fold_case(dtype, route, M, N, K, act, seed=0, mean=1.0, produced=False, **kw):
+    """Producer (residual GEMM + statistics) -> consumer with the LayerNorm folded into its weights.  produced=True: the case
+    relies on the real producer's stream (its mean in deviations)."""
+    assert not produced or _ops().gemm_ln_ok(M, K, K, "none", stats_out=True)
+    y, st = _fold_stream(dtype, M, K, seed, mean)
+    _fold_consumer(dtype, route, y, st, N, act, seed, **kw)
+
+
+def _adversarial_stream(dtype, M, K, seed):
+    """A stream no producer would write: row scales log-uniform over 1e-2 .. 1e2 and shuffled, row means of 0, 1, 4 and 32
+    deviations, and in every 64 rows one of zeros, one constant and one with a single non-zero element."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    scale = 10.0 ** (torch.rand(M, 1, device=DEV, generator=g) * 4 - 2)
+    mean = torch.tensor([0.0, 1.0, 4.0, 32.0], device=DEV)[torch.arange(M, device=DEV) % 4][:, None]
+    y = (torch.randn(M, K, device=DEV, generator=g) + mean) * scale
+    i = torch.arange(M, device=DEV)
+    zero, const, single = i % 64 == 5, i % 64 == 17, i % 64 == 29
+    y[zero] = 0
+    y[const] = scale[const].expand(-1, K)
+    y[single] = 0
+    y[single, (i[single] * 37) % K] = scale[single, 0]
+    return y.to(dtype), zero
+
+
+def _fold_adversarial(dtype, route, M, N, K, act, seed=0):
+    """The adversarial stream with statistics built by the test and NaN in the statistics rows past M (which the producer never
+    writes and the consumer reads): finite, inside the element bound everywhere, a zero row gives exactly b' (act none), and
+    the output is bit for bit that of the same launch with the padding rows zeroed.  No bars: relative row statistics mean
+    nothing on degenerate rows."""
+    ops = _ops()
+    y, zero = _adversarial_stream(dtype, M, K, seed)
+    assert (M + 255) // 256 * 256 - M >= 7
+    z, bfold, (wb, kw) = _fold_consumer(dtype, route, y, _built_stats(y, float("nan")), N, act, seed, bars=False,
+                                        what=f"adversarial stream {act}")
+    if act == "none":
+        assert torch.equal(z[zero], bfold.expand(int(zero.sum()), N)), "a zero row is not the folded bias"
+    kw["ln_stats"] = _built_stats(y, 0.0)
+    z0, _ = ops.gemm_ln(y, wb, bfold, **kw)
+    assert torch.equal(z0, z), "the statistics rows past M reach the output"
 
 
 def _p8w_glu():
@@ -218,15 +293,35 @@ def _p8w_glu():
     }
 
 
+MR = 8192 - 7  # 32 row tiles, the last one ragged: with N 2048 (1024 gated) the fewest tiles the 256-tile kernels take
+MP = 16500     # 65 row tiles, the last one ragged: with them a producer of width 1024 (4 column tiles) has its 256 tiles
+
+
 def _p8w_glu_fold():
-    return {"gemm_ln_fold": lambda dt: _glu_ln(dt, "p8w_glu_fold", 16500, 2048, 1024, fold=True)}
+    c = {"gemm_ln_fold": lambda dt: _fold_case(dt, "p8w_glu_fold", MP, 2048, 1024, "swiglu")}
+    for K in (256, 1024, 2304):  # 1, 4 and 9 -> 3 statistic slots
+        c[f"k{K}"] = lambda dt, K=K: _fold_case(dt, "p8w_glu_fold", MR, 1024, K, "swiglu", seed=K)
+    c["adversarial_stream"] = lambda dt: _fold_adversarial(dt, "p8w_glu_fold", 8192 - 100, 1024, 1024, "swiglu", seed=11)
+    return c
 
 
 def _p8w_fold():
-    return {
-        "none": lambda dt: _fold_case(dt, "p8w_fold", 16500, 2048, 1024, "none"),
-        "gelu": lambda dt: _fold_case(dt, "p8w_fold", 16500, 2048, 1024, "gelu", seed=1),
+    c = {
+        "none": lambda dt: _fold_case(dt, "p8w_fold", MP, 2048, 1024, "none"),
+        "gelu": lambda dt: _fold_case(dt, "p8w_fold", MP, 2048, 1024, "gelu", seed=1),
+        "k256_none": lambda dt: _fold_case(dt, "p8w_fold", 65536 - 100, 256, 256, "none", seed=2),
+        "k256_gelu": lambda dt: _fold_case(dt, "p8w_fold", 65536 - 100, 256, 256, "gelu", seed=3),
+        # M 16500: the producer GEMM [M, 1024, 1024] has the tiles, so these run the chain the modules run
+        "col_scale_half": lambda dt: _fold_case(dt, "p8w_fold", MP, 2048, 1024, "gelu", seed=4, col_scale=(1024, 2048, 0.25)),
+        "blocked_x_and_out": lambda dt: _fold_case(dt, "p8w_fold", MP, 2048, 1024, "none", seed=5, blocked=True),
+        # a residual of mean 8.8 and deviation 2 under a product of deviation 1: 8.8 / sqrt 5 = 3.9 deviations of mean
+        "mean_4_deviations": lambda dt: _fold_case(dt, "p8w_fold", MP, 2048, 1024, "gelu", seed=6, mean=8.8, produced=True),
+        "adversarial_stream": lambda dt: _fold_adversarial(dt, "p8w_fold", 8192 - 100, 2048, 1024, "none", seed=7),
     }
+    # statistic slots: 3, 8 (the LDS region full), 9 -> 3, 11 -> 1, 16 -> 8, 32 -> 8 (the last through ln_fold_weight_kernel<T, 32>)
+    for i, K in enumerate((768, 2048, 2304, 2816, 4096, 8192)):
+        c[f"k{K}"] = lambda dt, K=K, i=i: _fold_case(dt, "p8w_fold", MR, 2048, K, ("gelu", "none")[i % 2], seed=K)
+    return c
 
 
 def _stats_case(dtype, M, N, K, seed=0):
@@ -422,3 +517,171 @@ def test_fused_mlp_paths(dtype, blocked, act):
             _free()
     finally:
         _free()
+
+
+# ---- the two small kernels of the LayerNorm fold, directly ------------------------------------------------------------------
+def _floor16(v, dtype):
+    """The largest value of the 16-bit grid that is <= v (fp64 in, fp64 out)."""
+    r = gc.rn16(v, dtype)
+    below = gc.ulp16(r - gc.ulp16(r, dtype) / 4, dtype)  # (the spacing below a power of two is the smaller one)
+    return torch.where(r > v, r - below, r)
+
+
+def _ceil16(v, dtype):
+    return -_floor16(-v, dtype)
+
+
+def _fold_weight_call(w, gamma, beta, bias):
+    """mio_ln_fold_weight on w [N, K] with its own row stride (any ldw >= K: the kernel reads single elements)."""
+    from mio import _lib
+    N, K = w.shape
+    ws = torch.full((N, K), float("nan"), dtype=w.dtype, device=DEV)
+    bo = torch.full((N,), float("nan"), dtype=w.dtype, device=DEV)
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    rc = _lib.lib.mio_ln_fold_weight(w.data_ptr(), w.stride(0), gamma.data_ptr(), p(beta), p(bias), ws.data_ptr(), bo.data_ptr(),
+                                     N, K, _ops()._dtype_id(w), torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, _lib.lib.mio_last_error()
+    return ws, bo
+
+
+# below one pass of the 256 threads, off the 256 grid, the switch between the two kernels
+FOLD_K = [8, 255, 256, 2048, 2049, 4096, 8192]
+FOLD_N = 64
+
+
+def _fold_weight_inputs(dtype, K, spread, g):
+    """(gamma, w, beta, bias): gamma = 1 + 0.2 n with ldw = K, or gamma = +-2^j, j in -6 .. 6 (a spread of 4096) with ldw = K + 8
+    and NaN in the gap between rows.  Random rows, a zero row (3), a row with one dominant element (5) and, under the spread, a
+    row with w gamma = 0.75 in every column (9)."""
+    rnd = lambda *sh: torch.randn(*sh, device=DEV, generator=g)  # noqa: E731
+    if spread:
+        j = torch.randint(-6, 7, (K,), device=DEV, generator=g)
+        sign = torch.where(torch.rand(K, device=DEV, generator=g) < 0.5, -1.0, 1.0)
+        gamma = (sign * 2.0 ** j).to(dtype)
+    else:
+        gamma = (1 + 0.2 * rnd(K)).to(dtype)
+    buf = torch.full((FOLD_N, K + 8 if spread else K), float("nan"), dtype=dtype, device=DEV)
+    w = buf[:, :K]
+    w.copy_((rnd(FOLD_N, K) * 0.03 + 0.01).to(dtype))
+    w[3] = 0
+    w[5, (7 * K) // 11] = 8.0
+    if spread:
+        w[9] = (0.75 / gamma.double()).to(dtype)
+        assert torch.equal(w[9].double() * gamma.double(), torch.full((K,), 0.75, dtype=torch.float64, device=DEV))
+    return gamma, w, (0.1 * rnd(K)).to(dtype), (0.1 * rnd(FOLD_N)).to(dtype)
+
+
+def _check_fold_rows(ws, w, gamma, dtype, spread, tag):
+    """The prepared rows ws against the exact centred rows e = w gamma - mean_k(w gamma) in fp64 (test_ln_fold_weight_rows)."""
+    K = w.shape[1]
+    gK, gK1, u1 = gc._gamma(K), gc._gamma(K + 1), gc.U32
+    wg = w.double() * gamma.double()
+    e = wg - wg.mean(1, keepdim=True)
+    if spread:
+        e[9] = 0
+    d = gK1 * wg.abs().mean(1, keepdim=True) * (1 + u1) + u1 * e.abs()
+    wsd = ws.double()
+    out = (wsd < _floor16(e - d, dtype)) | (wsd > _ceil16(e + d, dtype))
+    assert not bool(out.any()), f"{tag}: {int(out.sum())} elements are no neighbour of their exact value"
+    assert not bool(wsd[3].any()), f"{tag}: the zero row"
+    if spread:
+        assert not bool(wsd[9].any()), f"{tag}: the constant row is not exactly zero"
+    rs, plain = wsd.sum(1).abs(), gc.rn16(e, dtype).sum(1).abs()
+    undecided = (gc.rn16(e - d, dtype) != gc.rn16(e + d, dtype)).double() * gc.ulp16(e.abs() + d, dtype)
+    worse = rs > plain + gK * wsd.abs().sum(1) + undecided.sum(1)
+    assert not bool(worse.any()), f"{tag}: rows {worse.nonzero().flatten().tolist()} sum farther from zero than plain rounding"
+    ulp = (wsd.abs().amax(1) * 2.0 ** -(gc._P[dtype] - 1)).clamp_min(1e-300)  # of the row's largest element, the dtype's own
+    print(f"{tag}: |row sum| at most {(rs / ulp).max().item():.3f} ulp of the row's largest element "
+          f"(plain rounding {(plain / ulp).max().item():.3f})")
+    assert bool((rs <= 2 * ulp).all()), f"{tag}: |row sum| {(rs / ulp).max().item():.3f} ulp of the largest element"
+
+
+def _check_bias_out(bo, w, beta, bias, dtype, tag):
+    """bias_out against b + w beta in fp64: the kernel's fp32 value is within tol = gamma_{K+1} (|b| + |w||beta|) of it (exact
+    products, K + 1 terms in any order) and is rounded ONCE, to nearest: half a 16-bit ulp, taken at |b + w beta| + tol."""
+    N, K = w.shape
+    gK1 = gc._gamma(K + 1)
+    want = torch.zeros(N, dtype=torch.float64, device=DEV) if bias is None else bias.double()
+    tol = gK1 * want.abs()
+    if beta is not None:
+        want = want + w.double() @ beta.double()
+        tol = tol + gK1 * (w.double().abs() @ beta.double().abs())
+    err = (bo.double() - want).abs()
+    bnd = gc.ulp16(want.abs() + tol, dtype) / 2 + tol
+    assert bool((err <= bnd).all()), f"{tag}: bias_out off by {(err / bnd).max().item():.3g} x (half an ulp + the fp32 bound)"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=["bfloat16", "float16"])
+@pytest.mark.parametrize("K", FOLD_K)
+def test_ln_fold_weight_rows(dtype, K):
+    """mio_ln_fold_weight on 64 rows against fp64: w' = gamma o w - mean_k(gamma o w), b' = b + w beta.
+    The two weight sets of _fold_weight_inputs (under the spread, row 9's products, partial sums and mean are exact in fp32, so
+    its centred row is exactly zero), each with and without beta and bias.
+      * every prepared element is one of the two 16-bit neighbours of its exact value e, allowing for the kernel's fp32
+        evaluation: the products are exact, their sum of K terms is off by at most gamma_K sum|w gamma|, the division and
+        the subtraction round once each, so the kernel's e lies within d = gamma_{K+1} mean|w gamma| (1 + u') + u' |e| of e and
+        the stored value in [floor16(e - d), ceil16(e + d)];
+      * |row sum| <= 2 ulp of the row's largest element (the dtype's ulp, as test_gemm_ln_fold_stream_with_large_mean has
+        it): the limit that judges every K;
+      * |row sum| <= that of the plain rounding of the same exact row + what the kernel cannot see: its fp32 evaluation of the sum
+        it minimises (gamma_K sum|w'|) and one ulp for each element whose plain rounding is not decided within d.  This slack is
+        the worst case over summation orders and grows like K ulp while the plain rounding's sum grows like sqrt(K / 12) ulp:
+        the comparison discriminates at K 8 .. 256 (a slack of an ulp or so in bf16) and no longer from K of a few thousand
+        on -- at K 8192 in fp16 d is about an ulp of a typical element and nearly every element is undecided -- where it
+        holds for any row inside the 2-ulp limit;
+      * bias_out is within half a 16-bit ulp + gamma_{K+1} (|b| + |w||beta|) of b + w beta (_check_bias_out);
+      * the prepared weight does not depend on beta or bias."""
+    g = torch.Generator(device=DEV).manual_seed(K)
+    for spread in (False, True):
+        gamma, w, beta0, bias0 = _fold_weight_inputs(dtype, K, spread, g)
+        first = None
+        for beta, bias in ((beta0, bias0), (None, bias0), (beta0, None), (None, None)):
+            tag = f"K {K} ldw {w.stride(0)} beta {beta is not None} bias {bias is not None}"
+            ws, bo = _fold_weight_call(w, gamma, beta, bias)
+            assert bool(torch.isfinite(ws).all() and torch.isfinite(bo).all()), tag
+            if first is None:
+                first = ws
+                _check_fold_rows(ws, w, gamma, dtype, spread, tag)
+            else:
+                assert torch.equal(ws, first), f"{tag}: the prepared weight depends on beta / bias"
+            _check_bias_out(bo, w, beta, bias, dtype, tag)
+    _free()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("slots_in,slots_out", [(16, 8), (9, 3), (11, 1), (32, 8)])
+def test_ln_stats_reduce(slots_in, slots_out):
+    """mio_ln_stats_reduce, ragged M: out[s'] = the sum of slots_in / slots_out consecutive slots, every value of the rows inside M
+    within gamma_per sum|terms| of the fp64 sum; the rows past M (NaN here) stay out of them."""
+    from mio import _lib
+    M = 512 + 37
+    mp = (M + 255) // 256 * 256
+    per = slots_in // slots_out
+    g = torch.Generator(device=DEV).manual_seed(slots_in)
+    st = torch.randn(slots_in, mp, 2, device=DEV, generator=g) * 30
+    st[..., 1] = st[..., 1] ** 2
+    st[:, M:] = float("nan")
+    out = torch.full((slots_out, mp, 2), float("nan"), dtype=torch.float32, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+    assert _lib.lib.mio_ln_stats_reduce(st.data_ptr(), slots_in, out.data_ptr(), slots_out, M, stream) == 0
+    terms = st[:, :M].double().view(slots_out, per, M, 2)
+    err = (out[:, :M].double() - terms.sum(1)).abs()
+    bnd = gc._gamma(per) * terms.abs().sum(1)
+    assert bool(torch.isfinite(out[:, :M]).all()) and bool((err <= bnd).all()), (err / bnd.clamp_min(1e-300)).max().item()
+
+
+@pytest.mark.gpu
+def test_stats_cover_every_route():
+    """Every (dtype, route) with cases has been judged with its bars (run alone, this test runs the first case of each route
+    itself).  The measured maxima are printed (-s shows them) in the layout of _gemm_check.BARS."""
+    want = {(dt, r) for dt in DTYPES for r in CASES if r != "empty"}
+    assert want == set(gc.BARS)
+    for dt, route in sorted(want - set(gc.STATS), key=str):
+        try:
+            next(iter(CASES[route].values()))(dt)
+        finally:
+            _free()
+    print("\n" + gc.stats_table())
+    assert want <= set(gc.STATS), sorted(map(str, want - set(gc.STATS)))
+    assert all(v["n"] > 0 and v["mean"] > 0 for v in gc.STATS.values())
