@@ -362,6 +362,13 @@ int mio_gemm_ln_bw(const void* x, const void* wb, const void* bias, const void* 
 /* ln_slots: statistic slots in ln_stats (0: K / 256, what a producer of width K writes); at most 8.  A wider stream (K > 2048)
  * goes through mio_ln_stats_reduce first: stats_out[s'] = sum of slots_in / slots_out consecutive slots, same row padding. */
 int mio_ln_stats_reduce(const float* stats_in, int32_t slots_in, float* stats_out, int32_t slots_out, int64_t M, void* stream);
+/* The consumer form behind an RMSNorm(gamma): mio_gemm_ln_bw's arguments, kernels, routes (mio_gemm_route, mio_gemm_ln_ok answer
+ * for both norms) and checks, with rstd = rsqrt(sum of squares / K + ln_eps): the statistics' sum entries are not used.  wb =
+ * mio_weight_block (swiglu: mio_weight_block_glu) of the 16-bit rounding of w * gamma (no centring, nothing folded into the bias;
+ * bias nullable).  ln_stats is required; residual and stats_out must be NULL (refused: the consumer form only). */
+int mio_gemm_rms_bw(const void* x, const void* wb, const void* bias, const void* bias_gate, const void* residual, void* y, int64_t M, int32_t N, int32_t K,
+                    int64_t ldx, int64_t ldy, int64_t ldr, int32_t act, int32_t dtype, int32_t flags, const float* ln_stats,
+                    int32_t ln_slots, float ln_eps, float* stats_out, int32_t cs_lo, int32_t cs_hi, float cs_val, void* stream);
 
 /* LayerNorm / residual+LayerNorm rows (the step either side of attention):
  * sum = x + alpha*residual (if residual), y = (sum-mean)/sqrt(var+eps)*weight + bias.
@@ -370,6 +377,13 @@ int mio_ln_stats_reduce(const float* stats_in, int32_t slots_in, float* stats_ou
 int mio_layernorm_fwd(const void* x, const void* residual, const void* weight, const void* bias,
                       void* y, void* sum_out, int64_t rows, int32_t cols, float eps, float alpha,
                       int32_t dtype, void* stream);
+/* RMSNorm / residual+RMSNorm rows (LLaMA-class decoders): s = x, or x + alpha*residual (with sum_out: rounded to dtype, stored
+ * there, and the rounded value is what is normalised, as in mio_layernorm_fwd); y = s * rsqrt(mean(s^2) + eps) * weight.  No
+ * bias.  cols % 8 == 0, cols <= 8192 (LayerNorm: 4096); y_blocked != 0: y in the blocked activation layout as
+ * mio_layernorm_fwd_bx writes it (cols % 32 == 0).  residual, sum_out nullable; every given pointer 16-byte aligned.
+ * rows == 0: returns 0 without a launch. */
+int mio_rmsnorm_fwd(const void* x, const void* residual, const void* weight, void* y, void* sum_out, int64_t rows,
+                    int32_t cols, float eps, float alpha, int32_t dtype, int32_t y_blocked, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Sliding-window attention forward (flash-attn's window_size = (left, right)): the params of

@@ -372,7 +372,9 @@ __global__ __launch_bounds__(G8_THREADS) void gemm8w_kernel(const GemmDev p) {
             sq += v[1];
           }
           const float mu = sm * ik;
-          mine[r] = __builtin_amdgcn_rsqf(fmaxf(sq * ik - mu * mu, 0.f) + p.ln_eps);
+          // RMSNorm (p.ln_rms, uniform): no mean; a select, so that a NaN or infinity in the unused sum entries stays out
+          const float var = p.ln_rms ? sq * ik : fmaxf(sq * ik - mu * mu, 0.f);
+          mine[r] = __builtin_amdgcn_rsqf(var + p.ln_eps);
         }
 #pragma unroll
         for (int r = 0; r < 8; ++r) rsv[r] = mine[16 * r + c16];

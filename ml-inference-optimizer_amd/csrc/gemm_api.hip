@@ -225,6 +225,24 @@ extern "C" int mio_gemm_ln_bw(const void* x, const void* wb, const void* bias, c
   return gemm_run("mio_gemm_ln_bw", c, stream);
 }
 
+// The consumer form of mio_gemm_ln_bw behind an RMSNorm: same kernels, routes and checks (form GEMM_LN), rstd without the mean.
+extern "C" int mio_gemm_rms_bw(const void* x, const void* wb, const void* bias, const void* bias_gate, const void* residual, void* y, int64_t M, int32_t N,
+                               int32_t K, int64_t ldx, int64_t ldy, int64_t ldr, int32_t act, int32_t dtype, int32_t flags,
+                               const float* ln_stats, int32_t ln_slots, float ln_eps, float* stats_out, int32_t cs_lo, int32_t cs_hi,
+                               float cs_val, void* stream) {
+  MIO_CHECK(M == 0 || (flags & ~7) == 0, "mio_gemm_rms_bw: unknown flag");
+  MIO_CHECK(ln_stats != nullptr, "mio_gemm_rms_bw: ln_stats must be non-null (the consumer form only)");
+  MIO_CHECK(residual == nullptr, "mio_gemm_rms_bw: the consumer form takes no residual");
+  MIO_CHECK(stats_out == nullptr, "mio_gemm_rms_bw: the consumer form writes no statistics (stats_out)");
+  GemmCall c = gemm_call(GEMM_LN, x, wb, bias, nullptr, y, M, N, K, ldx, ldy, ldr, act, dtype);
+  GemmDev& p = c.dev;
+  p.bias_g = bias_gate;
+  p.x_blk = (flags & MIO_GEMM_X_BLOCKED) != 0; p.y_blk = (flags & MIO_GEMM_Y_BLOCKED) != 0;
+  p.cs_lo = cs_lo; p.cs_hi = cs_hi; p.cs_val = cs_val;
+  p.ln_stats = ln_stats; p.ln_slots = ln_slots; p.ln_eps = ln_eps; p.ln_rms = 1;
+  return gemm_run("mio_gemm_rms_bw", c, stream);
+}
+
 // ---- route query ------------------------------------------------------------------------------------------------------
 extern "C" int32_t mio_gemm_route(int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
                                   int32_t has_residual, int32_t w_layout, int32_t fold_in, int32_t stats_out) {

@@ -56,6 +56,9 @@ struct GemmDev {
   float* stats_out;        // producer: [N / 256][tiles_m * 256][2]
   int ln_slots;
   float ln_eps;
+  // consumer only (mio_gemm_rms_bw): the norm is RMSNorm.  w holds the gamma-scaled weights (not centred: there is no mean), the
+  // read-out's rstd is rsqrt(sum of squares / K + eps) and the statistics' sum entries are not used.
+  int ln_rms;
 };
 
 constexpr int GEMM_LN_SLOTS_MAX = 8;  // 256-column statistic slots a folded LayerNorm may span (row width <= 2048): LDS region of gemm8w_kernel
@@ -66,7 +69,7 @@ static inline void gemm_dev_defaults(GemmDev& p) {
   p.x_blk = p.y_blk = p.w_blk = 0;
   p.dbg = nullptr;
   p.cs_lo = p.cs_hi = 0; p.cs_val = 1.f; p.group_m = 0;
-  p.res_blk = 0; p.ln_stats = nullptr; p.stats_out = nullptr; p.ln_slots = 0; p.ln_eps = 0.f;
+  p.res_blk = 0; p.ln_stats = nullptr; p.stats_out = nullptr; p.ln_slots = 0; p.ln_eps = 0.f; p.ln_rms = 0;
 }
 
 int mio_gemm_impl();  // MIO_GEMM_IMPL override (0 = default dispatch); defined in gemm_api.hip

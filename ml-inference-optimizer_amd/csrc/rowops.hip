@@ -1,4 +1,4 @@
-// HBM-bound row kernels either side of the MFMA kernels: LayerNorm / residual+LayerNorm and the
+// HBM-bound row kernels either side of the MFMA kernels: LayerNorm / RMSNorm (plain or residual first) and the
 // (o, lse) merge of two partial attention states.  One wave per row, 16-byte vector accesses.
 //   LayerNorm: reference kernels/triton/layernorm_kernels.py:35-188 (_layernorm_fwd_kernel,
 //              _layernorm_residual_fwd_kernel; wrapper triton_layernorm :191-276).
@@ -25,7 +25,9 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 // One wave per row; each lane owns chunks lane, lane+64, ... of 8 elements (cols % 8 == 0, cols <= 8*64*CH).
-template <typename T, int CH>
+// RMS: RMSNorm, y = s * rsqrt(mean(s^2) + eps) * w: no mean pass, no bias (`bias` is not read).  The LayerNorm form compiles
+// to what it was: every difference sits behind `if constexpr (RMS)`.
+template <typename T, int CH, bool RMS = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x, const T* __restrict__ res,
                                                         const T* __restrict__ w, const T* __restrict__ bias,
                                                         T* __restrict__ y, T* __restrict__ sum_out, int64_t rows,
@@ -54,22 +56,28 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
         }
       }
 #pragma unroll
-      for (int i = 0; i < 8; ++i) s += v[j][i];
+      for (int i = 0; i < 8; ++i) {
+        if constexpr (RMS) s += v[j][i] * v[j][i];
+        else s += v[j][i];
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) v[j][i] = 0.f;
     }
   }
-  const float mean = wave_sum(s) / (float)cols;
-  float q = 0.f;
+  float mean = 0.f, q = s;  // (RMS: s is already the sum of squares)
+  if constexpr (!RMS) {
+    mean = wave_sum(s) / (float)cols;
+    q = 0.f;
 #pragma unroll
-  for (int j = 0; j < CH; ++j) {
-    const int c = lane + 64 * j;
-    if (c < nch) {
+    for (int j = 0; j < CH; ++j) {
+      const int c = lane + 64 * j;
+      if (c < nch) {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float d = v[j][i] - mean;
-        q += d * d;
+        for (int i = 0; i < 8; ++i) {
+          const float d = v[j][i] - mean;
+          q += d * d;
+        }
       }
     }
   }
@@ -80,9 +88,14 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
     if (c < nch) {
       float wv[8], bv[8], o[8];
       unpack8<T>(*(const u32x4_t*)(w + 8 * c), wv);
-      if (bias != nullptr) unpack8<T>(*(const u32x4_t*)(bias + 8 * c), bv);
+      if constexpr (RMS) {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = (v[j][i] - mean) * rstd * wv[i] + (bias != nullptr ? bv[i] : 0.f);
+        for (int i = 0; i < 8; ++i) o[i] = v[j][i] * rstd * wv[i];
+      } else {
+        if (bias != nullptr) unpack8<T>(*(const u32x4_t*)(bias + 8 * c), bv);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = (v[j][i] - mean) * rstd * wv[i] + (bias != nullptr ? bv[i] : 0.f);
+      }
       // yblk: blocked activation layout (gemm_kernel.h GemmDev::x_blk): chunk c of the row is chunk c & 3 of the 64-byte
       // row segment in K-tile block c >> 2
       const int64_t yo = yblk ? (((row >> 8) * (cols >> 5) + (c >> 2)) * 256 + (row & 255)) * 32 + (c & 3) * 8
@@ -92,53 +105,69 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
   }
 }
 
-template <typename T>
-static int ln_launch(const void* x, const void* res, const void* w, const void* b, void* y, void* sum_out, int64_t rows,
-                     int cols, float eps, float alpha, hipStream_t st, int yblk) {
+// who: the entry point's name in refusals; RMS: the RMSNorm form (no bias; up to 8192 columns, LayerNorm stops at 4096)
+template <typename T, bool RMS>
+static int ln_launch(const char* who, const void* x, const void* res, const void* w, const void* b, void* y, void* sum_out,
+                     int64_t rows, int cols, float eps, float alpha, hipStream_t st, int yblk) {
   const int nch = cols / 8;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-#define LN_GO(CH)                                                                                             \
-  hipLaunchKernelGGL((layernorm_kernel<T, CH>), grid, block, 0, st, (const T*)x, (const T*)res, (const T*)w, \
+#define LN_GO(CH)                                                                                                  \
+  hipLaunchKernelGGL((layernorm_kernel<T, CH, RMS>), grid, block, 0, st, (const T*)x, (const T*)res, (const T*)w, \
                      (const T*)b, (T*)y, (T*)sum_out, rows, cols, eps, alpha, yblk)
   if (nch <= 64) LN_GO(1);
   else if (nch <= 128) LN_GO(2);
   else if (nch <= 256) LN_GO(4);
   else if (nch <= 512) LN_GO(8);
-  else return mio_fail("mio_layernorm_fwd: cols > 4096 not supported");
+  else if (RMS && nch <= 1024) {
+    if constexpr (RMS) LN_GO(16);
+  } else return mio_fail(std::string(who) + (RMS ? ": cols > 8192 not supported" : ": cols > 4096 not supported"));
 #undef LN_GO
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("layernorm launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return mio_fail(std::string(RMS ? "rmsnorm launch: " : "layernorm launch: ") + hipGetErrorString(e));
   return 0;
 }
 
-static int ln_entry(const char* who, const void* x, const void* residual, const void* weight, const void* bias, void* y,
+// the checks of the three entry points; LayerNorm's refusals keep the words they always had
+static int ln_entry(bool rms, const void* x, const void* residual, const void* weight, const void* bias, void* y,
                     void* sum_out, int64_t rows, int32_t cols, float eps, float alpha, int32_t dtype, void* stream, int yblk) {
-  (void)who;
-  MIO_CHECK(x && weight && y, "mio_layernorm_fwd: x, weight, y must be non-null");
-  MIO_CHECK(rows >= 0 && cols > 0 && cols % 8 == 0, "mio_layernorm_fwd: cols must be a positive multiple of 8");
-  MIO_CHECK(!yblk || cols % 32 == 0, "mio_layernorm_fwd_bx: cols must be a multiple of 32");
-  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, "mio_layernorm_fwd: dtype must be bf16 or fp16");
-  MIO_CHECK(mio_aligned16(x) && mio_aligned16(residual) && mio_aligned16(weight) && mio_aligned16(bias) &&
-                mio_aligned16(y) && mio_aligned16(sum_out),
-            "mio_layernorm_fwd: pointers must be 16-byte aligned");
+  const char* who = rms ? "mio_rmsnorm_fwd" : "mio_layernorm_fwd";
+#define LN_CHECK(cond, text) MIO_CHECK(cond, std::string(who) + (text))
+  LN_CHECK(x && weight && y, ": x, weight, y must be non-null");
+  LN_CHECK(rows >= 0 && cols > 0 && cols % 8 == 0, ": cols must be a positive multiple of 8");
+  LN_CHECK(!rms || cols <= 8192, ": cols > 8192 not supported");
+  LN_CHECK(!yblk || cols % 32 == 0, (rms ? ": y_blocked needs cols to be a multiple of 32" : "_bx: cols must be a multiple of 32"));
+  LN_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, ": dtype must be bf16 or fp16");
+  LN_CHECK(mio_aligned16(x) && mio_aligned16(residual) && mio_aligned16(weight) && mio_aligned16(bias) &&
+               mio_aligned16(y) && mio_aligned16(sum_out),
+           ": pointers must be 16-byte aligned");
+#undef LN_CHECK
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MIO_BF16)
-    return ln_launch<__bf16>(x, residual, weight, bias, y, sum_out, rows, cols, eps, alpha, st, yblk);
-  return ln_launch<_Float16>(x, residual, weight, bias, y, sum_out, rows, cols, eps, alpha, st, yblk);
+  if (rms)
+    return dtype == MIO_BF16 ? ln_launch<__bf16, true>(who, x, residual, weight, nullptr, y, sum_out, rows, cols, eps, alpha, st, yblk)
+                             : ln_launch<_Float16, true>(who, x, residual, weight, nullptr, y, sum_out, rows, cols, eps, alpha, st, yblk);
+  return dtype == MIO_BF16 ? ln_launch<__bf16, false>(who, x, residual, weight, bias, y, sum_out, rows, cols, eps, alpha, st, yblk)
+                           : ln_launch<_Float16, false>(who, x, residual, weight, bias, y, sum_out, rows, cols, eps, alpha, st, yblk);
 }
 
 extern "C" int mio_layernorm_fwd(const void* x, const void* residual, const void* weight, const void* bias, void* y,
                                  void* sum_out, int64_t rows, int32_t cols, float eps, float alpha, int32_t dtype,
                                  void* stream) {
-  return ln_entry("mio_layernorm_fwd", x, residual, weight, bias, y, sum_out, rows, cols, eps, alpha, dtype, stream, 0);
+  return ln_entry(false, x, residual, weight, bias, y, sum_out, rows, cols, eps, alpha, dtype, stream, 0);
 }
 
 // y in the blocked activation layout (include/mio_hip.h): ceil(rows / 256) * 256 x cols elements
 extern "C" int mio_layernorm_fwd_bx(const void* x, const void* residual, const void* weight, const void* bias, void* yb,
                                     void* sum_out, int64_t rows, int32_t cols, float eps, float alpha, int32_t dtype,
                                     void* stream) {
-  return ln_entry("mio_layernorm_fwd_bx", x, residual, weight, bias, yb, sum_out, rows, cols, eps, alpha, dtype, stream, 1);
+  return ln_entry(false, x, residual, weight, bias, yb, sum_out, rows, cols, eps, alpha, dtype, stream, 1);
+}
+
+// RMSNorm: y = T(s * rstd * weight), rstd = rsqrt(mean(s^2) + eps), s = x or T(x + alpha * residual) (then stored to sum_out);
+// y_blocked: y in the blocked activation layout.  cols <= 8192.
+extern "C" int mio_rmsnorm_fwd(const void* x, const void* residual, const void* weight, void* y, void* sum_out, int64_t rows,
+                               int32_t cols, float eps, float alpha, int32_t dtype, int32_t y_blocked, void* stream) {
+  return ln_entry(true, x, residual, weight, nullptr, y, sum_out, rows, cols, eps, alpha, dtype, stream, y_blocked ? 1 : 0);
 }
 
 // ---- merge of two normalised partial attention states ------------------------------------------

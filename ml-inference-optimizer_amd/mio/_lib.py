@@ -112,6 +112,8 @@ EXPORTS = (
     "mio_gemm_ln_bw",
     "mio_ln_stats_reduce",
     "mio_layernorm_fwd",
+    "mio_gemm_rms_bw",
+    "mio_rmsnorm_fwd",
     "mio_fa3_decode_workspace_bytes",
     "mio_fa3_decode_paged",
     "mio_fa3_decode_paged_window",
@@ -304,6 +306,10 @@ def _load() -> C.CDLL:
     lib.mio_ln_stats_reduce.argtypes = [vp, i32, vp, i32, i64, vp]
     lib.mio_ln_stats_reduce.restype = i32
     lib.mio_gemm_ln_bw.restype = i32
+    lib.mio_gemm_rms_bw.argtypes = list(lib.mio_gemm_ln_bw.argtypes)
+    lib.mio_gemm_rms_bw.restype = i32
+    lib.mio_rmsnorm_fwd.argtypes = [vp, vp, vp, vp, vp, i64, i32, f32, f32, i32, i32, vp]
+    lib.mio_rmsnorm_fwd.restype = i32
     lib.mio_layernorm_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, i32, vp]
     lib.mio_layernorm_fwd.restype = i32
     lib.mio_layernorm_fwd_bx.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, i32, vp]

@@ -77,16 +77,44 @@ def _get_blocked_glu(self, gate: torch.Tensor, up: torch.Tensor, dtype: torch.dt
 CastCache.get_blocked_glu = _get_blocked_glu
 
 
-def _get_ln_folded(self, lin: nn.Linear, ln: nn.LayerNorm, dtype: torch.dtype):
-    """(blocked gamma-scaled, row-centred weight, beta-folded bias) of a projection behind LayerNorm `ln` (ops.ln_fold_weight),
-    prepared once per version of the four parameters involved."""
-    ps = (lin.weight, lin.bias, ln.weight, ln.bias)
-    key = tuple((None if t is None else (t.data_ptr(), t._version)) for t in ps) + (dtype, lin.weight.device, "ln_fold")
-    slot = ("f", id(lin.weight), id(ln.weight))
+def norm_kind(norm: nn.Module, dtype: Optional[torch.dtype] = None) -> Tuple[str, float]:
+    """(kind, effective eps) of a norm module the wrappers take as pre_norm: "layernorm" for nn.LayerNorm, "rms" for nn.RMSNorm
+    (whose eps=None means torch.finfo(dtype).eps of the activations, as torch's own module resolves it); TypeError for anything
+    else.  The kind is the norm= of ops.gemm_ln / ops.gemm_route."""
+    if isinstance(norm, nn.LayerNorm):
+        return "layernorm", float(norm.eps)
+    if isinstance(norm, nn.RMSNorm):
+        if norm.eps is not None:
+            return "rms", float(norm.eps)
+        if dtype is None:
+            raise ValueError("an RMSNorm with eps=None takes its eps from the activation dtype: give dtype")
+        return "rms", float(torch.finfo(dtype).eps)
+    raise TypeError(f"pre_norm must be an nn.LayerNorm or an nn.RMSNorm, got {type(norm).__name__}")
+
+
+def apply_norm(x: torch.Tensor, norm: nn.Module, cache: "CastCache", dtype: torch.dtype, out_blocked: bool = False) -> torch.Tensor:
+    """norm(x) on the row kernel of the module's kind (an RMSNorm has no bias: none is read)."""
+    kind, eps = norm_kind(norm, x.dtype)
+    if kind == "rms":
+        return ops.rmsnorm(x, cache.get(norm.weight, dtype), eps, out_blocked=out_blocked)
+    return ops.layernorm(x, cache.get(norm.weight, dtype), cache.get(norm.bias, dtype), eps, out_blocked=out_blocked)
+
+
+def _get_ln_folded(self, lin: nn.Linear, ln: nn.Module, dtype: torch.dtype):
+    """The projection `lin` behind the norm `ln`, prepared once per version of the parameters involved.  LayerNorm: (blocked
+    gamma-scaled, row-centred weight, beta-folded bias) (ops.ln_fold_weight); RMSNorm: (blocked gamma-scaled weight, bias)
+    (ops.rms_fold_weight).  The kind is part of the key and the slot: one Linear behind two kinds of norm keeps two folds."""
+    kind = norm_kind(ln, dtype)[0]
+    ps = (lin.weight, lin.bias, ln.weight) + ((ln.bias,) if kind == "layernorm" else ())
+    key = tuple((None if t is None else (t.data_ptr(), t._version)) for t in ps) + (dtype, lin.weight.device, "ln_fold", kind)
+    slot = ("f", kind, id(lin.weight), id(ln.weight))
     hit = self._c.get(slot)
     if hit is not None and hit[0] == key:
         return hit[1]
-    t = ops.ln_fold_weight(self.get(lin.weight, dtype), self.get(ln.weight, dtype), self.get(ln.bias, dtype), self.get(lin.bias, dtype))
+    if kind == "rms":
+        t = ops.rms_fold_weight(self.get(lin.weight, dtype), self.get(ln.weight, dtype), self.get(lin.bias, dtype))
+    else:
+        t = ops.ln_fold_weight(self.get(lin.weight, dtype), self.get(ln.weight, dtype), self.get(ln.bias, dtype), self.get(lin.bias, dtype))
     self._c[slot] = (key, t)
     return t
 
@@ -94,17 +122,24 @@ def _get_ln_folded(self, lin: nn.Linear, ln: nn.LayerNorm, dtype: torch.dtype):
 CastCache.get_ln_folded = _get_ln_folded
 
 
-def _get_ln_folded_glu(self, gate: nn.Linear, up: nn.Linear, ln: nn.LayerNorm, dtype: torch.dtype):
-    """The SwiGLU pair behind LayerNorm `ln`: (interleaved blocked weight of the two folded weights, up bias', gate bias')."""
-    ps = (gate.weight, gate.bias, up.weight, up.bias, ln.weight, ln.bias)
-    key = tuple((None if t is None else (t.data_ptr(), t._version)) for t in ps) + (dtype, up.weight.device, "ln_fold_glu")
-    slot = ("fg", id(gate.weight), id(up.weight), id(ln.weight))
+def _get_ln_folded_glu(self, gate: nn.Linear, up: nn.Linear, ln: nn.Module, dtype: torch.dtype):
+    """The SwiGLU pair behind the norm `ln` (LayerNorm or RMSNorm, as get_ln_folded): (interleaved blocked weight of the two
+    folded weights, up bias', gate bias')."""
+    kind = norm_kind(ln, dtype)[0]
+    ps = (gate.weight, gate.bias, up.weight, up.bias, ln.weight) + ((ln.bias,) if kind == "layernorm" else ())
+    key = tuple((None if t is None else (t.data_ptr(), t._version)) for t in ps) + (dtype, up.weight.device, "ln_fold_glu", kind)
+    slot = ("fg", kind, id(gate.weight), id(up.weight), id(ln.weight))
     hit = self._c.get(slot)
     if hit is not None and hit[0] == key:
         return hit[1]
-    lw, lb = self.get(ln.weight, dtype), self.get(ln.bias, dtype)
-    wg, bg = ops.ln_fold_weight(self.get(gate.weight, dtype), lw, lb, self.get(gate.bias, dtype), blocked=False)
-    wu, bu = ops.ln_fold_weight(self.get(up.weight, dtype), lw, lb, self.get(up.bias, dtype), blocked=False)
+    lw = self.get(ln.weight, dtype)
+    if kind == "rms":
+        wg, bg = ops.rms_fold_weight(self.get(gate.weight, dtype), lw, self.get(gate.bias, dtype), blocked=False)
+        wu, bu = ops.rms_fold_weight(self.get(up.weight, dtype), lw, self.get(up.bias, dtype), blocked=False)
+    else:
+        lb = self.get(ln.bias, dtype)
+        wg, bg = ops.ln_fold_weight(self.get(gate.weight, dtype), lw, lb, self.get(gate.bias, dtype), blocked=False)
+        wu, bu = ops.ln_fold_weight(self.get(up.weight, dtype), lw, lb, self.get(up.bias, dtype), blocked=False)
     t = (ops.block_weight_glu(wg, wu), bu, bg)
     self._c[slot] = (key, t)
     return t
@@ -150,17 +185,17 @@ def linear(x: torch.Tensor, lin: nn.Linear, cache: CastCache, dtype: torch.dtype
                              col_scale=col_scale, x_blocked_shape=x_blocked_shape)
 
 
-def prenorm_linear(x: torch.Tensor, ln: nn.LayerNorm, lin: nn.Linear, cache: CastCache, dtype: torch.dtype,
+def prenorm_linear(x: torch.Tensor, ln: nn.Module, lin: nn.Linear, cache: CastCache, dtype: torch.dtype,
                    activation: str = "none", residual: Optional[torch.Tensor] = None, col_scale=None) -> torch.Tensor:
-    """lin(ln(x)) (+ activation, + residual).  At sizes that run the 256x256-tile kernels LayerNorm writes its output in
-    the blocked activation layout, so the GEMM's K-tile fetches are contiguous on both operands."""
+    """lin(ln(x)) (+ activation, + residual), ln a LayerNorm or an RMSNorm (norm_kind).  At sizes that run the 256x256-tile
+    kernels the norm writes its output in the blocked activation layout, so the GEMM's K-tile fetches are contiguous on both
+    operands."""
     w = cache.get(lin.weight, dtype)
     N, K = w.shape
     M = x.numel() // K
-    lw, lb = cache.get(ln.weight, dtype), cache.get(ln.bias, dtype)
     if K % 32 == 0 and not ops.NO_BLOCKED_X and ops.blocked_weight_ok(M, N, K, activation):
-        xb = ops.layernorm(x, lw, lb, ln.eps, out_blocked=True)
+        xb = apply_norm(x, ln, cache, dtype, out_blocked=True)
         return ops.gemm_bias_act(xb, w, cache.get(lin.bias, dtype), activation, residual=residual,
                                  w_blocked=cache.get_blocked(lin.weight, dtype), x_blocked_shape=tuple(x.shape),
                                  col_scale=col_scale)
-    return linear(ops.layernorm(x, lw, lb, ln.eps), lin, cache, dtype, activation, residual, col_scale=col_scale)
+    return linear(apply_norm(x, ln, cache, dtype), lin, cache, dtype, activation, residual, col_scale=col_scale)

@@ -20,7 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops
-from ..._nn import CastCache, ResidualStream, compute_dtype, linear, prenorm_linear
+from ..._nn import CastCache, ResidualStream, apply_norm, compute_dtype, linear, norm_kind, prenorm_linear
 
 
 @dataclass
@@ -283,7 +283,7 @@ class FlashSelfAttention(_AttentionBase):
             nn.init.normal_(lin.weight, mean=0.0, std=0.02)
             nn.init.zeros_(lin.bias)
 
-    def stream_ok(self, B: int, S: int, dtype: torch.dtype, pre_norm: Optional[nn.LayerNorm]) -> bool:
+    def stream_ok(self, B: int, S: int, dtype: torch.dtype, pre_norm: Optional[nn.Module]) -> bool:
         """True iff forward(...) can take / return the residual stream as a ResidualStream at this size: the folded GEMMs on both
         projections (ops.gemm_ln_ok); the attention between them is whatever forward() would run (pre-scaled K + blocked output
         where the kernels take the head dim, else the plain tiled kernel and a row-major context)."""
@@ -292,6 +292,7 @@ class FlashSelfAttention(_AttentionBase):
         n_tot, M = q_dim + 2 * kv_dim, B * S
         if dtype not in (torch.float16, torch.bfloat16) or pre_norm is None or pre_norm.weight is None or ops.NO_BLOCKED_X:
             return False
+        norm_kind(pre_norm, dtype)  # (a LayerNorm or an RMSNorm: TypeError otherwise)
         if _windowed(cfg):  # the stream form's attention is the pre-scaled-K / blocked-output kernel: no window there
             return False
         if cfg.rotary_dim > 0:  # nor rotary: the rotation comes before any scaling of K; forward() takes the ordinary route
@@ -312,7 +313,7 @@ class FlashSelfAttention(_AttentionBase):
         return (not _windowed(self.config) and self.config.rotary_dim == 0 and q_dim % 128 == 0 and kv_dim % 128 == 0 and ops.col_scale_ok(B * S, n_tot, self.qkv_proj.in_features)
                 and ops.fa3_k_prescaled_ok(B, S, S, self.num_attention_heads, self.head_dim, n_tot, n_tot))
 
-    def _forward_stream(self, x, pre_norm: nn.LayerNorm, stream_out: bool):
+    def _forward_stream(self, x, pre_norm: nn.Module, stream_out: bool):
         """The folded form: x is a ResidualStream (QKV normalises in its read-out, the output projection reads the residual from
         the blocked stream) or a [B, S, d] tensor (LayerNorm kernel in front, as forward() does); the output projection writes
         the new stream blocked + its row statistics (stream_out) or a plain [B, S, d] tensor."""
@@ -328,8 +329,9 @@ class FlashSelfAttention(_AttentionBase):
         cs = (q_dim, q_dim + kv_dim, sc * 1.4426950408889634) if kpre else None
         if is_stream:
             wfb, bfold = c.get_ln_folded(self.qkv_proj, pre_norm, dt)
-            qkv, _ = ops.gemm_ln(x.blocked, wfb, bfold, M=M, N=n_tot, K=d, x_blocked=True, ln_stats=x.stats, eps=pre_norm.eps,
-                                 col_scale=cs)
+            kind, eps = norm_kind(pre_norm, dt)
+            qkv, _ = ops.gemm_ln(x.blocked, wfb, bfold, M=M, N=n_tot, K=d, x_blocked=True, ln_stats=x.stats, eps=eps,
+                                 col_scale=cs, norm=kind)
             qkv = qkv.view(B, S, n_tot)
             res, res_blocked = x.blocked, True
         else:
@@ -350,10 +352,10 @@ class FlashSelfAttention(_AttentionBase):
         return ResidualStream(y, st, (B, S, d)) if stream_out else y.view(B, S, d)
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                residual: Optional[torch.Tensor] = None, pre_norm: Optional[nn.LayerNorm] = None,
+                residual: Optional[torch.Tensor] = None, pre_norm: Optional[nn.Module] = None,
                 stream_out: bool = False, **kwargs: Any) -> torch.Tensor:
-        """pre_norm (not in the reference): a LayerNorm to apply to hidden_states first -- the pre-LN block's
-        `attn(ln(x))` in one call, which lets LayerNorm hand its output to the QKV GEMM in the blocked layout.
+        """pre_norm (not in the reference): a LayerNorm or RMSNorm (mio._nn.norm_kind) to apply to hidden_states first -- the
+        pre-LN block's `attn(ln(x))` in one call, which lets the norm hand its output to the QKV GEMM in the blocked layout.
         hidden_states may be a ResidualStream (mio._nn) and stream_out=True returns one, where stream_ok() says so: the
         residual is then the stream itself (`x + attn(ln(x))`) and the LayerNorm is folded into the GEMMs (ops.gemm_ln)."""
         if isinstance(hidden_states, ResidualStream) or stream_out:
@@ -375,7 +377,7 @@ class FlashSelfAttention(_AttentionBase):
         c = self._cast
         q_dim, kv_dim = self.hidden_size, self.num_kv_heads * self.head_dim
         if pre_norm is not None and "block_tables" in kwargs:
-            x = ops.layernorm(x, c.get(pre_norm.weight, dt), c.get(pre_norm.bias, dt), pre_norm.eps)
+            x = apply_norm(x, pre_norm, c, dt)
             pre_norm = None
         if "block_tables" in kwargs:
             # only the query slice of the fused projection is needed on the paged path (:572-621)

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ..._nn import CastCache, ResidualStream, compute_dtype
+from ..._nn import CastCache, ResidualStream, apply_norm, compute_dtype, norm_kind
 
 
 @dataclass
@@ -58,13 +58,14 @@ class FusedMLP(nn.Module):
     def _gate(self, dtype):
         return None, None
 
-    def stream_ok(self, B: int, S: int, dtype: torch.dtype, pre_norm: Optional[nn.LayerNorm]) -> bool:
+    def stream_ok(self, B: int, S: int, dtype: torch.dtype, pre_norm: Optional[nn.Module]) -> bool:
         """True iff forward(...) can take (and return) the residual stream as a ResidualStream at this size (ops.gemm_ln_ok on
         both GEMMs; tanh-GELU or SwiGLU)."""
         act = self._kernel_activation()
         d, I, M = self.fc1.in_features, self.fc1.out_features, B * S
         if dtype not in (torch.float16, torch.bfloat16) or pre_norm is None or pre_norm.weight is None or ops.NO_BLOCKED_X:
             return False
+        norm_kind(pre_norm, dtype)  # (a LayerNorm or an RMSNorm: TypeError otherwise)
         if compute_dtype(self.config.precision, torch.empty(0, dtype=dtype)) != dtype:
             return False  # the stream form runs in the stream's dtype
         if act not in ("gelu", "swiglu") or tuple(pre_norm.normalized_shape) != (d,) or self.fc2.out_features != d:
@@ -74,7 +75,7 @@ class FusedMLP(nn.Module):
         return (ops.fused_mlp_blocked_weight_ok(M, d, I, act) and ops.gemm_ln_ok(M, I, d, act, fold_in=True)
                 and ops.gemm_ln_ok(M, d, I, "none", stats_out=True))
 
-    def _forward_stream(self, x: ResidualStream, pre_norm: nn.LayerNorm, stream_out: bool):
+    def _forward_stream(self, x: ResidualStream, pre_norm: nn.Module, stream_out: bool):
         """fc1 normalises the raw stream in its read-out and writes act(...) blocked; fc2 reads the residual from the blocked
         stream and writes the new stream (blocked + row statistics) or a plain [B, S, d] tensor."""
         c, act = self._cast, self._kernel_activation()
@@ -84,16 +85,17 @@ class FusedMLP(nn.Module):
             wfb, bfold, bgate = c.get_ln_folded_glu(self.fc1_gate, self.fc1, pre_norm, dt)
         else:
             (wfb, bfold), bgate = c.get_ln_folded(self.fc1, pre_norm, dt), None
+        kind, eps = norm_kind(pre_norm, dt)
         h, _ = ops.gemm_ln(x.blocked, wfb, bfold, M=M, N=I, K=d, activation=act, x_blocked=True, out_blocked=True,
-                           ln_stats=x.stats, eps=pre_norm.eps, bias_gate=bgate)
+                           ln_stats=x.stats, eps=eps, bias_gate=bgate, norm=kind)
         y, st = ops.gemm_ln(h, c.get_blocked(self.fc2.weight, dt), c.get(self.fc2.bias, dt), M=M, N=d, K=I, x_blocked=True,
                             residual=x.blocked, res_blocked=True, out_blocked=stream_out, stats_out=stream_out)
         return ResidualStream(y, st, (B, S, d)) if stream_out else y.view(B, S, d)
 
     def forward(self, hidden_states: torch.Tensor, residual: Optional[torch.Tensor] = None,
-                pre_norm: Optional[nn.LayerNorm] = None, stream_out: bool = False) -> torch.Tensor:
-        """pre_norm (not in the reference): a LayerNorm to apply to hidden_states first -- the pre-LN block's
-        `mlp(ln(x))` in one call, which lets LayerNorm hand its output to fc1 in the blocked layout.
+                pre_norm: Optional[nn.Module] = None, stream_out: bool = False) -> torch.Tensor:
+        """pre_norm (not in the reference): a LayerNorm or RMSNorm (mio._nn.norm_kind) to apply to hidden_states first -- the
+        pre-LN block's `mlp(ln(x))` in one call, which lets the norm hand its output to fc1 in the blocked layout.
         hidden_states may be a ResidualStream (mio._nn; the residual is then the stream itself and the LayerNorm is folded into
         fc1's read-out, ops.gemm_ln); stream_out=True returns one.  Where stream_ok() says so."""
         if isinstance(hidden_states, ResidualStream):
@@ -126,12 +128,11 @@ class FusedMLP(nn.Module):
             b2 = c.get_blocked(self.fc2.weight, dt)
         xshape = None
         if pre_norm is not None:
-            lw, lb = c.get(pre_norm.weight, dt), c.get(pre_norm.bias, dt)
             if b1 is not None and d % 32 == 0 and not ops.NO_BLOCKED_X:
                 xshape = tuple(x.shape)
-                x = ops.layernorm(x, lw, lb, pre_norm.eps, out_blocked=True)
+                x = apply_norm(x, pre_norm, c, dt, out_blocked=True)
             else:
-                x = ops.layernorm(x, lw, lb, pre_norm.eps)
+                x = apply_norm(x, pre_norm, c, dt)
         out = ops.fused_mlp(x, c.get(self.fc1.weight, dt), c.get(self.fc1.bias, dt), c.get(self.fc2.weight, dt),
                             c.get(self.fc2.bias, dt), act, gw, gb, residual=r, fc1_blocked=b1, fc2_blocked=b2,
                             x_blocked_shape=xshape)
@@ -190,11 +191,11 @@ class FusedTransformerMLP(nn.Module):
         else:
             self.mlp = FusedMLP(hidden_size, intermediate_size, self.config)
 
-    def stream_ok(self, B: int, S: int, dtype: torch.dtype, pre_norm: Optional[nn.LayerNorm]) -> bool:
+    def stream_ok(self, B: int, S: int, dtype: torch.dtype, pre_norm: Optional[nn.Module]) -> bool:
         return self.mlp.stream_ok(B, S, dtype, pre_norm)
 
     def forward(self, hidden_states: torch.Tensor, residual: Optional[torch.Tensor] = None,
-                pre_norm: Optional[nn.LayerNorm] = None, stream_out: bool = False) -> torch.Tensor:
+                pre_norm: Optional[nn.Module] = None, stream_out: bool = False) -> torch.Tensor:
         if isinstance(hidden_states, ResidualStream) or stream_out:
             return self.mlp(hidden_states, residual, pre_norm, stream_out)
         if pre_norm is not None:

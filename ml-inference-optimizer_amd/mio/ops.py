@@ -8,6 +8,8 @@ same exception types for the same conditions):
   ring_attention_forward    <- triton_ring_attention_forward (kernels/triton/attention_kernels.py:909-1005)
   fused_mlp                 <- triton_fused_mlp              (kernels/triton/mlp_kernels.py:648-756)
   layernorm                 <- triton_layernorm              (kernels/triton/layernorm_kernels.py:191-276)
+  rmsnorm / rms_fold_weight    RMSNorm rows (not a reference kernel: LLaMA-class blocks), and the weight of a projection behind one
+                               for gemm_ln(..., norm="rms")
   paged_attention_forward   <- triton_paged_attention_forward(kernels/triton/attention_kernels.py:1206-1311)
   reshape_and_cache         <- triton_reshape_and_cache      (kernels/triton/attention_kernels.py:1314-1407)
   rope_tables / apply_rotary / rope_and_cache_varlen
@@ -631,7 +633,8 @@ def gemm_route(x, w, bias=None, activation: str = "none", **kwargs) -> str:
     if activation not in _ACT:
         raise ValueError(f"Unsupported activation function: {activation}")
     act = _ACT[activation]
-    if "M" in kwargs:  # gemm_ln
+    if "M" in kwargs:  # gemm_ln (norm=: both norms run the same routes)
+        _norm_ok(kwargs.get("norm", "layernorm"), kwargs.get("ln_stats") is not None)
         M, N, K = int(kwargs["M"]), int(kwargs["N"]), int(kwargs["K"])
         _x2, ldx, r2, ldr = _gemm_ln_args(x, **kwargs)
         return _gemm_route(M, N, K, ldx, K, N, ldr, act, r2 is not None,
@@ -725,6 +728,35 @@ def ln_fold_weight(w: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Te
     return (block_weight(ws) if blocked else ws), bout
 
 
+def rms_fold_weight(w: torch.Tensor, gamma: torch.Tensor, bias: Optional[torch.Tensor] = None, blocked: bool = True):
+    """One-time preparation of a projection that sits behind an RMSNorm(gamma): returns (weight = w * gamma, the product taken in
+    fp32 and rounded once; bias unchanged).  There is no mean, so nothing is centred, and no beta, so nothing is folded into the
+    bias: gemm_ln(..., norm="rms")'s read-out multiplies by rstd and adds bias.  blocked=True returns block_weight of the [N, K]
+    product, blocked=False the row-major weight (the SwiGLU pair goes through block_weight_glu afterwards).  Preparation, not
+    hot path: torch ops."""
+    _need_cuda(w, gamma)
+    _dtype_id(w)
+    if w.dim() != 2:
+        raise ValueError(f"rms_fold_weight needs a 2-D weight, got {tuple(w.shape)}")
+    N, K = w.shape
+    _vec_ok(gamma, K, w.dtype, "gamma")
+    _vec_ok(bias, N, w.dtype, "bias")
+    ws = (w.float() * gamma.float()).to(w.dtype)
+    return (block_weight(ws) if blocked else ws), bias
+
+
+_NORMS = ("layernorm", "rms")
+
+
+def _norm_ok(norm: str, fold: bool) -> bool:
+    """gemm_ln's norm=: True for the RMS form, which is the consumer form only."""
+    if norm not in _NORMS:
+        raise ValueError(f"norm must be one of {_NORMS}, got {norm!r}")
+    if norm == "rms" and not fold:
+        raise ValueError("gemm_ln: norm='rms' is the consumer form (give ln_stats)")
+    return norm == "rms"
+
+
 def ln_stats_shape(M: int, width: int):
     return ((width + 255) // 256, (M + 255) // 256 * 256, 2)
 
@@ -764,14 +796,18 @@ def _gemm_ln_args(x, M, N, K, x_blocked=False, residual=None, res_blocked=False,
 def gemm_ln(x: torch.Tensor, w_blocked: torch.Tensor, bias: Optional[torch.Tensor], *, M: int, N: int, K: int,
             activation: str = "none", x_blocked: bool = False, residual: Optional[torch.Tensor] = None,
             res_blocked: bool = False, out_blocked: bool = False, ln_stats: Optional[torch.Tensor] = None,
-            eps: float = 1e-5, stats_out: bool = False, col_scale=None, bias_gate: Optional[torch.Tensor] = None):
+            eps: float = 1e-5, stats_out: bool = False, col_scale=None, bias_gate: Optional[torch.Tensor] = None,
+            norm: str = "layernorm"):
     """y = act(LN?(x) @ w^T + bias) (+ residual) on the 256-tile kernels with the LayerNorm folded in (module docstring of
     include/mio_hip.h, "LayerNorm folded into the GEMMs on either side of it").  Operands are [M, *] row-major 2-D tensors or,
     where the *_blocked flag says so, [ceil(M/256)*256, *] tensors in the blocked activation layout.
       ln_stats:           x is the raw residual stream, w_blocked / bias come from ln_fold_weight(...), ln_stats from the GEMM
                           that wrote x (stats_out=True);
-      stats_out=True:     also returns the (sum, sum of squares) statistics of the rounded output rows.
+      stats_out=True:     also returns the (sum, sum of squares) statistics of the rounded output rows;
+      norm="rms":         the norm behind ln_stats is an RMSNorm (mio_gemm_rms_bw): w_blocked / bias come from
+                          rms_fold_weight(...), the statistics from the same producer (their sums are not used).
     Returns (y, stats) -- stats is None unless stats_out."""
+    rms = _norm_ok(norm, ln_stats is not None)
     _need_cuda(x, w_blocked)
     if activation not in _ACT:
         raise ValueError(f"Unsupported activation function: {activation}")
@@ -811,8 +847,9 @@ def gemm_ln(x: torch.Tensor, w_blocked: torch.Tensor, bias: Optional[torch.Tenso
     y = torch.empty(mp if out_blocked else M, N, dtype=x.dtype, device=x.device)
     st = torch.empty(ln_stats_shape(M, N), dtype=torch.float32, device=x.device) if stats_out else None
     flags = (1 if x_blocked else 0) | (2 if out_blocked else 0) | (4 if (res_blocked and residual is not None) else 0)
-    check(lib.mio_gemm_ln_bw(x2.data_ptr(), w_blocked.data_ptr(), _ptr(bias), _ptr(bias_gate), _ptr(r2), y.data_ptr(), M, N, K, ldx, N, ldr,
-                             act, dt, flags, _ptr(ln_stats), slots, float(eps), _ptr(st), lo, hi, val, _stream()))
+    entry = lib.mio_gemm_rms_bw if rms else lib.mio_gemm_ln_bw
+    check(entry(x2.data_ptr(), w_blocked.data_ptr(), _ptr(bias), _ptr(bias_gate), _ptr(r2), y.data_ptr(), M, N, K, ldx, N, ldr,
+                act, dt, flags, _ptr(ln_stats), slots, float(eps), _ptr(st), lo, hi, val, _stream()))
     return y, st
 
 
@@ -953,6 +990,45 @@ def layernorm(x, weight, bias=None, eps: float = 1e-5, residual=None, residual_a
         y = torch.empty_like(x2)
         check(lib.mio_layernorm_fwd(x2.data_ptr(), _ptr(r2), weight.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(s),
                                     x2.shape[0], cols, float(eps), float(residual_alpha), dt, _stream()))
+        y = y.view(x.shape)
+    if return_sum:
+        return y, (s.view(x.shape) if s is not None else x)
+    return y
+
+
+RMSNORM_MAX_COLS = 8192
+
+
+def rmsnorm(x, weight, eps: float = 1e-6, residual=None, residual_alpha: float = 1.0, return_sum: bool = False,
+            out_blocked: bool = False):
+    """RMSNorm over the last dim (torch.nn.functional.rms_norm with a weight): y = s * rsqrt(mean(s^2) + eps) * weight, s = x or
+    x + alpha*residual (return_sum: rounded, returned, and y is RMSNorm of the returned tensor exactly).  Arguments and return
+    shapes as layernorm; up to 8192 columns."""
+    _need_cuda(x, weight)
+    dt = _dtype_id(x)
+    cols = x.shape[-1]
+    if cols > RMSNORM_MAX_COLS:
+        raise ValueError(f"rmsnorm takes up to {RMSNORM_MAX_COLS} columns, got {cols}")
+    _vec_ok(weight, cols, x.dtype, "rmsnorm weight")
+    _res_ok(residual, x.numel(), x.dtype)
+    x2 = x.reshape(-1, cols)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    r2 = None
+    if residual is not None:
+        r2 = residual.reshape(-1, cols)
+        if not r2.is_contiguous():
+            r2 = r2.contiguous()
+    s = torch.empty_like(x2) if (return_sum and r2 is not None) else None
+    if out_blocked:
+        if cols % 32 != 0:
+            raise ValueError("out_blocked needs cols % 32 == 0")
+        y = torch.empty((x2.shape[0] + 255) // 256 * 256, cols, dtype=x.dtype, device=x.device)
+    else:
+        y = torch.empty_like(x2)
+    check(lib.mio_rmsnorm_fwd(x2.data_ptr(), _ptr(r2), weight.data_ptr(), y.data_ptr(), _ptr(s), x2.shape[0], cols, float(eps),
+                              float(residual_alpha), dt, int(out_blocked), _stream()))
+    if not out_blocked:
         y = y.view(x.shape)
     if return_sum:
         return y, (s.view(x.shape) if s is not None else x)

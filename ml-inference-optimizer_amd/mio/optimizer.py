@@ -33,15 +33,40 @@ def apply_fused_mlp(model: nn.Module, config: Optional[FusedMLPConfig] = None) -
     return MLPConverter(cfg).convert_model(model)
 
 
+def _llama_rmsnorm_eps(m: nn.Module):
+    """The eps of a LLaMA-form RMSNorm written outside torch (transformers' LlamaRMSNorm, MistralRMSNorm, Qwen2RMSNorm, ...): a
+    class whose name ends in RMSNorm with a 1-D `weight` and `variance_epsilon` or `eps`; None for anything else.  Classes named
+    Gemma* scale by (1 + weight): not this norm, left alone."""
+    cls = type(m).__name__
+    if not cls.endswith("RMSNorm") or cls.startswith("Gemma") or isinstance(m, nn.RMSNorm):
+        return None
+    w = getattr(m, "weight", None)
+    eps = getattr(m, "variance_epsilon", getattr(m, "eps", None))
+    if not isinstance(w, torch.Tensor) or w.dim() != 1 or not isinstance(eps, (int, float)):
+        return None
+    return float(eps)
+
+
 def apply_fused_layernorm(model: nn.Module) -> nn.Module:
-    """KernelConfig.use_custom_layernorm of the reference (config/config_schema.py:13-19)."""
-    from .synthetic import FusedLayerNorm
+    """KernelConfig.use_custom_layernorm of the reference (config/config_schema.py:13-19).  Swaps nn.LayerNorm for
+    FusedLayerNorm, and nn.RMSNorm and the LLaMA-form RMSNorm classes (_llama_rmsnorm_eps) for FusedRMSNorm; the state is copied."""
+    from .synthetic import FusedLayerNorm, FusedRMSNorm
 
     for name, child in list(model.named_children()):
         if type(child) is nn.LayerNorm and len(child.normalized_shape) == 1 and child.elementwise_affine:
             new = FusedLayerNorm(child.normalized_shape[0], eps=child.eps).to(device=child.weight.device,
                                                                              dtype=child.weight.dtype)
             new.load_state_dict(child.state_dict())
+            setattr(model, name, new)
+        elif type(child) is nn.RMSNorm and len(child.normalized_shape) == 1 and child.elementwise_affine:
+            new = FusedRMSNorm(child.normalized_shape[0], eps=child.eps).to(device=child.weight.device, dtype=child.weight.dtype)
+            new.load_state_dict(child.state_dict())
+            setattr(model, name, new)
+        elif _llama_rmsnorm_eps(child) is not None:
+            new = FusedRMSNorm(child.weight.shape[0], eps=_llama_rmsnorm_eps(child)).to(device=child.weight.device,
+                                                                                        dtype=child.weight.dtype)
+            with torch.no_grad():
+                new.weight.copy_(child.weight)
             setattr(model, name, new)
         else:
             apply_fused_layernorm(child)

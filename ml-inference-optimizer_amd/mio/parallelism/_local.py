@@ -7,6 +7,8 @@ schedule tests replace them with checker implementations to exercise the communi
 a GPU (tests/test_parallel_gloo.py)."""
 from __future__ import annotations
 
+import torch
+
 from .. import ops
 
 
@@ -55,3 +57,11 @@ def layernorm(x, weight, bias=None, eps=1e-5):
     w = weight if weight.dtype == x.dtype else weight.to(x.dtype)
     b = bias if (bias is None or bias.dtype == x.dtype) else bias.to(x.dtype)
     return ops.layernorm(x, w, b, eps)
+
+
+def prenorm(x, pre_norm):
+    """pre_norm(x) for the tensor- and sequence-parallel sub-layers, which keep LayerNorm only."""
+    if not isinstance(pre_norm, torch.nn.LayerNorm):
+        raise TypeError(f"the tensor- and sequence-parallel sub-layers take an nn.LayerNorm as pre_norm only (an RMSNorm runs in "
+                        f"front of them, or in the single-device modules), got {type(pre_norm).__name__}")
+    return layernorm(x, pre_norm.weight, pre_norm.bias, pre_norm.eps)

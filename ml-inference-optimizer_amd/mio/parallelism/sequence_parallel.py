@@ -253,7 +253,7 @@ class SequenceParallelAttention(nn.Module):
         if self.training and self.dropout_p > 0:
             raise NotImplementedError("attention dropout (training) is not supported by the inference kernel")
         if pre_norm is not None:  # the pre-LN block's `attn(ln(x))` in one call, as FlashSelfAttention.forward takes it
-            hidden_states = _local.layernorm(hidden_states, pre_norm.weight, pre_norm.bias, pre_norm.eps)
+            hidden_states = _local.prenorm(hidden_states, pre_norm)
         B, Sl, _ = hidden_states.shape
         H, D = self.num_attention_heads, self.head_dim
         cfg = self.config
@@ -312,7 +312,7 @@ class SequenceParallelMLP(nn.Module):
     def forward(self, hidden_states: torch.Tensor, residual: Optional[torch.Tensor] = None,
                 pre_norm: Optional[nn.LayerNorm] = None) -> torch.Tensor:
         if pre_norm is not None:
-            hidden_states = _local.layernorm(hidden_states, pre_norm.weight, pre_norm.bias, pre_norm.eps)
+            hidden_states = _local.prenorm(hidden_states, pre_norm)
         h = _local.linear(hidden_states, self.dense_h_to_4h.weight, self.dense_h_to_4h.bias, self.activation)
         return _local.linear(h, self.dense_4h_to_h.weight, self.dense_4h_to_h.bias, "none", residual)
 

@@ -198,7 +198,7 @@ class TensorParallelMLP(nn.Module):
                 pre_norm: Optional[nn.LayerNorm] = None) -> torch.Tensor:
         """pre_norm (not in the reference): the pre-LN block's `mlp(ln(x))` in one call, as FusedMLP.forward takes it."""
         if pre_norm is not None:
-            hidden_states = _local.layernorm(hidden_states, pre_norm.weight, pre_norm.bias, pre_norm.eps)
+            hidden_states = _local.prenorm(hidden_states, pre_norm)
         return self.dense_4h_to_h(self.dense_h_to_4h(hidden_states), residual=residual)
 
 
@@ -252,7 +252,7 @@ class TensorParallelAttention(nn.Module):
         if self.training and self.dropout_p > 0:
             raise NotImplementedError("attention dropout (training) is not supported by the inference kernel")
         if pre_norm is not None:
-            hidden_states = _local.layernorm(hidden_states, pre_norm.weight, pre_norm.bias, pre_norm.eps)
+            hidden_states = _local.prenorm(hidden_states, pre_norm)
         B, S, _ = hidden_states.shape
         Hl, D = self.num_heads_per_partition, self.head_dim
         kv_in = encoder_hidden_states if (self.is_cross_attention and encoder_hidden_states is not None) else hidden_states

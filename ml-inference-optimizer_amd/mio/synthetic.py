@@ -14,7 +14,7 @@ from . import ops
 from .kernels.attention.flash_attention import FlashAttentionConfig, FlashSelfAttention
 from .kernels.attention.ring_attention import RingAttentionConfig, RingCrossAttention
 from .kernels.mlp.fused_mlp import FusedMLPConfig, FusedTransformerMLP
-from ._nn import ResidualStream
+from ._nn import ResidualStream, norm_kind
 
 
 class FusedLayerNorm(nn.LayerNorm):
@@ -28,13 +28,34 @@ class FusedLayerNorm(nn.LayerNorm):
         return ops.layernorm(x, w, b, self.eps)
 
 
+class FusedRMSNorm(nn.RMSNorm):
+    """nn.RMSNorm whose forward is the HIP row kernel (ops.rmsnorm); eps=None is torch.finfo(x.dtype).eps, as in torch."""
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if not x.is_cuda:
+            raise ValueError("HIP kernels require input tensors to be on a CUDA (ROCm) device.")
+        if self.weight is None or len(self.normalized_shape) != 1:
+            raise ValueError("FusedRMSNorm normalises the last dim with a weight (elementwise_affine=True)")
+        w = self.weight if self.weight.dtype == x.dtype else self.weight.to(x.dtype)  # fp32 parameters, 16-bit activations
+        return ops.rmsnorm(x, w, norm_kind(self, x.dtype)[1])
+
+
+_NORMS = {"layernorm": FusedLayerNorm, "rms": FusedRMSNorm}
+
+
+def _norm_module(norm: str, d: int) -> nn.Module:
+    if norm not in _NORMS:
+        raise ValueError(f"norm must be one of {sorted(_NORMS)}, got {norm!r}")
+    return _NORMS[norm](d)
+
+
 class Block(nn.Module):
-    def __init__(self, d: int, H: int, I: int, causal: bool, precision: str, activation: str = "gelu"):
+    def __init__(self, d: int, H: int, I: int, causal: bool, precision: str, activation: str = "gelu", norm: str = "layernorm"):
         super().__init__()
         acfg = FlashAttentionConfig(causal=causal, precision=precision)
-        self.ln_1 = FusedLayerNorm(d)
+        self.ln_1 = _norm_module(norm, d)  # (norm="rms": RMSNorm, the LLaMA-class block with activation="swiglu")
         self.attn = FlashSelfAttention(d, H, acfg)
-        self.ln_2 = FusedLayerNorm(d)
+        self.ln_2 = _norm_module(norm, d)
         self.mlp = FusedTransformerMLP(d, I, activation, FusedMLPConfig(precision=precision))
 
     def stream_ok(self, B: int, S: int, dtype: torch.dtype) -> bool:
@@ -122,12 +143,12 @@ class GPT2ShapedStack(nn.Module):
 
     def __init__(self, hidden_size: int = 1024, num_heads: int = 16, num_layers: int = 24,
                  intermediate_size: Optional[int] = None, causal: bool = True, precision: str = "bf16",
-                 activation: str = "gelu", seed: int = 0):
+                 activation: str = "gelu", seed: int = 0, norm: str = "layernorm"):
         super().__init__()
         I = intermediate_size or 4 * hidden_size
-        self.h = nn.ModuleList([Block(hidden_size, num_heads, I, causal, precision, activation)
+        self.h = nn.ModuleList([Block(hidden_size, num_heads, I, causal, precision, activation, norm)
                                 for _ in range(num_layers)])
-        self.ln_f = FusedLayerNorm(hidden_size)
+        self.ln_f = _norm_module(norm, hidden_size)
         self.no_ln_fold = False  # True: every LayerNorm runs as its own kernel (A/B of the fold, tools/ln_fold_ab.py)
         g = torch.Generator().manual_seed(seed)
         with torch.no_grad():  # N(0, 0.02) weights, zero biases (flash_attention.py:534-542)
