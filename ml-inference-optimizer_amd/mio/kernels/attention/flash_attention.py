@@ -11,7 +11,6 @@ One launch of mio_fa3_fwd per call; the projections run on the MFMA GEMM.  No Py
 from __future__ import annotations
 
 import copy
-import math
 from dataclasses import dataclass
 from typing import Any, Optional, Set, Tuple, Union
 
@@ -20,7 +19,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops
-from ..._nn import CastCache, ResidualStream, apply_norm, compute_dtype, linear, norm_kind, prenorm_linear
+from ..._nn import (CastCache, ResidualStream, apply_norm, as_dtype, attention_plan, compute_dtype, folded_linear, linear,
+                    prenorm_linear, residual_linear, stream_preconditions)
 
 
 @dataclass
@@ -75,10 +75,7 @@ class FlashAttention3(nn.Module):
         if not q.is_cuda:
             raise ValueError("HIP kernels require input tensors to be on a CUDA (ROCm) device.")
         cfg = self.config
-        if cfg.return_softmax:
-            raise NotImplementedError("return_softmax=True is not supported by the fused kernel")
-        if self.training and cfg.dropout_p > 0.0:
-            raise NotImplementedError("attention dropout (training) is not supported by the inference kernel")
+        _refuse(cfg, self.training)
         orig_dtype = q.dtype
         dt = compute_dtype(cfg.precision, q)
         if q.dtype != dt:
@@ -88,7 +85,15 @@ class FlashAttention3(nn.Module):
         out = ops.flash_attention(q, k, v, mask=mask, causal=cfg.causal, softmax_scale=cfg.softmax_scale,
                                   dropout_p=0.0, return_softmax=False, block_size=cfg.block_size,
                                   **_window_kw(cfg))
-        return out if out.dtype == orig_dtype else out.to(orig_dtype)
+        return as_dtype(out, orig_dtype)
+
+
+def _refuse(cfg, training: bool) -> None:
+    """What no attention kernel of this package computes: the softmax matrix, dropout."""
+    if cfg.return_softmax:
+        raise NotImplementedError("return_softmax=True is not supported by the fused kernel")
+    if training and cfg.dropout_p > 0.0:
+        raise NotImplementedError("attention dropout (training) is not supported by the inference kernel")
 
 
 def _window_kw(cfg) -> dict:
@@ -186,12 +191,24 @@ class _AttentionBase(nn.Module):
                                     **_decode_window_kw(self.config), **scales)
         return linear(out.view(B, q_len, self.hidden_size), self.o_proj, self._cast, dt, residual=residual)
 
-    def _attend(self, q, k, v, attention_mask):
+    def _plan(self, B, S, k_proj, k_cols, kv_stride, o_proj, mask: bool):
+        """mio._nn.attention_plan of a dense self-attention call of this module (Sq = Sk = S) under its config."""
         cfg = self.config
-        if cfg.return_softmax:
-            raise NotImplementedError("return_softmax=True is not supported by the fused kernel")
-        if self.training and cfg.dropout_p > 0.0:
-            raise NotImplementedError("attention dropout (training) is not supported by the inference kernel")
+        return attention_plan(B, S, S, self.num_attention_heads, self.num_kv_heads, self.head_dim, k_proj, k_cols, kv_stride,
+                              o_proj, softmax_scale=cfg.softmax_scale, mask=mask, normalize_query=cfg.normalize_query,
+                              return_softmax=cfg.return_softmax, windowed=_windowed(cfg), rotary=cfg.rotary_dim > 0)
+
+    def _context(self, q, k, v, plan, attention_mask, kwargs):
+        """Projected q [B,S,H,D] / k / v [B,S,Hkv,D] (views of the projection results) -> the attention result: rotary in place,
+        then the pre-scaled-K kernel where the plan says so (k then holds K * softmax_scale * log2(e), scaled in fp32 by the
+        projection's epilogue and rounded once; with plan.out_blocked the result comes in the out-projection's blocked
+        activation layout), else the plain path.  [B,S,H,D], or blocked [ceil(B*S/256)*256, H*D]."""
+        cfg = self.config
+        if cfg.rotary_dim > 0:
+            pos = self._dense_positions(kwargs, q.shape[1], q.device)
+            q, k = self._rotate(q, pos), self._rotate(k, pos)
+        if plan.kpre:
+            return ops.fa3_fwd(q, k, v, causal=cfg.causal, k_prescaled=True, out_blocked=plan.out_blocked)
         if cfg.normalize_query:
             q = F.normalize(q, dim=-1)
         return ops.flash_attention(q, k, v, mask=attention_mask, causal=cfg.causal,
@@ -226,42 +243,18 @@ class FlashAttentionLayer(_AttentionBase):
         B, S, _ = hidden_states.shape
         in_dtype = hidden_states.dtype
         dt = compute_dtype(self.config.precision, hidden_states)
-        x = hidden_states if in_dtype == dt else hidden_states.to(dt)
-        r = None if residual is None else (residual if residual.dtype == dt else residual.to(dt))
-        c = self._cast
+        x, r, c = as_dtype(hidden_states, dt), as_dtype(residual, dt), self._cast
         if "block_tables" in kwargs:
-            out = self._paged(linear(x, self.q_proj, c, dt), B, S, dt, kwargs, "FlashAttentionLayer", r)
-            return out if in_dtype == dt else out.to(in_dtype)
-        q = linear(x, self.q_proj, c, dt).view(B, S, self.num_attention_heads, self.head_dim)
-        # as FlashSelfAttention: where both kernels allow it the K projection's epilogue hands over K * softmax_scale * log2(e)
-        # (scaled in fp32, rounded once) and the attention launch is told so (ops.fa3_fwd k_prescaled)
-        cfg = self.config
+            return as_dtype(self._paged(linear(x, self.q_proj, c, dt), B, S, dt, kwargs, "FlashAttentionLayer", r), in_dtype)
+        _refuse(self.config, self.training)
+        # K is the whole output of k_proj; q / k / v are tensors of their own and the context stays row-major (no o_proj shape)
         kv_dim = self.num_kv_heads * self.head_dim
-        # (not with rotary: the rotation comes before any scaling of K)
-        kpre = (attention_mask is None and not cfg.normalize_query and not cfg.return_softmax and not _windowed(cfg)
-                and cfg.rotary_dim == 0
-                and kv_dim % 128 == 0
-                and self.k_proj.in_features % 32 == 0
-                and ops.fa3_k_prescaled_ok(B, S, S, self.num_attention_heads, self.head_dim, kv_dim, kv_dim)
-                and ops.blocked_weight_ok(B * S, kv_dim, self.k_proj.in_features)
-                and ops.col_scale_ok(B * S, kv_dim, self.k_proj.in_features))
-        cs = None
-        if kpre:
-            sc = cfg.softmax_scale if cfg.softmax_scale is not None else 1.0 / math.sqrt(self.head_dim)
-            cs = (0, kv_dim, sc * 1.4426950408889634)
-        k = linear(x, self.k_proj, c, dt, col_scale=cs).view(B, S, self.num_kv_heads, self.head_dim)
+        plan = self._plan(B, S, (B * S, kv_dim, self.k_proj.in_features), (0, kv_dim), kv_dim, None, attention_mask is not None)
+        q = linear(x, self.q_proj, c, dt).view(B, S, self.num_attention_heads, self.head_dim)
+        k = linear(x, self.k_proj, c, dt, col_scale=plan.col_scale).view(B, S, self.num_kv_heads, self.head_dim)
         v = linear(x, self.v_proj, c, dt).view(B, S, self.num_kv_heads, self.head_dim)
-        if cfg.rotary_dim > 0:
-            pos = self._dense_positions(kwargs, S, x.device)
-            q, k = self._rotate(q, pos), self._rotate(k, pos)
-        if kpre:
-            if self.training and cfg.dropout_p > 0.0:
-                raise NotImplementedError("attention dropout (training) is not supported by the inference kernel")
-            ctx = ops.fa3_fwd(q, k, v, causal=cfg.causal, k_prescaled=True).view(B, S, self.hidden_size)
-        else:
-            ctx = self._attend(q, k, v, attention_mask).view(B, S, self.hidden_size)
-        out = linear(ctx, self.o_proj, c, dt, residual=r)
-        return out if in_dtype == dt else out.to(in_dtype)
+        ctx = self._context(q, k, v, plan, attention_mask, kwargs).view(B, S, self.hidden_size)
+        return as_dtype(linear(ctx, self.o_proj, c, dt, residual=r), in_dtype)
 
 
 class FlashSelfAttention(_AttentionBase):
@@ -290,66 +283,14 @@ class FlashSelfAttention(_AttentionBase):
         cfg = self.config
         d, q_dim, kv_dim = self.qkv_proj.in_features, self.hidden_size, self.num_kv_heads * self.head_dim
         n_tot, M = q_dim + 2 * kv_dim, B * S
-        if dtype not in (torch.float16, torch.bfloat16) or pre_norm is None or pre_norm.weight is None or ops.NO_BLOCKED_X:
+        if not stream_preconditions(dtype, pre_norm, cfg.precision, d) or self.o_proj.out_features != d or q_dim != d:
             return False
-        norm_kind(pre_norm, dtype)  # (a LayerNorm or an RMSNorm: TypeError otherwise)
-        if _windowed(cfg):  # the stream form's attention is the pre-scaled-K / blocked-output kernel: no window there
-            return False
-        if cfg.rotary_dim > 0:  # nor rotary: the rotation comes before any scaling of K; forward() takes the ordinary route
-            return False
-        if compute_dtype(cfg.precision, torch.empty(0, dtype=dtype)) != dtype:
-            return False  # the stream form runs in the stream's dtype
-        if tuple(pre_norm.normalized_shape) != (d,) or self.o_proj.out_features != d or q_dim != d:
+        if _windowed(cfg) or cfg.rotary_dim > 0:  # forward() takes these on the ordinary route only
             return False
         if cfg.normalize_query or cfg.return_softmax or (self.training and cfg.dropout_p > 0.0):
             return False
         return (ops.blocked_weight_ok(M, n_tot, d) and ops.gemm_ln_ok(M, n_tot, d, "none", fold_in=True)
                 and ops.gemm_ln_ok(M, d, q_dim, "none", stats_out=True))
-
-    def _kpre_ok(self, B: int, S: int) -> bool:
-        """The QKV epilogue may hand the attention kernel K * softmax_scale * log2(e) (ops.fa3_fwd k_prescaled)."""
-        q_dim, kv_dim = self.hidden_size, self.num_kv_heads * self.head_dim
-        n_tot = q_dim + 2 * kv_dim
-        return (not _windowed(self.config) and self.config.rotary_dim == 0 and q_dim % 128 == 0 and kv_dim % 128 == 0 and ops.col_scale_ok(B * S, n_tot, self.qkv_proj.in_features)
-                and ops.fa3_k_prescaled_ok(B, S, S, self.num_attention_heads, self.head_dim, n_tot, n_tot))
-
-    def _forward_stream(self, x, pre_norm: nn.Module, stream_out: bool):
-        """The folded form: x is a ResidualStream (QKV normalises in its read-out, the output projection reads the residual from
-        the blocked stream) or a [B, S, d] tensor (LayerNorm kernel in front, as forward() does); the output projection writes
-        the new stream blocked + its row statistics (stream_out) or a plain [B, S, d] tensor."""
-        c, cfg = self._cast, self.config
-        is_stream = isinstance(x, ResidualStream)
-        B, S, d = x.shape
-        dt = x.dtype
-        M = B * S
-        q_dim, kv_dim = self.hidden_size, self.num_kv_heads * self.head_dim
-        n_tot = q_dim + 2 * kv_dim
-        sc = cfg.softmax_scale if cfg.softmax_scale is not None else 1.0 / math.sqrt(self.head_dim)
-        kpre = self._kpre_ok(B, S)  # head dims the pre-scaled-K kernels do not take (128) run the plain attention path below
-        cs = (q_dim, q_dim + kv_dim, sc * 1.4426950408889634) if kpre else None
-        if is_stream:
-            wfb, bfold = c.get_ln_folded(self.qkv_proj, pre_norm, dt)
-            kind, eps = norm_kind(pre_norm, dt)
-            qkv, _ = ops.gemm_ln(x.blocked, wfb, bfold, M=M, N=n_tot, K=d, x_blocked=True, ln_stats=x.stats, eps=eps,
-                                 col_scale=cs, norm=kind)
-            qkv = qkv.view(B, S, n_tot)
-            res, res_blocked = x.blocked, True
-        else:
-            qkv = prenorm_linear(x, pre_norm, self.qkv_proj, c, dt, col_scale=cs)
-            res, res_blocked = x.reshape(M, d), False
-        q = qkv[:, :, :q_dim].view(B, S, self.num_attention_heads, self.head_dim)
-        k = qkv[:, :, q_dim:q_dim + kv_dim].view(B, S, self.num_kv_heads, self.head_dim)
-        v = qkv[:, :, q_dim + kv_dim:].view(B, S, self.num_kv_heads, self.head_dim)
-        oblk = kpre and ops.fa3_o_blocked_ok(B, S, S, self.num_attention_heads, self.head_dim, n_tot, n_tot)
-        if kpre:
-            ctx = ops.fa3_fwd(q, k, v, causal=cfg.causal, k_prescaled=True, out_blocked=oblk)
-        else:
-            ctx = self._attend(q, k, v, None)
-        if not oblk:
-            ctx = ctx.reshape(M, q_dim)
-        y, st = ops.gemm_ln(ctx, c.get_blocked(self.o_proj.weight, dt), c.get(self.o_proj.bias, dt), M=M, N=d, K=q_dim,
-                            x_blocked=oblk, residual=res, res_blocked=res_blocked, out_blocked=stream_out, stats_out=stream_out)
-        return ResidualStream(y, st, (B, S, d)) if stream_out else y.view(B, S, d)
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, pre_norm: Optional[nn.Module] = None,
@@ -358,73 +299,57 @@ class FlashSelfAttention(_AttentionBase):
         pre-LN block's `attn(ln(x))` in one call, which lets the norm hand its output to the QKV GEMM in the blocked layout.
         hidden_states may be a ResidualStream (mio._nn) and stream_out=True returns one, where stream_ok() says so: the
         residual is then the stream itself (`x + attn(ln(x))`) and the LayerNorm is folded into the GEMMs (ops.gemm_ln)."""
-        if isinstance(hidden_states, ResidualStream) or stream_out:
+        stream = isinstance(hidden_states, ResidualStream) or stream_out
+        c, cfg = self._cast, self.config
+        if stream:  # runs in the stream's dtype (stream_ok): nothing is cast, the residual is the input itself
             B, S, _ = hidden_states.shape
             if attention_mask is not None or kwargs or (residual is not None and residual is not hidden_states) or \
                     not self.stream_ok(B, S, hidden_states.dtype, pre_norm):
                 raise ValueError("the ResidualStream form needs pre_norm, residual = the input itself, no mask / paged arguments "
                                  "and a size with stream_ok()")
-            return self._forward_stream(hidden_states, pre_norm, stream_out)
-        if hidden_states.dim() != 3:
-            raise ValueError(f"Expected 3D input tensor, got shape: {hidden_states.shape}")
-        if not hidden_states.is_cuda:
-            raise ValueError("HIP kernels require input tensors to be on a CUDA (ROCm) device.")
-        B, S, _ = hidden_states.shape
-        in_dtype = hidden_states.dtype
-        dt = compute_dtype(self.config.precision, hidden_states)
-        x = hidden_states if in_dtype == dt else hidden_states.to(dt)
-        r = None if residual is None else (residual if residual.dtype == dt else residual.to(dt))
-        c = self._cast
+            x = r = hidden_states
+            in_dtype = dt = hidden_states.dtype
+        else:
+            if hidden_states.dim() != 3:
+                raise ValueError(f"Expected 3D input tensor, got shape: {hidden_states.shape}")
+            if not hidden_states.is_cuda:
+                raise ValueError("HIP kernels require input tensors to be on a CUDA (ROCm) device.")
+            B, S, _ = hidden_states.shape
+            in_dtype = hidden_states.dtype
+            dt = compute_dtype(cfg.precision, hidden_states)
+            x, r = as_dtype(hidden_states, dt), as_dtype(residual, dt)
         q_dim, kv_dim = self.hidden_size, self.num_kv_heads * self.head_dim
-        if pre_norm is not None and "block_tables" in kwargs:
-            x = apply_norm(x, pre_norm, c, dt)
-            pre_norm = None
         if "block_tables" in kwargs:
+            if pre_norm is not None:
+                x = apply_norm(x, pre_norm, c, dt)
             # only the query slice of the fused projection is needed on the paged path (:572-621)
             wq = c.get(self.qkv_proj.weight, dt)[:q_dim]
             bq = c.get(self.qkv_proj.bias, dt)
             q2d = ops.gemm_bias_act(x, wq, None if bq is None else bq[:q_dim].contiguous())
-            out = self._paged(q2d, B, S, dt, kwargs, "FlashSelfAttention", r)
-            return out if in_dtype == dt else out.to(in_dtype)
-        # [B,S,q_dim+2*kv_dim]; q/k/v are strided views of it.  Where the kernels allow it the projection's epilogue hands
-        # over K * softmax_scale * log2(e) (scaled in fp32, rounded once): the attention kernel then takes the running
-        # reference through the MFMA's C operand and drops its per-score multiply-subtract / max pass (ops.fa3_fwd k_prescaled)
-        n_tot = q_dim + 2 * kv_dim
-        cfg = self.config
-        kpre = (attention_mask is None and not cfg.normalize_query and not cfg.return_softmax and not _windowed(cfg)
-                and cfg.rotary_dim == 0
-                and q_dim % 128 == 0
-                and kv_dim % 128 == 0 and self.qkv_proj.in_features % 32 == 0
-                and ops.fa3_k_prescaled_ok(B, S, S, self.num_attention_heads, self.head_dim, n_tot, n_tot)
-                and ops.blocked_weight_ok(B * S, n_tot, self.qkv_proj.in_features)
-                and ops.col_scale_ok(B * S, n_tot, self.qkv_proj.in_features))
-        cs = None
-        if kpre:
-            sc = cfg.softmax_scale if cfg.softmax_scale is not None else 1.0 / math.sqrt(self.head_dim)
-            cs = (q_dim, q_dim + kv_dim, sc * 1.4426950408889634)
-        qkv = (linear(x, self.qkv_proj, c, dt, col_scale=cs) if pre_norm is None
-               else prenorm_linear(x, pre_norm, self.qkv_proj, c, dt, col_scale=cs))
+            return as_dtype(self._paged(q2d, B, S, dt, kwargs, "FlashSelfAttention", r), in_dtype)
+        _refuse(cfg, self.training)
+        # [B,S,q_dim+2*kv_dim]; q / k / v are strided views of it, K its columns [q_dim, q_dim + kv_dim)
+        n_tot, d = q_dim + 2 * kv_dim, self.qkv_proj.in_features
+        plan = self._plan(B, S, (B * S, n_tot, d), (q_dim, q_dim + kv_dim), n_tot, (B * S, self.o_proj.out_features, q_dim),
+                          attention_mask is not None)
+        if isinstance(x, ResidualStream):
+            qkv = folded_linear(x, pre_norm, self.qkv_proj, c, col_scale=plan.col_scale).view(B, S, n_tot)
+        elif pre_norm is None:
+            qkv = linear(x, self.qkv_proj, c, dt, col_scale=plan.col_scale)
+        else:
+            qkv = prenorm_linear(x, pre_norm, self.qkv_proj, c, dt, col_scale=plan.col_scale)
         q = qkv[:, :, :q_dim].view(B, S, self.num_attention_heads, self.head_dim)
         k = qkv[:, :, q_dim:q_dim + kv_dim].view(B, S, self.num_kv_heads, self.head_dim)
         v = qkv[:, :, q_dim + kv_dim:].view(B, S, self.num_kv_heads, self.head_dim)
-        if cfg.rotary_dim > 0:
-            pos = self._dense_positions(kwargs, S, x.device)
-            q, k = self._rotate(q, pos), self._rotate(k, pos)
-        if kpre:
-            if self.training and cfg.dropout_p > 0.0:
-                raise NotImplementedError("attention dropout (training) is not supported by the inference kernel")
-            # where the output projection runs a 256-tile kernel the attention epilogue writes its [B*S, hidden] result in that
-            # GEMM's blocked activation layout (contiguous K-tiles on both operands)
-            if (self.hidden_size % 32 == 0 and ops.blocked_weight_ok(B * S, self.o_proj.out_features, self.hidden_size)
-                    and ops.fa3_o_blocked_ok(B, S, S, self.num_attention_heads, self.head_dim, n_tot, n_tot)):
-                ctx_b = ops.fa3_fwd(q, k, v, causal=cfg.causal, k_prescaled=True, out_blocked=True)
-                out = linear(ctx_b, self.o_proj, c, dt, residual=r, x_blocked_shape=(B, S, self.hidden_size))
-                return out if in_dtype == dt else out.to(in_dtype)
-            ctx = ops.fa3_fwd(q, k, v, causal=cfg.causal, k_prescaled=True).view(B, S, self.hidden_size)
+        ctx = self._context(q, k, v, plan, attention_mask, kwargs)
+        if stream:
+            return residual_linear(ctx if plan.out_blocked else ctx.reshape(B * S, q_dim), self.o_proj, c, x,
+                                   x_blocked=plan.out_blocked, stream_out=stream_out)
+        if plan.out_blocked:
+            out = linear(ctx, self.o_proj, c, dt, residual=r, x_blocked_shape=(B, S, q_dim))
         else:
-            ctx = self._attend(q, k, v, attention_mask).view(B, S, self.hidden_size)
-        out = linear(ctx, self.o_proj, c, dt, residual=r)
-        return out if in_dtype == dt else out.to(in_dtype)
+            out = linear(ctx.view(B, S, q_dim), self.o_proj, c, dt, residual=r)
+        return as_dtype(out, in_dtype)
 
 
 def _lin_weight(lin: nn.Module) -> torch.Tensor:

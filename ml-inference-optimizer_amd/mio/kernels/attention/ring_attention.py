@@ -18,7 +18,8 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ..._nn import CastCache, ResidualStream, apply_norm, compute_dtype, linear, norm_kind
+from ..._nn import (CastCache, ResidualStream, apply_norm, as_dtype, attention_plan, compute_dtype, folded_linear, linear,
+                    residual_linear, stream_preconditions)
 
 
 @dataclass
@@ -105,7 +106,7 @@ class RingSelfAttention(RingAttention):
     def prepare_attention_inputs(self, hidden_states: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(q, k, v) as [B,H,S,D] views (:237-273).  The 1/sqrt(D) scale is applied inside the kernel, not to q."""
         dt = self._check(hidden_states)
-        x = hidden_states if hidden_states.dtype == dt else hidden_states.to(dt)
+        x = as_dtype(hidden_states, dt)
         B, S, d = x.shape
         c = self._cast
         if self.config.fuse_qkv:
@@ -125,8 +126,7 @@ class RingSelfAttention(RingAttention):
         if attention_mask is not None and attention_mask.dim() == 4 and attention_mask.shape[2] == 1:
             attention_mask = attention_mask.expand(-1, -1, q.shape[2], -1)  # [B,1,1,S] key mask -> per query row
         ctx = ops.ring_attention_forward(q, k, v, attention_mask)
-        out = linear(ctx, self.out_proj, self._cast, dt)
-        return out if out.dtype == in_dtype else out.to(in_dtype)
+        return as_dtype(linear(ctx, self.out_proj, self._cast, dt), in_dtype)
 
 
 class RingCrossAttention(RingAttention):
@@ -144,10 +144,7 @@ class RingCrossAttention(RingAttention):
         """True iff forward(...) can take / return the query-side residual stream as a ResidualStream (mio._nn): the folded
         GEMMs on the query projection (LayerNorm in its read-out) and the output projection (blocked stream + row statistics)."""
         d, M = self.hidden_size, B * Sq
-        if dtype not in (torch.float16, torch.bfloat16) or pre_norm is None or pre_norm.weight is None or ops.NO_BLOCKED_X:
-            return False
-        norm_kind(pre_norm, dtype)  # (a LayerNorm or an RMSNorm: TypeError otherwise)
-        if compute_dtype(self.config.precision, torch.empty(0, dtype=dtype)) != dtype or tuple(pre_norm.normalized_shape) != (d,):
+        if not stream_preconditions(dtype, pre_norm, self.config.precision, d):
             return False
         return ops.gemm_ln_ok(M, d, d, "none", fold_in=True) and ops.gemm_ln_ok(M, d, d, "none", stats_out=True)
 
@@ -160,55 +157,35 @@ class RingCrossAttention(RingAttention):
         query_states may be a ResidualStream and stream_out=True returns one (where stream_ok()): the residual is then the stream itself, the
         LayerNorm runs in the query projection's read-out and the output projection writes the new stream blocked + its row
         statistics (ops.gemm_ln)."""
-        if isinstance(query_states, ResidualStream) or stream_out:
-            B, Sq, d = query_states.shape
-            if (residual is not None and residual is not query_states) or not self.stream_ok(B, Sq, query_states.dtype, pre_norm):
+        x, c = query_states, self._cast
+        stream = isinstance(x, ResidualStream) or stream_out
+        if stream:  # runs in the stream's dtype (stream_ok): nothing is cast, the residual is the query input itself
+            B, Sq, d = x.shape
+            if (residual is not None and residual is not x) or not self.stream_ok(B, Sq, x.dtype, pre_norm):
                 raise ValueError("the ResidualStream form needs pre_norm, residual = the query input itself and a size with stream_ok()")
-            dt, c, M = query_states.dtype, self._cast, B * Sq
+            in_dtype = dt = x.dtype
             self._check(key_value_states)
-            xkv = key_value_states if key_value_states.dtype == dt else key_value_states.to(dt)
-            if isinstance(query_states, ResidualStream):
-                wfb, bfold = c.get_ln_folded(self.q_proj, pre_norm, dt)
-                kind, eps = norm_kind(pre_norm, dt)
-                q2, _ = ops.gemm_ln(query_states.blocked, wfb, bfold, M=M, N=d, K=d, x_blocked=True, ln_stats=query_states.stats,
-                                    eps=eps, norm=kind)
-                res, res_blocked = query_states.blocked, True
-            else:
-                xn = apply_norm(query_states, pre_norm, c, dt)
-                q2 = linear(xn, self.q_proj, c, dt)
-                res, res_blocked = query_states.reshape(M, d), False
-            q = self._heads(q2.view(B, Sq, d))
-            Sk = xkv.shape[1]
-            kpre = (attention_mask is None and d % 128 == 0 and d % 32 == 0
-                    and ops.fa3_k_prescaled_ok(B, Sq, Sk, self.num_attention_heads, self.head_dim, d, d)
-                    and ops.blocked_weight_ok(B * Sk, d, d) and ops.col_scale_ok(B * Sk, d, d))
-            cs = (0, d, self.scale * 1.4426950408889634) if kpre else None
-            k = self._heads(linear(xkv, self.k_proj, c, dt, col_scale=cs))
-            v = self._heads(linear(xkv, self.v_proj, c, dt))
-            ctx = ops.ring_attention_forward(q, k, v, attention_mask, k_prescaled=kpre)
-            y, st = ops.gemm_ln(ctx.reshape(M, d), c.get_blocked(self.out_proj.weight, dt), c.get(self.out_proj.bias, dt), M=M, N=d,
-                                K=d, residual=res, res_blocked=res_blocked, out_blocked=stream_out, stats_out=stream_out)
-            return ResidualStream(y, st, (B, Sq, d)) if stream_out else y.view(B, Sq, d)
-        if pre_norm is not None:
-            query_states = apply_norm(query_states, pre_norm, self._cast, query_states.dtype)
-        in_dtype = query_states.dtype
-        dt = self._check(query_states)
-        self._check(key_value_states)
-        xq = query_states if query_states.dtype == dt else query_states.to(dt)
-        xkv = key_value_states if key_value_states.dtype == dt else key_value_states.to(dt)
-        c = self._cast
-        q = self._heads(linear(xq, self.q_proj, c, dt))
-        # where the kernels allow it the K projection's epilogue hands over K * softmax_scale * log2(e) (one rounding) and
-        # the attention kernel drops its per-score multiply (ops.fa3_fwd k_prescaled)
-        B, Sq, d = xq.shape
+            xq = x if isinstance(x, ResidualStream) else apply_norm(x, pre_norm, c, dt)
+        else:
+            xq = x if pre_norm is None else apply_norm(x, pre_norm, c, x.dtype)
+            in_dtype = xq.dtype
+            dt = self._check(xq)
+            self._check(key_value_states)
+            xq = as_dtype(xq, dt)
+            B, Sq, d = xq.shape
+        xkv = as_dtype(key_value_states, dt)
+        if isinstance(xq, ResidualStream):
+            q = self._heads(folded_linear(xq, pre_norm, self.q_proj, c).view(B, Sq, d))
+        else:
+            q = self._heads(linear(xq, self.q_proj, c, dt))
+        # K is the whole output of k_proj over the B * Sk context rows; the context is written through a head-major view of the
+        # [B,Sq,d] result, so it stays row-major (no o_proj shape)
         Sk = xkv.shape[1]
-        kpre = (attention_mask is None and d % 128 == 0 and d % 32 == 0
-                and ops.fa3_k_prescaled_ok(B, Sq, Sk, self.num_attention_heads, self.head_dim, d, d)
-                and ops.blocked_weight_ok(B * Sk, d, d) and ops.col_scale_ok(B * Sk, d, d))
-        cs = (0, d, self.scale * 1.4426950408889634) if kpre else None
-        k = self._heads(linear(xkv, self.k_proj, c, dt, col_scale=cs))
+        plan = attention_plan(B, Sq, Sk, self.num_attention_heads, self.num_attention_heads, self.head_dim, (B * Sk, d, d), (0, d),
+                              d, softmax_scale=self.scale, mask=attention_mask is not None)
+        k = self._heads(linear(xkv, self.k_proj, c, dt, col_scale=plan.col_scale))
         v = self._heads(linear(xkv, self.v_proj, c, dt))
-        ctx = ops.ring_attention_forward(q, k, v, attention_mask, k_prescaled=kpre)
-        r = None if residual is None else (residual if residual.dtype == dt else residual.to(dt))
-        out = linear(ctx, self.out_proj, c, dt, residual=r)
-        return out if out.dtype == in_dtype else out.to(in_dtype)
+        ctx = ops.ring_attention_forward(q, k, v, attention_mask, k_prescaled=plan.kpre)
+        if stream:
+            return residual_linear(ctx.reshape(B * Sq, d), self.out_proj, c, x, stream_out=stream_out)
+        return as_dtype(linear(ctx, self.out_proj, c, dt, residual=as_dtype(residual, dt)), in_dtype)

@@ -16,7 +16,8 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ..._nn import CastCache, ResidualStream, apply_norm, compute_dtype, norm_kind
+from ..._nn import (CastCache, ResidualStream, apply_norm, as_dtype, compute_dtype, folded_linear, residual_linear,
+                    stream_preconditions)
 
 
 @dataclass
@@ -63,12 +64,9 @@ class FusedMLP(nn.Module):
         both GEMMs; tanh-GELU or SwiGLU)."""
         act = self._kernel_activation()
         d, I, M = self.fc1.in_features, self.fc1.out_features, B * S
-        if dtype not in (torch.float16, torch.bfloat16) or pre_norm is None or pre_norm.weight is None or ops.NO_BLOCKED_X:
+        if not stream_preconditions(dtype, pre_norm, self.config.precision, d):
             return False
-        norm_kind(pre_norm, dtype)  # (a LayerNorm or an RMSNorm: TypeError otherwise)
-        if compute_dtype(self.config.precision, torch.empty(0, dtype=dtype)) != dtype:
-            return False  # the stream form runs in the stream's dtype
-        if act not in ("gelu", "swiglu") or tuple(pre_norm.normalized_shape) != (d,) or self.fc2.out_features != d:
+        if act not in ("gelu", "swiglu") or self.fc2.out_features != d:
             return False
         if self.training and self.dropout is not None:
             return False
@@ -78,19 +76,10 @@ class FusedMLP(nn.Module):
     def _forward_stream(self, x: ResidualStream, pre_norm: nn.Module, stream_out: bool):
         """fc1 normalises the raw stream in its read-out and writes act(...) blocked; fc2 reads the residual from the blocked
         stream and writes the new stream (blocked + row statistics) or a plain [B, S, d] tensor."""
-        c, act = self._cast, self._kernel_activation()
-        B, S, d = x.shape
-        dt, M, I = x.dtype, B * S, self.fc1.out_features
-        if act == "swiglu":
-            wfb, bfold, bgate = c.get_ln_folded_glu(self.fc1_gate, self.fc1, pre_norm, dt)
-        else:
-            (wfb, bfold), bgate = c.get_ln_folded(self.fc1, pre_norm, dt), None
-        kind, eps = norm_kind(pre_norm, dt)
-        h, _ = ops.gemm_ln(x.blocked, wfb, bfold, M=M, N=I, K=d, activation=act, x_blocked=True, out_blocked=True,
-                           ln_stats=x.stats, eps=eps, bias_gate=bgate, norm=kind)
-        y, st = ops.gemm_ln(h, c.get_blocked(self.fc2.weight, dt), c.get(self.fc2.bias, dt), M=M, N=d, K=I, x_blocked=True,
-                            residual=x.blocked, res_blocked=True, out_blocked=stream_out, stats_out=stream_out)
-        return ResidualStream(y, st, (B, S, d)) if stream_out else y.view(B, S, d)
+        act = self._kernel_activation()
+        gate = self.fc1_gate if act == "swiglu" else None
+        h = folded_linear(x, pre_norm, self.fc1, self._cast, act, gate=gate, out_blocked=True)
+        return residual_linear(h, self.fc2, self._cast, x, x_blocked=True, stream_out=stream_out)
 
     def forward(self, hidden_states: torch.Tensor, residual: Optional[torch.Tensor] = None,
                 pre_norm: Optional[nn.Module] = None, stream_out: bool = False) -> torch.Tensor:
@@ -114,9 +103,7 @@ class FusedMLP(nn.Module):
         act = self._kernel_activation()
         in_dtype = hidden_states.dtype
         dt = compute_dtype(self.config.precision, hidden_states)
-        x = hidden_states if in_dtype == dt else hidden_states.to(dt)
-        r = None if residual is None else (residual if residual.dtype == dt else residual.to(dt))
-        c = self._cast
+        x, r, c = as_dtype(hidden_states, dt), as_dtype(residual, dt), self._cast
         gw, gb = self._gate(dt)
         M, d, I = x.numel() // x.shape[-1], x.shape[-1], self.fc1.weight.shape[0]
         b1 = b2 = None  # blocked weight copies, when this shape runs the kernels that take them
@@ -136,7 +123,7 @@ class FusedMLP(nn.Module):
         out = ops.fused_mlp(x, c.get(self.fc1.weight, dt), c.get(self.fc1.bias, dt), c.get(self.fc2.weight, dt),
                             c.get(self.fc2.bias, dt), act, gw, gb, residual=r, fc1_blocked=b1, fc2_blocked=b2,
                             x_blocked_shape=xshape)
-        return out if out.dtype == in_dtype else out.to(in_dtype)
+        return as_dtype(out, in_dtype)
 
 
 class FusedMLPGeluTanh(FusedMLP):

@@ -960,16 +960,20 @@ def fused_mlp(
     return out
 
 
-def layernorm(x, weight, bias=None, eps: float = 1e-5, residual=None, residual_alpha: float = 1.0,
-              return_sum: bool = False, out_blocked: bool = False):
-    """Drop-in for triton_layernorm (layernorm_kernels.py:191-276): optional x + alpha*residual first.
-    out_blocked: y is returned as a [ceil(rows/256)*256, cols] tensor in the blocked activation layout
-    (include/mio_hip.h) for a following gemm_bias_act / fused_mlp with x_blocked_shape=x.shape."""
+RMSNORM_MAX_COLS = 8192
+
+
+def _row_norm(kind: str, x, weight, bias, eps, residual, residual_alpha, return_sum: bool, out_blocked: bool):
+    """layernorm / rmsnorm (kind "layernorm" / "rmsnorm"): the checks, the operands as contiguous rows, the outputs, one launch."""
+    rms = kind == "rmsnorm"
     _need_cuda(x, weight)
     dt = _dtype_id(x)
     cols = x.shape[-1]
-    _vec_ok(weight, cols, x.dtype, "layernorm weight")
-    _vec_ok(bias, cols, x.dtype, "layernorm bias")
+    if rms and cols > RMSNORM_MAX_COLS:
+        raise ValueError(f"rmsnorm takes up to {RMSNORM_MAX_COLS} columns, got {cols}")
+    _vec_ok(weight, cols, x.dtype, f"{kind} weight")
+    if not rms:
+        _vec_ok(bias, cols, x.dtype, "layernorm bias")
     _res_ok(residual, x.numel(), x.dtype)
     x2 = x.reshape(-1, cols)
     if not x2.is_contiguous():
@@ -984,19 +988,27 @@ def layernorm(x, weight, bias=None, eps: float = 1e-5, residual=None, residual_a
         if cols % 32 != 0:
             raise ValueError("out_blocked needs cols % 32 == 0")
         y = torch.empty((x2.shape[0] + 255) // 256 * 256, cols, dtype=x.dtype, device=x.device)
-        check(lib.mio_layernorm_fwd_bx(x2.data_ptr(), _ptr(r2), weight.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(s),
-                                       x2.shape[0], cols, float(eps), float(residual_alpha), dt, _stream()))
     else:
         y = torch.empty_like(x2)
-        check(lib.mio_layernorm_fwd(x2.data_ptr(), _ptr(r2), weight.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(s),
-                                    x2.shape[0], cols, float(eps), float(residual_alpha), dt, _stream()))
+    tail = (y.data_ptr(), _ptr(s), x2.shape[0], cols, float(eps), float(residual_alpha), dt)
+    if rms:
+        check(lib.mio_rmsnorm_fwd(x2.data_ptr(), _ptr(r2), weight.data_ptr(), *tail, int(out_blocked), _stream()))
+    else:
+        entry = lib.mio_layernorm_fwd_bx if out_blocked else lib.mio_layernorm_fwd
+        check(entry(x2.data_ptr(), _ptr(r2), weight.data_ptr(), _ptr(bias), *tail, _stream()))
+    if not out_blocked:
         y = y.view(x.shape)
     if return_sum:
         return y, (s.view(x.shape) if s is not None else x)
     return y
 
 
-RMSNORM_MAX_COLS = 8192
+def layernorm(x, weight, bias=None, eps: float = 1e-5, residual=None, residual_alpha: float = 1.0,
+              return_sum: bool = False, out_blocked: bool = False):
+    """Drop-in for triton_layernorm (layernorm_kernels.py:191-276): optional x + alpha*residual first.
+    out_blocked: y is returned as a [ceil(rows/256)*256, cols] tensor in the blocked activation layout
+    (include/mio_hip.h) for a following gemm_bias_act / fused_mlp with x_blocked_shape=x.shape."""
+    return _row_norm("layernorm", x, weight, bias, eps, residual, residual_alpha, return_sum, out_blocked)
 
 
 def rmsnorm(x, weight, eps: float = 1e-6, residual=None, residual_alpha: float = 1.0, return_sum: bool = False,
@@ -1004,35 +1016,7 @@ def rmsnorm(x, weight, eps: float = 1e-6, residual=None, residual_alpha: float =
     """RMSNorm over the last dim (torch.nn.functional.rms_norm with a weight): y = s * rsqrt(mean(s^2) + eps) * weight, s = x or
     x + alpha*residual (return_sum: rounded, returned, and y is RMSNorm of the returned tensor exactly).  Arguments and return
     shapes as layernorm; up to 8192 columns."""
-    _need_cuda(x, weight)
-    dt = _dtype_id(x)
-    cols = x.shape[-1]
-    if cols > RMSNORM_MAX_COLS:
-        raise ValueError(f"rmsnorm takes up to {RMSNORM_MAX_COLS} columns, got {cols}")
-    _vec_ok(weight, cols, x.dtype, "rmsnorm weight")
-    _res_ok(residual, x.numel(), x.dtype)
-    x2 = x.reshape(-1, cols)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    r2 = None
-    if residual is not None:
-        r2 = residual.reshape(-1, cols)
-        if not r2.is_contiguous():
-            r2 = r2.contiguous()
-    s = torch.empty_like(x2) if (return_sum and r2 is not None) else None
-    if out_blocked:
-        if cols % 32 != 0:
-            raise ValueError("out_blocked needs cols % 32 == 0")
-        y = torch.empty((x2.shape[0] + 255) // 256 * 256, cols, dtype=x.dtype, device=x.device)
-    else:
-        y = torch.empty_like(x2)
-    check(lib.mio_rmsnorm_fwd(x2.data_ptr(), _ptr(r2), weight.data_ptr(), y.data_ptr(), _ptr(s), x2.shape[0], cols, float(eps),
-                              float(residual_alpha), dt, int(out_blocked), _stream()))
-    if not out_blocked:
-        y = y.view(x.shape)
-    if return_sum:
-        return y, (s.view(x.shape) if s is not None else x)
-    return y
+    return _row_norm("rmsnorm", x, weight, None, eps, residual, residual_alpha, return_sum, out_blocked)
 
 
 # ------------------------------------------------------------------------------------------------

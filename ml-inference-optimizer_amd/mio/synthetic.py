@@ -49,14 +49,8 @@ def _norm_module(norm: str, d: int) -> nn.Module:
     return _NORMS[norm](d)
 
 
-class Block(nn.Module):
-    def __init__(self, d: int, H: int, I: int, causal: bool, precision: str, activation: str = "gelu", norm: str = "layernorm"):
-        super().__init__()
-        acfg = FlashAttentionConfig(causal=causal, precision=precision)
-        self.ln_1 = _norm_module(norm, d)  # (norm="rms": RMSNorm, the LLaMA-class block with activation="swiglu")
-        self.attn = FlashSelfAttention(d, H, acfg)
-        self.ln_2 = _norm_module(norm, d)
-        self.mlp = FusedTransformerMLP(d, I, activation, FusedMLPConfig(precision=precision))
+class _FoldableBlock(nn.Module):
+    """ln_1 -> attn -> ln_2 -> mlp, each sub-layer with its residual."""
 
     def stream_ok(self, B: int, S: int, dtype: torch.dtype) -> bool:
         """The block can run with both LayerNorms folded into the GEMMs around them (mio._nn.ResidualStream)."""
@@ -64,6 +58,16 @@ class Block(nn.Module):
         if a_ok is None or m_ok is None:                                                           # sequence parallel) have none
             return False
         return a_ok(B, S, dtype, self.ln_1) and m_ok(B, S, dtype, self.ln_2)
+
+
+class Block(_FoldableBlock):
+    def __init__(self, d: int, H: int, I: int, causal: bool, precision: str, activation: str = "gelu", norm: str = "layernorm"):
+        super().__init__()
+        acfg = FlashAttentionConfig(causal=causal, precision=precision)
+        self.ln_1 = _norm_module(norm, d)  # (norm="rms": RMSNorm, the LLaMA-class block with activation="swiglu")
+        self.attn = FlashSelfAttention(d, H, acfg)
+        self.ln_2 = _norm_module(norm, d)
+        self.mlp = FusedTransformerMLP(d, I, activation, FusedMLPConfig(precision=precision))
 
     def forward(self, x, stream_out: bool = False, fold: bool = True):
         """x: [B, S, d] tensor or the ResidualStream of the previous block (fold=False: every LayerNorm as its own kernel).  Where stream_ok(): ln_2 is folded into the output
@@ -81,7 +85,7 @@ class Block(nn.Module):
         return self.mlp(x, residual=x, pre_norm=self.ln_2)
 
 
-class CrossBlock(nn.Module):
+class CrossBlock(_FoldableBlock):
     """Diffusion-style block of BASELINE config 5: LN -> non-causal cross attention (q from x, k / v from a separate
     context tensor; the reference's RingCrossAttention projections, ring_attention.py:413-669) + residual -> LN ->
     FusedMLP-GELU + residual."""
@@ -92,12 +96,6 @@ class CrossBlock(nn.Module):
         self.attn = RingCrossAttention(d, H, RingAttentionConfig(precision=precision))
         self.ln_2 = FusedLayerNorm(d)
         self.mlp = FusedTransformerMLP(d, I, activation, FusedMLPConfig(precision=precision))
-
-    def stream_ok(self, B: int, S: int, dtype: torch.dtype) -> bool:
-        a_ok, m_ok = getattr(self.attn, "stream_ok", None), getattr(self.mlp, "stream_ok", None)
-        if a_ok is None or m_ok is None:
-            return False
-        return a_ok(B, S, dtype, self.ln_1) and m_ok(B, S, dtype, self.ln_2)
 
     def forward(self, x, context: torch.Tensor, stream_out: bool = False, fold: bool = True):
         """x: [B, S, d] tensor or the previous block's ResidualStream; the LayerNorms are folded into the GEMMs around them where
