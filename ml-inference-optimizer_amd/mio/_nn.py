@@ -85,6 +85,16 @@ class CastCache:
         return self._memo(("b", id(p)), (p.data_ptr(), p._version, dtype, p.device, "blocked"),
                           lambda: ops.block_weight(self.get(p, dtype)))
 
+    def get_cat(self, ps: Tuple[Optional[torch.Tensor], ...], dtype: torch.dtype, blocked: bool = False) -> Optional[torch.Tensor]:
+        """The row-concatenation of the parameters ps in dtype (None where they are: biases that are not there), or with blocked
+        that weight in the blocked layout; made again when one of them changes."""
+        if ps[0] is None:
+            return None
+        key = _versions(*ps) + (dtype, ps[0].device)
+        if blocked:
+            return self._memo(("cb",) + tuple(map(id, ps)), key, lambda: ops.block_weight(self.get_cat(ps, dtype)))
+        return self._memo(("c",) + tuple(map(id, ps)), key, lambda: torch.cat([self.get(p, dtype) for p in ps], dim=0).contiguous())
+
     def get_blocked_glu(self, gate: torch.Tensor, up: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
         """The SwiGLU gate / up parameters as ONE interleaved blocked weight (ops.block_weight_glu), repacked when either changes."""
         return self._memo(("g", id(gate), id(up)),

@@ -50,6 +50,21 @@ def set_tensor_model_parallel_attributes(tensor: torch.Tensor, is_parallel: bool
     setattr(tensor, "partition_stride", stride)
 
 
+def attention_projections(att, kind: str):
+    """([(weight, bias) of the q, k and v projection], o_proj) of a FlashSelfAttention (the three row blocks of its fused
+    qkv_proj) or a FlashAttentionLayer, for the converter of that `kind` ("tensor-parallel" / "sequence-parallel": the word its
+    refusal of grouped-query attention starts with)."""
+    from ..kernels.attention.flash_attention import FlashSelfAttention
+
+    d = att.hidden_size
+    if att.num_kv_heads != att.num_attention_heads:
+        raise NotImplementedError(f"{kind} conversion of GQA attention is not implemented")
+    if isinstance(att, FlashSelfAttention):
+        w, b = att.qkv_proj.weight, att.qkv_proj.bias
+        return [(w[i * d:(i + 1) * d], b[i * d:(i + 1) * d]) for i in range(3)], att.o_proj
+    return [(p.weight, p.bias) for p in (att.q_proj, att.k_proj, att.v_proj)], att.o_proj
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # combined tensor x sequence x data groups (reference parallel_utils.py:882-1019, orchestrator.py:20-110)
 # ---------------------------------------------------------------------------------------------------------------

@@ -27,8 +27,10 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from .._nn import CastCache, attention_plan
 from . import _local
 from . import communication as comm
+from .parallel_utils import attention_projections
 
 
 @dataclass
@@ -247,25 +249,33 @@ class SequenceParallelAttention(nn.Module):
                 nn.init.zeros_(lin.bias)
         self.last_communication_time = 0.0
         self._recv_buffers: Optional[dict] = {} if config.buffer_reuse else None  # mesh exchange receive buffers
+        self._cast = CastCache()
+
+    def _linear(self, x: torch.Tensor, lin: nn.Linear, **kw) -> torch.Tensor:
+        return _local.cached_linear(self._cast, x, lin.weight, lin.bias, **kw)
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, pre_norm: Optional[nn.LayerNorm] = None) -> torch.Tensor:
         if self.training and self.dropout_p > 0:
             raise NotImplementedError("attention dropout (training) is not supported by the inference kernel")
         if pre_norm is not None:  # the pre-LN block's `attn(ln(x))` in one call, as FlashSelfAttention.forward takes it
-            hidden_states = _local.prenorm(hidden_states, pre_norm)
+            hidden_states = _local.prenorm(hidden_states, pre_norm, self._cast)
         B, Sl, _ = hidden_states.shape
         H, D = self.num_attention_heads, self.head_dim
         cfg = self.config
         mode = cfg.attention_handling
-        q = _local.linear(hidden_states, self.query.weight, self.query.bias).view(B, Sl, H, D)
+        q = self._linear(hidden_states, self.query).view(B, Sl, H, D)
         # ring mode: the K projection scales its columns by softmax_scale * log2(e) in fp32 before their one rounding, and
-        # every ring step's attention launch drops its per-score multiply (ops.fa3_fwd k_prescaled) -- where both ends can
-        kpre = (mode == "ring" and cfg.sp_size > 1 and attention_mask is None and (H * D) % 128 == 0
-                and _local.k_prescale_ok(B, Sl // (2 if cfg.zigzag else 1), H, D, B * Sl, H * D, hidden_states.shape[-1]))
-        kcs = (0, H * D, D ** -0.5 * 1.4426950408889634) if kpre else None
-        k = _local.linear(hidden_states, self.key.weight, self.key.bias, col_scale=kcs).view(B, Sl, H, D)
-        v = _local.linear(hidden_states, self.value.weight, self.value.bias).view(B, Sl, H, D)
+        # every ring step's attention launch (Sq rows each, with the carry) drops its per-score multiply (ops.fa3_fwd k_prescaled)
+        # -- where both ends can (_nn.attention_plan)
+        kpre, kcs = False, None
+        if mode == "ring" and cfg.sp_size > 1:
+            Sq = Sl // (2 if cfg.zigzag else 1)
+            plan = attention_plan(B, Sq, Sq, H, H, D, (B * Sl, H * D, hidden_states.shape[-1]), (0, H * D), H * D,
+                                  mask=attention_mask is not None, carry=True)
+            kpre, kcs = plan.kpre, plan.col_scale
+        k = self._linear(hidden_states, self.key, col_scale=kcs).view(B, Sl, H, D)
+        v = self._linear(hidden_states, self.value).view(B, Sl, H, D)
         if mode == "local" or cfg.sp_size == 1:
             kw = dict(layout="bshd", causal=cfg.causal)
             if attention_mask is not None:
@@ -295,7 +305,7 @@ class SequenceParallelAttention(nn.Module):
                 if attention_mask is not None:
                     kw["additive_mask"] = attention_mask
                 ctx = _local.attention_step(q, kf, vf, **kw)
-        return _local.linear(ctx.reshape(B, Sl, H * D), self.output.weight, self.output.bias, "none", residual)
+        return self._linear(ctx.reshape(B, Sl, H * D), self.output, residual=residual)
 
 
 class SequenceParallelMLP(nn.Module):
@@ -308,13 +318,15 @@ class SequenceParallelMLP(nn.Module):
         self.dense_h_to_4h = nn.Linear(hidden_size, intermediate_size, bias=bias)
         self.dense_4h_to_h = nn.Linear(intermediate_size, hidden_size, bias=bias)
         self.activation = activation
+        self._cast = CastCache()
 
     def forward(self, hidden_states: torch.Tensor, residual: Optional[torch.Tensor] = None,
                 pre_norm: Optional[nn.LayerNorm] = None) -> torch.Tensor:
         if pre_norm is not None:
-            hidden_states = _local.prenorm(hidden_states, pre_norm)
-        h = _local.linear(hidden_states, self.dense_h_to_4h.weight, self.dense_h_to_4h.bias, self.activation)
-        return _local.linear(h, self.dense_4h_to_h.weight, self.dense_4h_to_h.bias, "none", residual)
+            hidden_states = _local.prenorm(hidden_states, pre_norm, self._cast)
+        fc1, fc2 = self.dense_h_to_4h, self.dense_4h_to_h
+        h = _local.cached_linear(self._cast, hidden_states, fc1.weight, fc1.bias, self.activation)
+        return _local.cached_linear(self._cast, h, fc2.weight, fc2.bias, "none", residual)
 
 
 class SequenceShardedModule(nn.Module):
@@ -374,26 +386,15 @@ class SequenceParallelConverter:
 
         for name, child in list(module.named_children()):
             if isinstance(child, (FlashAttentionLayer, FlashSelfAttention)):
-                d, H = child.hidden_size, child.num_attention_heads
-                if child.num_kv_heads != H:
-                    raise NotImplementedError("sequence-parallel conversion of GQA attention is not implemented")
+                qkv, o_proj = attention_projections(child, "sequence-parallel")
                 cfg = copy.copy(self.config)
                 cfg.causal = child.config.causal
-                new = SequenceParallelAttention(d, H, cfg, attention_dropout=0.0)
-                p0 = child.o_proj.weight
-                new = new.to(device=p0.device, dtype=p0.dtype)
+                new = SequenceParallelAttention(child.hidden_size, child.num_attention_heads, cfg, attention_dropout=0.0)
+                new = new.to(device=o_proj.weight.device, dtype=o_proj.weight.dtype)
                 with torch.no_grad():
-                    if isinstance(child, FlashSelfAttention):
-                        w, b = child.qkv_proj.weight, child.qkv_proj.bias
-                        for i, tgt in enumerate((new.query, new.key, new.value)):
-                            tgt.weight.copy_(w[i * d:(i + 1) * d])
-                            tgt.bias.copy_(b[i * d:(i + 1) * d])
-                    else:
-                        for src, tgt in ((child.q_proj, new.query), (child.k_proj, new.key), (child.v_proj, new.value)):
-                            tgt.weight.copy_(src.weight)
-                            tgt.bias.copy_(src.bias)
-                    new.output.weight.copy_(child.o_proj.weight)
-                    new.output.bias.copy_(child.o_proj.bias)
+                    for tgt, (w, b) in zip((new.query, new.key, new.value, new.output), qkv + [(o_proj.weight, o_proj.bias)]):
+                        tgt.weight.copy_(w)
+                        tgt.bias.copy_(b)
                 setattr(module, name, new)
             else:
                 self._convert(child)

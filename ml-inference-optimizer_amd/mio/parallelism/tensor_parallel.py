@@ -20,9 +20,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .._nn import CastCache, attention_plan
 from . import _local
 from . import communication as comm
-from .parallel_utils import divide, set_tensor_model_parallel_attributes, split_tensor_along_dim
+from .parallel_utils import attention_projections, divide, set_tensor_model_parallel_attributes, split_tensor_along_dim
 
 
 class TensorParallelConfig:
@@ -86,6 +87,7 @@ class ColumnParallelLinear(nn.Module):
         self.gather_output = gather_output if gather_output is not None else self.config.gather_output
         self.skip_bias_add = skip_bias_add
         self.activation = "none"  # fused epilogue when followed by an activation (TensorParallelMLP)
+        self._cast = CastCache()
 
     def reset_parameters(self):
         nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
@@ -95,7 +97,7 @@ class ColumnParallelLinear(nn.Module):
 
     def forward(self, input: torch.Tensor):
         fuse_bias = self.bias is not None and not self.skip_bias_add
-        out = _local.linear(input, self.weight, self.bias if fuse_bias else None, self.activation)
+        out = _local.cached_linear(self._cast, input, self.weight, self.bias if fuse_bias else None, self.activation)
         if self.gather_output and self.config.tp_size > 1:
             out = comm.all_gather(out, dim=-1, group=self.config.get_tp_group())
         if self.bias is not None and self.skip_bias_add:
@@ -126,6 +128,7 @@ class RowParallelLinear(nn.Module):
             set_tensor_model_parallel_attributes(self.bias, False, 0, 1)
         self.input_is_parallel = input_is_parallel
         self.skip_bias_add = skip_bias_add
+        self._cast = CastCache()
 
     def reset_parameters(self):
         nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
@@ -145,7 +148,7 @@ class RowParallelLinear(nn.Module):
         bias = self.bias if (self.bias is not None and not self.skip_bias_add and add_here) else None
         res = residual if add_here else None
         if not torch.distributed.is_initialized() or (tp == 1 and not comm.FORCE_SINGLE_RANK_COLLECTIVES):
-            out = _local.linear(input, self.weight, bias, "none", res)
+            out = _local.cached_linear(self._cast, input, self.weight, bias, "none", res)
         else:
             group = cfg.get_tp_group()
             x2 = input.reshape(-1, input.shape[-1])
@@ -157,7 +160,7 @@ class RowParallelLinear(nn.Module):
             works = []
             for i in range(n):
                 a, b = bounds[i], bounds[i + 1]
-                _local.linear(x2[a:b], self.weight, bias, "none", None if r2 is None else r2[a:b], out=out2[a:b])
+                _local.cached_linear(self._cast, x2[a:b], self.weight, bias, "none", None if r2 is None else r2[a:b], out=out2[a:b])
                 works.append(torch.distributed.all_reduce(out2[a:b], group=group, async_op=True))
             for w in works:
                 w.wait()  # stream-level wait on GPU; the host does not block
@@ -198,7 +201,7 @@ class TensorParallelMLP(nn.Module):
                 pre_norm: Optional[nn.LayerNorm] = None) -> torch.Tensor:
         """pre_norm (not in the reference): the pre-LN block's `mlp(ln(x))` in one call, as FusedMLP.forward takes it."""
         if pre_norm is not None:
-            hidden_states = _local.prenorm(hidden_states, pre_norm)
+            hidden_states = _local.prenorm(hidden_states, pre_norm, self.dense_h_to_4h._cast)
         return self.dense_4h_to_h(self.dense_h_to_4h(hidden_states), residual=residual)
 
 
@@ -230,21 +233,14 @@ class TensorParallelAttention(nn.Module):
             self.dropout_p = attention_dropout
         else:
             self.dropout_p = 0.0
-        self._fused = {}
+        self._cast = CastCache()
 
-    def _fused_weight(self, names: Tuple[str, ...]) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-        """Row-concatenation of the named local projections, rebuilt only when a parameter changes."""
-        lins = [getattr(self, n) for n in names]
-        key = tuple((l.weight.data_ptr(), l.weight._version, None if l.bias is None else l.bias._version,
-                     l.weight.dtype, l.weight.device) for l in lins)
-        hit = self._fused.get(names)
-        if hit is not None and hit[0] == key:
-            return hit[1], hit[2]
-        with torch.no_grad():
-            w = torch.cat([l.weight for l in lins], dim=0).contiguous()
-            b = None if lins[0].bias is None else torch.cat([l.bias for l in lins], dim=0).contiguous()
-        self._fused[names] = (key, w, b)
-        return w, b
+    def _fused_linear(self, x: torch.Tensor, lins: Tuple[ColumnParallelLinear, ...], col_scale=None) -> torch.Tensor:
+        """ONE GEMM on the row-concatenation of the local projections `lins`; the concatenated weight and bias and the weight's
+        blocked form are kept in this module's cache until a parameter changes."""
+        ws, dt = tuple(l.weight for l in lins), lins[0].weight.dtype
+        return _local.cached_linear(self._cast, x, self._cast.get_cat(ws, dt), self._cast.get_cat(tuple(l.bias for l in lins), dt),
+                                    col_scale=col_scale, parts=ws)
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 encoder_hidden_states: Optional[torch.Tensor] = None,
@@ -252,7 +248,7 @@ class TensorParallelAttention(nn.Module):
         if self.training and self.dropout_p > 0:
             raise NotImplementedError("attention dropout (training) is not supported by the inference kernel")
         if pre_norm is not None:
-            hidden_states = _local.prenorm(hidden_states, pre_norm)
+            hidden_states = _local.prenorm(hidden_states, pre_norm, self._cast)
         B, S, _ = hidden_states.shape
         Hl, D = self.num_heads_per_partition, self.head_dim
         kv_in = encoder_hidden_states if (self.is_cross_attention and encoder_hidden_states is not None) else hidden_states
@@ -260,17 +256,16 @@ class TensorParallelAttention(nn.Module):
         Sk = kv_in.shape[1]
         kpre = False
         if kv_in is hidden_states:  # self attention: one [3 n, hidden] GEMM, q / k / v are strided views of its result
-            w, b = self._fused_weight(("query", "key", "value"))
-            # where both kernels can: the K columns leave the GEMM multiplied by softmax_scale * log2(e) (one rounding) and
-            # the attention launch drops its per-score multiply (ops.fa3_fwd k_prescaled)
-            kpre = (attention_mask is None and n % 128 == 0
-                    and _local.k_prescale_ok(B, S, Hl, D, B * S, 3 * n, hidden_states.shape[-1], carry=False, row_stride=3 * n))
-            qkv = _local.linear(hidden_states, w, b, col_scale=(n, 2 * n, D ** -0.5 * 1.4426950408889634) if kpre else None)
+            # where both kernels can (_nn.attention_plan): the K columns [n, 2n) leave the GEMM multiplied by softmax_scale * log2(e)
+            # (one rounding) and the attention launch drops its per-score multiply (ops.fa3_fwd k_prescaled)
+            plan = attention_plan(B, S, S, Hl, Hl, D, (B * S, 3 * n, hidden_states.shape[-1]), (n, 2 * n), 3 * n,
+                                  mask=attention_mask is not None)
+            kpre = plan.kpre
+            qkv = self._fused_linear(hidden_states, (self.query, self.key, self.value), plan.col_scale)
             q, k, v = (qkv[..., i * n:(i + 1) * n].view(B, S, Hl, D) for i in range(3))
-        else:
+        else:  # cross attention: K stays unscaled
             q = self.query(hidden_states).view(B, S, Hl, D)
-            w, b = self._fused_weight(("key", "value"))
-            kv = _local.linear(kv_in, w, b)
+            kv = self._fused_linear(kv_in, (self.key, self.value))
             k, v = (kv[..., i * n:(i + 1) * n].view(B, Sk, Hl, D) for i in range(2))
         add = None
         if attention_mask is not None:  # additive [B,1,Sq,Sk] / [B,1,1,Sk] like the reference (:560-566)
@@ -295,15 +290,16 @@ class ModelParallelConverter:
         return model_tp
 
     # -- slicing helpers
-    def _col(self, lin: nn.Linear, **kw) -> ColumnParallelLinear:
+    def _col(self, weight: torch.Tensor, bias: Optional[torch.Tensor], **kw) -> ColumnParallelLinear:
+        """This rank's rows of the full [out, in] weight (and bias) as a ColumnParallelLinear."""
         tp, r = self.config.tp_size, self.config.tp_rank()
-        new = ColumnParallelLinear(lin.in_features, lin.out_features, lin.bias is not None, self.config, **kw)
-        new = new.to(device=lin.weight.device, dtype=lin.weight.dtype)
-        per = lin.out_features // tp
+        new = ColumnParallelLinear(weight.shape[1], weight.shape[0], bias is not None, self.config, **kw)
+        new = new.to(device=weight.device, dtype=weight.dtype)
+        per = weight.shape[0] // tp
         with torch.no_grad():
-            new.weight.copy_(lin.weight[r * per:(r + 1) * per])
-            if lin.bias is not None:
-                new.bias.copy_(lin.bias[r * per:(r + 1) * per])
+            new.weight.copy_(weight[r * per:(r + 1) * per])
+            if bias is not None:
+                new.bias.copy_(bias[r * per:(r + 1) * per])
         return new
 
     def _row(self, lin: nn.Linear, **kw) -> RowParallelLinear:
@@ -335,7 +331,7 @@ class ModelParallelConverter:
                     setattr(module, name, self._row(child, input_is_parallel=False))
                 elif any(s in lname for s in ("q_proj", "k_proj", "v_proj", "query", "key", "value", "fc1", "up_proj",
                                               "gate_proj", "dense_h_to_4h")):
-                    setattr(module, name, self._col(child, gather_output=True))
+                    setattr(module, name, self._col(child.weight, child.bias, gather_output=True))
             else:
                 self._convert_module(child)
 
@@ -343,29 +339,15 @@ class ModelParallelConverter:
         act = mlp._kernel_activation()
         d, I = mlp.fc1.in_features, mlp.fc1.out_features
         new = TensorParallelMLP(d, I, self.config, activation=act)
-        new.dense_h_to_4h = self._col(mlp.fc1, gather_output=False)
+        new.dense_h_to_4h = self._col(mlp.fc1.weight, mlp.fc1.bias, gather_output=False)
         new.dense_h_to_4h.activation = act
         new.dense_4h_to_h = self._row(mlp.fc2, input_is_parallel=True)
         return new
 
     def _convert_flash_attention(self, att) -> TensorParallelAttention:
-        from ..kernels.attention.flash_attention import FlashSelfAttention
-
-        tp = self.config.tp_size
-        d, H = att.hidden_size, att.num_attention_heads
-        if att.num_kv_heads != H:
-            raise NotImplementedError("tensor-parallel conversion of GQA attention is not implemented")
-        new = TensorParallelAttention(d, H, self.config, causal=att.config.causal)
-        if isinstance(att, FlashSelfAttention):
-            w, b = att.qkv_proj.weight, att.qkv_proj.bias
-            parts = [(w[i * d:(i + 1) * d], b[i * d:(i + 1) * d]) for i in range(3)]
-        else:
-            parts = [(p.weight, p.bias) for p in (att.q_proj, att.k_proj, att.v_proj)]
-        for tgt, (w, b) in zip(("query", "key", "value"), parts):
-            lin = nn.Linear(d, d).to(device=w.device, dtype=w.dtype)
-            with torch.no_grad():
-                lin.weight.copy_(w)
-                lin.bias.copy_(b)
-            setattr(new, tgt, self._col(lin, gather_output=False))
-        new.output = self._row(att.o_proj, input_is_parallel=True)
+        qkv, o_proj = attention_projections(att, "tensor-parallel")
+        new = TensorParallelAttention(att.hidden_size, att.num_attention_heads, self.config, causal=att.config.causal)
+        for tgt, (w, b) in zip(("query", "key", "value"), qkv):
+            setattr(new, tgt, self._col(w, b, gather_output=False))
+        new.output = self._row(o_proj, input_is_parallel=True)
         return new

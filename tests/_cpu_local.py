@@ -2,7 +2,9 @@
 
 They reproduce the CONTRACT of the two HIP entry points (ops.gemm_bias_act, ops.fa3_fwd incl. the
 (o_acc, lse) carry) with the CPU oracle, so the distributed schedules can be exercised without a GPU.
-Test-only: the product never imports this."""
+The schedule tests run shapes too small for the real capability queries, so install() also replaces the two queries
+mio._nn.attention_plan asks (ops.fa3_k_prescaled_ok, ops.col_scale_ok); the plan itself, with its mask and 128-column terms, is
+the real one.  Test-only: the product never imports this."""
 import torch
 
 import oracle
@@ -12,7 +14,7 @@ _ACTS = {"none": lambda x: x, "gelu": gelu_tanh, "gelu_erf": torch.nn.functional
          "relu": torch.relu, "silu": torch.nn.functional.silu}
 
 
-def linear(x, weight, bias=None, activation="none", residual=None, out=None, col_scale=None):
+def linear(x, weight, bias=None, activation="none", residual=None, out=None, col_scale=None, w_blocked=None):
     y = torch.nn.functional.linear(x.double(), weight.double(), None if bias is None else bias.double())
     y = _ACTS[activation](y)
     if col_scale is not None:  # (lo, hi, value): scaled before the one rounding to the storage dtype
@@ -63,19 +65,21 @@ def layernorm(x, weight, bias=None, eps=1e-5):
     return oracle.layernorm(x, weight, bias, eps).to(x.dtype)
 
 
-def k_prescale_ok(B, Sq, H, D, M, N, K, carry=True, row_stride=None):
-    return D <= 64  # (the HIP rule also wants Sq > 128 and a 256-tile GEMM shape; the schedule tests run smaller)
+def fa3_k_prescaled_ok(B, Sq, Sk, H, D, k_row_stride, v_row_stride, carry=False):
+    return D <= 64  # (the HIP rule also wants Sq > 128; the schedule tests run smaller)
+
+
+def col_scale_ok(M, N, K, activation="none"):
+    return True  # (the HIP rule wants a 256-tile GEMM shape)
 
 
 def install(monkeypatch=None):
+    from mio import ops
     from mio.parallelism import _local
-    if monkeypatch is not None:
-        monkeypatch.setattr(_local, "linear", linear)
-        monkeypatch.setattr(_local, "attention_step", attention_step)
-        monkeypatch.setattr(_local, "layernorm", layernorm)
-        monkeypatch.setattr(_local, "k_prescale_ok", k_prescale_ok)
-    else:
-        _local.linear = linear
-        _local.attention_step = attention_step
-        _local.layernorm = layernorm
-        _local.k_prescale_ok = k_prescale_ok
+    patches = [(_local, "linear", linear), (_local, "attention_step", attention_step), (_local, "layernorm", layernorm),
+               (ops, "fa3_k_prescaled_ok", fa3_k_prescaled_ok), (ops, "col_scale_ok", col_scale_ok)]
+    for mod, name, fn in patches:
+        if monkeypatch is not None:
+            monkeypatch.setattr(mod, name, fn)
+        else:
+            setattr(mod, name, fn)

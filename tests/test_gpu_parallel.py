@@ -234,9 +234,9 @@ def _spy_linear():
     from mio.parallelism import _local
     seen, real = [], _local.linear
 
-    def spy(x, weight, bias=None, activation="none", residual=None, out=None, col_scale=None):
+    def spy(x, weight, bias=None, activation="none", residual=None, out=None, col_scale=None, **kw):
         seen.append(col_scale)
-        return real(x, weight, bias, activation, residual, out, col_scale)
+        return real(x, weight, bias, activation, residual, out, col_scale, **kw)
     _local.linear = spy
     return seen
 
