@@ -323,6 +323,28 @@ typedef enum {
 } mio_gemm_route_t;
 int32_t mio_gemm_route(int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
                        int32_t has_residual, int32_t w_layout, int32_t fold_in, int32_t stats_out);
+
+/* The decode-step GEMM: mio_gemm_bias_act's contraction and epilogue for 1 <= M <= 64 rows (M = the batch of a decode step), on
+ * a kernel that streams the row-major [N, K] weight from HBM once, straight into registers (csrc/gemm_skinny.hip).  The
+ * reference has no such kernel: its decode step runs the projections and the MLP through F.linear
+ * (kernels/attention/flash_attention.py:629-631,654-657; kernels/mlp/fused_mlp.py:159,176).
+ *   arguments as mio_gemm_bias_act (ld*: multiples of 8 elements, K % 8 == 0, pointers 16-byte aligned, bias / residual
+ *   nullable, w_gate iff act == SWIGLU), but any N >= 1, and a workspace.
+ * K is cut into mio_gemm_skinny_splits() slices of whole 32-k steps (mio_gemm_skinny_slice: the k range of one) so that the
+ * launch fills the chip; with more than one slice the kernel writes fp32 partials [splits][M][N] (SwiGLU: twice, up then gate)
+ * into `workspace` (>= mio_gemm_skinny_workspace_bytes(), 0 with one slice) and a second small kernel sums them in slice order,
+ * applies bias / activation / residual and rounds once.  No workgroup waits for another: the result is bit-reproducible, and
+ * the launch neither allocates nor synchronises (graph-capturable).
+ * mio_gemm_skinny runs every legal shape; M == 0 returns 0 and launches nothing.  mio_gemm_skinny_ok only advises the module
+ * layer: 1 where the shape is legal AND measured at most 0.9 x the time of mio_gemm_bias_act's route (profiles/skinny_gemm.md).
+ * mio_gemm_skinny_splits / _slice return < 0 (mio_last_error()) on a shape the launch refuses. */
+size_t mio_gemm_skinny_workspace_bytes(int64_t M, int32_t N, int32_t K, int32_t act);
+int mio_gemm_skinny_splits(int64_t M, int32_t N, int32_t K, int32_t act);
+int mio_gemm_skinny_slice(int64_t M, int32_t N, int32_t K, int32_t act, int32_t slice, int32_t* k_begin, int32_t* k_end);
+int mio_gemm_skinny_ok(int64_t M, int32_t N, int32_t K, int32_t act);
+int mio_gemm_skinny(const void* x, const void* w, const void* bias, const void* w_gate, const void* bias_gate,
+                    const void* residual, void* y, void* workspace, int64_t M, int32_t N, int32_t K, int64_t ldx,
+                    int64_t ldw, int64_t ldy, int64_t ldr, int32_t act, int32_t dtype, void* stream);
 /* x_blocked != 0: the activation operand x is in the same blocked layout (m in the place of n; ceil(M/256)*256 x K
  * elements, ldx ignored) -- what mio_layernorm_fwd_bx writes, so that LayerNorm -> GEMM hands over contiguous K-tiles. */
 int mio_layernorm_fwd_bx(const void* x, const void* residual, const void* weight, const void* bias, void* yb,

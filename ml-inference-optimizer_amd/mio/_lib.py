@@ -105,6 +105,11 @@ EXPORTS = (
     "mio_weight_block_glu",
     "mio_fused_mlp_glu_fwd_bw",
     "mio_gemm_route",
+    "mio_gemm_skinny_workspace_bytes",
+    "mio_gemm_skinny_splits",
+    "mio_gemm_skinny_slice",
+    "mio_gemm_skinny_ok",
+    "mio_gemm_skinny",
     "mio_layernorm_fwd_bx",
     "mio_ln_stats_bytes",
     "mio_gemm_ln_ok",
@@ -268,6 +273,16 @@ def _load() -> C.CDLL:
     lib.mio_attn_merge.restype = i32
     lib.mio_gemm_bias_act.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
     lib.mio_gemm_bias_act.restype = i32
+    lib.mio_gemm_skinny_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.mio_gemm_skinny_workspace_bytes.restype = C.c_size_t
+    lib.mio_gemm_skinny_splits.argtypes = [i64, i32, i32, i32]
+    lib.mio_gemm_skinny_splits.restype = i32
+    lib.mio_gemm_skinny_slice.argtypes = [i64, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+    lib.mio_gemm_skinny_slice.restype = i32
+    lib.mio_gemm_skinny_ok.argtypes = [i64, i32, i32, i32]
+    lib.mio_gemm_skinny_ok.restype = i32
+    lib.mio_gemm_skinny.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
+    lib.mio_gemm_skinny.restype = i32
     lib.mio_fused_mlp_workspace_bytes.argtypes = [i64, i32, i32, i32]
     lib.mio_fused_mlp_workspace_bytes.restype = C.c_size_t
     lib.mio_fused_mlp_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]

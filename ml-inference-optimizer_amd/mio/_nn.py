@@ -165,12 +165,16 @@ class ResidualStream:
 
 
 def linear(x: torch.Tensor, lin: nn.Linear, cache: CastCache, dtype: torch.dtype, activation: str = "none",
-           residual: Optional[torch.Tensor] = None, col_scale=None, x_blocked_shape=None) -> torch.Tensor:
+           residual: Optional[torch.Tensor] = None, col_scale=None, x_blocked_shape=None, skinny: bool = False) -> torch.Tensor:
     """F.linear(x, W, b) (+ activation, + residual) on the MFMA GEMM.  At sizes that run the 256x256-tile kernels the
-    weight is handed over in the blocked layout (repacked once per parameter version, cached next to the cast copy)."""
+    weight is handed over in the blocked layout (repacked once per parameter version, cached next to the cast copy).
+    skinny (the modules' decode_gemm option): a row-major x without a column scale goes to the decode-step GEMM
+    (ops.gemm_skinny, the same row-major weight copy) where ops.gemm_skinny_ok advises it."""
     w = cache.get(lin.weight, dtype)
     N, K = w.shape
     M = x.numel() // K if x_blocked_shape is None else int(math.prod(x_blocked_shape[:-1]))
+    if skinny and x_blocked_shape is None and col_scale is None and ops.gemm_skinny_ok(M, N, K, activation):
+        return ops.gemm_skinny(x, w, cache.get(lin.bias, dtype), activation, residual=residual)
     wb = cache.get_blocked(lin.weight, dtype) if (K % 32 == 0 and ops.blocked_weight_ok(M, N, K, activation)) else None
     return ops.gemm_bias_act(x, w, cache.get(lin.bias, dtype), activation, residual=residual, w_blocked=wb,
                              col_scale=col_scale, x_blocked_shape=x_blocked_shape)

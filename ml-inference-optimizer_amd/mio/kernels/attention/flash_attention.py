@@ -46,6 +46,9 @@ class FlashAttentionConfig:
     rotary_base: float = 10000.0
     rotary_interleaved: bool = False
     max_position: int = 8192
+    # decode steps (the paged branch, "block_tables" in kwargs): the q / qkv projection and o_proj run on the decode-step GEMM
+    # (ops.gemm_skinny) where ops.gemm_skinny_ok advises it; off: every call as before
+    decode_gemm: bool = False
 
     @property
     def allowed_precisions(self) -> Set[str]:
@@ -189,7 +192,8 @@ class _AttentionBase(nn.Module):
         out = torch.empty(B, q_len, self.num_attention_heads, self.head_dim, dtype=dt, device=q2d.device)
         ops.paged_attention_forward(q, out.permute(0, 2, 1, 3), k_cache, v_cache, bt, cl, bs, max_seq_len, layer_idx,
                                     **_decode_window_kw(self.config), **scales)
-        return linear(out.view(B, q_len, self.hidden_size), self.o_proj, self._cast, dt, residual=residual)
+        return linear(out.view(B, q_len, self.hidden_size), self.o_proj, self._cast, dt, residual=residual,
+                      skinny=self.config.decode_gemm)
 
     def _plan(self, B, S, k_proj, k_cols, kv_stride, o_proj, mask: bool):
         """mio._nn.attention_plan of a dense self-attention call of this module (Sq = Sk = S) under its config."""
@@ -245,7 +249,8 @@ class FlashAttentionLayer(_AttentionBase):
         dt = compute_dtype(self.config.precision, hidden_states)
         x, r, c = as_dtype(hidden_states, dt), as_dtype(residual, dt), self._cast
         if "block_tables" in kwargs:
-            return as_dtype(self._paged(linear(x, self.q_proj, c, dt), B, S, dt, kwargs, "FlashAttentionLayer", r), in_dtype)
+            q2d = linear(x, self.q_proj, c, dt, skinny=self.config.decode_gemm)
+            return as_dtype(self._paged(q2d, B, S, dt, kwargs, "FlashAttentionLayer", r), in_dtype)
         _refuse(self.config, self.training)
         # K is the whole output of k_proj; q / k / v are tensors of their own and the context stays row-major (no o_proj shape)
         kv_dim = self.num_kv_heads * self.head_dim
@@ -325,7 +330,8 @@ class FlashSelfAttention(_AttentionBase):
             # only the query slice of the fused projection is needed on the paged path (:572-621)
             wq = c.get(self.qkv_proj.weight, dt)[:q_dim]
             bq = c.get(self.qkv_proj.bias, dt)
-            q2d = ops.gemm_bias_act(x, wq, None if bq is None else bq[:q_dim].contiguous())
+            gemm = ops.gemm_skinny if cfg.decode_gemm and ops.gemm_skinny_ok(B * S, q_dim, wq.shape[1]) else ops.gemm_bias_act
+            q2d = gemm(x, wq, None if bq is None else bq[:q_dim].contiguous())
             return as_dtype(self._paged(q2d, B, S, dt, kwargs, "FlashSelfAttention", r), in_dtype)
         _refuse(cfg, self.training)
         # [B,S,q_dim+2*kv_dim]; q / k / v are strided views of it, K its columns [q_dim, q_dim + kv_dim)

@@ -32,6 +32,9 @@ class FusedMLPConfig:
     sequence_parallel: bool = False
     tensor_parallel: bool = False
     checkpoint_activation: bool = False
+    # decode steps (at most 64 rows, plain-tensor input): fc1 and fc2 run as two decode-step GEMMs (ops.gemm_skinny) where
+    # ops.gemm_skinny_ok advises both; off: every call as before
+    decode_gemm: bool = False
 
 
 class FusedMLP(nn.Module):
@@ -106,6 +109,12 @@ class FusedMLP(nn.Module):
         x, r, c = as_dtype(hidden_states, dt), as_dtype(residual, dt), self._cast
         gw, gb = self._gate(dt)
         M, d, I = x.numel() // x.shape[-1], x.shape[-1], self.fc1.weight.shape[0]
+        if self.config.decode_gemm and ops.gemm_skinny_ok(M, I, d, act) and ops.gemm_skinny_ok(M, self.fc2.weight.shape[0], I):
+            if pre_norm is not None:
+                x = apply_norm(x, pre_norm, c, dt)
+            h = ops.gemm_skinny(x, c.get(self.fc1.weight, dt), c.get(self.fc1.bias, dt), act, gw, gb)
+            out = ops.gemm_skinny(h, c.get(self.fc2.weight, dt), c.get(self.fc2.bias, dt), residual=r)
+            return as_dtype(out, in_dtype)
         b1 = b2 = None  # blocked weight copies, when this shape runs the kernels that take them
         if ops.fused_mlp_blocked_weight_ok(M, d, I, act):
             if gw is None:

@@ -701,6 +701,65 @@ def gemm_bias_act(x, w, bias=None, activation: str = "none", w_gate=None, bias_g
     return out
 
 
+# ---- the decode-step GEMM (mio_gemm_skinny: 1 <= M <= 64 rows, the weight streamed once from its row-major copy) -----------------
+def gemm_skinny_ok(M: int, N: int, K: int, activation: str = "none") -> bool:
+    """True iff gemm_skinny is legal at this shape AND the measured better choice over gemm_bias_act (profiles/skinny_gemm.md).
+    Advice for the module layer: gemm_skinny itself runs every legal shape."""
+    return activation in _ACT and bool(lib.mio_gemm_skinny_ok(M, N, K, _ACT[activation]))
+
+
+def gemm_skinny_splits(M: int, N: int, K: int, activation: str = "none") -> int:
+    """The slices of K a gemm_skinny call of this shape runs (1: one launch, no workspace).  Host-only; ValueError where the
+    call would be refused."""
+    if activation not in _ACT:
+        raise ValueError(f"Unsupported activation function: {activation}")
+    n = lib.mio_gemm_skinny_splits(M, N, K, _ACT[activation])
+    if n < 0:
+        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def gemm_skinny(x, w, bias=None, activation: str = "none", w_gate=None, bias_gate=None, residual=None, out=None):
+    """gemm_bias_act for at most 64 rows (x [..., K] with prod(...) <= 64, w [N, K], any N): y = act(x @ w^T + bias) (+ residual)
+    on the weight-streaming kernel.  Allocates the split workspace only when the plan splits K."""
+    _need_cuda(x, w)
+    if activation not in _ACT:
+        raise ValueError(f"Unsupported activation function: {activation}")
+    act = _ACT[activation]
+    dt = _dtype_id(x)
+    if w.dtype != x.dtype:
+        raise ValueError("x and w must have the same dtype")
+    if w.shape[1] != x.shape[-1]:
+        raise ValueError(f"weight shape {tuple(w.shape)} does not match input features {x.shape[-1]}")
+    N, K = w.shape
+    _vec_ok(bias, N, x.dtype, "bias")
+    if act == _lib.ACT_SWIGLU:
+        _vec_ok(bias_gate, N, x.dtype, "bias_gate")
+        if w_gate is None:
+            raise ValueError("SwiGLU activation requires gate weights")
+        if w_gate.shape != w.shape or w_gate.dtype != w.dtype:
+            raise ValueError("w_gate must have w's shape and dtype")
+        _need_cuda(w_gate)
+    lead, x2 = tuple(x.shape[:-1]), _rows16(x.reshape(-1, K))
+    M = x2.shape[0]
+    if M > 64:
+        raise ValueError(f"gemm_skinny takes at most 64 rows, got {M} (gemm_bias_act runs taller calls)")
+    _res_ok(residual, M * N, x.dtype)
+    r2 = None if residual is None else _rows16(residual.reshape(-1, N))
+    w2 = _rows16(w)
+    g2, bias_gate = (_rows16(w_gate), bias_gate) if act == _lib.ACT_SWIGLU else (None, None)
+    if g2 is not None and g2.stride(0) != w2.stride(0):
+        g2, w2 = g2.contiguous(), w2.contiguous()
+    if out is None:  # (rows of N % 8 != 0 columns: a view of rows padded to the stride the kernel's 8-byte stores need)
+        out = torch.empty(*lead, (N + 7) // 8 * 8, dtype=x.dtype, device=x.device)[..., :N]
+    y2 = out.view(-1, N)
+    nbytes = lib.mio_gemm_skinny_workspace_bytes(M, N, K, act)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    check(lib.mio_gemm_skinny(x2.data_ptr(), w2.data_ptr(), _ptr(bias), _ptr(g2), _ptr(bias_gate), _ptr(r2), y2.data_ptr(),
+                              _ptr(ws), M, N, K, x2.stride(0), w2.stride(0), y2.stride(0), 0 if r2 is None else r2.stride(0), act, dt, _stream()))
+    return out
+
+
 # ---- LayerNorm folded into the GEMMs on either side of it (mio_gemm_ln_bw; reference fused_layernorm_qkv.py:37-420) ------------
 def gemm_ln_ok(M: int, N: int, K: int, activation: str = "none", fold_in: bool = False, stats_out: bool = False) -> bool:
     """True iff gemm_ln(...) runs this shape: fold_in = the projection behind a LayerNorm (ln_stats given),
