@@ -337,10 +337,14 @@ int32_t mio_gemm_route(int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw
  * the launch neither allocates nor synchronises (graph-capturable).
  * mio_gemm_skinny runs every legal shape; M == 0 returns 0 and launches nothing.  mio_gemm_skinny_ok only advises the module
  * layer: 1 where the shape is legal AND measured at most 0.9 x the time of mio_gemm_bias_act's route (profiles/skinny_gemm.md).
- * mio_gemm_skinny_splits / _slice return < 0 (mio_last_error()) on a shape the launch refuses. */
+ * mio_gemm_skinny_splits / _slice return < 0 (mio_last_error()) on a shape the launch refuses.
+ * Inside a slice a workgroup runs a double-buffered loop over chunks of mio_gemm_skinny_chunk_k(act) k (256, SwiGLU 128; < 0 on
+ * an unknown activation): ceil(slice length / chunk) chunks, which is what the tests ask to know which parts of that loop a
+ * shape reaches. */
 size_t mio_gemm_skinny_workspace_bytes(int64_t M, int32_t N, int32_t K, int32_t act);
 int mio_gemm_skinny_splits(int64_t M, int32_t N, int32_t K, int32_t act);
 int mio_gemm_skinny_slice(int64_t M, int32_t N, int32_t K, int32_t act, int32_t slice, int32_t* k_begin, int32_t* k_end);
+int mio_gemm_skinny_chunk_k(int32_t act);
 int mio_gemm_skinny_ok(int64_t M, int32_t N, int32_t K, int32_t act);
 int mio_gemm_skinny(const void* x, const void* w, const void* bias, const void* w_gate, const void* bias_gate,
                     const void* residual, void* y, void* workspace, int64_t M, int32_t N, int32_t K, int64_t ldx,

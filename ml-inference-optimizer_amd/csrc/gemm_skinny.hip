@@ -71,7 +71,7 @@ __device__ __forceinline__ void skinny_finish(const SkinnyDev& p, int m, int n, 
 template <typename T, int MF, bool GLU>
 __global__ __launch_bounds__(256) void gemm_skinny_kernel(const SkinnyDev p) {
   using X8 = typename DT<T>::x8;
-  constexpr int SKC = GLU ? 128 : 256;  // k per chunk: the weight registers of two chunks (this one, the next) are 64 VGPRs
+  constexpr int SKC = GLU ? SKINNY_CHUNK_K_GLU : SKINNY_CHUNK_K;  // k per chunk (gemm_skinny_plan.h)
   constexpr int KS = SKC / SKINNY_KSTEP, PCS = SKC / 8, ROWS = MF * 16, ROWB = SKC * 2;
   constexpr int XPT = ROWS * PCS / 256;  // 16-byte pieces of the x chunk per thread
   static_assert(PCS >= 16 && ROWS * PCS % 256 == 0, "chunk shape");
@@ -264,6 +264,12 @@ extern "C" int mio_gemm_skinny_slice(int64_t M, int32_t N, int32_t K, int32_t ac
   MIO_CHECK(k_begin && k_end && slice >= 0 && slice < pl.nsplit, "mio_gemm_skinny_slice: slice must be in [0, mio_gemm_skinny_splits)");
   skinny_slice(pl, K, slice, *k_begin, *k_end);
   return 0;
+}
+
+extern "C" int mio_gemm_skinny_chunk_k(int32_t act) {
+  std::string err;
+  if (!skinny_shape_ok("mio_gemm_skinny_chunk_k", 0, 0, 0, act, err)) return mio_fail(err);
+  return act == MIO_ACT_SWIGLU ? SKINNY_CHUNK_K_GLU : SKINNY_CHUNK_K;
 }
 
 extern "C" int mio_gemm_skinny_ok(int64_t M, int32_t N, int32_t K, int32_t act) {

@@ -12,6 +12,10 @@
 constexpr int SKINNY_M_MAX = 64;   // 1 .. 4 row fragments of 16
 constexpr int SKINNY_BN = 64;      // output columns per workgroup: 4 waves x one 16-row weight fragment
 constexpr int SKINNY_KSTEP = 32;   // k per MFMA: every slice is whole steps (the last one ends at K)
+// k per chunk of the kernel's double-buffered loop over a slice (mio_gemm_skinny_chunk_k): the weight registers of two chunks
+// (this one, the next) are 64 VGPRs, so SwiGLU, with two weights, takes half the k
+constexpr int SKINNY_CHUNK_K = 256;
+constexpr int SKINNY_CHUNK_K_GLU = 128;
 // workgroups the split aims for: two per CU.  tools/skinny_gemm_bench.py, profiles/skinny_gemm.md: the sweep ran with this value.
 constexpr int SKINNY_WGS = 512;
 

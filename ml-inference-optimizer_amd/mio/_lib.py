@@ -108,6 +108,7 @@ EXPORTS = (
     "mio_gemm_skinny_workspace_bytes",
     "mio_gemm_skinny_splits",
     "mio_gemm_skinny_slice",
+    "mio_gemm_skinny_chunk_k",
     "mio_gemm_skinny_ok",
     "mio_gemm_skinny",
     "mio_layernorm_fwd_bx",
@@ -279,6 +280,8 @@ def _load() -> C.CDLL:
     lib.mio_gemm_skinny_splits.restype = i32
     lib.mio_gemm_skinny_slice.argtypes = [i64, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.mio_gemm_skinny_slice.restype = i32
+    lib.mio_gemm_skinny_chunk_k.argtypes = [i32]
+    lib.mio_gemm_skinny_chunk_k.restype = i32
     lib.mio_gemm_skinny_ok.argtypes = [i64, i32, i32, i32]
     lib.mio_gemm_skinny_ok.restype = i32
     lib.mio_gemm_skinny.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]

@@ -1,7 +1,8 @@
 """CPU-only tests of the decode-step GEMM's host side, through the loaded library: the C-ABI symbols are declared and bound, every
 refusal of mio_gemm_skinny returns before a launch with a message under the entry point's name, an empty call returns 0, the
 workspace size follows the split count, the split count never falls as K grows, the slices are whole 32-k steps that cover K, and
-ops.gemm_skinny checks its arguments as ops.gemm_bias_act does.  Addresses are fake and 16-byte aligned; nothing is dereferenced."""
+ops.gemm_skinny checks its arguments as ops.gemm_bias_act does, and the GPU tests' case tables (tests/_skinny_cases.py) reach the
+kernel's seams under the plan the library holds.  Addresses are fake and 16-byte aligned; nothing is dereferenced."""
 import ctypes as C
 import os
 import re
@@ -9,10 +10,12 @@ import re
 import pytest
 import torch
 
+import _skinny_cases as sk
+
 A = 1 << 20  # a fake 16-byte aligned device address
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = {"mio_gemm_skinny_workspace_bytes": 4, "mio_gemm_skinny_splits": 4, "mio_gemm_skinny_ok": 4, "mio_gemm_skinny": 18,
-           "mio_gemm_skinny_slice": 7}  # name -> number of C arguments
+           "mio_gemm_skinny_slice": 7, "mio_gemm_skinny_chunk_k": 1}  # name -> number of C arguments
 SWIGLU = 5
 SHAPES = [(M, N, K) for M in (1, 5, 16, 37, 64) for N in (1, 72, 1000, 3072, 14336) for K in (8, 40, 264, 1024, 2056, 4104, 14336)]
 
@@ -130,6 +133,78 @@ def test_slices_cover_k_in_whole_steps():
         kb, ke = C.c_int32(), C.c_int32()
         assert lib.mio_gemm_skinny_slice(M, N, K, 0, n, C.byref(kb), C.byref(ke)) != 0
         assert _err().startswith("mio_gemm_skinny_slice: ")
+
+
+def test_chunk_query():
+    """k per chunk of the kernel's loop: 256, SwiGLU 128 (two weights in the same registers); an unknown activation is refused."""
+    lib = _lib().lib
+    assert [lib.mio_gemm_skinny_chunk_k(a) for a in range(SWIGLU + 1)] == [256] * SWIGLU + [128]
+    for act in (-1, SWIGLU + 1):
+        assert lib.mio_gemm_skinny_chunk_k(act) < 0
+        assert _err() == "mio_gemm_skinny_chunk_k: unknown activation"
+
+
+def _chunks(c):
+    """Chunks per slice of case c under the loaded library's plan: one entry per slice."""
+    lib, act = _lib().lib, sk.ACTS.index(c.act)
+    n, per = lib.mio_gemm_skinny_splits(c.M, c.N, c.K, act), lib.mio_gemm_skinny_chunk_k(act)
+    assert n >= 1 and per > 0, (c, _err())
+    out = []
+    for s in range(n):
+        kb, ke = C.c_int32(), C.c_int32()
+        assert lib.mio_gemm_skinny_slice(c.M, c.N, c.K, act, s, C.byref(kb), C.byref(ke)) == 0, (c, _err())
+        out.append(-(-(ke.value - kb.value) // per))
+    return out
+
+
+def test_case_tables_reach_the_seams():
+    """What tests/test_gpu_gemm_skinny.py runs, under the plan as it is now.  Every case splits K or not as its table says; the
+    deep cases reach, for plain and SwiGLU and for each count of row fragments, one slice of 3, of 4 and of 5 or more chunks, and
+    several slices of 3 or more chunks with unequal counts (with a full and with a ragged last row fragment, and at M 1); the
+    ragged-N cases write partials (N % 4 != 0 at N 1, below 16, just under a workgroup's 64 columns and above it); SwiGLU runs at
+    every count of row fragments through both epilogues, with and without its biases and residual.  A requirement nobody meets
+    is reported with the chunk counts of its table's cases of that kind."""
+    from mio import _lib as L
+    assert [L.ACT_SWIGLU, sk.ACTS.index("swiglu")] == [SWIGLU] * 2 and sk.ACTS.index("none") == 0
+    chunks = {c: _chunks(c) for t in sk.TABLES.values() for c in t}
+    wrong = [(name, c.what, chunks[c]) for name, t in sk.TABLES.items() for c in t if (len(chunks[c]) > 1) != c.split]
+    assert not wrong, f"the plan splits K otherwise than these cases say: {wrong}"
+    missing = []
+
+    def need(table, glu, text, pred):
+        mine = [c for c in sk.TABLES[table] if c.glu == glu]
+        if not any(pred(c, chunks[c]) for c in mine):
+            missing.append(f"{table}: no {'SwiGLU' if glu else 'plain'} case with {text}; its cases: "
+                           + ", ".join(f"{c.what} -> {chunks[c]}" for c in mine))
+
+    def deep(ch):  # several slices, each long enough to reload a register set, of unequal chunk counts
+        return len(ch) > 1 and min(ch) >= 3 and len(set(ch)) > 1
+
+    for glu in (False, True):
+        for mf in (1, 2, 3, 4):
+            for n, text in ((3, "3"), (4, "4"), (5, "5 or more")):
+                need("DEEP_UNSPLIT", glu, f"MF {mf}, one slice of {text} chunks",
+                     lambda c, ch: c.mf == mf and len(ch) == 1 and (ch[0] == n if n < 5 else ch[0] >= 5))
+            for full in (True, False):
+                need("DEEP_SPLIT", glu, f"MF {mf}, a {'full' if full else 'ragged'} last fragment, slices of >= 3 chunks, unequal",
+                     lambda c, ch: c.mf == mf and (c.M % 16 == 0) == full and deep(ch))
+        need("DEEP_SPLIT", glu, "M 1, slices of >= 3 chunks, unequal", lambda c, ch: c.M == 1 and deep(ch))
+        for lo, hi in ((3, 4), (4, 5)) if glu else ((3, 4),):  # the exits after a reload: odd and even counts side by side
+            need("DEEP_SPLIT", glu, f"slices of exactly {lo} and {hi} chunks", lambda c, ch: len(ch) > 1 and set(ch) == {lo, hi})
+        for text, ok in (("N 1", lambda N: N == 1), ("1 < N < 16", lambda N: 1 < N < 16), ("48 < N < 64", lambda N: 48 < N < 64),
+                         ("N > 64", lambda N: N > 64)):
+            need("N_EDGES_SPLIT", glu, f"several slices, N % 4 != 0, {text}", lambda c, ch: len(ch) > 1 and c.N % 4 != 0 and ok(c.N))
+    for mf in (1, 2, 3, 4):
+        for split in (False, True):
+            for full in (True, False):
+                need("SWIGLU_FRAGMENTS", True, f"MF {mf}, {'several slices' if split else 'one slice'}, "
+                     f"{'both biases and the residual' if full else 'no bias, no residual'}",
+                     lambda c, ch: c.mf == mf and (len(ch) > 1) == split and [c.bias, c.bias_gate, c.res] == [full] * 3)
+    assert not missing, "\n".join(missing)
+    # the deep tables hold nothing that is not deep, and stay within the K the borrowed statistical bars already judge here
+    for c in sk.DEEP_UNSPLIT + sk.DEEP_SPLIT:
+        assert min(chunks[c]) >= 3 and c.K <= 4104, (c.what, chunks[c])
+    assert all(c.N == sk.DEEP_N and c.K <= sk.DEEP_LDW for c in sk.DEEP_UNSPLIT)
 
 
 def test_ops_queries():
