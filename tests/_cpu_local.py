@@ -46,8 +46,8 @@ def attention_step(q, k, v, *, layout="bshd", causal=False, softmax_scale=None, 
     if carry_in:
         o_new, lse_new = oracle.merge_attention_states(o_acc, lse, o_new, lse_new)
     if o_acc is not None:
-        o_acc.copy_(o_new.float())
-        lse.copy_(lse_new.float())
+        o_acc.copy_(o_new)  # rounds to the carry buffers' dtype (fp32 in the product)
+        lse.copy_(lse_new)
     res = None
     if write_out:
         res = o_new.to(q.dtype)

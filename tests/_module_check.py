@@ -37,6 +37,14 @@ exactly where the module layer stores a 16-bit tensor on that route.  The roundi
       zero; the model rounds plainly to nearest, which leaves it a little LOOSER than the kernel on streams with a mean
       (about 0.1 u at mean 0.3), never tighter;
     * everything behind the pre-activation value is the unfolded form.
+  tensor-parallel form (model(tp=): mio/parallelism/tensor_parallel.py, judged by tests/_parallel_check.py)
+    * the projections, the attention and the activation are those of the unfolded form: a rank computes its own heads /
+      intermediate columns, and what it stores are column slices of what one device stores;
+    * the out-projection / fc2 is tp partial products over the column slices of the stored context / intermediate
+      (RowParallelLinear.forward: "_local.cached_linear(self._cast, x2[a:b], self.weight, bias, "none", ..., out=out2[a:b])" --
+      one GEMM store per rank and row chunk), rank 0's carrying bias and residual ("add_here = (rank == 0)");
+    * the partials are summed in the activation dtype ("torch.distributed.all_reduce(out2[a:b], group=group, async_op=True)"
+      on the 16-bit out2): a store after each add, in rank order.  At tp = 2 the one add is order-free.
   A module whose compute dtype differs from its parameters' / input's (fp16 into a bf16 module) first rounds both to the compute
   dtype (mio/_nn.py CastCache.get, as_dtype); the model does the same, the reference reads the tensors as they are.
 
@@ -123,7 +131,8 @@ two-block chain against the reference chain):
   dtypes: the module layer's planned routes add nothing to what their rounding points cost.  The bar that comes closest is the
   mean (1.5 x the model's): the largest statistic-to-bar ratio measured is 0.68.  No family comes near a margin, so MARGINS
   stands as taken from _decode_check, none widened.  Every ResidualStream's statistics passed the fp32 summation bound.
-  Not measured: the tensor- and sequence-parallel wrappers and the paged decode path through the modules (out of scope here).
+  Not measured here: the tensor- and sequence-parallel wrappers (tests/_parallel_check.py has their table) and the paged decode
+  path through the modules.
 """
 from __future__ import annotations
 
@@ -140,6 +149,7 @@ TILE = 256                      # rows of a GEMM tile / of a block of the blocke
 SLOT = 256                      # columns per statistics slot of a ResidualStream
 LOG2E = 1.4426950408889634
 NEG_FILL = -1e9                 # keep-masked scores (ops.flash_attention)
+ADD_MASK_FLOOR = -1e30          # additive-mask entries below count as this (_attn_check.ADD_MASK_FLOOR)
 MARGINS = {"worst": 3.0, "mean": 1.5, "tile": 2.0, "seq": 2.0}   # _decode_check.MARGINS; tile and seq take its 2
 FLOOR = 0.75                                                      # _decode_check.FLOOR
 OLD_BAR = 3e-3                  # the whole-tensor bar of tests/test_gpu_modules.py (bf16 routes)
@@ -259,6 +269,34 @@ def _add_residual(z, res, defect=None):
     return z + res
 
 
+def _row_parallel(A, h, w, b, res, tp=1, defect=None):
+    """The out-projection / fc2 of the stored context / intermediate h [M, K]: (stored output, unrounded branch).  tp = 1: one
+    GEMM with bias and residual in its epilogue, one store.  tp > 1: the tensor-parallel form (module docstring): tp partial
+    products over the column slices of h, rank 0's with bias and residual, each stored, then summed in rank order with a store
+    after each add."""
+    branch = h @ w.t() + b
+    if tp == 1:
+        return A.r(_add_residual(branch, res, defect)), branch
+    M, K = h.shape
+    per = K // tp
+    parts = []
+    for r in range(tp):
+        part = h[:, r * per:(r + 1) * per] @ w[:, r * per:(r + 1) * per].t()
+        if r == 0 or defect == "tp_bias_every_rank":
+            part = part + b
+        if res is not None and (r == 0 or defect == "tp_residual_every_rank"):
+            part = part + res
+        parts.append(A.r(part))                                 # RowParallelLinear.forward: the chunk GEMM's store
+    total = parts[0]
+    for part in parts[1:]:
+        total = A.r(total + part)                               # the all-reduce in the activation dtype
+    if defect == "tp_chunk_unreduced":                          # the last of TP_DEFECT_CHUNKS row chunks never met its all-reduce
+        total = total.clone()
+        a = (TP_DEFECT_CHUNKS - 1) * M // TP_DEFECT_CHUNKS
+        total[a:] = parts[0][a:]
+    return total, branch
+
+
 def _rotate(A, t, rot, base, interleaved=False):
     """t [B, S, h, D]: the first rot elements of every head rotated at positions 0 .. S-1 (neox pairing), stored in place."""
     S = t.shape[1]
@@ -278,10 +316,11 @@ def _rotate(A, t, rot, base, interleaved=False):
     return A.r(out)
 
 
-def _attention(A, q, k, v, scale_nat, causal, keep=None, window=None, chunk=8):
+def _attention(A, q, k, v, scale_nat, causal, keep=None, window=None, chunk=8, additive=None):
     """q [B,Sq,H,D], k / v [B,Sk,Hkv,D] fp64 -> context [B,Sq,H,D] (unrounded): softmax(q k^T * scale_nat) v with GQA, the mask
     conventions of _attn_check.reference (causal-excluded keys absent, or at -1e9 next to a keep mask; keep-masked keys at -1e9;
-    keys outside a window absent); the model rounds P = exp(s - max) to the dtype and sums it as rounded."""
+    keys outside a window absent; additive [B,1|H,Sq,Sk] entries floored at -1e30); the model rounds P = exp(s - max) to the
+    dtype and sums it as rounded."""
     B, Sq, H, D = q.shape
     Sk, Hkv = k.shape[1], k.shape[2]
     qi = torch.arange(Sq, device=q.device)[:, None]
@@ -305,13 +344,16 @@ def _attention(A, q, k, v, scale_nat, causal, keep=None, window=None, chunk=8):
         if keep is not None:
             kp = keep[b0:b1].to(q.device) != 0
             s = torch.where(kp[:, None, None, :], s, torch.full_like(s, NEG_FILL))
+        if additive is not None:
+            s = s + additive[b0:b1].to(q.device, torch.float64).clamp_min(ADD_MASK_FLOOR)
         p = A.r(torch.exp(s - s.amax(dim=-1, keepdim=True)))
         out[b0:b1] = torch.einsum("bhsk,bkhd->bshd", p, vv) / p.sum(-1).permute(0, 2, 1)[..., None]
     return out
 
 
-def _sublayer(A, spec, P, x, norm=None, fold=False, residual=True, context=None, keep=None, defect=None):
-    """One sub-layer on x [B, S, d]: (out [B, S, d], branch [B, S, d]) in fp64; A decides what is rounded."""
+def _sublayer(A, spec, P, x, norm=None, fold=False, residual=True, context=None, keep=None, defect=None, tp=1):
+    """One sub-layer on x [B, S, d]: (out [B, S, d], branch [B, S, d]) in fp64; A decides what is rounded.  tp: the tensor-parallel
+    degree of the out-projection / fc2 (_row_parallel)."""
     B, S, d = x.shape
     M = B * S
     x2 = A.load(x).reshape(M, d)
@@ -334,8 +376,7 @@ def _sublayer(A, spec, P, x, norm=None, fold=False, residual=True, context=None,
             h = _act(_pre(A, x2, [lin("fc1")], n, fold, defect)[0], act)
         h = A.r(h)                                              # the intermediate is stored
         w2, b2 = lin("fc2")
-        branch = h @ w2.t() + b2
-        out = A.r(_add_residual(branch, res, defect))
+        out, branch = _row_parallel(A, h, w2, b2, res, tp, defect)
         return out.view(B, S, d), branch.view(B, S, d)
     H, Hkv, D = spec["H"], spec["Hkv"], d // spec["H"]
     kvd = Hkv * D
@@ -350,6 +391,9 @@ def _sublayer(A, spec, P, x, norm=None, fold=False, residual=True, context=None,
             z[:, d:hi] *= cs
         z = A.r(z)
         q, k, v = z[:, :d], z[:, d:d + kvd], z[:, d + kvd:]
+        if defect == "tp_k_from_rank0":                         # every rank's attention reads rank 0's K columns
+            per = kvd // tp
+            k = torch.cat([k[:, :per]] * tp, dim=1)
         Sk, Bk = S, B
     else:
         q = A.r(_pre(A, x2, [lin("q_proj")], n, fold, defect)[0])
@@ -378,24 +422,25 @@ def _sublayer(A, spec, P, x, norm=None, fold=False, residual=True, context=None,
         ctx[1, :, h0], ctx[1, :, h0 + 1] = ctx[1, :, h0 + 1].clone(), ctx[1, :, h0].clone()
     ctx = A.r(ctx).reshape(M, d)                                # the context is stored
     wo, bo = lin("out_proj" if kind == "cross" else "o_proj")
-    branch = ctx @ wo.t() + bo
-    out = A.r(_add_residual(branch, res, defect))
+    out, branch = _row_parallel(A, ctx, wo, bo, res, tp, defect)
     return out.view(B, S, d), branch.view(B, S, d)
 
 
-def reference(spec, P, x, *, norm=None, residual=True, context=None, keep=None, device=None, parts=False):
+def reference(spec, P, x, *, norm=None, residual=True, context=None, keep=None, device=None, parts=False, tp=1):
     """fp64 [B, S, d] of one sub-layer (module docstring), nothing rounded; parts: (out, branch) -- the branch is what the
     sub-layer adds to its residual."""
-    out, branch = _sublayer(_Arith(None, device), spec, P, x, norm, False, residual, context, keep)
+    out, branch = _sublayer(_Arith(None, device), spec, P, x, norm, False, residual, context, keep, None, tp)
     return (out, branch) if parts else out
 
 
-def model(spec, P, x, *, dtype, norm=None, fold=False, residual=True, context=None, keep=None, device=None, defect=None):
+def model(spec, P, x, *, dtype, norm=None, fold=False, residual=True, context=None, keep=None, device=None, defect=None,
+          tp: int = 1):
     """The rounding model of one sub-layer at compute dtype `dtype`: fp64 values on the 16-bit grid, [B, S, d].  fold: the
-    folded form (the input is a ResidualStream).  defect: one of DEFECTS, planted."""
-    if defect is not None and defect not in DEFECTS:
+    folded form (the input is a ResidualStream).  defect: one of DEFECTS (or, with tp > 1, of TP_DEFECTS), planted.  tp: the
+    sub-layer as TensorParallelAttention / TensorParallelMLP run it over tp ranks (module docstring)."""
+    if defect is not None and defect not in DEFECTS and not (tp > 1 and defect in TP_DEFECTS):
         raise ValueError(defect)
-    return _sublayer(_Arith(dtype, device), spec, P, x, norm, fold, residual, context, keep, defect)[0]
+    return _sublayer(_Arith(dtype, device), spec, P, x, norm, fold, residual, context, keep, defect, tp)[0]
 
 
 # ---- judging -------------------------------------------------------------------------------------------------------------------
@@ -562,6 +607,16 @@ DEFECTS = {
     "gate_up_swap": "gate and up are swapped in one 128-column group",
     "head_shift": "one head's context lands in the neighbouring head's columns for one sequence",
     "stale_gamma": "a folded weight is built from a stale gamma",
+}
+
+
+# the faults tests/test_parallel_check.py plants into model(tp=2)
+TP_DEFECT_CHUNKS = 3            # RowParallelLinear's row chunks in the tp_chunk_unreduced fault (overlap_chunks = 3)
+TP_DEFECTS = {
+    "tp_bias_every_rank": "every rank adds the out-projection / fc2 bias to its partial",
+    "tp_residual_every_rank": "every rank adds the residual to its partial",
+    "tp_chunk_unreduced": "the last RowParallelLinear row chunk holds rank 0's partial only",
+    "tp_k_from_rank0": "rank 1's attention reads rank 0's K columns of the fused projection",
 }
 
 
