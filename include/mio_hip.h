@@ -349,6 +349,41 @@ int mio_gemm_skinny_ok(int64_t M, int32_t N, int32_t K, int32_t act);
 int mio_gemm_skinny(const void* x, const void* w, const void* bias, const void* w_gate, const void* bias_gate,
                     const void* residual, void* y, void* workspace, int64_t M, int32_t N, int32_t K, int64_t ldx,
                     int64_t ldw, int64_t ldy, int64_t ldr, int32_t act, int32_t dtype, void* stream);
+
+/* The decode-step GEMM on weight-only FP8: mio_gemm_skinny with the weight stored as OCP e4m3fn bytes (torch.float8_e4m3fn,
+ * row-major [N, K], ldw in bytes) and one fp32 scale per output column (csrc/gemm_skinny_w8.hip):
+ *   y = act(w_scale[n] * (x w8^T) + bias[n]) (+ residual)
+ *   SwiGLU: silu(w_scale_gate[n] * (x w8_gate^T) + bias_gate[n]) * (w_scale[n] * (x w8^T) + bias[n])
+ * It replaces the same F.linear sites of the reference as mio_gemm_skinny (kernels/attention/flash_attention.py:629-631,654-657;
+ * kernels/mlp/fused_mlp.py:159,176).  The reference has no quantised weights: this storage form, the kernel and the quantiser
+ * below have no counterpart there.  FP8 is how the weights are stored, not a compute precision: the bytes are widened exactly
+ * in registers and multiplied on the 16-bit MFMA, x / bias / residual / y stay bf16 or fp16 (dtype), and the result is the
+ * 16-bit kernel's on the dequantised weight plus one fp32 fma per output.
+ *   1 <= M <= 64, any N >= 1, K % 16 == 0, ldw % 16 == 0 (bytes) and >= K, ldx / ldy / ldr multiples of 8 elements, every
+ *   pointer 16-byte aligned; bias / residual nullable; w8_gate and w_scale_gate together iff act == SWIGLU; scales any finite
+ *   fp32 (a zero scale gives act(bias)).  M == 0 or N == 0 returns 0 and launches nothing; K == 0 is an empty sum.
+ * K is cut into mio_gemm_skinny_w8_splits() slices of whole 64-k steps (mio_gemm_skinny_w8_slice), partials and workspace as
+ * mio_gemm_skinny (mio_gemm_skinny_w8_workspace_bytes); bit-reproducible, graph-capturable.  Inside a slice a workgroup walks
+ * chunks of mio_gemm_skinny_w8_chunk_k(act) k with a ring of mio_gemm_skinny_w8_depth(act) register sets, depth - 1 chunks of
+ * weight loads in flight: both are tuning values the tests ask for (< 0 on an unknown activation).
+ * mio_gemm_skinny_w8_ok only advises the module layer: 1 where the shape is legal AND the kernel measured at most 0.9 x the
+ * time of the faster of mio_gemm_skinny and mio_gemm_bias_act on the 16-bit weight (profiles/skinny_gemm_w8.md).
+ * mio_weight_quant_w8 is the one-time preparation, per row n of a 16-bit weight w [N, K] (ldw in elements, K % 16 == 0):
+ *   a = max |w[n, :]| in fp32 (NaN elements ignored), scale[n] = a / 448 (1.0 where a == 0),
+ *   w8[n, k] = e4m3(clamp(float(w[n, k]) * (1.0f / scale[n]), -448, 448)), round to nearest even; a NaN element -> sign | 0x7f
+ * (the formula and NaN rule of mio_reshape_and_cache_kv8).  ldw8 in bytes, a multiple of 16. */
+int mio_weight_quant_w8(const void* w, int64_t ldw, void* w8, int64_t ldw8, float* scale, int32_t N, int32_t K, int32_t dtype,
+                        void* stream);
+size_t mio_gemm_skinny_w8_workspace_bytes(int64_t M, int32_t N, int32_t K, int32_t act);
+int mio_gemm_skinny_w8_splits(int64_t M, int32_t N, int32_t K, int32_t act);
+int mio_gemm_skinny_w8_slice(int64_t M, int32_t N, int32_t K, int32_t act, int32_t slice, int32_t* k_begin, int32_t* k_end);
+int mio_gemm_skinny_w8_chunk_k(int32_t act);
+int mio_gemm_skinny_w8_depth(int32_t act);
+int mio_gemm_skinny_w8_ok(int64_t M, int32_t N, int32_t K, int32_t act);
+int mio_gemm_skinny_w8(const void* x, const void* w8, const float* w_scale, const void* bias, const void* w8_gate,
+                       const float* w_scale_gate, const void* bias_gate, const void* residual, void* y, void* workspace,
+                       int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
+                       int32_t dtype, void* stream);
 /* x_blocked != 0: the activation operand x is in the same blocked layout (m in the place of n; ceil(M/256)*256 x K
  * elements, ldx ignored) -- what mio_layernorm_fwd_bx writes, so that LayerNorm -> GEMM hands over contiguous K-tiles. */
 int mio_layernorm_fwd_bx(const void* x, const void* residual, const void* weight, const void* bias, void* yb,

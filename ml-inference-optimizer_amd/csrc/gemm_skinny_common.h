@@ -1,0 +1,133 @@
+// What the two decode-step GEMM units share (gemm_skinny.hip: 16-bit weights; gemm_skinny_w8.hip: e4m3fn weights with one fp32
+// scale per output column): the launch's device arguments, the one epilogue and the split-K reduction.  SCALED is the only
+// difference between the units behind the accumulator: z = fma(acc, scale[n], bias[n]) in place of z = acc + bias[n].  With the
+// flag off nothing of the scales is read and the arithmetic is that of the 16-bit kernel alone.
+#pragma once
+#include "gemm_kernel.h"
+
+struct SkinnyDev {
+  const void* x;
+  const void* w;
+  const void* wg;
+  const void* bias;
+  const void* bias_g;
+  const void* res;
+  void* y;
+  float* ws;  // [nsplit][M][N] fp32 (SwiGLU: then the gate half); nullptr with one slice
+  int64_t ldx, ldw, ldy, ldr;
+  int M, N, K, act, nsplit, steps;
+  const float* scale;    // SCALED only: fp32 [N], the weight's per-column scale
+  const float* scale_g;  // SCALED and SwiGLU only: the gate weight's
+};
+
+__device__ __forceinline__ float skinny_act(int act, float v) {
+  switch (act) {
+    case MIO_ACT_GELU_TANH: return gemm_act<MIO_ACT_GELU_TANH>(v);
+    case MIO_ACT_GELU_ERF: return gemm_act<MIO_ACT_GELU_ERF>(v);
+    case MIO_ACT_RELU: return gemm_act<MIO_ACT_RELU>(v);
+    case MIO_ACT_SILU: return gemm_act<MIO_ACT_SILU>(v);
+    default: return v;
+  }
+}
+
+// the pre-activation value of one column from its fp32 sum: the bias add, behind the column's scale where the weight has one
+template <bool SCALED>
+__device__ __forceinline__ float skinny_pre(float acc, const float* scale, float b, int nn) {
+  if constexpr (SCALED) return __builtin_fmaf(acc, scale[nn], b);
+  else return acc + b;
+}
+
+// The one epilogue, of both kernels: row m, columns n .. n + 3 (those below N), from the fp32 sums v (and g, the gate's).
+template <typename T, bool GLU, bool SCALED = false>
+__device__ __forceinline__ void skinny_finish(const SkinnyDev& p, int m, int n, const float (&v)[4], const float (&g)[4]) {
+  const T* bias = (const T*)p.bias;
+  const T* bias_g = (const T*)p.bias_g;
+  const T* rrow = p.res ? (const T*)p.res + (int64_t)m * p.ldr : nullptr;
+  T* yrow = (T*)p.y + (int64_t)m * p.ldy;
+  float o[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int nn = n + i < p.N ? n + i : p.N - 1;  // (clamped: computed, not stored)
+    float z = skinny_pre<SCALED>(v[i], p.scale, bias ? (float)bias[nn] : 0.f, nn);
+    if constexpr (GLU) z = gemm_act<MIO_ACT_SILU>(skinny_pre<SCALED>(g[i], p.scale_g, bias_g ? (float)bias_g[nn] : 0.f, nn)) * z;
+    else z = skinny_act(p.act, z);
+    if (rrow) z += (float)rrow[nn];
+    o[i] = z;
+  }
+  if (n + 3 < p.N) {
+    *(u32x2_t*)(yrow + n) = (u32x2_t){pack2<T>(o[0], o[1]), pack2<T>(o[2], o[3])};
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (n + i < p.N) yrow[n + i] = (T)o[i];
+  }
+}
+
+// A lane's share of a workgroup's result, lane (c, q) of the wave at columns n0: rows 16 mf + c, columns n0 + 4 q .. + 3, through
+// the epilogue (one slice) or into the fp32 partials of slice s.
+template <typename T, int MF, bool GLU, bool SCALED>
+__device__ __forceinline__ void skinny_write(const SkinnyDev& p, int s, int c, int n, const f32x4_t (&acc)[MF],
+                                             const f32x4_t (&accg)[GLU ? MF : 1]) {
+#pragma unroll
+  for (int mf = 0; mf < MF; ++mf) {
+    const int m = mf * 16 + c;
+    if (m >= p.M) continue;
+    if (p.ws == nullptr) {
+      const float v[4] = {acc[mf][0], acc[mf][1], acc[mf][2], acc[mf][3]};
+      float g[4] = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (GLU) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] = accg[mf][i];
+      }
+      skinny_finish<T, GLU, SCALED>(p, m, n, v, g);
+    } else {
+      const int64_t plane = (int64_t)p.M * p.N;
+      float* dst = p.ws + (int64_t)s * plane + (int64_t)m * p.N + n;
+      if ((p.N & 3) == 0) {  // (n + 3 < N then, and the partial rows are 16-byte aligned)
+        *(f32x4_t*)dst = acc[mf];
+        if constexpr (GLU) *(f32x4_t*)(dst + (int64_t)p.nsplit * plane) = accg[mf];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (n + i < p.N) {
+            dst[i] = acc[mf][i];
+            if constexpr (GLU) dst[(int64_t)p.nsplit * plane + i] = accg[mf][i];
+          }
+      }
+    }
+  }
+}
+
+// The second launch: one thread per (row, 4 columns) sums the slices' partials in index order and runs the epilogue.
+template <typename T, bool GLU, bool SCALED = false>
+__global__ __launch_bounds__(256) void gemm_skinny_reduce_kernel(const SkinnyDev p) {
+  const int ngrp = (p.N + 3) / 4;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)p.M * ngrp) return;
+  const int m = (int)(idx / ngrp), n = (int)(idx % ngrp) * 4;
+  const int64_t plane = (int64_t)p.M * p.N;
+  const float* src = p.ws + (int64_t)m * p.N + n;
+  const float* srcg = src + (int64_t)p.nsplit * plane;
+  float v[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
+  if ((p.N & 3) == 0) {
+    for (int s = 0; s < p.nsplit; ++s) {
+      const f32x4_t t = *(const f32x4_t*)(src + s * plane);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] += t[i];
+      if constexpr (GLU) {
+        const f32x4_t u = *(const f32x4_t*)(srcg + s * plane);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] += u[i];
+      }
+    }
+  } else {
+    for (int s = 0; s < p.nsplit; ++s)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (n + i < p.N) {
+          v[i] += src[s * plane + i];
+          if constexpr (GLU) g[i] += srcg[s * plane + i];
+        }
+  }
+  skinny_finish<T, GLU, SCALED>(p, m, n, v, g);
+}

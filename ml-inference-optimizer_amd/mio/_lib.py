@@ -111,6 +111,14 @@ EXPORTS = (
     "mio_gemm_skinny_chunk_k",
     "mio_gemm_skinny_ok",
     "mio_gemm_skinny",
+    "mio_weight_quant_w8",
+    "mio_gemm_skinny_w8_workspace_bytes",
+    "mio_gemm_skinny_w8_splits",
+    "mio_gemm_skinny_w8_slice",
+    "mio_gemm_skinny_w8_chunk_k",
+    "mio_gemm_skinny_w8_depth",
+    "mio_gemm_skinny_w8_ok",
+    "mio_gemm_skinny_w8",
     "mio_layernorm_fwd_bx",
     "mio_ln_stats_bytes",
     "mio_gemm_ln_ok",
@@ -286,6 +294,21 @@ def _load() -> C.CDLL:
     lib.mio_gemm_skinny_ok.restype = i32
     lib.mio_gemm_skinny.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
     lib.mio_gemm_skinny.restype = i32
+    lib.mio_weight_quant_w8.argtypes = [vp, i64, vp, i64, vp, i32, i32, i32, vp]
+    lib.mio_weight_quant_w8.restype = i32
+    lib.mio_gemm_skinny_w8_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.mio_gemm_skinny_w8_workspace_bytes.restype = C.c_size_t
+    lib.mio_gemm_skinny_w8_splits.argtypes = [i64, i32, i32, i32]
+    lib.mio_gemm_skinny_w8_splits.restype = i32
+    lib.mio_gemm_skinny_w8_slice.argtypes = [i64, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+    lib.mio_gemm_skinny_w8_slice.restype = i32
+    for name in ("mio_gemm_skinny_w8_chunk_k", "mio_gemm_skinny_w8_depth"):
+        getattr(lib, name).argtypes = [i32]
+        getattr(lib, name).restype = i32
+    lib.mio_gemm_skinny_w8_ok.argtypes = [i64, i32, i32, i32]
+    lib.mio_gemm_skinny_w8_ok.restype = i32
+    lib.mio_gemm_skinny_w8.argtypes = [vp] * 10 + [i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
+    lib.mio_gemm_skinny_w8.restype = i32
     lib.mio_fused_mlp_workspace_bytes.argtypes = [i64, i32, i32, i32]
     lib.mio_fused_mlp_workspace_bytes.restype = C.c_size_t
     lib.mio_fused_mlp_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]

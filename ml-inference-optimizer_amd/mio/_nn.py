@@ -85,6 +85,12 @@ class CastCache:
         return self._memo(("b", id(p)), (p.data_ptr(), p._version, dtype, p.device, "blocked"),
                           lambda: ops.block_weight(self.get(p, dtype)))
 
+    def get_w8(self, p: torch.Tensor, dtype: torch.dtype) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The parameter as weight-only FP8 (ops.quantize_weight_w8 of its copy in dtype): (w8 [N, K] float8_e4m3fn, scale [N]
+        fp32), quantised again when its version changes."""
+        return self._memo(("w8", id(p)), (p.data_ptr(), p._version, dtype, p.device, "w8"),
+                          lambda: ops.quantize_weight_w8(self.get(p, dtype)))
+
     def get_cat(self, ps: Tuple[Optional[torch.Tensor], ...], dtype: torch.dtype, blocked: bool = False) -> Optional[torch.Tensor]:
         """The row-concatenation of the parameters ps in dtype (None where they are: biases that are not there), or with blocked
         that weight in the blocked layout; made again when one of them changes."""
@@ -165,14 +171,20 @@ class ResidualStream:
 
 
 def linear(x: torch.Tensor, lin: nn.Linear, cache: CastCache, dtype: torch.dtype, activation: str = "none",
-           residual: Optional[torch.Tensor] = None, col_scale=None, x_blocked_shape=None, skinny: bool = False) -> torch.Tensor:
+           residual: Optional[torch.Tensor] = None, col_scale=None, x_blocked_shape=None, skinny: bool = False,
+           skinny_w8: bool = False) -> torch.Tensor:
     """F.linear(x, W, b) (+ activation, + residual) on the MFMA GEMM.  At sizes that run the 256x256-tile kernels the
     weight is handed over in the blocked layout (repacked once per parameter version, cached next to the cast copy).
     skinny (the modules' decode_gemm option): a row-major x without a column scale goes to the decode-step GEMM
-    (ops.gemm_skinny, the same row-major weight copy) where ops.gemm_skinny_ok advises it."""
+    (ops.gemm_skinny, the same row-major weight copy) where ops.gemm_skinny_ok advises it.
+    skinny_w8 (the modules' decode_gemm_fp8 option): the same calls go to the decode-step GEMM on the weight's FP8 copy
+    (ops.gemm_skinny_w8, CastCache.get_w8) where ops.gemm_skinny_w8_ok advises it, and fall through to the above where not."""
     w = cache.get(lin.weight, dtype)
     N, K = w.shape
     M = x.numel() // K if x_blocked_shape is None else int(math.prod(x_blocked_shape[:-1]))
+    if skinny_w8 and x_blocked_shape is None and col_scale is None and ops.gemm_skinny_w8_ok(M, N, K, activation):
+        w8, scale = cache.get_w8(lin.weight, dtype)
+        return ops.gemm_skinny_w8(x, w8, scale, cache.get(lin.bias, dtype), activation, residual=residual)
     if skinny and x_blocked_shape is None and col_scale is None and ops.gemm_skinny_ok(M, N, K, activation):
         return ops.gemm_skinny(x, w, cache.get(lin.bias, dtype), activation, residual=residual)
     wb = cache.get_blocked(lin.weight, dtype) if (K % 32 == 0 and ops.blocked_weight_ok(M, N, K, activation)) else None

@@ -49,6 +49,10 @@ class FlashAttentionConfig:
     # decode steps (the paged branch, "block_tables" in kwargs): the q / qkv projection and o_proj run on the decode-step GEMM
     # (ops.gemm_skinny) where ops.gemm_skinny_ok advises it; off: every call as before
     decode_gemm: bool = False
+    # the same calls on weight-only FP8 copies of the weights (e4m3fn bytes, one fp32 scale per output channel, quantised once
+    # per parameter version; ops.gemm_skinny_w8) where ops.gemm_skinny_w8_ok advises it; a call it does not advise runs as
+    # decode_gemm says.  Activations, the output and every other call stay 16-bit: a storage form, not precision="fp8".
+    decode_gemm_fp8: bool = False
 
     @property
     def allowed_precisions(self) -> Set[str]:
@@ -193,7 +197,7 @@ class _AttentionBase(nn.Module):
         ops.paged_attention_forward(q, out.permute(0, 2, 1, 3), k_cache, v_cache, bt, cl, bs, max_seq_len, layer_idx,
                                     **_decode_window_kw(self.config), **scales)
         return linear(out.view(B, q_len, self.hidden_size), self.o_proj, self._cast, dt, residual=residual,
-                      skinny=self.config.decode_gemm)
+                      skinny=self.config.decode_gemm, skinny_w8=self.config.decode_gemm_fp8)
 
     def _plan(self, B, S, k_proj, k_cols, kv_stride, o_proj, mask: bool):
         """mio._nn.attention_plan of a dense self-attention call of this module (Sq = Sk = S) under its config."""
@@ -249,7 +253,7 @@ class FlashAttentionLayer(_AttentionBase):
         dt = compute_dtype(self.config.precision, hidden_states)
         x, r, c = as_dtype(hidden_states, dt), as_dtype(residual, dt), self._cast
         if "block_tables" in kwargs:
-            q2d = linear(x, self.q_proj, c, dt, skinny=self.config.decode_gemm)
+            q2d = linear(x, self.q_proj, c, dt, skinny=self.config.decode_gemm, skinny_w8=self.config.decode_gemm_fp8)
             return as_dtype(self._paged(q2d, B, S, dt, kwargs, "FlashAttentionLayer", r), in_dtype)
         _refuse(self.config, self.training)
         # K is the whole output of k_proj; q / k / v are tensors of their own and the context stays row-major (no o_proj shape)
@@ -330,8 +334,13 @@ class FlashSelfAttention(_AttentionBase):
             # only the query slice of the fused projection is needed on the paged path (:572-621)
             wq = c.get(self.qkv_proj.weight, dt)[:q_dim]
             bq = c.get(self.qkv_proj.bias, dt)
-            gemm = ops.gemm_skinny if cfg.decode_gemm and ops.gemm_skinny_ok(B * S, q_dim, wq.shape[1]) else ops.gemm_bias_act
-            q2d = gemm(x, wq, None if bq is None else bq[:q_dim].contiguous())
+            bq = None if bq is None else bq[:q_dim].contiguous()
+            if cfg.decode_gemm_fp8 and ops.gemm_skinny_w8_ok(B * S, q_dim, wq.shape[1]):
+                w8, scale = c.get_w8(self.qkv_proj.weight, dt)  # (the whole projection is quantised once; rows are independent)
+                q2d = ops.gemm_skinny_w8(x, w8[:q_dim], scale[:q_dim], bq)
+            else:
+                gemm = ops.gemm_skinny if cfg.decode_gemm and ops.gemm_skinny_ok(B * S, q_dim, wq.shape[1]) else ops.gemm_bias_act
+                q2d = gemm(x, wq, bq)
             return as_dtype(self._paged(q2d, B, S, dt, kwargs, "FlashSelfAttention", r), in_dtype)
         _refuse(cfg, self.training)
         # [B,S,q_dim+2*kv_dim]; q / k / v are strided views of it, K its columns [q_dim, q_dim + kv_dim)

@@ -35,6 +35,9 @@ class FusedMLPConfig:
     # decode steps (at most 64 rows, plain-tensor input): fc1 and fc2 run as two decode-step GEMMs (ops.gemm_skinny) where
     # ops.gemm_skinny_ok advises both; off: every call as before
     decode_gemm: bool = False
+    # the same two GEMMs on weight-only FP8 copies of the weights (e4m3fn bytes, one fp32 scale per output channel, quantised
+    # once per parameter version; ops.gemm_skinny_w8) where ops.gemm_skinny_w8_ok advises both; else as decode_gemm says
+    decode_gemm_fp8: bool = False
 
 
 class FusedMLP(nn.Module):
@@ -60,6 +63,10 @@ class FusedMLP(nn.Module):
         raise ValueError(f"Unsupported activation function: {act}")
 
     def _gate(self, dtype):
+        return None, None
+
+    def _gate_w8(self, dtype):
+        """The gate weight as weight-only FP8, (w8, scale) (CastCache.get_w8); none without a gate."""
         return None, None
 
     def stream_ok(self, B: int, S: int, dtype: torch.dtype, pre_norm: Optional[nn.Module]) -> bool:
@@ -109,6 +116,15 @@ class FusedMLP(nn.Module):
         x, r, c = as_dtype(hidden_states, dt), as_dtype(residual, dt), self._cast
         gw, gb = self._gate(dt)
         M, d, I = x.numel() // x.shape[-1], x.shape[-1], self.fc1.weight.shape[0]
+        if (self.config.decode_gemm_fp8 and ops.gemm_skinny_w8_ok(M, I, d, act)
+                and ops.gemm_skinny_w8_ok(M, self.fc2.weight.shape[0], I)):
+            if pre_norm is not None:
+                x = apply_norm(x, pre_norm, c, dt)
+            (w1, s1), (w2, s2) = c.get_w8(self.fc1.weight, dt), c.get_w8(self.fc2.weight, dt)
+            g8, gs = self._gate_w8(dt)
+            h = ops.gemm_skinny_w8(x, w1, s1, c.get(self.fc1.bias, dt), act, g8, gs, gb)
+            out = ops.gemm_skinny_w8(h, w2, s2, c.get(self.fc2.bias, dt), residual=r)
+            return as_dtype(out, in_dtype)
         if self.config.decode_gemm and ops.gemm_skinny_ok(M, I, d, act) and ops.gemm_skinny_ok(M, self.fc2.weight.shape[0], I):
             if pre_norm is not None:
                 x = apply_norm(x, pre_norm, c, dt)
@@ -159,6 +175,9 @@ class FusedMLPSwiGLU(FusedMLP):
 
     def _gate(self, dtype):
         return self._cast.get(self.fc1_gate.weight, dtype), self._cast.get(self.fc1_gate.bias, dtype)
+
+    def _gate_w8(self, dtype):
+        return self._cast.get_w8(self.fc1_gate.weight, dtype)
 
 
 class FusedMLPReLU(FusedMLP):

@@ -760,6 +760,121 @@ def gemm_skinny(x, w, bias=None, activation: str = "none", w_gate=None, bias_gat
     return out
 
 
+# ---- the decode-step GEMM on weight-only FP8 (mio_gemm_skinny_w8: e4m3fn weight bytes, one fp32 scale per output column) ---------
+_W8 = torch.float8_e4m3fn
+
+
+def gemm_skinny_w8_ok(M: int, N: int, K: int, activation: str = "none") -> bool:
+    """True iff gemm_skinny_w8 is legal at this shape AND measured at most 0.9 x the time of the faster of gemm_skinny and
+    gemm_bias_act on the 16-bit weight (profiles/skinny_gemm_w8.md).  Advice for the module layer: gemm_skinny_w8 itself runs
+    every legal shape."""
+    return activation in _ACT and bool(lib.mio_gemm_skinny_w8_ok(M, N, K, _ACT[activation]))
+
+
+def gemm_skinny_w8_splits(M: int, N: int, K: int, activation: str = "none") -> int:
+    """The slices of K a gemm_skinny_w8 call of this shape runs (1: one launch, no workspace).  Host-only; ValueError where the
+    call would be refused."""
+    if activation not in _ACT:
+        raise ValueError(f"Unsupported activation function: {activation}")
+    n = lib.mio_gemm_skinny_w8_splits(M, N, K, _ACT[activation])
+    if n < 0:
+        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def quantize_weight_w8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One-time preparation of a bf16 / fp16 weight [N, K] (K % 16 == 0) for gemm_skinny_w8: (w8 [N, K] torch.float8_e4m3fn,
+    scale [N] fp32) with scale[n] = max |w[n, :]| / 448 (1.0 for an all-zero row, NaN elements ignored) and
+    w8 = e4m3(clamp(w * (1 / scale), -448, 448)), so that w8 * scale[:, None] is w to within the format's rounding."""
+    _need_cuda(w)
+    dt = _dtype_id(w)
+    if w.dim() != 2:
+        raise ValueError(f"quantize_weight_w8 takes a 2-D weight [N, K], got shape {tuple(w.shape)}")
+    N, K = w.shape
+    if K % 16 != 0:
+        raise ValueError(f"quantize_weight_w8: K must be a multiple of 16, got {K}")
+    w2 = _rows16(w)
+    w8 = torch.empty(N, K, dtype=_W8, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    check(lib.mio_weight_quant_w8(w2.data_ptr(), w2.stride(0), w8.data_ptr(), K, scale.data_ptr(), N, K, dt, _stream()))
+    return w8, scale
+
+
+def _w8_ok(t: torch.Tensor, what: str) -> torch.Tensor:
+    """An fp8 weight operand: 2-D torch.float8_e4m3fn on the device (not e5m2, e4m3fnuz or an integer type); returned with unit
+    column stride and rows a multiple of 16 bytes apart at a 16-byte aligned address (a row slice stays a view)."""
+    if t.dtype != _W8:
+        raise ValueError(f"{what} must be torch.float8_e4m3fn (OCP e4m3), got {t.dtype}")
+    _need_cuda(t)
+    if t.dim() != 2:
+        raise ValueError(f"{what} must be a 2-D weight [N, K], got shape {tuple(t.shape)}")
+    if t.stride(1) != 1 or t.stride(0) % 16 or t.data_ptr() % 16:
+        return t.contiguous()
+    return t
+
+
+def _w8_scale(s: torch.Tensor, N: int, what: str) -> torch.Tensor:
+    """The fp32 scales of an fp8 weight as [N]: one per output column, or a one-element tensor (a per-tensor scale) expanded."""
+    if s is None or s.dtype != torch.float32:
+        raise ValueError(f"{what} must be an fp32 tensor (the scales of a torch.float8_e4m3fn weight), got "
+                         f"{None if s is None else s.dtype}")
+    _need_cuda(s)
+    if s.numel() == 1 and N != 1:
+        return s.reshape(1).expand(N).contiguous()
+    if s.dim() != 1 or s.numel() != N:
+        raise ValueError(f"{what} must have {N} elements (one per output column) or one, got shape {tuple(s.shape)}")
+    return s if s.is_contiguous() and s.data_ptr() % 16 == 0 else s.clone(memory_format=torch.contiguous_format)
+
+
+def gemm_skinny_w8(x, w8, w_scale, bias=None, activation: str = "none", w8_gate=None, w_scale_gate=None, bias_gate=None,
+                   residual=None, out=None):
+    """gemm_skinny on a weight-only FP8 weight (x [..., K] bf16 / fp16 with prod(...) <= 64; w8 [N, K] torch.float8_e4m3fn,
+    K % 16 == 0; w_scale fp32 [N] or one element): y = act(w_scale * (x @ w8^T) + bias) (+ residual), SwiGLU with w8_gate /
+    w_scale_gate / bias_gate.  Row slices of w8 and w_scale are legal operands.  Allocates the split workspace only when the plan
+    splits K."""
+    _need_cuda(x)
+    if activation not in _ACT:
+        raise ValueError(f"Unsupported activation function: {activation}")
+    act = _ACT[activation]
+    dt = _dtype_id(x)
+    w2 = _w8_ok(w8, "w8")
+    if w2.shape[1] != x.shape[-1]:
+        raise ValueError(f"weight shape {tuple(w2.shape)} does not match input features {x.shape[-1]}")
+    N, K = w2.shape
+    if K % 16 != 0:
+        raise ValueError(f"gemm_skinny_w8: K must be a multiple of 16, got {K}")
+    s2 = _w8_scale(w_scale, N, "w_scale")
+    _vec_ok(bias, N, x.dtype, "bias")
+    g2 = sg2 = None
+    if act == _lib.ACT_SWIGLU:
+        _vec_ok(bias_gate, N, x.dtype, "bias_gate")
+        if w8_gate is None or w_scale_gate is None:
+            raise ValueError("SwiGLU activation requires gate weights and their scales")
+        g2 = _w8_ok(w8_gate, "w8_gate")
+        if g2.shape != w2.shape:
+            raise ValueError("w8_gate must have w8's shape")
+        sg2 = _w8_scale(w_scale_gate, N, "w_scale_gate")
+        if g2.stride(0) != w2.stride(0):
+            g2, w2 = g2.contiguous(), w2.contiguous()
+    else:
+        bias_gate = None
+    lead, x2 = tuple(x.shape[:-1]), _rows16(x.reshape(-1, K))
+    M = x2.shape[0]
+    if M > 64:
+        raise ValueError(f"gemm_skinny_w8 takes at most 64 rows, got {M} (fp8 weights are read by the decode-step kernel only)")
+    _res_ok(residual, M * N, x.dtype)
+    r2 = None if residual is None else _rows16(residual.reshape(-1, N))
+    if out is None:  # (rows of N % 8 != 0 columns: a view of rows padded to the stride the kernel's 8-byte stores need)
+        out = torch.empty(*lead, (N + 7) // 8 * 8, dtype=x.dtype, device=x.device)[..., :N]
+    y2 = out.view(-1, N)
+    nbytes = lib.mio_gemm_skinny_w8_workspace_bytes(M, N, K, act)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    check(lib.mio_gemm_skinny_w8(x2.data_ptr(), w2.data_ptr(), s2.data_ptr(), _ptr(bias), _ptr(g2), _ptr(sg2), _ptr(bias_gate),
+                                 _ptr(r2), y2.data_ptr(), _ptr(ws), M, N, K, x2.stride(0), w2.stride(0), y2.stride(0),
+                                 0 if r2 is None else r2.stride(0), act, dt, _stream()))
+    return out
+
+
 # ---- LayerNorm folded into the GEMMs on either side of it (mio_gemm_ln_bw; reference fused_layernorm_qkv.py:37-420) ------------
 def gemm_ln_ok(M: int, N: int, K: int, activation: str = "none", fold_in: bool = False, stats_out: bool = False) -> bool:
     """True iff gemm_ln(...) runs this shape: fold_in = the projection behind a LayerNorm (ln_stats given),
