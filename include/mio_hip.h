@@ -651,6 +651,56 @@ int mio_rope_rows(const void* x, void* out, const int32_t* positions, const floa
                   int32_t tokens, int32_t heads, int32_t D, int32_t rot_dim, int32_t max_position,
                   int32_t interleaved, int32_t dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * QK-norm (csrc/qknorm_rope.hip): the per-head RMSNorm of q and k (Qwen3, Gemma 3) in front of the
+ * rotation above, in one pass.  A head row x[0 .. D) becomes n[d] = x[d] * r * w[d] with
+ * r = rsqrt(mean_{d < D}(x[d]^2) + eps) -- the mean over the whole head_dim, not over rot_dim -- in
+ * fp32, in mio_rmsnorm_fwd's order; the first rot_dim elements of n are rotated exactly as the
+ * rotary entry points rotate, the others are n itself, and the result is rounded ONCE into the
+ * stored format (16 bits; e4m3(clamp(y * (1.0f / k_scale), -448, 448)) for K into an fp8 cache):
+ * nothing is rounded between the norm and the rotation.  w is a DEVICE array [D] of the rows'
+ * dtype, 16-byte aligned, shared by all heads of its kind (q_weight for the query heads, k_weight
+ * for the key heads).  Gemma's (1 + w) form is the caller's: pass 1 + w.  A zero row gives zeros
+ * (eps > 0), a NaN in a head makes that head NaN; there is no other special case.
+ *
+ * mio_qknorm_rope_and_cache_varlen(_kv8): mio_rope_and_cache_varlen(_kv8) with the norm: the same
+ * arguments, token placement, liveness and skipping rules (a dead token writes nothing to the
+ * caches and gets a zero q_out row; a token whose cache row is skipped still gets its q), with
+ * q_weight / k_weight after sin and eps after dtype.  V is not normalised: its bytes are those of
+ * mio_reshape_and_cache_varlen(_kv8).
+ * mio_qknorm_rope_rows: mio_rope_rows with the norm (weight after sin, eps after dtype); out may be x.
+ * The fused write's q_out is bit-equal to mio_qknorm_rope_rows of the same q: one device function
+ * computes both.
+ * Refused before any launch, next to every refusal of the rotary entry points (D, rot_dim and the
+ * rest as above): eps negative or not finite, and -- where there is work -- a null norm weight or
+ * one off 16-byte alignment.
+ * ------------------------------------------------------------------------------------------ */
+int mio_qknorm_rope_and_cache_varlen(const void* q, void* q_out, const void* key, const void* value, void* k_cache,
+                                     void* v_cache, const int32_t* block_tables, const int32_t* cu_seqlens_new,
+                                     const int32_t* context_lengths, const int32_t* positions, const float* cos,
+                                     const float* sin, const void* q_weight, const void* k_weight,
+                                     const int64_t q_stride[2], const int64_t q_out_stride[2],
+                                     const int64_t k_stride[2], const int64_t v_stride[2], /* token, head */
+                                     int32_t B, int32_t total_new, int32_t H, int32_t Hkv, int32_t D, int32_t rot_dim,
+                                     int32_t max_position, int32_t interleaved, int32_t num_blocks, int32_t num_layers,
+                                     int32_t layer_idx, int32_t block_size, int32_t max_blocks_per_seq, int32_t dtype,
+                                     float eps, void* stream);
+int mio_qknorm_rope_and_cache_varlen_kv8(const void* q, void* q_out, const void* key, const void* value, void* k_cache,
+                                         void* v_cache, const float* k_scale, const float* v_scale,
+                                         const int32_t* block_tables, const int32_t* cu_seqlens_new,
+                                         const int32_t* context_lengths, const int32_t* positions, const float* cos,
+                                         const float* sin, const void* q_weight, const void* k_weight,
+                                         const int64_t q_stride[2], const int64_t q_out_stride[2],
+                                         const int64_t k_stride[2], const int64_t v_stride[2], int32_t B,
+                                         int32_t total_new, int32_t H, int32_t Hkv, int32_t D, int32_t rot_dim,
+                                         int32_t max_position, int32_t interleaved, int32_t num_blocks,
+                                         int32_t num_layers, int32_t layer_idx, int32_t block_size,
+                                         int32_t max_blocks_per_seq, int32_t dtype, float eps, void* stream);
+int mio_qknorm_rope_rows(const void* x, void* out, const int32_t* positions, const float* cos, const float* sin,
+                         const void* weight, const int64_t x_stride[2], const int64_t out_stride[2], /* token, head */
+                         int32_t tokens, int32_t heads, int32_t D, int32_t rot_dim, int32_t max_position,
+                         int32_t interleaved, int32_t dtype, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

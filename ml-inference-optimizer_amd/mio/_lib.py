@@ -143,6 +143,9 @@ EXPORTS = (
     "mio_rope_and_cache_varlen",
     "mio_rope_and_cache_varlen_kv8",
     "mio_rope_rows",
+    "mio_qknorm_rope_and_cache_varlen",
+    "mio_qknorm_rope_and_cache_varlen_kv8",
+    "mio_qknorm_rope_rows",
 )
 
 
@@ -395,6 +398,13 @@ def _load() -> C.CDLL:
     lib.mio_rope_and_cache_varlen_kv8.restype = i32
     lib.mio_rope_rows.argtypes = [vp] * 5 + [p64] * 2 + [i32] * 7 + [vp]
     lib.mio_rope_rows.restype = i32
+    # QK-norm: the rotary forms' arguments with the norm weight(s) after sin and eps after dtype
+    lib.mio_qknorm_rope_and_cache_varlen.argtypes = [vp] * 14 + [p64] * 4 + [i32] * 14 + [f32, vp]
+    lib.mio_qknorm_rope_and_cache_varlen.restype = i32
+    lib.mio_qknorm_rope_and_cache_varlen_kv8.argtypes = [vp] * 16 + [p64] * 4 + [i32] * 14 + [f32, vp]
+    lib.mio_qknorm_rope_and_cache_varlen_kv8.restype = i32
+    lib.mio_qknorm_rope_rows.argtypes = [vp] * 6 + [p64] * 2 + [i32] * 7 + [f32, vp]
+    lib.mio_qknorm_rope_rows.restype = i32
     return lib
 
 

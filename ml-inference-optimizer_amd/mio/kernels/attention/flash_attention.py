@@ -53,6 +53,12 @@ class FlashAttentionConfig:
     # per parameter version; ops.gemm_skinny_w8) where ops.gemm_skinny_w8_ok advises it; a call it does not advise runs as
     # decode_gemm says.  Activations, the output and every other call stay 16-bit: a storage form, not precision="fp8".
     decode_gemm_fp8: bool = False
+    # QK-norm (Qwen3, Gemma 3): every q and k head is RMS-normalised over head_dim with a learned [head_dim] weight
+    # (q_norm.weight / k_norm.weight, ones at construction) between the projection and the rotation, fused into the rotation
+    # (ops.qk_norm_rotary) and rounded once.  Needs rotary_dim > 0; off: no new submodules, the layers run exactly as before.
+    # Gemma's (1 + w) form: store 1 + w in the weights.
+    qk_norm: bool = False
+    qk_norm_eps: float = 1e-6
 
     @property
     def allowed_precisions(self) -> Set[str]:
@@ -131,6 +137,15 @@ def _paged_args(kwargs, who: str):
     return vals
 
 
+class _HeadNorm(nn.Module):
+    """The learned weight [head_dim] of a per-head RMSNorm (q_norm / k_norm of a layer with qk_norm).  It only holds the
+    parameter: the norm itself runs fused into the rotation (ops.qk_norm_rotary, ops.qknorm_rope_and_cache_varlen)."""
+
+    def __init__(self, head_dim: int):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(head_dim))
+
+
 class _AttentionBase(nn.Module):
     def _setup(self, hidden_size, num_attention_heads, config, num_kv_heads):
         self.hidden_size = hidden_size
@@ -147,6 +162,15 @@ class _AttentionBase(nn.Module):
         if rd and (rd < 0 or rd % 16 != 0 or rd > self.head_dim):
             raise ValueError(f"rotary_dim must be 0 (off) or a multiple of 16 up to head_dim {self.head_dim}, got {rd}")
         self._rope_key, self._rope_tabs = None, None  # plain attributes: the tables are derived, not state
+        if self.config.qk_norm and not rd:
+            raise ValueError("qk_norm=True needs rotary_dim > 0: the norm is fused into the rotation, a norm-only path is not built")
+
+    def _setup_qk_norm(self):
+        """q_norm / k_norm ([head_dim] weights, ones) where the config asks for QK-norm; nothing otherwise.  Called after the
+        projections are made, so their initialisation draws what it drew before."""
+        if self.config.qk_norm:
+            self.q_norm = _HeadNorm(self.head_dim)
+            self.k_norm = _HeadNorm(self.head_dim)
 
     def _rope_tables(self, device):
         """(cos, sin) of the config's schedule on device: built once, and again when max_position (or the schedule) changes."""
@@ -157,9 +181,14 @@ class _AttentionBase(nn.Module):
             self._rope_key = key
         return self._rope_tabs
 
-    def _rotate(self, t, positions):
-        """t [B,S,heads,D] (a fresh projection result or a view of one) rotated in place at positions int32 [B,S] or [S]."""
+    def _rotate(self, t, positions, norm=None):
+        """t [B,S,heads,D] (a fresh projection result or a view of one) rotated in place at positions int32 [B,S] or [S]; with
+        QK-norm on, normalised by `norm` (q_norm or k_norm: its weight in t's dtype, cast again when it changes) in the same
+        pass."""
         cos, sin = self._rope_tables(t.device)
+        if self.config.qk_norm:
+            return ops.qk_norm_rotary(t, self._cast.get(norm.weight, t.dtype), cos, sin, positions,
+                                      eps=self.config.qk_norm_eps, interleaved=self.config.rotary_interleaved, out=t)
         return ops.apply_rotary(t, cos, sin, positions, interleaved=self.config.rotary_interleaved, out=t)
 
     def _dense_positions(self, kwargs, S, device):
@@ -191,7 +220,9 @@ class _AttentionBase(nn.Module):
                        + torch.arange(q_len, dtype=torch.int32, device=q.device).view(1, q_len))
             else:
                 pos = pos.to(device=q.device, dtype=torch.int32)
-            q = self._rotate(q, pos)
+            # with qk_norm the keys were also normalised on their way into the cache (ops.qknorm_rope_and_cache_varlen with
+            # k_norm.weight); q is normalised here, in the same pass as its rotation
+            q = self._rotate(q, pos, getattr(self, "q_norm", None))
         q = q.permute(0, 2, 1, 3)
         out = torch.empty(B, q_len, self.num_attention_heads, self.head_dim, dtype=dt, device=q2d.device)
         ops.paged_attention_forward(q, out.permute(0, 2, 1, 3), k_cache, v_cache, bt, cl, bs, max_seq_len, layer_idx,
@@ -214,7 +245,8 @@ class _AttentionBase(nn.Module):
         cfg = self.config
         if cfg.rotary_dim > 0:
             pos = self._dense_positions(kwargs, q.shape[1], q.device)
-            q, k = self._rotate(q, pos), self._rotate(k, pos)
+            q = self._rotate(q, pos, getattr(self, "q_norm", None))
+            k = self._rotate(k, pos, getattr(self, "k_norm", None))
         if plan.kpre:
             return ops.fa3_fwd(q, k, v, causal=cfg.causal, k_prescaled=True, out_blocked=plan.out_blocked)
         if cfg.normalize_query:
@@ -236,6 +268,7 @@ class FlashAttentionLayer(_AttentionBase):
         self.o_proj = nn.Linear(hidden_size, hidden_size)
         self.flash_attention = FlashAttention3(self.config)
         self._init_weights()
+        self._setup_qk_norm()
 
     def _init_weights(self):
         for lin in (self.q_proj, self.k_proj, self.v_proj, self.o_proj):  # N(0, 0.02), zero bias (:531-542)
@@ -279,6 +312,7 @@ class FlashSelfAttention(_AttentionBase):
         self.o_proj = nn.Linear(hidden_size, hidden_size)
         self.flash_attention = FlashAttention3(self.config)
         self._init_weights()
+        self._setup_qk_norm()
 
     def _init_weights(self):
         for lin in (self.qkv_proj, self.o_proj):
@@ -475,6 +509,12 @@ class ModelConverter:
                 rep = rep.to(device=ref_p.device, dtype=ref_p.dtype)
             _copy_linear(rep.qkv_proj, getattr(module, qkv_name))
         _copy_linear(rep.o_proj, getattr(module, out_name))
+        if cfg.qk_norm:  # the source's per-head norm weights, where it has them in this shape; anything else is left alone
+            for n in ("q_norm", "k_norm"):
+                w = getattr(getattr(module, n, None), "weight", None)
+                if isinstance(w, torch.Tensor) and tuple(w.shape) == (rep.head_dim,):
+                    with torch.no_grad():
+                        getattr(rep, n).weight.copy_(w)
         rep.train(module.training)
         return rep
 

@@ -1611,15 +1611,25 @@ def apply_rotary(x, cos, sin, positions, *, interleaved: bool = False, out=None)
     position: y1 = x1 c - x2 s, y2 = x2 c + x1 s in fp32, rounded once; the neox pairing (i with i + rot_dim / 2) or, with
     interleaved, GPT-J's (2 i with 2 i + 1).  Elements past rot_dim are copied.  A position outside [0, max_position) gives a
     row of zeros.  out (x's shape and dtype, last dim contiguous, strides multiples of 8) may be x itself."""
-    who = "apply_rotary"
+    r = _rotary_rows_args("apply_rotary", x, cos, sin, positions, interleaved, out)
+    check(lib.mio_rope_rows(*r.head, *r.strides, *r.sizes, _stream()))
+    return r.res
+
+
+def _rotary_rows_args(who: str, x, cos, sin, positions, interleaved: bool, out, weight=None):
+    """The argument checks of the standalone rotary forms (apply_rotary, qk_norm_rotary) and what they pass to the library:
+    head (x, out, positions, cos, sin[, weight] addresses), strides (x, out), sizes (tokens, heads, D, rot_dim, max_position,
+    interleaved, dtype), res (the tensor to return) and keep (the tensors the addresses point into)."""
     if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4):
         raise ValueError(f"{who}: x must be [tokens, heads, head_dim] or [B, S, heads, head_dim]")
-    _need_cuda(x, cos, sin, positions, out)
+    _need_cuda(x, cos, sin, positions, out, weight)
     dt = _dtype_id(x)
     D = x.shape[-1]
     if D % 8 != 0 or D > 128:
         raise ValueError(f"head_dim must be a multiple of 8 and <= 128, got {D}")
     max_position, rot_dim = _rope_tables_ok(cos, sin, D, False, interleaved, x.device, who)
+    if weight is not None:
+        _qk_weight_ok(weight, x, "weight", who)
     if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32 or positions.device != x.device:
         raise ValueError(f"{who}: positions must be an int32 tensor on the device of x")
     if out is not None and (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device):
@@ -1655,9 +1665,46 @@ def apply_rotary(x, cos, sin, positions, *, interleaved: bool = False, out=None)
     T, Hn, _ = x3.shape
     xs = (C.c_int64 * 2)(x3.stride(0), x3.stride(1))
     os_ = (C.c_int64 * 2)(out3.stride(0), out3.stride(1))
-    check(lib.mio_rope_rows(x3.data_ptr(), out3.data_ptr(), positions.data_ptr(), cos.data_ptr(), sin.data_ptr(), xs, os_,
-                            T, Hn, D, rot_dim, max_position, int(bool(interleaved)), dt, _stream()))
-    return res
+    head = (x3.data_ptr(), out3.data_ptr(), positions.data_ptr(), cos.data_ptr(), sin.data_ptr())
+    if weight is not None:
+        head += (weight.data_ptr(),)
+    return types.SimpleNamespace(head=head, strides=(xs, os_), res=res, keep=(x3, out3, positions),
+                                 sizes=(T, Hn, D, rot_dim, max_position, int(bool(interleaved)), dt))
+
+
+def _qk_weight_ok(w, x, name: str, who: str) -> None:
+    """A QK-norm weight: [head_dim] of x's dtype on x's device, contiguous and 16-byte aligned."""
+    D = x.shape[-1]
+    if not isinstance(w, torch.Tensor) or w.dim() != 1 or w.numel() != D or w.dtype != x.dtype or w.device != x.device \
+            or not w.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous [head_dim] = [{D}] tensor of {x.dtype} on the device of the "
+                         f"normalised tensor")
+    if w.data_ptr() % 16:
+        raise ValueError(f"{who}: {name} must be 16-byte aligned")
+
+
+def _qk_eps(eps, who: str) -> float:
+    eps = float(eps)
+    if not math.isfinite(eps) or eps < 0.0:
+        raise ValueError(f"{who}: eps must be finite and not negative, got {eps}")
+    return eps
+
+
+def qk_norm_rotary(x, weight, cos, sin, positions, *, eps: float = 1e-6, interleaved: bool = False, out=None) -> torch.Tensor:
+    """QK-norm and rotary position embedding of x in one pass (mio_qknorm_rope_rows): every head row of x is RMS-normalised
+    over head_dim -- n = x * rsqrt(mean(x^2) + eps) * weight in fp32, the mean over the whole head_dim, not over rot_dim --
+    then the first rot_dim elements of n are rotated as apply_rotary rotates and the result is rounded once (nothing is
+    rounded between the norm and the rotation).  x, cos, sin, positions, interleaved and out as apply_rotary (out may be x);
+    weight [head_dim] in x's dtype, on x's device, contiguous, shared by all heads (q_norm.weight for q, k_norm.weight for k).
+    Gemma's (1 + w) form is the caller's concern: pass 1 + w.  A zero row gives zeros, a NaN in a head makes that head NaN, a
+    position outside [0, max_position) gives a row of zeros."""
+    who = "qk_norm_rotary"
+    eps = _qk_eps(eps, who)
+    if not isinstance(weight, torch.Tensor):
+        raise ValueError(f"{who}: weight must be a [head_dim] tensor")
+    r = _rotary_rows_args(who, x, cos, sin, positions, interleaved, out, weight)
+    check(lib.mio_qknorm_rope_rows(*r.head, *r.strides, *r.sizes, eps, _stream()))
+    return r.res
 
 
 def rope_and_cache_varlen(q, key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths,
@@ -1671,10 +1718,24 @@ def rope_and_cache_varlen(q, key, value, k_cache, v_cache, block_tables, cu_seql
     positions[t] (int32 [total_new]) where given -- the cache row does not depend on it.  A token outside every sequence, or
     whose position is outside [0, max_position), writes nothing to the caches and gets a q_out row of zeros.  Queued on the
     current stream with no host sync (graph-capturable)."""
-    who = "rope_and_cache_varlen"
-    _need_cuda(q, key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths, cos, sin, positions, q_out)
+    r = _rope_cache_args("rope_and_cache_varlen", q, key, value, k_cache, v_cache, block_tables, cu_seqlens_new,
+                         context_lengths, block_size, layer_idx, cos, sin, positions, interleaved, q_out, k_scale, v_scale)
+    fn = lib.mio_rope_and_cache_varlen_kv8 if r.kv8 else lib.mio_rope_and_cache_varlen
+    check(fn(*r.head, *r.strides, *r.sizes, _stream()))
+    return r.q_out
+
+
+def _rope_cache_args(who, q, key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths, block_size,
+                     layer_idx, cos, sin, positions, interleaved, q_out, k_scale, v_scale, weights=()):
+    """The argument checks of the rotating cache writes (rope_and_cache_varlen, qknorm_rope_and_cache_varlen: weights = the two
+    norm weights) and what they pass to the library: head (q .. sin[, q_weight, k_weight] addresses), strides (q, q_out, k, v),
+    sizes (B .. dtype), kv8, q_out and keep (the tensors the addresses point into)."""
+    _need_cuda(q, key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths, cos, sin, positions, q_out,
+               *weights)
     w = _cache_write_args(key, value, k_cache, v_cache, block_tables, context_lengths, block_size, layer_idx, k_scale,
                           v_scale, who, cu_seqlens_new, q)
+    for name, t in zip(("q_weight", "k_weight"), weights):
+        _qk_weight_ok(t, key, name, who)
     T, D = w.T, w.D
     max_position, rot_dim = _rope_tables_ok(cos, sin, D, w.kv8, interleaved, key.device, who)
     if positions is not None:
@@ -1690,11 +1751,37 @@ def rope_and_cache_varlen(q, key, value, k_cache, v_cache, block_tables, cu_seql
     q = _rows16(q)
     qs = (C.c_int64 * 2)(q.stride(0), q.stride(1))
     os_ = (C.c_int64 * 2)(q_out.stride(0), q_out.stride(1))
-    fn = lib.mio_rope_and_cache_varlen_kv8 if w.kv8 else lib.mio_rope_and_cache_varlen
-    check(fn(q.data_ptr(), q_out.data_ptr(), *w.data, *w.tables, _ptr(positions), cos.data_ptr(), sin.data_ptr(), qs, os_,
-             *w.strides, w.B, T, q.shape[1], w.Hkv, D, rot_dim, max_position, int(bool(interleaved)), *w.geom, w.dt,
-             _stream()))
-    return q_out
+    head = (q.data_ptr(), q_out.data_ptr(), *w.data, *w.tables, _ptr(positions), cos.data_ptr(), sin.data_ptr(),
+            *(t.data_ptr() for t in weights))
+    return types.SimpleNamespace(
+        head=head, strides=(qs, os_, *w.strides), kv8=w.kv8, q_out=q_out, keep=(q, w.keep),
+        sizes=(w.B, T, q.shape[1], w.Hkv, D, rot_dim, max_position, int(bool(interleaved)), *w.geom, w.dt))
+
+
+def qknorm_rope_and_cache_varlen(q, key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths,
+                                 block_size: int, layer_idx: int, cos, sin, q_weight, k_weight, *, eps: float = 1e-6,
+                                 positions=None, interleaved: bool = False, q_out=None, k_scale=None,
+                                 v_scale=None) -> torch.Tensor:
+    """rope_and_cache_varlen with QK-norm fused in (mio_qknorm_rope_and_cache_varlen / _kv8): every query head of q and every
+    key head of key is RMS-normalised over head_dim -- n = x * rsqrt(mean(x^2) + eps) * weight in fp32, the mean over the
+    whole head_dim, not over rot_dim; q_weight / k_weight [head_dim] in q's dtype, contiguous, shared by all heads of their
+    kind -- then rotated as rope_and_cache_varlen rotates and rounded ONCE into the stored format: q into q_out (returned;
+    may be q; allocated when None), K into the paged cache (16 bits, or e4m3 of y / k_scale for a float8_e4m3fn cache).
+    Nothing is rounded between the norm and the rotation.  V is untouched: its bytes are reshape_and_cache_varlen's.  Every
+    other argument, the token placement and the skipping rules as rope_and_cache_varlen: a token outside every sequence, or
+    whose position is outside [0, max_position), writes nothing to the caches and gets a q_out row of zeros.  q_out is
+    bit-equal to qk_norm_rotary(q, q_weight, ...).  Gemma's (1 + w) form is the caller's concern: pass 1 + w.  A zero row
+    gives zeros; a NaN in a head makes that head NaN.  Queued on the current stream with no host sync (graph-capturable)."""
+    who = "qknorm_rope_and_cache_varlen"
+    eps = _qk_eps(eps, who)
+    for name, t in (("q_weight", q_weight), ("k_weight", k_weight)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name} must be a [head_dim] tensor")
+    r = _rope_cache_args(who, q, key, value, k_cache, v_cache, block_tables, cu_seqlens_new, context_lengths, block_size,
+                         layer_idx, cos, sin, positions, interleaved, q_out, k_scale, v_scale, (q_weight, k_weight))
+    fn = lib.mio_qknorm_rope_and_cache_varlen_kv8 if r.kv8 else lib.mio_qknorm_rope_and_cache_varlen
+    check(fn(*r.head, *r.strides, *r.sizes, eps, _stream()))
+    return r.q_out
 
 
 # ------------------------------------------------------------------------------------------------
