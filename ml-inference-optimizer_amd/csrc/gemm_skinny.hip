@@ -1,5 +1,8 @@
 // Decode-step GEMM (1 <= M <= 64): y[M,N] = act(x[M,K] w[N,K]^T + bias) (+ residual), SwiGLU with a second weight; the C-ABI
-// entry points mio_gemm_skinny* (include/mio_hip.h).  The plan (checks, split of K, workspace) is gemm_skinny_plan.h.
+// entry points mio_gemm_skinny* (include/mio_hip.h).  This file is the kernel's K loop and the entry points' argument marshalling:
+// the plan (shape checks, split of K, workspace, tuning values) is gemm_skinny_plan.h under the form SKINNY_W16, and the launch's
+// checks, the launcher, the host queries, the epilogue and the reduction are gemm_skinny_common.h, all shared with the fp8-weight
+// unit (gemm_skinny_w8.hip).
 //
 // A decode step's linear layers stream their weights from HBM once and do almost no arithmetic on them, so the kernel is built
 // as the decode attention kernels are: many workgroups with loads in flight, none of them waiting on another.
@@ -14,16 +17,16 @@
 //   * split-K in two launches, as decode does it: workgroup (column tile, slice) writes fp32 partials [nsplit][M][N], and
 //     gemm_skinny_reduce_kernel sums the slices in index order, applies the epilogue and rounds once.  With one slice the first
 //     kernel runs the same epilogue itself.  No atomics, counters or barriers between workgroups: results are bit-reproducible.
-//     The epilogue, the partial stores and the reduction are gemm_skinny_common.h, shared with the fp8-weight unit.
-#include <string>
-
 #include "gemm_skinny_common.h"
-#include "gemm_skinny_plan.h"
+
+constexpr SkinnyForm FORM = SKINNY_W16;  // this unit's weight form (gemm_skinny_plan.h)
+constexpr int SKINNY_KSTEP = FORM.kstep;
+static_assert(FORM.sets(false) == 2 && FORM.sets(true) == 2, "the K loop below is double-buffered");
 
 template <typename T, int MF, bool GLU>
 __global__ __launch_bounds__(256) void gemm_skinny_kernel(const SkinnyDev p) {
   using X8 = typename DT<T>::x8;
-  constexpr int SKC = GLU ? SKINNY_CHUNK_K_GLU : SKINNY_CHUNK_K;  // k per chunk (gemm_skinny_plan.h)
+  constexpr int SKC = FORM.chunk(GLU);  // k per chunk
   constexpr int KS = SKC / SKINNY_KSTEP, PCS = SKC / 8, ROWS = MF * 16, ROWB = SKC * 2;
   constexpr int XPT = ROWS * PCS / 256;  // 16-byte pieces of the x chunk per thread
   static_assert(PCS >= 16 && ROWS * PCS % 256 == 0, "chunk shape");
@@ -113,96 +116,36 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const SkinnyDev p) {
   skinny_write<T, MF, GLU, false>(p, s, c, n, acc, accg);
 }
 
-template <typename T, int MF, bool GLU>
-static void skinny_launch_mf(const SkinnyDev& p, const SkinnyPlan& pl, hipStream_t st) {
-  hipLaunchKernelGGL((gemm_skinny_kernel<T, MF, GLU>), dim3((unsigned)pl.tiles_n, (unsigned)pl.nsplit), dim3(256), 0, st, p);
-}
+#define SKINNY_KERNELS(T, GLU)                                                                                        \
+  {{gemm_skinny_kernel<T, 1, GLU>, gemm_skinny_kernel<T, 2, GLU>, gemm_skinny_kernel<T, 3, GLU>, gemm_skinny_kernel<T, 4, GLU>}, \
+   gemm_skinny_reduce_kernel<T, GLU, false>}
+static const SkinnyKernelTable KERNELS = {{SKINNY_KERNELS(__bf16, true), SKINNY_KERNELS(__bf16, false)},
+                                          {SKINNY_KERNELS(_Float16, true), SKINNY_KERNELS(_Float16, false)}};
+#undef SKINNY_KERNELS
 
-template <typename T, bool GLU>
-static void skinny_launch(const SkinnyDev& p, const SkinnyPlan& pl, hipStream_t st) {
-  switch (pl.mf) {
-    case 1: skinny_launch_mf<T, 1, GLU>(p, pl, st); break;
-    case 2: skinny_launch_mf<T, 2, GLU>(p, pl, st); break;
-    case 3: skinny_launch_mf<T, 3, GLU>(p, pl, st); break;
-    default: skinny_launch_mf<T, 4, GLU>(p, pl, st); break;
-  }
-  if (pl.nsplit > 1) {
-    const int64_t threads = (int64_t)p.M * ((p.N + 3) / 4);
-    hipLaunchKernelGGL((gemm_skinny_reduce_kernel<T, GLU>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p);
-  }
-}
-
-// ---- host queries ------------------------------------------------------------------------------------------------------
+// ---- the C ABI: argument marshalling over gemm_skinny_common.h's host side -------------------------------------------
 extern "C" int mio_gemm_skinny_splits(int64_t M, int32_t N, int32_t K, int32_t act) {
-  std::string err;
-  if (!skinny_shape_ok("mio_gemm_skinny_splits", M, N, K, act, err)) return mio_fail(err);
-  return skinny_plan(M, N, K, act).nsplit;
+  return skinny_query_splits(FORM, "mio_gemm_skinny_splits", M, N, K, act);
 }
 
 extern "C" size_t mio_gemm_skinny_workspace_bytes(int64_t M, int32_t N, int32_t K, int32_t act) {
-  std::string err;
-  if (!skinny_shape_ok("mio_gemm_skinny_workspace_bytes", M, N, K, act, err)) {
-    mio_set_error(err);
-    return 0;
-  }
-  return skinny_workspace_bytes(skinny_plan(M, N, K, act), M, N);
+  return skinny_query_workspace_bytes(FORM, "mio_gemm_skinny_workspace_bytes", M, N, K, act);
 }
 
 extern "C" int mio_gemm_skinny_slice(int64_t M, int32_t N, int32_t K, int32_t act, int32_t slice, int32_t* k_begin, int32_t* k_end) {
-  std::string err;
-  if (!skinny_shape_ok("mio_gemm_skinny_slice", M, N, K, act, err)) return mio_fail(err);
-  const SkinnyPlan pl = skinny_plan(M, N, K, act);
-  MIO_CHECK(k_begin && k_end && slice >= 0 && slice < pl.nsplit, "mio_gemm_skinny_slice: slice must be in [0, mio_gemm_skinny_splits)");
-  skinny_slice(pl, K, slice, *k_begin, *k_end);
-  return 0;
+  return skinny_query_slice(FORM, "mio_gemm_skinny_slice", M, N, K, act, slice, k_begin, k_end);
 }
 
-extern "C" int mio_gemm_skinny_chunk_k(int32_t act) {
-  std::string err;
-  if (!skinny_shape_ok("mio_gemm_skinny_chunk_k", 0, 0, 0, act, err)) return mio_fail(err);
-  return act == MIO_ACT_SWIGLU ? SKINNY_CHUNK_K_GLU : SKINNY_CHUNK_K;
-}
+extern "C" int mio_gemm_skinny_chunk_k(int32_t act) { return skinny_query_chunk_k(FORM, "mio_gemm_skinny_chunk_k", act); }
 
 extern "C" int mio_gemm_skinny_ok(int64_t M, int32_t N, int32_t K, int32_t act) {
-  std::string err;
-  return (skinny_shape_ok("mio_gemm_skinny_ok", M, N, K, act, err) && skinny_advised(M, N, K, act)) ? 1 : 0;
+  return skinny_query_ok(FORM, "mio_gemm_skinny_ok", M, N, K, act);
 }
 
-// ---- launch ------------------------------------------------------------------------------------------------------------
 extern "C" int mio_gemm_skinny(const void* x, const void* w, const void* bias, const void* w_gate, const void* bias_gate,
                                const void* residual, void* y, void* workspace, int64_t M, int32_t N, int32_t K, int64_t ldx,
                                int64_t ldw, int64_t ldy, int64_t ldr, int32_t act, int32_t dtype, void* stream) {
-  const char* who = "mio_gemm_skinny";
-#define SKINNY_CHECK(cond, text) MIO_CHECK(cond, std::string(who) + (text))
-  std::string err;
-  if (!skinny_shape_ok(who, M, N, K, act, err)) return mio_fail(err);
-  SKINNY_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, ": dtype must be bf16 or fp16");
-  const bool glu = act == MIO_ACT_SWIGLU;
-  SKINNY_CHECK(glu == (w_gate != nullptr), ": w_gate is required iff act == SWIGLU");
-  SKINNY_CHECK(glu || bias_gate == nullptr, ": bias_gate belongs to act == SWIGLU");
-  SKINNY_CHECK(ldx % 8 == 0 && ldw % 8 == 0 && ldy % 8 == 0 && (!residual || ldr % 8 == 0), ": row strides must be multiples of 8 elements");
-  SKINNY_CHECK(ldx >= K && ldw >= K && ldy >= N && (!residual || ldr >= N), ": row stride smaller than row length");
-  SKINNY_CHECK(w && (M == 0 || (x && y)), ": x, w, y must be non-null");
-  SKINNY_CHECK(mio_aligned16(x) && mio_aligned16(w) && mio_aligned16(y) && mio_aligned16(w_gate) && mio_aligned16(residual) &&
-                   mio_aligned16(bias) && mio_aligned16(bias_gate) && mio_aligned16(workspace),
-               ": pointers must be 16-byte aligned");
-  const SkinnyPlan pl = skinny_plan(M, N, K, act);
-  if (M == 0 || N == 0) return 0;
-  SKINNY_CHECK(pl.nsplit == 1 || workspace != nullptr, ": workspace required (mio_gemm_skinny_workspace_bytes) when the plan splits K");
-#undef SKINNY_CHECK
-  SkinnyDev p;
-  p.x = x; p.w = w; p.wg = w_gate; p.bias = bias; p.bias_g = bias_gate; p.res = residual; p.y = y;
-  p.ws = pl.nsplit > 1 ? (float*)workspace : nullptr;
-  p.scale = nullptr; p.scale_g = nullptr;
-  p.ldx = ldx; p.ldw = ldw; p.ldy = ldy; p.ldr = ldr;
-  p.M = (int)M; p.N = N; p.K = K; p.act = act; p.nsplit = pl.nsplit; p.steps = pl.steps;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MIO_BF16) {
-    if (glu) skinny_launch<__bf16, true>(p, pl, st); else skinny_launch<__bf16, false>(p, pl, st);
-  } else {
-    if (glu) skinny_launch<_Float16, true>(p, pl, st); else skinny_launch<_Float16, false>(p, pl, st);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("mio_gemm_skinny launch: ") + hipGetErrorString(e));
-  return 0;
+  return skinny_run(FORM, KERNELS, x, w, nullptr, bias, w_gate, nullptr, bias_gate, residual, y, workspace, M, N, K, ldx, ldw, ldy,
+                    ldr, act, dtype, stream);
 }
+

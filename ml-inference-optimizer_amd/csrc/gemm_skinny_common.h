@@ -1,9 +1,14 @@
 // What the two decode-step GEMM units share (gemm_skinny.hip: 16-bit weights; gemm_skinny_w8.hip: e4m3fn weights with one fp32
-// scale per output column): the launch's device arguments, the one epilogue and the split-K reduction.  SCALED is the only
-// difference between the units behind the accumulator: z = fma(acc, scale[n], bias[n]) in place of z = acc + bias[n].  With the
-// flag off nothing of the scales is read and the arithmetic is that of the 16-bit kernel alone.
+// scale per output column).  On the device: the launch's arguments, the one epilogue and the split-K reduction.  SCALED is the
+// only difference between the units behind the accumulator: z = fma(acc, scale[n], bias[n]) in place of z = acc + bias[n].  With
+// the flag off nothing of the scales is read and the arithmetic is that of the 16-bit kernel alone.  On the host (the end of
+// this file): the launcher, the checks and argument fill of a launch and the host queries, each written once over the unit's
+// SkinnyForm (gemm_skinny_plan.h) and its table of kernels.  A unit keeps its K loop and its extern "C" wrappers.
 #pragma once
+#include <string>
+
 #include "gemm_kernel.h"
+#include "gemm_skinny_plan.h"
 
 struct SkinnyDev {
   const void* x;
@@ -130,4 +135,102 @@ __global__ __launch_bounds__(256) void gemm_skinny_reduce_kernel(const SkinnyDev
         }
   }
   skinny_finish<T, GLU, SCALED>(p, m, n, v, g);
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+// The kernels of one (dtype, SwiGLU or not) pair of a unit: its K-loop kernel at 1 .. 4 row fragments and the reduction.
+using SkinnyKernel = void (*)(const SkinnyDev);
+struct SkinnyKernels {
+  SkinnyKernel main[4], reduce;
+};
+// a unit's table: [MIO_BF16 / MIO_FP16][SwiGLU / plain]
+using SkinnyKernelTable = SkinnyKernels[2][2];
+
+static inline void skinny_launch(const SkinnyKernels& k, const SkinnyDev& p, const SkinnyPlan& pl, hipStream_t st) {
+  hipLaunchKernelGGL(k.main[pl.mf - 1], dim3((unsigned)pl.tiles_n, (unsigned)pl.nsplit), dim3(256), 0, st, p);
+  if (pl.nsplit > 1) {
+    const int64_t threads = (int64_t)p.M * ((p.N + 3) / 4);
+    hipLaunchKernelGGL(k.reduce, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p);
+  }
+}
+
+// A launch of either unit: every check, the plan, the empty call, the device arguments and the launches.  scale / scale_g are
+// the weights' per-column scales (null for a form without them); ldw counts in the unit the form's ldw_multiple does.
+static inline int skinny_run(const SkinnyForm& f, const SkinnyKernelTable& kernels, const void* x, const void* w, const float* scale,
+                             const void* bias, const void* w_gate, const float* scale_g, const void* bias_gate, const void* residual,
+                             void* y, void* workspace, int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy,
+                             int64_t ldr, int32_t act, int32_t dtype, void* stream) {
+#define SKINNY_CHECK(cond, text) MIO_CHECK(cond, std::string(f.name) + (text))
+  std::string err;
+  if (!skinny_shape_ok(f, f.name, M, N, K, act, err)) return mio_fail(err);
+  SKINNY_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, f.dtype_text);
+  const bool glu = act == MIO_ACT_SWIGLU;
+  SKINNY_CHECK(glu == (w_gate != nullptr) && (!f.scaled || glu == (scale_g != nullptr)), f.gate_text);
+  SKINNY_CHECK(glu || bias_gate == nullptr, ": bias_gate belongs to act == SWIGLU");
+  SKINNY_CHECK(ldw % f.ldw_multiple == 0, f.ldw_multiple_text);
+  SKINNY_CHECK(ldw >= K, f.ldw_short_text);
+  SKINNY_CHECK(ldx % 8 == 0 && ldy % 8 == 0 && (!residual || ldr % 8 == 0), f.ld_multiple_text);
+  SKINNY_CHECK(ldx >= K && ldy >= N && (!residual || ldr >= N), ": row stride smaller than row length");
+  SKINNY_CHECK(w && (!f.scaled || scale) && (M == 0 || (x && y)), f.null_text);
+  SKINNY_CHECK(mio_aligned16(x) && mio_aligned16(w) && mio_aligned16(y) && mio_aligned16(w_gate) && mio_aligned16(residual) &&
+                   mio_aligned16(bias) && mio_aligned16(bias_gate) && mio_aligned16(workspace) && mio_aligned16(scale) &&
+                   mio_aligned16(scale_g),
+               ": pointers must be 16-byte aligned");
+  const SkinnyPlan pl = skinny_plan(f, M, N, K, act);
+  if (M == 0 || N == 0) return 0;
+  SKINNY_CHECK(pl.nsplit == 1 || workspace != nullptr, std::string(": workspace required (") + f.name + "_workspace_bytes) when the plan splits K");
+#undef SKINNY_CHECK
+  SkinnyDev p;
+  p.x = x; p.w = w; p.wg = w_gate; p.bias = bias; p.bias_g = bias_gate; p.res = residual; p.y = y;
+  p.ws = pl.nsplit > 1 ? (float*)workspace : nullptr;
+  p.scale = scale; p.scale_g = scale_g;
+  p.ldx = ldx; p.ldw = ldw; p.ldy = ldy; p.ldr = ldr;
+  p.M = (int)M; p.N = N; p.K = K; p.act = act; p.nsplit = pl.nsplit; p.steps = pl.steps;
+  skinny_launch(kernels[dtype == MIO_BF16 ? 0 : 1][glu ? 0 : 1], p, pl, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return mio_fail(std::string(f.name) + " launch: " + hipGetErrorString(e));
+  return 0;
+}
+
+// The host queries; who is the extern "C" entry point that asks.
+static inline int skinny_query_splits(const SkinnyForm& f, const char* who, int64_t M, int32_t N, int32_t K, int32_t act) {
+  std::string err;
+  if (!skinny_shape_ok(f, who, M, N, K, act, err)) return mio_fail(err);
+  return skinny_plan(f, M, N, K, act).nsplit;
+}
+
+static inline size_t skinny_query_workspace_bytes(const SkinnyForm& f, const char* who, int64_t M, int32_t N, int32_t K, int32_t act) {
+  std::string err;
+  if (!skinny_shape_ok(f, who, M, N, K, act, err)) {
+    mio_set_error(err);
+    return 0;
+  }
+  return skinny_workspace_bytes(skinny_plan(f, M, N, K, act), M, N);
+}
+
+static inline int skinny_query_slice(const SkinnyForm& f, const char* who, int64_t M, int32_t N, int32_t K, int32_t act, int32_t slice,
+                                     int32_t* k_begin, int32_t* k_end) {
+  std::string err;
+  if (!skinny_shape_ok(f, who, M, N, K, act, err)) return mio_fail(err);
+  const SkinnyPlan pl = skinny_plan(f, M, N, K, act);
+  MIO_CHECK(k_begin && k_end && slice >= 0 && slice < pl.nsplit, std::string(who) + ": slice must be in [0, " + f.name + "_splits)");
+  skinny_slice(f, pl, K, slice, *k_begin, *k_end);
+  return 0;
+}
+
+static inline int skinny_query_chunk_k(const SkinnyForm& f, const char* who, int32_t act) {
+  std::string err;
+  if (!skinny_shape_ok(f, who, 0, 0, 0, act, err)) return mio_fail(err);
+  return f.chunk(act == MIO_ACT_SWIGLU);
+}
+
+static inline int skinny_query_depth(const SkinnyForm& f, const char* who, int32_t act) {
+  std::string err;
+  if (!skinny_shape_ok(f, who, 0, 0, 0, act, err)) return mio_fail(err);
+  return f.sets(act == MIO_ACT_SWIGLU);
+}
+
+static inline int skinny_query_ok(const SkinnyForm& f, const char* who, int64_t M, int32_t N, int32_t K, int32_t act) {
+  std::string err;
+  return (skinny_shape_ok(f, who, M, N, K, act, err) && f.advised(M, N, K, act)) ? 1 : 0;
 }

@@ -1,8 +1,9 @@
 // Decode-step GEMM on weight-only FP8 (1 <= M <= 64): y[M,N] = act(scale[n] * (x[M,K] w8[N,K]^T) + bias[n]) (+ residual), SwiGLU
 // with a second weight and its own scales; and the one-time quantiser that makes (w8, scale) from a 16-bit weight.  The C-ABI
-// entry points mio_gemm_skinny_w8* and mio_weight_quant_w8 (include/mio_hip.h).  The plan (checks, split of K, workspace, tuning
-// values) is gemm_skinny_w8_plan.h; the epilogue, the partial stores and the reduction are gemm_skinny_common.h, shared with
-// gemm_skinny.hip, whose structure this kernel keeps.  Weights are OCP e4m3fn bytes (torch.float8_e4m3fn), row-major [N, K], with
+// entry points mio_gemm_skinny_w8* and mio_weight_quant_w8 (include/mio_hip.h).  This file is the kernel's K loop, the quantiser
+// and the entry points' argument marshalling: the plan (shape checks, split of K, workspace, tuning values) is gemm_skinny_plan.h
+// under the form SKINNY_W8, and the launch's checks, the launcher, the host queries, the epilogue and the reduction are
+// gemm_skinny_common.h, all shared with gemm_skinny.hip.  Weights are OCP e4m3fn bytes (torch.float8_e4m3fn), row-major [N, K], with
 // one fp32 scale per output column; x, bias, residual and y stay bf16 / fp16.  Every e4m3fn value is exact in bf16 and fp16, so
 // the bytes are widened in registers at scale 1 (kv8_to_x8) and multiplied on the 16-bit MFMA: the arithmetic is the 16-bit
 // kernel's plus one fp32 fma per output.  FP8 is a storage form of the weights here, not a compute precision.
@@ -14,7 +15,7 @@
 //     LDS.  (An MFMA sums over the 32 (lane group, element) slots; which k sits in a slot is free as long as A and B agree.)
 //   * x is staged once per workgroup through LDS in whole rows, 16-byte piece p of row r at p ^ (r & 15), rows >= M and k past
 //     the slice as zeros that are never read from memory.  Two LDS buffers, one barrier per chunk.
-//   * Loads in flight.  A chunk is SKW8_CHUNK_K k (SwiGLU _GLU); the weight registers are a ring of SKW8_DEPTH sets, one chunk
+//   * Loads in flight.  A chunk is the form's chunk_k k (SwiGLU chunk_k_glu); the weight registers are a ring of depth sets, one chunk
 //     each, so DEPTH - 1 chunks of loads are outstanding while one is multiplied.  The x pieces of a chunk are loaded into
 //     registers immediately BEFORE that chunk's weight loads and stored to LDS only when the chunk is due: the vector memory
 //     counter retires loads in issue order, so waiting for an x load issued behind younger weight loads would drain the ring.
@@ -28,17 +29,17 @@
 //   * the weight row is min(n0 + c, N - 1): a lane past the last column computes a copy of the last row and stores nothing;
 //   * x rows >= M and x pieces at k >= ke are zeros written to LDS, never read from memory; weight bytes not loaded are 0x00,
 //     which is +0.0, so no padding byte of any operand reaches a product.
-#include <string>
-
 #include "gemm_skinny_common.h"
-#include "gemm_skinny_w8_plan.h"
 #include "kv8_cvt.h"
+
+constexpr SkinnyForm FORM = SKINNY_W8;  // this unit's weight form (gemm_skinny_plan.h)
+constexpr int SKW8_KSTEP = FORM.kstep;
 
 template <typename T, int MF, bool GLU>
 __global__ __launch_bounds__(256) void gemm_skinny_w8_kernel(const SkinnyDev p) {
   using X8 = typename DT<T>::x8;
-  constexpr int SKC = GLU ? SKW8_CHUNK_K_GLU : SKW8_CHUNK_K;  // k per chunk (gemm_skinny_w8_plan.h)
-  constexpr int D = GLU ? SKW8_DEPTH_GLU : SKW8_DEPTH;        // register sets in the ring
+  constexpr int SKC = FORM.chunk(GLU);  // k per chunk
+  constexpr int D = FORM.sets(GLU);     // register sets in the ring
   constexpr int KS = SKC / SKW8_KSTEP, PCS = SKC / 8, ROWS = MF * 16, ROWB = SKC * 2;
   constexpr int XPT = ROWS * PCS / 256;  // 16-byte pieces of the x chunk per thread
   static_assert(PCS >= 16 && ROWS * PCS % 256 == 0 && SKC % SKW8_KSTEP == 0 && D >= 2, "chunk shape");
@@ -177,70 +178,7 @@ __global__ __launch_bounds__(256) void weight_quant_w8_kernel(const T* w, int64_
     *(u32x4_t*)(dst + k) = kv8_quant16<T>(*(const u32x4_t*)(src + k), *(const u32x4_t*)(src + k + 8), inv);
 }
 
-template <typename T, int MF, bool GLU>
-static void skinny_w8_launch_mf(const SkinnyDev& p, const SkinnyW8Plan& pl, hipStream_t st) {
-  hipLaunchKernelGGL((gemm_skinny_w8_kernel<T, MF, GLU>), dim3((unsigned)pl.tiles_n, (unsigned)pl.nsplit), dim3(256), 0, st, p);
-}
-
-template <typename T, bool GLU>
-static void skinny_w8_launch(const SkinnyDev& p, const SkinnyW8Plan& pl, hipStream_t st) {
-  switch (pl.mf) {
-    case 1: skinny_w8_launch_mf<T, 1, GLU>(p, pl, st); break;
-    case 2: skinny_w8_launch_mf<T, 2, GLU>(p, pl, st); break;
-    case 3: skinny_w8_launch_mf<T, 3, GLU>(p, pl, st); break;
-    default: skinny_w8_launch_mf<T, 4, GLU>(p, pl, st); break;
-  }
-  if (pl.nsplit > 1) {
-    const int64_t threads = (int64_t)p.M * ((p.N + 3) / 4);
-    hipLaunchKernelGGL((gemm_skinny_reduce_kernel<T, GLU, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p);
-  }
-}
-
-// ---- host queries ------------------------------------------------------------------------------------------------------
-extern "C" int mio_gemm_skinny_w8_splits(int64_t M, int32_t N, int32_t K, int32_t act) {
-  std::string err;
-  if (!skinny_w8_shape_ok("mio_gemm_skinny_w8_splits", M, N, K, act, err)) return mio_fail(err);
-  return skinny_w8_plan(M, N, K, act).nsplit;
-}
-
-extern "C" size_t mio_gemm_skinny_w8_workspace_bytes(int64_t M, int32_t N, int32_t K, int32_t act) {
-  std::string err;
-  if (!skinny_w8_shape_ok("mio_gemm_skinny_w8_workspace_bytes", M, N, K, act, err)) {
-    mio_set_error(err);
-    return 0;
-  }
-  return skinny_w8_workspace_bytes(skinny_w8_plan(M, N, K, act), M, N);
-}
-
-extern "C" int mio_gemm_skinny_w8_slice(int64_t M, int32_t N, int32_t K, int32_t act, int32_t slice, int32_t* k_begin,
-                                        int32_t* k_end) {
-  std::string err;
-  if (!skinny_w8_shape_ok("mio_gemm_skinny_w8_slice", M, N, K, act, err)) return mio_fail(err);
-  const SkinnyW8Plan pl = skinny_w8_plan(M, N, K, act);
-  MIO_CHECK(k_begin && k_end && slice >= 0 && slice < pl.nsplit,
-            "mio_gemm_skinny_w8_slice: slice must be in [0, mio_gemm_skinny_w8_splits)");
-  skinny_w8_slice(pl, K, slice, *k_begin, *k_end);
-  return 0;
-}
-
-extern "C" int mio_gemm_skinny_w8_chunk_k(int32_t act) {
-  std::string err;
-  if (!skinny_w8_shape_ok("mio_gemm_skinny_w8_chunk_k", 0, 0, 0, act, err)) return mio_fail(err);
-  return act == MIO_ACT_SWIGLU ? SKW8_CHUNK_K_GLU : SKW8_CHUNK_K;
-}
-
-extern "C" int mio_gemm_skinny_w8_depth(int32_t act) {
-  std::string err;
-  if (!skinny_w8_shape_ok("mio_gemm_skinny_w8_depth", 0, 0, 0, act, err)) return mio_fail(err);
-  return act == MIO_ACT_SWIGLU ? SKW8_DEPTH_GLU : SKW8_DEPTH;
-}
-
-extern "C" int mio_gemm_skinny_w8_ok(int64_t M, int32_t N, int32_t K, int32_t act) {
-  std::string err;
-  return (skinny_w8_shape_ok("mio_gemm_skinny_w8_ok", M, N, K, act, err) && skinny_w8_advised(M, N, K, act)) ? 1 : 0;
-}
-
-// ---- launches ----------------------------------------------------------------------------------------------------------
+// ---- the quantiser's launch ----------------------------------------------------------------------------------------
 extern "C" int mio_weight_quant_w8(const void* w, int64_t ldw, void* w8, int64_t ldw8, float* scale, int32_t N, int32_t K,
                                    int32_t dtype, void* stream) {
   const std::string who = "mio_weight_quant_w8";
@@ -264,46 +202,40 @@ extern "C" int mio_weight_quant_w8(const void* w, int64_t ldw, void* w8, int64_t
   return 0;
 }
 
+#define SKINNY_KERNELS(T, GLU)                                                                         \
+  {{gemm_skinny_w8_kernel<T, 1, GLU>, gemm_skinny_w8_kernel<T, 2, GLU>, gemm_skinny_w8_kernel<T, 3, GLU>, \
+    gemm_skinny_w8_kernel<T, 4, GLU>},                                                                 \
+   gemm_skinny_reduce_kernel<T, GLU, true>}
+static const SkinnyKernelTable KERNELS = {{SKINNY_KERNELS(__bf16, true), SKINNY_KERNELS(__bf16, false)},
+                                          {SKINNY_KERNELS(_Float16, true), SKINNY_KERNELS(_Float16, false)}};
+#undef SKINNY_KERNELS
+
+// ---- the C ABI of the GEMM: argument marshalling over gemm_skinny_common.h's host side -----------------------------
+extern "C" int mio_gemm_skinny_w8_splits(int64_t M, int32_t N, int32_t K, int32_t act) {
+  return skinny_query_splits(FORM, "mio_gemm_skinny_w8_splits", M, N, K, act);
+}
+
+extern "C" size_t mio_gemm_skinny_w8_workspace_bytes(int64_t M, int32_t N, int32_t K, int32_t act) {
+  return skinny_query_workspace_bytes(FORM, "mio_gemm_skinny_w8_workspace_bytes", M, N, K, act);
+}
+
+extern "C" int mio_gemm_skinny_w8_slice(int64_t M, int32_t N, int32_t K, int32_t act, int32_t slice, int32_t* k_begin,
+                                        int32_t* k_end) {
+  return skinny_query_slice(FORM, "mio_gemm_skinny_w8_slice", M, N, K, act, slice, k_begin, k_end);
+}
+
+extern "C" int mio_gemm_skinny_w8_chunk_k(int32_t act) { return skinny_query_chunk_k(FORM, "mio_gemm_skinny_w8_chunk_k", act); }
+
+extern "C" int mio_gemm_skinny_w8_depth(int32_t act) { return skinny_query_depth(FORM, "mio_gemm_skinny_w8_depth", act); }
+
+extern "C" int mio_gemm_skinny_w8_ok(int64_t M, int32_t N, int32_t K, int32_t act) {
+  return skinny_query_ok(FORM, "mio_gemm_skinny_w8_ok", M, N, K, act);
+}
+
 extern "C" int mio_gemm_skinny_w8(const void* x, const void* w8, const float* w_scale, const void* bias, const void* w8_gate,
                                   const float* w_scale_gate, const void* bias_gate, const void* residual, void* y, void* workspace,
                                   int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
                                   int32_t dtype, void* stream) {
-  const char* who = "mio_gemm_skinny_w8";
-#define SKW8_CHECK(cond, text) MIO_CHECK(cond, std::string(who) + (text))
-  std::string err;
-  if (!skinny_w8_shape_ok(who, M, N, K, act, err)) return mio_fail(err);
-  SKW8_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, ": dtype must be bf16 or fp16 (the activations'; the weights are e4m3fn bytes)");
-  const bool glu = act == MIO_ACT_SWIGLU;
-  SKW8_CHECK(glu == (w8_gate != nullptr) && glu == (w_scale_gate != nullptr),
-             ": w8_gate and w_scale_gate are required together iff act == SWIGLU");
-  SKW8_CHECK(glu || bias_gate == nullptr, ": bias_gate belongs to act == SWIGLU");
-  SKW8_CHECK(ldw % 16 == 0, ": ldw must be a multiple of 16 bytes");
-  SKW8_CHECK(ldw >= K, ": ldw smaller than K");
-  SKW8_CHECK(ldx % 8 == 0 && ldy % 8 == 0 && (!residual || ldr % 8 == 0), ": ldx, ldy, ldr must be multiples of 8 elements");
-  SKW8_CHECK(ldx >= K && ldy >= N && (!residual || ldr >= N), ": row stride smaller than row length");
-  SKW8_CHECK(w8 && w_scale && (M == 0 || (x && y)), ": x, w8, w_scale, y must be non-null");
-  SKW8_CHECK(mio_aligned16(x) && mio_aligned16(w8) && mio_aligned16(y) && mio_aligned16(w8_gate) && mio_aligned16(residual) &&
-                 mio_aligned16(bias) && mio_aligned16(bias_gate) && mio_aligned16(workspace) && mio_aligned16(w_scale) &&
-                 mio_aligned16(w_scale_gate),
-             ": pointers must be 16-byte aligned");
-  const SkinnyW8Plan pl = skinny_w8_plan(M, N, K, act);
-  if (M == 0 || N == 0) return 0;
-  SKW8_CHECK(pl.nsplit == 1 || workspace != nullptr,
-             ": workspace required (mio_gemm_skinny_w8_workspace_bytes) when the plan splits K");
-#undef SKW8_CHECK
-  SkinnyDev p;
-  p.x = x; p.w = w8; p.wg = w8_gate; p.bias = bias; p.bias_g = bias_gate; p.res = residual; p.y = y;
-  p.ws = pl.nsplit > 1 ? (float*)workspace : nullptr;
-  p.scale = w_scale; p.scale_g = w_scale_gate;
-  p.ldx = ldx; p.ldw = ldw; p.ldy = ldy; p.ldr = ldr;
-  p.M = (int)M; p.N = N; p.K = K; p.act = act; p.nsplit = pl.nsplit; p.steps = pl.steps;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MIO_BF16) {
-    if (glu) skinny_w8_launch<__bf16, true>(p, pl, st); else skinny_w8_launch<__bf16, false>(p, pl, st);
-  } else {
-    if (glu) skinny_w8_launch<_Float16, true>(p, pl, st); else skinny_w8_launch<_Float16, false>(p, pl, st);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string("mio_gemm_skinny_w8 launch: ") + hipGetErrorString(e));
-  return 0;
+  return skinny_run(FORM, KERNELS, x, w8, w_scale, bias, w8_gate, w_scale_gate, bias_gate, residual, y, workspace, M, N, K, ldx, ldw,
+                    ldy, ldr, act, dtype, stream);
 }

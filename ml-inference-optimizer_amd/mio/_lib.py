@@ -285,31 +285,20 @@ def _load() -> C.CDLL:
     lib.mio_attn_merge.restype = i32
     lib.mio_gemm_bias_act.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
     lib.mio_gemm_bias_act.restype = i32
-    lib.mio_gemm_skinny_workspace_bytes.argtypes = [i64, i32, i32, i32]
-    lib.mio_gemm_skinny_workspace_bytes.restype = C.c_size_t
-    lib.mio_gemm_skinny_splits.argtypes = [i64, i32, i32, i32]
-    lib.mio_gemm_skinny_splits.restype = i32
-    lib.mio_gemm_skinny_slice.argtypes = [i64, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
-    lib.mio_gemm_skinny_slice.restype = i32
-    lib.mio_gemm_skinny_chunk_k.argtypes = [i32]
-    lib.mio_gemm_skinny_chunk_k.restype = i32
-    lib.mio_gemm_skinny_ok.argtypes = [i64, i32, i32, i32]
-    lib.mio_gemm_skinny_ok.restype = i32
+    # the decode-step GEMM's host queries, one family per weight form: the same signatures under both names
+    for fam in ("mio_gemm_skinny", "mio_gemm_skinny_w8"):
+        for query, restype in (("workspace_bytes", C.c_size_t), ("splits", i32), ("ok", i32)):
+            getattr(lib, f"{fam}_{query}").argtypes = [i64, i32, i32, i32]
+            getattr(lib, f"{fam}_{query}").restype = restype
+        getattr(lib, f"{fam}_slice").argtypes = [i64, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+        getattr(lib, f"{fam}_slice").restype = i32
+    for name in ("mio_gemm_skinny_chunk_k", "mio_gemm_skinny_w8_chunk_k", "mio_gemm_skinny_w8_depth"):
+        getattr(lib, name).argtypes = [i32]
+        getattr(lib, name).restype = i32
     lib.mio_gemm_skinny.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
     lib.mio_gemm_skinny.restype = i32
     lib.mio_weight_quant_w8.argtypes = [vp, i64, vp, i64, vp, i32, i32, i32, vp]
     lib.mio_weight_quant_w8.restype = i32
-    lib.mio_gemm_skinny_w8_workspace_bytes.argtypes = [i64, i32, i32, i32]
-    lib.mio_gemm_skinny_w8_workspace_bytes.restype = C.c_size_t
-    lib.mio_gemm_skinny_w8_splits.argtypes = [i64, i32, i32, i32]
-    lib.mio_gemm_skinny_w8_splits.restype = i32
-    lib.mio_gemm_skinny_w8_slice.argtypes = [i64, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
-    lib.mio_gemm_skinny_w8_slice.restype = i32
-    for name in ("mio_gemm_skinny_w8_chunk_k", "mio_gemm_skinny_w8_depth"):
-        getattr(lib, name).argtypes = [i32]
-        getattr(lib, name).restype = i32
-    lib.mio_gemm_skinny_w8_ok.argtypes = [i64, i32, i32, i32]
-    lib.mio_gemm_skinny_w8_ok.restype = i32
     lib.mio_gemm_skinny_w8.argtypes = [vp] * 10 + [i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
     lib.mio_gemm_skinny_w8.restype = i32
     lib.mio_fused_mlp_workspace_bytes.argtypes = [i64, i32, i32, i32]

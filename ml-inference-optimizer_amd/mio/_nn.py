@@ -170,23 +170,51 @@ class ResidualStream:
         return self.blocked.view(mp // 256, d // 32, 256, 32).permute(0, 2, 1, 3).reshape(mp, d)[:B * S].reshape(B, S, d)
 
 
+def decode_route(calls, skinny: bool, skinny_w8: bool) -> Optional[str]:
+    """The decode-step route of the GEMMs calls = [(M, N, K, activation), ...] that run as a group, under the modules' decode_gemm
+    (skinny) and decode_gemm_fp8 (skinny_w8) options: "w8" (ops.gemm_skinny_w8 on the weights' FP8 copies) if that option is on
+    and ops.gemm_skinny_w8_ok advises every call, else "skinny" (ops.gemm_skinny) if that one is on and ops.gemm_skinny_ok advises
+    every call, else None.  An option that is off asks nothing."""
+    if skinny_w8 and all(ops.gemm_skinny_w8_ok(*c) for c in calls):
+        return "w8"
+    if skinny and all(ops.gemm_skinny_ok(*c) for c in calls):
+        return "skinny"
+    return None
+
+
+def routed_linear(route: Optional[str], x: torch.Tensor, lin: nn.Linear, cache: "CastCache", dtype: torch.dtype,
+                  activation: str = "none", gate: Optional[nn.Linear] = None, rows: Optional[int] = None,
+                  residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """lin(x) (+ activation; gate: the SwiGLU gate projection; + residual) of a row-major x on the route decode_route decided,
+    None being ops.gemm_bias_act on the row-major weight.  rows: only the first `rows` output features of lin (the query rows
+    of a fused qkv projection).  "w8" reads CastCache.get_w8's copies (a sliced projection is quantised whole, once: rows are
+    independent), the others the 16-bit copies."""
+    bias = cache.get(lin.bias, dtype)
+    bias = None if bias is None else bias[:rows].contiguous()
+    gb = None if gate is None else cache.get(gate.bias, dtype)
+    if route == "w8":
+        w8, scale = cache.get_w8(lin.weight, dtype)
+        g8, gs = (None, None) if gate is None else cache.get_w8(gate.weight, dtype)
+        return ops.gemm_skinny_w8(x, w8[:rows], scale[:rows], bias, activation, g8, gs, gb, residual)
+    gemm = ops.gemm_skinny if route == "skinny" else ops.gemm_bias_act
+    gw = None if gate is None else cache.get(gate.weight, dtype)
+    return gemm(x, cache.get(lin.weight, dtype)[:rows], bias, activation, gw, gb, residual)
+
+
 def linear(x: torch.Tensor, lin: nn.Linear, cache: CastCache, dtype: torch.dtype, activation: str = "none",
            residual: Optional[torch.Tensor] = None, col_scale=None, x_blocked_shape=None, skinny: bool = False,
            skinny_w8: bool = False) -> torch.Tensor:
     """F.linear(x, W, b) (+ activation, + residual) on the MFMA GEMM.  At sizes that run the 256x256-tile kernels the
     weight is handed over in the blocked layout (repacked once per parameter version, cached next to the cast copy).
-    skinny (the modules' decode_gemm option): a row-major x without a column scale goes to the decode-step GEMM
-    (ops.gemm_skinny, the same row-major weight copy) where ops.gemm_skinny_ok advises it.
-    skinny_w8 (the modules' decode_gemm_fp8 option): the same calls go to the decode-step GEMM on the weight's FP8 copy
-    (ops.gemm_skinny_w8, CastCache.get_w8) where ops.gemm_skinny_w8_ok advises it, and fall through to the above where not."""
-    w = cache.get(lin.weight, dtype)
-    N, K = w.shape
+    skinny / skinny_w8 (the modules' decode_gemm / decode_gemm_fp8 options): a row-major x without a column scale goes to the
+    decode-step GEMM decode_route picks, if it picks one."""
+    N, K = lin.weight.shape
     M = x.numel() // K if x_blocked_shape is None else int(math.prod(x_blocked_shape[:-1]))
-    if skinny_w8 and x_blocked_shape is None and col_scale is None and ops.gemm_skinny_w8_ok(M, N, K, activation):
-        w8, scale = cache.get_w8(lin.weight, dtype)
-        return ops.gemm_skinny_w8(x, w8, scale, cache.get(lin.bias, dtype), activation, residual=residual)
-    if skinny and x_blocked_shape is None and col_scale is None and ops.gemm_skinny_ok(M, N, K, activation):
-        return ops.gemm_skinny(x, w, cache.get(lin.bias, dtype), activation, residual=residual)
+    if x_blocked_shape is None and col_scale is None:
+        route = decode_route([(M, N, K, activation)], skinny, skinny_w8)
+        if route is not None:
+            return routed_linear(route, x, lin, cache, dtype, activation, residual=residual)
+    w = cache.get(lin.weight, dtype)
     wb = cache.get_blocked(lin.weight, dtype) if (K % 32 == 0 and ops.blocked_weight_ok(M, N, K, activation)) else None
     return ops.gemm_bias_act(x, w, cache.get(lin.bias, dtype), activation, residual=residual, w_blocked=wb,
                              col_scale=col_scale, x_blocked_shape=x_blocked_shape)

@@ -19,8 +19,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops
-from ..._nn import (CastCache, ResidualStream, apply_norm, as_dtype, attention_plan, compute_dtype, folded_linear, linear,
-                    prenorm_linear, residual_linear, stream_preconditions)
+from ..._nn import (CastCache, ResidualStream, apply_norm, as_dtype, attention_plan, compute_dtype, decode_route, folded_linear,
+                    linear, prenorm_linear, residual_linear, routed_linear, stream_preconditions)
 
 
 @dataclass
@@ -366,15 +366,8 @@ class FlashSelfAttention(_AttentionBase):
             if pre_norm is not None:
                 x = apply_norm(x, pre_norm, c, dt)
             # only the query slice of the fused projection is needed on the paged path (:572-621)
-            wq = c.get(self.qkv_proj.weight, dt)[:q_dim]
-            bq = c.get(self.qkv_proj.bias, dt)
-            bq = None if bq is None else bq[:q_dim].contiguous()
-            if cfg.decode_gemm_fp8 and ops.gemm_skinny_w8_ok(B * S, q_dim, wq.shape[1]):
-                w8, scale = c.get_w8(self.qkv_proj.weight, dt)  # (the whole projection is quantised once; rows are independent)
-                q2d = ops.gemm_skinny_w8(x, w8[:q_dim], scale[:q_dim], bq)
-            else:
-                gemm = ops.gemm_skinny if cfg.decode_gemm and ops.gemm_skinny_ok(B * S, q_dim, wq.shape[1]) else ops.gemm_bias_act
-                q2d = gemm(x, wq, bq)
+            route = decode_route([(B * S, q_dim, self.qkv_proj.in_features, "none")], cfg.decode_gemm, cfg.decode_gemm_fp8)
+            q2d = routed_linear(route, x, self.qkv_proj, c, dt, rows=q_dim)
             return as_dtype(self._paged(q2d, B, S, dt, kwargs, "FlashSelfAttention", r), in_dtype)
         _refuse(cfg, self.training)
         # [B,S,q_dim+2*kv_dim]; q / k / v are strided views of it, K its columns [q_dim, q_dim + kv_dim)

@@ -16,8 +16,8 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ..._nn import (CastCache, ResidualStream, apply_norm, as_dtype, compute_dtype, folded_linear, residual_linear,
-                    stream_preconditions)
+from ..._nn import (CastCache, ResidualStream, apply_norm, as_dtype, compute_dtype, decode_route, folded_linear, residual_linear,
+                    routed_linear, stream_preconditions)
 
 
 @dataclass
@@ -65,10 +65,6 @@ class FusedMLP(nn.Module):
     def _gate(self, dtype):
         return None, None
 
-    def _gate_w8(self, dtype):
-        """The gate weight as weight-only FP8, (w8, scale) (CastCache.get_w8); none without a gate."""
-        return None, None
-
     def stream_ok(self, B: int, S: int, dtype: torch.dtype, pre_norm: Optional[nn.Module]) -> bool:
         """True iff forward(...) can take (and return) the residual stream as a ResidualStream at this size (ops.gemm_ln_ok on
         both GEMMs; tanh-GELU or SwiGLU)."""
@@ -114,23 +110,15 @@ class FusedMLP(nn.Module):
         in_dtype = hidden_states.dtype
         dt = compute_dtype(self.config.precision, hidden_states)
         x, r, c = as_dtype(hidden_states, dt), as_dtype(residual, dt), self._cast
-        gw, gb = self._gate(dt)
         M, d, I = x.numel() // x.shape[-1], x.shape[-1], self.fc1.weight.shape[0]
-        if (self.config.decode_gemm_fp8 and ops.gemm_skinny_w8_ok(M, I, d, act)
-                and ops.gemm_skinny_w8_ok(M, self.fc2.weight.shape[0], I)):
+        route = decode_route([(M, I, d, act), (M, self.fc2.weight.shape[0], I, "none")], self.config.decode_gemm,
+                             self.config.decode_gemm_fp8)
+        if route is not None:
             if pre_norm is not None:
                 x = apply_norm(x, pre_norm, c, dt)
-            (w1, s1), (w2, s2) = c.get_w8(self.fc1.weight, dt), c.get_w8(self.fc2.weight, dt)
-            g8, gs = self._gate_w8(dt)
-            h = ops.gemm_skinny_w8(x, w1, s1, c.get(self.fc1.bias, dt), act, g8, gs, gb)
-            out = ops.gemm_skinny_w8(h, w2, s2, c.get(self.fc2.bias, dt), residual=r)
-            return as_dtype(out, in_dtype)
-        if self.config.decode_gemm and ops.gemm_skinny_ok(M, I, d, act) and ops.gemm_skinny_ok(M, self.fc2.weight.shape[0], I):
-            if pre_norm is not None:
-                x = apply_norm(x, pre_norm, c, dt)
-            h = ops.gemm_skinny(x, c.get(self.fc1.weight, dt), c.get(self.fc1.bias, dt), act, gw, gb)
-            out = ops.gemm_skinny(h, c.get(self.fc2.weight, dt), c.get(self.fc2.bias, dt), residual=r)
-            return as_dtype(out, in_dtype)
+            h = routed_linear(route, x, self.fc1, c, dt, act, gate=self.fc1_gate if act == "swiglu" else None)
+            return as_dtype(routed_linear(route, h, self.fc2, c, dt, residual=r), in_dtype)
+        gw, gb = self._gate(dt)
         b1 = b2 = None  # blocked weight copies, when this shape runs the kernels that take them
         if ops.fused_mlp_blocked_weight_ok(M, d, I, act):
             if gw is None:
@@ -175,9 +163,6 @@ class FusedMLPSwiGLU(FusedMLP):
 
     def _gate(self, dtype):
         return self._cast.get(self.fc1_gate.weight, dtype), self._cast.get(self.fc1_gate.bias, dtype)
-
-    def _gate_w8(self, dtype):
-        return self._cast.get_w8(self.fc1_gate.weight, dtype)
 
 
 class FusedMLPReLU(FusedMLP):

@@ -701,85 +701,99 @@ def gemm_bias_act(x, w, bias=None, activation: str = "none", w_gate=None, bias_g
     return out
 
 
-# ---- the decode-step GEMM (mio_gemm_skinny: 1 <= M <= 64 rows, the weight streamed once from its row-major copy) -----------------
+# ---- the decode-step GEMM (1 <= M <= 64 rows, the weight streamed once from its row-major copy): mio_gemm_skinny on 16-bit weights,
+# mio_gemm_skinny_w8 on e4m3fn weight bytes with one fp32 scale per output column ------------------------------------------------
+_W8 = torch.float8_e4m3fn
+
+
+def _skinny_ok(name: str, M: int, N: int, K: int, activation: str) -> bool:
+    return activation in _ACT and bool(getattr(lib, f"mio_{name}_ok")(M, N, K, _ACT[activation]))
+
+
+def _skinny_splits(name: str, M: int, N: int, K: int, activation: str) -> int:
+    if activation not in _ACT:
+        raise ValueError(f"Unsupported activation function: {activation}")
+    n = getattr(lib, f"mio_{name}_splits")(M, N, K, _ACT[activation])
+    if n < 0:
+        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def _skinny(fn, ws_bytes, tall: str, x, N: int, K: int, ldw: int, w_ptrs, g_ptrs, bias, activation: str, bias_gate, residual, out):
+    """What gemm_skinny and gemm_skinny_w8 do around their weight operands, which the caller has checked.  fn / ws_bytes: the
+    C launch and its workspace query; ldw: the row stride of the weight [N, K] (and of the gate); w_ptrs / g_ptrs: the addresses
+    of the weight and of the gate with what goes with them, as fn takes them between x and bias and between bias and bias_gate."""
+    if activation not in _ACT:
+        raise ValueError(f"Unsupported activation function: {activation}")
+    act = _ACT[activation]
+    dt = _dtype_id(x)
+    _vec_ok(bias, N, x.dtype, "bias")
+    if act == _lib.ACT_SWIGLU:
+        _vec_ok(bias_gate, N, x.dtype, "bias_gate")
+    else:
+        bias_gate = None
+    lead, x2 = tuple(x.shape[:-1]), _rows16(x.reshape(-1, K))
+    M = x2.shape[0]
+    if M > 64:  # (fn is mio_<the op's name>)
+        raise ValueError(f"{fn.__name__[4:]} takes at most 64 rows, got {M} ({tall})")
+    _res_ok(residual, M * N, x.dtype)
+    r2 = None if residual is None else _rows16(residual.reshape(-1, N))
+    if out is None:  # (rows of N % 8 != 0 columns: a view of rows padded to the stride the kernel's 8-byte stores need)
+        out = torch.empty(*lead, (N + 7) // 8 * 8, dtype=x.dtype, device=x.device)[..., :N]
+    y2 = out.view(-1, N)
+    nbytes = ws_bytes(M, N, K, act)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    check(fn(x2.data_ptr(), *w_ptrs, _ptr(bias), *g_ptrs, _ptr(bias_gate), _ptr(r2), y2.data_ptr(), _ptr(ws), M, N, K, x2.stride(0),
+             ldw, y2.stride(0), 0 if r2 is None else r2.stride(0), act, dt, _stream()))
+    return out
+
+
 def gemm_skinny_ok(M: int, N: int, K: int, activation: str = "none") -> bool:
     """True iff gemm_skinny is legal at this shape AND the measured better choice over gemm_bias_act (profiles/skinny_gemm.md).
     Advice for the module layer: gemm_skinny itself runs every legal shape."""
-    return activation in _ACT and bool(lib.mio_gemm_skinny_ok(M, N, K, _ACT[activation]))
+    return _skinny_ok("gemm_skinny", M, N, K, activation)
 
 
 def gemm_skinny_splits(M: int, N: int, K: int, activation: str = "none") -> int:
     """The slices of K a gemm_skinny call of this shape runs (1: one launch, no workspace).  Host-only; ValueError where the
     call would be refused."""
-    if activation not in _ACT:
-        raise ValueError(f"Unsupported activation function: {activation}")
-    n = lib.mio_gemm_skinny_splits(M, N, K, _ACT[activation])
-    if n < 0:
-        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
-    return n
+    return _skinny_splits("gemm_skinny", M, N, K, activation)
 
 
 def gemm_skinny(x, w, bias=None, activation: str = "none", w_gate=None, bias_gate=None, residual=None, out=None):
     """gemm_bias_act for at most 64 rows (x [..., K] with prod(...) <= 64, w [N, K], any N): y = act(x @ w^T + bias) (+ residual)
     on the weight-streaming kernel.  Allocates the split workspace only when the plan splits K."""
     _need_cuda(x, w)
-    if activation not in _ACT:
-        raise ValueError(f"Unsupported activation function: {activation}")
-    act = _ACT[activation]
-    dt = _dtype_id(x)
     if w.dtype != x.dtype:
         raise ValueError("x and w must have the same dtype")
     if w.shape[1] != x.shape[-1]:
         raise ValueError(f"weight shape {tuple(w.shape)} does not match input features {x.shape[-1]}")
-    N, K = w.shape
-    _vec_ok(bias, N, x.dtype, "bias")
-    if act == _lib.ACT_SWIGLU:
-        _vec_ok(bias_gate, N, x.dtype, "bias_gate")
+    w2, g2 = _rows16(w), None
+    if activation == "swiglu":
         if w_gate is None:
             raise ValueError("SwiGLU activation requires gate weights")
         if w_gate.shape != w.shape or w_gate.dtype != w.dtype:
             raise ValueError("w_gate must have w's shape and dtype")
         _need_cuda(w_gate)
-    lead, x2 = tuple(x.shape[:-1]), _rows16(x.reshape(-1, K))
-    M = x2.shape[0]
-    if M > 64:
-        raise ValueError(f"gemm_skinny takes at most 64 rows, got {M} (gemm_bias_act runs taller calls)")
-    _res_ok(residual, M * N, x.dtype)
-    r2 = None if residual is None else _rows16(residual.reshape(-1, N))
-    w2 = _rows16(w)
-    g2, bias_gate = (_rows16(w_gate), bias_gate) if act == _lib.ACT_SWIGLU else (None, None)
-    if g2 is not None and g2.stride(0) != w2.stride(0):
-        g2, w2 = g2.contiguous(), w2.contiguous()
-    if out is None:  # (rows of N % 8 != 0 columns: a view of rows padded to the stride the kernel's 8-byte stores need)
-        out = torch.empty(*lead, (N + 7) // 8 * 8, dtype=x.dtype, device=x.device)[..., :N]
-    y2 = out.view(-1, N)
-    nbytes = lib.mio_gemm_skinny_workspace_bytes(M, N, K, act)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
-    check(lib.mio_gemm_skinny(x2.data_ptr(), w2.data_ptr(), _ptr(bias), _ptr(g2), _ptr(bias_gate), _ptr(r2), y2.data_ptr(),
-                              _ptr(ws), M, N, K, x2.stride(0), w2.stride(0), y2.stride(0), 0 if r2 is None else r2.stride(0), act, dt, _stream()))
-    return out
-
-
-# ---- the decode-step GEMM on weight-only FP8 (mio_gemm_skinny_w8: e4m3fn weight bytes, one fp32 scale per output column) ---------
-_W8 = torch.float8_e4m3fn
+        g2 = _rows16(w_gate)
+        if g2.stride(0) != w2.stride(0):
+            g2, w2 = g2.contiguous(), w2.contiguous()
+    N, K = w2.shape
+    return _skinny(lib.mio_gemm_skinny, lib.mio_gemm_skinny_workspace_bytes, "gemm_bias_act runs taller calls", x, N, K, w2.stride(0),
+                   (w2.data_ptr(),), (_ptr(g2),), bias, activation, bias_gate, residual, out)
 
 
 def gemm_skinny_w8_ok(M: int, N: int, K: int, activation: str = "none") -> bool:
     """True iff gemm_skinny_w8 is legal at this shape AND measured at most 0.9 x the time of the faster of gemm_skinny and
     gemm_bias_act on the 16-bit weight (profiles/skinny_gemm_w8.md).  Advice for the module layer: gemm_skinny_w8 itself runs
     every legal shape."""
-    return activation in _ACT and bool(lib.mio_gemm_skinny_w8_ok(M, N, K, _ACT[activation]))
+    return _skinny_ok("gemm_skinny_w8", M, N, K, activation)
 
 
 def gemm_skinny_w8_splits(M: int, N: int, K: int, activation: str = "none") -> int:
     """The slices of K a gemm_skinny_w8 call of this shape runs (1: one launch, no workspace).  Host-only; ValueError where the
     call would be refused."""
-    if activation not in _ACT:
-        raise ValueError(f"Unsupported activation function: {activation}")
-    n = lib.mio_gemm_skinny_w8_splits(M, N, K, _ACT[activation])
-    if n < 0:
-        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
-    return n
+    return _skinny_splits("gemm_skinny_w8", M, N, K, activation)
 
 
 def quantize_weight_w8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -833,10 +847,6 @@ def gemm_skinny_w8(x, w8, w_scale, bias=None, activation: str = "none", w8_gate=
     w_scale_gate / bias_gate.  Row slices of w8 and w_scale are legal operands.  Allocates the split workspace only when the plan
     splits K."""
     _need_cuda(x)
-    if activation not in _ACT:
-        raise ValueError(f"Unsupported activation function: {activation}")
-    act = _ACT[activation]
-    dt = _dtype_id(x)
     w2 = _w8_ok(w8, "w8")
     if w2.shape[1] != x.shape[-1]:
         raise ValueError(f"weight shape {tuple(w2.shape)} does not match input features {x.shape[-1]}")
@@ -844,10 +854,8 @@ def gemm_skinny_w8(x, w8, w_scale, bias=None, activation: str = "none", w8_gate=
     if K % 16 != 0:
         raise ValueError(f"gemm_skinny_w8: K must be a multiple of 16, got {K}")
     s2 = _w8_scale(w_scale, N, "w_scale")
-    _vec_ok(bias, N, x.dtype, "bias")
     g2 = sg2 = None
-    if act == _lib.ACT_SWIGLU:
-        _vec_ok(bias_gate, N, x.dtype, "bias_gate")
+    if activation == "swiglu":
         if w8_gate is None or w_scale_gate is None:
             raise ValueError("SwiGLU activation requires gate weights and their scales")
         g2 = _w8_ok(w8_gate, "w8_gate")
@@ -856,23 +864,9 @@ def gemm_skinny_w8(x, w8, w_scale, bias=None, activation: str = "none", w8_gate=
         sg2 = _w8_scale(w_scale_gate, N, "w_scale_gate")
         if g2.stride(0) != w2.stride(0):
             g2, w2 = g2.contiguous(), w2.contiguous()
-    else:
-        bias_gate = None
-    lead, x2 = tuple(x.shape[:-1]), _rows16(x.reshape(-1, K))
-    M = x2.shape[0]
-    if M > 64:
-        raise ValueError(f"gemm_skinny_w8 takes at most 64 rows, got {M} (fp8 weights are read by the decode-step kernel only)")
-    _res_ok(residual, M * N, x.dtype)
-    r2 = None if residual is None else _rows16(residual.reshape(-1, N))
-    if out is None:  # (rows of N % 8 != 0 columns: a view of rows padded to the stride the kernel's 8-byte stores need)
-        out = torch.empty(*lead, (N + 7) // 8 * 8, dtype=x.dtype, device=x.device)[..., :N]
-    y2 = out.view(-1, N)
-    nbytes = lib.mio_gemm_skinny_w8_workspace_bytes(M, N, K, act)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
-    check(lib.mio_gemm_skinny_w8(x2.data_ptr(), w2.data_ptr(), s2.data_ptr(), _ptr(bias), _ptr(g2), _ptr(sg2), _ptr(bias_gate),
-                                 _ptr(r2), y2.data_ptr(), _ptr(ws), M, N, K, x2.stride(0), w2.stride(0), y2.stride(0),
-                                 0 if r2 is None else r2.stride(0), act, dt, _stream()))
-    return out
+    return _skinny(lib.mio_gemm_skinny_w8, lib.mio_gemm_skinny_w8_workspace_bytes, "fp8 weights are read by the decode-step kernel only",
+                   x, N, K, w2.stride(0), (w2.data_ptr(), s2.data_ptr()), (_ptr(g2), _ptr(sg2)), bias, activation, bias_gate,
+                   residual, out)
 
 
 # ---- LayerNorm folded into the GEMMs on either side of it (mio_gemm_ln_bw; reference fused_layernorm_qkv.py:37-420) ------------

@@ -1,7 +1,7 @@
 """The shapes of the GPU tests of the decode-step GEMM on weight-only FP8 (tests/test_gpu_gemm_skinny_w8.py), as plain tables: a
 helper module, not a conftest, and free of torch so that the CPU suite can read it.
 
-Which seams of csrc/gemm_skinny_w8.hip a shape reaches is decided by the plan (gemm_skinny_w8_plan.h): the row fragments MF =
+Which seams of csrc/gemm_skinny_w8.hip a shape reaches is decided by the plan (gemm_skinny_plan.h, SKINNY_W8): the row fragments MF =
 ceil(M / 16), the slices of K in whole 64-k steps (mio_gemm_skinny_w8_splits / _slice: at least 16 M k each) and, inside a slice,
 the chunks of the kernel's loop (mio_gemm_skinny_w8_chunk_k) over a ring of mio_gemm_skinny_w8_depth register sets.  The first
 depth - 1 chunks of a slice fill the ring before the loop; the loop body is unrolled depth times, so the refill of every set, the
