@@ -7,6 +7,8 @@ The LayerNorm-fold routes are judged against _gemm_check.reference_fold, built f
 statistics handed to the launch, the folded weights and biases).  The cases beyond 32-bit offsets (an output over
 4 GiB, an x over 2 GiB, row strides at and past the per-tile offset limit) check 16-row blocks on both sides of every 2^31- and
 2^32-byte boundary and the last, ragged, row tile in fp64 on the GPU."""
+from types import SimpleNamespace
+
 import pytest
 import torch
 
@@ -50,9 +52,21 @@ def _operands(dtype, M, N, K, act="none", bias=True, res=False, seed=0, ldx=None
     return x, w, b, r, wg, bg
 
 
-def _gemm(dtype, route, M, N, K, act="none", bias=True, res=False, ldx=None, guard=False, blocked_w=False, blocked_x=False,
-          col_scale=None, bias_gate=True, seed=0, what=""):
-    """One gemm_bias_act call: route asserted, the whole output checked."""
+class Parts:
+    """A case in three callables, so that tests/test_gpu_repeatable.py can repeat the launch alone:
+    build(dtype) -> p, a SimpleNamespace of the operands (route asserted by the host query); launch(p) -> what the call returns,
+    reading its operands from p only; judge(p, ret): the checks.  Calling the case runs the three in order."""
+
+    def __init__(self, build, launch, judge):
+        self.build, self.launch, self.judge = build, launch, judge
+
+    def __call__(self, dtype):
+        p = self.build(dtype)
+        self.judge(p, self.launch(p))
+
+
+def _gemm_build(dtype, route, M, N, K, act="none", bias=True, res=False, ldx=None, guard=False, blocked_w=False, blocked_x=False,
+                col_scale=None, bias_gate=True, seed=0, what=""):
     ops = _ops()
     gate = act == "swiglu"
     x, w, b, r, wg, bg = _operands(dtype, M, N, K, act, bias, res, seed, ldx, gate, bias_gate)
@@ -73,24 +87,42 @@ def _gemm(dtype, route, M, N, K, act="none", bias=True, res=False, ldx=None, gua
     if blocked_x:
         xin = ops.block_weight(x)  # the blocked activation layout is the blocked weight layout with m in the place of n
         kw["x_blocked_shape"] = (M, K)
-    assert ops.gemm_route(xin, w, b, act, **kw) == route, what
-    y = ops.gemm_bias_act(xin, w, b, act, **kw)
-    ref = gc.reference(x, w, b, act, wg, bg, r, col_scale, device=DEV)
-    gc.check(y, ref, dtype, route, guard=buf, fill=FILL, what=what)
+    p = SimpleNamespace(dtype=dtype, route=route, shape=(M, N, K), act=act, x=x, xin=xin, w=w, b=b, r=r, wg=wg, bg=bg, kw=kw,
+                        buf=buf, col_scale=col_scale, what=what)
+    assert _gemm_route_of(p) == route, what
+    return p
+
+
+def _gemm_route_of(p):
+    return _ops().gemm_route(p.xin, p.w, p.b, p.act, **p.kw)
+
+
+def _gemm_launch(p):
+    return _ops().gemm_bias_act(p.xin, p.w, p.b, p.act, **p.kw)
+
+
+def _gemm_judge(p, y):
+    ref = gc.reference(p.x, p.w, p.b, p.act, p.wg, p.bg, p.r, p.col_scale, device=DEV)
+    gc.check(y, ref, p.dtype, p.route, guard=p.buf, fill=FILL, what=p.what)
+
+
+def _gemm_parts(route, M, N, K, act="none", **kw):
+    """One gemm_bias_act call: route asserted, the whole output checked."""
+    return Parts(lambda dt: _gemm_build(dt, route, M, N, K, act, **kw), _gemm_launch, _gemm_judge)
 
 
 # ---- the cases, per route: name -> callable(dtype) ---------------------------------------------------------------------
 def _t128():
     c = {
-        "m1_n8_k8": lambda dt: _gemm(dt, "t128", 1, 8, 8, res=True),
-        "m37_n72_k4104_tail": lambda dt: _gemm(dt, "t128", 37, 72, 4104, bias=False),
-        "x_stride_k_plus_8": lambda dt: _gemm(dt, "t128", 37, 72, 40, "gelu", ldx=48, res=True),
-        "guarded_out": lambda dt: _gemm(dt, "t128", 37, 72, 40, "silu", guard=True, res=True),
-        "m300_n512_k1024": lambda dt: _gemm(dt, "t128", 300, 512, 1024, "gelu", res=True),
+        "m1_n8_k8": _gemm_parts("t128", 1, 8, 8, res=True),
+        "m37_n72_k4104_tail": _gemm_parts("t128", 37, 72, 4104, bias=False),
+        "x_stride_k_plus_8": _gemm_parts("t128", 37, 72, 40, "gelu", ldx=48, res=True),
+        "guarded_out": _gemm_parts("t128", 37, 72, 40, "silu", guard=True, res=True),
+        "m300_n512_k1024": _gemm_parts("t128", 300, 512, 1024, "gelu", res=True),
     }
     for i, a in enumerate(ACTS):
-        c[f"m37_n72_k40_{a}_bias"] = lambda dt, a=a: _gemm(dt, "t128", 37, 72, 40, a)
-        c[f"m37_n8_k8_{a}_res_nobias"] = lambda dt, a=a: _gemm(dt, "t128", 37, 8, 8, a, bias=False, res=True)
+        c[f"m37_n72_k40_{a}_bias"] = _gemm_parts("t128", 37, 72, 40, a)
+        c[f"m37_n8_k8_{a}_res_nobias"] = _gemm_parts("t128", 37, 8, 8, a, bias=False, res=True)
     return c
 
 
@@ -99,78 +131,96 @@ def _t256():
     for i, K in enumerate((8, 40, 264, 64, 96)):
         for j, a in enumerate(ACTS):
             if (i + j) % 2 == 0 or K == 96:  # every K and every activation, half the grid
-                c[f"k{K}_{a}"] = lambda dt, K=K, a=a: _gemm(dt, "t256", 4096, 4096, K, a, res=(K % 64 == 0), seed=K)
-    c["k96_guarded"] = lambda dt: _gemm(dt, "t256", 4096 + 100, 4096 - 8, 96, "relu", guard=True)
+                c[f"k{K}_{a}"] = _gemm_parts("t256", 4096, 4096, K, a, res=(K % 64 == 0), seed=K)
+    c["k96_guarded"] = _gemm_parts("t256", 4096 + 100, 4096 - 8, 96, "relu", guard=True)
     # x rows 4 Mi elements apart: the row stride is past the 32-bit per-tile offsets (a buffer of about 4 GiB)
-    c["x_stride_past_limit"] = lambda dt: _gemm(dt, "t256", 512, 32768, 256, "gelu", ldx=STRIDE_MAX + 8)
+    c["x_stride_past_limit"] = _gemm_parts("t256", 512, 32768, 256, "gelu", ldx=STRIDE_MAX + 8)
     return c
 
 
 def _p8w():
     c = {
-        "tiles_256": lambda dt: _gemm(dt, "p8w", 65536, 256, 256, "gelu"),
-        "tiles_257": lambda dt: _gemm(dt, "p8w", 65536 + 256, 256, 128),
-        "skinny_m1": lambda dt: _gemm(dt, "p8w", 1, 65536, 128, "silu"),
-        "skinny_m200_n_ragged8": lambda dt: _gemm(dt, "p8w", 200, 65536 + 8, 160),
-        "skinny_n8": lambda dt: _gemm(dt, "p8w", 65536, 8, 256, "relu"),
-        "skinny_n24": lambda dt: _gemm(dt, "p8w", 65536 + 100, 24, 544, "gelu"),
-        "k4096": lambda dt: _gemm(dt, "p8w", 4096, 4096, 4096),
-        "n_ragged248_k160": lambda dt: _gemm(dt, "p8w", 4096, 4096 - 248, 160, "gelu_erf", bias=False),
-        "blocked_w_k544": lambda dt: _gemm(dt, "p8w", 4096 + 37, 4096 + 8, 544, "silu", blocked_w=True),
-        "blocked_x": lambda dt: _gemm(dt, "p8w", 4096 + 37, 4096, 256, "gelu", blocked_w=True, blocked_x=True),
-        "col_scale_all": lambda dt: _gemm(dt, "p8w", 4096, 4096, 256, col_scale=(0, 4096, 0.125), blocked_w=True),
-        "col_scale_band_to_n": lambda dt: _gemm(dt, "p8w", 8192 + 100, 3072 + 128, 512, "gelu",
+        "tiles_256": _gemm_parts("p8w", 65536, 256, 256, "gelu"),
+        "tiles_257": _gemm_parts("p8w", 65536 + 256, 256, 128),
+        "skinny_m1": _gemm_parts("p8w", 1, 65536, 128, "silu"),
+        "skinny_m200_n_ragged8": _gemm_parts("p8w", 200, 65536 + 8, 160),
+        "skinny_n8": _gemm_parts("p8w", 65536, 8, 256, "relu"),
+        "skinny_n24": _gemm_parts("p8w", 65536 + 100, 24, 544, "gelu"),
+        "k4096": _gemm_parts("p8w", 4096, 4096, 4096),
+        "n_ragged248_k160": _gemm_parts("p8w", 4096, 4096 - 248, 160, "gelu_erf", bias=False),
+        "blocked_w_k544": _gemm_parts("p8w", 4096 + 37, 4096 + 8, 544, "silu", blocked_w=True),
+        "blocked_x": _gemm_parts("p8w", 4096 + 37, 4096, 256, "gelu", blocked_w=True, blocked_x=True),
+        "col_scale_all": _gemm_parts("p8w", 4096, 4096, 256, col_scale=(0, 4096, 0.125), blocked_w=True),
+        "col_scale_band_to_n": _gemm_parts("p8w", 8192 + 100, 3072 + 128, 512, "gelu",
                                                 col_scale=(2048, 3072 + 128, 0.18033688), blocked_w=True),
-        "guarded_out": lambda dt: _gemm(dt, "p8w", 4096 + 100, 4096 - 8, 128, guard=True),
+        "guarded_out": _gemm_parts("p8w", 4096 + 100, 4096 - 8, 128, guard=True),
         "out_stride_at_limit": lambda dt: _strided_out(dt),
     }
     for a in ACTS:
-        c[f"act_{a}_k128"] = lambda dt, a=a: _gemm(dt, "p8w", 4096 + 1, 4096, 128, a, seed=3)
+        c[f"act_{a}_k128"] = _gemm_parts("p8w", 4096 + 1, 4096, 128, a, seed=3)
     return c
 
 
 def _p8w_res():
     c = {
-        "tiles_256": lambda dt: _gemm(dt, "p8w_res", 4096, 4096, 128, res=True),
-        "tiles_257": lambda dt: _gemm(dt, "p8w_res", 65536 + 256, 256, 160, "gelu", res=True),
-        "skinny_m1": lambda dt: _gemm(dt, "p8w_res", 1, 65536, 128, res=True),
-        "skinny_n8": lambda dt: _gemm(dt, "p8w_res", 65536 + 13, 8, 544, "silu", res=True),
-        "k4096": lambda dt: _gemm(dt, "p8w_res", 4096 + 100, 4096 + 8, 4096, res=True),
-        "n_ragged248_nobias": lambda dt: _gemm(dt, "p8w_res", 4096, 4096 - 248, 256, "relu", bias=False, res=True),
-        "blocked_w_x": lambda dt: _gemm(dt, "p8w_res", 4096 + 37, 4096, 256, blocked_w=True, blocked_x=True, res=True),
-        "guarded_out": lambda dt: _gemm(dt, "p8w_res", 4096 + 100, 4096 - 8, 160, "gelu", guard=True, res=True),
+        "tiles_256": _gemm_parts("p8w_res", 4096, 4096, 128, res=True),
+        "tiles_257": _gemm_parts("p8w_res", 65536 + 256, 256, 160, "gelu", res=True),
+        "skinny_m1": _gemm_parts("p8w_res", 1, 65536, 128, res=True),
+        "skinny_n8": _gemm_parts("p8w_res", 65536 + 13, 8, 544, "silu", res=True),
+        "k4096": _gemm_parts("p8w_res", 4096 + 100, 4096 + 8, 4096, res=True),
+        "n_ragged248_nobias": _gemm_parts("p8w_res", 4096, 4096 - 248, 256, "relu", bias=False, res=True),
+        "blocked_w_x": _gemm_parts("p8w_res", 4096 + 37, 4096, 256, blocked_w=True, blocked_x=True, res=True),
+        "guarded_out": _gemm_parts("p8w_res", 4096 + 100, 4096 - 8, 160, "gelu", guard=True, res=True),
     }
     for a in ACTS:
-        c[f"act_{a}"] = lambda dt, a=a: _gemm(dt, "p8w_res", 4096 + 1, 4096, 128, a, res=True, blocked_w=True, seed=5)
+        c[f"act_{a}"] = _gemm_parts("p8w_res", 4096 + 1, 4096, 128, a, res=True, blocked_w=True, seed=5)
     return c
 
 
 def _glu_t128x64():
     return {
-        "m37_n72_k40": lambda dt: _gemm(dt, "glu_t128x64", 37, 72, 40, "swiglu"),
-        "n_ragged_no_bias": lambda dt: _gemm(dt, "glu_t128x64", 300, 200, 264, "swiglu", bias=False),
-        "n_ragged_no_bias_gate": lambda dt: _gemm(dt, "glu_t128x64", 300, 1000, 1024, "swiglu", bias_gate=False),
-        "guarded_out": lambda dt: _gemm(dt, "glu_t128x64", 129, 136, 72, "swiglu", guard=True),
+        "m37_n72_k40": _gemm_parts("glu_t128x64", 37, 72, 40, "swiglu"),
+        "n_ragged_no_bias": _gemm_parts("glu_t128x64", 300, 200, 264, "swiglu", bias=False),
+        "n_ragged_no_bias_gate": _gemm_parts("glu_t128x64", 300, 1000, 1024, "swiglu", bias_gate=False),
+        "guarded_out": _gemm_parts("glu_t128x64", 129, 136, 72, "swiglu", guard=True),
     }
 
 
 def _glu_t256x128():
     return {
-        "n4104": lambda dt: _gemm(dt, "glu_t256x128", 4096, 4096 + 8, 256, "swiglu"),
-        "n_ragged_no_bias_k40": lambda dt: _gemm(dt, "glu_t256x128", 4096 + 100, 2048 - 8, 40, "swiglu", bias=False),
-        "guarded_no_bias_gate": lambda dt: _gemm(dt, "glu_t256x128", 4096 + 1, 2048 + 8, 1024, "swiglu", guard=True,
+        "n4104": _gemm_parts("glu_t256x128", 4096, 4096 + 8, 256, "swiglu"),
+        "n_ragged_no_bias_k40": _gemm_parts("glu_t256x128", 4096 + 100, 2048 - 8, 40, "swiglu", bias=False),
+        "guarded_no_bias_gate": _gemm_parts("glu_t256x128", 4096 + 1, 2048 + 8, 1024, "swiglu", guard=True,
                                                  bias_gate=False),
     }
 
 
-def _glu_ln(dtype, route, M, N, K, seed=0, what=""):
-    """The gated stage through block_weight_glu + gemm_ln."""
+def _ln_route_of(p):
+    """The route of a gemm_ln launch described by p (x, wb, b, kw)."""
+    return _ops().gemm_route(p.x, p.wb, p.b, **p.kw)
+
+
+def _ln_launch(p):
+    return _ops().gemm_ln(p.x, p.wb, p.b, **p.kw)
+
+
+def _glu_ln_build(dtype, route, M, N, K, seed=0, what=""):
     ops = _ops()
     x, wu, bu, _, wg, bg = _operands(dtype, M, N, K, "swiglu", True, False, seed, gate=True)
     wb = ops.block_weight_glu(wg, wu)
-    assert ops.gemm_route(x, wb, bu, "swiglu", M=M, N=N, K=K, bias_gate=bg) == route
-    h, _ = ops.gemm_ln(x, wb, bu, M=M, N=N, K=K, activation="swiglu", bias_gate=bg)
-    gc.check(h, gc.reference(x, wu, bu, "swiglu", wg, bg, device=DEV), dtype, route, what=what)
+    p = SimpleNamespace(dtype=dtype, route=route, shape=(M, N, K), x=x, wb=wb, b=bu, wu=wu, wg=wg, bg=bg, what=what,
+                        kw=dict(M=M, N=N, K=K, activation="swiglu", bias_gate=bg))
+    assert _ln_route_of(p) == route
+    return p
+
+
+def _glu_ln_judge(p, ret):
+    gc.check(ret[0], gc.reference(p.x, p.wu, p.b, "swiglu", p.wg, p.bg, device=DEV), p.dtype, p.route, what=p.what)
+
+
+def _glu_ln_parts(route, M, N, K, **kw):
+    """The gated stage through block_weight_glu + gemm_ln."""
+    return Parts(lambda dt: _glu_ln_build(dt, route, M, N, K, **kw), _ln_launch, _glu_ln_judge)
 
 
 EPS = 1e-5
@@ -210,6 +260,15 @@ def _fold_consumer(dtype, route, y, st, N, act, seed, col_scale=None, blocked=Fa
     """One consumer launch on the stream y with the statistics st: the route asserted, the output judged by gc.check against
     gc.reference_fold of what the kernel reads -- the whole output, or at K >= 4096 (where the fp64 reference is large) the
     16-row blocks of _seam_rows.  Returns (z, folded bias, the launch's keyword arguments)."""
+    p = _fold_build(dtype, route, y, st, N, act, seed, col_scale, what)
+    z, none = _ln_launch(p)
+    _fold_judge(p, (z, none), blocked=blocked, bars=bars)
+    return z, p.b, (p.wb, p.kw)
+
+
+def _fold_build(dtype, route, y, st, N, act, seed, col_scale=None, what=""):
+    """The consumer's operands on the stream y (p.x) with the statistics st: the folded weights, the launch's keyword arguments,
+    the route asserted."""
     ops = _ops()
     M, K = y.shape
     gam, bet = _rand((K,), dtype, 0.2, seed + 4, shift=1.0), _rand((K,), dtype, 0.1, seed + 5)
@@ -228,28 +287,38 @@ def _fold_consumer(dtype, route, y, st, N, act, seed, col_scale=None, blocked=Fa
         assert torch.equal(wb, ops.block_weight(ws)) and torch.equal(bfold2, bfold), "the blocked fold is not block_weight(ws)"
     if col_scale is not None:
         kw["col_scale"] = col_scale
-    assert ops.gemm_route(y, wb, bfold, **kw) == route, what
-    z, none = ops.gemm_ln(y, wb, bfold, **kw)
+    p = SimpleNamespace(dtype=dtype, route=route, shape=(M, N, K), act=act, x=y, wb=wb, b=bfold, kw=kw, ws=ws, rkw=rkw,
+                        col_scale=col_scale, what=what)
+    assert _ln_route_of(p) == route, what
+    return p
+
+
+def _fold_judge(p, ret, blocked=False, bars=True):
+    ops = _ops()
+    z, none = ret
+    (M, N, K), y, kw = p.shape, p.x, p.kw
     assert none is None and tuple(z.shape) == (M, N)
     if blocked:  # the same launch through the blocked activation layout on both sides: bit for bit
         from test_gpu_kernels import _block, _unblock
-        zb, _ = ops.gemm_ln(_block(y), wb, bfold, x_blocked=True, out_blocked=True, **kw)
+        zb, _ = ops.gemm_ln(_block(y), p.wb, p.b, x_blocked=True, out_blocked=True, **kw)
         assert torch.equal(_unblock(zb, M, N), z), "blocked x / blocked output differs from the row-major launch"
-    stl = ops.ln_stats_for_launch(st, M)  # what gemm_ln itself hands to the launch (the same call gives the same bits)
+    stl = ops.ln_stats_for_launch(kw["ln_stats"], M)  # what gemm_ln itself hands to the launch (the same call gives the same bits)
     rows = _seam_rows(M) if K >= 4096 else None
     pick = (lambda t: t) if rows is None else (lambda t: t[rows])  # noqa: E731
-    ref = gc.reference_fold(pick(y), stl[:, :M] if rows is None else stl[:, rows], ws, bfold, eps=EPS, act=act,
-                            col_scale=col_scale, device=DEV, **rkw)
-    gc.check(pick(z), ref, dtype, route, bars=bars, what=what or f"fold M {M} N {N} K {K} {act}")
-    return z, bfold, (wb, kw)
+    ref = gc.reference_fold(pick(y), stl[:, :M] if rows is None else stl[:, rows], p.ws, p.b, eps=EPS, act=p.act,
+                            col_scale=p.col_scale, device=DEV, **p.rkw)
+    gc.check(pick(z), ref, p.dtype, p.route, bars=bars, what=p.what or f"fold M {M} N {N} K {K} {p.act}")
 
 
-def _fold_case(dtype, route, M, N, K, act, seed=0, mean=1.0, produced=False, **kw):
+def _fold_parts(route, M, N, K, act, seed=0, mean=1.0, produced=False, col_scale=None, blocked=False, bars=True, what=""):
     """Producer (residual GEMM + statistics) -> consumer with the LayerNorm folded into its weights.  produced=True: the case
     relies on the real producer's stream (its mean in deviations)."""
-    assert not produced or _ops().gemm_ln_ok(M, K, K, "none", stats_out=True)
-    y, st = _fold_stream(dtype, M, K, seed, mean)
-    _fold_consumer(dtype, route, y, st, N, act, seed, **kw)
+    def build(dtype):
+        assert not produced or _ops().gemm_ln_ok(M, K, K, "none", stats_out=True)
+        y, st = _fold_stream(dtype, M, K, seed, mean)
+        return _fold_build(dtype, route, y, st, N, act, seed, col_scale, what)
+
+    return Parts(build, _ln_launch, lambda p, ret: _fold_judge(p, ret, blocked=blocked, bars=bars))
 
 
 def _adversarial_stream(dtype, M, K, seed):
@@ -287,8 +356,8 @@ def _fold_adversarial(dtype, route, M, N, K, act, seed=0):
 
 def _p8w_glu():
     return {
-        "gemm_ln_n2048": lambda dt: _glu_ln(dt, "p8w_glu", 4096, 2048, 256),
-        "gemm_ln_ragged_m_k1024": lambda dt: _glu_ln(dt, "p8w_glu", 4096 + 100, 2048, 1024, seed=2),
+        "gemm_ln_n2048": _glu_ln_parts("p8w_glu", 4096, 2048, 256),
+        "gemm_ln_ragged_m_k1024": _glu_ln_parts("p8w_glu", 4096 + 100, 2048, 1024, seed=2),
         "fused_mlp_blocked": lambda dt: _mlp(dt, "swiglu", True, True, "p8w_glu"),
     }
 
@@ -298,41 +367,49 @@ MP = 16500     # 65 row tiles, the last one ragged: with them a producer of widt
 
 
 def _p8w_glu_fold():
-    c = {"gemm_ln_fold": lambda dt: _fold_case(dt, "p8w_glu_fold", MP, 2048, 1024, "swiglu")}
+    c = {"gemm_ln_fold": _fold_parts("p8w_glu_fold", MP, 2048, 1024, "swiglu")}
     for K in (256, 1024, 2304):  # 1, 4 and 9 -> 3 statistic slots
-        c[f"k{K}"] = lambda dt, K=K: _fold_case(dt, "p8w_glu_fold", MR, 1024, K, "swiglu", seed=K)
+        c[f"k{K}"] = _fold_parts("p8w_glu_fold", MR, 1024, K, "swiglu", seed=K)
     c["adversarial_stream"] = lambda dt: _fold_adversarial(dt, "p8w_glu_fold", 8192 - 100, 1024, 1024, "swiglu", seed=11)
     return c
 
 
 def _p8w_fold():
     c = {
-        "none": lambda dt: _fold_case(dt, "p8w_fold", MP, 2048, 1024, "none"),
-        "gelu": lambda dt: _fold_case(dt, "p8w_fold", MP, 2048, 1024, "gelu", seed=1),
-        "k256_none": lambda dt: _fold_case(dt, "p8w_fold", 65536 - 100, 256, 256, "none", seed=2),
-        "k256_gelu": lambda dt: _fold_case(dt, "p8w_fold", 65536 - 100, 256, 256, "gelu", seed=3),
+        "none": _fold_parts("p8w_fold", MP, 2048, 1024, "none"),
+        "gelu": _fold_parts("p8w_fold", MP, 2048, 1024, "gelu", seed=1),
+        "k256_none": _fold_parts("p8w_fold", 65536 - 100, 256, 256, "none", seed=2),
+        "k256_gelu": _fold_parts("p8w_fold", 65536 - 100, 256, 256, "gelu", seed=3),
         # M 16500: the producer GEMM [M, 1024, 1024] has the tiles, so these run the chain the modules run
-        "col_scale_half": lambda dt: _fold_case(dt, "p8w_fold", MP, 2048, 1024, "gelu", seed=4, col_scale=(1024, 2048, 0.25)),
-        "blocked_x_and_out": lambda dt: _fold_case(dt, "p8w_fold", MP, 2048, 1024, "none", seed=5, blocked=True),
+        "col_scale_half": _fold_parts("p8w_fold", MP, 2048, 1024, "gelu", seed=4, col_scale=(1024, 2048, 0.25)),
+        "blocked_x_and_out": _fold_parts("p8w_fold", MP, 2048, 1024, "none", seed=5, blocked=True),
         # a residual of mean 8.8 and deviation 2 under a product of deviation 1: 8.8 / sqrt 5 = 3.9 deviations of mean
-        "mean_4_deviations": lambda dt: _fold_case(dt, "p8w_fold", MP, 2048, 1024, "gelu", seed=6, mean=8.8, produced=True),
+        "mean_4_deviations": _fold_parts("p8w_fold", MP, 2048, 1024, "gelu", seed=6, mean=8.8, produced=True),
         "adversarial_stream": lambda dt: _fold_adversarial(dt, "p8w_fold", 8192 - 100, 2048, 1024, "none", seed=7),
     }
     # statistic slots: 3, 8 (the LDS region full), 9 -> 3, 11 -> 1, 16 -> 8, 32 -> 8 (the last through ln_fold_weight_kernel<T, 32>)
     for i, K in enumerate((768, 2048, 2304, 2816, 4096, 8192)):
-        c[f"k{K}"] = lambda dt, K=K, i=i: _fold_case(dt, "p8w_fold", MR, 2048, K, ("gelu", "none")[i % 2], seed=K)
+        c[f"k{K}"] = _fold_parts("p8w_fold", MR, 2048, K, ("gelu", "none")[i % 2], seed=K)
     return c
 
 
-def _stats_case(dtype, M, N, K, seed=0):
+def _stats_parts(M, N, K, seed=0):
     """The producer form: y = x w^T + b + r checked as p8w_stats, and stats_out[slot][row] = (sum, sum of squares) of the
     kernel's own stored y over the slot's 256 columns, against fp64 within the fp32 summation bound gamma_n sum |terms|."""
-    ops = _ops()
-    x, w, b, r, _, _ = _operands(dtype, M, N, K, res=True, seed=seed)
-    wb = ops.block_weight(w)
-    assert ops.gemm_route(x, wb, b, M=M, N=N, K=K, residual=r, stats_out=True) == "p8w_stats"
-    y, st = ops.gemm_ln(x, wb, b, M=M, N=N, K=K, residual=r, stats_out=True)
-    gc.check(y, gc.reference(x, w, b, residual=r, device=DEV), dtype, "p8w_stats")
+    def build(dtype):
+        x, w, b, r, _, _ = _operands(dtype, M, N, K, res=True, seed=seed)
+        p = SimpleNamespace(dtype=dtype, route="p8w_stats", shape=(M, N, K), x=x, w=w, wb=_ops().block_weight(w), b=b, r=r,
+                            kw=dict(M=M, N=N, K=K, residual=r, stats_out=True))
+        assert _ln_route_of(p) == "p8w_stats"
+        return p
+
+    return Parts(build, _ln_launch, _stats_judge)
+
+
+def _stats_judge(p, ret):
+    y, st = ret
+    (M, N, K), dtype = p.shape, p.dtype
+    gc.check(y, gc.reference(p.x, p.w, p.b, residual=p.r, device=DEV), dtype, "p8w_stats")
     yf = y.double().view(M, N // 256, 256)
     s, q = yf.sum(-1).t(), (yf * yf).sum(-1).t()
     gam = lambda n: n * gc.U32 / (1 - n * gc.U32)  # noqa: E731  (any order, an accumulator that truncates included)
@@ -344,9 +421,9 @@ def _stats_case(dtype, M, N, K, seed=0):
 
 def _p8w_stats():
     return {
-        "n1024_k1024": lambda dt: _stats_case(dt, 16500, 1024, 1024),
-        "n256_k128_tiles_257": lambda dt: _stats_case(dt, 65536 + 256, 256, 128, seed=1),
-        "n2048_k4096": lambda dt: _stats_case(dt, 8192 + 7, 2048, 4096, seed=2),
+        "n1024_k1024": _stats_parts(16500, 1024, 1024),
+        "n256_k128_tiles_257": _stats_parts(65536 + 256, 256, 128, seed=1),
+        "n2048_k4096": _stats_parts(8192 + 7, 2048, 4096, seed=2),
     }
 
 
@@ -481,6 +558,28 @@ def test_gemm_fp16_subnormal_outputs():
 
 # ---- fused MLP: both paths, every activation, ragged M, with and without residual -------------------------------------------
 def _mlp(dtype, act, blocked, res, want1=None, seed=0):
+    _mlp_parts(act, blocked, res, want1, seed)(dtype)
+
+
+def _mlp_parts(act, blocked, res, want1=None, seed=0):
+    return Parts(lambda dt: _mlp_build(dt, act, blocked, res, want1, seed), _mlp_launch, _mlp_judge)
+
+
+def _mlp_route_of(p):
+    return _ops().fused_mlp_route(p.x, p.w1, p.b1, p.w2, p.b2, p.act, p.wg, p.bg, residual=p.r, **p.kw)
+
+
+def _mlp_launch(p):
+    return _ops().fused_mlp(p.x, p.w1, p.b1, p.w2, p.b2, p.act, p.wg, p.bg, residual=p.r, **p.kw)
+
+
+def _mlp_judge(p, y):
+    r = p.r
+    ref = gc.reference_mlp(p.x[0], p.w1, p.b1, p.w2, p.b2, p.act, p.wg, p.bg, None if r is None else r[0], device=DEV)
+    gc.check(y[0], ref, p.dtype, p.route["stage2"], what=f"fused mlp {p.act} {p.route['path']}")
+
+
+def _mlp_build(dtype, act, blocked, res, want1=None, seed=0):
     ops = _ops()
     if blocked:
         M, d, I = 16384 + 100, 1024, 1024
@@ -495,15 +594,14 @@ def _mlp(dtype, act, blocked, res, want1=None, seed=0):
     if blocked and (act == "swiglu" or res):  # blocked weights; else the plain weights on the same two-stage path
         kw["fc1_blocked"] = ops.block_weight_glu(wg, w1) if act == "swiglu" else ops.block_weight(w1)
         kw["fc2_blocked"] = ops.block_weight(w2)
-    rt = ops.fused_mlp_route(x, w1, b1, w2, b2, act, wg, bg, residual=r, **kw)
+    p = SimpleNamespace(dtype=dtype, act=act, x=x, w1=w1, b1=b1, w2=w2, b2=b2, wg=wg, bg=bg, r=r, kw=kw)
+    p.route = _mlp_route_of(p)
     want = {"path": "blocked" if blocked else "two_launch",
             "stage1": want1 or (("p8w_glu" if act == "swiglu" else "p8w") if blocked else
                                 ("glu_t128x64" if act == "swiglu" else "t128")),
             "stage2": ("p8w_res" if res else "p8w") if blocked else "t128"}
-    assert rt == want, rt
-    y = ops.fused_mlp(x, w1, b1, w2, b2, act, wg, bg, residual=r, **kw)
-    ref = gc.reference_mlp(x[0], w1, b1, w2, b2, act, wg, bg, None if r is None else r[0], device=DEV)
-    gc.check(y[0], ref, dtype, rt["stage2"], what=f"fused mlp {act} {rt['path']}")
+    assert p.route == want, p.route
+    return p
 
 
 @pytest.mark.gpu
