@@ -74,6 +74,11 @@ const char* mio_last_error(void);
  *   fp32 output is also written to o_acc (and lse must be non-NULL).  `o` may be NULL when
  *   o_acc is given (intermediate ring steps).
  * Sk == 0: no key is read; o = 0, lse = -inf (carry_in: the carried state is written back).
+ * Memory the launch does not own may hold anything, NaN bit patterns included, and does not influence the
+ *   result -- here and in the varlen, paged and windowed forms below: the bytes between D and the head stride,
+ *   heads / rows / batch entries of a larger buffer around q, k, v, o or the mask, and, without a user mask,
+ *   every 64-key tile (counted from key 0) that holds no key visible to any query row < Sq; o / lse / o_acc
+ *   are written at rows < Sq only (a blocked o: its padding rows past B*Sq stay untouched).
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   const void* q;
@@ -194,6 +199,9 @@ int32_t mio_fa3_varlen_route(const mio_fa3_varlen_params_t* p);
  * The kernel clamps cu_seqlens_q as mio_fa3_fwd_varlen does, every logical block into
  * [0, max_blocks_per_seq) and every page into [0, num_blocks): a bad table gives wrong numbers,
  * never an access outside the buffers.  Rows of o outside every sequence are not written.
+ * No cache slot at or past Lk_b, no other layer, no page outside the tables, no 64-key tile without a visible
+ * key and no table entry of a logical block that holds no such tile influences the result: they may hold
+ * anything (NaN bit patterns too), as for mio_fa3_decode_paged.
  * causal: bottom-right aligned per sequence (query i sees key j iff j <= i + Lk_b - Lq_b).  Rows
  * with no visible key, and every row of a sequence with Lk_b == 0, get o = 0, lse = -inf.
  * lse (nullable): fp32 [H,total_q].  block_size must be a multiple of 64 (a 64-key tile never

@@ -109,6 +109,10 @@
     }
     // ---- tiles: the workgroup walks n_tiles (barriers, staging); this wave computes the first n_w of them
     int n_tiles, n_w;
+    // the last rows inside Sq of the block and of this wave: the rows past Sq see further, and a tile only they see is not
+    // to be read
+    const int q_last = q0 + FA3_BM - 1 < p.Sq - 1 ? q0 + FA3_BM - 1 : p.Sq - 1;
+    const int w_last = wrow0 + 32 * QT - 1 < p.Sq - 1 ? wrow0 + 32 * QT - 1 : p.Sq - 1;
 #ifdef FA_WINDOW
     const int win_off = p.q_offset - p.k_offset, win_r = CAUSAL ? 0 : wr;
     auto win_tlo = [&](int qb0) -> int {  // first (absolute) tile of the pass whose first row is qb0
@@ -119,7 +123,7 @@
     {
       int kmax = p.Sk - 1, kw = p.Sk - 1;
       if (win_r >= 0) {
-        const int c = q0 + FA3_BM - 1 + win_off + win_r, cw = wrow0 + 32 * QT - 1 + win_off + win_r;
+        const int c = q_last + win_off + win_r, cw = w_last + win_off + win_r;
         kmax = c < kmax ? c : kmax;
         kw = cw < kw ? cw : kw;
       }
@@ -132,10 +136,10 @@
                 pass + 1 < npass ? win_tlo((CAUSAL ? qi : qblk) * FA3_BM) : t_lo, pass == 0);
 #else
     if (CAUSAL) {
-      int kmax = q0 + FA3_BM - 1 + p.q_offset - p.k_offset;
+      int kmax = q_last + p.q_offset - p.k_offset;
       if (kmax > p.Sk - 1) kmax = p.Sk - 1;
       n_tiles = kmax < 0 ? 0 : kmax / FA_BN + 1;
-      int kw = wrow0 + 32 * QT - 1 + p.q_offset - p.k_offset;
+      int kw = w_last + p.q_offset - p.k_offset;
       if (kw > p.Sk - 1) kw = p.Sk - 1;
       n_w = kw < 0 ? 0 : kw / FA_BN + 1;
     } else {

@@ -105,6 +105,10 @@
   auto pass_q0 = [&](int pass) __attribute__((always_inline)) -> int {
     return (CAUSAL ? (pass == 0 ? p.nqblk - 1 - qi : qi) : qi) * FA5_BM;
   };
+  // the last row inside Sq of the rows [r0, r0 + n): the rows past Sq see further, and a tile only they see is not to be read
+  auto last_row_in = [&](int r0, int n) __attribute__((always_inline)) -> int {
+    return r0 + n - 1 < p.Sq - 1 ? r0 + n - 1 : p.Sq - 1;
+  };
 #ifdef FA_WINDOW
   const int win_off = p.q_offset - p.k_offset, win_r = CAUSAL ? 0 : wr;
   auto pass_tlo = [&](int pass) __attribute__((always_inline)) -> int {  // first (absolute) KV tile of that pass
@@ -114,7 +118,7 @@
   auto pass_tiles = [&](int pass) __attribute__((always_inline)) -> int {  // KV tiles the workgroup walks in that pass
     int kmax = p.Sk - 1;
     if (win_r >= 0) {
-      const int c = pass_q0(pass) + FA5_BM - 1 + win_off + win_r;
+      const int c = last_row_in(pass_q0(pass), FA5_BM) + win_off + win_r;
       kmax = c < kmax ? c : kmax;
     }
     const int n = kmax < 0 ? 0 : kmax / FA_BN + 1 - pass_tlo(pass);
@@ -123,7 +127,7 @@
 #else
   auto pass_tiles = [&](int pass) __attribute__((always_inline)) -> int {  // KV tiles the workgroup walks in that pass
     if (!CAUSAL) return (p.Sk + FA_BN - 1) / FA_BN;
-    int kmax = pass_q0(pass) + FA5_BM - 1 + p.q_offset - p.k_offset;
+    int kmax = last_row_in(pass_q0(pass), FA5_BM) + p.q_offset - p.k_offset;
     if (kmax > p.Sk - 1) kmax = p.Sk - 1;
     return kmax < 0 ? 0 : kmax / FA_BN + 1;
   };
@@ -203,7 +207,7 @@
     FA_WIN_PASS(t_lo, t_lo + n_tiles, t_lo_next, pass == 0);
     int n_w = n_tiles;
     if (win_r >= 0) {
-      int kw = wrow0 + 31 + win_off + win_r;
+      int kw = last_row_in(wrow0, 32) + win_off + win_r;
       if (kw > p.Sk - 1) kw = p.Sk - 1;
       n_w = kw < 0 ? 0 : kw / FA_BN + 1 - t_lo;
       n_w = n_w < 0 ? 0 : (n_w > n_tiles ? n_tiles : n_w);
@@ -229,7 +233,7 @@
 #else
     int n_w = n_tiles;
     if (CAUSAL) {
-      int kw = wrow0 + 31 + p.q_offset - p.k_offset;
+      int kw = last_row_in(wrow0, 32) + p.q_offset - p.k_offset;
       if (kw > p.Sk - 1) kw = p.Sk - 1;
       n_w = kw < 0 ? 0 : kw / FA_BN + 1;
     }

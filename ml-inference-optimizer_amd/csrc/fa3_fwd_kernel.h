@@ -180,7 +180,8 @@ __global__ __launch_bounds__(256) void fa3_fwd_kernel(const FaDev p) {
   // ---- number of KV tiles this workgroup visits
   int n_tiles;
   if (CAUSAL && MASK == 0) {
-    int kmax = q0 + FA_BM - 1 + p.q_offset - p.k_offset;
+    // (the block's last row inside Sq: the rows past it see further, and a tile only they see is not to be read)
+    int kmax = (q0 + FA_BM - 1 < p.Sq - 1 ? q0 + FA_BM - 1 : p.Sq - 1) + p.q_offset - p.k_offset;
     if (kmax > p.Sk - 1) kmax = p.Sk - 1;
     n_tiles = kmax < 0 ? 0 : kmax / FA_BN + 1;
   } else {
