@@ -25,7 +25,7 @@ extern "C" {
 
 #define MIO_VERSION 106 /* 0.1.0 */
 
-typedef enum { MIO_BF16 = 0, MIO_FP16 = 1 } mio_dtype_t;
+typedef enum { MIO_BF16 = 0, MIO_FP16 = 1, MIO_FP32 = 2 /* mio_sample_tokens' logits only */ } mio_dtype_t;
 
 typedef enum {
   MIO_ACT_NONE = 0,
@@ -708,6 +708,55 @@ int mio_qknorm_rope_rows(const void* x, void* out, const int32_t* positions, con
                          const void* weight, const int64_t x_stride[2], const int64_t out_stride[2], /* token, head */
                          int32_t tokens, int32_t heads, int32_t D, int32_t rot_dim, int32_t max_position,
                          int32_t interleaved, int32_t dtype, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Token sampling (csrc/sampling.hip): [B, V] logits to token ids in one launch -- greedy,
+ * temperature, top-k, top-p and min-p, every parameter per row and read from DEVICE memory, the
+ * uniforms supplied by the caller (no RNG state in the kernel: graph-capturable, reproducible).
+ *
+ * Per row b: x[b, 0..V) the stored logits (bf16, fp16 or fp32 -- dtype MIO_FP32 is accepted here
+ * and nowhere else), row stride ld >= V in elements; T_b temperature, k_b top-k, p_b top-p, q_b
+ * min-p, u_b a uniform in [0, 1).  temperature, top_p, min_p, u are fp32 [B], top_k is int32 [B]; a
+ * null top_k, top_p or min_p turns that filter off for every row.
+ *
+ * Order.  A NaN logit counts as -inf, a +inf logit as the largest finite fp32.  Tokens are totally
+ * ordered: i before j iff x_i > x_j, or x_i == x_j and i < j.  The order is exact on the stored
+ * values; temperature does not change it.
+ * Greedy.  T_b NaN or T_b <= 0: the first token of the order (the argmax, lowest index on ties).
+ * Otherwise, with m = max x and w_i = exp((x_i - m) / T_b):
+ *   1. top-k: S1 = the first k_b tokens of the order; k_b <= 0 or k_b >= V means all tokens.
+ *   2. top-p over the renormalised top-k set: Z1 = sum_{S1} w,
+ *      S2 = { i in S1 : sum_{j in S1, j before i} w_j < p_b * Z1 }; p_b >= 1 or NaN means off; the
+ *      first token is always kept, also for p_b <= 0.
+ *   3. min-p: S3 = { i in S2 : w_i >= q_b } (the ratio to the most likely token: w_max = 1);
+ *      q_b <= 0 or NaN means off; the first token is always kept.
+ *   4. draw: Z = sum_{S3} w, C_i = sum_{j in S3, j <= i} w_j (ascending token index); the result is
+ *      the token i of S3 with C_i - w_i <= u_b * Z < C_i, u_b first clamped into [0, 1).  Should
+ *      rounding carry the search past the end, the result is the last token of S3: never a token
+ *      outside S3, never an index >= V.
+ * A row with no finite logit returns token -1, kept count 0 and a zero probability row; it does
+ * not fault and produces no NaN.
+ *
+ * Outputs, each optional, at least one required: tokens_out int64 [B]; kept_out int32 [B] = |S3|
+ * (1 on a greedy row); probs_out fp32 [B, V] by its own row stride ld_probs >= V: w_i / Z on S3 and
+ * exactly 0.0f elsewhere (one-hot on a greedy row); bytes between its rows are left alone.
+ *
+ * Masses are summed in 64-bit fixed point (quantum 2^-40 of w_max = 1), so every sum is exactly
+ * associative and reruns are bit-identical whatever the scheduling.
+ * Limits: 1 <= V <= 2^20; B >= 0 (B == 0 returns 0 without a launch); logits 16-byte aligned; ld
+ * arbitrary (rows may start off a 16-byte boundary: the kernel peels heads and tails itself and
+ * reads nothing outside [row, row + V)).  Asynchronous on stream; allocates nothing; no workspace.
+ * Parameter values live on the device and are not validated: every out-of-range value has the
+ * meaning given above.
+ * Refused (< 0) before any launch: null logits, temperature or u (u may be null only when
+ * tokens_out is null: nothing is drawn then), every output null, V < 1 or V > 2^20, B < 0, ld < V,
+ * probs_out with ld_probs < V, an unknown dtype, logits off 16-byte alignment (or a parameter or
+ * output array off its element's alignment).
+ * ------------------------------------------------------------------------------------------ */
+int mio_sample_tokens(const void* logits, int64_t ld, const float* temperature, const int32_t* top_k,
+                      const float* top_p, const float* min_p, const float* u, int64_t* tokens_out,
+                      int32_t* kept_out, float* probs_out, int64_t ld_probs, int32_t B, int32_t V,
+                      int32_t dtype /* MIO_BF16 | MIO_FP16 | MIO_FP32 */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmio_hip_dbg.so" if os.environ.get("MIO_LIB_DBG") == "1" else "libmio_hip.so")
 
 MIO_BF16, MIO_FP16 = 0, 1
+MIO_FP32 = 2  # mio_sample_tokens' logits only
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_RELU, ACT_SILU, ACT_SWIGLU = range(6)
 MASK_NONE, MASK_KEEP_U8, MASK_ADD_F32 = range(3)
 # mio_fa3_route_t: the kernel mio_fa3_fwd launches (include/mio_hip.h)
@@ -146,6 +147,7 @@ EXPORTS = (
     "mio_qknorm_rope_and_cache_varlen",
     "mio_qknorm_rope_and_cache_varlen_kv8",
     "mio_qknorm_rope_rows",
+    "mio_sample_tokens",
 )
 
 
@@ -394,6 +396,9 @@ def _load() -> C.CDLL:
     lib.mio_qknorm_rope_and_cache_varlen_kv8.restype = i32
     lib.mio_qknorm_rope_rows.argtypes = [vp] * 6 + [p64] * 2 + [i32] * 7 + [f32, vp]
     lib.mio_qknorm_rope_rows.restype = i32
+    # sampling: logits, ld, temperature, top_k, top_p, min_p, u, tokens_out, kept_out, probs_out, ld_probs, B, V, dtype, stream
+    lib.mio_sample_tokens.argtypes = [vp, i64] + [vp] * 8 + [i64, i32, i32, i32, vp]
+    lib.mio_sample_tokens.restype = i32
     return lib
 
 

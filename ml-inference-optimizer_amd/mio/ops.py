@@ -16,6 +16,9 @@ same exception types for the same conditions):
                                rotary position embedding (not a reference kernel: its LLaMA path rotates K in PyTorch before
                                caching it, baseline/model_utils.py): the fp32 angle tables, the standalone rotation of the dense
                                path, and the rotation fused into the varlen paged-cache write (16-bit and fp8 caches)
+  sample_tokens / sampling_probs
+                               token sampling (not a reference kernel: its facade promises .generate()): [B, V] logits to token
+                               ids in one launch -- greedy, temperature, top-k, top-p, min-p per row from device tensors
 There is no fallback path: a non-zero return from the library raises RuntimeError.
 """
 from __future__ import annotations
@@ -1776,6 +1779,107 @@ def qknorm_rope_and_cache_varlen(q, key, value, k_cache, v_cache, block_tables, 
     fn = lib.mio_qknorm_rope_and_cache_varlen_kv8 if r.kv8 else lib.mio_qknorm_rope_and_cache_varlen
     check(fn(*r.head, *r.strides, *r.sizes, eps, _stream()))
     return r.q_out
+
+
+# ------------------------------------------------------------------------------------------------
+# token sampling
+# ------------------------------------------------------------------------------------------------
+SAMPLE_MAX_VOCAB = 1 << 20
+_SAMPLE_DTYPES = {torch.bfloat16: _lib.MIO_BF16, torch.float16: _lib.MIO_FP16, torch.float32: _lib.MIO_FP32}
+
+
+def _sample_param(v, B: int, dtype: torch.dtype, name: str, who: str, device, required: bool = False):
+    """A per-row parameter as a device tensor [B] of dtype: a tensor is checked, a Python scalar is broadcast with torch.full
+    (no synchronisation), None stays None (the filter is off for every row)."""
+    if v is None:
+        if required:
+            raise ValueError(f"{who}: {name} is required")
+        return None
+    if isinstance(v, torch.Tensor):
+        if not v.is_cuda:
+            raise ValueError("HIP kernels require input tensors to be on a CUDA (ROCm) device.")
+        if v.dtype != dtype or v.dim() != 1 or v.numel() != B or not v.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor of {B} elements, got {v.dtype} "
+                             f"{tuple(v.shape)}")
+        return v
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError(f"{who}: {name} must be a number or a tensor, got {type(v).__name__}")
+    if dtype == torch.int32:
+        if isinstance(v, float) and v != int(v):
+            raise ValueError(f"{who}: {name} must be an integer, got {v}")
+        v = max(-1, min(int(v), 2 ** 31 - 1))
+    return torch.full((B,), v, dtype=dtype, device=device)
+
+
+def _sample(who: str, logits, temperature, top_k, top_p, min_p, u, generator, tokens: bool, kept: bool, probs: bool):
+    if not isinstance(logits, torch.Tensor):
+        raise ValueError(f"{who}: logits must be a tensor")
+    _need_cuda(logits)
+    if logits.dtype not in _SAMPLE_DTYPES:
+        raise ValueError(f"{who}: logits must be bf16, fp16 or fp32, got {logits.dtype}")
+    if logits.dim() < 1:
+        raise ValueError(f"{who}: logits must be [..., V]")
+    V = logits.shape[-1]
+    if not 1 <= V <= SAMPLE_MAX_VOCAB:
+        raise ValueError(f"{who}: the vocabulary must be 1 .. {SAMPLE_MAX_VOCAB} tokens, got {V}")
+    if logits.stride(-1) != 1 and V > 1:
+        raise ValueError(f"{who}: logits must have last-dim stride 1")
+    lead = logits.shape[:-1]
+    x = logits if logits.dim() == 2 else logits.reshape(-1, V)
+    if x.stride(-1) != 1 and V > 1:
+        x = x.contiguous()
+    B = x.shape[0]
+    ld = x.stride(0) if B > 1 else V
+    if ld < V or x.data_ptr() % 16:
+        x = x.contiguous()
+        ld = V
+    dev = x.device
+    T = _sample_param(temperature, B, torch.float32, "temperature", who, dev, required=True)
+    k = _sample_param(top_k, B, torch.int32, "top_k", who, dev)
+    p = _sample_param(top_p, B, torch.float32, "top_p", who, dev)
+    q = _sample_param(min_p, B, torch.float32, "min_p", who, dev)
+    if tokens:
+        if u is None:
+            u = torch.rand(B, generator=generator, device=dev, dtype=torch.float32)
+        elif generator is not None:
+            raise ValueError(f"{who}: give u or generator, not both")
+        else:
+            u = _sample_param(u, B, torch.float32, "u", who, dev)
+    tok = torch.empty(B, dtype=torch.int64, device=dev) if tokens else None
+    kep = torch.empty(B, dtype=torch.int32, device=dev) if kept else None
+    pr = torch.empty(B, V, dtype=torch.float32, device=dev) if probs else None
+    if B > 0:  # an empty batch has no addresses to hand over
+        check(lib.mio_sample_tokens(x.data_ptr(), ld, T.data_ptr(), _ptr(k), _ptr(p), _ptr(q), _ptr(u) if tokens else None,
+                                    _ptr(tok), _ptr(kep), _ptr(pr), V, B, V, _SAMPLE_DTYPES[x.dtype], _stream()))
+    return (None if tok is None else tok.view(lead), None if kep is None else kep.view(lead),
+            None if pr is None else pr.view(*lead, V))
+
+
+def sample_tokens(logits, temperature, top_k=None, top_p=None, min_p=None, *, u=None, generator=None,
+                  return_kept: bool = False, return_probs: bool = False):
+    """One token id per row of logits [B, V] (or [..., V], flattened; bf16, fp16 or fp32, last-dim stride 1) in one launch
+    (mio_sample_tokens; the semantics are stated in include/mio_hip.h): greedy where temperature <= 0, else temperature
+    sampling restricted by top-k, then top-p over the renormalised top-k set, then min-p, drawn with the uniform u[b] in
+    [0, 1) by an index-ordered CDF search.  Ties are ordered by token index; a NaN logit counts as -inf.
+
+    temperature, top_p, min_p, u: fp32 device tensors [B] or Python scalars; top_k: int32 [B] or an int.  A scalar becomes a
+    device tensor with torch.full, a None filter is off; nothing synchronises, so the call can be captured in a graph (pass
+    tensors then, and update them in place: see mio.sampling.Sampler).  u=None draws torch.rand(B, generator=generator) on the
+    device.  Returns tokens (int64, logits.shape[:-1]; -1 for a row with no finite logit), followed by kept (int32, the size
+    of the filtered set) when return_kept and probs (fp32 [..., V], the filtered distribution, exactly 0 outside the kept
+    set) when return_probs.  ValueError for CPU tensors, wrong dtypes or shapes, a strided last dim; RuntimeError with the
+    library's message on a refusal."""
+    tok, kep, pr = _sample("sample_tokens", logits, temperature, top_k, top_p, min_p, u, generator, True, bool(return_kept),
+                           bool(return_probs))
+    if not return_kept and not return_probs:
+        return tok
+    return (tok,) + ((kep,) if return_kept else ()) + ((pr,) if return_probs else ())
+
+
+def sampling_probs(logits, temperature, top_k=None, top_p=None, min_p=None):
+    """The filtered distribution sample_tokens draws from, fp32 [..., V]: w_i / Z on the kept set, exactly 0 elsewhere, one-hot
+    on a greedy row, all zero on a row with no finite logit.  The arguments of sample_tokens without u: nothing is drawn."""
+    return _sample("sampling_probs", logits, temperature, top_k, top_p, min_p, None, None, False, False, True)[2]
 
 
 # ------------------------------------------------------------------------------------------------
