@@ -241,7 +241,9 @@ int32_t mio_fa3_paged_route(const mio_fa3_paged_params_t* p);
  * o = w_a*o_a + w_b*o_b, lse = logaddexp(lse_a, lse_b), w_x = exp(lse_x - lse).
  * Restates the (alpha, beta) update of kernels/triton/attention_kernels.py:1573-1585.
  * o_* fp32 [rows, D] contiguous with rows = B*Sq*H laid out [B,Sq,H]; lse_* fp32 [B,H,Sq].
- * Result in (o_a, lse_a); if o_out != NULL the merged output is also written there in `dtype`. */
+ * Result in (o_a, lse_a); if o_out != NULL the merged output is also written there in `dtype`.
+ * Memory the launch does not own may hold anything, NaN bit patterns included, and does not influence the result: the
+ * bytes around the five operands are neither read into it nor written; o_b and lse_b are not written. */
 int mio_attn_merge(float* o_a, float* lse_a, const float* o_b, const float* lse_b, void* o_out,
                    int32_t B, int32_t Sq, int32_t H, int32_t D, int32_t dtype, void* stream);
 
@@ -253,6 +255,20 @@ int mio_attn_merge(float* o_a, float* lse_a, const float* o_b, const float* lse_
  * (F.linear call sites: kernels/mlp/fused_mlp.py:159,176,225,236,265-266,274;
  *  kernels/attention/flash_attention.py:629-631,654-657).
  * ldx/ldw/ldy/ldr: row strides in elements (multiples of 8); K % 8 == 0; bias/residual nullable.
+ * Memory the launch does not own may hold anything, NaN bit patterns included, and does not influence the result -- here
+ *   and in every entry point below that ends in a GEMM (the *_bw forms, mio_gemm_ln_bw / mio_gemm_rms_bw, the three
+ *   FusedMLP forwards, mio_gemm_skinny, mio_gemm_skinny_w8) and in the weight preparations.  A launch owns x[m, k], m < M,
+ *   k < K; w[n, k] and w_gate[n, k], n < N, k < K (a prepared weight: the whole prepared buffer, whose padding the library
+ *   wrote); bias[n], bias_gate[n], w_scale[n], w_scale_gate[n], n < N; residual[m, n], m < M, n < N; and of the statistics
+ *   ln_stats[s][m], s < ln_slots, m < M.  Not owned: the columns K .. ld of x, w, w_gate (bytes K .. ldw of an fp8 weight),
+ *   the columns N .. ld of the residual and of y, the elements in front of element 0 and at and past N of a bias or scale,
+ *   the rows in front of row 0 and the rows >= M (x, residual, y) or >= N (weights) of a larger buffer, the rows
+ *   M .. ceil(M/256)*256 of a blocked x or residual and of every statistics slot, the statistics slots >= ln_slots, and a
+ *   workspace's contents before the launch.  The K tail, the rows a tile has past M or N and the idle stages of the
+ *   persistent kernel are zero-filled, clamped to an owned row or discarded: none of them reaches a stored value.
+ *   y is written at m < M, n < N only: the bytes between N and ldy, the rows around y and, of a blocked y
+ *   (MIO_GEMM_Y_BLOCKED), the padding rows M .. ceil(M/256)*256 keep what they held.
+ *   Inputs are never written.
  * ------------------------------------------------------------------------------------------ */
 int mio_gemm_bias_act(const void* x, const void* w, const void* bias, const void* w_gate,
                       const void* bias_gate, const void* residual, void* y, int64_t M, int32_t N,
@@ -266,7 +282,10 @@ int mio_gemm_bias_act(const void* x, const void* w, const void* bias, const void
  * x [M,d], w1/wg [I,d], w2 [d,I], biases nullable; workspace >= mio_fused_mlp_workspace_bytes()
  * holds the bf16/fp16 [M,I] activation (written once by stage 1's epilogue, read once by stage 2; rows rounded up
  * to whole 256-row blocks: at sizes where both GEMMs run the 256x256-tile kernels the library keeps it in a blocked
- * layout of contiguous 16 KiB K-tiles). */
+ * layout of contiguous 16 KiB K-tiles).  What the workspace holds before the launch does not matter (stage 2 reads only what
+ * stage 1 wrote for rows < M), nothing outside its mio_fused_mlp_workspace_bytes() is touched, and what it holds afterwards is
+ * unspecified.  x, the weights and the residual are contiguous rows here: the ownership rule of mio_gemm_bias_act holds for the
+ * rows around them, for the elements around the biases and for y. */
 size_t mio_fused_mlp_workspace_bytes(int64_t M, int32_t d, int32_t I, int32_t act);
 int mio_fused_mlp_fwd(const void* x, const void* w1, const void* b1, const void* wg, const void* bg,
                       const void* w2, const void* b2, const void* residual, void* y, void* workspace,
@@ -278,7 +297,10 @@ int mio_fused_mlp_fwd(const void* x, const void* w1, const void* b1, const void*
  * (mio_weight_blocked_bytes).  The reference has no counterpart (its weights stay nn.Linear tensors read by tl.load,
  * kernels/triton/mlp_kernels.py:91-126); the plain-weight entry points above remain the drop-in boundary.
  * *_ok() == 0: the shape does not take those kernels -- keep the plain weight and call the plain entry point
- * (the *_bw entry points return an error then). */
+ * (the *_bw entry points return an error then).
+ * The preparations (mio_weight_block, mio_weight_block_glu, mio_ln_fold_weight, mio_weight_quant_w8) read w[n, k], n < N,
+ * k < K of their source and nothing else of it: the columns K .. ldw and the rows around it may hold anything.  The padding
+ * rows of a blocked weight are written as zeros whatever lies behind row N - 1 of the source. */
 size_t mio_weight_blocked_bytes(int32_t N, int32_t K);
 int mio_weight_block(const void* w, int64_t ldw, void* wb, int32_t N, int32_t K, int32_t dtype, void* stream);
 int32_t mio_gemm_blocked_weight_ok(int64_t M, int32_t N, int32_t K, int32_t act);
@@ -342,7 +364,10 @@ int32_t mio_gemm_route(int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw
  * launch fills the chip; with more than one slice the kernel writes fp32 partials [splits][M][N] (SwiGLU: twice, up then gate)
  * into `workspace` (>= mio_gemm_skinny_workspace_bytes(), 0 with one slice) and a second small kernel sums them in slice order,
  * applies bias / activation / residual and rounds once.  No workgroup waits for another: the result is bit-reproducible, and
- * the launch neither allocates nor synchronises (graph-capturable).
+ * the launch neither allocates nor synchronises (graph-capturable).  The ownership rule of mio_gemm_bias_act holds here and
+ * in mio_gemm_skinny_w8 (the rows M .. 63 behind x that pad the last row fragment, the columns K .. ld, the elements around
+ * bias and scales are not owned); what the workspace holds before the launch does not matter and nothing outside its
+ * mio_gemm_skinny_workspace_bytes() is touched.
  * mio_gemm_skinny runs every legal shape; M == 0 returns 0 and launches nothing.  mio_gemm_skinny_ok only advises the module
  * layer: 1 where the shape is legal AND measured at most 0.9 x the time of mio_gemm_bias_act's route (profiles/skinny_gemm.md).
  * mio_gemm_skinny_splits / _slice return < 0 (mio_last_error()) on a shape the launch refuses.
@@ -402,14 +427,19 @@ int mio_layernorm_fwd_bx(const void* x, const void* residual, const void* weight
  * (kernels/triton/layernorm_kernels.py:35-188) between two GEMMs of a transformer block:
  *   producer = the GEMM that writes the residual stream (out-proj / fc2 with the residual epilogue): stats_out != NULL makes it
  *     also write, per output row and 256-column tile, (sum, sum of squares) of the ROUNDED row: [N / 256][ceil(M/256)*256][2]
- *     fp32 (mio_ln_stats_bytes(M, N)); deterministic (fixed summation order, no atomics);
+ *     fp32 (mio_ln_stats_bytes(M, N)); deterministic (fixed summation order, no atomics).  The kernel stores all 256 rows of
+ *     a row tile: the rows M .. ceil(M/256)*256 of every slot ARE written, with the statistics of rows it recomputes from
+ *     clamped (owned) rows of x and the residual -- values without meaning that depend on nothing the launch does not own;
  *   consumer = the projection behind the LayerNorm: ln_stats (a producer's stats_out of width K) != NULL: x is the raw stream,
  *     wb = mio_weight_block of the gamma-scaled, row-centred weight and bias the beta-folded bias (both from mio_ln_fold_weight:
  *     (x - mean 1) . w = x . (w - mean(w) 1), so centring the weight rows makes the plain product the centred one); the
  *     read-out computes rstd * acc + bias, then act / column scale.  Rounding: mio_ln_fold_weight chooses the rounding direction
  *     of a few elements per row so that the 16-bit row sums to zero within an ulp or two (plain rounding would leave ~sqrt(K/12)
  *     ulp, and the product would carry mean(x) times that); measured error equals the LayerNorm kernel + GEMM's (2.3e-3 bf16)
- *     for streams whose row mean is up to 4x their deviation.
+ *     for streams whose row mean is up to 4x their deviation.  The consumer owns ln_stats[s][m][0..1] for s < ln_slots and
+ *     m < M (mio_gemm_rms_bw: only [1], the sum of squares): the rows M .. ceil(M/256)*256 of a slot (a producer's leftovers, or
+ *     nothing at all) and the slots >= ln_slots of a larger buffer may hold anything, NaN bit patterns and values that survive
+ *     the variance's fmaxf(., 0) included.
  * flags: the operands in the blocked activation layout ((256-row, 32-column) blocks of 16 KiB, rows padded to 256; ld* ignored
  * for a blocked operand): x (as mio_gemm_bias_act_bw's x_blocked), y (what the next GEMM takes as blocked x), residual.
  * Shapes: mio_gemm_ln_ok(M, N, K, act, fold_in, stats_out) != 0 (blocked-weight shapes; fold_in: K % 256 == 0, K <= 8192 (the
@@ -429,7 +459,10 @@ int mio_gemm_ln_bw(const void* x, const void* wb, const void* bias, const void* 
                    int64_t ldx, int64_t ldy, int64_t ldr, int32_t act, int32_t dtype, int32_t flags, const float* ln_stats,
                    int32_t ln_slots, float ln_eps, float* stats_out, int32_t cs_lo, int32_t cs_hi, float cs_val, void* stream);
 /* ln_slots: statistic slots in ln_stats (0: K / 256, what a producer of width K writes); at most 8.  A wider stream (K > 2048)
- * goes through mio_ln_stats_reduce first: stats_out[s'] = sum of slots_in / slots_out consecutive slots, same row padding. */
+ * goes through mio_ln_stats_reduce first: stats_out[s'] = sum of slots_in / slots_out consecutive slots, same row padding:
+ * the padding rows M .. ceil(M/256)*256 of stats_out are written with the sums of the input's padding rows, whatever those
+ * hold (unspecified values, which the consumer does not own either); the rows < M depend on the rows < M of the slots_in
+ * slots only. */
 int mio_ln_stats_reduce(const float* stats_in, int32_t slots_in, float* stats_out, int32_t slots_out, int64_t M, void* stream);
 /* The consumer form behind an RMSNorm(gamma): mio_gemm_ln_bw's arguments, kernels, routes (mio_gemm_route, mio_gemm_ln_ok answer
  * for both norms) and checks, with rstd = rsqrt(sum of squares / K + ln_eps): the statistics' sum entries are not used.  wb =
@@ -442,7 +475,12 @@ int mio_gemm_rms_bw(const void* x, const void* wb, const void* bias, const void*
 /* LayerNorm / residual+LayerNorm rows (the step either side of attention):
  * sum = x + alpha*residual (if residual), y = (sum-mean)/sqrt(var+eps)*weight + bias.
  * Replaces triton_layernorm -> _layernorm_fwd_kernel / _layernorm_residual_fwd_kernel
- * (kernels/triton/layernorm_kernels.py:191-276; kernels :35-188).  sum_out nullable. */
+ * (kernels/triton/layernorm_kernels.py:191-276; kernels :35-188).  sum_out nullable.
+ * x, residual, y and sum_out are `rows` contiguous rows of `cols` elements (there is no row stride).  Memory the launch does
+ * not own may hold anything, NaN bit patterns included, and does not influence the result -- in mio_layernorm_fwd,
+ * mio_layernorm_fwd_bx and mio_rmsnorm_fwd: the rows around x and the residual and the elements around weight and bias are
+ * not read into it, the bytes around y and sum_out and the padding rows past `rows` of a blocked y are not written, inputs
+ * are not written. */
 int mio_layernorm_fwd(const void* x, const void* residual, const void* weight, const void* bias,
                       void* y, void* sum_out, int64_t rows, int32_t cols, float eps, float alpha,
                       int32_t dtype, void* stream);

@@ -4,13 +4,15 @@ holds for any summation order, the split of K included.  The shapes are the tabl
 reach each seam: every count of row fragments, K tails and K below one step and K 0, one slice and several (asserted through
 ops.gemm_skinny_splits, so both kernels' epilogues are known to have run), slices of three and more chunks of the kernel's
 double-buffered loop (plain and SwiGLU, every count of row fragments), N down to one column and past a workgroup's 64, with and
-without partials, every activation, strides of x, w, the residual and the output, operands inside NaN-filled buffers, the
-workspace's bounds, determinism and a captured graph.  What the tables reach under the plan is asserted on the CPU
+without partials, every activation, strides of x, w, the residual and the output, operands inside buffers whose other bytes are
+finite, NaN and huge in turn (tests/_hostile_gemm.py), the workspace's bounds, determinism and a captured graph.  What the
+tables reach under the plan is asserted on the CPU
 (tests/test_gemm_skinny_host.py::test_case_tables_reach_the_seams)."""
 import pytest
 import torch
 
 import _gemm_check as gc
+import _hostile_gemm as hg
 import _skinny_cases as sk
 
 pytestmark = pytest.mark.gpu
@@ -192,47 +194,71 @@ def test_swiglu_fragments(dtype):
 
 
 def _poisoned(dtype, c, ldw, ldw_gate):
-    """Case c with every operand a view inside a NaN-filled buffer: x is the first M rows and K columns of [64, ldx], w and
-    w_gate the first K columns of [N, ldw], the residual the first N columns of [M, ldr], the output inside a NaN guard."""
+    """Case c with every operand a view inside a larger buffer (tests/_hostile_gemm.Embedded): x is the first M rows and K columns
+    of [64, ldx], w and w_gate the first K columns of [N + 2, ldw] behind one guard row, the residual the first N columns of
+    [M + 1, ldr], the biases 8 elements into [N + 16], the output one row and 16 columns into its buffer.  Returns {name: Embedded}."""
     x, w, b, r, wg, bg = _operands(dtype, c.M, c.N, c.K, c.bias, c.res, c.seed, None, c.glu, c.bias_gate)
+    e = {"x": hg.Embedded(x, (64, c.ldx)), "w": hg.Embedded(w, (c.N + 2, ldw), (1, 0), seed=1),
+         "r": hg.Embedded(r, (c.M + 1, c.ldr), seed=2),
+         "y": hg.Embedded(None, (c.M + 2, (c.N + 32 + 7) // 8 * 8), (1, 16), out_shape=(c.M, c.N), dtype=dtype, device=DEV)}
+    if b is not None:
+        e["b"] = hg.Embedded(b, (c.N + 16,), (8,), seed=3)
+    if c.glu:
+        e["wg"] = hg.Embedded(wg, (c.N + 2, ldw_gate), (1, 0), seed=4)
+        if bg is not None:
+            e["bg"] = hg.Embedded(bg, (c.N + 16,), (8,), seed=5)
+    return e
 
-    def inside(t, rows, cols):
-        buf = torch.full((rows, cols), NAN, dtype=dtype, device=DEV)
-        buf[:t.shape[0], :t.shape[1]] = t
-        return buf[:t.shape[0], :t.shape[1]]
 
-    x, w, r = inside(x, 64, c.ldx), inside(w, c.N, ldw), inside(r, c.M, c.ldr)
-    wg = inside(wg, c.N, ldw_gate) if c.glu else None
-    buf = torch.full((c.M + 2, (c.N + 32 + 7) // 8 * 8), NAN, dtype=dtype, device=DEV)
-    return x, w, b, r, wg, bg, buf
+def _poisoned_launch(e, c, out=True):
+    v = lambda n: e[n].view if n in e else None  # noqa: E731
+    return _ops().gemm_skinny(v("x"), v("w"), v("b"), c.act, w_gate=v("wg"), bias_gate=v("bg"), residual=v("r"),
+                              out=v("y") if out else None)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_poisoned_paddings(dtype):
     """Nothing next to the operands reaches the arithmetic: x columns K .. ldx and x rows M .. 63 (the rows the kernel pads the
-    last fragment with), w and w_gate columns K .. ldw, residual columns N .. ldr and the output's guard are all NaN, with one
-    slice and with several (whose last ends in a step of 8 k), at M 37 and M 5, plain and SwiGLU.  One NaN read into a product, a
-    sum or the epilogue makes an output NaN, which the finite check reports; the guard must still be NaN everywhere."""
+    last fragment with), w and w_gate columns K .. ldw and the rows around them, residual columns N .. ldr and the row behind
+    it, the elements around the biases and the output's guard hold, in three launches at the same addresses, finite randn
+    (benign), NaN (0xFF bytes) and +-finfo.max / 8 (huge: fmaxf and v_max drop a NaN operand, a huge one they keep), with one
+    slice and with several (whose last ends in a step of 8 k), at M 37 and M 5, plain and SwiGLU.  The benign launch is judged
+    against the fp64 reference; the NaN and the huge launch must equal it bit for bit; after each, every byte the launch does
+    not own is what it was."""
     ops = _ops()
     for c in sk.POISONED:
         ldw = c.K + sk.POISONED_LDW_PAD
-        x, w, b, r, wg, bg, buf = _poisoned(dtype, c, ldw, ldw)
-        for t in (x, w, r) + ((wg,) if c.glu else ()):  # the views go to the launch as they are: no copy drops the poison
+        e = _poisoned(dtype, c, ldw, ldw)
+        for n in ("x", "w", "r") + (("wg",) if c.glu else ()):  # the views go to the launch as they are: no copy drops the poison
+            t = e[n].view
             assert ops._rows16(t) is t and not t.is_contiguous()
         assert (ops.gemm_skinny_splits(c.M, c.N, c.K, c.act) > 1) == c.split, c.what
-        out = buf[1:c.M + 1, 16:c.N + 16]
-        y = ops.gemm_skinny(x, w, b, c.act, w_gate=wg, bias_gate=bg, residual=r, out=out)
-        assert y.data_ptr() == out.data_ptr()
-        _judge(y, gc.reference(x, w, b, c.act, wg, bg, r, device=DEV), dtype, "poisoned " + c.what)
-        outside = torch.ones_like(buf, dtype=torch.bool)
-        outside[1:c.M + 1, 16:c.N + 16] = False
-        assert bool(torch.isnan(buf[outside]).all()), f"{c.what}: guard elements outside the output view were overwritten"
+        got = {}
+        for fill in hg.FILLS:
+            for t in e.values():
+                t.fill(fill)
+            y = _poisoned_launch(e, c)
+            torch.cuda.synchronize()
+            assert y.data_ptr() == e["y"].view.data_ptr()
+            for n, t in e.items():
+                assert t.untouched(), f"{c.what} fill {fill}: bytes of {n} that the launch does not own were overwritten"
+            got[fill] = y.clone()
+        v = lambda n: e[n].value if n in e else None  # noqa: E731
+        _judge(got["benign"], gc.reference(v("x"), v("w"), v("b"), c.act, v("wg"), v("bg"), v("r"), device=DEV), dtype,
+               "poisoned " + c.what)
+        for fill in ("nan", "huge"):
+            d = got[fill].view(torch.int16) != got["benign"].view(torch.int16)
+            assert not bool(d.any()), (f"{c.what} fill {fill}: {int(d.sum())} output elements differ from the benign launch, "
+                                       f"first at (row, column) {tuple(d.nonzero()[0].tolist())}")
     # w and w_gate at different row strides: the kernel has one ldw, so ops.gemm_skinny hands it contiguous copies of both
     c = [c for c in sk.POISONED if c.glu and c.split][0]
-    x, w, b, r, wg, bg, _ = _poisoned(dtype, c, c.K + 16, c.K + 8)
-    assert w.stride(0) != wg.stride(0)
-    y = ops.gemm_skinny(x, w, b, c.act, w_gate=wg, bias_gate=bg, residual=r)
-    _judge(y, gc.reference(x, w, b, c.act, wg, bg, r, device=DEV), dtype, "two weight strides " + c.what)
+    e = _poisoned(dtype, c, c.K + 16, c.K + 8)
+    for t in e.values():
+        t.fill("nan")
+    assert e["w"].view.stride(0) != e["wg"].view.stride(0)
+    y = _poisoned_launch(e, c, out=False)
+    v = lambda n: e[n].value if n in e else None  # noqa: E731
+    _judge(y, gc.reference(v("x"), v("w"), v("b"), c.act, v("wg"), v("bg"), v("r"), device=DEV), dtype, "two weight strides " + c.what)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

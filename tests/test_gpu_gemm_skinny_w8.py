@@ -9,6 +9,7 @@ up weight's, and the ZERO_SCALE cases carry zeros in a few columns."""
 import pytest
 import torch
 
+import _hostile_gemm as hg
 import _w8_cases as wc
 import _w8_check as w8c
 
@@ -201,43 +202,66 @@ def test_deep_pipeline(dtype, table, deep_weights):
 
 
 def _poisoned(dtype, c):
-    """Case c with every operand a view inside a NaN-filled buffer: x is the first M rows and K columns of [64, ldx], w8 and
-    w8_gate the first K columns of [N, ldw] (padding bytes 0x7f), the residual the first N columns of [M, ldr], the output inside
-    a NaN guard."""
+    """Case c with every operand a view inside a larger buffer (tests/_hostile_gemm.Embedded): x is the first M rows and K columns
+    of [64, ldx], w8 and w8_gate the first K bytes of the rows of [N + 2, ldw] behind one guard row, the scales and biases 8
+    elements into [N + 16], the residual the first N columns of [M + 1, ldr], the output one row and 16 columns into its buffer.
+    Returns {name: Embedded}."""
     x, q, s, b, r, qg, sg, bg = _operands(dtype, c)
-
-    def inside(t, rows, cols):
-        buf = torch.full((rows, cols), NAN, dtype=dtype, device=DEV)
-        buf[:t.shape[0], :t.shape[1]] = t
-        return buf[:t.shape[0], :t.shape[1]]
-
-    x, r = inside(x, 64, c.ldx), inside(r, c.M, c.ldr)
-    buf = torch.full((c.M + 2, (c.N + 32 + 7) // 8 * 8), NAN, dtype=dtype, device=DEV)
-    return x, q, s, b, r, qg, sg, bg, buf
+    q, qg = q.contiguous(), (qg.contiguous() if c.glu else None)
+    e = {"x": hg.Embedded(x, (64, c.ldx)), "w8": hg.Embedded(q, (c.N + 2, c.ldw), (1, 0), seed=1),
+         "s": hg.Embedded(s, (c.N + 16,), (8,), seed=2), "r": hg.Embedded(r, (c.M + 1, c.ldr), seed=3),
+         "y": hg.Embedded(None, (c.M + 2, (c.N + 32 + 7) // 8 * 8), (1, 16), out_shape=(c.M, c.N), dtype=dtype, device=DEV)}
+    if b is not None:
+        e["b"] = hg.Embedded(b, (c.N + 16,), (8,), seed=4)
+    if c.glu:
+        e["w8g"] = hg.Embedded(qg, (c.N + 2, c.ldw), (1, 0), seed=5)
+        e["sg"] = hg.Embedded(sg, (c.N + 16,), (8,), seed=6)
+        if bg is not None:
+            e["bg"] = hg.Embedded(bg, (c.N + 16,), (8,), seed=7)
+    return e
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_poisoned_paddings(dtype):
     """Nothing next to the operands reaches the arithmetic: x columns K .. ldx and x rows M .. 63, the weights' bytes in columns
-    K .. ldw (0x7f, NaN), residual columns N .. ldr and the output's guard are all NaN, with one slice and with several, at M 37
-    and M 5, plain and SwiGLU.  One NaN read into a product, a sum or the epilogue makes an output NaN, which the finite check
-    reports; the guard must still be NaN everywhere."""
+    K .. ldw and in the rows around them, the scales and biases in front of element 0 and at and past N, residual columns
+    N .. ldr and the row behind it, and the output's guard hold, in three launches at the same addresses, finite values (benign),
+    NaN (0xFF bytes: NaN in e4m3fn too) and huge values (+-finfo.max / 8, 1e30 in the scales, +-448 in the weight bytes:
+    fmaxf and v_max drop a NaN operand, a huge one they keep), with one slice and with several, at M 37 and M 5, plain and
+    SwiGLU.  The benign launch is judged against the fp64 reference; the NaN and the huge launch must equal it bit for bit;
+    after each, every byte the launch does not own is what it was."""
     ops = _ops()
     for c in wc.POISONED:
-        x, q, s, b, r, qg, sg, bg, buf = _poisoned(dtype, c)
-        for t in (q,) + ((qg,) if c.glu else ()):
+        e = _poisoned(dtype, c)
+        v = lambda n: e[n].view if n in e else None  # noqa: E731
+        for n in ("w8",) + (("w8g",) if c.glu else ()):
+            t = v(n)
             assert ops._w8_ok(t, "w8") is t and not t.is_contiguous()
-            assert bool((t.as_strided((c.N, c.ldw - c.K), (c.ldw, 1), t.storage_offset() + c.K).view(torch.uint8) == 0x7f).all())
-        for t in (x, r):
+        for n in ("x", "r"):
+            t = v(n)
             assert ops._rows16(t) is t and not t.is_contiguous()
+        for n in ("s",) + (("sg",) if c.glu else ()):  # (the scales go to the launch where they lie: no clone drops the poison)
+            t = v(n)
+            assert ops._w8_scale(t, c.N, n) is t
         assert (ops.gemm_skinny_w8_splits(c.M, c.N, c.K, c.act) > 1) == c.split, c.what
-        out = buf[1:c.M + 1, 16:c.N + 16]
-        y = ops.gemm_skinny_w8(x, q, s, b, c.act, w8_gate=qg, w_scale_gate=sg, bias_gate=bg, residual=r, out=out)
-        assert y.data_ptr() == out.data_ptr()
-        w8c.judge(y, w8c.reference_w8(x, q, s, b, c.act, qg, sg, bg, r, device=DEV), dtype, "poisoned " + c.what)
-        outside = torch.ones_like(buf, dtype=torch.bool)
-        outside[1:c.M + 1, 16:c.N + 16] = False
-        assert bool(torch.isnan(buf[outside]).all()), f"{c.what}: guard elements outside the output view were overwritten"
+        got = {}
+        for fill in hg.FILLS:
+            for t in e.values():
+                t.fill(fill)
+            y = ops.gemm_skinny_w8(v("x"), v("w8"), v("s"), v("b"), c.act, w8_gate=v("w8g"), w_scale_gate=v("sg"),
+                                   bias_gate=v("bg"), residual=v("r"), out=v("y"))
+            torch.cuda.synchronize()
+            assert y.data_ptr() == v("y").data_ptr()
+            for n, t in e.items():
+                assert t.untouched(), f"{c.what} fill {fill}: bytes of {n} that the launch does not own were overwritten"
+            got[fill] = y.clone()
+        o = lambda n: e[n].value if n in e else None  # noqa: E731
+        w8c.judge(got["benign"], w8c.reference_w8(o("x"), o("w8"), o("s"), o("b"), c.act, o("w8g"), o("sg"), o("bg"), o("r"),
+                                                  device=DEV), dtype, "poisoned " + c.what)
+        for fill in ("nan", "huge"):
+            d = got[fill].view(torch.int16) != got["benign"].view(torch.int16)
+            assert not bool(d.any()), (f"{c.what} fill {fill}: {int(d.sum())} output elements differ from the benign launch, "
+                                       f"first at (row, column) {tuple(d.nonzero()[0].tolist())}")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -142,6 +142,29 @@ def test_rmsnorm_out_blocked(dtype, cols):
         assert bool((pad == FILL).all()), "rows past M of the blocked output were written"
 
 
+@pytest.mark.parametrize("blocked", [False, True], ids=["rows", "blocked"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=["bf16", "fp16"])
+def test_rmsnorm_hostile_memory(dtype, blocked):
+    """mio_rmsnorm_fwd through test_gpu_rows.hostile_rows: x and the residual between guard rows, the weight inside guards, y
+    (blocked: only its rows below `rows`) and sum_out inside guards; three launches at the same addresses with finite randn,
+    NaN and huge values in every byte the launch does not own: outputs bit-equal, those bytes untouched.  One chunk, a ragged
+    second chunk and RMSNorm's widest rows; a partly filled last workgroup and a second 256-row block.  The benign launch is
+    ops.rmsnorm's result bit for bit (which test_rmsnorm_rows judges against fp64)."""
+    from test_gpu_rows import hostile_rows
+    ops = _ops()
+    for rows, cols in ((5, 32), (257, 1024), (3, 8192)) if blocked else ((5, 8), (257, 520), (3, 8192)):
+        x, _ = _rows_input(dtype, rows, cols, cols + rows)
+        res, _ = _rows_input(dtype, rows, cols, cols + rows + 1)
+        w = _rand((cols,), dtype, 0.2, cols + 2, shift=1.0)
+        for r, want_sum in ((None, False), (res, True), (res, False)):
+            y, s = hostile_rows(dtype, rows, cols, x, r, w, None, 0.5, want_sum, blocked, rms=True, eps=EPS)
+            want = ops.rmsnorm(x, w, EPS, residual=r, residual_alpha=0.5, return_sum=want_sum)
+            ws = None
+            if want_sum:
+                want, ws = want
+            assert torch.equal(y, want) and (ws is None or r is None or torch.equal(s, ws)), (rows, cols, want_sum)
+
+
 def test_rmsnorm_refuses_wide_rows():
     ops = _ops()
     with pytest.raises(ValueError, match="8192"):

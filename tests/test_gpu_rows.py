@@ -8,6 +8,7 @@ import functools
 import pytest
 import torch
 
+import _hostile_gemm as hg
 import _rms_check as rc
 import _rows_check as rw
 
@@ -189,6 +190,107 @@ def test_layernorm_no_rows(dtype):
         y, s, ybuf, sbuf = _launch(dtype, x, res, w, b, 0.5, True, blocked=blocked, rows=0)
         torch.cuda.synchronize()
         assert bool((ybuf == FILL).all()) and bool((sbuf == FILL).all())
+
+
+# ---- hostile memory around every operand (tests/_hostile_gemm.py) ------------------------------------------------------------------
+def hostile_rows(dtype, rows, cols, x, res, w, b, alpha, want_sum, blocked, rms=False, eps=EPS):
+    """One row-kernel launch form in hostile memory: x and the residual between guard rows, weight and bias 8 elements into
+    their buffers, y (blocked: only its rows below `rows` are the launch's) and sum_out 64 elements into theirs.  The C ABI gives
+    these kernels no row stride, so there are no columns past `cols` to poison.  Three launches at the same addresses (benign,
+    NaN, huge): every output bit-equal to the benign launch's, every byte the launch does not own untouched.  Returns the benign
+    (y, sum_out)."""
+    lib = _lib().lib
+    mp = (rows + 255) // 256 * 256
+    ny = (mp if blocked else rows) * cols
+    e = {"x": hg.Embedded(x, (rows + 2, cols), (1, 0)), "w": hg.Embedded(w, (cols + 16,), (8,), seed=1),
+         "y": hg.Embedded(None, (ny + 128,), (64,), out_shape=(ny,), dtype=dtype, device=DEV,
+                          own_index=hg.blocked_index(rows, cols) if blocked else None)}
+    if res is not None:
+        e["res"] = hg.Embedded(res, (rows + 2, cols), (1, 0), seed=2)
+    if b is not None:
+        e["b"] = hg.Embedded(b, (cols + 16,), (8,), seed=3)
+    if want_sum:
+        e["sum"] = hg.Embedded(None, (rows * cols + 128,), (64,), out_shape=(rows * cols,), dtype=dtype, device=DEV)
+    p = lambda n: e[n].view.data_ptr() if n in e else None  # noqa: E731
+    what = f"rows {rows} cols {cols} residual {res is not None} sum_out {want_sum} blocked {blocked} rms {rms}"
+    got = {}
+    for fill in hg.FILLS:
+        for t in e.values():
+            t.fill(fill)
+        tail = (p("y"), p("sum"), rows, cols, ctypes.c_float(eps), ctypes.c_float(alpha), _dt(dtype))
+        if rms:
+            rcode = lib.mio_rmsnorm_fwd(p("x"), p("res"), p("w"), *tail, int(blocked), _stream())
+        else:
+            rcode = (lib.mio_layernorm_fwd_bx if blocked else lib.mio_layernorm_fwd)(p("x"), p("res"), p("w"), p("b"), *tail, _stream())
+        assert rcode == 0, _last_error()
+        torch.cuda.synchronize()
+        for n, t in e.items():
+            assert t.untouched(), f"{what} fill {fill}: bytes of {n} that the launch does not own were overwritten"
+        y = e["y"].view[hg.blocked_index(rows, cols).to(DEV)] if blocked else e["y"].view.view(rows, cols)
+        got[fill] = (y.clone(), e["sum"].view.view(rows, cols).clone() if want_sum else None)
+    for fill in ("nan", "huge"):
+        for i, name in enumerate(("y", "sum_out")):
+            if got[fill][i] is not None:
+                d = got[fill][i].view(torch.int16) != got["benign"][i].view(torch.int16)
+                assert not bool(d.any()), (f"{what} fill {fill}: {int(d.sum())} elements of {name} differ from the benign launch, "
+                                           f"first at (row, column) {tuple(d.nonzero()[0].tolist())}")
+    return got["benign"]
+
+
+@pytest.mark.parametrize("blocked", [False, True], ids=["rows", "blocked"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_layernorm_hostile_memory(dtype, blocked):
+    """mio_layernorm_fwd and mio_layernorm_fwd_bx through hostile_rows: one chunk per lane and the widest instantiation, a ragged
+    width, a partly filled last workgroup and a second 256-row block, without a residual, with one and sum_out, with one and
+    none.  The benign launch is ops.layernorm's result bit for bit (which test_layernorm_rows judges against fp64)."""
+    ops = _ops()
+    for rows, cols in ((5, 64), (257, 1024), (3, 4096)) if blocked else ((5, 8), (257, 520), (3, 4096)):
+        x, res, w, b, _ = _case(dtype, rows, cols)
+        for r, want_sum, bias in ((None, False, b), (res, True, b), (res, False, None)):
+            y, s = hostile_rows(dtype, rows, cols, x, r, w, bias, 0.5, want_sum, blocked)
+            want = ops.layernorm(x, w, bias, EPS, residual=r, residual_alpha=0.5, return_sum=want_sum)
+            ws = None
+            if want_sum:
+                want, ws = want
+            assert torch.equal(y, want) and (ws is None or torch.equal(s, ws)), (rows, cols, want_sum)
+
+
+@pytest.mark.parametrize("shape", rw.MERGE_SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("out_dtype", DTYPES + [None], ids=IDS + ["no_out"])
+def test_attn_merge_hostile_memory(out_dtype, shape):
+    """mio_attn_merge with o_a, lse_a, o_b, lse_b and o_out 8 (o_out: 64) elements into buffers whose other bytes hold, in three
+    launches at the same addresses, finite randn, NaN and 1e30: the merged (o_a, lse_a) and o_out bit-equal to the benign
+    launch's -- which is ops.attn_merge's result on plain tensors bit for bit --, side b and every byte around the five
+    operands untouched."""
+    ops, lib = _ops(), _lib().lib
+    B, Sq, H, D = shape
+    st = rw.merge_states(*shape, seed=sum(shape), device=DEV)
+    e = {n: hg.Embedded(t.reshape(-1), (t.numel() + 16,), (8,), seed=i, written=n in ("o_a", "lse_a"))
+         for i, (n, t) in enumerate(zip(("o_a", "lse_a", "o_b", "lse_b"), st))}
+    if out_dtype is not None:
+        n = B * Sq * H * D
+        e["out"] = hg.Embedded(None, (n + 128,), (64,), out_shape=(n,), dtype=out_dtype, device=DEV)
+    p = lambda n: e[n].view.data_ptr() if n in e else None  # noqa: E731
+    got = {}
+    for fill in hg.FILLS:
+        for t in e.values():
+            t.fill(fill)
+        rcode = lib.mio_attn_merge(p("o_a"), p("lse_a"), p("o_b"), p("lse_b"), p("out"), B, Sq, H, D,
+                                   _dt(out_dtype or torch.bfloat16), _stream())
+        assert rcode == 0, _last_error()
+        torch.cuda.synchronize()
+        for n, t in e.items():
+            assert t.untouched(), f"merge {shape} fill {fill}: bytes of {n} that the launch does not own were overwritten"
+        got[fill] = [hg.bits(e[n].view).clone() for n in ("o_a", "lse_a") + (("out",) if out_dtype is not None else ())]
+    for fill in ("nan", "huge"):
+        for a, b_, n in zip(got[fill], got["benign"], ("o_a", "lse_a", "o_out")):
+            assert torch.equal(a, b_), f"merge {shape} fill {fill}: {int((a != b_).sum())} elements of {n} differ from the benign launch"
+    o_a, l_a, o_b, l_b = (t.clone() for t in st)
+    out = None if out_dtype is None else torch.empty(B, Sq, H, D, dtype=out_dtype, device=DEV)
+    ops.attn_merge(o_a, l_a, o_b, l_b, out=out)
+    want = [o_a, l_a] + ([out] if out is not None else [])
+    for a, t in zip(got["benign"], want):
+        assert torch.equal(a, hg.bits(t.reshape(-1))), f"merge {shape}: the benign launch is not ops.attn_merge's result"
 
 
 # ---- attn_merge --------------------------------------------------------------------------------------------------------------------
