@@ -796,6 +796,78 @@ int mio_sample_tokens(const void* logits, int64_t ld, const float* temperature, 
                       int32_t* kept_out, float* probs_out, int64_t ld_probs, int32_t B, int32_t V,
                       int32_t dtype /* MIO_BF16 | MIO_FP16 | MIO_FP32 */, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mixture-of-experts MLP for decode steps (csrc/moe.hip, csrc/moe_plan.h): a router
+ * and two grouped GEMMs over stacked expert weights, the routing device data from start to end.
+ *
+ * Shapes.  T tokens (0 <= T <= 64), E experts (1 <= E <= 256), top_k = k (1 <= k <= min(E, 8)),
+ * hidden size d, expert intermediate size I.  Activations bf16 or fp16.  Expert weights 16-bit,
+ * row-major and stacked: w_up [E, I, d], w_gate [E, I, d] (SwiGLU only), w_down [E, d, I]; ldw the
+ * row stride (a multiple of 8 elements, >= the row's length), expert_stride the distance between
+ * experts (elements, a multiple of 8, at least one expert's extent).  Biases optional, contiguous
+ * [E, I] and [E, d].  A routed row is r = t k + j: token t, slot j.
+ *
+ * mio_moe_route.  logits [T, E] (bf16, fp16 or fp32 -- MIO_FP32 is accepted here), row stride
+ * ld >= E.  Per token:
+ *   Order.  As mio_sample_tokens orders tokens: a NaN logit counts as -inf, -0 as +0.  a before b
+ *     iff x_a > x_b, or x_a == x_b and a < b; exact on the STORED values, so a +inf logit sorts
+ *     before every finite one (before a stored largest finite fp32 too: fp32 logits only).
+ *   Choice.  ids[t, j] is the j-th expert of that order, j = 0 .. k - 1.
+ *   Weights.  In the weights, and only there, a +inf logit counts as the largest finite fp32 (so
+ *     x - m is never inf - inf).  m = max x, p_e = exp(x_e - m) / sum over ALL E of exp(x - m); w[t, j] = p_{ids[t, j]};
+ *     with renormalize that value divided by sum_j p_{ids[t, j]} (slot order).  renormalize = 1 is
+ *     Mixtral and Qwen3-MoE, 0 is OLMoE and Qwen2-MoE.  fp32.
+ *   Degenerate row.  No finite logit: ids = 0 .. k - 1, all weights exactly 0; no NaN, no fault.
+ * Outputs (device): ids int32 [T, k]; weights fp32 [T, k]; expert_offsets int32 [E + 1]
+ * (offsets[e] = routed rows whose expert is < e; offsets[E] = T k); sorted_rows int32 [T k]
+ * (positions offsets[e] .. offsets[e + 1] hold expert e's routed rows in ascending r); row_pos
+ * int32 [T k], the inverse: sorted_rows[row_pos[r]] = r.  ids, offsets, sorted_rows and row_pos are
+ * exactly determined by the input.
+ *
+ * mio_moe_up.  For sorted position p of expert e, token t = sorted_rows[p] / k:
+ *   h[p, :] = silu(x[t] Wgate_e^T + bg_e) * (x[t] Wup_e^T + bu_e)       (act == SWIGLU)
+ *   h[p, :] = act(x[t] Wup_e^T + bu_e)                                  (none, gelu, gelu_erf, relu, silu)
+ * fp32 accumulation, one rounding to the 16-bit dtype.  Only rows p < T k of h [T k, ldh] are written.
+ *
+ * mio_moe_down.  y[t, :] = sum_{j = 0 .. k-1} weights[t, j] (h[row_pos[t k + j]] Wdown_e^T + bd_e)
+ * + residual[t], e = ids[t, j]: fp32, the K slices in slice order, then the slots in slot order
+ * j = 0, 1, ..., one rounding.  residual is optional (also where a shared expert's output goes in).
+ *
+ * All three: no float atomics, no counters or barriers between workgroups, the same bits on every
+ * rerun; nothing allocated, nothing read back to the host; graph-capturable on one stream; T == 0
+ * returns 0 and launches nothing.  Ownership: rows of x (of h) are read only for the tokens routed
+ * to the expert at hand; the weights and biases of an expert with no routed row are never read;
+ * nothing past [row, row + K) of any operand is read; of a workspace only the first
+ * _workspace_bytes are touched.
+ * K (d for up, I for down) is cut into mio_moe_{up,down}_splits(T, k, E, N, K[, act]) slices of
+ * whole 32-k steps, N the output columns (I for up, d for down).  The plan is a pure function of
+ * these sizes: no device value is consulted.  Up with one slice finishes in its first kernel and
+ * needs no workspace; otherwise fp32 partials [splits][T k][N] (SwiGLU: two such) go to `workspace`
+ * (>= mio_moe_up_workspace_bytes).  Down always runs through partials: workspace
+ * >= mio_moe_down_workspace_bytes = splits * T k * N * 4 is required whenever T > 0.
+ * Refused (< 0, mio_last_error() names the entry point) before any launch: T > 64 (decode steps
+ * only), E or top_k out of range, K not a multiple of 8, strides short or not multiples of 8,
+ * pointers off 16-byte alignment (the route's int32 / fp32 arrays: off 4), w_gate without SWIGLU or
+ * SWIGLU without it, a missing workspace, an unknown dtype or activation.  The queries return < 0
+ * (_splits) or 0 with the message set (_workspace_bytes) on a shape the launch refuses.
+ * ------------------------------------------------------------------------------------------ */
+int mio_moe_route(const void* logits, int64_t ld, int32_t* ids, float* weights, int32_t* expert_offsets,
+                  int32_t* sorted_rows, int32_t* row_pos, int32_t T, int32_t E, int32_t top_k,
+                  int32_t renormalize, int32_t dtype /* MIO_BF16 | MIO_FP16 | MIO_FP32 */, void* stream);
+int mio_moe_up_splits(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K, int32_t act);
+size_t mio_moe_up_workspace_bytes(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K, int32_t act);
+int mio_moe_down_splits(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K);
+size_t mio_moe_down_workspace_bytes(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K);
+int mio_moe_up(const void* x, const void* w_up, const void* b_up, const void* w_gate, const void* b_gate,
+               const int32_t* expert_offsets, const int32_t* sorted_rows, void* h, void* workspace,
+               int32_t T, int32_t top_k, int32_t E, int32_t I, int32_t d, int64_t ldx, int64_t ldw,
+               int64_t expert_stride, int64_t ldh, int32_t act, int32_t dtype, void* stream);
+int mio_moe_down(const void* h, const void* w_down, const void* b_down, const int32_t* ids,
+                 const float* weights, const int32_t* expert_offsets, const int32_t* row_pos,
+                 const void* residual, void* y, void* workspace, int32_t T, int32_t top_k, int32_t E,
+                 int32_t d, int32_t I, int64_t ldh, int64_t ldw, int64_t expert_stride, int64_t ldy,
+                 int64_t ldr, int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

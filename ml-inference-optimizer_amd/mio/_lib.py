@@ -148,6 +148,13 @@ EXPORTS = (
     "mio_qknorm_rope_and_cache_varlen_kv8",
     "mio_qknorm_rope_rows",
     "mio_sample_tokens",
+    "mio_moe_route",
+    "mio_moe_up_splits",
+    "mio_moe_up_workspace_bytes",
+    "mio_moe_down_splits",
+    "mio_moe_down_workspace_bytes",
+    "mio_moe_up",
+    "mio_moe_down",
 )
 
 
@@ -399,6 +406,26 @@ def _load() -> C.CDLL:
     # sampling: logits, ld, temperature, top_k, top_p, min_p, u, tokens_out, kept_out, probs_out, ld_probs, B, V, dtype, stream
     lib.mio_sample_tokens.argtypes = [vp, i64] + [vp] * 8 + [i64, i32, i32, i32, vp]
     lib.mio_sample_tokens.restype = i32
+    # mixture of experts: logits, ld, the five outputs, T, E, top_k, renormalize, dtype, stream
+    lib.mio_moe_route.argtypes = [vp, i64] + [vp] * 5 + [i32] * 5 + [vp]
+    lib.mio_moe_route.restype = i32
+    # the grouped GEMMs' plan queries: T, top_k, E, N, K (up: and act)
+    lib.mio_moe_up_splits.argtypes = [i32] * 6
+    lib.mio_moe_up_splits.restype = i32
+    lib.mio_moe_up_workspace_bytes.argtypes = [i32] * 6
+    lib.mio_moe_up_workspace_bytes.restype = C.c_size_t
+    lib.mio_moe_down_splits.argtypes = [i32] * 5
+    lib.mio_moe_down_splits.restype = i32
+    lib.mio_moe_down_workspace_bytes.argtypes = [i32] * 5
+    lib.mio_moe_down_workspace_bytes.restype = C.c_size_t
+    # x, w_up, b_up, w_gate, b_gate, expert_offsets, sorted_rows, h, workspace, T, top_k, E, I, d, ldx, ldw, expert_stride, ldh, act,
+    # dtype, stream
+    lib.mio_moe_up.argtypes = [vp] * 9 + [i32] * 5 + [i64] * 4 + [i32, i32, vp]
+    lib.mio_moe_up.restype = i32
+    # h, w_down, b_down, ids, weights, expert_offsets, row_pos, residual, y, workspace, T, top_k, E, d, I, ldh, ldw, expert_stride,
+    # ldy, ldr, dtype, stream
+    lib.mio_moe_down.argtypes = [vp] * 10 + [i32] * 5 + [i64] * 5 + [i32, vp]
+    lib.mio_moe_down.restype = i32
     return lib
 
 

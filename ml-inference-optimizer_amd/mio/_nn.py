@@ -91,6 +91,16 @@ class CastCache:
         return self._memo(("w8", id(p)), (p.data_ptr(), p._version, dtype, p.device, "w8"),
                           lambda: ops.quantize_weight_w8(self.get(p, dtype)))
 
+    def get_row_padded(self, p: torch.Tensor, dtype: torch.dtype, multiple: int) -> torch.Tensor:
+        """The 2-D parameter in dtype with zero rows appended up to the next multiple of `multiple` rows (itself where it has that
+        many already), made again when its version changes."""
+        w = self.get(p, dtype)
+        pad = -w.shape[0] % multiple
+        if pad == 0:
+            return w
+        return self._memo(("rp", id(p), multiple), (p.data_ptr(), p._version, dtype, p.device, "row_padded"),
+                          lambda: torch.cat([w, w.new_zeros(pad, w.shape[1])]))
+
     def get_cat(self, ps: Tuple[Optional[torch.Tensor], ...], dtype: torch.dtype, blocked: bool = False) -> Optional[torch.Tensor]:
         """The row-concatenation of the parameters ps in dtype (None where they are: biases that are not there), or with blocked
         that weight in the blocked layout; made again when one of them changes."""

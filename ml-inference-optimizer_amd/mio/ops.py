@@ -19,6 +19,10 @@ same exception types for the same conditions):
   sample_tokens / sampling_probs
                                token sampling (not a reference kernel: its facade promises .generate()): [B, V] logits to token
                                ids in one launch -- greedy, temperature, top-k, top-p, min-p per row from device tensors
+  moe_route / moe_up / moe_down / moe_mlp
+                               mixture-of-experts MLP of a decode step (not a reference kernel: its models are dense): the router
+                               (top-k of a softmax over all experts, routed rows grouped by expert, all on the device) and the
+                               grouped up / down GEMMs over stacked expert weights with the combine
 There is no fallback path: a non-zero return from the library raises RuntimeError.
 """
 from __future__ import annotations
@@ -29,7 +33,7 @@ import ctypes as C
 import math
 import operator
 import types
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -1880,6 +1884,231 @@ def sampling_probs(logits, temperature, top_k=None, top_p=None, min_p=None):
     """The filtered distribution sample_tokens draws from, fp32 [..., V]: w_i / Z on the kept set, exactly 0 elsewhere, one-hot
     on a greedy row, all zero on a row with no finite logit.  The arguments of sample_tokens without u: nothing is drawn."""
     return _sample("sampling_probs", logits, temperature, top_k, top_p, min_p, None, None, False, False, True)[2]
+
+
+# ------------------------------------------------------------------------------------------------
+# mixture-of-experts MLP for decode steps: router, grouped up projection, grouped down projection + combine
+# ------------------------------------------------------------------------------------------------
+MOE_MAX_TOKENS, MOE_MAX_EXPERTS, MOE_MAX_TOP_K = 64, 256, 8
+
+
+class MoERoute(NamedTuple):
+    """What moe_route decides, all device tensors (semantics: include/mio_hip.h): ids int32 [T, k] and weights fp32 [T, k] per
+    token; expert_offsets int32 [E + 1], sorted_rows int32 [T k] and row_pos int32 [T k], the routed rows r = t k + j grouped by
+    expert in ascending r and the inverse of that permutation."""
+    ids: torch.Tensor
+    weights: torch.Tensor
+    expert_offsets: torch.Tensor
+    sorted_rows: torch.Tensor
+    row_pos: torch.Tensor
+    top_k: int
+    num_experts: int
+
+
+def _moe_route_ok(route, who: str, device) -> Tuple[int, int, int]:
+    """(T, k, E) of a MoERoute whose tensors are what the kernels take from raw pointers."""
+    if not isinstance(route, MoERoute):
+        raise ValueError(f"{who}: route must be a MoERoute (ops.moe_route)")
+    T, k, E = route.ids.shape[0], route.top_k, route.num_experts
+    want = (("ids", route.ids, torch.int32, (T, k)), ("weights", route.weights, torch.float32, (T, k)),
+            ("expert_offsets", route.expert_offsets, torch.int32, (E + 1,)), ("sorted_rows", route.sorted_rows, torch.int32, (T * k,)),
+            ("row_pos", route.row_pos, torch.int32, (T * k,)))
+    for name, t, dtype, shape in want:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+            raise ValueError(f"{who}: route.{name} must be a tensor on the activations' device")
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{who}: route.{name} must be a contiguous {dtype} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    return T, k, E
+
+
+def moe_route(router_logits, top_k: int, renormalize: bool = True, out: Optional[MoERoute] = None) -> MoERoute:
+    """Route T <= 64 tokens over E <= 256 experts in one launch (mio_moe_route): router_logits [T, E] (or [..., E], flattened; bf16,
+    fp16 or fp32, last-dim stride 1) -> the top_k experts of every token in the sampler's order (ties to the lowest index, NaN as
+    -inf), their softmax-over-all-experts weights (renormalize: divided by their sum), and the routed rows grouped by expert.
+    out: a MoERoute of the same (T, top_k, E) to write into (a captured step reuses its buffers).  T == 0 launches nothing and
+    zeroes expert_offsets (out's too).  Nothing is read back to the host."""
+    who = "moe_route"
+    if not isinstance(router_logits, torch.Tensor):
+        raise ValueError(f"{who}: router_logits must be a tensor")
+    _need_cuda(router_logits)
+    if router_logits.dtype not in _SAMPLE_DTYPES:
+        raise ValueError(f"{who}: router_logits must be bf16, fp16 or fp32, got {router_logits.dtype}")
+    if router_logits.dim() < 1:
+        raise ValueError(f"{who}: router_logits must be [..., E]")
+    E = router_logits.shape[-1]
+    k = operator.index(top_k)
+    if not 1 <= E <= MOE_MAX_EXPERTS:
+        raise ValueError(f"{who}: 1 .. {MOE_MAX_EXPERTS} experts, got {E}")
+    if not 1 <= k <= min(E, MOE_MAX_TOP_K):
+        raise ValueError(f"{who}: top_k must be in [1, min(E, {MOE_MAX_TOP_K})], got {k}")
+    x = router_logits if router_logits.dim() == 2 else router_logits.reshape(-1, E)
+    if x.stride(-1) != 1 and E > 1:
+        x = x.contiguous()
+    T = x.shape[0]
+    if T > MOE_MAX_TOKENS:
+        raise ValueError(f"{who} takes at most {MOE_MAX_TOKENS} tokens (decode steps only), got {T}")
+    ld = x.stride(0) if T > 1 else E
+    if ld < E or x.data_ptr() % 16:
+        x, ld = x.contiguous(), E
+        if x.data_ptr() % 16:  # (already contiguous at a storage offset off 16 bytes: contiguous() returned it as it was)
+            x = x.clone()
+    dev = x.device
+    if out is None:
+        i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)  # noqa: E731
+        out = MoERoute(i32(T, k), torch.empty(T, k, dtype=torch.float32, device=dev), i32(E + 1), i32(T * k), i32(T * k), k, E)
+    elif _moe_route_ok(out, who, dev) != (T, k, E):
+        raise ValueError(f"{who}: out was made for another (T, top_k, E)")
+    if T == 0:  # (nothing is launched: the offsets of an empty routing are zeros, in the caller's buffer as in ours)
+        out.expert_offsets.zero_()
+    else:
+        check(lib.mio_moe_route(x.data_ptr(), ld, out.ids.data_ptr(), out.weights.data_ptr(), out.expert_offsets.data_ptr(),
+                                out.sorted_rows.data_ptr(), out.row_pos.data_ptr(), T, E, k, 1 if renormalize else 0,
+                                _SAMPLE_DTYPES[x.dtype], _stream()))
+    return out
+
+
+def _moe_act(activation: str) -> int:
+    if activation not in _ACT:
+        raise ValueError(f"Unsupported activation function: {activation}")
+    return _ACT[activation]
+
+
+def moe_up_splits(T: int, top_k: int, E: int, I: int, d: int, activation: str = "swiglu") -> int:
+    """The slices of K = d a moe_up call of this shape runs (1: one launch, no workspace).  Host-only; ValueError where the call
+    would be refused."""
+    n = lib.mio_moe_up_splits(T, top_k, E, I, d, _moe_act(activation))
+    if n < 0:
+        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def moe_down_splits(T: int, top_k: int, E: int, d: int, I: int) -> int:
+    """The slices of K = I a moe_down call of this shape runs.  Host-only; ValueError where the call would be refused."""
+    n = lib.mio_moe_down_splits(T, top_k, E, d, I)
+    if n < 0:
+        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def _moe_weight(w, E: int, dtype, name: str, who: str, like=None) -> torch.Tensor:
+    """A stacked expert weight [E, N, K] as the kernels take it: last-dim stride 1, row and expert strides multiples of 8, 16-byte
+    aligned (a copy otherwise); like: the weight it must share shape and strides with (the SwiGLU gate and up)."""
+    if not isinstance(w, torch.Tensor) or w.dim() != 3 or w.shape[0] != E:
+        raise ValueError(f"{who}: {name} must be a stacked expert weight [E = {E}, N, K]")
+    _need_cuda(w)
+    if w.dtype != dtype:
+        raise ValueError(f"{who}: {name} must have the activation dtype {dtype}, got {w.dtype}")
+    N, K = w.shape[1:]
+    ok = (w.stride(2) == 1 and w.stride(1) % 8 == 0 and w.stride(1) >= K and w.stride(0) % 8 == 0
+          and w.stride(0) >= (N - 1) * w.stride(1) + K and w.data_ptr() % 16 == 0)
+    if not ok or (like is not None and w.stride() != like.stride()):
+        w = w.contiguous()
+    return w
+
+
+def _moe_bias(b, E: int, N: int, dtype, name: str, who: str):
+    if b is None:
+        return None
+    _need_cuda(b)
+    if b.dtype != dtype or tuple(b.shape) != (E, N):
+        raise ValueError(f"{who}: {name} must be a {dtype} tensor of shape ({E}, {N}), got {b.dtype} {tuple(b.shape)}")
+    return b if b.is_contiguous() and b.data_ptr() % 16 == 0 else b.contiguous().clone()
+
+
+def _pad8(n: int) -> int:
+    return (n + 7) // 8 * 8
+
+
+def _ld(t: torch.Tensor, n: int) -> int:
+    """The row stride of t [rows, n] as the launch takes it (a single row has no stride to speak of)."""
+    return t.stride(0) if t.shape[0] > 1 else _pad8(n)
+
+
+def moe_up(x, route: MoERoute, w_up, act: str = "swiglu", w_gate=None, b_up=None, b_gate=None, out=None):
+    """The grouped up projection (mio_moe_up): x [T, d], w_up (and w_gate for swiglu) [E, I, d] -> h [T k, I] BY SORTED POSITION:
+    row p is act(x[t] w_up[e]^T + b_up[e]) (swiglu: silu(x[t] w_gate[e]^T + b_gate[e]) * that) for the expert e and the token
+    t = sorted_rows[p] // k of position p.  One launch over all experts (two when the plan splits K); experts without a routed
+    row are not read.  out: h to write into, [T k, I], row stride a multiple of 8."""
+    who = "moe_up"
+    _need_cuda(x)
+    a = _moe_act(act)
+    dt = _dtype_id(x)
+    if x.dim() != 2:
+        raise ValueError(f"{who}: x must be [T, d], got {tuple(x.shape)}")
+    T, k, E = _moe_route_ok(route, who, x.device)
+    if x.shape[0] != T:
+        raise ValueError(f"{who}: x has {x.shape[0]} rows, the route {T} tokens")
+    glu = a == _lib.ACT_SWIGLU
+    if glu != (w_gate is not None):
+        raise ValueError("SwiGLU activation requires gate weights" if glu else f"{who}: w_gate belongs to act='swiglu'")
+    w = _moe_weight(w_up, E, x.dtype, "w_up", who)
+    I, d = w.shape[1:]
+    if x.shape[1] != d:
+        raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match input features {x.shape[1]}")
+    g = None
+    if glu:
+        if w_gate.shape != w_up.shape:
+            raise ValueError(f"{who}: w_gate must have w_up's shape")
+        g = _moe_weight(w_gate, E, x.dtype, "w_gate", who, like=w)
+        if g.stride() != w.stride():
+            w = w.contiguous()
+    bu = _moe_bias(b_up, E, I, x.dtype, "b_up", who)
+    bg = _moe_bias(b_gate, E, I, x.dtype, "b_gate", who) if glu else None
+    x2 = _rows16(x)
+    if out is None:
+        out = torch.empty(T * k, _pad8(I), dtype=x.dtype, device=x.device)[:, :I]
+    elif tuple(out.shape) != (T * k, I) or out.dtype != x.dtype or (I > 1 and out.stride(1) != 1) or out.stride(0) % 8:
+        raise ValueError(f"{who}: out must be [{T * k}, {I}] {x.dtype} with a row stride that is a multiple of 8")
+    if T == 0:
+        return out
+    nbytes = lib.mio_moe_up_workspace_bytes(T, k, E, I, d, a)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    check(lib.mio_moe_up(x2.data_ptr(), w.data_ptr(), _ptr(bu), _ptr(g), _ptr(bg), route.expert_offsets.data_ptr(),
+                         route.sorted_rows.data_ptr(), out.data_ptr(), _ptr(ws), T, k, E, I, d, _ld(x2, d), w.stride(1), w.stride(0),
+                         _ld(out, I), a, dt, _stream()))
+    return out
+
+
+def moe_down(h, route: MoERoute, w_down, b_down=None, residual=None, out=None):
+    """The grouped down projection and the combine (mio_moe_down): h [T k, I] by sorted position (moe_up's output), w_down
+    [E, d, I] -> y [T, d] = sum_j weights[t, j] (h[row_pos[t k + j]] w_down[e]^T + b_down[e]) (+ residual[t]), e = ids[t, j]: the
+    slots summed in fp32 in slot order and rounded once.  residual [T, d] is also where a shared expert's output goes in."""
+    who = "moe_down"
+    _need_cuda(h)
+    dt = _dtype_id(h)
+    T, k, E = _moe_route_ok(route, who, h.device)
+    if h.dim() != 2 or h.shape[0] != T * k:
+        raise ValueError(f"{who}: h must be [T k = {T * k}, I], got {tuple(h.shape)}")
+    w = _moe_weight(w_down, E, h.dtype, "w_down", who)
+    d, I = w.shape[1:]
+    if h.shape[1] != I:
+        raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match h's {h.shape[1]} features")
+    bd = _moe_bias(b_down, E, d, h.dtype, "b_down", who)
+    h2 = _rows16(h)
+    _res_ok(residual, T * d, h.dtype)
+    r2 = None if residual is None else _rows16(residual.reshape(T, d))
+    if r2 is not None and T > 1 and r2.stride(0) % 8:  # (d % 8 != 0, contiguous: rows at the stride the kernel's loads are laid out for)
+        r2 = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d].copy_(r2)
+    if out is None:
+        out = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d]
+    elif tuple(out.shape) != (T, d) or out.dtype != h.dtype or (d > 1 and out.stride(1) != 1) or out.stride(0) % 8:
+        raise ValueError(f"{who}: out must be [{T}, {d}] {h.dtype} with a row stride that is a multiple of 8")
+    if T == 0:
+        return out
+    nbytes = lib.mio_moe_down_workspace_bytes(T, k, E, d, I)
+    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=h.device)
+    check(lib.mio_moe_down(h2.data_ptr(), w.data_ptr(), _ptr(bd), route.ids.data_ptr(), route.weights.data_ptr(),
+                           route.expert_offsets.data_ptr(), route.row_pos.data_ptr(), _ptr(r2), out.data_ptr(), ws.data_ptr(), T, k, E, d,
+                           I, _ld(h2, I), w.stride(1), w.stride(0), _ld(out, d), 0 if r2 is None else _ld(r2, d), dt, _stream()))
+    return out
+
+
+def moe_mlp(x, route: MoERoute, w_up, w_down, act: str = "swiglu", w_gate=None, b_up=None, b_gate=None, b_down=None,
+            residual=None, out=None):
+    """The experts' MLP of a decode step under a routing: moe_up, then moe_down.  x [T, d] (T <= 64), w_up / w_gate [E, I, d],
+    w_down [E, d, I], biases [E, I] / [E, d].  h and both workspaces come from torch's allocator; nothing synchronises, so the
+    call can be captured in a graph."""
+    return moe_down(moe_up(x, route, w_up, act, w_gate, b_up, b_gate), route, w_down, b_down, residual, out)
 
 
 # ------------------------------------------------------------------------------------------------
