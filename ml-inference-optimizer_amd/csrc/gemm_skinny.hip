@@ -20,100 +20,23 @@
 #include "gemm_skinny_common.h"
 
 constexpr SkinnyForm FORM = SKINNY_W16;  // this unit's weight form (gemm_skinny_plan.h)
-constexpr int SKINNY_KSTEP = FORM.kstep;
-static_assert(FORM.sets(false) == 2 && FORM.sets(true) == 2, "the K loop below is double-buffered");
 
+// The K loop itself is gemm_skinny_w16_head.inc + gemm_skinny_w16_loop.inc, shared with the mixture-of-experts unit (moe.hip).
+// The dense rows description: the weight starts at p.w, all MF fragments are live, staged row r < M is row r of x.
 template <typename T, int MF, bool GLU>
 __global__ __launch_bounds__(256) void gemm_skinny_kernel(const SkinnyDev p) {
-  using X8 = typename DT<T>::x8;
-  constexpr int SKC = FORM.chunk(GLU);  // k per chunk
-  constexpr int KS = SKC / SKINNY_KSTEP, PCS = SKC / 8, ROWS = MF * 16, ROWB = SKC * 2;
-  constexpr int XPT = ROWS * PCS / 256;  // 16-byte pieces of the x chunk per thread
-  static_assert(PCS >= 16 && ROWS * PCS % 256 == 0, "chunk shape");
-  __shared__ __attribute__((aligned(16))) char sx[2][ROWS * ROWB];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, q = lane >> 4;
-  const int n0 = blockIdx.x * SKINNY_BN + wave * 16;
-  const bool active = n0 < p.N;  // (a wave past the last column stages x and keeps the barriers, nothing else)
-  const int s = blockIdx.y;
-  const int kb = (int)((int64_t)s * p.steps / p.nsplit) * SKINNY_KSTEP;
-  const int ke = min(p.K, (int)((int64_t)(s + 1) * p.steps / p.nsplit) * SKINNY_KSTEP);
-  const int nc = (ke - kb + SKC - 1) / SKC;
-
-  const int nrow = min(n0 + c, p.N - 1);
-  const T* wrow = (const T*)p.w + (int64_t)nrow * p.ldw;
-  const T* grow = GLU ? (const T*)p.wg + (int64_t)nrow * p.ldw : nullptr;
-  const T* xg = (const T*)p.x;
-
-  auto load_w = [&](u32x4_t (&wr)[KS], u32x4_t (&gr)[GLU ? KS : 1], int ch) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int k = kb + ch * SKC + ks * SKINNY_KSTEP + 8 * q;
-      const bool ok = active && k < ke;
-      wr[ks] = (u32x4_t){0u, 0u, 0u, 0u};
-      if (ok) wr[ks] = *(const u32x4_t*)(wrow + k);
-      if constexpr (GLU) {
-        gr[ks] = (u32x4_t){0u, 0u, 0u, 0u};
-        if (ok) gr[ks] = *(const u32x4_t*)(grow + k);
-      }
-    }
-  };
-  auto stage_x = [&](int ch, int buf) {
-    u32x4_t v[XPT];
-#pragma unroll
-    for (int i = 0; i < XPT; ++i) {
-      const int idx = tid + i * 256, row = idx / PCS, pc = idx % PCS;
-      const int k = kb + ch * SKC + pc * 8;
-      v[i] = (u32x4_t){0u, 0u, 0u, 0u};
-      if (row < p.M && k < ke) v[i] = *(const u32x4_t*)(xg + (int64_t)row * p.ldx + k);
-    }
-#pragma unroll
-    for (int i = 0; i < XPT; ++i) {
-      const int idx = tid + i * 256, row = idx / PCS, pc = idx % PCS;
-      *(u32x4_t*)(sx[buf] + row * ROWB + ((pc ^ (row & 15)) * 16)) = v[i];
-    }
-  };
-
-  f32x4_t acc[MF], accg[GLU ? MF : 1];
-#pragma unroll
-  for (int mf = 0; mf < MF; ++mf) {
-    acc[mf] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    if constexpr (GLU) accg[mf] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  }
-  auto compute = [&](const u32x4_t (&wr)[KS], const u32x4_t (&gr)[GLU ? KS : 1], int buf) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int mf = 0; mf < MF; ++mf) {
-        const X8 xf = __builtin_bit_cast(X8, *(const u32x4_t*)(sx[buf] + (mf * 16 + c) * ROWB + (((ks * 4 + q) ^ c) * 16)));
-        acc[mf] = DT<T>::mfma16(__builtin_bit_cast(X8, wr[ks]), xf, acc[mf]);
-        if constexpr (GLU) accg[mf] = DT<T>::mfma16(__builtin_bit_cast(X8, gr[ks]), xf, accg[mf]);
-      }
-    }
-  };
-
-  // Two register sets: the loads of chunk ch + 1 are issued before chunk ch is multiplied.  One barrier per chunk: the x buffer
-  // written for chunk ch was last read for chunk ch - 2, before the barrier of chunk ch - 1.
-  u32x4_t wa[KS], wb[KS], ga[GLU ? KS : 1], gb[GLU ? KS : 1];
-  if (nc > 0) load_w(wa, ga, 0);
-  for (int ch = 0; ch < nc; ch += 2) {
-    stage_x(ch, 0);
-    __syncthreads();
-    if (ch + 1 < nc) load_w(wb, gb, ch + 1);
-    compute(wa, ga, 0);
-    if (ch + 1 >= nc) break;
-    stage_x(ch + 1, 1);
-    __syncthreads();
-    if (ch + 2 < nc) load_w(wa, ga, ch + 2);
-    compute(wb, gb, 1);
-  }
+  const auto wbase = [] { return (int64_t)0; };
+#include "gemm_skinny_w16_head.inc"
+  constexpr int nf = MF;
+  constexpr bool all_live = true;
+  const auto xhas = [&](int, int r) { return r < p.M; };
+  const auto xrow = [](int, int r) { return r; };
+#include "gemm_skinny_w16_loop.inc"
 
   if (!active) return;
   const int n = n0 + 4 * q;
   if (n >= p.N) return;
-  skinny_write<T, MF, GLU, false>(p, s, c, n, acc, accg);
+  skinny_write<T, MF, GLU, false>(skinny_finish_args(p), p.ws, p.nsplit, p.M, s, c, n, 0, p.M, acc, accg);
 }
 
 #define SKINNY_KERNELS(T, GLU)                                                                                        \

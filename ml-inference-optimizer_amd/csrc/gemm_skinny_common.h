@@ -25,6 +25,33 @@ struct SkinnyDev {
   const float* scale_g;  // SCALED and SwiGLU only: the gate weight's
 };
 
+// What the epilogue reads, and nothing else: a launch's (skinny_finish_args) or, in moe.hip, one expert's.
+struct SkinnyFinish {
+  const void* bias;
+  const void* bias_g;
+  const void* res;
+  void* y;
+  int64_t ldy, ldr;
+  int N, act;
+  const float* scale;
+  const float* scale_g;
+};
+
+__device__ __forceinline__ SkinnyFinish skinny_finish_args(const SkinnyDev& p) {
+  return {p.bias, p.bias_g, p.res, p.y, p.ldy, p.ldr, p.N, p.act, p.scale, p.scale_g};
+}
+
+// The shape of the 16-bit K loop (gemm_skinny_w16_head.inc, gemm_skinny_w16_loop.inc) at MF row fragments, from the form's values
+constexpr int SKINNY_KSTEP = SKINNY_W16.kstep;
+static_assert(SKINNY_W16.sets(false) == 2 && SKINNY_W16.sets(true) == 2, "the 16-bit K loop is double-buffered");
+template <int MF, bool GLU>
+struct SkinnyW16Tile {
+  static constexpr int SKC = SKINNY_W16.chunk(GLU);  // k per chunk
+  static constexpr int KS = SKC / SKINNY_KSTEP, PCS = SKC / 8, ROWS = MF * 16, ROWB = SKC * 2;
+  static constexpr int XPT = ROWS * PCS / 256;  // 16-byte pieces of the x chunk per thread
+  static_assert(PCS >= 16 && ROWS * PCS % 256 == 0, "chunk shape");
+};
+
 __device__ __forceinline__ float skinny_act(int act, float v) {
   switch (act) {
     case MIO_ACT_GELU_TANH: return gemm_act<MIO_ACT_GELU_TANH>(v);
@@ -44,7 +71,7 @@ __device__ __forceinline__ float skinny_pre(float acc, const float* scale, float
 
 // The one epilogue, of both kernels: row m, columns n .. n + 3 (those below N), from the fp32 sums v (and g, the gate's).
 template <typename T, bool GLU, bool SCALED = false>
-__device__ __forceinline__ void skinny_finish(const SkinnyDev& p, int m, int n, const float (&v)[4], const float (&g)[4]) {
+__device__ __forceinline__ void skinny_finish(const SkinnyFinish& p, int m, int n, const float (&v)[4], const float (&g)[4]) {
   const T* bias = (const T*)p.bias;
   const T* bias_g = (const T*)p.bias_g;
   const T* rrow = p.res ? (const T*)p.res + (int64_t)m * p.ldr : nullptr;
@@ -68,54 +95,57 @@ __device__ __forceinline__ void skinny_finish(const SkinnyDev& p, int m, int n, 
   }
 }
 
-// A lane's share of a workgroup's result, lane (c, q) of the wave at columns n0: rows 16 mf + c, columns n0 + 4 q .. + 3, through
-// the epilogue (one slice) or into the fp32 partials of slice s.
+// A lane's share of a workgroup's result, lane (c, q) of the wave at columns n0: of the cnt rows at r0 (the dense units: all M
+// from 0; an expert: its sorted positions) rows r0 + 16 mf + c, columns n = n0 + 4 q .. + 3, through the epilogue (ws null: one
+// slice) or into slice s of the fp32 partials ws [nsplit][rows][N] (SwiGLU: then the gate half).  The launch's values come by
+// reference, so that they are read where they are used, as they were when every kernel read its own launch arguments here: by
+// value the compiler orders the K-loop kernels' code differently.
 template <typename T, int MF, bool GLU, bool SCALED>
-__device__ __forceinline__ void skinny_write(const SkinnyDev& p, int s, int c, int n, const f32x4_t (&acc)[MF],
+__device__ __forceinline__ void skinny_write(const SkinnyFinish& f, float* const& ws, const int& nsplit, const int& rows, int s, int c,
+                                             int n, const int& r0, const int& cnt, const f32x4_t (&acc)[MF],
                                              const f32x4_t (&accg)[GLU ? MF : 1]) {
 #pragma unroll
   for (int mf = 0; mf < MF; ++mf) {
     const int m = mf * 16 + c;
-    if (m >= p.M) continue;
-    if (p.ws == nullptr) {
+    if (m >= cnt) continue;
+    const int pos = r0 + m;
+    if (ws == nullptr) {
       const float v[4] = {acc[mf][0], acc[mf][1], acc[mf][2], acc[mf][3]};
       float g[4] = {0.f, 0.f, 0.f, 0.f};
       if constexpr (GLU) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) g[i] = accg[mf][i];
       }
-      skinny_finish<T, GLU, SCALED>(p, m, n, v, g);
+      skinny_finish<T, GLU, SCALED>(f, pos, n, v, g);
     } else {
-      const int64_t plane = (int64_t)p.M * p.N;
-      float* dst = p.ws + (int64_t)s * plane + (int64_t)m * p.N + n;
-      if ((p.N & 3) == 0) {  // (n + 3 < N then, and the partial rows are 16-byte aligned)
+      const int64_t plane = (int64_t)rows * f.N;
+      float* dst = ws + (int64_t)s * plane + (int64_t)pos * f.N + n;
+      if ((f.N & 3) == 0) {  // (n + 3 < N then, and the partial rows are 16-byte aligned)
         *(f32x4_t*)dst = acc[mf];
-        if constexpr (GLU) *(f32x4_t*)(dst + (int64_t)p.nsplit * plane) = accg[mf];
+        if constexpr (GLU) *(f32x4_t*)(dst + (int64_t)nsplit * plane) = accg[mf];
       } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          if (n + i < p.N) {
+          if (n + i < f.N) {
             dst[i] = acc[mf][i];
-            if constexpr (GLU) dst[(int64_t)p.nsplit * plane + i] = accg[mf][i];
+            if constexpr (GLU) dst[(int64_t)nsplit * plane + i] = accg[mf][i];
           }
       }
     }
   }
 }
 
-// The second launch: one thread per (row, 4 columns) sums the slices' partials in index order and runs the epilogue.
-template <typename T, bool GLU, bool SCALED = false>
-__global__ __launch_bounds__(256) void gemm_skinny_reduce_kernel(const SkinnyDev p) {
-  const int ngrp = (p.N + 3) / 4;
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (int64_t)p.M * ngrp) return;
-  const int m = (int)(idx / ngrp), n = (int)(idx % ngrp) * 4;
-  const int64_t plane = (int64_t)p.M * p.N;
-  const float* src = p.ws + (int64_t)m * p.N + n;
-  const float* srcg = src + (int64_t)p.nsplit * plane;
-  float v[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
-  if ((p.N & 3) == 0) {
-    for (int s = 0; s < p.nsplit; ++s) {
+// The slice sum: the partials ws [nsplit][rows][N] of row pos, columns n .. n + 3 (those below N), added in slice order
+// starting from 0.f into v; GLU: and the gate half's, which follows the nsplit planes of rows * N, into g.
+template <bool GLU>
+__device__ __forceinline__ void skinny_slice_sum(const float* ws, int nsplit, int64_t plane, int N, int pos, int n, float (&v)[4],
+                                                 float (&g)[4]) {
+  const float* src = ws + (int64_t)pos * N + n;
+  const float* srcg = src + (int64_t)nsplit * plane;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] = g[i] = 0.f;
+  if ((N & 3) == 0) {
+    for (int s = 0; s < nsplit; ++s) {
       const f32x4_t t = *(const f32x4_t*)(src + s * plane);
 #pragma unroll
       for (int i = 0; i < 4; ++i) v[i] += t[i];
@@ -126,15 +156,26 @@ __global__ __launch_bounds__(256) void gemm_skinny_reduce_kernel(const SkinnyDev
       }
     }
   } else {
-    for (int s = 0; s < p.nsplit; ++s)
+    for (int s = 0; s < nsplit; ++s)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        if (n + i < p.N) {
+        if (n + i < N) {
           v[i] += src[s * plane + i];
           if constexpr (GLU) g[i] += srcg[s * plane + i];
         }
   }
-  skinny_finish<T, GLU, SCALED>(p, m, n, v, g);
+}
+
+// The second launch: one thread per (row, 4 columns) sums the slices' partials in index order and runs the epilogue.
+template <typename T, bool GLU, bool SCALED = false>
+__global__ __launch_bounds__(256) void gemm_skinny_reduce_kernel(const SkinnyDev p) {
+  const int ngrp = (p.N + 3) / 4;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)p.M * ngrp) return;
+  const int m = (int)(idx / ngrp), n = (int)(idx % ngrp) * 4;
+  float v[4], g[4];
+  skinny_slice_sum<GLU>(p.ws, p.nsplit, (int64_t)p.M * p.N, p.N, m, n, v, g);
+  skinny_finish<T, GLU, SCALED>(skinny_finish_args(p), m, n, v, g);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------

@@ -11,6 +11,13 @@
 
 #include "mio_hip.h"
 
+// what a kernel calls as well: __host__ __device__ under a HIP compiler, nothing under a plain host compiler
+#if defined(__HIP__) || defined(__HIPCC__)
+#define SKINNY_HD __host__ __device__
+#else
+#define SKINNY_HD
+#endif
+
 constexpr int SKINNY_M_MAX = 64;   // 1 .. 4 row fragments of 16
 constexpr int SKINNY_BN = 64;      // output columns per workgroup: 4 waves x one 16-row weight fragment
 // workgroups the split aims for: two per CU.  tools/skinny_gemm_bench.py, profiles/skinny_gemm.md: the sweep ran with this value.
@@ -95,10 +102,16 @@ struct SkinnyPlan {
   bool glu;
 };
 
-// k range of slice s: whole steps, at most one step apart in length, the last one cut at K
+// k range of slice s of nsplit over `steps` steps of kstep: whole steps, at most one step apart in length, the last one cut at K.
+// The one statement of it: the kernels of both forms and of the mixture-of-experts unit (moe.hip) call it, as do the hosts' slice
+// queries.  (32-bit like steps itself: steps * kstep <= K + kstep - 1, which skinny_plan has formed as an int to get steps.)
+SKINNY_HD inline void skinny_slice_range(int steps, int nsplit, int kstep, int32_t K, int s, int32_t& kb, int32_t& ke) {
+  kb = (int32_t)((int64_t)s * steps / nsplit) * kstep;
+  const int32_t end = (int32_t)((int64_t)(s + 1) * steps / nsplit) * kstep;
+  ke = K < end ? K : end;
+}
 static inline void skinny_slice(const SkinnyForm& f, const SkinnyPlan& pl, int32_t K, int s, int32_t& kb, int32_t& ke) {
-  kb = (int32_t)((int64_t)s * pl.steps / pl.nsplit) * f.kstep;
-  ke = (int32_t)std::min<int64_t>(K, ((int64_t)(s + 1) * pl.steps / pl.nsplit) * f.kstep);
+  skinny_slice_range(pl.steps, pl.nsplit, f.kstep, K, s, kb, ke);
 }
 
 // Split rule.  Slices for SKINNY_WGS workgroups, each at least min_k_per_row * M elements (rounded up to whole steps): a slice's

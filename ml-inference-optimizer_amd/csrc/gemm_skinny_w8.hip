@@ -51,8 +51,8 @@ __global__ __launch_bounds__(256) void gemm_skinny_w8_kernel(const SkinnyDev p) 
   const int n0 = blockIdx.x * SKINNY_BN + wave * 16;
   const bool active = n0 < p.N;  // (a wave past the last column stages x and keeps the barriers, nothing else)
   const int s = blockIdx.y;
-  const int kb = (int)((int64_t)s * p.steps / p.nsplit) * SKW8_KSTEP;
-  const int ke = min(p.K, (int)((int64_t)(s + 1) * p.steps / p.nsplit) * SKW8_KSTEP);
+  int kb, ke;
+  skinny_slice_range(p.steps, p.nsplit, SKW8_KSTEP, p.K, s, kb, ke);
   const int nc = (ke - kb + SKC - 1) / SKC;
 
   const int nrow = min(n0 + c, p.N - 1);
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_w8_kernel(const SkinnyDev p) 
   if (!active) return;
   const int n = n0 + 4 * q;
   if (n >= p.N) return;
-  skinny_write<T, MF, GLU, true>(p, s, c, n, acc, accg);
+  skinny_write<T, MF, GLU, true>(skinny_finish_args(p), p.ws, p.nsplit, p.M, s, c, n, 0, p.M, acc, accg);
 }
 
 // One-time preparation of a weight: one wave per row.  a = max |w[n, :]| in fp32 (NaN elements ignored), scale[n] = a / 448

@@ -1,7 +1,9 @@
 // Mixture-of-experts MLP for decode steps (T <= 64 tokens, E <= 256 experts, top_k <= 8): the router and the two grouped GEMMs;
 // the C-ABI entry points mio_moe_route, mio_moe_up, mio_moe_down and their host queries (semantics: include/mio_hip.h, DESIGN
-// 4.2d).  The plan (shape checks, split of K, workspaces) is moe_plan.h; the epilogue arithmetic is gemm_skinny_common.h's
-// skinny_finish, the one the decode-step GEMM runs.
+// 4.2d).  The plan (shape checks, split of K, workspaces) is moe_plan.h.  The grouped GEMM's K loop is the decode-step GEMM's,
+// the same text (gemm_skinny_w16_head.inc, gemm_skinny_w16_loop.inc) under an expert's rows description; the slice range, the
+// slice sum and the epilogue arithmetic are gemm_skinny_plan.h's skinny_slice_range and gemm_skinny_common.h's skinny_slice_sum
+// and skinny_finish, the ones the decode-step GEMM runs.
 //
 // Router: ONE workgroup of 16 waves, a wave per token (tokens wave, wave + 16, ...).  A lane holds the logits of experts lane,
 // lane + 64, lane + 128, lane + 192 as fp32 (exact for bf16 / fp16) and their order-preserving keys; top_k rounds of a wave max
@@ -10,7 +12,7 @@
 // the <= 512 chosen ids in routed-row order, which yields its count, and -- behind a prefix over the counts -- its rows in
 // ascending order by construction.  No atomic of any kind.
 //
-// Grouped GEMM: the decode-step GEMM's K loop (gemm_skinny.hip: a 16 x 32 weight fragment as the MFMA A operand straight from
+// Grouped GEMM: the decode-step GEMM's K loop (gemm_skinny_w16_loop.inc: a 16 x 32 weight fragment as the MFMA A operand straight from
 // the row-major weight into VGPRs, x rows staged through LDS with the p ^ (r & 15) swizzle, two register sets, one barrier per
 // chunk, v_mfma_f32_16x16x32) with the expert as the grid's third dimension.  A workgroup reads offsets[e], offsets[e + 1] and
 // returns at once when its expert has no rows: before any weight load and before any barrier, and the same for all its threads.
@@ -163,52 +165,33 @@ struct MoeDev {
   int T, topk, E, rows, N, K, act, nsplit, steps;
 };
 
-// the epilogue's arguments for expert e: skinny_finish reads bias, bias_g, res, y, ldy, ldr, N, act
-__device__ __forceinline__ SkinnyDev moe_finish_args(const MoeDev& p, int e) {
-  SkinnyDev sd;
-  sd.x = nullptr; sd.w = nullptr; sd.wg = nullptr;
-  sd.bias = p.bias ? (const char*)p.bias + (int64_t)e * p.N * 2 : nullptr;
-  sd.bias_g = p.bias_g ? (const char*)p.bias_g + (int64_t)e * p.N * 2 : nullptr;
-  sd.res = nullptr;
-  sd.y = p.y;
-  sd.ws = nullptr;
-  sd.ldx = 0; sd.ldw = 0; sd.ldy = p.ldy; sd.ldr = 0;
-  sd.M = p.rows; sd.N = p.N; sd.K = p.K; sd.act = p.act; sd.nsplit = p.nsplit; sd.steps = p.steps;
-  sd.scale = nullptr; sd.scale_g = nullptr;
-  return sd;
+// the epilogue's arguments for expert e: its biases, no residual, no scales
+__device__ __forceinline__ SkinnyFinish moe_finish_args(const MoeDev& p, int e) {
+  SkinnyFinish f = {};
+  f.bias = p.bias ? (const char*)p.bias + (int64_t)e * p.N * 2 : nullptr;
+  f.bias_g = p.bias_g ? (const char*)p.bias_g + (int64_t)e * p.N * 2 : nullptr;
+  f.y = p.y;
+  f.ldy = p.ldy;
+  f.N = p.N;
+  f.act = p.act;
+  return f;
 }
 
+// The K loop itself is gemm_skinny_w16_head.inc + gemm_skinny_w16_loop.inc, the decode-step GEMM's.  An expert's rows description:
+// the weight starts e * expert_stride into p.w; the fragments its cnt rows reach are live; staged row r < cnt is the x row behind
+// sorted position r0 + r, through sorted_rows (up: routed row / top_k is the token) or the position itself (down: h is stored so).
 template <typename T, int MF, bool GLU>
 __global__ __launch_bounds__(256) void moe_gemm_kernel(const MoeDev p) {
-  using X8 = typename DT<T>::x8;
-  constexpr int SKC = GLU ? MOE_CHUNK_K_GLU : MOE_CHUNK_K;  // k per chunk
-  constexpr int KS = SKC / MOE_KSTEP, PCS = SKC / 8, ROWS = MF * 16, ROWB = SKC * 2;
-  constexpr int XPT = ROWS * PCS / 256;  // 16-byte pieces of the x chunk per thread
-  static_assert(PCS >= 16 && ROWS * PCS % 256 == 0, "chunk shape");
-  __shared__ __attribute__((aligned(16))) char sx[2][ROWS * ROWB];
-
-  // the expert's rows: sorted positions [r0, r0 + cnt).  No rows: nothing of this expert is read.
+  // the expert's rows: sorted positions [r0, r0 + cnt).  No rows: nothing of this expert is read and no barrier is met, the same
+  // for all the workgroup's threads.
   const int e = blockIdx.z;
   const int r0 = max(0, min(p.offsets[e], p.rows));
-  const int cnt = min(min(p.offsets[e + 1], p.rows) - r0, ROWS);  // (an expert has at most T <= ROWS rows)
+  const int cnt = min(min(p.offsets[e + 1], p.rows) - r0, MF * 16);  // (an expert has at most T <= 16 MF rows)
   if (cnt <= 0) return;
-  const int nf = (cnt + 15) >> 4;  // row fragments this workgroup stages and multiplies
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, q = lane >> 4;
-  const int n0 = blockIdx.x * SKINNY_BN + wave * 16;
-  const bool active = n0 < p.N;  // (a wave past the last column stages x and keeps the barriers, nothing else)
-  const int s = blockIdx.y;
-  const int kb = (int)((int64_t)s * p.steps / p.nsplit) * MOE_KSTEP;
-  const int ke = min(p.K, (int)((int64_t)(s + 1) * p.steps / p.nsplit) * MOE_KSTEP);
-  const int nc = (ke - kb + SKC - 1) / SKC;
-
-  const int nrow = min(n0 + c, p.N - 1);
-  const T* wrow = (const T*)p.w + (int64_t)e * p.estride + (int64_t)nrow * p.ldw;
-  const T* grow = GLU ? (const T*)p.wg + (int64_t)e * p.estride + (int64_t)nrow * p.ldw : nullptr;
-  const T* xg = (const T*)p.x;
-
+  const int nf = (cnt + 15) >> 4;
+  constexpr bool all_live = false;
+  const auto wbase = [&] { return (int64_t)e * p.estride; };
+#include "gemm_skinny_w16_head.inc"
   // the x row behind each piece this thread stages (the same for every chunk); -1: a row past the expert's count
   int xsrc[XPT];
 #pragma unroll
@@ -220,77 +203,16 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(const MoeDev p) {
       xsrc[i] = p.sorted_rows ? min(max(p.sorted_rows[pos] / p.topk, 0), p.T - 1) : pos;
     }
   }
-
-  auto load_w = [&](u32x4_t (&wr)[KS], u32x4_t (&gr)[GLU ? KS : 1], int ch) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int k = kb + ch * SKC + ks * MOE_KSTEP + 8 * q;
-      const bool ok = active && k < ke;
-      wr[ks] = (u32x4_t){0u, 0u, 0u, 0u};
-      if (ok) wr[ks] = *(const u32x4_t*)(wrow + k);
-      if constexpr (GLU) {
-        gr[ks] = (u32x4_t){0u, 0u, 0u, 0u};
-        if (ok) gr[ks] = *(const u32x4_t*)(grow + k);
-      }
-    }
-  };
-  auto stage_x = [&](int ch, int buf) {
-    u32x4_t v[XPT];
-#pragma unroll
-    for (int i = 0; i < XPT; ++i) {
-      const int pc = (tid + i * 256) % PCS;
-      const int k = kb + ch * SKC + pc * 8;
-      v[i] = (u32x4_t){0u, 0u, 0u, 0u};
-      if (xsrc[i] >= 0 && k < ke) v[i] = *(const u32x4_t*)(xg + (int64_t)xsrc[i] * p.ldx + k);
-    }
-#pragma unroll
-    for (int i = 0; i < XPT; ++i) {
-      const int idx = tid + i * 256, row = idx / PCS, pc = idx % PCS;
-      if (row < nf * 16) *(u32x4_t*)(sx[buf] + row * ROWB + ((pc ^ (row & 15)) * 16)) = v[i];
-    }
-  };
-
-  f32x4_t acc[MF], accg[GLU ? MF : 1];
-#pragma unroll
-  for (int mf = 0; mf < MF; ++mf) {
-    acc[mf] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    if constexpr (GLU) accg[mf] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  }
-  auto compute = [&](const u32x4_t (&wr)[KS], const u32x4_t (&gr)[GLU ? KS : 1], int buf) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int mf = 0; mf < MF; ++mf) {
-        if (mf < nf) {  // (workgroup-uniform)
-          const X8 xf = __builtin_bit_cast(X8, *(const u32x4_t*)(sx[buf] + (mf * 16 + c) * ROWB + (((ks * 4 + q) ^ c) * 16)));
-          acc[mf] = DT<T>::mfma16(__builtin_bit_cast(X8, wr[ks]), xf, acc[mf]);
-          if constexpr (GLU) accg[mf] = DT<T>::mfma16(__builtin_bit_cast(X8, gr[ks]), xf, accg[mf]);
-        }
-      }
-    }
-  };
-
-  // Two register sets: the loads of chunk ch + 1 are issued before chunk ch is multiplied.  One barrier per chunk: the x buffer
-  // written for chunk ch was last read for chunk ch - 2, before the barrier of chunk ch - 1.
-  u32x4_t wa[KS], wb[KS], ga[GLU ? KS : 1], gb[GLU ? KS : 1];
-  if (nc > 0) load_w(wa, ga, 0);
-  for (int ch = 0; ch < nc; ch += 2) {
-    stage_x(ch, 0);
-    __syncthreads();
-    if (ch + 1 < nc) load_w(wb, gb, ch + 1);
-    compute(wa, ga, 0);
-    if (ch + 1 >= nc) break;
-    stage_x(ch + 1, 1);
-    __syncthreads();
-    if (ch + 2 < nc) load_w(wa, ga, ch + 2);
-    compute(wb, gb, 1);
-  }
+  const auto xhas = [&](int i, int) { return xsrc[i] >= 0; };
+  const auto xrow = [&](int i, int) { return xsrc[i]; };
+#include "gemm_skinny_w16_loop.inc"
 
   if (!active) return;
   const int n = n0 + 4 * q;
   if (n >= p.N) return;
-  // lane (c, q): rows 16 mf + c of the expert, i.e. sorted positions r0 + 16 mf + c, columns n .. n + 3
-  const SkinnyDev sd = moe_finish_args(p, e);
+  // lane (c, q): rows 16 mf + c of the expert, i.e. sorted positions r0 + 16 mf + c, columns n .. n + 3.  This is skinny_write
+  // (gemm_skinny_common.h) at (r0, cnt), written out: through the call these kernels compile to other instructions, not these.
+  const SkinnyFinish sd = moe_finish_args(p, e);
 #pragma unroll
   for (int mf = 0; mf < MF; ++mf) {
     const int m = mf * 16 + c;
@@ -322,25 +244,6 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(const MoeDev p) {
   }
 }
 
-// the slices' partials of sorted position pos, columns n .. n + 3 (those below N), summed in slice order
-__device__ __forceinline__ void moe_slice_sum(const float* ws, int nsplit, int64_t plane, int N, int pos, int n, float (&v)[4]) {
-  const float* src = ws + (int64_t)pos * N + n;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[i] = 0.f;
-  if ((N & 3) == 0) {
-    for (int s = 0; s < nsplit; ++s) {
-      const f32x4_t t = *(const f32x4_t*)(src + s * plane);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] += t[i];
-    }
-  } else {
-    for (int s = 0; s < nsplit; ++s)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (n + i < N) v[i] += src[s * plane + i];
-  }
-}
-
 // Up's second launch: one thread per (sorted position, 4 columns) sums the slices' partials in index order and runs the epilogue
 // with the biases of the position's expert: the e with offsets[e] <= pos < offsets[e + 1].
 template <typename T, bool GLU>
@@ -355,10 +258,8 @@ __global__ __launch_bounds__(256) void moe_up_reduce_kernel(const MoeDev p) {
     if (p.offsets[mid] <= pos) lo = mid;
     else hi = mid - 1;
   }
-  const int64_t plane = (int64_t)p.rows * p.N;
-  float v[4], g[4] = {0.f, 0.f, 0.f, 0.f};
-  moe_slice_sum(p.ws, p.nsplit, plane, p.N, pos, n, v);
-  if constexpr (GLU) moe_slice_sum(p.ws + (int64_t)p.nsplit * plane, p.nsplit, plane, p.N, pos, n, g);
+  float v[4], g[4];
+  skinny_slice_sum<GLU>(p.ws, p.nsplit, (int64_t)p.rows * p.N, p.N, pos, n, v, g);
   skinny_finish<T, GLU, false>(moe_finish_args(p, lo), pos, n, v, g);
 }
 
@@ -390,8 +291,8 @@ __global__ __launch_bounds__(256) void moe_down_finish_kernel(const MoeDownDev p
     const int e = min(max(p.ids[r], 0), p.E - 1);
     const int pos = min(max(p.row_pos[r], 0), p.rows - 1);
     const float wj = p.weights[r];
-    float z[4];
-    moe_slice_sum(p.ws, p.nsplit, plane, p.N, pos, n, z);
+    float z[4], unused[4];
+    skinny_slice_sum<false>(p.ws, p.nsplit, plane, p.N, pos, n, z, unused);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int nn = n + i < p.N ? n + i : p.N - 1;  // (clamped: computed, not stored)

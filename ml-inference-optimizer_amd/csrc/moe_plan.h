@@ -15,16 +15,12 @@
 constexpr int MOE_T_MAX = SKINNY_M_MAX;  // tokens of one launch: a token picks an expert at most once, so an expert has <= T rows
 constexpr int MOE_E_MAX = 256;           // experts: the router's wave holds 4 logits per lane
 constexpr int MOE_TOPK_MAX = 8;
-constexpr int MOE_KSTEP = 32;            // k per step: one v_mfma_f32_16x16x32; every slice is whole steps (the last ends at K)
-constexpr int MOE_CHUNK_K = 256, MOE_CHUNK_K_GLU = 128;  // k per chunk of the K loop, as the 16-bit decode-step GEMM's
+constexpr SkinnyForm MOE_FORM = SKINNY_W16;  // the grouped GEMM runs the 16-bit decode-step GEMM's K loop: its step and chunks
 
-struct MoePlan {
-  int rows;     // routed rows: T * k
-  int mf;       // row fragments the kernel is built for: ceil(T / 16), the host's bound on an expert's rows
-  int tiles_n;  // ceil(N / SKINNY_BN)
-  int steps;    // ceil(K / MOE_KSTEP)
-  int nsplit;   // slices of K; slice s covers steps [s * steps / nsplit, (s + 1) * steps / nsplit)
-  bool glu;
+// The 16-bit decode-step GEMM's plan at M = T: mf = ceil(T / 16) row fragments, the host's bound on an expert's rows, for which
+// the kernel is built; tiles_n; steps; glu.  nsplit is this unit's own (moe_nsplit), and the slices are skinny_slice's.
+struct MoePlan : SkinnyPlan {
+  int rows;  // routed rows: T * k
 };
 
 // the experts the split aims at: how many are active is device data, so the most that can be
@@ -40,19 +36,14 @@ static inline int moe_experts_aimed(int64_t T, int32_t k, int32_t E) { return (i
 static inline int moe_min_slice(int64_t T, int32_t k, int32_t E) {
   const int aimed = moe_experts_aimed(T, k, E);
   const int64_t rbar = std::max<int64_t>(1, (T * k + aimed - 1) / aimed);
-  return (int)std::max<int64_t>(MOE_KSTEP, (8 * rbar + MOE_KSTEP - 1) / MOE_KSTEP * MOE_KSTEP);
+  const int kstep = MOE_FORM.kstep;
+  return (int)std::max<int64_t>(kstep, (MOE_FORM.min_k_per_row * rbar + kstep - 1) / kstep * kstep);
 }
 
 static inline int moe_nsplit(int64_t T, int32_t k, int32_t E, int32_t N, int32_t K) {
   const int64_t wgs = (int64_t)moe_experts_aimed(T, k, E) * ((N + SKINNY_BN - 1) / SKINNY_BN);
   const int want = wgs > 0 ? (int)((SKINNY_WGS + wgs - 1) / wgs) : 1;
   return std::max(1, std::min(want, K / moe_min_slice(T, k, E)));
-}
-
-// k range of slice s: whole steps, at most one step apart in length, the last one cut at K
-static inline void moe_slice(const MoePlan& pl, int32_t K, int s, int32_t& kb, int32_t& ke) {
-  kb = (int32_t)((int64_t)s * pl.steps / pl.nsplit) * MOE_KSTEP;
-  ke = (int32_t)std::min<int64_t>(K, ((int64_t)(s + 1) * pl.steps / pl.nsplit) * MOE_KSTEP);
 }
 
 // the routing part of every entry point's checks; who prefixes the message
@@ -79,12 +70,9 @@ static inline bool moe_shape_ok(const char* who, int64_t T, int32_t k, int32_t E
 
 static inline MoePlan moe_plan(int64_t T, int32_t k, int32_t E, int32_t N, int32_t K, int32_t act) {
   MoePlan pl;
-  pl.rows = (int)(T * k);
-  pl.mf = (int)std::max<int64_t>(1, (T + 15) / 16);
-  pl.tiles_n = (N + SKINNY_BN - 1) / SKINNY_BN;
-  pl.steps = (K + MOE_KSTEP - 1) / MOE_KSTEP;
+  static_cast<SkinnyPlan&>(pl) = skinny_plan(MOE_FORM, T, N, K, act);
   pl.nsplit = moe_nsplit(T, k, E, N, K);
-  pl.glu = act == MIO_ACT_SWIGLU;
+  pl.rows = (int)(T * k);
   return pl;
 }
 

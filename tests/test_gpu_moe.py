@@ -231,6 +231,65 @@ def test_down_options(dtype):
         _run(c, dtype, "down", pads=True)
 
 
+# T -> (a K of one slice, a K of several): the slice is at least 8 T k, in steps of 32 (32, 160 and 512 k); all K % 32 == 8
+ONE_EXPERT_K = {1: (40, 328), 17: (40, 488), 64: (40, 1544)}
+
+
+def _decode_gemm(x, w, b, act, wg=None, bg=None, r=None):
+    """ops.gemm_skinny.  One row of N % 8 != 0 columns goes to mio_gemm_skinny itself with ldy = N padded to 8: ops.gemm_skinny
+    hands the launch the row stride torch reports for a one-row view, which is N, and the launch refuses it."""
+    ops, lib = _ops(), _lib()
+    (M, K), N = x.shape, w.shape[0]
+    if M > 1 or N % 8 == 0:
+        return ops.gemm_skinny(x, w, b, act, wg, bg, residual=r)
+    a = ops._ACT[act]
+    y = torch.empty(1, (N + 7) // 8 * 8, dtype=x.dtype, device=DEV)
+    n = lib.mio_gemm_skinny_workspace_bytes(M, N, K, a)
+    ws = torch.empty(n // 4, dtype=torch.float32, device=DEV) if n else None
+    rc = lib.mio_gemm_skinny(_p(x), _p(w), _p(b), _p(wg), _p(bg), _p(r), _p(y), _p(ws), M, N, K, K, w.stride(0), y.stride(0),
+                             0 if r is None else r.stride(0), a, ops._dtype_id(x), torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, lib.mio_last_error().decode()
+    return y[:, :N]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("T", sorted(ONE_EXPERT_K))
+def test_one_expert_is_the_decode_gemm(dtype, T):
+    """E = 1, top_k = 1: the route is the identity with weights exactly 1.0f, and the split rule is the decode-step GEMM's (one
+    expert aimed at, T rows for it).  The grouped GEMMs and the decode-step GEMM run one K loop, one partial store, one slice sum
+    and one epilogue, so up equals ops.gemm_skinny on the same x, weight, bias and activation bit for bit (SwiGLU and gelu), and down
+    (bias, residual) equals ops.gemm_skinny(..., residual=...) bit for bit: 1.0f * z is z, and 0.f + the one slice's partial is
+    the accumulator but for -0, which the bias add turns into +0 on both sides.  N 70 (N % 4 != 0: the partials go element by
+    element, the last workgroup is ragged) and N 72; one slice and several, asserted through the host queries."""
+    ops = _ops()
+    route = ops.moe_route(torch.zeros(T, 1, device=DEV), 1)
+    rows = torch.arange(T, dtype=torch.int32, device=DEV)
+    assert torch.equal(route.weights.view(torch.int32), torch.ones(T, 1, device=DEV).view(torch.int32))
+    assert torch.equal(route.sorted_rows, rows) and torch.equal(route.row_pos.reshape(-1), rows)
+    seen = set()
+    for N in (70, 72):
+        for K in ONE_EXPERT_K[T]:
+            x = _rand((T, K), dtype, seed=K + T)
+            w, wg = _rand((1, N, K), dtype, K ** -0.5, 1), _rand((1, N, K), dtype, K ** -0.5, 2)
+            b, bg = _rand((1, N), dtype, 0.5, 3), _rand((1, N), dtype, 0.5, 4)
+            r = _rand((T, (N + 7) // 8 * 8), dtype, 1.0, 5)[:, :N]  # (a residual's row stride is a multiple of 8 elements)
+            for act in ("swiglu", "gelu"):
+                n = ops.gemm_skinny_splits(T, N, K, act)
+                assert ops.moe_up_splits(T, 1, 1, N, K, act) == n, (T, N, K, act)
+                seen.add(n > 1)
+                glu = act == "swiglu"
+                want = _decode_gemm(x, w[0], b[0], act, wg[0] if glu else None, bg[0] if glu else None)
+                got = ops.moe_up(x, route, w, act, wg if glu else None, b, bg if glu else None)
+                assert torch.equal(got.view(torch.int16), want.view(torch.int16)), f"up T {T} N {N} K {K} {act} {dtype}"
+            n = ops.gemm_skinny_splits(T, N, K, "none")
+            assert ops.moe_down_splits(T, 1, 1, N, K) == n, (T, N, K)
+            seen.add(n > 1)
+            want = _decode_gemm(x, w[0], b[0], "none", r=r)
+            got = ops.moe_down(x, route, w, b, r)
+            assert torch.equal(got.view(torch.int16), want.view(torch.int16)), f"down T {T} N {N} K {K} {dtype}"
+    assert seen == {False, True}
+
+
 @pytest.fixture(scope="module")
 def deep_weights():
     """dtype -> (w, w_gate, bias, bias_gate) of the DEEP table, built on first use, shared by its cases (column prefixes) and never
