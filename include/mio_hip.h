@@ -525,6 +525,17 @@ int32_t mio_fa3_paged_route_window(const mio_fa3_paged_params_t* p, int32_t wind
  * Keys at positions >= max_blocks * block_size (a context longer than its block-table row) are
  * ignored.  No cache slot at or past context_lengths[b], and no table entry past the last needed
  * block, influences the result: such slots and entries may hold anything (NaN bit patterns too).
+ * What a launch may read and write (tests/_hostile_decode.py holds every route to it, bit for bit,
+ * under NaN and under huge finite values in everything else): of q the D elements of each
+ * (b, h, qi) row; context_lengths[0..B); of the caches the slots of layer_idx at the positions
+ * max(0, ctx_b - q_len - window_left) <= j < min(ctx_b, max_blocks * block_size) (from 0 without a
+ * window) and the table entries of the blocks that hold one; with an fp8 cache the two scales of
+ * layer_idx.  Keys in front of that range, the pages that hold only such keys and their table
+ * entries may hold anything (a table entry must still name a block inside the cache), as may
+ * the other layers, sequences and kv heads' data as far as one row of o is concerned.  What the
+ * workspace holds before a launch does not matter, and nothing outside its
+ * mio_fa3_decode_workspace_bytes() is written.  Of o the D elements of each (b, h, qi) row are
+ * written; the bytes of q / o between D and the row stride are neither read nor written.
  * ------------------------------------------------------------------------------------------ */
 size_t mio_fa3_decode_workspace_bytes(int32_t B, int32_t H, int32_t q_len, int32_t D, int32_t max_ctx);
 int mio_fa3_decode_paged(const void* q, void* o, const void* k_cache, const void* v_cache,

@@ -5,7 +5,7 @@ launch may not use is NaN, padded block-table entries name an all-NaN block) int
 kernel the launch takes, and is judged by _decode_check.check(): finite, exact zeros for empty rows, per-row error in
 units of the dtype's unit roundoff against bars taken from the fp32 model of the same case.  Further: caches whose owned
 blocks lie past 2^31 elements / 2^32 bytes, and launches through the C ABI with a workspace of exactly
-mio_fa3_decode_workspace_bytes() between guard zones.
+mio_fa3_decode_workspace_bytes() between guard zones, all-NaN before the launch.
 """
 import pytest
 import torch
@@ -118,7 +118,8 @@ def test_decode_high_cache_offsets(route, kv8):
 @pytest.mark.parametrize("case", dc.WORKSPACE_CASES, ids=lambda c: c["name"])
 def test_decode_workspace_is_enough(case):
     """mio_fa3_decode_workspace_bytes() knows neither the kv head count, the block size nor the cache's element size: a
-    launch given exactly that many bytes, in the middle of a patterned buffer, leaves the bytes around them untouched."""
+    launch given exactly that many bytes, in the middle of a patterned buffer, leaves the bytes around them untouched.  The
+    bytes themselves hold 0xFF before the launch (NaN as fp32): whatever a launch merges, it has stored itself."""
     from mio import _lib
     ops = _ops()
     lib = _lib.lib
@@ -136,6 +137,7 @@ def test_decode_workspace_is_enough(case):
     guard = (nbytes + 255) // 256 * 256   # at least the region's size on either side: an overrun stays inside the buffer
     pattern = 0xA5
     work = torch.full((2 * guard + nbytes,), pattern, dtype=torch.uint8, device=DEV)
+    work[guard:guard + nbytes] = 0xFF   # what the launch finds in its workspace: NaN as fp32 partials and lse
     ws = work.data_ptr() + guard
     assert ws % 16 == 0
     stream = ops._stream()
@@ -150,7 +152,7 @@ def test_decode_workspace_is_enough(case):
     del keep
     assert (work[:guard] == pattern).all(), "bytes in front of the workspace were written"
     assert (work[guard + nbytes:] == pattern).all(), "bytes behind the workspace were written"
-    assert (work[guard:guard + nbytes] != pattern).any(), "the launch used no workspace: the case has a single split"
+    assert (work[guard:guard + nbytes] != 0xFF).any(), "the workspace interior did not change: the case has a single split"
     dc.check(out, ref, lse, case["dtype"], dc.family(case), model_o, case["name"], win=case["left"] >= 0)
 
 
