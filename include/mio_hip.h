@@ -674,6 +674,11 @@ int32_t mio_fa3_paged_kv8_route(const mio_fa3_paged_params_t* p, const float* k_
  * [0, max_position), writes nothing to the caches and its q_out row is zeros.  A token whose cache
  * row is skipped (position before the sequence, past the table row, block id outside
  * [0, num_blocks)) but whose rotation position is valid still gets its q_out row.
+ * context_lengths is the caller's and is only read: a sequence whose length goes on growing past
+ * max_position, or past its block-table row, keeps the cache bytes it had.  A decode launch over
+ * such a sequence counts the unwritten positions below the table row's end as keys and reads what
+ * their slots hold (they must hold finite values for a finite result), ignores the positions past
+ * it, and a zero q_out row weighs every key it sees alike (tests/_step_check.py).
  * mio_rope_and_cache_varlen_kv8: the same into an fp8 (e4m3fn) cache with the layer's scales as in
  * mio_reshape_and_cache_varlen_kv8: K is e4m3(clamp(rot(k) * (1.0f / k_scale), -448, 448)), one
  * rounding from fp32; NaN stays NaN.
