@@ -884,6 +884,71 @@ int mio_moe_down(const void* h, const void* w_down, const void* b_down, const in
                  int32_t d, int32_t I, int64_t ldh, int64_t ldw, int64_t expert_stride, int64_t ldy,
                  int64_t ldr, int32_t dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mixture-of-experts MLP for tall inputs (csrc/moe_prefill.hip, csrc/moe_prefill_plan.h; DESIGN
+ * 4.2e): the same router semantics and the same two projections for 0 <= T <= 8192 tokens in one
+ * pass over the active experts' weights.  Shapes, dtypes, weight layout, strides and biases are
+ * those of the decode block above; T <= 64 is accepted (correct, not advised: the decode entry
+ * points are built for it).
+ *
+ * mio_moe_prefill_route.  Inputs and per-token semantics exactly mio_moe_route's: the order, the
+ * choice, the weights, the +inf and NaN handling, the degenerate row, renormalize.  Outputs: the
+ * same five arrays with the same definitions (an expert's rows in ascending routed-row order), and
+ * a TILE MAP for the grouped GEMMs, BM = 128 sorted positions of one expert per tile:
+ *   tile_expert int32 [max_tiles], tile_row0 int32 [max_tiles], num_tiles int32 [1].
+ * Expert e with c_e rows contributes ceil(c_e / BM) tiles; tiles are listed by ascending expert,
+ * then ascending first sorted position; tile_row0 is the tile's first sorted position; entries past
+ * num_tiles are not written.  The map is exactly determined by the logits.
+ * max_tiles = mio_moe_prefill_max_tiles(T, k, E) = floor(T k / BM) + min(E, T k), a pure function
+ * of the sizes (ceil(c / BM) <= floor(c / BM) + 1, summed over the experts with rows).
+ * Three launches (a wave per token; a workgroup per expert for its offset; a workgroup per expert
+ * for its rows and tiles): integers only in the sort, no atomics of any kind, no counters or
+ * barriers between workgroups.
+ *
+ * mio_moe_prefill_up.  h as stated for mio_moe_up: for sorted position p of expert e, token
+ * t = sorted_rows[p] / k,
+ *   h[p, :] = silu(x[t] Wgate_e^T + bg_e) * (x[t] Wup_e^T + bu_e)       (act == SWIGLU)
+ *   h[p, :] = act(x[t] Wup_e^T + bu_e)                                  (none, gelu, gelu_erf, relu, silu)
+ * fp32 accumulation, one rounding to the 16-bit dtype.  Only rows p < T k of h [T k, ldh] are
+ * written.  One launch; K is never split and there is no workspace.
+ *
+ * mio_moe_prefill_down.  y as stated for mio_moe_down with one slice:
+ *   y[t, :] = sum_{j = 0 .. k-1} weights[t, j] (h[row_pos[t k + j]] Wdown_e^T + bd_e) + residual[t],
+ * e = ids[t, j]: fp32, the slots in slot order j = 0, 1, ..., one rounding.  The grouped GEMM writes
+ * fp32 rows [T k][d] by sorted position into `workspace` (>= mio_moe_prefill_down_workspace_bytes
+ * = 4 T k d, required whenever T > 0); a finishing launch per (token, 4 columns) adds the bias of
+ * the slot's expert, applies the routing weight, sums the slots, adds the residual and rounds once.
+ *
+ * All three: the same bits on every rerun; nothing allocated, nothing read back to the host (the
+ * grid is sized by max_tiles and a workgroup past num_tiles returns at once), so a captured graph
+ * replays under any routing; one stream; T == 0 returns 0 and launches nothing.  Ownership as in
+ * the decode block: rows of x (of h) are read only for routed tokens (positions p < T k); the
+ * weights and biases of an expert with no routed row are never read; nothing past [row, row + K) of
+ * any operand is read; of the workspace only the first _workspace_bytes are touched.
+ * Refused (< 0, mio_last_error() names the entry point) before any launch: T > 8192, E or top_k
+ * out of range, K not a multiple of 8, strides short or not multiples of 8, pointers off 16-byte
+ * alignment (the route's int32 / fp32 arrays: off 4), w_gate without SWIGLU or SWIGLU without it, a
+ * missing workspace, an unknown dtype or activation.  The queries return < 0 (_max_tiles) or 0 with
+ * the message set (_workspace_bytes) on a shape the launches refuse.
+ * ------------------------------------------------------------------------------------------ */
+int mio_moe_prefill_max_tiles(int32_t T, int32_t top_k, int32_t E);
+int mio_moe_prefill_route(const void* logits, int64_t ld, int32_t* ids, float* weights, int32_t* expert_offsets,
+                          int32_t* sorted_rows, int32_t* row_pos, int32_t* tile_expert, int32_t* tile_row0,
+                          int32_t* num_tiles, int32_t T, int32_t E, int32_t top_k, int32_t renormalize,
+                          int32_t dtype /* MIO_BF16 | MIO_FP16 | MIO_FP32 */, void* stream);
+int mio_moe_prefill_up(const void* x, const void* w_up, const void* b_up, const void* w_gate, const void* b_gate,
+                       const int32_t* expert_offsets, const int32_t* sorted_rows, const int32_t* tile_expert,
+                       const int32_t* tile_row0, const int32_t* num_tiles, void* h, int32_t T, int32_t top_k,
+                       int32_t E, int32_t I, int32_t d, int64_t ldx, int64_t ldw, int64_t expert_stride,
+                       int64_t ldh, int32_t act, int32_t dtype, void* stream);
+size_t mio_moe_prefill_down_workspace_bytes(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K);
+int mio_moe_prefill_down(const void* h, const void* w_down, const void* b_down, const int32_t* ids,
+                         const float* weights, const int32_t* expert_offsets, const int32_t* row_pos,
+                         const int32_t* tile_expert, const int32_t* tile_row0, const int32_t* num_tiles,
+                         const void* residual, void* y, void* workspace, int32_t T, int32_t top_k, int32_t E,
+                         int32_t d, int32_t I, int64_t ldh, int64_t ldw, int64_t expert_stride, int64_t ldy,
+                         int64_t ldr, int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,12 +23,8 @@
 // order.  Up finishes in the first kernel when there is one slice; down always goes through the partials, because its second
 // launch is where the top_k slots of a token meet: slice sum, bias, routing weight, slot sum in slot order, residual, one
 // rounding.  No atomics, counters or barriers between workgroups.
-#include <cfloat>
-
-#include "gemm_skinny_common.h"
+#include "moe_common.h"
 #include "moe_plan.h"
-
-typedef unsigned long long moe_u64;
 
 // ---- router ------------------------------------------------------------------------------------------------------------------
 struct MoeRouteDev {
@@ -45,81 +41,17 @@ struct MoeRouteDev {
 constexpr int MOE_RT_NT = 1024, MOE_RT_NW = MOE_RT_NT / 64;
 static_assert(MOE_E_MAX <= 4 * 64 && MOE_E_MAX <= MOE_RT_NT, "four logits per lane; one sorting thread per expert");
 
-// the order-preserving key of a canonical fp32 (no NaN, no -0) and its inverse
-__device__ __forceinline__ uint32_t moe_key(float x) {
-  const uint32_t h = __float_as_uint(x);
-  return (h & 0x80000000u) ? ~h : (h | 0x80000000u);
-}
-__device__ __forceinline__ float moe_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-// exp(x - m) for x <= m, m finite: 1 at the maximum, 0 for -inf
-__device__ __forceinline__ float moe_w(float x, float m) {
-  const float d = x - m;
-  const float t = d * 1.4426950408889634f;
-  const float w = (t == t) ? fast_exp2(t) : 0.f;
-  return d == 0.f ? 1.f : fminf(w, 1.f);
-}
-
 template <typename L>
 __global__ __launch_bounds__(MOE_RT_NT) void moe_route_kernel(const MoeRouteDev a) {
   __shared__ int32_t s_ids[MOE_T_MAX * MOE_TOPK_MAX];
   __shared__ int32_t s_cnt[MOE_E_MAX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t key_ninf = moe_key(-INFINITY);
 
   for (int t = wave; t < a.T; t += MOE_RT_NW) {  // (wave-uniform)
     const L* row = (const L*)a.logits + (int64_t)t * a.ld;
-    float x[4];
-    moe_u64 cand[4];
-    moe_u64 best = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = lane + 64 * i;
-      x[i] = -INFINITY;
-      cand[i] = 0;  // (below every expert's: the smallest key, -inf's, is not 0)
-      if (e < a.E) {
-        float v = (float)row[e];
-        if (v != v) v = -INFINITY;
-        if (v == 0.f) v = 0.f;  // -0 -> +0
-        x[i] = fminf(v, FLT_MAX);
-        cand[i] = ((moe_u64)moe_key(v) << 32) | (uint32_t)~(uint32_t)e;
-      }
-      best = cand[i] > best ? cand[i] : best;
-    }
-    for (int o = 32; o >= 1; o >>= 1) {
-      const moe_u64 u = __shfl_xor(best, o, 64);
-      best = u > best ? u : best;
-    }
-    const uint32_t kmax = (uint32_t)(best >> 32);
-    int my_id = lane;  // lane j < top_k ends up with slot j
-    float my_w = 0.f;
-    if (kmax != key_ninf) {  // (else no finite logit: ids 0 .. top_k - 1, weights 0)
-      const float m = fminf(moe_unkey(kmax), FLT_MAX);
-      float z = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) z += (lane + 64 * i < a.E) ? moe_w(x[i], m) : 0.f;
-      for (int o = 32; o >= 1; o >>= 1) z += __shfl_xor(z, o, 64);
-      for (int j = 0; j < a.topk; ++j) {
-        moe_u64 b = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) b = cand[i] > b ? cand[i] : b;
-        for (int o = 32; o >= 1; o >>= 1) {
-          const moe_u64 u = __shfl_xor(b, o, 64);
-          b = u > b ? u : b;
-        }
-        const int idx = (int)~(uint32_t)b;
-        const float pj = moe_w(fminf(moe_unkey((uint32_t)(b >> 32)), FLT_MAX), m) / z;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (lane + 64 * i == idx) cand[i] = 0;
-        if (lane == j) my_id = idx, my_w = pj;
-      }
-      if (a.renorm) {
-        float s = 0.f;
-        for (int j = 0; j < a.topk; ++j) s += __shfl(my_w, j, 64);  // slot order
-        my_w = my_w / s;  // (s > 0: slot 0 is the maximum, whose weight is 1 / z)
-      }
-    }
+    int my_id;  // lane j < top_k: slot j
+    float my_w;
+    moe_route_token(row, a.E, a.topk, a.renorm, lane, my_id, my_w);
     if (lane < a.topk) {
       const int r = t * a.topk + lane;
       a.ids[r] = my_id;
@@ -263,57 +195,7 @@ __global__ __launch_bounds__(256) void moe_up_reduce_kernel(const MoeDev p) {
   skinny_finish<T, GLU, false>(moe_finish_args(p, lo), pos, n, v, g);
 }
 
-// Down's second launch: one thread per (token, 4 columns).  Per slot j in order: the slices' partials of the slot's sorted
-// position in slice order, the bias of its expert, times the routing weight; then the residual and the one rounding.
-struct MoeDownDev {
-  const float* ws;
-  const void* bias;  // [E, N] or null
-  const void* res;
-  void* y;
-  const int32_t* ids;
-  const float* weights;
-  const int32_t* row_pos;
-  int64_t ldy, ldr;
-  int T, topk, E, rows, N, nsplit;
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void moe_down_finish_kernel(const MoeDownDev p) {
-  const int ngrp = (p.N + 3) / 4;
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (int64_t)p.T * ngrp) return;
-  const int t = (int)(idx / ngrp), n = (int)(idx % ngrp) * 4;
-  const int64_t plane = (int64_t)p.rows * p.N;
-  const T* bias = (const T*)p.bias;
-  float o[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int j = 0; j < p.topk; ++j) {
-    const int r = t * p.topk + j;
-    const int e = min(max(p.ids[r], 0), p.E - 1);
-    const int pos = min(max(p.row_pos[r], 0), p.rows - 1);
-    const float wj = p.weights[r];
-    float z[4], unused[4];
-    skinny_slice_sum<false>(p.ws, p.nsplit, plane, p.N, pos, n, z, unused);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int nn = n + i < p.N ? n + i : p.N - 1;  // (clamped: computed, not stored)
-      const float zz = z[i] + (bias ? (float)bias[(int64_t)e * p.N + nn] : 0.f);
-      o[i] = j == 0 ? wj * zz : o[i] + wj * zz;
-    }
-  }
-  const T* rrow = p.res ? (const T*)p.res + (int64_t)t * p.ldr : nullptr;
-  T* yrow = (T*)p.y + (int64_t)t * p.ldy;
-  if (rrow) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] += (float)rrow[n + i < p.N ? n + i : p.N - 1];
-  }
-  if (n + 3 < p.N) {
-    *(u32x2_t*)(yrow + n) = (u32x2_t){pack2<T>(o[0], o[1]), pack2<T>(o[2], o[3])};
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (n + i < p.N) yrow[n + i] = (T)o[i];
-  }
-}
+// Down's second launch is moe_common.h's moe_down_finish_kernel: one thread per (token, 4 columns), the slots in slot order.
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 using MoeKernel = void (*)(const MoeDev);
@@ -456,8 +338,8 @@ extern "C" int mio_moe_down(const void* h, const void* w_down, const void* b_dow
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k.main[pl.mf - 1], dim3((unsigned)pl.tiles_n, (unsigned)pl.nsplit, (unsigned)E), dim3(256), 0, st, p);
   const int64_t threads = (int64_t)T * ((d + 3) / 4);
-  if (dtype == MIO_BF16) hipLaunchKernelGGL(moe_down_finish_kernel<__bf16>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, f);
-  else hipLaunchKernelGGL(moe_down_finish_kernel<_Float16>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, f);
+  if (dtype == MIO_BF16) hipLaunchKernelGGL((moe_down_finish_kernel<__bf16, 0>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, f);
+  else hipLaunchKernelGGL((moe_down_finish_kernel<_Float16, 0>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, f);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mio_fail(fn + " launch: " + hipGetErrorString(e));
   return 0;

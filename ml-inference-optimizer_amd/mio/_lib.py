@@ -155,6 +155,11 @@ EXPORTS = (
     "mio_moe_down_workspace_bytes",
     "mio_moe_up",
     "mio_moe_down",
+    "mio_moe_prefill_max_tiles",
+    "mio_moe_prefill_route",
+    "mio_moe_prefill_up",
+    "mio_moe_prefill_down_workspace_bytes",
+    "mio_moe_prefill_down",
 )
 
 
@@ -426,6 +431,23 @@ def _load() -> C.CDLL:
     # ldy, ldr, dtype, stream
     lib.mio_moe_down.argtypes = [vp] * 10 + [i32] * 5 + [i64] * 5 + [i32, vp]
     lib.mio_moe_down.restype = i32
+    # mixture of experts, tall inputs: T, top_k, E
+    lib.mio_moe_prefill_max_tiles.argtypes = [i32] * 3
+    lib.mio_moe_prefill_max_tiles.restype = i32
+    # logits, ld, the five outputs, tile_expert, tile_row0, num_tiles, T, E, top_k, renormalize, dtype, stream
+    lib.mio_moe_prefill_route.argtypes = [vp, i64] + [vp] * 8 + [i32] * 5 + [vp]
+    lib.mio_moe_prefill_route.restype = i32
+    # x, w_up, b_up, w_gate, b_gate, expert_offsets, sorted_rows, tile_expert, tile_row0, num_tiles, h, T, top_k, E, I, d, ldx, ldw,
+    # expert_stride, ldh, act, dtype, stream
+    lib.mio_moe_prefill_up.argtypes = [vp] * 11 + [i32] * 5 + [i64] * 4 + [i32, i32, vp]
+    lib.mio_moe_prefill_up.restype = i32
+    # T, top_k, E, N, K
+    lib.mio_moe_prefill_down_workspace_bytes.argtypes = [i32] * 5
+    lib.mio_moe_prefill_down_workspace_bytes.restype = C.c_size_t
+    # h, w_down, b_down, ids, weights, expert_offsets, row_pos, tile_expert, tile_row0, num_tiles, residual, y, workspace, T, top_k,
+    # E, d, I, ldh, ldw, expert_stride, ldy, ldr, dtype, stream
+    lib.mio_moe_prefill_down.argtypes = [vp] * 13 + [i32] * 5 + [i64] * 5 + [i32, vp]
+    lib.mio_moe_prefill_down.restype = i32
     return lib
 
 

@@ -21,10 +21,14 @@ from ..._nn import CastCache, as_dtype
 @dataclass
 class MoEConfig:
     """activation: "swiglu" (gate and up weights) or one of none / gelu / gelu_erf / relu / silu (up weight only).  renormalize: the
-    top_k softmax weights divided by their sum (Mixtral, Qwen3-MoE: True; OLMoE, Qwen2-MoE: False).  dtype: the compute dtype."""
+    top_k softmax weights divided by their sum (Mixtral, Qwen3-MoE: True; OLMoE, Qwen2-MoE: False).  dtype: the compute dtype.
+    grouped_prefill: inputs of more than 64 rows run the tiled grouped GEMMs (ops.moe_route_prefill, ops.moe_mlp_prefill): one
+    routing and one pass over the active experts' weights per 8192 rows, in place of the decode path in row chunks of 64.  Off
+    by default: forward is then what it was, to the bit."""
     activation: str = "swiglu"
     renormalize: bool = True
     dtype: torch.dtype = torch.bfloat16
+    grouped_prefill: bool = False
 
 
 class MoEMLP(nn.Module):
@@ -62,7 +66,7 @@ class MoEMLP(nn.Module):
         self._cast = CastCache()
 
     def _router_logits(self, x: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
-        """router(x) [T, E] for at most 64 rows: the decode-step GEMM where ops.gemm_skinny_ok advises it, else ops.gemm_bias_act.
+        """router(x) [T, E]: the decode-step GEMM where ops.gemm_skinny_ok advises it (at most 64 rows), else ops.gemm_bias_act.
         Where E is no multiple of 8 the GEMM runs on a copy of the router weight with zero rows up to the next multiple (made once
         per version of the parameter), so its output rows keep the 16-byte stride both GEMMs write at; the logits are the
         first E columns of that, which ops.moe_route takes by its row stride."""
@@ -74,8 +78,8 @@ class MoEMLP(nn.Module):
     def forward(self, hidden_states: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         """hidden_states [..., d] (flattened to [T, d]); residual of the same shape is added inside the combine's one rounding.
         T <= 64 is one routing and one pass over the active experts' weights.  T > 64 runs the same path in row chunks of 64: correct,
-        without host synchronisation, but every chunk streams its experts' weights again -- a prefill-grade grouped GEMM is out of
-        scope."""
+        without host synchronisation, but every chunk streams its experts' weights again -- unless config.grouped_prefill is on:
+        then T > 64 is one router GEMM, one ops.moe_route_prefill and one ops.moe_mlp_prefill per 8192 rows."""
         if not hidden_states.is_cuda:
             raise ValueError("Input tensor must be on a CUDA device for the HIP kernels")
         d = self.hidden_size
@@ -90,6 +94,14 @@ class MoEMLP(nn.Module):
         w_up, w_down = c.get(self.w_up, dt), c.get(self.w_down, dt)
         w_gate = c.get(self.w_gate, dt) if self.w_gate is not None else None
         out = torch.empty(T, ops._pad8(d), dtype=dt, device=x.device)[:, :d]
+        if self.config.grouped_prefill and T > ops.MOE_MAX_TOKENS:
+            for lo in range(0, T, ops.MOE_PREFILL_MAX_TOKENS):
+                hi = min(T, lo + ops.MOE_PREFILL_MAX_TOKENS)
+                xc = x[lo:hi]
+                route = ops.moe_route_prefill(self._router_logits(xc, dt), self.top_k, self.config.renormalize)
+                ops.moe_mlp_prefill(xc, route, w_up, w_down, self.config.activation, w_gate, residual=None if r is None else r[lo:hi],
+                                    out=out[lo:hi])
+            return as_dtype(out.reshape(*hidden_states.shape[:-1], d), in_dtype)
         for lo in range(0, T, ops.MOE_MAX_TOKENS):
             hi = min(T, lo + ops.MOE_MAX_TOKENS)
             xc = x[lo:hi]

@@ -23,6 +23,9 @@ same exception types for the same conditions):
                                mixture-of-experts MLP of a decode step (not a reference kernel: its models are dense): the router
                                (top-k of a softmax over all experts, routed rows grouped by expert, all on the device) and the
                                grouped up / down GEMMs over stacked expert weights with the combine
+  moe_route_prefill / moe_up_prefill / moe_down_prefill / moe_mlp_prefill
+                               the same for tall inputs (T <= 8192): a tile map built on the device, 128 x 128 x 64 tiled grouped
+                               GEMMs, one pass over the active experts' weights
 There is no fallback path: a non-zero return from the library raises RuntimeError.
 """
 from __future__ import annotations
@@ -2109,6 +2112,192 @@ def moe_mlp(x, route: MoERoute, w_up, w_down, act: str = "swiglu", w_gate=None, 
     w_down [E, d, I], biases [E, I] / [E, d].  h and both workspaces come from torch's allocator; nothing synchronises, so the
     call can be captured in a graph."""
     return moe_down(moe_up(x, route, w_up, act, w_gate, b_up, b_gate), route, w_down, b_down, residual, out)
+
+
+# ------------------------------------------------------------------------------------------------
+# mixture-of-experts MLP for tall inputs (prefill): router in three launches, tiled grouped GEMMs over a device-built tile map
+# ------------------------------------------------------------------------------------------------
+MOE_PREFILL_MAX_TOKENS = 8192
+
+
+class MoEPrefillRoute(NamedTuple):
+    """What moe_route_prefill decides: MoERoute's fields under the same names with the same definitions, and the tile map of the
+    grouped GEMMs (semantics: include/mio_hip.h): tile_expert int32 [max_tiles], tile_row0 int32 [max_tiles], num_tiles int32
+    [1], max_tiles = moe_prefill_max_tiles(T, top_k, E); entries past num_tiles are not written."""
+    ids: torch.Tensor
+    weights: torch.Tensor
+    expert_offsets: torch.Tensor
+    sorted_rows: torch.Tensor
+    row_pos: torch.Tensor
+    top_k: int
+    num_experts: int
+    tile_expert: torch.Tensor
+    tile_row0: torch.Tensor
+    num_tiles: torch.Tensor
+
+
+def moe_prefill_max_tiles(T: int, top_k: int, E: int) -> int:
+    """The bound on the tile map, floor(T k / 128) + min(E, T k).  Host-only; ValueError where the launches would refuse the shape."""
+    n = lib.mio_moe_prefill_max_tiles(T, top_k, E)
+    if n < 0:
+        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def _moe_prefill_route_ok(route, who: str, device) -> Tuple[int, int, int]:
+    """(T, k, E) of a MoEPrefillRoute whose tensors are what the kernels take from raw pointers."""
+    if not isinstance(route, MoEPrefillRoute):
+        raise ValueError(f"{who}: route must be a MoEPrefillRoute (ops.moe_route_prefill)")
+    T, k, E = _moe_route_ok(MoERoute(*route[:7]), who, device)
+    if T > MOE_PREFILL_MAX_TOKENS:
+        raise ValueError(f"{who} takes at most {MOE_PREFILL_MAX_TOKENS} tokens, got {T}")
+    mt = moe_prefill_max_tiles(T, k, E)
+    for name, t, shape in (("tile_expert", route.tile_expert, (mt,)), ("tile_row0", route.tile_row0, (mt,)), ("num_tiles", route.num_tiles, (1,))):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+            raise ValueError(f"{who}: route.{name} must be a tensor on the activations' device")
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{who}: route.{name} must be a contiguous int32 tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    return T, k, E
+
+
+def moe_route_prefill(router_logits, top_k: int, renormalize: bool = True, out: Optional[MoEPrefillRoute] = None) -> MoEPrefillRoute:
+    """Route T <= 8192 tokens over E <= 256 experts (mio_moe_prefill_route, three launches): router_logits [T, E] (or [..., E],
+    flattened; bf16, fp16 or fp32, last-dim stride 1) -> what moe_route gives per token, the routed rows grouped by expert, and the
+    tile map moe_up_prefill / moe_down_prefill walk.  out: a MoEPrefillRoute of the same (T, top_k, E) to write into (a captured
+    graph reuses its buffers).  T == 0 launches nothing and zeroes expert_offsets and num_tiles.  Nothing is read back."""
+    who = "moe_route_prefill"
+    if not isinstance(router_logits, torch.Tensor):
+        raise ValueError(f"{who}: router_logits must be a tensor")
+    _need_cuda(router_logits)
+    if router_logits.dtype not in _SAMPLE_DTYPES:
+        raise ValueError(f"{who}: router_logits must be bf16, fp16 or fp32, got {router_logits.dtype}")
+    if router_logits.dim() < 1:
+        raise ValueError(f"{who}: router_logits must be [..., E]")
+    E = router_logits.shape[-1]
+    k = operator.index(top_k)
+    if not 1 <= E <= MOE_MAX_EXPERTS:
+        raise ValueError(f"{who}: 1 .. {MOE_MAX_EXPERTS} experts, got {E}")
+    if not 1 <= k <= min(E, MOE_MAX_TOP_K):
+        raise ValueError(f"{who}: top_k must be in [1, min(E, {MOE_MAX_TOP_K})], got {k}")
+    x = router_logits if router_logits.dim() == 2 else router_logits.reshape(-1, E)
+    if x.stride(-1) != 1 and E > 1:
+        x = x.contiguous()
+    T = x.shape[0]
+    if T > MOE_PREFILL_MAX_TOKENS:
+        raise ValueError(f"{who} takes at most {MOE_PREFILL_MAX_TOKENS} tokens, got {T}")
+    ld = x.stride(0) if T > 1 else E
+    if ld < E or x.data_ptr() % 16:
+        x, ld = x.contiguous(), E
+        if x.data_ptr() % 16:  # (already contiguous at a storage offset off 16 bytes: contiguous() returned it as it was)
+            x = x.clone()
+    dev = x.device
+    if out is None:
+        i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)  # noqa: E731
+        mt = moe_prefill_max_tiles(T, k, E)
+        out = MoEPrefillRoute(i32(T, k), torch.empty(T, k, dtype=torch.float32, device=dev), i32(E + 1), i32(T * k), i32(T * k), k, E,
+                              i32(mt), i32(mt), i32(1))
+    elif _moe_prefill_route_ok(out, who, dev) != (T, k, E):
+        raise ValueError(f"{who}: out was made for another (T, top_k, E)")
+    if T == 0:
+        out.expert_offsets.zero_()
+        out.num_tiles.zero_()
+    else:
+        check(lib.mio_moe_prefill_route(x.data_ptr(), ld, out.ids.data_ptr(), out.weights.data_ptr(), out.expert_offsets.data_ptr(),
+                                        out.sorted_rows.data_ptr(), out.row_pos.data_ptr(), out.tile_expert.data_ptr(),
+                                        out.tile_row0.data_ptr(), out.num_tiles.data_ptr(), T, E, k, 1 if renormalize else 0,
+                                        _SAMPLE_DTYPES[x.dtype], _stream()))
+    return out
+
+
+def moe_up_prefill(x, route: MoEPrefillRoute, w_up, act: str = "swiglu", w_gate=None, b_up=None, b_gate=None, out=None):
+    """moe_up for a tall input (mio_moe_prefill_up): x [T, d], w_up (and w_gate for swiglu) [E, I, d] -> h [T k, I] by sorted
+    position, one launch of 128 x 128 x 64 tiles (swiglu: 128 x 64 up and gate columns) over the route's tile map; a weight tile is
+    read once per 128 rows of its expert.  out: h to write into, [T k, I], row stride a multiple of 8."""
+    who = "moe_up_prefill"
+    _need_cuda(x)
+    a = _moe_act(act)
+    dt = _dtype_id(x)
+    if x.dim() != 2:
+        raise ValueError(f"{who}: x must be [T, d], got {tuple(x.shape)}")
+    T, k, E = _moe_prefill_route_ok(route, who, x.device)
+    if x.shape[0] != T:
+        raise ValueError(f"{who}: x has {x.shape[0]} rows, the route {T} tokens")
+    glu = a == _lib.ACT_SWIGLU
+    if glu != (w_gate is not None):
+        raise ValueError("SwiGLU activation requires gate weights" if glu else f"{who}: w_gate belongs to act='swiglu'")
+    w = _moe_weight(w_up, E, x.dtype, "w_up", who)
+    I, d = w.shape[1:]
+    if x.shape[1] != d:
+        raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match input features {x.shape[1]}")
+    g = None
+    if glu:
+        if w_gate.shape != w_up.shape:
+            raise ValueError(f"{who}: w_gate must have w_up's shape")
+        g = _moe_weight(w_gate, E, x.dtype, "w_gate", who, like=w)
+        if g.stride() != w.stride():
+            w = w.contiguous()
+    bu = _moe_bias(b_up, E, I, x.dtype, "b_up", who)
+    bg = _moe_bias(b_gate, E, I, x.dtype, "b_gate", who) if glu else None
+    x2 = _rows16(x)
+    if out is None:
+        out = torch.empty(T * k, _pad8(I), dtype=x.dtype, device=x.device)[:, :I]
+    elif tuple(out.shape) != (T * k, I) or out.dtype != x.dtype or (I > 1 and out.stride(1) != 1) or out.stride(0) % 8:
+        raise ValueError(f"{who}: out must be [{T * k}, {I}] {x.dtype} with a row stride that is a multiple of 8")
+    if T == 0:
+        return out
+    check(lib.mio_moe_prefill_up(x2.data_ptr(), w.data_ptr(), _ptr(bu), _ptr(g), _ptr(bg), route.expert_offsets.data_ptr(),
+                                 route.sorted_rows.data_ptr(), route.tile_expert.data_ptr(), route.tile_row0.data_ptr(),
+                                 route.num_tiles.data_ptr(), out.data_ptr(), T, k, E, I, d, _ld(x2, d), w.stride(1), w.stride(0),
+                                 _ld(out, I), a, dt, _stream()))
+    return out
+
+
+def moe_down_prefill(h, route: MoEPrefillRoute, w_down, b_down=None, residual=None, out=None, workspace=None):
+    """moe_down for a tall input (mio_moe_prefill_down): h [T k, I] by sorted position, w_down [E, d, I] -> y [T, d] as moe_down
+    states it; the tiled grouped GEMM writes fp32 rows by sorted position, a second launch sums a token's slots in slot order
+    and rounds once.  workspace: an fp32 tensor of at least T k d elements to use in place of one from torch's allocator."""
+    who = "moe_down_prefill"
+    _need_cuda(h)
+    dt = _dtype_id(h)
+    T, k, E = _moe_prefill_route_ok(route, who, h.device)
+    if h.dim() != 2 or h.shape[0] != T * k:
+        raise ValueError(f"{who}: h must be [T k = {T * k}, I], got {tuple(h.shape)}")
+    w = _moe_weight(w_down, E, h.dtype, "w_down", who)
+    d, I = w.shape[1:]
+    if h.shape[1] != I:
+        raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match h's {h.shape[1]} features")
+    bd = _moe_bias(b_down, E, d, h.dtype, "b_down", who)
+    h2 = _rows16(h)
+    _res_ok(residual, T * d, h.dtype)
+    r2 = None if residual is None else _rows16(residual.reshape(T, d))
+    if r2 is not None and T > 1 and r2.stride(0) % 8:  # (d % 8 != 0, contiguous: rows at the stride the kernel's loads are laid out for)
+        r2 = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d].copy_(r2)
+    if out is None:
+        out = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d]
+    elif tuple(out.shape) != (T, d) or out.dtype != h.dtype or (d > 1 and out.stride(1) != 1) or out.stride(0) % 8:
+        raise ValueError(f"{who}: out must be [{T}, {d}] {h.dtype} with a row stride that is a multiple of 8")
+    if T == 0:
+        return out
+    need = lib.mio_moe_prefill_down_workspace_bytes(T, k, E, d, I) // 4
+    if workspace is None:
+        workspace = torch.empty(max(need, 4), dtype=torch.float32, device=h.device)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.device != h.device or workspace.dtype != torch.float32
+          or not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 16):
+        raise ValueError(f"{who}: workspace must be a contiguous, 16-byte aligned fp32 tensor of at least {need} elements on h's device")
+    check(lib.mio_moe_prefill_down(h2.data_ptr(), w.data_ptr(), _ptr(bd), route.ids.data_ptr(), route.weights.data_ptr(),
+                                   route.expert_offsets.data_ptr(), route.row_pos.data_ptr(), route.tile_expert.data_ptr(),
+                                   route.tile_row0.data_ptr(), route.num_tiles.data_ptr(), _ptr(r2), out.data_ptr(),
+                                   workspace.data_ptr(), T, k, E, d, I, _ld(h2, I), w.stride(1), w.stride(0), _ld(out, d),
+                                   0 if r2 is None else _ld(r2, d), dt, _stream()))
+    return out
+
+
+def moe_mlp_prefill(x, route: MoEPrefillRoute, w_up, w_down, act: str = "swiglu", w_gate=None, b_up=None, b_gate=None, b_down=None,
+                    residual=None, out=None):
+    """The experts' MLP of a tall input under a routing: moe_up_prefill, then moe_down_prefill.  x [T, d] (T <= 8192), w_up /
+    w_gate [E, I, d], w_down [E, d, I], biases [E, I] / [E, d].  h and the workspace come from torch's allocator; nothing
+    synchronises, so the call can be captured in a graph."""
+    return moe_down_prefill(moe_up_prefill(x, route, w_up, act, w_gate, b_up, b_gate), route, w_down, b_down, residual, out)
 
 
 # ------------------------------------------------------------------------------------------------
