@@ -885,6 +885,54 @@ int mio_moe_down(const void* h, const void* w_down, const void* b_down, const in
                  int64_t ldr, int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same two grouped GEMMs on weight-only FP8 expert weights (csrc/moe_w8.hip, csrc/moe_plan.h
+ * under the one-byte form).  The routing arrays are mio_moe_route's; shapes, limits,
+ * the meaning of h and y, the ownership rules and the determinism are those stated above.
+ *
+ * Weights.  OCP e4m3fn bytes (torch.float8_e4m3fn), row-major and stacked: w8_up [E, I, d], w8_gate
+ * [E, I, d] (SwiGLU only), w8_down [E, d, I]; ldw the row stride and expert_stride the distance
+ * between experts, both in BYTES, both multiples of 16, ldw >= K, expert_stride at least one
+ * expert's extent.  Scales fp32, contiguous, one per expert and output channel: s_up [E, I],
+ * s_gate [E, I], s_down [E, d] (mio_weight_quant_w8 on the [E N, K] view makes both).  x, h, the
+ * biases, the residual and y stay bf16 / fp16 (`dtype`).  K (d for up, I for down) must be a
+ * multiple of 16.
+ *
+ * Arithmetic.  Every e4m3fn value is exact in bf16 and fp16: the bytes are widened at scale 1 and
+ * multiplied on the 16-bit MFMA with fp32 accumulation; the scales stay out of the K loop.
+ *   up:    z = fma(x[t] . q_e[n, :], s_up[e, n], bu[e, n]); h = act(z), SwiGLU silu(z_gate) * z with
+ *          the gate's own bytes, scales and bias; one rounding.
+ *   down:  y[t, :] = sum_j weights[t, j] fma(h[row_pos[t k + j]] . q_e[n, :], s_down[e, n], bd[e, n])
+ *          + residual[t], e = ids[t, j]: the K slices in slice order, the scale of the slot's
+ *          expert before the routing weight, the slots in slot order, one rounding.
+ * At E = 1, top_k = 1 both are mio_gemm_skinny_w8's results to the bit, under the same split of K.
+ * The scales and biases of an expert with no routed row are never read, nor its weight bytes.
+ *
+ * Plan.  mio_moe_{up,down}_w8_splits slices of whole 64-k steps, each at least 16 x the mean rows
+ * per aimed expert long, so the fp32 partials stay at or under a quarter of the one-byte weight
+ * bytes read; a pure function of the sizes.  Workspaces as for the 16-bit entry points, sized by
+ * mio_moe_{up,down}_w8_workspace_bytes.
+ * Refused (< 0, mio_last_error() names the entry point) before any launch: everything the 16-bit
+ * entry points refuse, with K a multiple of 16 in place of 8 and ldw / expert_stride multiples of
+ * 16 bytes; null scales; a gate weight without gate scales or gate scales without a gate weight; a
+ * dtype other than MIO_BF16 / MIO_FP16.  T == 0 or N == 0 returns 0 and launches nothing; K == 0
+ * behaves as in mio_gemm_skinny_w8 (the sums are 0: h = act(bias), y = sum_j w_j bd + residual).
+ * ------------------------------------------------------------------------------------------ */
+int mio_moe_up_w8_splits(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K, int32_t act);
+size_t mio_moe_up_w8_workspace_bytes(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K, int32_t act);
+int mio_moe_down_w8_splits(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K);
+size_t mio_moe_down_w8_workspace_bytes(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K);
+int mio_moe_up_w8(const void* x, const void* w8_up, const float* s_up, const void* b_up, const void* w8_gate,
+                  const float* s_gate, const void* b_gate, const int32_t* expert_offsets,
+                  const int32_t* sorted_rows, void* h, void* workspace, int32_t T, int32_t top_k, int32_t E,
+                  int32_t I, int32_t d, int64_t ldx, int64_t ldw, int64_t expert_stride, int64_t ldh,
+                  int32_t act, int32_t dtype, void* stream);
+int mio_moe_down_w8(const void* h, const void* w8_down, const float* s_down, const void* b_down,
+                    const int32_t* ids, const float* weights, const int32_t* expert_offsets,
+                    const int32_t* row_pos, const void* residual, void* y, void* workspace, int32_t T,
+                    int32_t top_k, int32_t E, int32_t d, int32_t I, int64_t ldh, int64_t ldw,
+                    int64_t expert_stride, int64_t ldy, int64_t ldr, int32_t dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mixture-of-experts MLP for tall inputs (csrc/moe_prefill.hip, csrc/moe_prefill_plan.h; DESIGN
  * 4.2e): the same router semantics and the same two projections for 0 <= T <= 8192 tokens in one
  * pass over the active experts' weights.  Shapes, dtypes, weight layout, strides and biases are

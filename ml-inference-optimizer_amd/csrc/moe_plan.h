@@ -1,8 +1,9 @@
-// The plan of the mixture-of-experts decode-step launches (moe.hip: mio_moe_route, mio_moe_up, mio_moe_down): shape checks, the
-// split of K, the workspaces.  Host-only, no HIP, in the manner of gemm_skinny_plan.h, whose constants it shares: the launches and
-// the host queries (mio_moe_up_splits, mio_moe_up_workspace_bytes, mio_moe_down_splits, mio_moe_down_workspace_bytes) all ask
-// here.  A plan is a pure function of (T, k, E, N, K, act): the routing is device data and is never consulted, so a captured
-// graph replays under any routing.
+// The plan of the mixture-of-experts decode-step launches (moe.hip: mio_moe_route, mio_moe_up, mio_moe_down; moe_w8.hip:
+// mio_moe_up_w8, mio_moe_down_w8 on e4m3fn expert weights): shape checks, the split of K, the workspaces.  Host-only, no HIP, in the
+// manner of gemm_skinny_plan.h, whose constants and weight forms it shares: the launches and the host queries (mio_moe_up[_w8]_splits,
+// mio_moe_up[_w8]_workspace_bytes, mio_moe_down[_w8]_splits, mio_moe_down[_w8]_workspace_bytes) all ask here.  A plan is a pure
+// function of the weight form and (T, k, E, N, K, act): the routing is device data and is never consulted, so a captured graph
+// replays under any routing.  Every function takes the form first; the overloads without one are the 16-bit unit's (MOE_FORM).
 #pragma once
 #include <stdint.h>
 
@@ -27,24 +28,27 @@ struct MoePlan : SkinnyPlan {
 static inline int moe_experts_aimed(int64_t T, int32_t k, int32_t E) { return (int)std::max<int64_t>(1, std::min<int64_t>(E, T * k)); }
 
 // Split rule.  Slices so that experts_aimed x tiles_n x nsplit reaches SKINNY_WGS workgroups, each slice at least
-// 8 * rbar k long (whole steps), rbar = ceil(T k / experts_aimed) the rows per expert when the aimed experts share the routed rows
+// min_k_per_row * rbar k long (whole steps; 8 rbar for 16-bit weights, 16 rbar for one-byte weights), rbar = ceil(T k / experts_aimed) the rows per expert when the aimed experts share the routed rows
 // evenly.  Reason: every routed row gets one fp32 partial row per slice whatever the routing, 4 T k N nsplit bytes in all,
 // against 2 N K bytes of weight per active expert; at experts_aimed active experts the ratio is 2 rbar nsplit / K <= 2 rbar /
-// min_len = 1/4, the bound the decode-step GEMM keeps with its 8 M.  A routing that leaves experts idle reads less weight for the
+// min_len = 1/4, the bound the decode-step GEMM keeps with its 8 M; against N K bytes of e4m3fn weight the ratio is 4 rbar nsplit / K
+// <= 4 rbar / (16 rbar) = 1/4 again, the bound of that form's 16 M.  A routing that leaves experts idle reads less weight for the
 // same partials; the host cannot know, and the plan does not try to.  Slices are cut in steps, so with nsplit <= steps none is
 // empty and two differ by one step at most; K / min_len grows with K at fixed (T, k, E, N), so the count never falls as K grows.
-static inline int moe_min_slice(int64_t T, int32_t k, int32_t E) {
+static inline int moe_min_slice(const SkinnyForm& f, int64_t T, int32_t k, int32_t E) {
   const int aimed = moe_experts_aimed(T, k, E);
   const int64_t rbar = std::max<int64_t>(1, (T * k + aimed - 1) / aimed);
-  const int kstep = MOE_FORM.kstep;
-  return (int)std::max<int64_t>(kstep, (MOE_FORM.min_k_per_row * rbar + kstep - 1) / kstep * kstep);
+  const int kstep = f.kstep;
+  return (int)std::max<int64_t>(kstep, (f.min_k_per_row * rbar + kstep - 1) / kstep * kstep);
 }
+static inline int moe_min_slice(int64_t T, int32_t k, int32_t E) { return moe_min_slice(MOE_FORM, T, k, E); }
 
-static inline int moe_nsplit(int64_t T, int32_t k, int32_t E, int32_t N, int32_t K) {
+static inline int moe_nsplit(const SkinnyForm& f, int64_t T, int32_t k, int32_t E, int32_t N, int32_t K) {
   const int64_t wgs = (int64_t)moe_experts_aimed(T, k, E) * ((N + SKINNY_BN - 1) / SKINNY_BN);
   const int want = wgs > 0 ? (int)((SKINNY_WGS + wgs - 1) / wgs) : 1;
-  return std::max(1, std::min(want, K / moe_min_slice(T, k, E)));
+  return std::max(1, std::min(want, K / moe_min_slice(f, T, k, E)));
 }
+static inline int moe_nsplit(int64_t T, int32_t k, int32_t E, int32_t N, int32_t K) { return moe_nsplit(MOE_FORM, T, k, E, N, K); }
 
 // the routing part of every entry point's checks; who prefixes the message
 static inline bool moe_route_shape_ok(const char* who, int64_t T, int32_t k, int32_t E, std::string& err) {
@@ -58,22 +62,29 @@ static inline bool moe_route_shape_ok(const char* who, int64_t T, int32_t k, int
 }
 
 // the shape part of a grouped GEMM's checks (N output columns, K the reduction), shared with the host queries
-static inline bool moe_shape_ok(const char* who, int64_t T, int32_t k, int32_t E, int32_t N, int32_t K, int32_t act, std::string& err) {
+static inline bool moe_shape_ok(const SkinnyForm& f, const char* who, int64_t T, int32_t k, int32_t E, int32_t N, int32_t K,
+                                int32_t act, std::string& err) {
   if (!moe_route_shape_ok(who, T, k, E, err)) return false;
   if (N < 0 || K < 0) err = ": sizes must not be negative";
-  else if (K % 8 != 0) err = ": K must be a multiple of 8";
+  else if (K % f.k_multiple != 0) err = f.k_multiple_text;
   else if (act < MIO_ACT_NONE || act > MIO_ACT_SWIGLU) err = ": unknown activation";
   else return true;
   err = who + err;
   return false;
 }
+static inline bool moe_shape_ok(const char* who, int64_t T, int32_t k, int32_t E, int32_t N, int32_t K, int32_t act, std::string& err) {
+  return moe_shape_ok(MOE_FORM, who, T, k, E, N, K, act, err);
+}
 
-static inline MoePlan moe_plan(int64_t T, int32_t k, int32_t E, int32_t N, int32_t K, int32_t act) {
+static inline MoePlan moe_plan(const SkinnyForm& f, int64_t T, int32_t k, int32_t E, int32_t N, int32_t K, int32_t act) {
   MoePlan pl;
-  static_cast<SkinnyPlan&>(pl) = skinny_plan(MOE_FORM, T, N, K, act);
-  pl.nsplit = moe_nsplit(T, k, E, N, K);
+  static_cast<SkinnyPlan&>(pl) = skinny_plan(f, T, N, K, act);
+  pl.nsplit = moe_nsplit(f, T, k, E, N, K);
   pl.rows = (int)(T * k);
   return pl;
+}
+static inline MoePlan moe_plan(int64_t T, int32_t k, int32_t E, int32_t N, int32_t K, int32_t act) {
+  return moe_plan(MOE_FORM, T, k, E, N, K, act);
 }
 
 // up: fp32 partials [nsplit][T k][N] by sorted position (SwiGLU: the up half, then the gate half); none with one slice

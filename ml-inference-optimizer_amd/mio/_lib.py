@@ -155,6 +155,12 @@ EXPORTS = (
     "mio_moe_down_workspace_bytes",
     "mio_moe_up",
     "mio_moe_down",
+    "mio_moe_up_w8_splits",
+    "mio_moe_up_w8_workspace_bytes",
+    "mio_moe_down_w8_splits",
+    "mio_moe_down_w8_workspace_bytes",
+    "mio_moe_up_w8",
+    "mio_moe_down_w8",
     "mio_moe_prefill_max_tiles",
     "mio_moe_prefill_route",
     "mio_moe_prefill_up",
@@ -431,6 +437,19 @@ def _load() -> C.CDLL:
     # ldy, ldr, dtype, stream
     lib.mio_moe_down.argtypes = [vp] * 10 + [i32] * 5 + [i64] * 5 + [i32, vp]
     lib.mio_moe_down.restype = i32
+    # the same on e4m3fn expert weights: the queries take the same sizes; the launches take the fp32 scales behind each weight
+    for name, n, restype in (("up_w8_splits", 6, i32), ("up_w8_workspace_bytes", 6, C.c_size_t), ("down_w8_splits", 5, i32),
+                             ("down_w8_workspace_bytes", 5, C.c_size_t)):
+        getattr(lib, f"mio_moe_{name}").argtypes = [i32] * n
+        getattr(lib, f"mio_moe_{name}").restype = restype
+    # x, w8_up, s_up, b_up, w8_gate, s_gate, b_gate, expert_offsets, sorted_rows, h, workspace, T, top_k, E, I, d, ldx, ldw (bytes),
+    # expert_stride (bytes), ldh, act, dtype, stream
+    lib.mio_moe_up_w8.argtypes = [vp] * 11 + [i32] * 5 + [i64] * 4 + [i32, i32, vp]
+    lib.mio_moe_up_w8.restype = i32
+    # h, w8_down, s_down, b_down, ids, weights, expert_offsets, row_pos, residual, y, workspace, T, top_k, E, d, I, ldh, ldw (bytes),
+    # expert_stride (bytes), ldy, ldr, dtype, stream
+    lib.mio_moe_down_w8.argtypes = [vp] * 11 + [i32] * 5 + [i64] * 5 + [i32, vp]
+    lib.mio_moe_down_w8.restype = i32
     # mixture of experts, tall inputs: T, top_k, E
     lib.mio_moe_prefill_max_tiles.argtypes = [i32] * 3
     lib.mio_moe_prefill_max_tiles.restype = i32

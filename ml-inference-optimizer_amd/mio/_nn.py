@@ -91,6 +91,12 @@ class CastCache:
         return self._memo(("w8", id(p)), (p.data_ptr(), p._version, dtype, p.device, "w8"),
                           lambda: ops.quantize_weight_w8(self.get(p, dtype)))
 
+    def get_experts_w8(self, p: torch.Tensor, dtype: torch.dtype) -> Tuple[torch.Tensor, torch.Tensor]:
+        """get_w8 for a stacked expert weight [E, N, K] (ops.quantize_expert_weights_w8 of its copy in dtype): (w8 [E, N, K]
+        float8_e4m3fn, scale [E, N] fp32), quantised again when its version changes."""
+        return self._memo(("ew8", id(p)), (p.data_ptr(), p._version, dtype, p.device, "experts_w8"),
+                          lambda: ops.quantize_expert_weights_w8(self.get(p, dtype)))
+
     def get_row_padded(self, p: torch.Tensor, dtype: torch.dtype, multiple: int) -> torch.Tensor:
         """The 2-D parameter in dtype with zero rows appended up to the next multiple of `multiple` rows (itself where it has that
         many already), made again when its version changes."""

@@ -24,11 +24,17 @@ class MoEConfig:
     top_k softmax weights divided by their sum (Mixtral, Qwen3-MoE: True; OLMoE, Qwen2-MoE: False).  dtype: the compute dtype.
     grouped_prefill: inputs of more than 64 rows run the tiled grouped GEMMs (ops.moe_route_prefill, ops.moe_mlp_prefill): one
     routing and one pass over the active experts' weights per 8192 rows, in place of the decode path in row chunks of 64.  Off
-    by default: forward is then what it was, to the bit."""
+    by default: forward is then what it was, to the bit.
+    expert_weights_fp8: the decode kernels (T <= 64 and the row-chunk path) read weight-only FP8 copies of w_up, w_gate and w_down
+    (ops.quantize_expert_weights_w8: e4m3fn bytes, one fp32 scale per expert and output channel, made once per version of a
+    parameter) through ops.moe_mlp_w8: half the weight bytes per step.  hidden_size and intermediate_size must then be multiples
+    of 16.  The router GEMM stays 16-bit, and so does grouped_prefill, which keeps reading the 16-bit weights.  Off by default:
+    forward is then what it was, to the bit.  Whether it pays at a shape is the caller's to measure (profiles/moe_w8.md)."""
     activation: str = "swiglu"
     renormalize: bool = True
     dtype: torch.dtype = torch.bfloat16
     grouped_prefill: bool = False
+    expert_weights_fp8: bool = False
 
 
 class MoEMLP(nn.Module):
@@ -36,7 +42,9 @@ class MoEMLP(nn.Module):
 
     Parameters: router.weight [E, d]; w_up [E, I, d], w_gate [E, I, d] (swiglu only), w_down [E, d, I], stacked per expert; no
     biases.  A parameter stored in another dtype than config.dtype is cast once per version (CastCache), so an in-place update is
-    seen by the next forward."""
+    seen by the next forward.  With config.expert_weights_fp8 the decode kernels read weight-only FP8 copies of the three stacked
+    expert weights (e4m3fn bytes and fp32 scales [E, N]), quantised from the compute-dtype copies once per version in the same
+    way; the parameters themselves stay as they are stored."""
 
     def __init__(self, hidden_size: int, intermediate_size: int, num_experts: int, top_k: int, config: Optional[MoEConfig] = None):
         super().__init__()
@@ -47,6 +55,9 @@ class MoEMLP(nn.Module):
             raise ValueError(f"top_k must be in [1, min(num_experts, {ops.MOE_MAX_TOP_K})], got {top_k}")
         if self.config.activation not in ops._ACT:
             raise ValueError(f"Unsupported activation function: {self.config.activation}")
+        if self.config.expert_weights_fp8 and (hidden_size % 16 or intermediate_size % 16):
+            raise ValueError(f"expert_weights_fp8 needs hidden_size and intermediate_size to be multiples of 16 (the FP8 kernels' "
+                             f"16-byte weight loads), got {hidden_size} and {intermediate_size}")
         self.hidden_size, self.intermediate_size = hidden_size, intermediate_size
         self.num_experts, self.top_k = num_experts, top_k
         self.router = nn.Linear(hidden_size, num_experts, bias=False)
@@ -79,7 +90,9 @@ class MoEMLP(nn.Module):
         """hidden_states [..., d] (flattened to [T, d]); residual of the same shape is added inside the combine's one rounding.
         T <= 64 is one routing and one pass over the active experts' weights.  T > 64 runs the same path in row chunks of 64: correct,
         without host synchronisation, but every chunk streams its experts' weights again -- unless config.grouped_prefill is on:
-        then T > 64 is one router GEMM, one ops.moe_route_prefill and one ops.moe_mlp_prefill per 8192 rows."""
+        then T > 64 is one router GEMM, one ops.moe_route_prefill and one ops.moe_mlp_prefill per 8192 rows.  With
+        config.expert_weights_fp8 the decode path (T <= 64 and the row chunks) reads the FP8 copies of the expert weights; the
+        grouped prefill path reads the 16-bit weights."""
         if not hidden_states.is_cuda:
             raise ValueError("Input tensor must be on a CUDA device for the HIP kernels")
         d = self.hidden_size
@@ -91,10 +104,21 @@ class MoEMLP(nn.Module):
         x = as_dtype(hidden_states, dt).reshape(-1, d)
         r = None if residual is None else as_dtype(residual, dt).reshape(-1, d)
         T = x.shape[0]
+        out = torch.empty(T, ops._pad8(d), dtype=dt, device=x.device)[:, :d]
+        prefill = self.config.grouped_prefill and T > ops.MOE_MAX_TOKENS
+        if self.config.expert_weights_fp8 and not prefill:
+            (q_up, s_up), (q_down, s_down) = c.get_experts_w8(self.w_up, dt), c.get_experts_w8(self.w_down, dt)
+            q_gate, s_gate = c.get_experts_w8(self.w_gate, dt) if self.w_gate is not None else (None, None)
+            for lo in range(0, T, ops.MOE_MAX_TOKENS):
+                hi = min(T, lo + ops.MOE_MAX_TOKENS)
+                xc = x[lo:hi]
+                route = ops.moe_route(self._router_logits(xc, dt), self.top_k, self.config.renormalize)
+                ops.moe_mlp_w8(xc, route, q_up, s_up, q_down, s_down, self.config.activation, q_gate, s_gate,
+                               residual=None if r is None else r[lo:hi], out=out[lo:hi])
+            return as_dtype(out.reshape(*hidden_states.shape[:-1], d), in_dtype)
         w_up, w_down = c.get(self.w_up, dt), c.get(self.w_down, dt)
         w_gate = c.get(self.w_gate, dt) if self.w_gate is not None else None
-        out = torch.empty(T, ops._pad8(d), dtype=dt, device=x.device)[:, :d]
-        if self.config.grouped_prefill and T > ops.MOE_MAX_TOKENS:
+        if prefill:
             for lo in range(0, T, ops.MOE_PREFILL_MAX_TOKENS):
                 hi = min(T, lo + ops.MOE_PREFILL_MAX_TOKENS)
                 xc = x[lo:hi]

@@ -23,6 +23,9 @@ same exception types for the same conditions):
                                mixture-of-experts MLP of a decode step (not a reference kernel: its models are dense): the router
                                (top-k of a softmax over all experts, routed rows grouped by expert, all on the device) and the
                                grouped up / down GEMMs over stacked expert weights with the combine
+  quantize_expert_weights_w8 / moe_up_w8 / moe_down_w8 / moe_mlp_w8
+                               the grouped GEMMs of a decode step on weight-only FP8 (e4m3fn) expert weights with one fp32 scale
+                               per expert and output channel, under the same routing
   moe_route_prefill / moe_up_prefill / moe_down_prefill / moe_mlp_prefill
                                the same for tall inputs (T <= 8192): a tile map built on the device, 128 x 128 x 64 tiled grouped
                                GEMMs, one pass over the active experts' weights
@@ -2112,6 +2115,154 @@ def moe_mlp(x, route: MoERoute, w_up, w_down, act: str = "swiglu", w_gate=None, 
     w_down [E, d, I], biases [E, I] / [E, d].  h and both workspaces come from torch's allocator; nothing synchronises, so the
     call can be captured in a graph."""
     return moe_down(moe_up(x, route, w_up, act, w_gate, b_up, b_gate), route, w_down, b_down, residual, out)
+
+
+# ---- the same on weight-only FP8 expert weights (mio_moe_up_w8, mio_moe_down_w8; DESIGN 4.2f) --------------------------------------
+def quantize_expert_weights_w8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One-time preparation of a stacked bf16 / fp16 expert weight [E, N, K] (K % 16 == 0) for moe_up_w8 / moe_down_w8: (w8
+    [E, N, K] torch.float8_e4m3fn, scale [E, N] fp32), one scale per expert and output channel.  It is quantize_weight_w8 on the
+    [E N, K] view (a row's scale reads that row alone), so expert e's part equals quantize_weight_w8(w[e]) byte for byte."""
+    if not isinstance(w, torch.Tensor) or w.dim() != 3:
+        raise ValueError(f"quantize_expert_weights_w8 takes a stacked weight [E, N, K], got {getattr(w, 'shape', None)}")
+    E, N, K = w.shape
+    w8, scale = quantize_weight_w8(w.reshape(E * N, K))
+    return w8.view(E, N, K), scale.view(E, N)
+
+
+def _moe_w8_splits(fn, *sizes) -> int:
+    n = fn(*sizes)
+    if n < 0:
+        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def moe_up_w8_splits(T: int, top_k: int, E: int, I: int, d: int, activation: str = "swiglu") -> int:
+    """The slices of K = d a moe_up_w8 call of this shape runs (1: one launch, no workspace).  Host-only; ValueError where the
+    call would be refused."""
+    return _moe_w8_splits(lib.mio_moe_up_w8_splits, T, top_k, E, I, d, _moe_act(activation))
+
+
+def moe_down_w8_splits(T: int, top_k: int, E: int, d: int, I: int) -> int:
+    """The slices of K = I a moe_down_w8 call of this shape runs.  Host-only; ValueError where the call would be refused."""
+    return _moe_w8_splits(lib.mio_moe_down_w8_splits, T, top_k, E, d, I)
+
+
+def _moe_weight_w8(w, E: int, name: str, who: str, like=None) -> torch.Tensor:
+    """A stacked FP8 expert weight [E, N, K] as the kernels take it: torch.float8_e4m3fn, K % 16 == 0, last-dim stride 1, row and
+    expert strides multiples of 16 bytes, 16-byte aligned (a copy otherwise); like: the weight it must share strides with."""
+    if not isinstance(w, torch.Tensor) or w.dim() != 3 or w.shape[0] != E:
+        raise ValueError(f"{who}: {name} must be a stacked expert weight [E = {E}, N, K]")
+    _need_cuda(w)
+    if w.dtype != _W8:
+        raise ValueError(f"{who}: {name} must be torch.float8_e4m3fn (OCP e4m3), got {w.dtype}")
+    N, K = w.shape[1:]
+    if K % 16 != 0:
+        raise ValueError(f"{who}: K must be a multiple of 16, got {K} ({name})")
+    ok = (w.stride(2) == 1 and w.stride(1) % 16 == 0 and w.stride(1) >= K and w.stride(0) % 16 == 0
+          and w.stride(0) >= (N - 1) * w.stride(1) + K and w.data_ptr() % 16 == 0)
+    if not ok or (like is not None and w.stride() != like.stride()):
+        w = w.contiguous()
+    return w
+
+
+def _moe_scale_w8(s, E: int, N: int, name: str, who: str) -> torch.Tensor:
+    if not isinstance(s, torch.Tensor) or s.dtype != torch.float32 or tuple(s.shape) != (E, N):
+        raise ValueError(f"{who}: {name} must be an fp32 tensor of shape ({E}, {N}) (one scale per expert and output channel), got "
+                         f"{getattr(s, 'dtype', None)} {tuple(getattr(s, 'shape', ()))}")
+    _need_cuda(s)
+    return s if s.is_contiguous() else s.contiguous()
+
+
+def moe_up_w8(x, route: MoERoute, w8_up, s_up, act: str = "swiglu", w8_gate=None, s_gate=None, b_up=None, b_gate=None, out=None):
+    """moe_up on weight-only FP8 expert weights (mio_moe_up_w8): x [T, d] bf16 / fp16, w8_up (and w8_gate for swiglu) [E, I, d]
+    torch.float8_e4m3fn with d % 16 == 0, s_up / s_gate fp32 [E, I] (quantize_expert_weights_w8 makes both) -> h [T k, I] by sorted
+    position: row p is act(s_up[e] * (x[t] w8_up[e]^T) + b_up[e]) (swiglu: silu of the gate's, times that).  Weights whose strides
+    are multiples of 16 bytes go to the launch as they are.  Nothing synchronises with the host."""
+    who = "moe_up_w8"
+    _need_cuda(x)
+    a = _moe_act(act)
+    dt = _dtype_id(x)
+    if x.dim() != 2:
+        raise ValueError(f"{who}: x must be [T, d], got {tuple(x.shape)}")
+    T, k, E = _moe_route_ok(route, who, x.device)
+    if x.shape[0] != T:
+        raise ValueError(f"{who}: x has {x.shape[0]} rows, the route {T} tokens")
+    glu = a == _lib.ACT_SWIGLU
+    if glu != (w8_gate is not None) or glu != (s_gate is not None):
+        raise ValueError("SwiGLU activation requires gate weights and their scales" if glu
+                         else f"{who}: w8_gate and s_gate belong to act='swiglu'")
+    w = _moe_weight_w8(w8_up, E, "w8_up", who)
+    I, d = w.shape[1:]
+    if x.shape[1] != d:
+        raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match input features {x.shape[1]}")
+    su = _moe_scale_w8(s_up, E, I, "s_up", who)
+    g = sg = None
+    if glu:
+        if w8_gate.shape != w8_up.shape:
+            raise ValueError(f"{who}: w8_gate must have w8_up's shape")
+        g = _moe_weight_w8(w8_gate, E, "w8_gate", who, like=w)
+        if g.stride() != w.stride():
+            w = w.contiguous()
+        sg = _moe_scale_w8(s_gate, E, I, "s_gate", who)
+    bu = _moe_bias(b_up, E, I, x.dtype, "b_up", who)
+    bg = _moe_bias(b_gate, E, I, x.dtype, "b_gate", who) if glu else None
+    x2 = _rows16(x)
+    if out is None:
+        out = torch.empty(T * k, _pad8(I), dtype=x.dtype, device=x.device)[:, :I]
+    elif tuple(out.shape) != (T * k, I) or out.dtype != x.dtype or (I > 1 and out.stride(1) != 1) or out.stride(0) % 8:
+        raise ValueError(f"{who}: out must be [{T * k}, {I}] {x.dtype} with a row stride that is a multiple of 8")
+    if T == 0:
+        return out
+    nbytes = lib.mio_moe_up_w8_workspace_bytes(T, k, E, I, d, a)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    check(lib.mio_moe_up_w8(x2.data_ptr(), w.data_ptr(), su.data_ptr(), _ptr(bu), _ptr(g), _ptr(sg), _ptr(bg),
+                            route.expert_offsets.data_ptr(), route.sorted_rows.data_ptr(), out.data_ptr(), _ptr(ws), T, k, E, I, d,
+                            _ld(x2, d), w.stride(1), w.stride(0), _ld(out, I), a, dt, _stream()))
+    return out
+
+
+def moe_down_w8(h, route: MoERoute, w8_down, s_down, b_down=None, residual=None, out=None):
+    """moe_down on weight-only FP8 expert weights (mio_moe_down_w8): h [T k, I] by sorted position, w8_down [E, d, I]
+    torch.float8_e4m3fn with I % 16 == 0, s_down fp32 [E, d] -> y [T, d] = sum_j weights[t, j] (s_down[e] * (h[row_pos[t k + j]]
+    w8_down[e]^T) + b_down[e]) (+ residual[t]), e = ids[t, j]: the slots in slot order, rounded once."""
+    who = "moe_down_w8"
+    _need_cuda(h)
+    dt = _dtype_id(h)
+    T, k, E = _moe_route_ok(route, who, h.device)
+    if h.dim() != 2 or h.shape[0] != T * k:
+        raise ValueError(f"{who}: h must be [T k = {T * k}, I], got {tuple(h.shape)}")
+    w = _moe_weight_w8(w8_down, E, "w8_down", who)
+    d, I = w.shape[1:]
+    if h.shape[1] != I:
+        raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match h's {h.shape[1]} features")
+    sd = _moe_scale_w8(s_down, E, d, "s_down", who)
+    bd = _moe_bias(b_down, E, d, h.dtype, "b_down", who)
+    h2 = _rows16(h)
+    _res_ok(residual, T * d, h.dtype)
+    r2 = None if residual is None else _rows16(residual.reshape(T, d))
+    if r2 is not None and T > 1 and r2.stride(0) % 8:  # (d % 8 != 0, contiguous: rows at the stride the kernel's loads are laid out for)
+        r2 = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d].copy_(r2)
+    if out is None:
+        out = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d]
+    elif tuple(out.shape) != (T, d) or out.dtype != h.dtype or (d > 1 and out.stride(1) != 1) or out.stride(0) % 8:
+        raise ValueError(f"{who}: out must be [{T}, {d}] {h.dtype} with a row stride that is a multiple of 8")
+    if T == 0:
+        return out
+    nbytes = lib.mio_moe_down_w8_workspace_bytes(T, k, E, d, I)
+    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=h.device)
+    check(lib.mio_moe_down_w8(h2.data_ptr(), w.data_ptr(), sd.data_ptr(), _ptr(bd), route.ids.data_ptr(), route.weights.data_ptr(),
+                              route.expert_offsets.data_ptr(), route.row_pos.data_ptr(), _ptr(r2), out.data_ptr(), ws.data_ptr(), T, k,
+                              E, d, I, _ld(h2, I), w.stride(1), w.stride(0), _ld(out, d), 0 if r2 is None else _ld(r2, d), dt,
+                              _stream()))
+    return out
+
+
+def moe_mlp_w8(x, route: MoERoute, w8_up, s_up, w8_down, s_down, act: str = "swiglu", w8_gate=None, s_gate=None, b_up=None,
+               b_gate=None, b_down=None, residual=None, out=None):
+    """moe_mlp on weight-only FP8 expert weights: moe_up_w8, then moe_down_w8.  x, h, the biases, the residual and y stay bf16 /
+    fp16; nothing synchronises, so the call can be captured in a graph."""
+    return moe_down_w8(moe_up_w8(x, route, w8_up, s_up, act, w8_gate, s_gate, b_up, b_gate), route, w8_down, s_down, b_down, residual,
+                       out)
 
 
 # ------------------------------------------------------------------------------------------------
