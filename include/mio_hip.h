@@ -417,6 +417,38 @@ int mio_gemm_skinny_w8(const void* x, const void* w8, const float* w_scale, cons
                        const float* w_scale_gate, const void* bias_gate, const void* residual, void* y, void* workspace,
                        int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
                        int32_t dtype, void* stream);
+
+/* The FP8 x FP8 GEMM for tall inputs (W8A8; csrc/gemm_f8.hip, plan csrc/gemm_f8_plan.h): both operands are OCP e4m3fn bytes
+ * (torch.float8_e4m3fn) multiplied on v_mfma_f32_16x16x128_f8f6f4 with a plain fp32 accumulator, the scales in the read-out:
+ *   z[m, n] = (x_scale[m] * w_scale[n]) * sum_k x8[m, k] w8[n, k] + bias[n]
+ *   y[m, n] = round16(act(z[m, n]) + residual[m, n])
+ *   SwiGLU:   round16(silu(z_gate[m, n]) * z[m, n] + residual[m, n]), z_gate from w8_gate, w_scale_gate, bias_gate
+ * The reference has no quantised GEMM: this replaces the F.linear sites of its prefill (kernels/attention/flash_attention.py:629-631,
+ * 654-657; kernels/mlp/fused_mlp.py:159,176) for a model held as mio_weight_quant_w8 bytes.  Here FP8 is the compute precision.
+ *   x8 [M, K] with one fp32 scale per row: mio_weight_quant_w8 run on the activation matrix (per-token dynamic quantisation);
+ *   w8 / w8_gate [N, K] with one fp32 scale per output column: the row-major copy mio_gemm_skinny_w8 reads, not re-laid.
+ *   ldx, ldw in bytes, multiples of 16 and >= K; ldy, ldr in elements of out_dtype, multiples of 8 and >= N; x8, w8, w8_gate,
+ *   residual, y 16-byte aligned; scales 4-byte, biases 2-byte aligned.  bias / bias_gate (out_dtype, length N) and residual
+ *   (out_dtype) nullable; w8_gate and w_scale_gate together iff act == SWIGLU, bias_gate only then.  out_dtype MIO_BF16 or
+ *   MIO_FP16: the inputs carry no 16-bit type, the caller chooses.
+ *   M >= 0, N >= 0, K >= 0 with K % 16 == 0, at most 2^31 - 1 output tiles.  M == 0 or N == 0 returns 0 and launches nothing;
+ *   K == 0 is an empty sum: y = act(bias) + residual.  Every legal shape runs.
+ * Operation order: s = x_scale[m] * w_scale[n] (one fp32 product), z = fma(acc, s, bias[n]), the activation of
+ * mio_gemm_bias_act, the residual add, one rounding.  K is not split and nothing is accumulated in memory: reruns are
+ * bit-identical, and the launch neither allocates nor synchronises (graph-capturable).
+ * Ownership is mio_gemm_bias_act's rule: the launch owns x8[m, k], m < M, k < K; w8[n, k], w8_gate[n, k], n < N, k < K;
+ * x_scale[m]; w_scale[n], w_scale_gate[n], bias[n], bias_gate[n]; residual[m, n]; and writes y[m, n], m < M, n < N, only.  Rows a
+ * tile has past M or N and the bytes of a K step at and past K are zeros made in registers (0x00 is +0.0), never read.
+ * Every refusal returns < 0 with mio_last_error() set, before any launch.
+ * mio_gemm_f8_ok only advises the module layer: 1 where the shape is legal AND quantiser + mio_gemm_f8 measured at most 0.9 x
+ * the time of mio_gemm_bias_act's route on the 16-bit weight (profiles/gemm_f8.md); 0 at every shape that was not measured.
+ * mio_gemm_f8_route names the tile and form the launch takes ("empty", "f8_t256x256", "f8_glu_t256x128"); NULL
+ * (mio_last_error()) for a shape the launch refuses. */
+int mio_gemm_f8(const void* x8, int64_t ldx, const float* x_scale, const void* w8, int64_t ldw, const float* w_scale,
+                const void* bias, const void* w8_gate, const float* w_scale_gate, const void* bias_gate, const void* residual,
+                int64_t ldr, void* y, int64_t ldy, int64_t M, int32_t N, int32_t K, int32_t act, int32_t out_dtype, void* stream);
+int mio_gemm_f8_ok(int64_t M, int32_t N, int32_t K, int32_t act);
+const char* mio_gemm_f8_route(int64_t M, int32_t N, int32_t K, int32_t act);
 /* x_blocked != 0: the activation operand x is in the same blocked layout (m in the place of n; ceil(M/256)*256 x K
  * elements, ldx ignored) -- what mio_layernorm_fwd_bx writes, so that LayerNorm -> GEMM hands over contiguous K-tiles. */
 int mio_layernorm_fwd_bx(const void* x, const void* residual, const void* weight, const void* bias, void* yb,

@@ -120,6 +120,9 @@ EXPORTS = (
     "mio_gemm_skinny_w8_depth",
     "mio_gemm_skinny_w8_ok",
     "mio_gemm_skinny_w8",
+    "mio_gemm_f8",
+    "mio_gemm_f8_ok",
+    "mio_gemm_f8_route",
     "mio_layernorm_fwd_bx",
     "mio_ln_stats_bytes",
     "mio_gemm_ln_ok",
@@ -321,6 +324,13 @@ def _load() -> C.CDLL:
     lib.mio_weight_quant_w8.restype = i32
     lib.mio_gemm_skinny_w8.argtypes = [vp] * 10 + [i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
     lib.mio_gemm_skinny_w8.restype = i32
+    # x8, ldx, x_scale, w8, ldw, w_scale, bias, w8_gate, w_scale_gate, bias_gate, residual, ldr, y, ldy, M, N, K, act, out_dtype, stream
+    lib.mio_gemm_f8.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i32, i32, i32, i32, vp]
+    lib.mio_gemm_f8.restype = i32
+    lib.mio_gemm_f8_ok.argtypes = [i64, i32, i32, i32]
+    lib.mio_gemm_f8_ok.restype = i32
+    lib.mio_gemm_f8_route.argtypes = [i64, i32, i32, i32]
+    lib.mio_gemm_f8_route.restype = C.c_char_p
     lib.mio_fused_mlp_workspace_bytes.argtypes = [i64, i32, i32, i32]
     lib.mio_fused_mlp_workspace_bytes.restype = C.c_size_t
     lib.mio_fused_mlp_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]

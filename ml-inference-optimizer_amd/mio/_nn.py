@@ -217,19 +217,38 @@ def routed_linear(route: Optional[str], x: torch.Tensor, lin: nn.Linear, cache: 
     return gemm(x, cache.get(lin.weight, dtype)[:rows], bias, activation, gw, gb, residual)
 
 
+def f8_route(calls, f8: bool) -> bool:
+    """True iff the GEMMs calls = [(M, N, K, activation), ...] that run as a group take the FP8 x FP8 route under the modules'
+    gemm_fp8 option (f8): the option is on, every K is a multiple of 16 and ops.gemm_f8_ok advises every call."""
+    return f8 and all(c[2] % 16 == 0 and ops.gemm_f8_ok(*c) for c in calls)
+
+
+def f8_linear(x: torch.Tensor, lin: nn.Linear, cache: "CastCache", dtype: torch.dtype, activation: str = "none",
+              gate: Optional[nn.Linear] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """lin(x) (+ activation; gate: the SwiGLU gate projection; + residual) of a row-major x on the FP8 x FP8 GEMM: the rows of x
+    quantised per token, against CastCache.get_w8's copies, the ones the decode route reads (ops.gemm_w8a8)."""
+    w8, scale = cache.get_w8(lin.weight, dtype)
+    g8, gs = (None, None) if gate is None else cache.get_w8(gate.weight, dtype)
+    gb = None if gate is None else cache.get(gate.bias, dtype)
+    return ops.gemm_w8a8(x, w8, scale, cache.get(lin.bias, dtype), activation, g8, gs, gb, residual)
+
+
 def linear(x: torch.Tensor, lin: nn.Linear, cache: CastCache, dtype: torch.dtype, activation: str = "none",
            residual: Optional[torch.Tensor] = None, col_scale=None, x_blocked_shape=None, skinny: bool = False,
-           skinny_w8: bool = False) -> torch.Tensor:
+           skinny_w8: bool = False, f8: bool = False) -> torch.Tensor:
     """F.linear(x, W, b) (+ activation, + residual) on the MFMA GEMM.  At sizes that run the 256x256-tile kernels the
     weight is handed over in the blocked layout (repacked once per parameter version, cached next to the cast copy).
     skinny / skinny_w8 (the modules' decode_gemm / decode_gemm_fp8 options): a row-major x without a column scale goes to the
-    decode-step GEMM decode_route picks, if it picks one."""
+    decode-step GEMM decode_route picks, if it picks one; f8 (the modules' gemm_fp8 option): else to the FP8 x FP8 GEMM where
+    f8_route says so."""
     N, K = lin.weight.shape
     M = x.numel() // K if x_blocked_shape is None else int(math.prod(x_blocked_shape[:-1]))
     if x_blocked_shape is None and col_scale is None:
         route = decode_route([(M, N, K, activation)], skinny, skinny_w8)
         if route is not None:
             return routed_linear(route, x, lin, cache, dtype, activation, residual=residual)
+        if f8_route([(M, N, K, activation)], f8):
+            return f8_linear(x, lin, cache, dtype, activation, residual=residual)
     w = cache.get(lin.weight, dtype)
     wb = cache.get_blocked(lin.weight, dtype) if (K % 32 == 0 and ops.blocked_weight_ok(M, N, K, activation)) else None
     return ops.gemm_bias_act(x, w, cache.get(lin.bias, dtype), activation, residual=residual, w_blocked=wb,
@@ -237,13 +256,15 @@ def linear(x: torch.Tensor, lin: nn.Linear, cache: CastCache, dtype: torch.dtype
 
 
 def prenorm_linear(x: torch.Tensor, ln: nn.Module, lin: nn.Linear, cache: CastCache, dtype: torch.dtype,
-                   activation: str = "none", residual: Optional[torch.Tensor] = None, col_scale=None) -> torch.Tensor:
+                   activation: str = "none", residual: Optional[torch.Tensor] = None, col_scale=None, f8: bool = False) -> torch.Tensor:
     """lin(ln(x)) (+ activation, + residual), ln a LayerNorm or an RMSNorm (norm_kind).  At sizes that run the 256x256-tile
     kernels the norm writes its output in the blocked activation layout, so the GEMM's K-tile fetches are contiguous on both
-    operands."""
+    operands.  f8: as linear's; the norm then writes row-major rows for the quantiser."""
     w = cache.get(lin.weight, dtype)
     N, K = w.shape
     M = x.numel() // K
+    if col_scale is None and f8_route([(M, N, K, activation)], f8):
+        return f8_linear(apply_norm(x, ln, cache, dtype), lin, cache, dtype, activation, residual=residual)
     if K % 32 == 0 and not ops.NO_BLOCKED_X and ops.blocked_weight_ok(M, N, K, activation):
         xb = apply_norm(x, ln, cache, dtype, out_blocked=True)
         return ops.gemm_bias_act(xb, w, cache.get(lin.bias, dtype), activation, residual=residual,

@@ -53,6 +53,10 @@ class FlashAttentionConfig:
     # per parameter version; ops.gemm_skinny_w8) where ops.gemm_skinny_w8_ok advises it; a call it does not advise runs as
     # decode_gemm says.  Activations, the output and every other call stay 16-bit: a storage form, not precision="fp8".
     decode_gemm_fp8: bool = False
+    # prefill: the q / k / v / qkv and out projections of plain-tensor inputs as FP8 x FP8 GEMMs (ops.gemm_w8a8: the rows
+    # quantised per token, against the same FP8 weight copies) where ops.gemm_f8_ok advises the call and it carries no column
+    # scale or blocked operand; the ResidualStream forms stay 16-bit; off: every call as before
+    gemm_fp8: bool = False
     # QK-norm (Qwen3, Gemma 3): every q and k head is RMS-normalised over head_dim with a learned [head_dim] weight
     # (q_norm.weight / k_norm.weight, ones at construction) between the projection and the rotation, fused into the rotation
     # (ops.qk_norm_rotary) and rounded once.  Needs rotary_dim > 0; off: no new submodules, the layers run exactly as before.
@@ -292,11 +296,12 @@ class FlashAttentionLayer(_AttentionBase):
         # K is the whole output of k_proj; q / k / v are tensors of their own and the context stays row-major (no o_proj shape)
         kv_dim = self.num_kv_heads * self.head_dim
         plan = self._plan(B, S, (B * S, kv_dim, self.k_proj.in_features), (0, kv_dim), kv_dim, None, attention_mask is not None)
-        q = linear(x, self.q_proj, c, dt).view(B, S, self.num_attention_heads, self.head_dim)
-        k = linear(x, self.k_proj, c, dt, col_scale=plan.col_scale).view(B, S, self.num_kv_heads, self.head_dim)
-        v = linear(x, self.v_proj, c, dt).view(B, S, self.num_kv_heads, self.head_dim)
+        f8 = self.config.gemm_fp8
+        q = linear(x, self.q_proj, c, dt, f8=f8).view(B, S, self.num_attention_heads, self.head_dim)
+        k = linear(x, self.k_proj, c, dt, col_scale=plan.col_scale, f8=f8).view(B, S, self.num_kv_heads, self.head_dim)
+        v = linear(x, self.v_proj, c, dt, f8=f8).view(B, S, self.num_kv_heads, self.head_dim)
         ctx = self._context(q, k, v, plan, attention_mask, kwargs).view(B, S, self.hidden_size)
-        return as_dtype(linear(ctx, self.o_proj, c, dt, residual=r), in_dtype)
+        return as_dtype(linear(ctx, self.o_proj, c, dt, residual=r, f8=f8), in_dtype)
 
 
 class FlashSelfAttention(_AttentionBase):
@@ -377,9 +382,9 @@ class FlashSelfAttention(_AttentionBase):
         if isinstance(x, ResidualStream):
             qkv = folded_linear(x, pre_norm, self.qkv_proj, c, col_scale=plan.col_scale).view(B, S, n_tot)
         elif pre_norm is None:
-            qkv = linear(x, self.qkv_proj, c, dt, col_scale=plan.col_scale)
+            qkv = linear(x, self.qkv_proj, c, dt, col_scale=plan.col_scale, f8=cfg.gemm_fp8)
         else:
-            qkv = prenorm_linear(x, pre_norm, self.qkv_proj, c, dt, col_scale=plan.col_scale)
+            qkv = prenorm_linear(x, pre_norm, self.qkv_proj, c, dt, col_scale=plan.col_scale, f8=cfg.gemm_fp8)
         q = qkv[:, :, :q_dim].view(B, S, self.num_attention_heads, self.head_dim)
         k = qkv[:, :, q_dim:q_dim + kv_dim].view(B, S, self.num_kv_heads, self.head_dim)
         v = qkv[:, :, q_dim + kv_dim:].view(B, S, self.num_kv_heads, self.head_dim)
@@ -390,7 +395,7 @@ class FlashSelfAttention(_AttentionBase):
         if plan.out_blocked:
             out = linear(ctx, self.o_proj, c, dt, residual=r, x_blocked_shape=(B, S, q_dim))
         else:
-            out = linear(ctx.view(B, S, q_dim), self.o_proj, c, dt, residual=r)
+            out = linear(ctx.view(B, S, q_dim), self.o_proj, c, dt, residual=r, f8=cfg.gemm_fp8)
         return as_dtype(out, in_dtype)
 
 

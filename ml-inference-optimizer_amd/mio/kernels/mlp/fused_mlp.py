@@ -16,8 +16,8 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ..._nn import (CastCache, ResidualStream, apply_norm, as_dtype, compute_dtype, decode_route, folded_linear, residual_linear,
-                    routed_linear, stream_preconditions)
+from ..._nn import (CastCache, ResidualStream, apply_norm, as_dtype, compute_dtype, decode_route, f8_linear, f8_route, folded_linear,
+                    residual_linear, routed_linear, stream_preconditions)
 
 
 @dataclass
@@ -38,6 +38,9 @@ class FusedMLPConfig:
     # the same two GEMMs on weight-only FP8 copies of the weights (e4m3fn bytes, one fp32 scale per output channel, quantised
     # once per parameter version; ops.gemm_skinny_w8) where ops.gemm_skinny_w8_ok advises both; else as decode_gemm says
     decode_gemm_fp8: bool = False
+    # taller plain-tensor inputs: fc1 and fc2 as two FP8 x FP8 GEMMs (ops.gemm_w8a8: the rows quantised per token, against the
+    # same FP8 weight copies) where ops.gemm_f8_ok advises both; the ResidualStream forms stay 16-bit; off: every call as before
+    gemm_fp8: bool = False
 
 
 class FusedMLP(nn.Module):
@@ -118,6 +121,11 @@ class FusedMLP(nn.Module):
                 x = apply_norm(x, pre_norm, c, dt)
             h = routed_linear(route, x, self.fc1, c, dt, act, gate=self.fc1_gate if act == "swiglu" else None)
             return as_dtype(routed_linear(route, h, self.fc2, c, dt, residual=r), in_dtype)
+        if f8_route([(M, I, d, act), (M, self.fc2.weight.shape[0], I, "none")], self.config.gemm_fp8):
+            if pre_norm is not None:
+                x = apply_norm(x, pre_norm, c, dt)
+            h = f8_linear(x, self.fc1, c, dt, act, gate=self.fc1_gate if act == "swiglu" else None)
+            return as_dtype(f8_linear(h, self.fc2, c, dt, residual=r), in_dtype)
         gw, gb = self._gate(dt)
         b1 = b2 = None  # blocked weight copies, when this shape runs the kernels that take them
         if ops.fused_mlp_blocked_weight_ok(M, d, I, act):

@@ -26,6 +26,9 @@ same exception types for the same conditions):
   quantize_expert_weights_w8 / moe_up_w8 / moe_down_w8 / moe_mlp_w8
                                the grouped GEMMs of a decode step on weight-only FP8 (e4m3fn) expert weights with one fp32 scale
                                per expert and output channel, under the same routing
+  quantize_rows_f8 / gemm_f8 / gemm_w8a8
+                               the GEMM of tall inputs on FP8 compute (not a reference kernel): per-token e4m3fn activations against
+                               the e4m3fn weight copy of quantize_weight_w8 on the fp8 matrix instruction, scales in the read-out
   moe_route_prefill / moe_up_prefill / moe_down_prefill / moe_mlp_prefill
                                the same for tall inputs (T <= 8192): a tile map built on the device, 128 x 128 x 64 tiled grouped
                                GEMMs, one pass over the active experts' weights
@@ -880,6 +883,104 @@ def gemm_skinny_w8(x, w8, w_scale, bias=None, activation: str = "none", w8_gate=
     return _skinny(lib.mio_gemm_skinny_w8, lib.mio_gemm_skinny_w8_workspace_bytes, "fp8 weights are read by the decode-step kernel only",
                    x, N, K, w2.stride(0), (w2.data_ptr(), s2.data_ptr()), (_ptr(g2), _ptr(sg2)), bias, activation, bias_gate,
                    residual, out)
+
+
+# ---- the FP8 x FP8 GEMM for tall inputs (mio_gemm_f8): e4m3fn activations with one fp32 scale per row against the
+# e4m3fn weight copy gemm_skinny_w8 reads, on the fp8 matrix instruction ---------------------------------------------------------
+_DT_ID = {torch.bfloat16: _lib.MIO_BF16, torch.float16: _lib.MIO_FP16}
+
+
+def quantize_rows_f8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-token dynamic quantisation of bf16 / fp16 activations x [..., K] (K % 16 == 0), flattened to rows: (x8 [M, K]
+    torch.float8_e4m3fn, x_scale [M] fp32).  It is quantize_weight_w8 on the activation matrix: the same kernel, formula and NaN
+    rule, one scale per row."""
+    if x.dim() < 1:
+        raise ValueError("quantize_rows_f8 takes activations [..., K]")
+    return quantize_weight_w8(x.reshape(-1, x.shape[-1]))
+
+
+def _f8_act(activation: str) -> int:
+    if activation not in _ACT:
+        raise ValueError(f"Unsupported activation function: {activation}")
+    return _ACT[activation]
+
+
+def gemm_f8_ok(M: int, N: int, K: int, activation: str = "none") -> bool:
+    """True iff gemm_f8 is legal at this shape AND quantize_rows_f8 + gemm_f8 measured at most 0.9 x the time of the route
+    gemm_bias_act takes on the 16-bit weight (profiles/gemm_f8.md); False at every shape that was not measured.  Advice for the
+    module layer: gemm_f8 itself runs every legal shape."""
+    return activation in _ACT and bool(lib.mio_gemm_f8_ok(M, N, K, _ACT[activation]))
+
+
+def gemm_f8_route(M: int, N: int, K: int, activation: str = "none") -> str:
+    """The tile shape and form a gemm_f8 call of this shape takes ("empty", "f8_t256x256", "f8_glu_t256x128").  Host-only;
+    ValueError where the call would be refused."""
+    name = lib.mio_gemm_f8_route(M, N, K, _f8_act(activation))
+    if name is None:
+        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
+    return name.decode()
+
+
+def _rows_pad8(t: torch.Tensor, M: int, N: int) -> torch.Tensor:
+    """t as [M, N] rows a multiple of 8 elements apart at a 16-byte aligned address (itself where it already is)."""
+    t = t.reshape(M, N)
+    if t.stride(1) == 1 and (M <= 1 or t.stride(0) % 8 == 0) and t.data_ptr() % 16 == 0:
+        return t
+    return torch.empty(M, _pad8(N), dtype=t.dtype, device=t.device)[:, :N].copy_(t)
+
+
+def gemm_f8(x8, x_scale, w8, w_scale, bias=None, activation: str = "none", w8_gate=None, w_scale_gate=None, bias_gate=None,
+            residual=None, out=None, out_dtype: torch.dtype = torch.bfloat16):
+    """y [M, N] = act((x_scale[:, None] * w_scale[None, :]) * (x8 @ w8^T) + bias) (+ residual) in out_dtype (bf16 / fp16), both
+    operands torch.float8_e4m3fn multiplied on the fp8 MFMA: x8 [M, K] with x_scale fp32 [M] or one element (quantize_rows_f8),
+    w8 [N, K] with w_scale fp32 [N] or one element (quantize_weight_w8), K % 16 == 0.  SwiGLU: silu of the gate's (w8_gate,
+    w_scale_gate, bias_gate) times that.  bias / bias_gate / residual in out_dtype.  Row slices are legal operands."""
+    act = _f8_act(activation)
+    if out_dtype not in _DT_ID:
+        raise ValueError(f"gemm_f8 writes bf16 or fp16, got out_dtype {out_dtype}")
+    x2, w2 = _w8_ok(x8, "x8"), _w8_ok(w8, "w8")
+    (M, K), N = x2.shape, w2.shape[0]
+    if w2.shape[1] != K:
+        raise ValueError(f"weight shape {tuple(w2.shape)} does not match input features {K}")
+    if K % 16 != 0:
+        raise ValueError(f"gemm_f8: K must be a multiple of 16, got {K}")
+    xs, s2 = _w8_scale(x_scale, M, "x_scale"), _w8_scale(w_scale, N, "w_scale")
+    g2 = sg2 = None
+    if act == _lib.ACT_SWIGLU:
+        if w8_gate is None or w_scale_gate is None:
+            raise ValueError("SwiGLU activation requires gate weights and their scales")
+        g2 = _w8_ok(w8_gate, "w8_gate")
+        if g2.shape != w2.shape:
+            raise ValueError("w8_gate must have w8's shape")
+        sg2 = _w8_scale(w_scale_gate, N, "w_scale_gate")
+        if g2.stride(0) != w2.stride(0):
+            g2, w2 = g2.contiguous(), w2.contiguous()
+        _vec_ok(bias_gate, N, out_dtype, "bias_gate")
+    elif w8_gate is not None or w_scale_gate is not None:
+        raise ValueError("w8_gate and w_scale_gate belong to activation='swiglu'")
+    else:
+        bias_gate = None
+    _vec_ok(bias, N, out_dtype, "bias")
+    _res_ok(residual, M * N, out_dtype)
+    r2 = None if residual is None else _rows_pad8(residual, M, N)
+    if out is None:
+        out = torch.empty(M, _pad8(N), dtype=out_dtype, device=x2.device)[:, :N]
+    elif out.dtype != out_dtype or tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise ValueError(f"out must be a {out_dtype} [{M}, {N}] tensor with unit column stride")
+    check(lib.mio_gemm_f8(x2.data_ptr(), _ld(x2, K), xs.data_ptr(), w2.data_ptr(), _ld(w2, K), s2.data_ptr(),
+                          _ptr(bias), _ptr(g2), _ptr(sg2), _ptr(bias_gate), _ptr(r2), 0 if r2 is None else _ld(r2, N),
+                          out.data_ptr(), _ld(out, N), M, N, K, act, _DT_ID[out_dtype], _stream()))
+    return out
+
+
+def gemm_w8a8(x, w8, w_scale, bias=None, activation: str = "none", w8_gate=None, w_scale_gate=None, bias_gate=None, residual=None,
+              out=None):
+    """gemm_bias_act on a weight held as quantize_weight_w8 bytes, for tall x [..., K] (bf16 / fp16): quantize_rows_f8(x), then
+    gemm_f8 with out_dtype = x.dtype.  Returns [..., N]."""
+    x8, xs = quantize_rows_f8(x)
+    y = gemm_f8(x8, xs, w8, w_scale, bias, activation, w8_gate, w_scale_gate, bias_gate, residual,
+                None if out is None else out.view(-1, out.shape[-1]), x.dtype)
+    return out if out is not None else y.reshape(*x.shape[:-1], y.shape[1])
 
 
 # ---- LayerNorm folded into the GEMMs on either side of it (mio_gemm_ln_bw; reference fused_layernorm_qkv.py:37-420) ------------
