@@ -52,6 +52,17 @@ struct SkinnyW16Tile {
   static_assert(PCS >= 16 && ROWS * PCS % 256 == 0, "chunk shape");
 };
 
+// The shape of the FP8 K loop (gemm_skinny_w8_head.inc, gemm_skinny_w8_loop.inc) at MF row fragments, from the form's values
+constexpr int SKINNY_W8_KSTEP = SKINNY_W8.kstep;
+template <int MF, bool GLU>
+struct SkinnyW8Tile {
+  static constexpr int SKC = SKINNY_W8.chunk(GLU);  // k per chunk
+  static constexpr int D = SKINNY_W8.sets(GLU);     // register sets in the ring
+  static constexpr int KS = SKC / SKINNY_W8_KSTEP, PCS = SKC / 8, ROWS = MF * 16, ROWB = SKC * 2;
+  static constexpr int XPT = ROWS * PCS / 256;  // 16-byte pieces of the x chunk per thread
+  static_assert(PCS >= 16 && ROWS * PCS % 256 == 0 && SKC % SKINNY_W8_KSTEP == 0 && D >= 2, "chunk shape");
+};
+
 __device__ __forceinline__ float skinny_act(int act, float v) {
   switch (act) {
     case MIO_ACT_GELU_TANH: return gemm_act<MIO_ACT_GELU_TANH>(v);

@@ -51,6 +51,12 @@ static inline bool skinny_w8_advised(int64_t M, int32_t N, int32_t K, int32_t ac
   return M <= 16 && nk >= (int64_t)4096 * 4096;
 }
 
+// The refusals of the mixture-of-experts decode launches over stacked weights of a form (moe_gemm_common.h) that read differently
+// for the two forms; the entry point's name goes in front.  The scale texts of a form without scales are never shown.
+struct SkinnyMoeTexts {
+  const char *ldw_multiple, *ld_multiple, *gate, *up_scale, *down_scale, *up_null, *down_null, *aligned;
+};
+
 // A weight form: what the plan, the checks and the kernel's K loop of one unit read.
 struct SkinnyForm {
   const char* name;   // the launch entry point; the queries are name_splits, name_workspace_bytes, ...
@@ -66,6 +72,7 @@ struct SkinnyForm {
   // the refusals that read differently for the two forms (the entry point's name goes in front)
   const char *m_max_text, *k_multiple_text, *dtype_text, *gate_text, *ldw_multiple_text, *ldw_short_text, *ld_multiple_text,
       *null_text;
+  SkinnyMoeTexts moe;
   constexpr int chunk(bool glu) const { return glu ? chunk_k_glu : chunk_k; }
   constexpr int sets(bool glu) const { return glu ? depth_glu : depth; }
 };
@@ -77,7 +84,11 @@ constexpr SkinnyForm SKINNY_W16 = {
     /*chunk_k*/ 256, 128, /*depth*/ 2, 2, skinny_advised,
     ": M must be at most 64 (mio_gemm_bias_act runs taller calls)", ": K must be a multiple of 8", ": dtype must be bf16 or fp16",
     ": w_gate is required iff act == SWIGLU", ": row strides must be multiples of 8 elements",
-    ": row stride smaller than row length", ": row strides must be multiples of 8 elements", ": x, w, y must be non-null"};
+    ": row stride smaller than row length", ": row strides must be multiples of 8 elements", ": x, w, y must be non-null",
+    {": row and expert strides must be multiples of 8 elements", ": row and expert strides must be multiples of 8 elements",
+     ": w_gate is required iff act == SWIGLU", "", "", ": x, w_up, h, expert_offsets, sorted_rows must be non-null",
+     ": h, w_down, y, ids, weights, expert_offsets, row_pos must be non-null",
+     ": pointers must be 16-byte aligned (the route's arrays: 4-byte)"}};
 
 // e4m3fn weights.  A step is the 64 k of a 16-byte weight piece per lane group: one load feeds two MFMAs.  A register set holds
 // one chunk of weight bytes per lane, 4 loads of 16 bytes at 256 k (SwiGLU: 2 weights x 2 loads at 128 k), and the x pieces of
@@ -92,7 +103,12 @@ constexpr SkinnyForm SKINNY_W8 = {
     ": M must be at most 64 (fp8 weights are read by the decode-step kernel only)", ": K must be a multiple of 16",
     ": dtype must be bf16 or fp16 (the activations'; the weights are e4m3fn bytes)",
     ": w8_gate and w_scale_gate are required together iff act == SWIGLU", ": ldw must be a multiple of 16 bytes",
-    ": ldw smaller than K", ": ldx, ldy, ldr must be multiples of 8 elements", ": x, w8, w_scale, y must be non-null"};
+    ": ldw smaller than K", ": ldx, ldy, ldr must be multiples of 8 elements", ": x, w8, w_scale, y must be non-null",
+    {": ldw and expert_stride must be multiples of 16 bytes", ": activation row strides must be multiples of 8 elements",
+     ": w8_gate and s_gate are required together iff act == SWIGLU", ": s_up (the fp32 scales [E, I]) must be non-null",
+     ": s_down (the fp32 scales [E, d]) must be non-null", ": x, w8_up, h, expert_offsets, sorted_rows must be non-null",
+     ": h, w8_down, y, ids, weights, expert_offsets, row_pos must be non-null",
+     ": pointers must be 16-byte aligned (the scales and the route's arrays: 4-byte)"}};
 
 struct SkinnyPlan {
   int mf;        // row fragments: ceil(M / 16)

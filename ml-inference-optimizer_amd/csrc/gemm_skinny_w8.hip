@@ -1,7 +1,8 @@
 // Decode-step GEMM on weight-only FP8 (1 <= M <= 64): y[M,N] = act(scale[n] * (x[M,K] w8[N,K]^T) + bias[n]) (+ residual), SwiGLU
 // with a second weight and its own scales; and the one-time quantiser that makes (w8, scale) from a 16-bit weight.  The C-ABI
-// entry points mio_gemm_skinny_w8* and mio_weight_quant_w8 (include/mio_hip.h).  This file is the kernel's K loop, the quantiser
-// and the entry points' argument marshalling: the plan (shape checks, split of K, workspace, tuning values) is gemm_skinny_plan.h
+// entry points mio_gemm_skinny_w8* and mio_weight_quant_w8 (include/mio_hip.h).  This file is the kernel under the dense rows
+// description, the quantiser and the entry points' argument marshalling: the K loop described below is gemm_skinny_w8_head.inc +
+// gemm_skinny_w8_loop.inc, shared with the mixture-of-experts unit on FP8 expert weights (moe_w8.hip); the plan (shape checks, split of K, workspace, tuning values) is gemm_skinny_plan.h
 // under the form SKINNY_W8, and the launch's checks, the launcher, the host queries, the epilogue and the reduction are
 // gemm_skinny_common.h, all shared with gemm_skinny.hip.  Weights are OCP e4m3fn bytes (torch.float8_e4m3fn), row-major [N, K], with
 // one fp32 scale per output column; x, bias, residual and y stay bf16 / fp16.  Every e4m3fn value is exact in bf16 and fp16, so
@@ -33,112 +34,18 @@
 #include "kv8_cvt.h"
 
 constexpr SkinnyForm FORM = SKINNY_W8;  // this unit's weight form (gemm_skinny_plan.h)
-constexpr int SKW8_KSTEP = FORM.kstep;
 
+// The K loop itself is gemm_skinny_w8_head.inc + gemm_skinny_w8_loop.inc, shared with the grouped GEMM on FP8 expert weights
+// (moe_w8.hip).  The dense rows description: the weight starts at p.w, every fragment is live, staged row r is row r of x.
 template <typename T, int MF, bool GLU>
 __global__ __launch_bounds__(256) void gemm_skinny_w8_kernel(const SkinnyDev p) {
-  using X8 = typename DT<T>::x8;
-  constexpr int SKC = FORM.chunk(GLU);  // k per chunk
-  constexpr int D = FORM.sets(GLU);     // register sets in the ring
-  constexpr int KS = SKC / SKW8_KSTEP, PCS = SKC / 8, ROWS = MF * 16, ROWB = SKC * 2;
-  constexpr int XPT = ROWS * PCS / 256;  // 16-byte pieces of the x chunk per thread
-  static_assert(PCS >= 16 && ROWS * PCS % 256 == 0 && SKC % SKW8_KSTEP == 0 && D >= 2, "chunk shape");
-  __shared__ __attribute__((aligned(16))) char sx[2][ROWS * ROWB];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, q = lane >> 4;
-  const int n0 = blockIdx.x * SKINNY_BN + wave * 16;
-  const bool active = n0 < p.N;  // (a wave past the last column stages x and keeps the barriers, nothing else)
-  const int s = blockIdx.y;
-  int kb, ke;
-  skinny_slice_range(p.steps, p.nsplit, SKW8_KSTEP, p.K, s, kb, ke);
-  const int nc = (ke - kb + SKC - 1) / SKC;
-
-  const int nrow = min(n0 + c, p.N - 1);
-  const uint8_t* wrow = (const uint8_t*)p.w + (int64_t)nrow * p.ldw;
-  const uint8_t* grow = GLU ? (const uint8_t*)p.wg + (int64_t)nrow * p.ldw : nullptr;
-  const T* xg = (const T*)p.x;
-
-  auto load_w = [&](u32x4_t (&wr)[KS], u32x4_t (&gr)[GLU ? KS : 1], int ch) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int k = kb + ch * SKC + ks * SKW8_KSTEP + 16 * q;
-      const bool ok = active && k < ke;
-      wr[ks] = (u32x4_t){0u, 0u, 0u, 0u};
-      if (ok) wr[ks] = *(const u32x4_t*)(wrow + k);
-      if constexpr (GLU) {
-        gr[ks] = (u32x4_t){0u, 0u, 0u, 0u};
-        if (ok) gr[ks] = *(const u32x4_t*)(grow + k);
-      }
-    }
-  };
-  auto load_x = [&](u32x4_t (&v)[XPT], int ch) {
-#pragma unroll
-    for (int i = 0; i < XPT; ++i) {
-      const int idx = tid + i * 256, row = idx / PCS, pc = idx % PCS;
-      const int k = kb + ch * SKC + pc * 8;
-      v[i] = (u32x4_t){0u, 0u, 0u, 0u};
-      if (row < p.M && k < ke) v[i] = *(const u32x4_t*)(xg + (int64_t)row * p.ldx + k);
-    }
-  };
-  auto put_x = [&](const u32x4_t (&v)[XPT], int buf) {
-#pragma unroll
-    for (int i = 0; i < XPT; ++i) {
-      const int idx = tid + i * 256, row = idx / PCS, pc = idx % PCS;
-      *(u32x4_t*)(sx[buf] + row * ROWB + ((pc ^ (row & 15)) * 16)) = v[i];
-    }
-  };
-
-  f32x4_t acc[MF], accg[GLU ? MF : 1];
-#pragma unroll
-  for (int mf = 0; mf < MF; ++mf) {
-    acc[mf] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    if constexpr (GLU) accg[mf] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  }
-  auto compute = [&](const u32x4_t (&wr)[KS], const u32x4_t (&gr)[GLU ? KS : 1], int buf) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {  // bytes 8 j .. 8 j + 7 of the piece: k0 + 16 q + 8 j, x piece ks * 8 + 2 q + j
-        const X8 wf = kv8_to_x8<T>((u32x2_t){wr[ks][2 * j], wr[ks][2 * j + 1]});
-        X8 gf;
-        if constexpr (GLU) gf = kv8_to_x8<T>((u32x2_t){gr[ks][2 * j], gr[ks][2 * j + 1]});
-#pragma unroll
-        for (int mf = 0; mf < MF; ++mf) {
-          const X8 xf = __builtin_bit_cast(X8, *(const u32x4_t*)(sx[buf] + (mf * 16 + c) * ROWB + (((ks * 8 + 2 * q + j) ^ c) * 16)));
-          acc[mf] = DT<T>::mfma16(wf, xf, acc[mf]);
-          if constexpr (GLU) accg[mf] = DT<T>::mfma16(gf, xf, accg[mf]);
-        }
-      }
-    }
-  };
-
-  // A ring of D register sets.  Chunk ch lives in set ch % D: its x pieces and then its weight bytes are requested D - 1 chunks
-  // ahead, into the set the chunk before the current one has just left.  One barrier per chunk: the x buffer written for chunk
-  // ch was last read for chunk ch - 2, before the barrier of chunk ch - 1.
-  u32x4_t wr[D][KS], gr[D][GLU ? KS : 1], xr[D][XPT];
-#pragma unroll
-  for (int j = 0; j < D - 1; ++j)
-    if (j < nc) {
-      load_x(xr[j], j);
-      load_w(wr[j], gr[j], j);
-    }
-  for (int ch = 0; ch < nc; ch += D) {
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-      const int cur = ch + j;
-      if (cur < nc) {  // (the same in every thread of the workgroup)
-        put_x(xr[j], cur & 1);
-        __syncthreads();
-        if (cur + D - 1 < nc) {
-          load_x(xr[(j + D - 1) % D], cur + D - 1);
-          load_w(wr[(j + D - 1) % D], gr[(j + D - 1) % D], cur + D - 1);
-        }
-        compute(wr[j], gr[j], cur & 1);
-      }
-    }
-  }
+  const auto wbase = [] { return (int64_t)0; };
+#include "gemm_skinny_w8_head.inc"
+  constexpr int nf = MF;
+  constexpr bool all_live = true;
+  const auto xhas = [&](int, int r) { return r < p.M; };
+  const auto xrow = [](int, int r) { return r; };
+#include "gemm_skinny_w8_loop.inc"
 
   if (!active) return;
   const int n = n0 + 4 * q;

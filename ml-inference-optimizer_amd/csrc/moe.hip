@@ -1,9 +1,12 @@
-// Mixture-of-experts MLP for decode steps (T <= 64 tokens, E <= 256 experts, top_k <= 8): the router and the two grouped GEMMs;
-// the C-ABI entry points mio_moe_route, mio_moe_up, mio_moe_down and their host queries (semantics: include/mio_hip.h, DESIGN
-// 4.2d).  The plan (shape checks, split of K, workspaces) is moe_plan.h.  The grouped GEMM's K loop is the decode-step GEMM's,
-// the same text (gemm_skinny_w16_head.inc, gemm_skinny_w16_loop.inc) under an expert's rows description; the slice range, the
-// slice sum and the epilogue arithmetic are gemm_skinny_plan.h's skinny_slice_range and gemm_skinny_common.h's skinny_slice_sum
-// and skinny_finish, the ones the decode-step GEMM runs.
+// Mixture-of-experts MLP for decode steps (T <= 64 tokens, E <= 256 experts, top_k <= 8) on 16-bit expert weights: the router and
+// the grouped GEMM's kernel; the C-ABI entry points mio_moe_route, mio_moe_up, mio_moe_down and their host queries (semantics:
+// include/mio_hip.h).  This file owns the router, the K-loop kernel of the 16-bit form and the entry points'
+// argument marshalling.  Shared with the FP8 unit (moe_w8.hip) and owned by moe_gemm_common.h: the launch's arguments, the checks,
+// the host queries, both launches and up's reduction; by moe_rows_head.inc / moe_rows_gather.inc: an expert's rows description;
+// by moe_common.h: down's finishing launch (and the per-token routing, shared with moe_prefill.hip); by moe_plan.h: the plan
+// (shape checks, split of K, workspaces).  The K loop is the decode-step GEMM's (gemm_skinny_w16_head.inc,
+// gemm_skinny_w16_loop.inc); the slice range, the slice sum and the epilogue arithmetic are gemm_skinny_plan.h's
+// skinny_slice_range and gemm_skinny_common.h's skinny_slice_sum and skinny_finish, the ones the decode-step GEMM runs.
 //
 // Router: ONE workgroup of 16 waves, a wave per token (tokens wave, wave + 16, ...).  A lane holds the logits of experts lane,
 // lane + 64, lane + 128, lane + 192 as fp32 (exact for bf16 / fp16) and their order-preserving keys; top_k rounds of a wave max
@@ -23,8 +26,9 @@
 // order.  Up finishes in the first kernel when there is one slice; down always goes through the partials, because its second
 // launch is where the top_k slots of a token meet: slice sum, bias, routing weight, slot sum in slot order, residual, one
 // rounding.  No atomics, counters or barriers between workgroups.
-#include "moe_common.h"
-#include "moe_plan.h"
+#include "moe_gemm_common.h"
+
+constexpr SkinnyForm FORM = SKINNY_W16;  // this unit's weight form (gemm_skinny_plan.h)
 
 // ---- router ------------------------------------------------------------------------------------------------------------------
 struct MoeRouteDev {
@@ -83,60 +87,13 @@ __global__ __launch_bounds__(MOE_RT_NT) void moe_route_kernel(const MoeRouteDev 
 }
 
 // ---- grouped GEMM -------------------------------------------------------------------------------------------------------------
-struct MoeDev {
-  const void* x;     // up: the tokens [T, ldx]; down: h by sorted position [T k, ldx]
-  const void* w;     // [E][N, ldw], experts expert_stride elements apart
-  const void* wg;    // SwiGLU: the gate weight, same strides
-  const void* bias;  // [E, N] or null
-  const void* bias_g;
-  void* y;           // up with one slice: h [T k, ldy]
-  float* ws;         // fp32 partials [nsplit][T k][N] by sorted position (SwiGLU: then the gate half); null: finish in the kernel
-  const int32_t* offsets;
-  const int32_t* sorted_rows;  // up: routed row of a sorted position; null (down): x rows ARE sorted positions
-  int64_t ldx, ldw, estride, ldy;
-  int T, topk, E, rows, N, K, act, nsplit, steps;
-};
-
-// the epilogue's arguments for expert e: its biases, no residual, no scales
-__device__ __forceinline__ SkinnyFinish moe_finish_args(const MoeDev& p, int e) {
-  SkinnyFinish f = {};
-  f.bias = p.bias ? (const char*)p.bias + (int64_t)e * p.N * 2 : nullptr;
-  f.bias_g = p.bias_g ? (const char*)p.bias_g + (int64_t)e * p.N * 2 : nullptr;
-  f.y = p.y;
-  f.ldy = p.ldy;
-  f.N = p.N;
-  f.act = p.act;
-  return f;
-}
-
-// The K loop itself is gemm_skinny_w16_head.inc + gemm_skinny_w16_loop.inc, the decode-step GEMM's.  An expert's rows description:
-// the weight starts e * expert_stride into p.w; the fragments its cnt rows reach are live; staged row r < cnt is the x row behind
-// sorted position r0 + r, through sorted_rows (up: routed row / top_k is the token) or the position itself (down: h is stored so).
+// The K loop is gemm_skinny_w16_head.inc + gemm_skinny_w16_loop.inc, the decode-step GEMM's, under an expert's rows description
+// (moe_rows_head.inc, moe_rows_gather.inc).
 template <typename T, int MF, bool GLU>
-__global__ __launch_bounds__(256) void moe_gemm_kernel(const MoeDev p) {
-  // the expert's rows: sorted positions [r0, r0 + cnt).  No rows: nothing of this expert is read and no barrier is met, the same
-  // for all the workgroup's threads.
-  const int e = blockIdx.z;
-  const int r0 = max(0, min(p.offsets[e], p.rows));
-  const int cnt = min(min(p.offsets[e + 1], p.rows) - r0, MF * 16);  // (an expert has at most T <= 16 MF rows)
-  if (cnt <= 0) return;
-  const int nf = (cnt + 15) >> 4;
-  constexpr bool all_live = false;
-  const auto wbase = [&] { return (int64_t)e * p.estride; };
+__global__ __launch_bounds__(256) void moe_gemm_kernel(const MoeDev<false> p) {
+#include "moe_rows_head.inc"
 #include "gemm_skinny_w16_head.inc"
-  // the x row behind each piece this thread stages (the same for every chunk); -1: a row past the expert's count
-  int xsrc[XPT];
-#pragma unroll
-  for (int i = 0; i < XPT; ++i) {
-    const int row = (tid + i * 256) / PCS;
-    xsrc[i] = -1;
-    if (row < cnt) {
-      const int pos = r0 + row;
-      xsrc[i] = p.sorted_rows ? min(max(p.sorted_rows[pos] / p.topk, 0), p.T - 1) : pos;
-    }
-  }
-  const auto xhas = [&](int i, int) { return xsrc[i] >= 0; };
-  const auto xrow = [&](int i, int) { return xsrc[i]; };
+#include "moe_rows_gather.inc"
 #include "gemm_skinny_w16_loop.inc"
 
   if (!active) return;
@@ -144,7 +101,7 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(const MoeDev p) {
   if (n >= p.N) return;
   // lane (c, q): rows 16 mf + c of the expert, i.e. sorted positions r0 + 16 mf + c, columns n .. n + 3.  This is skinny_write
   // (gemm_skinny_common.h) at (r0, cnt), written out: through the call these kernels compile to other instructions, not these.
-  const SkinnyFinish sd = moe_finish_args(p, e);
+  const SkinnyFinish sd = moe_finish_args<false>(p, e);
 #pragma unroll
   for (int mf = 0; mf < MF; ++mf) {
     const int m = mf * 16 + c;
@@ -176,41 +133,9 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(const MoeDev p) {
   }
 }
 
-// Up's second launch: one thread per (sorted position, 4 columns) sums the slices' partials in index order and runs the epilogue
-// with the biases of the position's expert: the e with offsets[e] <= pos < offsets[e + 1].
-template <typename T, bool GLU>
-__global__ __launch_bounds__(256) void moe_up_reduce_kernel(const MoeDev p) {
-  const int ngrp = (p.N + 3) / 4;
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (int64_t)p.rows * ngrp) return;
-  const int pos = (int)(idx / ngrp), n = (int)(idx % ngrp) * 4;
-  int lo = 0, hi = p.E - 1;
-  while (lo < hi) {  // the largest e with offsets[e] <= pos (offsets[0] = 0; empty experts repeat an offset)
-    const int mid = (lo + hi + 1) >> 1;
-    if (p.offsets[mid] <= pos) lo = mid;
-    else hi = mid - 1;
-  }
-  float v[4], g[4];
-  skinny_slice_sum<GLU>(p.ws, p.nsplit, (int64_t)p.rows * p.N, p.N, pos, n, v, g);
-  skinny_finish<T, GLU, false>(moe_finish_args(p, lo), pos, n, v, g);
-}
+static const MoeKernelTable<false> KERNELS = MOE_KERNEL_TABLE(moe_gemm_kernel, 0, false);
 
-// Down's second launch is moe_common.h's moe_down_finish_kernel: one thread per (token, 4 columns), the slots in slot order.
-
-// ---- host ---------------------------------------------------------------------------------------------------------------------
-using MoeKernel = void (*)(const MoeDev);
-struct MoeKernels {
-  MoeKernel main[4], reduce;
-};
-#define MOE_KERNELS(T, GLU) \
-  {{moe_gemm_kernel<T, 1, GLU>, moe_gemm_kernel<T, 2, GLU>, moe_gemm_kernel<T, 3, GLU>, moe_gemm_kernel<T, 4, GLU>}, moe_up_reduce_kernel<T, GLU>}
-// [MIO_BF16 / MIO_FP16][SwiGLU / plain]
-static const MoeKernels MOE_TABLE[2][2] = {{MOE_KERNELS(__bf16, true), MOE_KERNELS(__bf16, false)},
-                                           {MOE_KERNELS(_Float16, true), MOE_KERNELS(_Float16, false)}};
-#undef MOE_KERNELS
-
-static inline bool moe_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
+// ---- the C ABI -----------------------------------------------------------------------------------------------------------------
 extern "C" int mio_moe_route(const void* logits, int64_t ld, int32_t* ids, float* weights, int32_t* expert_offsets,
                              int32_t* sorted_rows, int32_t* row_pos, int32_t T, int32_t E, int32_t top_k, int32_t renormalize,
                              int32_t dtype, void* stream) {
@@ -230,117 +155,38 @@ extern "C" int mio_moe_route(const void* logits, int64_t ld, int32_t* ids, float
   if (dtype == MIO_BF16) hipLaunchKernelGGL(moe_route_kernel<__bf16>, dim3(1), dim3(MOE_RT_NT), 0, st, a);
   else if (dtype == MIO_FP16) hipLaunchKernelGGL(moe_route_kernel<_Float16>, dim3(1), dim3(MOE_RT_NT), 0, st, a);
   else hipLaunchKernelGGL(moe_route_kernel<float>, dim3(1), dim3(MOE_RT_NT), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(fn + " launch: " + hipGetErrorString(e));
-  return 0;
+  return moe_launched(fn);
 }
 
-// what mio_moe_up and mio_moe_down check alike: the grouped GEMM's operands (x rows of K, weights [E][N, ldw], outputs of N)
-static int moe_gemm_checks(const std::string& fn, int64_t T, int32_t k, int32_t E, int32_t N, int32_t K, int32_t act, int32_t dtype,
-                           int64_t ldx, int64_t ldw, int64_t estride, int64_t ldy) {
-  std::string err;
-  if (!moe_shape_ok(fn.c_str(), T, k, E, N, K, act, err)) return mio_fail(err);
-  MIO_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, fn + ": dtype must be bf16 or fp16");
-  MIO_CHECK(ldx % 8 == 0 && ldw % 8 == 0 && ldy % 8 == 0 && estride % 8 == 0, fn + ": row and expert strides must be multiples of 8 elements");
-  MIO_CHECK(ldx >= K && ldw >= K && ldy >= N, fn + ": row stride smaller than row length");
-  MIO_CHECK(N == 0 || estride >= (int64_t)(N - 1) * ldw + K, fn + ": expert_stride smaller than one expert's weight");
-  return 0;
-}
-
+// the grouped GEMMs: argument marshalling over moe_gemm_common.h's host side
 extern "C" int mio_moe_up_splits(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K, int32_t act) {
-  std::string err;
-  if (!moe_shape_ok("mio_moe_up_splits", T, top_k, E, N, K, act, err)) return mio_fail(err);
-  return moe_plan(T, top_k, E, N, K, act).nsplit;
+  return moe_query_splits(FORM, "mio_moe_up_splits", T, top_k, E, N, K, act);
 }
 
 extern "C" size_t mio_moe_up_workspace_bytes(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K, int32_t act) {
-  std::string err;
-  if (!moe_shape_ok("mio_moe_up_workspace_bytes", T, top_k, E, N, K, act, err)) {
-    mio_set_error(err);
-    return 0;
-  }
-  return moe_up_workspace_bytes(moe_plan(T, top_k, E, N, K, act), N);
+  return moe_query_workspace_bytes(FORM, "mio_moe_up_workspace_bytes", false, T, top_k, E, N, K, act);
 }
 
 extern "C" int mio_moe_down_splits(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K) {
-  std::string err;
-  if (!moe_shape_ok("mio_moe_down_splits", T, top_k, E, N, K, MIO_ACT_NONE, err)) return mio_fail(err);
-  return moe_plan(T, top_k, E, N, K, MIO_ACT_NONE).nsplit;
+  return moe_query_splits(FORM, "mio_moe_down_splits", T, top_k, E, N, K, MIO_ACT_NONE);
 }
 
 extern "C" size_t mio_moe_down_workspace_bytes(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K) {
-  std::string err;
-  if (!moe_shape_ok("mio_moe_down_workspace_bytes", T, top_k, E, N, K, MIO_ACT_NONE, err)) {
-    mio_set_error(err);
-    return 0;
-  }
-  return moe_down_workspace_bytes(moe_plan(T, top_k, E, N, K, MIO_ACT_NONE), N);
+  return moe_query_workspace_bytes(FORM, "mio_moe_down_workspace_bytes", true, T, top_k, E, N, K, MIO_ACT_NONE);
 }
 
 extern "C" int mio_moe_up(const void* x, const void* w_up, const void* b_up, const void* w_gate, const void* b_gate,
                           const int32_t* expert_offsets, const int32_t* sorted_rows, void* h, void* workspace, int32_t T,
                           int32_t top_k, int32_t E, int32_t I, int32_t d, int64_t ldx, int64_t ldw, int64_t expert_stride,
                           int64_t ldh, int32_t act, int32_t dtype, void* stream) {
-  const std::string fn = "mio_moe_up";
-  if (int rc = moe_gemm_checks(fn, T, top_k, E, I, d, act, dtype, ldx, ldw, expert_stride, ldh)) return rc;
-  const bool glu = act == MIO_ACT_SWIGLU;
-  MIO_CHECK(glu == (w_gate != nullptr), fn + ": w_gate is required iff act == SWIGLU");
-  MIO_CHECK(glu || b_gate == nullptr, fn + ": b_gate belongs to act == SWIGLU");
-  MIO_CHECK(w_up && (T == 0 || (x && h && expert_offsets && sorted_rows)), fn + ": x, w_up, h, expert_offsets, sorted_rows must be non-null");
-  MIO_CHECK(mio_aligned16(x) && mio_aligned16(w_up) && mio_aligned16(w_gate) && mio_aligned16(b_up) && mio_aligned16(b_gate) &&
-                mio_aligned16(h) && mio_aligned16(workspace) && moe_aligned4(expert_offsets) && moe_aligned4(sorted_rows),
-            fn + ": pointers must be 16-byte aligned (the route's arrays: 4-byte)");
-  const MoePlan pl = moe_plan(T, top_k, E, I, d, act);
-  if (T == 0 || I == 0) return 0;
-  MIO_CHECK(pl.nsplit == 1 || workspace != nullptr, fn + ": workspace required (mio_moe_up_workspace_bytes) when the plan splits K");
-  MoeDev p;
-  p.x = x; p.w = w_up; p.wg = w_gate; p.bias = b_up; p.bias_g = b_gate; p.y = h;
-  p.ws = pl.nsplit > 1 ? (float*)workspace : nullptr;
-  p.offsets = expert_offsets; p.sorted_rows = sorted_rows;
-  p.ldx = ldx; p.ldw = ldw; p.estride = expert_stride; p.ldy = ldh;
-  p.T = T; p.topk = top_k; p.E = E; p.rows = pl.rows; p.N = I; p.K = d; p.act = act; p.nsplit = pl.nsplit; p.steps = pl.steps;
-  const MoeKernels& k = MOE_TABLE[dtype == MIO_BF16 ? 0 : 1][glu ? 0 : 1];
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k.main[pl.mf - 1], dim3((unsigned)pl.tiles_n, (unsigned)pl.nsplit, (unsigned)E), dim3(256), 0, st, p);
-  if (pl.nsplit > 1) {
-    const int64_t threads = (int64_t)pl.rows * ((I + 3) / 4);
-    hipLaunchKernelGGL(k.reduce, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(fn + " launch: " + hipGetErrorString(e));
-  return 0;
+  return moe_run_up(FORM, KERNELS, "mio_moe_up", x, w_up, nullptr, b_up, w_gate, nullptr, b_gate, expert_offsets, sorted_rows, h,
+                    workspace, T, top_k, E, I, d, ldx, ldw, expert_stride, ldh, act, dtype, stream);
 }
 
 extern "C" int mio_moe_down(const void* h, const void* w_down, const void* b_down, const int32_t* ids, const float* weights,
                             const int32_t* expert_offsets, const int32_t* row_pos, const void* residual, void* y, void* workspace,
                             int32_t T, int32_t top_k, int32_t E, int32_t d, int32_t I, int64_t ldh, int64_t ldw,
                             int64_t expert_stride, int64_t ldy, int64_t ldr, int32_t dtype, void* stream) {
-  const std::string fn = "mio_moe_down";
-  if (int rc = moe_gemm_checks(fn, T, top_k, E, d, I, MIO_ACT_NONE, dtype, ldh, ldw, expert_stride, ldy)) return rc;
-  MIO_CHECK(!residual || (ldr % 8 == 0 && ldr >= d), fn + ": ldr must be a multiple of 8 elements and at least d");
-  MIO_CHECK(w_down && (T == 0 || (h && y && ids && weights && expert_offsets && row_pos)),
-            fn + ": h, w_down, y, ids, weights, expert_offsets, row_pos must be non-null");
-  MIO_CHECK(mio_aligned16(h) && mio_aligned16(w_down) && mio_aligned16(b_down) && mio_aligned16(residual) && mio_aligned16(y) &&
-                mio_aligned16(workspace) && moe_aligned4(ids) && moe_aligned4(weights) && moe_aligned4(expert_offsets) &&
-                moe_aligned4(row_pos),
-            fn + ": pointers must be 16-byte aligned (the route's arrays: 4-byte)");
-  const MoePlan pl = moe_plan(T, top_k, E, d, I, MIO_ACT_NONE);
-  if (T == 0 || d == 0) return 0;
-  MIO_CHECK(workspace != nullptr, fn + ": workspace required (mio_moe_down_workspace_bytes)");
-  MoeDev p;
-  p.x = h; p.w = w_down; p.wg = nullptr; p.bias = nullptr; p.bias_g = nullptr; p.y = nullptr;
-  p.ws = (float*)workspace;
-  p.offsets = expert_offsets; p.sorted_rows = nullptr;
-  p.ldx = ldh; p.ldw = ldw; p.estride = expert_stride; p.ldy = 0;
-  p.T = T; p.topk = top_k; p.E = E; p.rows = pl.rows; p.N = d; p.K = I; p.act = MIO_ACT_NONE; p.nsplit = pl.nsplit; p.steps = pl.steps;
-  const MoeDownDev f = {(const float*)workspace, b_down, residual, y, ids, weights, row_pos, ldy, ldr, T, top_k, E, pl.rows, d, pl.nsplit};
-  const MoeKernels& k = MOE_TABLE[dtype == MIO_BF16 ? 0 : 1][1];
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k.main[pl.mf - 1], dim3((unsigned)pl.tiles_n, (unsigned)pl.nsplit, (unsigned)E), dim3(256), 0, st, p);
-  const int64_t threads = (int64_t)T * ((d + 3) / 4);
-  if (dtype == MIO_BF16) hipLaunchKernelGGL((moe_down_finish_kernel<__bf16, 0>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, f);
-  else hipLaunchKernelGGL((moe_down_finish_kernel<_Float16, 0>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, f);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(fn + " launch: " + hipGetErrorString(e));
-  return 0;
+  return moe_run_down(FORM, KERNELS, "mio_moe_down", h, w_down, nullptr, b_down, ids, weights, expert_offsets, row_pos, residual, y,
+                      workspace, T, top_k, E, d, I, ldh, ldw, expert_stride, ldy, ldr, dtype, stream);
 }

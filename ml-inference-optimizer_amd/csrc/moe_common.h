@@ -1,6 +1,8 @@
-// What the two mixture-of-experts units share on the device (moe.hip: decode steps, T <= 64; moe_prefill.hip: tall inputs): a
-// token's routing -- the order, the choice, the softmax weights -- as one device function, so that the two routers cannot drift,
-// and down's finishing launch, which has no bound on T: one thread per (token, 4 columns) over the slots in slot order.
+// What the mixture-of-experts units share on the device (moe.hip, moe_w8.hip: decode steps, T <= 64, on 16-bit and e4m3fn expert
+// weights; moe_prefill.hip: tall inputs): a token's routing -- the order, the choice, the softmax weights -- as one device
+// function, so that the two routers cannot drift, and down's finishing launch, which has no bound on T: one thread per (token, 4
+// columns) over the slots in slot order, with the expert's scale in front of the bias where the weights carry scales.  What only
+// the two decode units share is moe_gemm_common.h.
 #pragma once
 #include <cfloat>
 
@@ -84,10 +86,13 @@ __device__ __forceinline__ void moe_route_token(const L* row, int E, int topk, i
 }
 
 // Down's second launch: one thread per (token, 4 columns).  Per slot j in order: the slices' partials of the slot's sorted
-// position in slice order, the bias of its expert, times the routing weight; then the residual and the one rounding.  UNIT names
-// the including unit (0: moe.hip, 1: moe_prefill.hip), so that each object carries a kernel symbol of its own.
+// position in slice order, z = sum + bias[e, n] with the slot's expert e (SCALED, e4m3fn expert weights: fma(sum, scale[e, n],
+// bias[e, n]), the scale going in before the routing weight), times the routing weight; then the residual and the one rounding.
+// UNIT names the including unit (0: moe.hip, 1: moe_prefill.hip, 2: moe_w8.hip), so that each object carries a kernel symbol of
+// its own.
 struct MoeDownDev {
   const float* ws;
+  const float* scale;  // SCALED only: fp32 [E, N]; null otherwise
   const void* bias;  // [E, N] or null
   const void* res;
   void* y;
@@ -98,7 +103,7 @@ struct MoeDownDev {
   int T, topk, E, rows, N, nsplit;
 };
 
-template <typename T, int UNIT>
+template <typename T, int UNIT, bool SCALED = false>
 __global__ __launch_bounds__(256) void moe_down_finish_kernel(const MoeDownDev p) {
   const int ngrp = (p.N + 3) / 4;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -117,7 +122,10 @@ __global__ __launch_bounds__(256) void moe_down_finish_kernel(const MoeDownDev p
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int nn = n + i < p.N ? n + i : p.N - 1;  // (clamped: computed, not stored)
-      const float zz = z[i] + (bias ? (float)bias[(int64_t)e * p.N + nn] : 0.f);
+      const int64_t at = (int64_t)e * p.N + nn;
+      float zz;
+      if constexpr (SCALED) zz = __builtin_fmaf(z[i], p.scale[at], bias ? (float)bias[at] : 0.f);
+      else zz = z[i] + (bias ? (float)bias[at] : 0.f);
       o[i] = j == 0 ? wj * zz : o[i] + wj * zz;
     }
   }

@@ -3,7 +3,7 @@
 // manner of gemm_skinny_plan.h, whose constants and weight forms it shares: the launches and the host queries (mio_moe_up[_w8]_splits,
 // mio_moe_up[_w8]_workspace_bytes, mio_moe_down[_w8]_splits, mio_moe_down[_w8]_workspace_bytes) all ask here.  A plan is a pure
 // function of the weight form and (T, k, E, N, K, act): the routing is device data and is never consulted, so a captured graph
-// replays under any routing.  Every function takes the form first; the overloads without one are the 16-bit unit's (MOE_FORM).
+// replays under any routing.  Every function that depends on the form takes it first: a caller names its form.
 #pragma once
 #include <stdint.h>
 
@@ -16,9 +16,8 @@
 constexpr int MOE_T_MAX = SKINNY_M_MAX;  // tokens of one launch: a token picks an expert at most once, so an expert has <= T rows
 constexpr int MOE_E_MAX = 256;           // experts: the router's wave holds 4 logits per lane
 constexpr int MOE_TOPK_MAX = 8;
-constexpr SkinnyForm MOE_FORM = SKINNY_W16;  // the grouped GEMM runs the 16-bit decode-step GEMM's K loop: its step and chunks
 
-// The 16-bit decode-step GEMM's plan at M = T: mf = ceil(T / 16) row fragments, the host's bound on an expert's rows, for which
+// The form's decode-step GEMM plan at M = T: mf = ceil(T / 16) row fragments, the host's bound on an expert's rows, for which
 // the kernel is built; tiles_n; steps; glu.  nsplit is this unit's own (moe_nsplit), and the slices are skinny_slice's.
 struct MoePlan : SkinnyPlan {
   int rows;  // routed rows: T * k
@@ -41,14 +40,12 @@ static inline int moe_min_slice(const SkinnyForm& f, int64_t T, int32_t k, int32
   const int kstep = f.kstep;
   return (int)std::max<int64_t>(kstep, (f.min_k_per_row * rbar + kstep - 1) / kstep * kstep);
 }
-static inline int moe_min_slice(int64_t T, int32_t k, int32_t E) { return moe_min_slice(MOE_FORM, T, k, E); }
 
 static inline int moe_nsplit(const SkinnyForm& f, int64_t T, int32_t k, int32_t E, int32_t N, int32_t K) {
   const int64_t wgs = (int64_t)moe_experts_aimed(T, k, E) * ((N + SKINNY_BN - 1) / SKINNY_BN);
   const int want = wgs > 0 ? (int)((SKINNY_WGS + wgs - 1) / wgs) : 1;
   return std::max(1, std::min(want, K / moe_min_slice(f, T, k, E)));
 }
-static inline int moe_nsplit(int64_t T, int32_t k, int32_t E, int32_t N, int32_t K) { return moe_nsplit(MOE_FORM, T, k, E, N, K); }
 
 // the routing part of every entry point's checks; who prefixes the message
 static inline bool moe_route_shape_ok(const char* who, int64_t T, int32_t k, int32_t E, std::string& err) {
@@ -72,9 +69,6 @@ static inline bool moe_shape_ok(const SkinnyForm& f, const char* who, int64_t T,
   err = who + err;
   return false;
 }
-static inline bool moe_shape_ok(const char* who, int64_t T, int32_t k, int32_t E, int32_t N, int32_t K, int32_t act, std::string& err) {
-  return moe_shape_ok(MOE_FORM, who, T, k, E, N, K, act, err);
-}
 
 static inline MoePlan moe_plan(const SkinnyForm& f, int64_t T, int32_t k, int32_t E, int32_t N, int32_t K, int32_t act) {
   MoePlan pl;
@@ -82,9 +76,6 @@ static inline MoePlan moe_plan(const SkinnyForm& f, int64_t T, int32_t k, int32_
   pl.nsplit = moe_nsplit(f, T, k, E, N, K);
   pl.rows = (int)(T * k);
   return pl;
-}
-static inline MoePlan moe_plan(int64_t T, int32_t k, int32_t E, int32_t N, int32_t K, int32_t act) {
-  return moe_plan(MOE_FORM, T, k, E, N, K, act);
 }
 
 // up: fp32 partials [nsplit][T k][N] by sorted position (SwiGLU: the up half, then the gate half); none with one slice

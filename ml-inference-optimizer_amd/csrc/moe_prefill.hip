@@ -421,7 +421,7 @@ extern "C" int mio_moe_prefill_down(const void* h, const void* w_down, const voi
   MIO_CHECK(workspace != nullptr, fn + ": workspace required (mio_moe_prefill_down_workspace_bytes)");
   MoePfDev p = moe_pf_args(h, w_down, expert_offsets, nullptr, tile_expert, tile_row0, num_tiles, ldh, ldw, expert_stride, T, top_k, E, d, I);
   p.ws = (float*)workspace;
-  const MoeDownDev f = {(const float*)workspace, b_down, residual, y, ids, weights, row_pos, ldy, ldr, T, top_k, E, p.rows, d, 1};
+  const MoeDownDev f = {(const float*)workspace, nullptr, b_down, residual, y, ids, weights, row_pos, ldy, ldr, T, top_k, E, p.rows, d, 1};
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(MOE_PF_TABLE[dtype == MIO_BF16 ? 0 : 1][2], dim3((unsigned)p.max_tiles, (unsigned)((d + MOE_PF_BN - 1) / MOE_PF_BN)),
                      dim3(MOE_PF_NT), 0, st, p);

@@ -2083,34 +2083,43 @@ def _moe_act(activation: str) -> int:
 def moe_up_splits(T: int, top_k: int, E: int, I: int, d: int, activation: str = "swiglu") -> int:
     """The slices of K = d a moe_up call of this shape runs (1: one launch, no workspace).  Host-only; ValueError where the call
     would be refused."""
-    n = lib.mio_moe_up_splits(T, top_k, E, I, d, _moe_act(activation))
-    if n < 0:
-        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
-    return n
+    return _moe_splits(lib.mio_moe_up_splits, T, top_k, E, I, d, _moe_act(activation))
 
 
 def moe_down_splits(T: int, top_k: int, E: int, d: int, I: int) -> int:
     """The slices of K = I a moe_down call of this shape runs.  Host-only; ValueError where the call would be refused."""
-    n = lib.mio_moe_down_splits(T, top_k, E, d, I)
+    return _moe_splits(lib.mio_moe_down_splits, T, top_k, E, d, I)
+
+
+def _moe_splits(fn, *sizes) -> int:
+    n = fn(*sizes)
     if n < 0:
         raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
     return n
 
 
-def _moe_weight(w, E: int, dtype, name: str, who: str, like=None) -> torch.Tensor:
-    """A stacked expert weight [E, N, K] as the kernels take it: last-dim stride 1, row and expert strides multiples of 8, 16-byte
-    aligned (a copy otherwise); like: the weight it must share shape and strides with (the SwiGLU gate and up)."""
+def _moe_weight(w, E: int, dtype, name: str, who: str, like=None, multiple: int = 8, k_multiple: int = 1) -> torch.Tensor:
+    """A stacked expert weight [E, N, K] of dtype (the activations', or torch.float8_e4m3fn) as the kernels take it: K a multiple
+    of k_multiple, last-dim stride 1, row and expert strides multiples of `multiple` elements (16 bytes), 16-byte aligned (a copy
+    otherwise); like: the weight it must share strides with (the SwiGLU gate and up)."""
     if not isinstance(w, torch.Tensor) or w.dim() != 3 or w.shape[0] != E:
         raise ValueError(f"{who}: {name} must be a stacked expert weight [E = {E}, N, K]")
     _need_cuda(w)
     if w.dtype != dtype:
-        raise ValueError(f"{who}: {name} must have the activation dtype {dtype}, got {w.dtype}")
+        raise ValueError(f"{who}: {name} must be torch.float8_e4m3fn (OCP e4m3), got {w.dtype}" if dtype == _W8
+                         else f"{who}: {name} must have the activation dtype {dtype}, got {w.dtype}")
     N, K = w.shape[1:]
-    ok = (w.stride(2) == 1 and w.stride(1) % 8 == 0 and w.stride(1) >= K and w.stride(0) % 8 == 0
+    if K % k_multiple != 0:
+        raise ValueError(f"{who}: K must be a multiple of {k_multiple}, got {K} ({name})")
+    ok = (w.stride(2) == 1 and w.stride(1) % multiple == 0 and w.stride(1) >= K and w.stride(0) % multiple == 0
           and w.stride(0) >= (N - 1) * w.stride(1) + K and w.data_ptr() % 16 == 0)
     if not ok or (like is not None and w.stride() != like.stride()):
         w = w.contiguous()
     return w
+
+
+def _moe_weight_w8(w, E: int, dtype, name: str, who: str, like=None) -> torch.Tensor:
+    return _moe_weight(w, E, _W8, name, who, like, multiple=16, k_multiple=16)
 
 
 def _moe_bias(b, E: int, N: int, dtype, name: str, who: str):
@@ -2136,7 +2145,14 @@ def moe_up(x, route: MoERoute, w_up, act: str = "swiglu", w_gate=None, b_up=None
     row p is act(x[t] w_up[e]^T + b_up[e]) (swiglu: silu(x[t] w_gate[e]^T + b_gate[e]) * that) for the expert e and the token
     t = sorted_rows[p] // k of position p.  One launch over all experts (two when the plan splits K); experts without a routed
     row are not read.  out: h to write into, [T k, I], row stride a multiple of 8."""
-    who = "moe_up"
+    return _moe_up_core("moe_up", lib.mio_moe_up, lib.mio_moe_up_workspace_bytes, _moe_weight, "w_", x, route, w_up, act, w_gate,
+                        b_up, b_gate, out)
+
+
+def _moe_up_core(who, entry, workspace_bytes, weight, pre, x, route, w_up, act, w_gate, b_up, b_gate, out, scales=None):
+    """moe_up and moe_up_w8: the route and shape checks, bias preparation, out validation, the workspace and the call of `entry`.
+    weight validates a stacked weight (_moe_weight's signature), pre is the weights' name prefix ("w_", "w8_"), scales the pair
+    (s_up, s_gate) of a form whose weights carry them."""
     _need_cuda(x)
     a = _moe_act(act)
     dt = _dtype_id(x)
@@ -2146,19 +2162,25 @@ def moe_up(x, route: MoERoute, w_up, act: str = "swiglu", w_gate=None, b_up=None
     if x.shape[0] != T:
         raise ValueError(f"{who}: x has {x.shape[0]} rows, the route {T} tokens")
     glu = a == _lib.ACT_SWIGLU
-    if glu != (w_gate is not None):
+    if scales is None and glu != (w_gate is not None):
         raise ValueError("SwiGLU activation requires gate weights" if glu else f"{who}: w_gate belongs to act='swiglu'")
-    w = _moe_weight(w_up, E, x.dtype, "w_up", who)
+    if scales is not None and (glu != (w_gate is not None) or glu != (scales[1] is not None)):
+        raise ValueError("SwiGLU activation requires gate weights and their scales" if glu
+                         else f"{who}: w8_gate and s_gate belong to act='swiglu'")
+    w = weight(w_up, E, x.dtype, pre + "up", who)
     I, d = w.shape[1:]
     if x.shape[1] != d:
         raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match input features {x.shape[1]}")
+    s = () if scales is None else (_moe_scale_w8(scales[0], E, I, "s_up", who), None)
     g = None
     if glu:
         if w_gate.shape != w_up.shape:
-            raise ValueError(f"{who}: w_gate must have w_up's shape")
-        g = _moe_weight(w_gate, E, x.dtype, "w_gate", who, like=w)
+            raise ValueError(f"{who}: {pre}gate must have {pre}up's shape")
+        g = weight(w_gate, E, x.dtype, pre + "gate", who, like=w)
         if g.stride() != w.stride():
             w = w.contiguous()
+        if s:
+            s = (s[0], _moe_scale_w8(scales[1], E, I, "s_gate", who))
     bu = _moe_bias(b_up, E, I, x.dtype, "b_up", who)
     bg = _moe_bias(b_gate, E, I, x.dtype, "b_gate", who) if glu else None
     x2 = _rows16(x)
@@ -2168,11 +2190,12 @@ def moe_up(x, route: MoERoute, w_up, act: str = "swiglu", w_gate=None, b_up=None
         raise ValueError(f"{who}: out must be [{T * k}, {I}] {x.dtype} with a row stride that is a multiple of 8")
     if T == 0:
         return out
-    nbytes = lib.mio_moe_up_workspace_bytes(T, k, E, I, d, a)
+    nbytes = workspace_bytes(T, k, E, I, d, a)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
-    check(lib.mio_moe_up(x2.data_ptr(), w.data_ptr(), _ptr(bu), _ptr(g), _ptr(bg), route.expert_offsets.data_ptr(),
-                         route.sorted_rows.data_ptr(), out.data_ptr(), _ptr(ws), T, k, E, I, d, _ld(x2, d), w.stride(1), w.stride(0),
-                         _ld(out, I), a, dt, _stream()))
+    # (the scaled entry point takes each weight's scales behind the weight)
+    check(entry(x2.data_ptr(), w.data_ptr(), *map(_ptr, s[:1]), _ptr(bu), _ptr(g), *map(_ptr, s[1:]), _ptr(bg),
+                route.expert_offsets.data_ptr(), route.sorted_rows.data_ptr(), out.data_ptr(), _ptr(ws), T, k, E, I, d, _ld(x2, d),
+                w.stride(1), w.stride(0), _ld(out, I), a, dt, _stream()))
     return out
 
 
@@ -2180,16 +2203,23 @@ def moe_down(h, route: MoERoute, w_down, b_down=None, residual=None, out=None):
     """The grouped down projection and the combine (mio_moe_down): h [T k, I] by sorted position (moe_up's output), w_down
     [E, d, I] -> y [T, d] = sum_j weights[t, j] (h[row_pos[t k + j]] w_down[e]^T + b_down[e]) (+ residual[t]), e = ids[t, j]: the
     slots summed in fp32 in slot order and rounded once.  residual [T, d] is also where a shared expert's output goes in."""
-    who = "moe_down"
+    return _moe_down_core("moe_down", lib.mio_moe_down, lib.mio_moe_down_workspace_bytes, _moe_weight, "w_down", h, route, w_down,
+                          b_down, residual, out)
+
+
+def _moe_down_core(who, entry, workspace_bytes, weight, wname, h, route, w_down, b_down, residual, out, scales=None):
+    """moe_down and moe_down_w8: the route and shape checks, bias and residual preparation, out validation, the workspace and the
+    call of `entry`.  weight validates the stacked weight named wname; scales is (s_down,) of a form whose weights carry scales."""
     _need_cuda(h)
     dt = _dtype_id(h)
     T, k, E = _moe_route_ok(route, who, h.device)
     if h.dim() != 2 or h.shape[0] != T * k:
         raise ValueError(f"{who}: h must be [T k = {T * k}, I], got {tuple(h.shape)}")
-    w = _moe_weight(w_down, E, h.dtype, "w_down", who)
+    w = weight(w_down, E, h.dtype, wname, who)
     d, I = w.shape[1:]
     if h.shape[1] != I:
         raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match h's {h.shape[1]} features")
+    s = () if scales is None else (_moe_scale_w8(scales[0], E, d, "s_down", who),)
     bd = _moe_bias(b_down, E, d, h.dtype, "b_down", who)
     h2 = _rows16(h)
     _res_ok(residual, T * d, h.dtype)
@@ -2202,11 +2232,11 @@ def moe_down(h, route: MoERoute, w_down, b_down=None, residual=None, out=None):
         raise ValueError(f"{who}: out must be [{T}, {d}] {h.dtype} with a row stride that is a multiple of 8")
     if T == 0:
         return out
-    nbytes = lib.mio_moe_down_workspace_bytes(T, k, E, d, I)
+    nbytes = workspace_bytes(T, k, E, d, I)
     ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=h.device)
-    check(lib.mio_moe_down(h2.data_ptr(), w.data_ptr(), _ptr(bd), route.ids.data_ptr(), route.weights.data_ptr(),
-                           route.expert_offsets.data_ptr(), route.row_pos.data_ptr(), _ptr(r2), out.data_ptr(), ws.data_ptr(), T, k, E, d,
-                           I, _ld(h2, I), w.stride(1), w.stride(0), _ld(out, d), 0 if r2 is None else _ld(r2, d), dt, _stream()))
+    check(entry(h2.data_ptr(), w.data_ptr(), *map(_ptr, s), _ptr(bd), route.ids.data_ptr(), route.weights.data_ptr(),
+                route.expert_offsets.data_ptr(), route.row_pos.data_ptr(), _ptr(r2), out.data_ptr(), ws.data_ptr(), T, k, E, d, I,
+                _ld(h2, I), w.stride(1), w.stride(0), _ld(out, d), 0 if r2 is None else _ld(r2, d), dt, _stream()))
     return out
 
 
@@ -2230,40 +2260,15 @@ def quantize_expert_weights_w8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Ten
     return w8.view(E, N, K), scale.view(E, N)
 
 
-def _moe_w8_splits(fn, *sizes) -> int:
-    n = fn(*sizes)
-    if n < 0:
-        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
-    return n
-
-
 def moe_up_w8_splits(T: int, top_k: int, E: int, I: int, d: int, activation: str = "swiglu") -> int:
     """The slices of K = d a moe_up_w8 call of this shape runs (1: one launch, no workspace).  Host-only; ValueError where the
     call would be refused."""
-    return _moe_w8_splits(lib.mio_moe_up_w8_splits, T, top_k, E, I, d, _moe_act(activation))
+    return _moe_splits(lib.mio_moe_up_w8_splits, T, top_k, E, I, d, _moe_act(activation))
 
 
 def moe_down_w8_splits(T: int, top_k: int, E: int, d: int, I: int) -> int:
     """The slices of K = I a moe_down_w8 call of this shape runs.  Host-only; ValueError where the call would be refused."""
-    return _moe_w8_splits(lib.mio_moe_down_w8_splits, T, top_k, E, d, I)
-
-
-def _moe_weight_w8(w, E: int, name: str, who: str, like=None) -> torch.Tensor:
-    """A stacked FP8 expert weight [E, N, K] as the kernels take it: torch.float8_e4m3fn, K % 16 == 0, last-dim stride 1, row and
-    expert strides multiples of 16 bytes, 16-byte aligned (a copy otherwise); like: the weight it must share strides with."""
-    if not isinstance(w, torch.Tensor) or w.dim() != 3 or w.shape[0] != E:
-        raise ValueError(f"{who}: {name} must be a stacked expert weight [E = {E}, N, K]")
-    _need_cuda(w)
-    if w.dtype != _W8:
-        raise ValueError(f"{who}: {name} must be torch.float8_e4m3fn (OCP e4m3), got {w.dtype}")
-    N, K = w.shape[1:]
-    if K % 16 != 0:
-        raise ValueError(f"{who}: K must be a multiple of 16, got {K} ({name})")
-    ok = (w.stride(2) == 1 and w.stride(1) % 16 == 0 and w.stride(1) >= K and w.stride(0) % 16 == 0
-          and w.stride(0) >= (N - 1) * w.stride(1) + K and w.data_ptr() % 16 == 0)
-    if not ok or (like is not None and w.stride() != like.stride()):
-        w = w.contiguous()
-    return w
+    return _moe_splits(lib.mio_moe_down_w8_splits, T, top_k, E, d, I)
 
 
 def _moe_scale_w8(s, E: int, N: int, name: str, who: str) -> torch.Tensor:
@@ -2279,83 +2284,16 @@ def moe_up_w8(x, route: MoERoute, w8_up, s_up, act: str = "swiglu", w8_gate=None
     torch.float8_e4m3fn with d % 16 == 0, s_up / s_gate fp32 [E, I] (quantize_expert_weights_w8 makes both) -> h [T k, I] by sorted
     position: row p is act(s_up[e] * (x[t] w8_up[e]^T) + b_up[e]) (swiglu: silu of the gate's, times that).  Weights whose strides
     are multiples of 16 bytes go to the launch as they are.  Nothing synchronises with the host."""
-    who = "moe_up_w8"
-    _need_cuda(x)
-    a = _moe_act(act)
-    dt = _dtype_id(x)
-    if x.dim() != 2:
-        raise ValueError(f"{who}: x must be [T, d], got {tuple(x.shape)}")
-    T, k, E = _moe_route_ok(route, who, x.device)
-    if x.shape[0] != T:
-        raise ValueError(f"{who}: x has {x.shape[0]} rows, the route {T} tokens")
-    glu = a == _lib.ACT_SWIGLU
-    if glu != (w8_gate is not None) or glu != (s_gate is not None):
-        raise ValueError("SwiGLU activation requires gate weights and their scales" if glu
-                         else f"{who}: w8_gate and s_gate belong to act='swiglu'")
-    w = _moe_weight_w8(w8_up, E, "w8_up", who)
-    I, d = w.shape[1:]
-    if x.shape[1] != d:
-        raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match input features {x.shape[1]}")
-    su = _moe_scale_w8(s_up, E, I, "s_up", who)
-    g = sg = None
-    if glu:
-        if w8_gate.shape != w8_up.shape:
-            raise ValueError(f"{who}: w8_gate must have w8_up's shape")
-        g = _moe_weight_w8(w8_gate, E, "w8_gate", who, like=w)
-        if g.stride() != w.stride():
-            w = w.contiguous()
-        sg = _moe_scale_w8(s_gate, E, I, "s_gate", who)
-    bu = _moe_bias(b_up, E, I, x.dtype, "b_up", who)
-    bg = _moe_bias(b_gate, E, I, x.dtype, "b_gate", who) if glu else None
-    x2 = _rows16(x)
-    if out is None:
-        out = torch.empty(T * k, _pad8(I), dtype=x.dtype, device=x.device)[:, :I]
-    elif tuple(out.shape) != (T * k, I) or out.dtype != x.dtype or (I > 1 and out.stride(1) != 1) or out.stride(0) % 8:
-        raise ValueError(f"{who}: out must be [{T * k}, {I}] {x.dtype} with a row stride that is a multiple of 8")
-    if T == 0:
-        return out
-    nbytes = lib.mio_moe_up_w8_workspace_bytes(T, k, E, I, d, a)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
-    check(lib.mio_moe_up_w8(x2.data_ptr(), w.data_ptr(), su.data_ptr(), _ptr(bu), _ptr(g), _ptr(sg), _ptr(bg),
-                            route.expert_offsets.data_ptr(), route.sorted_rows.data_ptr(), out.data_ptr(), _ptr(ws), T, k, E, I, d,
-                            _ld(x2, d), w.stride(1), w.stride(0), _ld(out, I), a, dt, _stream()))
-    return out
+    return _moe_up_core("moe_up_w8", lib.mio_moe_up_w8, lib.mio_moe_up_w8_workspace_bytes, _moe_weight_w8, "w8_", x, route, w8_up, act,
+                        w8_gate, b_up, b_gate, out, scales=(s_up, s_gate))
 
 
 def moe_down_w8(h, route: MoERoute, w8_down, s_down, b_down=None, residual=None, out=None):
     """moe_down on weight-only FP8 expert weights (mio_moe_down_w8): h [T k, I] by sorted position, w8_down [E, d, I]
     torch.float8_e4m3fn with I % 16 == 0, s_down fp32 [E, d] -> y [T, d] = sum_j weights[t, j] (s_down[e] * (h[row_pos[t k + j]]
     w8_down[e]^T) + b_down[e]) (+ residual[t]), e = ids[t, j]: the slots in slot order, rounded once."""
-    who = "moe_down_w8"
-    _need_cuda(h)
-    dt = _dtype_id(h)
-    T, k, E = _moe_route_ok(route, who, h.device)
-    if h.dim() != 2 or h.shape[0] != T * k:
-        raise ValueError(f"{who}: h must be [T k = {T * k}, I], got {tuple(h.shape)}")
-    w = _moe_weight_w8(w8_down, E, "w8_down", who)
-    d, I = w.shape[1:]
-    if h.shape[1] != I:
-        raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match h's {h.shape[1]} features")
-    sd = _moe_scale_w8(s_down, E, d, "s_down", who)
-    bd = _moe_bias(b_down, E, d, h.dtype, "b_down", who)
-    h2 = _rows16(h)
-    _res_ok(residual, T * d, h.dtype)
-    r2 = None if residual is None else _rows16(residual.reshape(T, d))
-    if r2 is not None and T > 1 and r2.stride(0) % 8:  # (d % 8 != 0, contiguous: rows at the stride the kernel's loads are laid out for)
-        r2 = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d].copy_(r2)
-    if out is None:
-        out = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d]
-    elif tuple(out.shape) != (T, d) or out.dtype != h.dtype or (d > 1 and out.stride(1) != 1) or out.stride(0) % 8:
-        raise ValueError(f"{who}: out must be [{T}, {d}] {h.dtype} with a row stride that is a multiple of 8")
-    if T == 0:
-        return out
-    nbytes = lib.mio_moe_down_w8_workspace_bytes(T, k, E, d, I)
-    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=h.device)
-    check(lib.mio_moe_down_w8(h2.data_ptr(), w.data_ptr(), sd.data_ptr(), _ptr(bd), route.ids.data_ptr(), route.weights.data_ptr(),
-                              route.expert_offsets.data_ptr(), route.row_pos.data_ptr(), _ptr(r2), out.data_ptr(), ws.data_ptr(), T, k,
-                              E, d, I, _ld(h2, I), w.stride(1), w.stride(0), _ld(out, d), 0 if r2 is None else _ld(r2, d), dt,
-                              _stream()))
-    return out
+    return _moe_down_core("moe_down_w8", lib.mio_moe_down_w8, lib.mio_moe_down_w8_workspace_bytes, _moe_weight_w8, "w8_down", h, route,
+                          w8_down, b_down, residual, out, scales=(s_down,))
 
 
 def moe_mlp_w8(x, route: MoERoute, w8_up, s_up, w8_down, s_down, act: str = "swiglu", w8_gate=None, s_gate=None, b_up=None,

@@ -18,14 +18,18 @@ CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I../../incl
 FA_FLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]
 
 
-def device_isa(tmp_path, src, defines, attention=True):
+# what the Makefile adds for the units that keep the packed fp32 forms out of their epilogues (moe_prefill.hip, moe_w8.hip)
+NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+
+
+def device_isa(tmp_path, src, defines, attention=True, extra_flags=()):
     """The file (under tmp_path) of the device assembly of csrc/<src> compiled with -D<define> for each of defines (plus
-    FA_FLAGS when attention).  Skips the test when hipcc is missing."""
+    FA_FLAGS when attention, plus extra_flags).  Skips the test when hipcc is missing."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
     isa = tmp_path / (os.path.splitext(src)[0] + "".join("_" + d.replace("=", "") for d in defines) + ".s")
-    cmd = [hipcc, *CXXFLAGS, *(FA_FLAGS if attention else []), *("-D" + d for d in defines), "-S", "--cuda-device-only",
+    cmd = [hipcc, *CXXFLAGS, *(FA_FLAGS if attention else []), *extra_flags, *("-D" + d for d in defines), "-S", "--cuda-device-only",
            src, "-o", str(isa)]
     subprocess.run(cmd, cwd=CSRC, check=True, capture_output=True)
     return isa

@@ -57,6 +57,8 @@ CASES = [
     ("T 64 over E 128, 28 idle, two slices", 64, 8, 128, 72, 1040, "swiglu", True, True, 100),
     ("K 1040 plain: 5 chunks on the depth-3 ring", 64, 8, 256, 70, 1040, "none", True, False, 256),
     ("K 656 SwiGLU: 6 chunks on the depth-4 ring", 64, 8, 256, 72, 656, "swiglu", False, False, 256),
+    # the scaled branch of the shared down finish with b_down, a residual and N % 4 != 0 at once over several slices
+    ("T 3, N 15: bias and ragged columns across two slices", 3, 2, 4, 15, 144, "gelu", True, True, 4),
 ]
 
 

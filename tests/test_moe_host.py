@@ -109,8 +109,23 @@ def test_empty_calls_and_queries():
         ops.moe_route(torch.zeros(4, 8), 2)  # a CPU tensor: there is no fallback
 
 
+@pytest.mark.parametrize("src,kernel,flags", [("moe.hip", "moe_gemm_kernel", ()), ("moe_w8.hip", "moe_gemm_w8_kernel", "no_packed")])
+def test_kernels_fit_256_vgprs_without_scratch(tmp_path, src, kernel, flags):
+    """The compiled decode units' kernel metadata, each unit under its Makefile flags: every instance of the grouped GEMM kernel (2
+    dtypes x 4 row-fragment counts x plain / SwiGLU), up's reduction and down's finishing launch use no scratch, spill nothing and
+    stay within 256 VGPRs."""
+    import _isa
+    extra = _isa.NO_PACKED_FP32_FLAGS if flags == "no_packed" else ()
+    text = _isa.device_isa(tmp_path, src, [], attention=False, extra_flags=extra).read_text()
+    for name_re, count in ((rf"_Z\d+{kernel}I\w+", 16), (r"_Z20moe_up_reduce_kernel\w+", 4), (r"_Z22moe_down_finish_kernel\w+", 2)):
+        blocks = _isa.metadata(text, name_re)
+        assert len(blocks) == count, (name_re, len(blocks))
+        for blk in blocks:
+            _isa.check_fits_256(blk)
+
+
 # ---- the plan ----------------------------------------------------------------------------------------------------------------------
-SWEEP = [(T, k, E, N) for T in (1, 4, 17, 64) for k, E in ((1, 1), (2, 8), (4, 60), (8, 128), (8, 256), (1, 256))
+SWEEP =[(T, k, E, N) for T in (1, 4, 17, 64) for k, E in ((1, 1), (2, 8), (4, 60), (8, 128), (8, 256), (1, 256))
          for N in (1, 72, 136, 1000, 14336)]
 
 
