@@ -1,10 +1,11 @@
-"""Mixture-of-experts MLP for decode steps on the HIP kernels (not a reference module: its models are dense).
+"""Mixture-of-experts MLP on the HIP kernels, for decode steps and for tall inputs (not a reference module: its models are dense).
 
 MoEMLP replaces the MLP of a Mixtral / Qwen-MoE / OLMoE class block: a router (one linear layer to E logits per token), the
 top_k experts of every token, and the weighted sum of those experts' MLPs.  forward() is the router GEMM, ops.moe_route and
 ops.moe_mlp (the grouped up projection, then the grouped down projection with the combine): four to six launches whatever E is,
-the routing device data from start to end, so a step can be captured in a graph.  There is no PyTorch path: CPU tensors raise
-ValueError as the other modules do.
+the routing device data from start to end, so a step can be captured in a graph.  MoEConfig selects the FP8 copies of the expert
+weights (ops.moe_mlp_w8) or, for more than 64 rows, the tiled path (ops.moe_route_prefill, ops.moe_mlp_prefill).  There is no
+PyTorch path: CPU tensors raise ValueError as the other modules do.
 """
 from __future__ import annotations
 
@@ -104,34 +105,25 @@ class MoEMLP(nn.Module):
         x = as_dtype(hidden_states, dt).reshape(-1, d)
         r = None if residual is None else as_dtype(residual, dt).reshape(-1, d)
         T = x.shape[0]
-        out = torch.empty(T, ops._pad8(d), dtype=dt, device=x.device)[:, :d]
+        out = ops.empty_rows8(T, d, dt, x.device)
+        # the path, chosen once on the whole T (a short last chunk of a tall input stays on the prefill ops): its chunk length,
+        # its route and MLP ops, and the weights under the names that MLP op takes them by
         prefill = self.config.grouped_prefill and T > ops.MOE_MAX_TOKENS
         if self.config.expert_weights_fp8 and not prefill:
+            chunk, route_op, mlp_op = ops.MOE_MAX_TOKENS, ops.moe_route, ops.moe_mlp_w8
             (q_up, s_up), (q_down, s_down) = c.get_experts_w8(self.w_up, dt), c.get_experts_w8(self.w_down, dt)
             q_gate, s_gate = c.get_experts_w8(self.w_gate, dt) if self.w_gate is not None else (None, None)
-            for lo in range(0, T, ops.MOE_MAX_TOKENS):
-                hi = min(T, lo + ops.MOE_MAX_TOKENS)
-                xc = x[lo:hi]
-                route = ops.moe_route(self._router_logits(xc, dt), self.top_k, self.config.renormalize)
-                ops.moe_mlp_w8(xc, route, q_up, s_up, q_down, s_down, self.config.activation, q_gate, s_gate,
-                               residual=None if r is None else r[lo:hi], out=out[lo:hi])
-            return as_dtype(out.reshape(*hidden_states.shape[:-1], d), in_dtype)
-        w_up, w_down = c.get(self.w_up, dt), c.get(self.w_down, dt)
-        w_gate = c.get(self.w_gate, dt) if self.w_gate is not None else None
-        if prefill:
-            for lo in range(0, T, ops.MOE_PREFILL_MAX_TOKENS):
-                hi = min(T, lo + ops.MOE_PREFILL_MAX_TOKENS)
-                xc = x[lo:hi]
-                route = ops.moe_route_prefill(self._router_logits(xc, dt), self.top_k, self.config.renormalize)
-                ops.moe_mlp_prefill(xc, route, w_up, w_down, self.config.activation, w_gate, residual=None if r is None else r[lo:hi],
-                                    out=out[lo:hi])
-            return as_dtype(out.reshape(*hidden_states.shape[:-1], d), in_dtype)
-        for lo in range(0, T, ops.MOE_MAX_TOKENS):
-            hi = min(T, lo + ops.MOE_MAX_TOKENS)
+            weights = dict(w8_up=q_up, s_up=s_up, w8_down=q_down, s_down=s_down, w8_gate=q_gate, s_gate=s_gate)
+        else:
+            chunk, route_op, mlp_op = ((ops.MOE_PREFILL_MAX_TOKENS, ops.moe_route_prefill, ops.moe_mlp_prefill) if prefill
+                                       else (ops.MOE_MAX_TOKENS, ops.moe_route, ops.moe_mlp))
+            weights = dict(w_up=c.get(self.w_up, dt), w_down=c.get(self.w_down, dt),
+                           w_gate=c.get(self.w_gate, dt) if self.w_gate is not None else None)
+        for lo in range(0, T, chunk):
+            hi = min(T, lo + chunk)
             xc = x[lo:hi]
-            route = ops.moe_route(self._router_logits(xc, dt), self.top_k, self.config.renormalize)
-            ops.moe_mlp(xc, route, w_up, w_down, self.config.activation, w_gate, residual=None if r is None else r[lo:hi],
-                        out=out[lo:hi])
+            route = route_op(self._router_logits(xc, dt), self.top_k, self.config.renormalize)
+            mlp_op(xc, route, act=self.config.activation, **weights, residual=None if r is None else r[lo:hi], out=out[lo:hi])
         return as_dtype(out.reshape(*hidden_states.shape[:-1], d), in_dtype)
 
     def load_from_expert_state_dict(self, state_dict: Dict[str, torch.Tensor], prefix: str = "", gate: str = "gate.weight",

@@ -1994,9 +1994,12 @@ def sampling_probs(logits, temperature, top_k=None, top_p=None, min_p=None):
 
 
 # ------------------------------------------------------------------------------------------------
-# mixture-of-experts MLP for decode steps: router, grouped up projection, grouped down projection + combine
+# mixture-of-experts MLP: router, grouped up projection, grouped down projection + combine.  Three paths -- decode steps on
+# 16-bit experts, decode steps on FP8 experts, tall inputs (prefill) over a tile map -- each a _MoEPath record; route, up and
+# down are stated once (_moe_route_core, _moe_up_core, _moe_down_core) and the public ops hand them their path
 # ------------------------------------------------------------------------------------------------
 MOE_MAX_TOKENS, MOE_MAX_EXPERTS, MOE_MAX_TOP_K = 64, 256, 8
+MOE_PREFILL_MAX_TOKENS = 8192
 
 
 class MoERoute(NamedTuple):
@@ -2010,6 +2013,22 @@ class MoERoute(NamedTuple):
     row_pos: torch.Tensor
     top_k: int
     num_experts: int
+
+
+class MoEPrefillRoute(NamedTuple):
+    """What moe_route_prefill decides: MoERoute's fields under the same names with the same definitions, and the tile map of the
+    grouped GEMMs (semantics: include/mio_hip.h): tile_expert int32 [max_tiles], tile_row0 int32 [max_tiles], num_tiles int32
+    [1], max_tiles = moe_prefill_max_tiles(T, top_k, E); entries past num_tiles are not written."""
+    ids: torch.Tensor
+    weights: torch.Tensor
+    expert_offsets: torch.Tensor
+    sorted_rows: torch.Tensor
+    row_pos: torch.Tensor
+    top_k: int
+    num_experts: int
+    tile_expert: torch.Tensor
+    tile_row0: torch.Tensor
+    num_tiles: torch.Tensor
 
 
 def _moe_route_ok(route, who: str, device) -> Tuple[int, int, int]:
@@ -2028,13 +2047,101 @@ def _moe_route_ok(route, who: str, device) -> Tuple[int, int, int]:
     return T, k, E
 
 
+def _moe_splits(fn, *sizes) -> int:
+    """A host query of the library that answers a count, or below 0 with the refusal in mio_last_error."""
+    n = fn(*sizes)
+    if n < 0:
+        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def moe_prefill_max_tiles(T: int, top_k: int, E: int) -> int:
+    """The bound on the tile map, floor(T k / 128) + min(E, T k).  Host-only; ValueError where the launches would refuse the shape."""
+    return _moe_splits(lib.mio_moe_prefill_max_tiles, T, top_k, E)
+
+
+def _moe_tile_shapes(T: int, k: int, E: int):
+    """((field, shape), ...) of a MoEPrefillRoute's tile map, int32 tensors in the order the entry points take them."""
+    mt = moe_prefill_max_tiles(T, k, E)
+    return ("tile_expert", (mt,)), ("tile_row0", (mt,)), ("num_tiles", (1,))
+
+
+def _moe_prefill_route_ok(route, who: str, device) -> Tuple[int, int, int]:
+    """(T, k, E) of a MoEPrefillRoute whose tensors are what the kernels take from raw pointers."""
+    if not isinstance(route, MoEPrefillRoute):
+        raise ValueError(f"{who}: route must be a MoEPrefillRoute (ops.moe_route_prefill)")
+    T, k, E = _moe_route_ok(MoERoute(*route[:7]), who, device)
+    if T > MOE_PREFILL_MAX_TOKENS:
+        raise ValueError(f"{who} takes at most {MOE_PREFILL_MAX_TOKENS} tokens, got {T}")
+    for name, shape in _moe_tile_shapes(T, k, E):
+        t = getattr(route, name)
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+            raise ValueError(f"{who}: route.{name} must be a tensor on the activations' device")
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{who}: route.{name} must be a contiguous int32 tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    return T, k, E
+
+
+class _MoEPath(NamedTuple):
+    """What differs between the ways through the MoE MLP; everything else is the cores'.  One instance per path, made at import."""
+    route_op: str                 # the public ops' names, as refusals cite them
+    up_op: str
+    down_op: str
+    route_type: type              # what route_op returns and up_op / down_op take ...
+    route_ok: object              # ... and its checker, (route, who, device) -> (T, k, E)
+    max_tokens: int               # the router's cap on T ...
+    cap_note: str                 # ... and what its refusal adds behind "tokens"
+    tiled: bool                   # the route brings a tile map, and the entry points take its three pointers
+    route_entry: object           # the C entry points
+    up_entry: object
+    up_workspace_bytes: object    # the host query behind up's workspace; None: up_entry takes no workspace
+    down_entry: object
+    down_workspace_bytes: object
+    w_dtype: Optional[torch.dtype]  # the stacked weights' dtype; None: the activations'
+    w_multiple: int               # row and expert strides of a weight are multiples of this many elements (16 bytes) ...
+    k_multiple: int               # ... and K a multiple of this
+    pre: str                      # the weights' names: pre + "up" / "gate" / "down"
+    scaled: bool                  # every weight comes with fp32 scales [E, N], handed to the entry point behind it
+
+
+def _moe_tile_ptrs(route: MoEPrefillRoute) -> tuple:
+    """The tile map's pointers in the order the entry points of a tiled path take them."""
+    return route.tile_expert.data_ptr(), route.tile_row0.data_ptr(), route.num_tiles.data_ptr()
+
+
+_MOE_DECODE = _MoEPath(
+    route_op="moe_route", up_op="moe_up", down_op="moe_down", route_type=MoERoute, route_ok=_moe_route_ok,
+    max_tokens=MOE_MAX_TOKENS, cap_note=" (decode steps only)", tiled=False, route_entry=lib.mio_moe_route,
+    up_entry=lib.mio_moe_up, up_workspace_bytes=lib.mio_moe_up_workspace_bytes,
+    down_entry=lib.mio_moe_down, down_workspace_bytes=lib.mio_moe_down_workspace_bytes,
+    w_dtype=None, w_multiple=8, k_multiple=1, pre="w_", scaled=False)
+# (DESIGN 4.2f: the same route; e4m3fn weight bytes, so 16 elements are 16 bytes)
+_MOE_DECODE_W8 = _MOE_DECODE._replace(
+    up_op="moe_up_w8", down_op="moe_down_w8",
+    up_entry=lib.mio_moe_up_w8, up_workspace_bytes=lib.mio_moe_up_w8_workspace_bytes,
+    down_entry=lib.mio_moe_down_w8, down_workspace_bytes=lib.mio_moe_down_w8_workspace_bytes,
+    w_dtype=_W8, w_multiple=16, k_multiple=16, pre="w8_", scaled=True)
+# (DESIGN 4.2e: the 16-bit weights under a route with a tile map; up finishes in its one launch)
+_MOE_PREFILL = _MOE_DECODE._replace(
+    route_op="moe_route_prefill", up_op="moe_up_prefill", down_op="moe_down_prefill", route_type=MoEPrefillRoute,
+    route_ok=_moe_prefill_route_ok, max_tokens=MOE_PREFILL_MAX_TOKENS, cap_note="", tiled=True,
+    route_entry=lib.mio_moe_prefill_route, up_entry=lib.mio_moe_prefill_up, up_workspace_bytes=None,
+    down_entry=lib.mio_moe_prefill_down, down_workspace_bytes=lib.mio_moe_prefill_down_workspace_bytes)
+
+
 def moe_route(router_logits, top_k: int, renormalize: bool = True, out: Optional[MoERoute] = None) -> MoERoute:
     """Route T <= 64 tokens over E <= 256 experts in one launch (mio_moe_route): router_logits [T, E] (or [..., E], flattened; bf16,
     fp16 or fp32, last-dim stride 1) -> the top_k experts of every token in the sampler's order (ties to the lowest index, NaN as
     -inf), their softmax-over-all-experts weights (renormalize: divided by their sum), and the routed rows grouped by expert.
     out: a MoERoute of the same (T, top_k, E) to write into (a captured step reuses its buffers).  T == 0 launches nothing and
     zeroes expert_offsets (out's too).  Nothing is read back to the host."""
-    who = "moe_route"
+    return _moe_route_core(_MOE_DECODE, router_logits, top_k, renormalize, out)
+
+
+def _moe_route_core(p: _MoEPath, router_logits, top_k: int, renormalize: bool, out):
+    """moe_route and moe_route_prefill: the logits checks, the stride and alignment fix-ups, the outputs (made here, or the
+    caller's, checked), the zeroing of an empty routing and the call of p.route_entry."""
+    who = p.route_op
     if not isinstance(router_logits, torch.Tensor):
         raise ValueError(f"{who}: router_logits must be a tensor")
     _need_cuda(router_logits)
@@ -2052,8 +2159,8 @@ def moe_route(router_logits, top_k: int, renormalize: bool = True, out: Optional
     if x.stride(-1) != 1 and E > 1:
         x = x.contiguous()
     T = x.shape[0]
-    if T > MOE_MAX_TOKENS:
-        raise ValueError(f"{who} takes at most {MOE_MAX_TOKENS} tokens (decode steps only), got {T}")
+    if T > p.max_tokens:
+        raise ValueError(f"{who} takes at most {p.max_tokens} tokens{p.cap_note}, got {T}")
     ld = x.stride(0) if T > 1 else E
     if ld < E or x.data_ptr() % 16:
         x, ld = x.contiguous(), E
@@ -2062,15 +2169,19 @@ def moe_route(router_logits, top_k: int, renormalize: bool = True, out: Optional
     dev = x.device
     if out is None:
         i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)  # noqa: E731
-        out = MoERoute(i32(T, k), torch.empty(T, k, dtype=torch.float32, device=dev), i32(E + 1), i32(T * k), i32(T * k), k, E)
-    elif _moe_route_ok(out, who, dev) != (T, k, E):
+        tiles = _moe_tile_shapes(T, k, E) if p.tiled else ()  # (asked before anything is allocated; the map is allocated last)
+        out = p.route_type(i32(T, k), torch.empty(T, k, dtype=torch.float32, device=dev), i32(E + 1), i32(T * k), i32(T * k), k, E,
+                           *(tiles and [i32(*shape) for _, shape in tiles]))
+    elif p.route_ok(out, who, dev) != (T, k, E):
         raise ValueError(f"{who}: out was made for another (T, top_k, E)")
-    if T == 0:  # (nothing is launched: the offsets of an empty routing are zeros, in the caller's buffer as in ours)
+    if T == 0:  # (nothing is launched: the offsets and the tile count of an empty routing are zeros, in the caller's buffer as in ours)
         out.expert_offsets.zero_()
+        if p.tiled:
+            out.num_tiles.zero_()
     else:
-        check(lib.mio_moe_route(x.data_ptr(), ld, out.ids.data_ptr(), out.weights.data_ptr(), out.expert_offsets.data_ptr(),
-                                out.sorted_rows.data_ptr(), out.row_pos.data_ptr(), T, E, k, 1 if renormalize else 0,
-                                _SAMPLE_DTYPES[x.dtype], _stream()))
+        check(p.route_entry(x.data_ptr(), ld, out.ids.data_ptr(), out.weights.data_ptr(), out.expert_offsets.data_ptr(),
+                            out.sorted_rows.data_ptr(), out.row_pos.data_ptr(), *(_moe_tile_ptrs(out) if p.tiled else ()), T, E, k,
+                            1 if renormalize else 0, _SAMPLE_DTYPES[x.dtype], _stream()))
     return out
 
 
@@ -2091,35 +2202,26 @@ def moe_down_splits(T: int, top_k: int, E: int, d: int, I: int) -> int:
     return _moe_splits(lib.mio_moe_down_splits, T, top_k, E, d, I)
 
 
-def _moe_splits(fn, *sizes) -> int:
-    n = fn(*sizes)
-    if n < 0:
-        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
-    return n
-
-
-def _moe_weight(w, E: int, dtype, name: str, who: str, like=None, multiple: int = 8, k_multiple: int = 1) -> torch.Tensor:
-    """A stacked expert weight [E, N, K] of dtype (the activations', or torch.float8_e4m3fn) as the kernels take it: K a multiple
-    of k_multiple, last-dim stride 1, row and expert strides multiples of `multiple` elements (16 bytes), 16-byte aligned (a copy
-    otherwise); like: the weight it must share strides with (the SwiGLU gate and up)."""
+def _moe_weight(p: _MoEPath, w, E: int, act_dtype, name: str, who: str, like=None) -> torch.Tensor:
+    """A stacked expert weight [E, N, K] of the path's dtype (the activations', or torch.float8_e4m3fn) as the kernels take it: K
+    a multiple of p.k_multiple, last-dim stride 1, row and expert strides multiples of p.w_multiple elements (16 bytes), 16-byte
+    aligned (a copy otherwise); like: the weight it must share strides with (the SwiGLU gate and up)."""
     if not isinstance(w, torch.Tensor) or w.dim() != 3 or w.shape[0] != E:
         raise ValueError(f"{who}: {name} must be a stacked expert weight [E = {E}, N, K]")
     _need_cuda(w)
+    dtype = p.w_dtype or act_dtype
     if w.dtype != dtype:
         raise ValueError(f"{who}: {name} must be torch.float8_e4m3fn (OCP e4m3), got {w.dtype}" if dtype == _W8
                          else f"{who}: {name} must have the activation dtype {dtype}, got {w.dtype}")
     N, K = w.shape[1:]
-    if K % k_multiple != 0:
-        raise ValueError(f"{who}: K must be a multiple of {k_multiple}, got {K} ({name})")
-    ok = (w.stride(2) == 1 and w.stride(1) % multiple == 0 and w.stride(1) >= K and w.stride(0) % multiple == 0
+    if K % p.k_multiple != 0:
+        raise ValueError(f"{who}: K must be a multiple of {p.k_multiple}, got {K} ({name})")
+    mult = p.w_multiple
+    ok = (w.stride(2) == 1 and w.stride(1) % mult == 0 and w.stride(1) >= K and w.stride(0) % mult == 0
           and w.stride(0) >= (N - 1) * w.stride(1) + K and w.data_ptr() % 16 == 0)
     if not ok or (like is not None and w.stride() != like.stride()):
         w = w.contiguous()
     return w
-
-
-def _moe_weight_w8(w, E: int, dtype, name: str, who: str, like=None) -> torch.Tensor:
-    return _moe_weight(w, E, _W8, name, who, like, multiple=16, k_multiple=16)
 
 
 def _moe_bias(b, E: int, N: int, dtype, name: str, who: str):
@@ -2140,62 +2242,75 @@ def _ld(t: torch.Tensor, n: int) -> int:
     return t.stride(0) if t.shape[0] > 1 else _pad8(n)
 
 
+def empty_rows8(rows: int, n: int, dtype: torch.dtype, device) -> torch.Tensor:
+    """An uninitialised [rows, n] tensor whose rows lie the next multiple of 8 elements apart: the row stride every out= of the
+    MoE ops asks for, and what they return where none is given."""
+    return torch.empty(rows, _pad8(n), dtype=dtype, device=device)[:, :n]
+
+
 def moe_up(x, route: MoERoute, w_up, act: str = "swiglu", w_gate=None, b_up=None, b_gate=None, out=None):
     """The grouped up projection (mio_moe_up): x [T, d], w_up (and w_gate for swiglu) [E, I, d] -> h [T k, I] BY SORTED POSITION:
     row p is act(x[t] w_up[e]^T + b_up[e]) (swiglu: silu(x[t] w_gate[e]^T + b_gate[e]) * that) for the expert e and the token
     t = sorted_rows[p] // k of position p.  One launch over all experts (two when the plan splits K); experts without a routed
     row are not read.  out: h to write into, [T k, I], row stride a multiple of 8."""
-    return _moe_up_core("moe_up", lib.mio_moe_up, lib.mio_moe_up_workspace_bytes, _moe_weight, "w_", x, route, w_up, act, w_gate,
-                        b_up, b_gate, out)
+    return _moe_up_core(_MOE_DECODE, x, route, w_up, act, w_gate, b_up, b_gate, out)
 
 
-def _moe_up_core(who, entry, workspace_bytes, weight, pre, x, route, w_up, act, w_gate, b_up, b_gate, out, scales=None):
-    """moe_up and moe_up_w8: the route and shape checks, bias preparation, out validation, the workspace and the call of `entry`.
-    weight validates a stacked weight (_moe_weight's signature), pre is the weights' name prefix ("w_", "w8_"), scales the pair
-    (s_up, s_gate) of a form whose weights carry them."""
+def _moe_out_ok(who: str, out, rows: int, n: int, dtype) -> None:
+    """The rule the kernels' stores hold a caller's out= [rows, n] to (empty_rows8 makes such a tensor)."""
+    if tuple(out.shape) != (rows, n) or out.dtype != dtype or (n > 1 and out.stride(1) != 1) or out.stride(0) % 8:
+        raise ValueError(f"{who}: out must be [{rows}, {n}] {dtype} with a row stride that is a multiple of 8")
+
+
+def _moe_up_core(p: _MoEPath, x, route, w_up, act, w_gate, b_up, b_gate, out, s_up=None, s_gate=None):
+    """moe_up, moe_up_w8 and moe_up_prefill: the route and shape checks, the gate rules, weight, scale and bias preparation, out
+    validation, the workspace of a path whose up launch takes one, and the call of p.up_entry.  s_up, s_gate: the scales of a
+    path whose weights carry them."""
+    who, pre = p.up_op, p.pre
     _need_cuda(x)
     a = _moe_act(act)
     dt = _dtype_id(x)
     if x.dim() != 2:
         raise ValueError(f"{who}: x must be [T, d], got {tuple(x.shape)}")
-    T, k, E = _moe_route_ok(route, who, x.device)
+    T, k, E = p.route_ok(route, who, x.device)
     if x.shape[0] != T:
         raise ValueError(f"{who}: x has {x.shape[0]} rows, the route {T} tokens")
     glu = a == _lib.ACT_SWIGLU
-    if scales is None and glu != (w_gate is not None):
-        raise ValueError("SwiGLU activation requires gate weights" if glu else f"{who}: w_gate belongs to act='swiglu'")
-    if scales is not None and (glu != (w_gate is not None) or glu != (scales[1] is not None)):
-        raise ValueError("SwiGLU activation requires gate weights and their scales" if glu
-                         else f"{who}: w8_gate and s_gate belong to act='swiglu'")
-    w = weight(w_up, E, x.dtype, pre + "up", who)
+    if glu != (w_gate is not None) or (p.scaled and glu != (s_gate is not None)):
+        if glu:
+            raise ValueError("SwiGLU activation requires gate weights" + (" and their scales" if p.scaled else ""))
+        raise ValueError(f"{who}: {pre}gate {'and s_gate belong' if p.scaled else 'belongs'} to act='swiglu'")
+    w = _moe_weight(p, w_up, E, x.dtype, pre + "up", who)
     I, d = w.shape[1:]
     if x.shape[1] != d:
         raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match input features {x.shape[1]}")
-    s = () if scales is None else (_moe_scale_w8(scales[0], E, I, "s_up", who), None)
-    g = None
+    su = (_moe_scale_w8(s_up, E, I, "s_up", who),) if p.scaled else ()
+    g, sg = None, (None,) if p.scaled else ()
     if glu:
         if w_gate.shape != w_up.shape:
             raise ValueError(f"{who}: {pre}gate must have {pre}up's shape")
-        g = weight(w_gate, E, x.dtype, pre + "gate", who, like=w)
+        g = _moe_weight(p, w_gate, E, x.dtype, pre + "gate", who, like=w)
         if g.stride() != w.stride():
             w = w.contiguous()
-        if s:
-            s = (s[0], _moe_scale_w8(scales[1], E, I, "s_gate", who))
+        if p.scaled:
+            sg = (_moe_scale_w8(s_gate, E, I, "s_gate", who),)
     bu = _moe_bias(b_up, E, I, x.dtype, "b_up", who)
     bg = _moe_bias(b_gate, E, I, x.dtype, "b_gate", who) if glu else None
     x2 = _rows16(x)
     if out is None:
-        out = torch.empty(T * k, _pad8(I), dtype=x.dtype, device=x.device)[:, :I]
-    elif tuple(out.shape) != (T * k, I) or out.dtype != x.dtype or (I > 1 and out.stride(1) != 1) or out.stride(0) % 8:
-        raise ValueError(f"{who}: out must be [{T * k}, {I}] {x.dtype} with a row stride that is a multiple of 8")
+        out = empty_rows8(T * k, I, x.dtype, x.device)
+    else:
+        _moe_out_ok(who, out, T * k, I, x.dtype)
     if T == 0:
         return out
-    nbytes = workspace_bytes(T, k, E, I, d, a)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
-    # (the scaled entry point takes each weight's scales behind the weight)
-    check(entry(x2.data_ptr(), w.data_ptr(), *map(_ptr, s[:1]), _ptr(bu), _ptr(g), *map(_ptr, s[1:]), _ptr(bg),
-                route.expert_offsets.data_ptr(), route.sorted_rows.data_ptr(), out.data_ptr(), _ptr(ws), T, k, E, I, d, _ld(x2, d),
-                w.stride(1), w.stride(0), _ld(out, I), a, dt, _stream()))
+    ws, takes_ws = None, p.up_workspace_bytes is not None
+    if takes_ws:
+        nbytes = p.up_workspace_bytes(T, k, E, I, d, a)
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    # (a scaled entry point takes each weight's scales behind the weight, a tiled one the tile map behind the route's arrays)
+    check(p.up_entry(x2.data_ptr(), w.data_ptr(), *map(_ptr, su), _ptr(bu), _ptr(g), *map(_ptr, sg), _ptr(bg),
+                     route.expert_offsets.data_ptr(), route.sorted_rows.data_ptr(), *(_moe_tile_ptrs(route) if p.tiled else ()),
+                     out.data_ptr(), *((_ptr(ws),) if takes_ws else ()), T, k, E, I, d, _ld(x2, d), w.stride(1), w.stride(0), _ld(out, I), a, dt, _stream()))
     return out
 
 
@@ -2203,40 +2318,46 @@ def moe_down(h, route: MoERoute, w_down, b_down=None, residual=None, out=None):
     """The grouped down projection and the combine (mio_moe_down): h [T k, I] by sorted position (moe_up's output), w_down
     [E, d, I] -> y [T, d] = sum_j weights[t, j] (h[row_pos[t k + j]] w_down[e]^T + b_down[e]) (+ residual[t]), e = ids[t, j]: the
     slots summed in fp32 in slot order and rounded once.  residual [T, d] is also where a shared expert's output goes in."""
-    return _moe_down_core("moe_down", lib.mio_moe_down, lib.mio_moe_down_workspace_bytes, _moe_weight, "w_down", h, route, w_down,
-                          b_down, residual, out)
+    return _moe_down_core(_MOE_DECODE, h, route, w_down, b_down, residual, out)
 
 
-def _moe_down_core(who, entry, workspace_bytes, weight, wname, h, route, w_down, b_down, residual, out, scales=None):
-    """moe_down and moe_down_w8: the route and shape checks, bias and residual preparation, out validation, the workspace and the
-    call of `entry`.  weight validates the stacked weight named wname; scales is (s_down,) of a form whose weights carry scales."""
+def _moe_down_core(p: _MoEPath, h, route, w_down, b_down, residual, out, s_down=None, workspace=None):
+    """moe_down, moe_down_w8 and moe_down_prefill: the route and shape checks, weight, scale, bias and residual preparation, out
+    validation, the workspace (the caller's where the op offers that, checked) and the call of p.down_entry.  s_down: the scales
+    of a path whose weights carry them."""
+    who = p.down_op
     _need_cuda(h)
     dt = _dtype_id(h)
-    T, k, E = _moe_route_ok(route, who, h.device)
+    T, k, E = p.route_ok(route, who, h.device)
     if h.dim() != 2 or h.shape[0] != T * k:
         raise ValueError(f"{who}: h must be [T k = {T * k}, I], got {tuple(h.shape)}")
-    w = weight(w_down, E, h.dtype, wname, who)
+    w = _moe_weight(p, w_down, E, h.dtype, p.pre + "down", who)
     d, I = w.shape[1:]
     if h.shape[1] != I:
         raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match h's {h.shape[1]} features")
-    s = () if scales is None else (_moe_scale_w8(scales[0], E, d, "s_down", who),)
+    s = (_moe_scale_w8(s_down, E, d, "s_down", who),) if p.scaled else ()
     bd = _moe_bias(b_down, E, d, h.dtype, "b_down", who)
     h2 = _rows16(h)
     _res_ok(residual, T * d, h.dtype)
     r2 = None if residual is None else _rows16(residual.reshape(T, d))
     if r2 is not None and T > 1 and r2.stride(0) % 8:  # (d % 8 != 0, contiguous: rows at the stride the kernel's loads are laid out for)
-        r2 = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d].copy_(r2)
+        r2 = empty_rows8(T, d, h.dtype, h.device).copy_(r2)
     if out is None:
-        out = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d]
-    elif tuple(out.shape) != (T, d) or out.dtype != h.dtype or (d > 1 and out.stride(1) != 1) or out.stride(0) % 8:
-        raise ValueError(f"{who}: out must be [{T}, {d}] {h.dtype} with a row stride that is a multiple of 8")
+        out = empty_rows8(T, d, h.dtype, h.device)
+    else:
+        _moe_out_ok(who, out, T, d, h.dtype)
     if T == 0:
         return out
-    nbytes = workspace_bytes(T, k, E, d, I)
-    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=h.device)
-    check(entry(h2.data_ptr(), w.data_ptr(), *map(_ptr, s), _ptr(bd), route.ids.data_ptr(), route.weights.data_ptr(),
-                route.expert_offsets.data_ptr(), route.row_pos.data_ptr(), _ptr(r2), out.data_ptr(), ws.data_ptr(), T, k, E, d, I,
-                _ld(h2, I), w.stride(1), w.stride(0), _ld(out, d), 0 if r2 is None else _ld(r2, d), dt, _stream()))
+    need = p.down_workspace_bytes(T, k, E, d, I) // 4
+    if workspace is None:
+        workspace = torch.empty(max(need, 4), dtype=torch.float32, device=h.device)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.device != h.device or workspace.dtype != torch.float32
+          or not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 16):
+        raise ValueError(f"{who}: workspace must be a contiguous, 16-byte aligned fp32 tensor of at least {need} elements on h's device")
+    check(p.down_entry(h2.data_ptr(), w.data_ptr(), *map(_ptr, s), _ptr(bd), route.ids.data_ptr(), route.weights.data_ptr(),
+                       route.expert_offsets.data_ptr(), route.row_pos.data_ptr(), *(_moe_tile_ptrs(route) if p.tiled else ()), _ptr(r2),
+                       out.data_ptr(), workspace.data_ptr(), T, k, E, d, I, _ld(h2, I), w.stride(1), w.stride(0), _ld(out, d),
+                       0 if r2 is None else _ld(r2, d), dt, _stream()))
     return out
 
 
@@ -2284,16 +2405,14 @@ def moe_up_w8(x, route: MoERoute, w8_up, s_up, act: str = "swiglu", w8_gate=None
     torch.float8_e4m3fn with d % 16 == 0, s_up / s_gate fp32 [E, I] (quantize_expert_weights_w8 makes both) -> h [T k, I] by sorted
     position: row p is act(s_up[e] * (x[t] w8_up[e]^T) + b_up[e]) (swiglu: silu of the gate's, times that).  Weights whose strides
     are multiples of 16 bytes go to the launch as they are.  Nothing synchronises with the host."""
-    return _moe_up_core("moe_up_w8", lib.mio_moe_up_w8, lib.mio_moe_up_w8_workspace_bytes, _moe_weight_w8, "w8_", x, route, w8_up, act,
-                        w8_gate, b_up, b_gate, out, scales=(s_up, s_gate))
+    return _moe_up_core(_MOE_DECODE_W8, x, route, w8_up, act, w8_gate, b_up, b_gate, out, s_up, s_gate)
 
 
 def moe_down_w8(h, route: MoERoute, w8_down, s_down, b_down=None, residual=None, out=None):
     """moe_down on weight-only FP8 expert weights (mio_moe_down_w8): h [T k, I] by sorted position, w8_down [E, d, I]
     torch.float8_e4m3fn with I % 16 == 0, s_down fp32 [E, d] -> y [T, d] = sum_j weights[t, j] (s_down[e] * (h[row_pos[t k + j]]
     w8_down[e]^T) + b_down[e]) (+ residual[t]), e = ids[t, j]: the slots in slot order, rounded once."""
-    return _moe_down_core("moe_down_w8", lib.mio_moe_down_w8, lib.mio_moe_down_w8_workspace_bytes, _moe_weight_w8, "w8_down", h, route,
-                          w8_down, b_down, residual, out, scales=(s_down,))
+    return _moe_down_core(_MOE_DECODE_W8, h, route, w8_down, b_down, residual, out, s_down)
 
 
 def moe_mlp_w8(x, route: MoERoute, w8_up, s_up, w8_down, s_down, act: str = "swiglu", w8_gate=None, s_gate=None, b_up=None,
@@ -2304,182 +2423,28 @@ def moe_mlp_w8(x, route: MoERoute, w8_up, s_up, w8_down, s_down, act: str = "swi
                        out)
 
 
-# ------------------------------------------------------------------------------------------------
-# mixture-of-experts MLP for tall inputs (prefill): router in three launches, tiled grouped GEMMs over a device-built tile map
-# ------------------------------------------------------------------------------------------------
-MOE_PREFILL_MAX_TOKENS = 8192
-
-
-class MoEPrefillRoute(NamedTuple):
-    """What moe_route_prefill decides: MoERoute's fields under the same names with the same definitions, and the tile map of the
-    grouped GEMMs (semantics: include/mio_hip.h): tile_expert int32 [max_tiles], tile_row0 int32 [max_tiles], num_tiles int32
-    [1], max_tiles = moe_prefill_max_tiles(T, top_k, E); entries past num_tiles are not written."""
-    ids: torch.Tensor
-    weights: torch.Tensor
-    expert_offsets: torch.Tensor
-    sorted_rows: torch.Tensor
-    row_pos: torch.Tensor
-    top_k: int
-    num_experts: int
-    tile_expert: torch.Tensor
-    tile_row0: torch.Tensor
-    num_tiles: torch.Tensor
-
-
-def moe_prefill_max_tiles(T: int, top_k: int, E: int) -> int:
-    """The bound on the tile map, floor(T k / 128) + min(E, T k).  Host-only; ValueError where the launches would refuse the shape."""
-    n = lib.mio_moe_prefill_max_tiles(T, top_k, E)
-    if n < 0:
-        raise ValueError(lib.mio_last_error().decode("utf-8", "replace"))
-    return n
-
-
-def _moe_prefill_route_ok(route, who: str, device) -> Tuple[int, int, int]:
-    """(T, k, E) of a MoEPrefillRoute whose tensors are what the kernels take from raw pointers."""
-    if not isinstance(route, MoEPrefillRoute):
-        raise ValueError(f"{who}: route must be a MoEPrefillRoute (ops.moe_route_prefill)")
-    T, k, E = _moe_route_ok(MoERoute(*route[:7]), who, device)
-    if T > MOE_PREFILL_MAX_TOKENS:
-        raise ValueError(f"{who} takes at most {MOE_PREFILL_MAX_TOKENS} tokens, got {T}")
-    mt = moe_prefill_max_tiles(T, k, E)
-    for name, t, shape in (("tile_expert", route.tile_expert, (mt,)), ("tile_row0", route.tile_row0, (mt,)), ("num_tiles", route.num_tiles, (1,))):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
-            raise ValueError(f"{who}: route.{name} must be a tensor on the activations' device")
-        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"{who}: route.{name} must be a contiguous int32 tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
-    return T, k, E
-
-
+# ---- the same for tall inputs (mio_moe_prefill_route / _up / _down): router in three launches, tiled grouped GEMMs
+# over a device-built tile map --------------------------------------------------------------------------------------------------------
 def moe_route_prefill(router_logits, top_k: int, renormalize: bool = True, out: Optional[MoEPrefillRoute] = None) -> MoEPrefillRoute:
     """Route T <= 8192 tokens over E <= 256 experts (mio_moe_prefill_route, three launches): router_logits [T, E] (or [..., E],
     flattened; bf16, fp16 or fp32, last-dim stride 1) -> what moe_route gives per token, the routed rows grouped by expert, and the
     tile map moe_up_prefill / moe_down_prefill walk.  out: a MoEPrefillRoute of the same (T, top_k, E) to write into (a captured
     graph reuses its buffers).  T == 0 launches nothing and zeroes expert_offsets and num_tiles.  Nothing is read back."""
-    who = "moe_route_prefill"
-    if not isinstance(router_logits, torch.Tensor):
-        raise ValueError(f"{who}: router_logits must be a tensor")
-    _need_cuda(router_logits)
-    if router_logits.dtype not in _SAMPLE_DTYPES:
-        raise ValueError(f"{who}: router_logits must be bf16, fp16 or fp32, got {router_logits.dtype}")
-    if router_logits.dim() < 1:
-        raise ValueError(f"{who}: router_logits must be [..., E]")
-    E = router_logits.shape[-1]
-    k = operator.index(top_k)
-    if not 1 <= E <= MOE_MAX_EXPERTS:
-        raise ValueError(f"{who}: 1 .. {MOE_MAX_EXPERTS} experts, got {E}")
-    if not 1 <= k <= min(E, MOE_MAX_TOP_K):
-        raise ValueError(f"{who}: top_k must be in [1, min(E, {MOE_MAX_TOP_K})], got {k}")
-    x = router_logits if router_logits.dim() == 2 else router_logits.reshape(-1, E)
-    if x.stride(-1) != 1 and E > 1:
-        x = x.contiguous()
-    T = x.shape[0]
-    if T > MOE_PREFILL_MAX_TOKENS:
-        raise ValueError(f"{who} takes at most {MOE_PREFILL_MAX_TOKENS} tokens, got {T}")
-    ld = x.stride(0) if T > 1 else E
-    if ld < E or x.data_ptr() % 16:
-        x, ld = x.contiguous(), E
-        if x.data_ptr() % 16:  # (already contiguous at a storage offset off 16 bytes: contiguous() returned it as it was)
-            x = x.clone()
-    dev = x.device
-    if out is None:
-        i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)  # noqa: E731
-        mt = moe_prefill_max_tiles(T, k, E)
-        out = MoEPrefillRoute(i32(T, k), torch.empty(T, k, dtype=torch.float32, device=dev), i32(E + 1), i32(T * k), i32(T * k), k, E,
-                              i32(mt), i32(mt), i32(1))
-    elif _moe_prefill_route_ok(out, who, dev) != (T, k, E):
-        raise ValueError(f"{who}: out was made for another (T, top_k, E)")
-    if T == 0:
-        out.expert_offsets.zero_()
-        out.num_tiles.zero_()
-    else:
-        check(lib.mio_moe_prefill_route(x.data_ptr(), ld, out.ids.data_ptr(), out.weights.data_ptr(), out.expert_offsets.data_ptr(),
-                                        out.sorted_rows.data_ptr(), out.row_pos.data_ptr(), out.tile_expert.data_ptr(),
-                                        out.tile_row0.data_ptr(), out.num_tiles.data_ptr(), T, E, k, 1 if renormalize else 0,
-                                        _SAMPLE_DTYPES[x.dtype], _stream()))
-    return out
+    return _moe_route_core(_MOE_PREFILL, router_logits, top_k, renormalize, out)
 
 
 def moe_up_prefill(x, route: MoEPrefillRoute, w_up, act: str = "swiglu", w_gate=None, b_up=None, b_gate=None, out=None):
     """moe_up for a tall input (mio_moe_prefill_up): x [T, d], w_up (and w_gate for swiglu) [E, I, d] -> h [T k, I] by sorted
     position, one launch of 128 x 128 x 64 tiles (swiglu: 128 x 64 up and gate columns) over the route's tile map; a weight tile is
     read once per 128 rows of its expert.  out: h to write into, [T k, I], row stride a multiple of 8."""
-    who = "moe_up_prefill"
-    _need_cuda(x)
-    a = _moe_act(act)
-    dt = _dtype_id(x)
-    if x.dim() != 2:
-        raise ValueError(f"{who}: x must be [T, d], got {tuple(x.shape)}")
-    T, k, E = _moe_prefill_route_ok(route, who, x.device)
-    if x.shape[0] != T:
-        raise ValueError(f"{who}: x has {x.shape[0]} rows, the route {T} tokens")
-    glu = a == _lib.ACT_SWIGLU
-    if glu != (w_gate is not None):
-        raise ValueError("SwiGLU activation requires gate weights" if glu else f"{who}: w_gate belongs to act='swiglu'")
-    w = _moe_weight(w_up, E, x.dtype, "w_up", who)
-    I, d = w.shape[1:]
-    if x.shape[1] != d:
-        raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match input features {x.shape[1]}")
-    g = None
-    if glu:
-        if w_gate.shape != w_up.shape:
-            raise ValueError(f"{who}: w_gate must have w_up's shape")
-        g = _moe_weight(w_gate, E, x.dtype, "w_gate", who, like=w)
-        if g.stride() != w.stride():
-            w = w.contiguous()
-    bu = _moe_bias(b_up, E, I, x.dtype, "b_up", who)
-    bg = _moe_bias(b_gate, E, I, x.dtype, "b_gate", who) if glu else None
-    x2 = _rows16(x)
-    if out is None:
-        out = torch.empty(T * k, _pad8(I), dtype=x.dtype, device=x.device)[:, :I]
-    elif tuple(out.shape) != (T * k, I) or out.dtype != x.dtype or (I > 1 and out.stride(1) != 1) or out.stride(0) % 8:
-        raise ValueError(f"{who}: out must be [{T * k}, {I}] {x.dtype} with a row stride that is a multiple of 8")
-    if T == 0:
-        return out
-    check(lib.mio_moe_prefill_up(x2.data_ptr(), w.data_ptr(), _ptr(bu), _ptr(g), _ptr(bg), route.expert_offsets.data_ptr(),
-                                 route.sorted_rows.data_ptr(), route.tile_expert.data_ptr(), route.tile_row0.data_ptr(),
-                                 route.num_tiles.data_ptr(), out.data_ptr(), T, k, E, I, d, _ld(x2, d), w.stride(1), w.stride(0),
-                                 _ld(out, I), a, dt, _stream()))
-    return out
+    return _moe_up_core(_MOE_PREFILL, x, route, w_up, act, w_gate, b_up, b_gate, out)
 
 
 def moe_down_prefill(h, route: MoEPrefillRoute, w_down, b_down=None, residual=None, out=None, workspace=None):
     """moe_down for a tall input (mio_moe_prefill_down): h [T k, I] by sorted position, w_down [E, d, I] -> y [T, d] as moe_down
     states it; the tiled grouped GEMM writes fp32 rows by sorted position, a second launch sums a token's slots in slot order
     and rounds once.  workspace: an fp32 tensor of at least T k d elements to use in place of one from torch's allocator."""
-    who = "moe_down_prefill"
-    _need_cuda(h)
-    dt = _dtype_id(h)
-    T, k, E = _moe_prefill_route_ok(route, who, h.device)
-    if h.dim() != 2 or h.shape[0] != T * k:
-        raise ValueError(f"{who}: h must be [T k = {T * k}, I], got {tuple(h.shape)}")
-    w = _moe_weight(w_down, E, h.dtype, "w_down", who)
-    d, I = w.shape[1:]
-    if h.shape[1] != I:
-        raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match h's {h.shape[1]} features")
-    bd = _moe_bias(b_down, E, d, h.dtype, "b_down", who)
-    h2 = _rows16(h)
-    _res_ok(residual, T * d, h.dtype)
-    r2 = None if residual is None else _rows16(residual.reshape(T, d))
-    if r2 is not None and T > 1 and r2.stride(0) % 8:  # (d % 8 != 0, contiguous: rows at the stride the kernel's loads are laid out for)
-        r2 = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d].copy_(r2)
-    if out is None:
-        out = torch.empty(T, _pad8(d), dtype=h.dtype, device=h.device)[:, :d]
-    elif tuple(out.shape) != (T, d) or out.dtype != h.dtype or (d > 1 and out.stride(1) != 1) or out.stride(0) % 8:
-        raise ValueError(f"{who}: out must be [{T}, {d}] {h.dtype} with a row stride that is a multiple of 8")
-    if T == 0:
-        return out
-    need = lib.mio_moe_prefill_down_workspace_bytes(T, k, E, d, I) // 4
-    if workspace is None:
-        workspace = torch.empty(max(need, 4), dtype=torch.float32, device=h.device)
-    elif (not isinstance(workspace, torch.Tensor) or workspace.device != h.device or workspace.dtype != torch.float32
-          or not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 16):
-        raise ValueError(f"{who}: workspace must be a contiguous, 16-byte aligned fp32 tensor of at least {need} elements on h's device")
-    check(lib.mio_moe_prefill_down(h2.data_ptr(), w.data_ptr(), _ptr(bd), route.ids.data_ptr(), route.weights.data_ptr(),
-                                   route.expert_offsets.data_ptr(), route.row_pos.data_ptr(), route.tile_expert.data_ptr(),
-                                   route.tile_row0.data_ptr(), route.num_tiles.data_ptr(), _ptr(r2), out.data_ptr(),
-                                   workspace.data_ptr(), T, k, E, d, I, _ld(h2, I), w.stride(1), w.stride(0), _ld(out, d),
-                                   0 if r2 is None else _ld(r2, d), dt, _stream()))
-    return out
+    return _moe_down_core(_MOE_PREFILL, h, route, w_down, b_down, residual, out, workspace=workspace)
 
 
 def moe_mlp_prefill(x, route: MoEPrefillRoute, w_up, w_down, act: str = "swiglu", w_gate=None, b_up=None, b_gate=None, b_down=None,

@@ -2,12 +2,17 @@
 MoEMLP with MoEConfig(grouped_prefill=True)) against the fp64 restatement of tests/_moe_check.py, stage by stage from the bytes
 each launch read, under the bounds and bars the decode path is judged by.  Shapes sit at the seams of the 128 x 128 x 64 tile
 (SwiGLU: 64 up columns and their gate columns): partial and full row tiles, an idle expert, a K tail below one chunk and three
-chunks plus a tail, ragged and exact column tiles."""
+chunks plus a tail, ragged and exact column tiles.
+
+The last two sections hold the three paths (decode on 16-bit experts, decode on FP8 experts, prefill) to what their shared route,
+up and down cores promise: refusals under the name of the op that was called, every copy the cores make on the way to a launch,
+and MoEMLP's one chunk loop at its seams, bit for bit."""
 import pytest
 import torch
 
 import _moe_cases as cs
 import _moe_check as mc
+import test_gpu_moe_w8 as w8t  # (the FP8 path's weights and fp64 references)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -236,3 +241,194 @@ def test_refusals():
     assert tuple(y.shape) == (0, 8)
     with pytest.raises(ValueError, match="decode steps only"):
         ops.moe_route(torch.zeros(65, 8, device=DEV), 2)
+
+
+# ---- the three paths through the one route, up and down core -------------------------------------------------------------------------
+# path -> (route op, up op, down op, the route op of the other class)
+PATHS = {"decode": ("moe_route", "moe_up", "moe_down", "moe_route_prefill"),
+         "decode_w8": ("moe_route", "moe_up_w8", "moe_down_w8", "moe_route_prefill"),
+         "prefill": ("moe_route_prefill", "moe_up_prefill", "moe_down_prefill", "moe_route")}
+
+
+def _weight(path, E, N, K, dtype, seed, strided=True):
+    """A stacked weight as the path's ops take it: (w,) 16-bit, (w8, scale) on the FP8 path; strided: rows 16 wider, a spare row."""
+    if path == "decode_w8":
+        q, s = w8t._quant(E, N, K, dtype, seed)
+        return (q if strided else q.contiguous(), s)
+    w = _rand((E, N, K), dtype, K ** -0.5, seed)
+    return (_strided(w, (E, N + 1, K + 16)) if strided else w,)
+
+
+def _up(path, x, route, w, act, g=None, **kw):
+    """The path's up op on w (and the gate g), each as _weight made it."""
+    if path == "decode_w8":
+        return _ops().moe_up_w8(x, route, *w, act, *(g or (None, None)), **kw)
+    return getattr(_ops(), PATHS[path][1])(x, route, *w, act, *(g or (None,)), **kw)
+
+
+def _down(path, h, route, w, **kw):
+    return getattr(_ops(), PATHS[path][2])(h, route, *w, **kw)
+
+
+def _judge_up(path, h, x, route, w, act, g, dtype, what):
+    if path == "decode_w8":
+        w8t.w8c.judge(h, w8t._up_ref(x, route, *w, act, *(g or (None, None))), dtype, what)
+    else:
+        mc.check_up(h, mc.up_reference(x, route, *w, act, *(g or (None,)), device=DEV), dtype, what)
+
+
+def _judge_down(path, y, h, route, w, res, dtype, what):
+    eff = w8t._eff(*w) if path == "decode_w8" else w[0]
+    mc.check_down(y, mc.down_reference(h, route, eff, None, res, device=DEV), dtype, what)
+
+
+@pytest.mark.parametrize("path", sorted(PATHS))
+def test_refusals_name_their_op(path):
+    """T 3, E 4, k 2, d 16, I 16.  What the one core refuses it refuses under the name of the public op that was called, as a
+    ValueError: the ops layer's own, raised before the entry point is called (whose refusal would be a RuntimeError).  The two
+    SwiGLU messages carry no op name, as before."""
+    ops = _ops()
+    route_op, up_op, down_op, other_route_op = PATHS[path]
+    T, E, k, d, I, dtype = 3, 4, 2, 16, 16, torch.bfloat16
+    w8 = path == "decode_w8"
+    logits = _permuted_logits(T, E, torch.float32, 1)
+    route, other = getattr(ops, route_op)(logits, k), getattr(ops, other_route_op)(logits, k)
+    kind = type(route).__name__
+    x, h = _rand((T, d), dtype, seed=1), _rand((T * k, I), dtype, seed=2)
+    wu, wg, wd = (_weight(path, E, *s, dtype, i) for i, s in enumerate([(I, d), (I, d), (d, I)]))
+    gate = "w8_gate and s_gate belong" if w8 else "w_gate belongs"
+    up_name, down_name = ("w8_up", "w8_down") if w8 else ("w_up", "w_down")
+    wrong = (lambda w: (_rand(w[0].shape, dtype, seed=9), *w[1:])) if w8 else (lambda w: (w[0].to(torch.float16),))
+    dtype_text = "must be torch.float8_e4m3fn" if w8 else "must have the activation dtype"
+    nan_rows = lambda rows, n: torch.full((rows, n), NAN, dtype=dtype, device=DEV)  # noqa: E731
+    refused = [
+        (rf"^{up_op}: route must be a {kind} ", lambda: _up(path, x, other, wu, "swiglu", wg)),
+        (rf"^{down_op}: route must be a {kind} ", lambda: _down(path, h, other, wd)),
+        (rf"^{up_op}: x has 4 rows, the route 3 tokens", lambda: _up(path, _rand((T + 1, d), dtype), route, wu, "swiglu", wg)),
+        (rf"^{down_op}: h must be \[T k = 6, I\]", lambda: _down(path, h[:5], route, wd)),
+        (rf"^{up_op}: {gate} to act='swiglu'$", lambda: _up(path, x, route, wu, "gelu", wg)),
+        (r"^SwiGLU activation requires gate weights" + (" and their scales$" if w8 else "$"), lambda: _up(path, x, route, wu, "swiglu")),
+        (rf"^{up_op}: {up_name} {dtype_text}", lambda: _up(path, x, route, wrong(wu), "gelu")),
+        (rf"^{down_op}: {down_name} {dtype_text}", lambda: _down(path, h, route, wrong(wd))),
+        (rf"^{up_op}: out must be \[6, 16\] ", lambda: _up(path, x, route, wu, "gelu", out=nan_rows(T * k + 1, I))),
+        (rf"^{up_op}: out must be \[6, 16\] .* multiple of 8", lambda: _up(path, x, route, wu, "gelu", out=nan_rows(T * k, I + 4)[:, :I])),
+        (rf"^{down_op}: out must be \[3, 16\] ", lambda: _down(path, h, route, wd, out=nan_rows(T, d + 8))),
+        (rf"^{down_op}: out must be \[3, 16\] .* multiple of 8", lambda: _down(path, h, route, wd, out=nan_rows(T, d + 4)[:, :d])),
+    ]
+    if w8:  # the scaled form also refuses a gate without its scales, and the reverse
+        refused += [(r"^SwiGLU activation requires gate weights and their scales$", lambda: _up(path, x, route, wu, "swiglu", (wg[0], None))),
+                    (rf"^{up_op}: {gate} to act='swiglu'$", lambda: _up(path, x, route, wu, "gelu", (None, wg[1])))]
+    out = nan_rows(T, d)
+    if path == "prefill":
+        need = ops.lib.mio_moe_prefill_down_workspace_bytes(T, k, E, d, I) // 4
+        assert need >= T * k * d
+        ws = torch.zeros(need + 4, device=DEV)
+        text = rf"^{down_op}: workspace must be a contiguous, 16-byte aligned fp32 tensor of at least {need} elements"
+        refused += [(text, lambda: _down(path, h, route, wd, out=out, workspace=ws[:need - 1])),
+                    (text, lambda: _down(path, h, route, wd, out=out, workspace=ws[1:need + 1]))]
+    for text, call in refused:
+        with pytest.raises(ValueError, match=text):
+            call()
+    assert bool(torch.isnan(out).all())  # (nothing was written behind a refusal)
+    _down(path, h, route, wd, out=out)   # and the same call, unrefused, writes it
+    assert bool(torch.isfinite(out).all())
+
+
+@pytest.mark.parametrize("route_op", ["moe_route", "moe_route_prefill"])
+def test_route_fixups(route_op):
+    """Logits the launch cannot take as they are, each judged against the reference routing of the values handed in: contiguous at
+    a storage offset of one element (contiguous() returns them as they are: cloned), rows 24 apart at such an offset (copied), one
+    row expanded to T (row stride 0 < E: copied), a single row out of a strided buffer (its stride is not consulted), no row."""
+    route = getattr(_ops(), route_op)
+    T, E, k = 5, 8, 2
+    base = _permuted_logits(T, E, torch.float32, 3)
+    off = torch.zeros(T * E + 1, device=DEV)[1:].view(T, E).copy_(base)
+    wide = torch.full((T * (E + 24) + 1,), NAN, device=DEV)[1:].view(T, E + 24)[:, :E].copy_(base)
+    row = base[2:3].expand(T, E)
+    one = base[4:5]
+    assert off.is_contiguous() and off.data_ptr() % 16 == 4 and wide.data_ptr() % 16 == 4 and wide.stride(0) == E + 24
+    assert row.stride(0) == 0 and one.stride(0) == E + 24 and one.data_ptr() % 16 == 0
+    for what, logits in (("offset", off), ("offset, wide rows", wide), ("expanded", row), ("one row", one)):
+        got = route(logits, k)
+        mc.check_route(mc.route_reference(logits, k, True), *got[:5], what=f"{route_op} {what}")
+    empty = route(base[:0], k)
+    assert tuple(empty.ids.shape) == (0, k) and not bool(empty.expert_offsets.any())
+
+
+@pytest.mark.parametrize("path", sorted(PATHS))
+def test_up_down_fixups(path):
+    """Operands that take each copy the cores make, judged by the checkers against fp64, at E 4, k 2, K 16, N 20: a gate that is
+    contiguous under an up weight with padded rows (up is then copied too: one pair of strides goes to the launch); a contiguous
+    residual of 20 columns (T 3: copied to rows 24 apart; T 1: taken as it is, at the single-row stride); h and y of one row; T 0."""
+    ops = _ops()
+    E, k, K, N, dtype = 4, 2, 16, 20, torch.bfloat16
+    wu, wg, wd = _weight(path, E, N, K, dtype, 1), _weight(path, E, N, K, dtype, 2, strided=False), _weight(path, E, N, K, dtype, 3)
+    assert wu[0].stride() != wg[0].stride() and wg[0].is_contiguous()
+    for T in (3, 1, 0):
+        kk = 1 if T == 1 else k
+        route = getattr(ops, PATHS[path][0])(_permuted_logits(T, E, torch.float32, 5), kk)
+        x, h, res = _rand((T, K), dtype, seed=6), _rand((T * kk, K), dtype, seed=7), _rand((T, N), dtype, seed=8)
+        assert res.is_contiguous()
+        hu = _up(path, x, route, wu, "swiglu", wg)
+        y = _down(path, h, route, wd, residual=res)
+        assert tuple(hu.shape) == (T * kk, N) and tuple(y.shape) == (T, N)
+        if T:
+            assert hu.stride(0) == 24 and y.stride(0) == 24
+            _judge_up(path, hu, x, route, wu, "swiglu", wg, dtype, f"{path} up T {T}")
+            _judge_down(path, y, h, route, wd, res, dtype, f"{path} down T {T}")
+
+
+# ---- the module's one chunk loop -------------------------------------------------------------------------------------------------------
+def _module(**config):
+    from mio.kernels.mlp import MoEConfig, MoEMLP
+    torch.manual_seed(4)
+    m = MoEMLP(32, 48, 4, 2, MoEConfig(**config)).to(DEV)
+    with torch.no_grad():
+        m.router.weight.mul_(8.0)  # logits a few units apart
+    return m
+
+
+def _by_hand(m, x, res, bounds, path):
+    """The path's ops on the row ranges `bounds` of x, with the module's router logits and the weight copies it reads."""
+    ops, dt = _ops(), m.config.dtype
+    if path == "decode_w8":
+        up, down, gate = (m._cast.get_experts_w8(p, dt) for p in (m.w_up, m.w_down, m.w_gate))
+    else:
+        up, down, gate = ((p.detach().to(dt),) for p in (m.w_up, m.w_down, m.w_gate))
+    parts = []
+    for lo, hi in bounds:
+        route = getattr(ops, PATHS[path][0])(m._router_logits(x[lo:hi], dt), m.top_k, m.config.renormalize)
+        parts.append(_down(path, _up(path, x[lo:hi], route, up, "swiglu", gate), route, down, residual=res[lo:hi]))
+    return torch.cat(parts)
+
+
+@pytest.mark.parametrize("path", sorted(PATHS))
+def test_module_at_the_chunk_seam(path):
+    """E 4, k 2, d 32, I 48, bf16, a residual, T 70: forward is the path's ops on rows [0, 64) and [64, 70), bit for bit -- on the
+    prefill path one call on all 70 rows."""
+    m = _module(expert_weights_fp8=path == "decode_w8", grouped_prefill=path == "prefill")
+    x, res = _rand((70, 32), torch.bfloat16, seed=1), _rand((70, 32), torch.bfloat16, seed=2)
+    want = _by_hand(m, x, res, [(0, 70)] if path == "prefill" else [(0, 64), (64, 70)], path)
+    assert torch.equal(m(x, res).view(torch.int16), want.view(torch.int16))
+
+
+def test_module_prefill_tail_stays_on_the_prefill_ops(monkeypatch):
+    """T 8200 under grouped_prefill: rows [0, 8192) and the 8-row tail [8192, 8200) both go through the prefill ops (the path is
+    chosen on the whole T), and forward is those two calls, bit for bit."""
+    ops = _ops()
+    m = _module(grouped_prefill=True)
+    x, res = _rand((8200, 32), torch.bfloat16, seed=1), _rand((8200, 32), torch.bfloat16, seed=2)
+    want = _by_hand(m, x, res, [(0, 8192), (8192, 8200)], "prefill")
+    routed = []
+
+    def noting(name, op):
+        def route(logits, *args, **kwargs):
+            routed.append((name, logits.shape[0]))
+            return op(logits, *args, **kwargs)
+        return route
+
+    for name in ("moe_route", "moe_route_prefill"):
+        monkeypatch.setattr(ops, name, noting(name, getattr(ops, name)))
+    got = m(x, res)
+    assert routed == [("moe_route_prefill", 8192), ("moe_route_prefill", 8)]
+    assert torch.equal(got.view(torch.int16), want.view(torch.int16))
