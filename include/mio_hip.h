@@ -418,6 +418,55 @@ int mio_gemm_skinny_w8(const void* x, const void* w8, const float* w_scale, cons
                        int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int32_t act,
                        int32_t dtype, void* stream);
 
+/* The decode-step GEMM on MXFP4 weights: mio_gemm_skinny with the weight stored in the OCP microscaling FP4 form
+ * (csrc/gemm_skinny_w4.hip), the byte order of torch.float4_e2m1fn_x2 and of gpt-oss's *_blocks / *_scales:
+ *   w4       uint8, row-major [N, K / 2], ldw in BYTES: e2m1 elements (sign, 2 exponent bits, 1 mantissa bit: +-{0, 0.5, 1,
+ *            1.5, 2, 3, 4, 6}), element 2 i in the low nibble of byte i, element 2 i + 1 in the high nibble;
+ *   w_scale  uint8 e8m0, [N, K / 32], row stride lds in BYTES: byte b means 2^(b - 127), one per 32 consecutive k.
+ *   deq[n, k] = e2m1(w4[n, k]) * 2^(w_scale[n, k / 32] - 127)
+ *   y = act(x deq^T + bias[n]) (+ residual);  SwiGLU: silu(x deq_gate^T + bias_gate[n]) * (x deq^T + bias[n])
+ * The reference has no quantised weights: this storage form, the kernel and the quantiser below have no counterpart there.
+ * MXFP4 is how the weights are stored, not a compute precision: v_cvt_scalef32_pk_bf16_fp4 widens two nibbles to bf16 with the
+ * block scale applied in the conversion, the products run on the bf16 MFMA with fp32 accumulation, and the epilogue is
+ * mio_gemm_skinny's.  The scale byte: the widening is exact wherever 0.5 * 2^(b - 127) is a normal bf16 and 6 * 2^(b - 127) is
+ * finite, 2 <= b <= 252.  b = 255 is the format's NaN.  Outside that range the result is the conversion instruction's, observed
+ * once on an MI355X: b = 0 and b = 1 still give the exact products, as bf16 subnormals (0.5 * 2^-127 is 0x0020), which the MFMA
+ * carries through; b = 253 gives +-Inf for the nibbles +-4 and +-6, b = 254 for +-2, +-3, +-4, +-6, all other products exact;
+ * b = 255 gives NaN for every nibble, the zeros included.
+ * x, bias, residual and y are bf16 ONLY: MIO_FP16 is refused, because e2m1 * 2^e is exact in fp16 only inside a narrow
+ * exponent range.
+ *   1 <= M <= 64, any N >= 1, K % 32 == 0 (whole blocks; K % 128 in {0, 32, 64, 96} all served), ldw % 16 == 0 (bytes) and >=
+ *   K / 2, lds % 4 == 0 (bytes) and >= K / 32, ldx / ldy / ldr multiples of 8 elements, every pointer 16-byte aligned but the
+ *   scales', which are 4-byte aligned; bias / residual nullable; w4_gate and w_scale_gate together iff act == SWIGLU (the gate
+ *   shares ldw and lds).  Bytes [K / 32, lds) of a scale row may be loaded and reach no result; nothing outside rows n < N of
+ *   either operand is touched.  M == 0 or N == 0 returns 0 and launches nothing; K == 0 is an empty sum.
+ * K is cut into mio_gemm_skinny_w4_splits() slices of whole 128-k steps, each at least 32 M long (mio_gemm_skinny_w4_slice), so
+ * the fp32 partials stay at or under a quarter of the half-byte weight bytes; partials and workspace as mio_gemm_skinny
+ * (mio_gemm_skinny_w4_workspace_bytes), summed in slice order by the same second launch; bit-reproducible, graph-capturable.
+ * Inside a slice a workgroup walks chunks of mio_gemm_skinny_w4_chunk_k(act) k with a ring of mio_gemm_skinny_w4_depth(act)
+ * register sets (< 0 on an unknown activation).  mio_gemm_skinny_w4_ok only advises the module layer: 1 where the shape is
+ * legal AND the kernel measured at most 0.9 x the time of the faster of mio_gemm_skinny_w8 and mio_gemm_skinny on the same
+ * weight (profiles/skinny_gemm_w4.md); it admits nothing unmeasured.
+ * Refused (< 0, mio_last_error() names the entry point) before any launch: what mio_gemm_skinny_w8 refuses, with K % 32, ldw
+ * against K / 2, the lds rules above, and MIO_FP16.
+ * mio_weight_quant_mxfp4 is the one-time preparation of a bf16 / fp16 weight w [N, K] (ldw in elements, K % 32 == 0; ldw4 in
+ * bytes, a multiple of 16, >= K / 2; lds in bytes, >= K / 32), the OCP MX rule, per block of 32:
+ *   a = max |v| in fp32 (NaN elements ignored); e = clamp(floor(log2 a) - 2, -127, 127), e = 0 where a == 0; scale byte e + 127;
+ *   element = v * 2^-e rounded to nearest even on the e2m1 grid, saturating at +-6 (floor: the block maximum may saturate);
+ *   +-Inf gives +-6, NaN a signed zero. */
+int mio_weight_quant_mxfp4(const void* w, int64_t ldw, void* w4, int64_t ldw4, void* scale, int64_t lds, int32_t N, int32_t K,
+                           int32_t dtype, void* stream);
+size_t mio_gemm_skinny_w4_workspace_bytes(int64_t M, int32_t N, int32_t K, int32_t act);
+int mio_gemm_skinny_w4_splits(int64_t M, int32_t N, int32_t K, int32_t act);
+int mio_gemm_skinny_w4_slice(int64_t M, int32_t N, int32_t K, int32_t act, int32_t slice, int32_t* k_begin, int32_t* k_end);
+int mio_gemm_skinny_w4_chunk_k(int32_t act);
+int mio_gemm_skinny_w4_depth(int32_t act);
+int mio_gemm_skinny_w4_ok(int64_t M, int32_t N, int32_t K, int32_t act);
+int mio_gemm_skinny_w4(const void* x, const void* w4, const void* w_scale, const void* bias, const void* w4_gate,
+                       const void* w_scale_gate, const void* bias_gate, const void* residual, void* y, void* workspace,
+                       int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t lds, int64_t ldy, int64_t ldr,
+                       int32_t act, int32_t dtype, void* stream);
+
 /* The FP8 x FP8 GEMM for tall inputs (W8A8; csrc/gemm_f8.hip, plan csrc/gemm_f8_plan.h): both operands are OCP e4m3fn bytes
  * (torch.float8_e4m3fn) multiplied on v_mfma_f32_16x16x128_f8f6f4 with a plain fp32 accumulator, the scales in the read-out:
  *   z[m, n] = (x_scale[m] * w_scale[n]) * sum_k x8[m, k] w8[n, k] + bias[n]
@@ -963,6 +1012,47 @@ int mio_moe_down_w8(const void* h, const void* w8_down, const float* s_down, con
                     const int32_t* row_pos, const void* residual, void* y, void* workspace, int32_t T,
                     int32_t top_k, int32_t E, int32_t d, int32_t I, int64_t ldh, int64_t ldw,
                     int64_t expert_stride, int64_t ldy, int64_t ldr, int32_t dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The same two grouped GEMMs on MXFP4 expert weights (csrc/moe_w4.hip, csrc/moe_plan.h under the
+ * half-byte form).  The routing arrays are mio_moe_route's; shapes, limits, the
+ * meaning of h and y, the slot order, the ownership rules and the determinism are those stated for
+ * the 16-bit and FP8 entry points above.
+ *
+ * Weights.  The storage form of mio_gemm_skinny_w4, stacked: w4_up [E, I, d / 2], w4_gate the same
+ * (SwiGLU only), w4_down [E, d, I / 2]; ldw and expert_stride in BYTES, multiples of 16, ldw >= K /
+ * 2.  Block scales e8m0: s_up [E, I, d / 32], s_gate the same, s_down [E, d, I / 32]; row stride
+ * lds and scale_expert_stride in BYTES, multiples of 4, lds >= K / 32, base 4-byte aligned.  K (d
+ * for up, I for down) must be a multiple of 32.  x, h, the biases, the residual and y are bf16 only.
+ *
+ * Arithmetic.  deq_e[n, k] = e2m1 * 2^(scale byte - 127), applied in the conversion inside the K
+ * loop, exact in bf16 for scale bytes 2 .. 252; products on the bf16 MFMA with fp32 accumulation;
+ * the epilogues are the 16-bit entry points' on deq_e.  At E = 1, top_k = 1 both equal
+ * mio_gemm_skinny_w4 to the bit under the same split of K.  The weight bytes, the scale bytes and
+ * the biases of an expert with no routed row are never read.
+ *
+ * Plan.  mio_moe_{up,down}_w4_splits slices of whole 128-k steps, each at least 32 x the mean rows
+ * per aimed expert long; a pure function of the sizes.  Workspaces as for the 16-bit entry points,
+ * sized by mio_moe_{up,down}_w4_workspace_bytes.
+ * Refused (< 0, mio_last_error() names the entry point) before any launch: everything the FP8
+ * entry points refuse, with K a multiple of 32, ldw against K / 2, the scale stride rules above,
+ * and MIO_FP16.  T == 0 or N == 0 returns 0 and launches nothing; K == 0 is an empty sum.
+ * ------------------------------------------------------------------------------------------ */
+int mio_moe_up_w4_splits(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K, int32_t act);
+size_t mio_moe_up_w4_workspace_bytes(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K, int32_t act);
+int mio_moe_down_w4_splits(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K);
+size_t mio_moe_down_w4_workspace_bytes(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K);
+int mio_moe_up_w4(const void* x, const void* w4_up, const void* s_up, const void* b_up, const void* w4_gate,
+                  const void* s_gate, const void* b_gate, const int32_t* expert_offsets,
+                  const int32_t* sorted_rows, void* h, void* workspace, int32_t T, int32_t top_k, int32_t E,
+                  int32_t I, int32_t d, int64_t ldx, int64_t ldw, int64_t expert_stride, int64_t lds,
+                  int64_t scale_expert_stride, int64_t ldh, int32_t act, int32_t dtype, void* stream);
+int mio_moe_down_w4(const void* h, const void* w4_down, const void* s_down, const void* b_down,
+                    const int32_t* ids, const float* weights, const int32_t* expert_offsets,
+                    const int32_t* row_pos, const void* residual, void* y, void* workspace, int32_t T,
+                    int32_t top_k, int32_t E, int32_t d, int32_t I, int64_t ldh, int64_t ldw,
+                    int64_t expert_stride, int64_t lds, int64_t scale_expert_stride, int64_t ldy, int64_t ldr,
+                    int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Mixture-of-experts MLP for tall inputs (csrc/moe_prefill.hip, csrc/moe_prefill_plan.h; DESIGN

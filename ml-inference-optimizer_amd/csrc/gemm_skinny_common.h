@@ -63,6 +63,18 @@ struct SkinnyW8Tile {
   static_assert(PCS >= 16 && ROWS * PCS % 256 == 0 && SKC % SKINNY_W8_KSTEP == 0 && D >= 2, "chunk shape");
 };
 
+// The shape of the MXFP4 K loop (gemm_skinny_w4_head.inc, gemm_skinny_w4_loop.inc) at MF row fragments, from the form's values
+constexpr int SKINNY_W4_KSTEP = SKINNY_W4.kstep;
+template <int MF, bool GLU>
+struct SkinnyW4Tile {
+  static constexpr int SKC = SKINNY_W4.chunk(GLU);  // k per chunk
+  static constexpr int D = SKINNY_W4.sets(GLU);     // register sets in the ring
+  static constexpr int PCS = SKC / 8, ROWS = MF * 16, ROWB = SKC * 2;
+  static constexpr int XPT = ROWS * PCS / 256;  // 16-byte pieces of the x chunk per thread
+  // lane group q owns the 64 k at 64 q of a chunk: two MX blocks, two weight loads, one 2-byte scale load
+  static_assert(SKC == 256 && SKC % SKINNY_W4_KSTEP == 0 && ROWS * PCS % 256 == 0 && D >= 2, "chunk shape");
+};
+
 __device__ __forceinline__ float skinny_act(int act, float v) {
   switch (act) {
     case MIO_ACT_GELU_TANH: return gemm_act<MIO_ACT_GELU_TANH>(v);
@@ -206,42 +218,65 @@ static inline void skinny_launch(const SkinnyKernels& k, const SkinnyDev& p, con
   }
 }
 
-// A launch of either unit: every check, the plan, the empty call, the device arguments and the launches.  scale / scale_g are
-// the weights' per-column scales (null for a form without them); ldw counts in the unit the form's ldw_multiple does.
+// What a launch of any unit does in front of its kernels: every check, the plan and the device arguments.  scale / scale_g are
+// the weights' scales (fp32 per column, or e8m0 block bytes; null for a form without them); ldw counts in the unit the form's
+// ldw_multiple does.  Returns nonzero on a refusal; launch = false on an empty call, which launches nothing.
+static inline int skinny_prepare(const SkinnyForm& f, const void* x, const void* w, const void* scale, const void* bias,
+                                 const void* w_gate, const void* scale_g, const void* bias_gate, const void* residual, void* y,
+                                 void* workspace, int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr,
+                                 int32_t act, int32_t dtype, SkinnyDev& p, SkinnyPlan& pl, bool& launch) {
+#define SKINNY_CHECK(cond, text) MIO_CHECK(cond, std::string(f.name) + (text))
+  launch = false;
+  std::string err;
+  if (!skinny_shape_ok(f, f.name, M, N, K, act, err)) return mio_fail(err);
+  SKINNY_CHECK(dtype == MIO_BF16 || (dtype == MIO_FP16 && !f.block_scaled), f.dtype_text);
+  const bool glu = act == MIO_ACT_SWIGLU, has_scales = f.scaled || f.block_scaled;
+  SKINNY_CHECK(glu == (w_gate != nullptr) && (!has_scales || glu == (scale_g != nullptr)), f.gate_text);
+  SKINNY_CHECK(glu || bias_gate == nullptr, ": bias_gate belongs to act == SWIGLU");
+  SKINNY_CHECK(ldw % f.ldw_multiple == 0, f.ldw_multiple_text);
+  SKINNY_CHECK(ldw >= skinny_row_units(f, K), f.ldw_short_text);
+  SKINNY_CHECK(ldx % 8 == 0 && ldy % 8 == 0 && (!residual || ldr % 8 == 0), f.ld_multiple_text);
+  SKINNY_CHECK(ldx >= K && ldy >= N && (!residual || ldr >= N), ": row stride smaller than row length");
+  SKINNY_CHECK(w && (!has_scales || scale) && (M == 0 || (x && y)), f.null_text);
+  const auto scale_aligned = [&](const void* s) { return f.block_scaled ? (reinterpret_cast<uintptr_t>(s) & 3) == 0 : mio_aligned16(s); };
+  SKINNY_CHECK(mio_aligned16(x) && mio_aligned16(w) && mio_aligned16(y) && mio_aligned16(w_gate) && mio_aligned16(residual) &&
+                   mio_aligned16(bias) && mio_aligned16(bias_gate) && mio_aligned16(workspace) && scale_aligned(scale) &&
+                   scale_aligned(scale_g),
+               f.block_scaled ? ": pointers must be 16-byte aligned (the block scales: 4-byte)" : ": pointers must be 16-byte aligned");
+  pl = skinny_plan(f, M, N, K, act);
+  if (M == 0 || N == 0) return 0;
+  SKINNY_CHECK(pl.nsplit == 1 || workspace != nullptr, std::string(": workspace required (") + f.name + "_workspace_bytes) when the plan splits K");
+#undef SKINNY_CHECK
+  p.x = x; p.w = w; p.wg = w_gate; p.bias = bias; p.bias_g = bias_gate; p.res = residual; p.y = y;
+  p.ws = pl.nsplit > 1 ? (float*)workspace : nullptr;
+  // (block scales are the unit's own typed arguments: they go in inside its K loop and the epilogue reads none)
+  p.scale = f.scaled ? (const float*)scale : nullptr; p.scale_g = f.scaled ? (const float*)scale_g : nullptr;
+  p.ldx = ldx; p.ldw = ldw; p.ldy = ldy; p.ldr = ldr;
+  p.M = (int)M; p.N = N; p.K = K; p.act = act; p.nsplit = pl.nsplit; p.steps = pl.steps;
+  launch = true;
+  return 0;
+}
+
+static inline int skinny_launched(const SkinnyForm& f) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return mio_fail(std::string(f.name) + " launch: " + hipGetErrorString(e));
+  return 0;
+}
+
+// A launch of the 16-bit or the one-byte unit.
 static inline int skinny_run(const SkinnyForm& f, const SkinnyKernelTable& kernels, const void* x, const void* w, const float* scale,
                              const void* bias, const void* w_gate, const float* scale_g, const void* bias_gate, const void* residual,
                              void* y, void* workspace, int64_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy,
                              int64_t ldr, int32_t act, int32_t dtype, void* stream) {
-#define SKINNY_CHECK(cond, text) MIO_CHECK(cond, std::string(f.name) + (text))
-  std::string err;
-  if (!skinny_shape_ok(f, f.name, M, N, K, act, err)) return mio_fail(err);
-  SKINNY_CHECK(dtype == MIO_BF16 || dtype == MIO_FP16, f.dtype_text);
-  const bool glu = act == MIO_ACT_SWIGLU;
-  SKINNY_CHECK(glu == (w_gate != nullptr) && (!f.scaled || glu == (scale_g != nullptr)), f.gate_text);
-  SKINNY_CHECK(glu || bias_gate == nullptr, ": bias_gate belongs to act == SWIGLU");
-  SKINNY_CHECK(ldw % f.ldw_multiple == 0, f.ldw_multiple_text);
-  SKINNY_CHECK(ldw >= K, f.ldw_short_text);
-  SKINNY_CHECK(ldx % 8 == 0 && ldy % 8 == 0 && (!residual || ldr % 8 == 0), f.ld_multiple_text);
-  SKINNY_CHECK(ldx >= K && ldy >= N && (!residual || ldr >= N), ": row stride smaller than row length");
-  SKINNY_CHECK(w && (!f.scaled || scale) && (M == 0 || (x && y)), f.null_text);
-  SKINNY_CHECK(mio_aligned16(x) && mio_aligned16(w) && mio_aligned16(y) && mio_aligned16(w_gate) && mio_aligned16(residual) &&
-                   mio_aligned16(bias) && mio_aligned16(bias_gate) && mio_aligned16(workspace) && mio_aligned16(scale) &&
-                   mio_aligned16(scale_g),
-               ": pointers must be 16-byte aligned");
-  const SkinnyPlan pl = skinny_plan(f, M, N, K, act);
-  if (M == 0 || N == 0) return 0;
-  SKINNY_CHECK(pl.nsplit == 1 || workspace != nullptr, std::string(": workspace required (") + f.name + "_workspace_bytes) when the plan splits K");
-#undef SKINNY_CHECK
   SkinnyDev p;
-  p.x = x; p.w = w; p.wg = w_gate; p.bias = bias; p.bias_g = bias_gate; p.res = residual; p.y = y;
-  p.ws = pl.nsplit > 1 ? (float*)workspace : nullptr;
-  p.scale = scale; p.scale_g = scale_g;
-  p.ldx = ldx; p.ldw = ldw; p.ldy = ldy; p.ldr = ldr;
-  p.M = (int)M; p.N = N; p.K = K; p.act = act; p.nsplit = pl.nsplit; p.steps = pl.steps;
-  skinny_launch(kernels[dtype == MIO_BF16 ? 0 : 1][glu ? 0 : 1], p, pl, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mio_fail(std::string(f.name) + " launch: " + hipGetErrorString(e));
-  return 0;
+  SkinnyPlan pl;
+  bool launch;
+  if (int rc = skinny_prepare(f, x, w, scale, bias, w_gate, scale_g, bias_gate, residual, y, workspace, M, N, K, ldx, ldw, ldy, ldr, act,
+                              dtype, p, pl, launch))
+    return rc;
+  if (!launch) return 0;
+  skinny_launch(kernels[dtype == MIO_BF16 ? 0 : 1][pl.glu ? 0 : 1], p, pl, (hipStream_t)stream);
+  return skinny_launched(f);
 }
 
 // The host queries; who is the extern "C" entry point that asks.

@@ -1,4 +1,5 @@
-// The plan of a decode-step GEMM launch, for both weight forms (gemm_skinny.hip: 16-bit weights; gemm_skinny_w8.hip: e4m3fn weights):
+// The plan of a decode-step GEMM launch, for the weight forms (gemm_skinny.hip: 16-bit weights; gemm_skinny_w8.hip: e4m3fn weights;
+// gemm_skinny_w4.hip: MXFP4 weights):
 // shape checks, the split of K, the workspace, the tuning values of the kernels' K loops and the advice mio_gemm_skinny*_ok gives
 // the module layer.  What differs between the forms is a SkinnyForm; everything else is written once and takes one.  Host-only,
 // no HIP: the launches and the host queries (mio_gemm_skinny*_splits, _workspace_bytes, _slice, _chunk_k, _depth, _ok) all ask
@@ -61,6 +62,8 @@ struct SkinnyMoeTexts {
 struct SkinnyForm {
   const char* name;   // the launch entry point; the queries are name_splits, name_workspace_bytes, ...
   bool scaled;        // the weights carry fp32 per-column scales (two more pointers in the call)
+  bool block_scaled;  // the weights carry e8m0 block-scale bytes [N, K / 32] (the same two pointers and a row stride), applied
+                      // inside the K loop: nothing is left for the epilogue, which runs with scaled = false
   int kstep;          // k per step of the kernel: every slice is whole steps (the last one ends at K)
   int k_multiple;     // K must be a multiple of this: the k of one 16-byte weight load
   int min_k_per_row;  // a slice is at least this many k per row of x (the split rule below)
@@ -80,7 +83,7 @@ struct SkinnyForm {
 // 16-bit weights.  A step is one MFMA's 32 k.  The loop is double-buffered: the weight registers of two chunks (this one, the
 // next) are 64 VGPRs, so SwiGLU, with two weights, takes half the k.
 constexpr SkinnyForm SKINNY_W16 = {
-    "mio_gemm_skinny", /*scaled*/ false, /*kstep*/ 32, /*k_multiple*/ 8, /*min_k_per_row*/ 8, /*ldw_multiple*/ 8,
+    "mio_gemm_skinny", /*scaled*/ false, /*block_scaled*/ false, /*kstep*/ 32, /*k_multiple*/ 8, /*min_k_per_row*/ 8, /*ldw_multiple*/ 8,
     /*chunk_k*/ 256, 128, /*depth*/ 2, 2, skinny_advised,
     ": M must be at most 64 (mio_gemm_bias_act runs taller calls)", ": K must be a multiple of 8", ": dtype must be bf16 or fp16",
     ": w_gate is required iff act == SWIGLU", ": row strides must be multiples of 8 elements",
@@ -98,7 +101,7 @@ constexpr SkinnyForm SKINNY_W16 = {
 // (profiles/skinny_gemm_w8.md): plain depth 4 is within 1 % of depth 3 up to M 16 and slower at M 32 / 64 (268 VGPRs at four row
 // fragments: past 256, one wave per SIMD); SwiGLU depth 3 is within 2 % of depth 4.
 constexpr SkinnyForm SKINNY_W8 = {
-    "mio_gemm_skinny_w8", /*scaled*/ true, /*kstep*/ 64, /*k_multiple*/ 16, /*min_k_per_row*/ 16, /*ldw_multiple*/ 16,
+    "mio_gemm_skinny_w8", /*scaled*/ true, /*block_scaled*/ false, /*kstep*/ 64, /*k_multiple*/ 16, /*min_k_per_row*/ 16, /*ldw_multiple*/ 16,
     /*chunk_k*/ 256, 128, /*depth*/ 3, 4, skinny_w8_advised,
     ": M must be at most 64 (fp8 weights are read by the decode-step kernel only)", ": K must be a multiple of 16",
     ": dtype must be bf16 or fp16 (the activations'; the weights are e4m3fn bytes)",
@@ -109,6 +112,48 @@ constexpr SkinnyForm SKINNY_W8 = {
      ": s_down (the fp32 scales [E, d]) must be non-null", ": x, w8_up, h, expert_offsets, sorted_rows must be non-null",
      ": h, w8_down, y, ids, weights, expert_offsets, row_pos must be non-null",
      ": pointers must be 16-byte aligned (the scales and the route's arrays: 4-byte)"}};
+
+// Where the module layer should take the MXFP4-weight kernel: the regions of tools/skinny_w4_bench.py's sweep in which it ran in at
+// most 0.9 x the time of the faster of mio_gemm_skinny_w8 and mio_gemm_skinny on the same weight (profiles/skinny_gemm_w4.md: bf16,
+// weights streamed from HBM).  SwiGLU: M <= 16 from 14336 x 4096, the one shape measured, up (0.80 x; M 64 ran 0.91 x).  Plain
+// activations: 0.91 - 0.95 x for M <= 16 at 4096 x 4096, 6144 x 4096 and 4096 x 14336, and 1.00 - 1.36 x at M 64: no region
+// qualifies, and none is admitted.  The SwiGLU region is open upwards from that size, any aspect ratio and every M 1 .. 16, as
+// skinny_w8_advised's regions are; nothing below the sizes measured is admitted.
+static inline bool skinny_w4_advised(int64_t M, int32_t N, int32_t K, int32_t act) {
+  if (M < 1 || M > 16 || N < 1 || K < 32) return false;
+  return act == MIO_ACT_SWIGLU && (int64_t)N * K >= (int64_t)14336 * 4096;
+}
+
+// MXFP4 weights: e2m1 nibbles, two per byte, with one e8m0 scale byte per 32 consecutive k.  A 16-byte weight load is one block of
+// 32 k.  Slices are cut in steps of 128 k, four blocks, so that a slice's first scale byte sits on a dword of its row; a chunk is
+// 256 k, in which lane group q owns the two consecutive blocks at 64 q: two weight loads and one 2-byte scale load per lane
+// and chunk.  A register set holds 32 bytes of weight per lane (SwiGLU: 64), a quarter of the one-byte form's per k, so the ring is
+// one set deeper than that form's plain ring at fewer registers; what fills a set is the x pieces (8 x 16 bytes at four row
+// fragments).  The x chunk in LDS is 2 x 64 rows x 512 B = 64 KiB at four row fragments, the static limit, so the chunk does not
+// grow to the 512 k at which a scale dword would ride with four weight loads.  Tried on the sweeps of tools/skinny_w4_bench.py and
+// tools/moe_w4_bench.py (profiles/skinny_gemm_w4.md, profiles/moe_w4.md) at depth 3 / 4 / 5 plain and 4 / 3 / 2 SwiGLU: plain depth 5
+// is 2 - 13 % faster for M <= 16 and 1.2 - 1.6 x slower at M 64 (past 256 VGPRs at four row fragments), depth 3 is within 3 % of
+// depth 4; SwiGLU depth 4 is slower, depth 2 equal up to M 16 and faster at M 64, but measured only next to plain depth 5, a pair
+// that loses on the MoE step at T 64.  At depth 4 / 3 the dense kernel reaches 0.8 - 2.4 TB/s of half-byte weight (the grouped
+// one 0.5 - 3.3 TB/s, profiles/moe_w4.md), so the conversions and the x traffic bound it, not HBM.
+constexpr SkinnyForm SKINNY_W4 = {
+    "mio_gemm_skinny_w4", /*scaled*/ false, /*block_scaled*/ true, /*kstep*/ 128, /*k_multiple*/ 32, /*min_k_per_row*/ 32,
+    /*ldw_multiple*/ 16, /*chunk_k*/ 256, 256, /*depth*/ 4, 3, skinny_w4_advised,
+    ": M must be at most 64 (MXFP4 weights are read by the decode-step kernel only)",
+    ": K must be a multiple of 32 (whole MX blocks)",
+    ": dtype must be bf16 (e2m1 x 2^e is exact in bf16; in fp16 only inside a narrow exponent range)",
+    ": w4_gate and w_scale_gate are required together iff act == SWIGLU", ": ldw must be a multiple of 16 bytes",
+    ": ldw smaller than K / 2 bytes", ": ldx, ldy, ldr must be multiples of 8 elements", ": x, w4, w_scale, y must be non-null",
+    {": ldw and expert_stride must be multiples of 16 bytes", ": activation row strides must be multiples of 8 elements",
+     ": w4_gate and s_gate are required together iff act == SWIGLU", ": s_up (the e8m0 block scales [E, I, d / 32]) must be non-null",
+     ": s_down (the e8m0 block scales [E, d, I / 32]) must be non-null", ": x, w4_up, h, expert_offsets, sorted_rows must be non-null",
+     ": h, w4_down, y, ids, weights, expert_offsets, row_pos must be non-null",
+     ": pointers must be 16-byte aligned (the block scales and the route's arrays: 4-byte)"}};
+
+// bytes of a weight row's K elements in the form's storage, in the unit ldw counts in
+static inline int64_t skinny_row_units(const SkinnyForm& f, int32_t K) { return f.block_scaled ? K / 2 : K; }
+// the block-scale operands of a block-scaled form: row (and expert) strides in bytes, multiples of 4, a row at least K / 32
+static inline bool skinny_lds_ok(int64_t lds, int32_t K) { return lds % 4 == 0 && lds >= K / 32; }
 
 struct SkinnyPlan {
   int mf;        // row fragments: ceil(M / 16)

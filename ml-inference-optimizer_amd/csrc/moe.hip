@@ -90,7 +90,7 @@ __global__ __launch_bounds__(MOE_RT_NT) void moe_route_kernel(const MoeRouteDev 
 // The K loop is gemm_skinny_w16_head.inc + gemm_skinny_w16_loop.inc, the decode-step GEMM's, under an expert's rows description
 // (moe_rows_head.inc, moe_rows_gather.inc).
 template <typename T, int MF, bool GLU>
-__global__ __launch_bounds__(256) void moe_gemm_kernel(const MoeDev<false> p) {
+__global__ __launch_bounds__(256) void moe_gemm_kernel(const MoeDev<MOE_SCALES_NONE> p) {
 #include "moe_rows_head.inc"
 #include "gemm_skinny_w16_head.inc"
 #include "moe_rows_gather.inc"
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(const MoeDev<false> p) {
   }
 }
 
-static const MoeKernelTable<false> KERNELS = MOE_KERNEL_TABLE(moe_gemm_kernel, 0, false);
+static const MoeKernelTable<MOE_SCALES_NONE> KERNELS = MOE_KERNEL_TABLE(moe_gemm_kernel, 0, MOE_SCALES_NONE);
 
 // ---- the C ABI -----------------------------------------------------------------------------------------------------------------
 extern "C" int mio_moe_route(const void* logits, int64_t ld, int32_t* ids, float* weights, int32_t* expert_offsets,

@@ -88,8 +88,8 @@ __device__ __forceinline__ void moe_route_token(const L* row, int E, int topk, i
 // Down's second launch: one thread per (token, 4 columns).  Per slot j in order: the slices' partials of the slot's sorted
 // position in slice order, z = sum + bias[e, n] with the slot's expert e (SCALED, e4m3fn expert weights: fma(sum, scale[e, n],
 // bias[e, n]), the scale going in before the routing weight), times the routing weight; then the residual and the one rounding.
-// UNIT names the including unit (0: moe.hip, 1: moe_prefill.hip, 2: moe_w8.hip), so that each object carries a kernel symbol of
-// its own.
+// UNIT names the including unit (0: moe.hip, 1: moe_prefill.hip, 2: moe_w8.hip, 3: moe_w4.hip), so that each object carries a
+// kernel symbol of its own.
 struct MoeDownDev {
   const float* ws;
   const float* scale;  // SCALED only: fp32 [E, N]; null otherwise

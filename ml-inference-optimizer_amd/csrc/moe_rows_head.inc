@@ -1,6 +1,6 @@
-// An expert's rows description for the decode-step GEMM's K loop, written once for moe_gemm_kernel (moe.hip) and
-// moe_gemm_w8_kernel (moe_w8.hip), in two pieces of text around the form's K-loop set-up (gemm_skinny_w16_head.inc /
-// gemm_skinny_w8_head.inc, which say why this is text): this one in front of it, moe_rows_gather.inc behind it.  MF and the
+// An expert's rows description for the decode-step GEMM's K loop, written once for moe_gemm_kernel (moe.hip),
+// moe_gemm_w8_kernel (moe_w8.hip) and moe_gemm_w4_kernel (moe_w4.hip), in two pieces of text around the form's K-loop set-up
+// (gemm_skinny_w16_head.inc / gemm_skinny_w8_head.inc / gemm_skinny_w4_head.inc, which say why this is text): this one in front of it, moe_rows_gather.inc behind it.  MF and the
 // launch's arguments `p` (a MoeDev) come from the including kernel.
 //
 // This piece: the expert's rows, sorted positions [r0, r0 + cnt).  No rows: nothing of this expert is read and no barrier is met,

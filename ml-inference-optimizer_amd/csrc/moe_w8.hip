@@ -35,7 +35,7 @@
 constexpr SkinnyForm FORM = SKINNY_W8;  // this unit's weight form (gemm_skinny_plan.h)
 
 template <typename T, int MF, bool GLU>
-__global__ __launch_bounds__(256) void moe_gemm_w8_kernel(const MoeDev<true> p) {
+__global__ __launch_bounds__(256) void moe_gemm_w8_kernel(const MoeDev<MOE_SCALES_CHANNEL> p) {
 #include "moe_rows_head.inc"
 #include "gemm_skinny_w8_head.inc"
 #include "moe_rows_gather.inc"
@@ -46,10 +46,10 @@ __global__ __launch_bounds__(256) void moe_gemm_w8_kernel(const MoeDev<true> p) 
   if (n >= p.N) return;
   // lane (c, q): rows 16 mf + c of the expert, i.e. sorted positions r0 + 16 mf + c, columns n .. n + 3: unscaled partials, or
   // the scaled epilogue with the expert's scale and bias rows
-  skinny_write<T, MF, GLU, true>(moe_finish_args<true>(p, e), p.ws, p.nsplit, p.rows, s, c, n, r0, cnt, acc, accg);
+  skinny_write<T, MF, GLU, true>(moe_finish_args<MOE_SCALES_CHANNEL>(p, e), p.ws, p.nsplit, p.rows, s, c, n, r0, cnt, acc, accg);
 }
 
-static const MoeKernelTable<true> KERNELS = MOE_KERNEL_TABLE(moe_gemm_w8_kernel, 2, true);
+static const MoeKernelTable<MOE_SCALES_CHANNEL> KERNELS = MOE_KERNEL_TABLE(moe_gemm_w8_kernel, 2, MOE_SCALES_CHANNEL);
 
 // ---- the C ABI: argument marshalling over moe_gemm_common.h's host side ---------------------------------------------------------
 extern "C" int mio_moe_up_w8_splits(int32_t T, int32_t top_k, int32_t E, int32_t N, int32_t K, int32_t act) {

@@ -120,6 +120,14 @@ EXPORTS = (
     "mio_gemm_skinny_w8_depth",
     "mio_gemm_skinny_w8_ok",
     "mio_gemm_skinny_w8",
+    "mio_weight_quant_mxfp4",
+    "mio_gemm_skinny_w4_workspace_bytes",
+    "mio_gemm_skinny_w4_splits",
+    "mio_gemm_skinny_w4_slice",
+    "mio_gemm_skinny_w4_chunk_k",
+    "mio_gemm_skinny_w4_depth",
+    "mio_gemm_skinny_w4_ok",
+    "mio_gemm_skinny_w4",
     "mio_gemm_f8",
     "mio_gemm_f8_ok",
     "mio_gemm_f8_route",
@@ -164,6 +172,12 @@ EXPORTS = (
     "mio_moe_down_w8_workspace_bytes",
     "mio_moe_up_w8",
     "mio_moe_down_w8",
+    "mio_moe_up_w4_splits",
+    "mio_moe_up_w4_workspace_bytes",
+    "mio_moe_down_w4_splits",
+    "mio_moe_down_w4_workspace_bytes",
+    "mio_moe_up_w4",
+    "mio_moe_down_w4",
     "mio_moe_prefill_max_tiles",
     "mio_moe_prefill_route",
     "mio_moe_prefill_up",
@@ -309,13 +323,14 @@ def _load() -> C.CDLL:
     lib.mio_gemm_bias_act.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
     lib.mio_gemm_bias_act.restype = i32
     # the decode-step GEMM's host queries, one family per weight form: the same signatures under both names
-    for fam in ("mio_gemm_skinny", "mio_gemm_skinny_w8"):
+    for fam in ("mio_gemm_skinny", "mio_gemm_skinny_w8", "mio_gemm_skinny_w4"):
         for query, restype in (("workspace_bytes", C.c_size_t), ("splits", i32), ("ok", i32)):
             getattr(lib, f"{fam}_{query}").argtypes = [i64, i32, i32, i32]
             getattr(lib, f"{fam}_{query}").restype = restype
         getattr(lib, f"{fam}_slice").argtypes = [i64, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
         getattr(lib, f"{fam}_slice").restype = i32
-    for name in ("mio_gemm_skinny_chunk_k", "mio_gemm_skinny_w8_chunk_k", "mio_gemm_skinny_w8_depth"):
+    for name in ("mio_gemm_skinny_chunk_k", "mio_gemm_skinny_w8_chunk_k", "mio_gemm_skinny_w8_depth", "mio_gemm_skinny_w4_chunk_k",
+                 "mio_gemm_skinny_w4_depth"):
         getattr(lib, name).argtypes = [i32]
         getattr(lib, name).restype = i32
     lib.mio_gemm_skinny.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
@@ -324,6 +339,12 @@ def _load() -> C.CDLL:
     lib.mio_weight_quant_w8.restype = i32
     lib.mio_gemm_skinny_w8.argtypes = [vp] * 10 + [i64, i32, i32, i64, i64, i64, i64, i32, i32, vp]
     lib.mio_gemm_skinny_w8.restype = i32
+    # w, ldw, w4, ldw4 (bytes), scale, lds (bytes), N, K, dtype, stream
+    lib.mio_weight_quant_mxfp4.argtypes = [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp]
+    lib.mio_weight_quant_mxfp4.restype = i32
+    # as mio_gemm_skinny_w8, with lds (bytes) behind ldw (bytes)
+    lib.mio_gemm_skinny_w4.argtypes = [vp] * 10 + [i64, i32, i32, i64, i64, i64, i64, i64, i32, i32, vp]
+    lib.mio_gemm_skinny_w4.restype = i32
     # x8, ldx, x_scale, w8, ldw, w_scale, bias, w8_gate, w_scale_gate, bias_gate, residual, ldr, y, ldy, M, N, K, act, out_dtype, stream
     lib.mio_gemm_f8.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i32, i32, i32, i32, vp]
     lib.mio_gemm_f8.restype = i32
@@ -460,6 +481,15 @@ def _load() -> C.CDLL:
     # expert_stride (bytes), ldy, ldr, dtype, stream
     lib.mio_moe_down_w8.argtypes = [vp] * 11 + [i32] * 5 + [i64] * 5 + [i32, vp]
     lib.mio_moe_down_w8.restype = i32
+    for name, n, restype in (("up_w4_splits", 6, i32), ("up_w4_workspace_bytes", 6, C.c_size_t), ("down_w4_splits", 5, i32),
+                             ("down_w4_workspace_bytes", 5, C.c_size_t)):
+        getattr(lib, f"mio_moe_{name}").argtypes = [i32] * n
+        getattr(lib, f"mio_moe_{name}").restype = restype
+    # as the _w8 pair, with lds and scale_expert_stride (bytes) behind expert_stride
+    lib.mio_moe_up_w4.argtypes = [vp] * 11 + [i32] * 5 + [i64] * 6 + [i32, i32, vp]
+    lib.mio_moe_up_w4.restype = i32
+    lib.mio_moe_down_w4.argtypes = [vp] * 11 + [i32] * 5 + [i64] * 7 + [i32, vp]
+    lib.mio_moe_down_w4.restype = i32
     # mixture of experts, tall inputs: T, top_k, E
     lib.mio_moe_prefill_max_tiles.argtypes = [i32] * 3
     lib.mio_moe_prefill_max_tiles.restype = i32

@@ -97,6 +97,12 @@ class CastCache:
         return self._memo(("ew8", id(p)), (p.data_ptr(), p._version, dtype, p.device, "experts_w8"),
                           lambda: ops.quantize_expert_weights_w8(self.get(p, dtype)))
 
+    def get_experts_mxfp4(self, p: torch.Tensor, dtype: torch.dtype) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The MXFP4 copy of a stacked expert weight [E, N, K] (ops.quantize_expert_weights_mxfp4 of its copy in dtype): (w4
+        [E, N, K / 2] uint8, scale [E, N, K / 32] uint8 e8m0), quantised again when its version changes."""
+        return self._memo(("ew4", id(p)), (p.data_ptr(), p._version, dtype, p.device, "experts_mxfp4"),
+                          lambda: ops.quantize_expert_weights_mxfp4(self.get(p, dtype)))
+
     def get_row_padded(self, p: torch.Tensor, dtype: torch.dtype, multiple: int) -> torch.Tensor:
         """The 2-D parameter in dtype with zero rows appended up to the next multiple of `multiple` rows (itself where it has that
         many already), made again when its version changes."""

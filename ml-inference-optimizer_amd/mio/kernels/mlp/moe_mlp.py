@@ -30,12 +30,20 @@ class MoEConfig:
     (ops.quantize_expert_weights_w8: e4m3fn bytes, one fp32 scale per expert and output channel, made once per version of a
     parameter) through ops.moe_mlp_w8: half the weight bytes per step.  hidden_size and intermediate_size must then be multiples
     of 16.  The router GEMM stays 16-bit, and so does grouped_prefill, which keeps reading the 16-bit weights.  Off by default:
-    forward is then what it was, to the bit.  Whether it pays at a shape is the caller's to measure (profiles/moe_w8.md)."""
+    forward is then what it was, to the bit.  Whether it pays at a shape is the caller's to measure (profiles/moe_w8.md).
+    expert_weights_mxfp4: the same with MXFP4 copies (ops.quantize_expert_weights_mxfp4: e2m1 nibbles, one e8m0 scale byte per 32
+    k) through ops.moe_mlp_w4: a quarter of the 16-bit weight bytes plus 1/32 for the scales per step.  Exclusive with
+    expert_weights_fp8; hidden_size and intermediate_size must be multiples of 32; dtype must be bf16.  The router GEMM and
+    grouped_prefill stay 16-bit.  Off by default (profiles/moe_w4.md)."""
     activation: str = "swiglu"
     renormalize: bool = True
     dtype: torch.dtype = torch.bfloat16
     grouped_prefill: bool = False
     expert_weights_fp8: bool = False
+    expert_weights_mxfp4: bool = False
+
+
+_MXFP4_NAMES = ("w4_up", "s_up", "w4_down", "s_down", "w4_gate", "s_gate")  # ops.moe_mlp_w4's names for the loaded bytes
 
 
 class MoEMLP(nn.Module):
@@ -59,6 +67,15 @@ class MoEMLP(nn.Module):
         if self.config.expert_weights_fp8 and (hidden_size % 16 or intermediate_size % 16):
             raise ValueError(f"expert_weights_fp8 needs hidden_size and intermediate_size to be multiples of 16 (the FP8 kernels' "
                              f"16-byte weight loads), got {hidden_size} and {intermediate_size}")
+        if self.config.expert_weights_mxfp4:
+            if self.config.expert_weights_fp8:
+                raise ValueError("expert_weights_mxfp4 and expert_weights_fp8 are exclusive")
+            if hidden_size % 32 or intermediate_size % 32:
+                raise ValueError(f"expert_weights_mxfp4 needs hidden_size and intermediate_size to be multiples of 32 (whole MX "
+                                 f"blocks), got {hidden_size} and {intermediate_size}")
+            if self.config.dtype != torch.bfloat16:
+                raise ValueError("expert_weights_mxfp4 needs dtype bf16: e2m1 x 2^e is not exact in fp16 outside a narrow exponent range")
+        self._mxfp4 = False  # load_mxfp4_experts: pre-quantised bytes, held as buffers, stand in place of the 16-bit expert parameters
         self.hidden_size, self.intermediate_size = hidden_size, intermediate_size
         self.num_experts, self.top_k = num_experts, top_k
         self.router = nn.Linear(hidden_size, num_experts, bias=False)
@@ -108,8 +125,18 @@ class MoEMLP(nn.Module):
         out = ops.empty_rows8(T, d, dt, x.device)
         # the path, chosen once on the whole T (a short last chunk of a tall input stays on the prefill ops): its chunk length,
         # its route and MLP ops, and the weights under the names that MLP op takes them by
-        prefill = self.config.grouped_prefill and T > ops.MOE_MAX_TOKENS
-        if self.config.expert_weights_fp8 and not prefill:
+        prefill = self.config.grouped_prefill and T > ops.MOE_MAX_TOKENS and not self._mxfp4
+        if self._mxfp4 or (self.config.expert_weights_mxfp4 and not prefill):
+            chunk, route_op, mlp_op = ops.MOE_MAX_TOKENS, ops.moe_route, ops.moe_mlp_w4
+            if dt != torch.bfloat16:
+                raise ValueError("MXFP4 expert weights need dtype bf16")
+            if self._mxfp4:
+                weights = {name: getattr(self, "mxfp4_" + name) for name in _MXFP4_NAMES}
+            else:
+                (q_up, s_up), (q_down, s_down) = c.get_experts_mxfp4(self.w_up, dt), c.get_experts_mxfp4(self.w_down, dt)
+                q_gate, s_gate = c.get_experts_mxfp4(self.w_gate, dt) if self.w_gate is not None else (None, None)
+                weights = dict(w4_up=q_up, s_up=s_up, w4_down=q_down, s_down=s_down, w4_gate=q_gate, s_gate=s_gate)
+        elif self.config.expert_weights_fp8 and not prefill:
             chunk, route_op, mlp_op = ops.MOE_MAX_TOKENS, ops.moe_route, ops.moe_mlp_w8
             (q_up, s_up), (q_down, s_down) = c.get_experts_w8(self.w_up, dt), c.get_experts_w8(self.w_down, dt)
             q_gate, s_gate = c.get_experts_w8(self.w_gate, dt) if self.w_gate is not None else (None, None)
@@ -126,6 +153,37 @@ class MoEMLP(nn.Module):
             mlp_op(xc, route, act=self.config.activation, **weights, residual=None if r is None else r[lo:hi], out=out[lo:hi])
         return as_dtype(out.reshape(*hidden_states.shape[:-1], d), in_dtype)
 
+    def load_mxfp4_experts(self, blocks_up, scales_up, blocks_gate, scales_gate, blocks_down, scales_down) -> None:
+        """Take pre-quantised MXFP4 expert weights as they are: blocks uint8 [E, N, K / 2] (or [E, N, K / 32, 16], taken by view),
+        e2m1 nibbles with element 2 i in the low nibble of byte i, and scales uint8 e8m0 [E, N, K / 32]; N, K = I, d for up and
+        gate, d, I for down; the gate pair is None where the activation is not swiglu.  The module then holds no 16-bit expert
+        weights (w_up, w_gate and w_down become None): the decode path on these bytes is its only one, T > 64 goes in row chunks
+        of 64, and config.dtype must be bf16.  The tensors are kept, not copied, where the kernels can take them as they lie, as
+        non-persistent buffers mxfp4_w4_up, mxfp4_s_up, ...: module.to(device) moves them, state_dict() does not hold them (a
+        checkpoint of such a module is the bytes it was loaded from), and load_from_expert_state_dict is refused afterwards."""
+        E, I, d = self.num_experts, self.intermediate_size, self.hidden_size
+        if d % 32 or I % 32 or self.config.dtype != torch.bfloat16:
+            raise ValueError("MXFP4 expert weights need hidden_size and intermediate_size to be multiples of 32 and dtype bf16")
+        if (blocks_gate is not None) != (self.config.activation == "swiglu") or (blocks_gate is None) != (scales_gate is None):
+            raise ValueError("the gate blocks and scales are given together, with activation 'swiglu' only")
+
+        def take(blocks, scales, N, K, name):
+            if blocks is None:
+                return None, None
+            if blocks.dim() == 4 and tuple(blocks.shape) == (E, N, K // 32, 16):
+                blocks = blocks.reshape(E, N, K // 2)
+            if tuple(blocks.shape) != (E, N, K // 2) or tuple(scales.shape) != (E, N, K // 32):
+                raise ValueError(f"{name}: expected blocks {(E, N, K // 2)} (or {(E, N, K // 32, 16)}) and scales {(E, N, K // 32)}, got "
+                                 f"{tuple(blocks.shape)} and {tuple(scales.shape)}")
+            return ops._as_bytes(blocks, name + " blocks"), ops._moe_scales(ops._MOE_DECODE_W4, scales, E, N, K, name + " scales", "load_mxfp4_experts")
+
+        (q_up, s_up), (q_gate, s_gate), (q_down, s_down) = (take(blocks_up, scales_up, I, d, "up"), take(blocks_gate, scales_gate, I, d, "gate"),
+                                                            take(blocks_down, scales_down, d, I, "down"))
+        for name, t in zip(_MXFP4_NAMES, (q_up, s_up, q_down, s_down, q_gate, s_gate)):
+            self.register_buffer("mxfp4_" + name, t, persistent=False)
+        self._mxfp4 = True
+        self.w_up = self.w_gate = self.w_down = None
+
     def load_from_expert_state_dict(self, state_dict: Dict[str, torch.Tensor], prefix: str = "", gate: str = "gate.weight",
                                     expert: str = "experts.{e}", names: Sequence[str] = ("w1", "w3", "w2")) -> None:
         """Stack per-expert weights into this module's parameters.  Keys: {prefix}{gate} is the router [E, d]; expert e's
@@ -133,6 +191,8 @@ class MoEMLP(nn.Module):
         down projection [d, I]).  The defaults are HF Mixtral's layout (block_sparse_moe.gate, experts.N.w1 / w3 / w2); Qwen-MoE
         is gate="gate.weight", names=("gate_proj", "up_proj", "down_proj").  Without a gate weight (activation != "swiglu") the
         first name is not read.  KeyError for a missing key, ValueError for a wrong shape."""
+        if self._mxfp4:
+            raise ValueError("this module holds MXFP4 expert bytes (load_mxfp4_experts) and no 16-bit expert parameters to load into")
         n_gate, n_up, n_down = names
 
         def take(key, shape):

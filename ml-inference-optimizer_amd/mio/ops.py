@@ -26,6 +26,9 @@ same exception types for the same conditions):
   quantize_expert_weights_w8 / moe_up_w8 / moe_down_w8 / moe_mlp_w8
                                the grouped GEMMs of a decode step on weight-only FP8 (e4m3fn) expert weights with one fp32 scale
                                per expert and output channel, under the same routing
+  quantize_weight_mxfp4 / gemm_skinny_w4 / quantize_expert_weights_mxfp4 / moe_up_w4 / moe_down_w4 / moe_mlp_w4
+                               the decode-step GEMM and the grouped GEMMs on MXFP4 weights (e2m1 nibbles, two per byte, one
+                               e8m0 scale byte per 32 k), bf16 only
   quantize_rows_f8 / gemm_f8 / gemm_w8a8
                                the GEMM of tall inputs on FP8 compute (not a reference kernel): per-token e4m3fn activations against
                                the e4m3fn weight copy of quantize_weight_w8 on the fp8 matrix instruction, scales in the read-out
@@ -735,10 +738,12 @@ def _skinny_splits(name: str, M: int, N: int, K: int, activation: str) -> int:
     return n
 
 
-def _skinny(fn, ws_bytes, tall: str, x, N: int, K: int, ldw: int, w_ptrs, g_ptrs, bias, activation: str, bias_gate, residual, out):
+def _skinny(fn, ws_bytes, tall: str, x, N: int, K: int, ldw: int, w_ptrs, g_ptrs, bias, activation: str, bias_gate, residual, out,
+            lds: tuple = ()):
     """What gemm_skinny and gemm_skinny_w8 do around their weight operands, which the caller has checked.  fn / ws_bytes: the
     C launch and its workspace query; ldw: the row stride of the weight [N, K] (and of the gate); w_ptrs / g_ptrs: the addresses
-    of the weight and of the gate with what goes with them, as fn takes them between x and bias and between bias and bias_gate."""
+    of the weight and of the gate with what goes with them, as fn takes them between x and bias and between bias and bias_gate;
+    lds: (the row stride of the block scales,) where fn takes one behind ldw."""
     if activation not in _ACT:
         raise ValueError(f"Unsupported activation function: {activation}")
     act = _ACT[activation]
@@ -760,7 +765,7 @@ def _skinny(fn, ws_bytes, tall: str, x, N: int, K: int, ldw: int, w_ptrs, g_ptrs
     nbytes = ws_bytes(M, N, K, act)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
     check(fn(x2.data_ptr(), *w_ptrs, _ptr(bias), *g_ptrs, _ptr(bias_gate), _ptr(r2), y2.data_ptr(), _ptr(ws), M, N, K, x2.stride(0),
-             ldw, y2.stride(0), 0 if r2 is None else r2.stride(0), act, dt, _stream()))
+             ldw, *lds, y2.stride(0), 0 if r2 is None else r2.stride(0), act, dt, _stream()))
     return out
 
 
@@ -883,6 +888,120 @@ def gemm_skinny_w8(x, w8, w_scale, bias=None, activation: str = "none", w8_gate=
     return _skinny(lib.mio_gemm_skinny_w8, lib.mio_gemm_skinny_w8_workspace_bytes, "fp8 weights are read by the decode-step kernel only",
                    x, N, K, w2.stride(0), (w2.data_ptr(), s2.data_ptr()), (_ptr(g2), _ptr(sg2)), bias, activation, bias_gate,
                    residual, out)
+
+
+# ---- the same on MXFP4 weights (mio_gemm_skinny_w4): e2m1 nibbles, two per byte, with one e8m0 scale byte per 32
+# consecutive k, the byte order of torch.float4_e2m1fn_x2 and of gpt-oss's *_blocks / *_scales ----------------------------------------
+_BYTE_VIEWS = tuple(getattr(torch, n) for n in ("float4_e2m1fn_x2", "float8_e8m0fnu") if hasattr(torch, n))
+
+
+def _as_bytes(t, what: str) -> torch.Tensor:
+    """An MXFP4 operand as uint8: uint8 itself, or torch's packed-nibble / e8m0 dtypes by view."""
+    if not isinstance(t, torch.Tensor) or (t.dtype != torch.uint8 and t.dtype not in _BYTE_VIEWS):
+        raise ValueError(f"{what} must be a uint8 tensor (MXFP4 bytes), got {getattr(t, 'dtype', None)}")
+    _need_cuda(t)
+    return t if t.dtype == torch.uint8 else t.view(torch.uint8)
+
+
+def _pad4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+def _block_scales(s, lead: tuple, nb: int, what: str, like=None) -> torch.Tensor:
+    """The e8m0 block scales [*lead, nb] of an MXFP4 weight as the kernels take them: last-dim stride 1, every other stride a
+    multiple of 4 bytes that clears what lies inside it, a 4-byte aligned base, and, for an odd nb, one byte of its storage behind
+    the last row (the kernels load scale bytes in pairs).  Otherwise, and where the strides differ from like's (the scales it
+    must share them with), a copy with rows padded to 4 bytes."""
+    s = _as_bytes(s, what)
+    if tuple(s.shape) != (*lead, nb):
+        raise ValueError(f"{what} must have shape {(*lead, nb)} (one e8m0 byte per 32 k), got {tuple(s.shape)}")
+    ok, need = s.stride(-1) == 1 and s.data_ptr() % 4 == 0, nb
+    for i in range(len(lead) - 1, -1, -1):
+        ok, need = ok and s.stride(i) % 4 == 0 and s.stride(i) >= need, (lead[i] - 1) * s.stride(i) + need
+    ok = ok and (nb % 2 == 0 or s.untyped_storage().nbytes() > s.storage_offset() + need)
+    if not ok or (like is not None and s.stride() != like.stride()):
+        s = torch.empty(*lead, _pad4(nb), dtype=torch.uint8, device=s.device)[..., :nb].copy_(s)
+    return s
+
+
+def gemm_skinny_w4_ok(M: int, N: int, K: int, activation: str = "none") -> bool:
+    """True iff gemm_skinny_w4 is legal at this shape AND measured at most 0.9 x the time of the faster of gemm_skinny_w8 and
+    gemm_skinny on the same weight (profiles/skinny_gemm_w4.md).  Advice for the module layer: gemm_skinny_w4 itself runs every
+    legal shape."""
+    return _skinny_ok("gemm_skinny_w4", M, N, K, activation)
+
+
+def gemm_skinny_w4_splits(M: int, N: int, K: int, activation: str = "none") -> int:
+    """The slices of K a gemm_skinny_w4 call of this shape runs (1: one launch, no workspace).  Host-only; ValueError where the
+    call would be refused."""
+    return _skinny_splits("gemm_skinny_w4", M, N, K, activation)
+
+
+def quantize_weight_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One-time preparation of a bf16 / fp16 weight [N, K] (K % 32 == 0) for gemm_skinny_w4 by the OCP MX rule: (w4 [N, K / 2]
+    uint8, element 2 i in the low nibble of byte i; w_scale [N, K / 32] uint8 e8m0).  Per block of 32: a = max |v| (NaN ignored),
+    e = clamp(floor(log2 a) - 2, -127, 127) (0 where a == 0), scale byte e + 127, element = v * 2^-e rounded to nearest even on the
+    e2m1 grid +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating at +-6; +-Inf gives +-6, NaN a signed zero."""
+    _need_cuda(w)
+    dt = _dtype_id(w)
+    if w.dim() != 2:
+        raise ValueError(f"quantize_weight_mxfp4 takes a 2-D weight [N, K], got shape {tuple(w.shape)}")
+    N, K = w.shape
+    if K % 32 != 0:
+        raise ValueError(f"quantize_weight_mxfp4: K must be a multiple of 32 (whole MX blocks), got {K}")
+    w2 = _rows16(w)
+    w4 = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device)
+    lds = _pad4(K // 32)
+    scale = torch.empty(N, lds, dtype=torch.uint8, device=w.device)[:, :K // 32]
+    check(lib.mio_weight_quant_mxfp4(w2.data_ptr(), w2.stride(0), w4.data_ptr(), K // 2, scale.data_ptr(), lds, N, K, dt, _stream()))
+    return w4, scale
+
+
+def _w4_ok(t, what: str) -> torch.Tensor:
+    """An MXFP4 weight operand: 2-D bytes [N, K / 2] on the device; returned with unit column stride and rows a multiple of 16
+    bytes apart at a 16-byte aligned address (a row slice stays a view)."""
+    t = _as_bytes(t, what)
+    if t.dim() != 2:
+        raise ValueError(f"{what} must be a 2-D weight [N, K / 2], got shape {tuple(t.shape)}")
+    if t.stride(1) != 1 or t.stride(0) % 16 or t.stride(0) < t.shape[1] or t.data_ptr() % 16:
+        return t.contiguous()
+    return t
+
+
+def gemm_skinny_w4(x, w4, w_scale, bias=None, activation: str = "none", w4_gate=None, w_scale_gate=None, bias_gate=None,
+                   residual=None, out=None):
+    """gemm_skinny on an MXFP4 weight (x [..., K] bf16 with prod(...) <= 64; w4 [N, K / 2] uint8 e2m1 nibbles, K % 32 == 0;
+    w_scale [N, K / 32] uint8 e8m0): y = act(x @ deq(w4, w_scale)^T + bias) (+ residual), deq = e2m1 * 2^(scale - 127), SwiGLU with
+    w4_gate / w_scale_gate / bias_gate.  fp16 is refused: e2m1 * 2^e is not exact in fp16 outside a narrow exponent range.  Row
+    slices of w4 and w_scale are legal operands; scales of any row stride are taken, and where the stride is no multiple of 4
+    bytes or the base is not 4-byte aligned a copy with padded rows is made.  Allocates the split workspace only when the plan
+    splits K."""
+    _need_cuda(x)
+    w2 = _w4_ok(w4, "w4")
+    N, K = w2.shape[0], 2 * w2.shape[1]
+    if K != x.shape[-1]:
+        raise ValueError(f"weight shape {tuple(w2.shape)} (K = {K}) does not match input features {x.shape[-1]}")
+    if K % 32 != 0:
+        raise ValueError(f"gemm_skinny_w4: K must be a multiple of 32 (whole MX blocks), got {K}")
+    s2 = _block_scales(w_scale, (N,), K // 32, "w_scale")
+    g2 = sg2 = None
+    if activation == "swiglu":
+        if w4_gate is None or w_scale_gate is None:
+            raise ValueError("SwiGLU activation requires gate weights and their scales")
+        g2 = _w4_ok(w4_gate, "w4_gate")
+        if g2.shape != w2.shape:
+            raise ValueError("w4_gate must have w4's shape")
+        if g2.stride(0) != w2.stride(0):
+            g2, w2 = g2.contiguous(), w2.contiguous()
+        sg2 = _block_scales(w_scale_gate, (N,), K // 32, "w_scale_gate")
+        if N > 1 and sg2.stride(0) != s2.stride(0):  # (one lds for both: padded copies share it)
+            s2, sg2 = (torch.empty(N, _pad4(K // 32), dtype=torch.uint8, device=t.device)[:, :K // 32].copy_(t) for t in (s2, sg2))
+    elif w4_gate is not None or w_scale_gate is not None:
+        raise ValueError("w4_gate and w_scale_gate belong to activation='swiglu'")
+    lds = s2.stride(0) if N > 1 else _pad4(K // 32)
+    return _skinny(lib.mio_gemm_skinny_w4, lib.mio_gemm_skinny_w4_workspace_bytes, "MXFP4 weights are read by the decode-step kernel only",
+                   x, N, K, w2.stride(0), (w2.data_ptr(), s2.data_ptr()), (_ptr(g2), _ptr(sg2)), bias, activation, bias_gate,
+                   residual, out, lds=(lds,))
 
 
 # ---- the FP8 x FP8 GEMM for tall inputs (mio_gemm_f8; DESIGN 4.2g): e4m3fn activations with one fp32 scale per row against the
@@ -2101,7 +2220,9 @@ class _MoEPath(NamedTuple):
     w_multiple: int               # row and expert strides of a weight are multiples of this many elements (16 bytes) ...
     k_multiple: int               # ... and K a multiple of this
     pre: str                      # the weights' names: pre + "up" / "gate" / "down"
-    scaled: bool                  # every weight comes with fp32 scales [E, N], handed to the entry point behind it
+    scaled: bool                  # every weight comes with scales, handed to the entry point behind it: fp32 [E, N], or ...
+    block_scales: bool = False    # ... e8m0 block bytes [E, N, K / 32], whose row and expert strides follow the weights' strides
+    k_per_elem: int = 1           # k per stored weight element: 2 where a byte holds two e2m1 nibbles
 
 
 def _moe_tile_ptrs(route: MoEPrefillRoute) -> tuple:
@@ -2121,6 +2242,12 @@ _MOE_DECODE_W8 = _MOE_DECODE._replace(
     up_entry=lib.mio_moe_up_w8, up_workspace_bytes=lib.mio_moe_up_w8_workspace_bytes,
     down_entry=lib.mio_moe_down_w8, down_workspace_bytes=lib.mio_moe_down_w8_workspace_bytes,
     w_dtype=_W8, w_multiple=16, k_multiple=16, pre="w8_", scaled=True)
+# (the same route; MXFP4 bytes [E, N, K / 2] with e8m0 block scales [E, N, K / 32])
+_MOE_DECODE_W4 = _MOE_DECODE._replace(
+    up_op="moe_up_w4", down_op="moe_down_w4",
+    up_entry=lib.mio_moe_up_w4, up_workspace_bytes=lib.mio_moe_up_w4_workspace_bytes,
+    down_entry=lib.mio_moe_down_w4, down_workspace_bytes=lib.mio_moe_down_w4_workspace_bytes,
+    w_dtype=torch.uint8, w_multiple=16, k_multiple=32, pre="w4_", scaled=True, block_scales=True, k_per_elem=2)
 # (the 16-bit weights under a route with a tile map; up finishes in its one launch)
 _MOE_PREFILL = _MOE_DECODE._replace(
     route_op="moe_route_prefill", up_op="moe_up_prefill", down_op="moe_down_prefill", route_type=MoEPrefillRoute,
@@ -2210,12 +2337,14 @@ def _moe_weight(p: _MoEPath, w, E: int, act_dtype, name: str, who: str, like=Non
         raise ValueError(f"{who}: {name} must be a stacked expert weight [E = {E}, N, K]")
     _need_cuda(w)
     dtype = p.w_dtype or act_dtype
+    if p.block_scales:
+        w = _as_bytes(w, f"{who}: {name}")
     if w.dtype != dtype:
         raise ValueError(f"{who}: {name} must be torch.float8_e4m3fn (OCP e4m3), got {w.dtype}" if dtype == _W8
                          else f"{who}: {name} must have the activation dtype {dtype}, got {w.dtype}")
-    N, K = w.shape[1:]
-    if K % p.k_multiple != 0:
-        raise ValueError(f"{who}: K must be a multiple of {p.k_multiple}, got {K} ({name})")
+    N, K = w.shape[1:]  # (K in stored elements)
+    if K * p.k_per_elem % p.k_multiple != 0:
+        raise ValueError(f"{who}: K must be a multiple of {p.k_multiple}, got {K * p.k_per_elem} ({name})")
     mult = p.w_multiple
     ok = (w.stride(2) == 1 and w.stride(1) % mult == 0 and w.stride(1) >= K and w.stride(0) % mult == 0
           and w.stride(0) >= (N - 1) * w.stride(1) + K and w.data_ptr() % 16 == 0)
@@ -2281,10 +2410,10 @@ def _moe_up_core(p: _MoEPath, x, route, w_up, act, w_gate, b_up, b_gate, out, s_
             raise ValueError("SwiGLU activation requires gate weights" + (" and their scales" if p.scaled else ""))
         raise ValueError(f"{who}: {pre}gate {'and s_gate belong' if p.scaled else 'belongs'} to act='swiglu'")
     w = _moe_weight(p, w_up, E, x.dtype, pre + "up", who)
-    I, d = w.shape[1:]
+    I, d = w.shape[1], w.shape[2] * p.k_per_elem
     if x.shape[1] != d:
         raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match input features {x.shape[1]}")
-    su = (_moe_scale_w8(s_up, E, I, "s_up", who),) if p.scaled else ()
+    su = (_moe_scales(p, s_up, E, I, d, "s_up", who),) if p.scaled else ()
     g, sg = None, (None,) if p.scaled else ()
     if glu:
         if w_gate.shape != w_up.shape:
@@ -2293,7 +2422,9 @@ def _moe_up_core(p: _MoEPath, x, route, w_up, act, w_gate, b_up, b_gate, out, s_
         if g.stride() != w.stride():
             w = w.contiguous()
         if p.scaled:
-            sg = (_moe_scale_w8(s_gate, E, I, "s_gate", who),)
+            sg = (_moe_scales(p, s_gate, E, I, d, "s_gate", who),)
+            if p.block_scales and sg[0].stride() != su[0].stride():  # (one pair of strides for both: padded copies share it)
+                su, sg = ((_pad_block_scales(t),) for t in (su[0], sg[0]))
     bu = _moe_bias(b_up, E, I, x.dtype, "b_up", who)
     bg = _moe_bias(b_gate, E, I, x.dtype, "b_gate", who) if glu else None
     x2 = _rows16(x)
@@ -2310,7 +2441,8 @@ def _moe_up_core(p: _MoEPath, x, route, w_up, act, w_gate, b_up, b_gate, out, s_
     # (a scaled entry point takes each weight's scales behind the weight, a tiled one the tile map behind the route's arrays)
     check(p.up_entry(x2.data_ptr(), w.data_ptr(), *map(_ptr, su), _ptr(bu), _ptr(g), *map(_ptr, sg), _ptr(bg),
                      route.expert_offsets.data_ptr(), route.sorted_rows.data_ptr(), *(_moe_tile_ptrs(route) if p.tiled else ()),
-                     out.data_ptr(), *((_ptr(ws),) if takes_ws else ()), T, k, E, I, d, _ld(x2, d), w.stride(1), w.stride(0), _ld(out, I), a, dt, _stream()))
+                     out.data_ptr(), *((_ptr(ws),) if takes_ws else ()), T, k, E, I, d, _ld(x2, d), w.stride(1), w.stride(0),
+                     *(su[0].stride()[1::-1] if p.block_scales else ()), _ld(out, I), a, dt, _stream()))
     return out
 
 
@@ -2332,10 +2464,10 @@ def _moe_down_core(p: _MoEPath, h, route, w_down, b_down, residual, out, s_down=
     if h.dim() != 2 or h.shape[0] != T * k:
         raise ValueError(f"{who}: h must be [T k = {T * k}, I], got {tuple(h.shape)}")
     w = _moe_weight(p, w_down, E, h.dtype, p.pre + "down", who)
-    d, I = w.shape[1:]
+    d, I = w.shape[1], w.shape[2] * p.k_per_elem
     if h.shape[1] != I:
         raise ValueError(f"{who}: weight shape {tuple(w.shape)} does not match h's {h.shape[1]} features")
-    s = (_moe_scale_w8(s_down, E, d, "s_down", who),) if p.scaled else ()
+    s = (_moe_scales(p, s_down, E, d, I, "s_down", who),) if p.scaled else ()
     bd = _moe_bias(b_down, E, d, h.dtype, "b_down", who)
     h2 = _rows16(h)
     _res_ok(residual, T * d, h.dtype)
@@ -2356,7 +2488,8 @@ def _moe_down_core(p: _MoEPath, h, route, w_down, b_down, residual, out, s_down=
         raise ValueError(f"{who}: workspace must be a contiguous, 16-byte aligned fp32 tensor of at least {need} elements on h's device")
     check(p.down_entry(h2.data_ptr(), w.data_ptr(), *map(_ptr, s), _ptr(bd), route.ids.data_ptr(), route.weights.data_ptr(),
                        route.expert_offsets.data_ptr(), route.row_pos.data_ptr(), *(_moe_tile_ptrs(route) if p.tiled else ()), _ptr(r2),
-                       out.data_ptr(), workspace.data_ptr(), T, k, E, d, I, _ld(h2, I), w.stride(1), w.stride(0), _ld(out, d),
+                       out.data_ptr(), workspace.data_ptr(), T, k, E, d, I, _ld(h2, I), w.stride(1), w.stride(0),
+                       *(s[0].stride()[1::-1] if p.block_scales else ()), _ld(out, d),
                        0 if r2 is None else _ld(r2, d), dt, _stream()))
     return out
 
@@ -2400,6 +2533,21 @@ def _moe_scale_w8(s, E: int, N: int, name: str, who: str) -> torch.Tensor:
     return s if s.is_contiguous() else s.contiguous()
 
 
+def _pad_block_scales(s: torch.Tensor) -> torch.Tensor:
+    """A copy of block scales [E, N, nb] with rows padded to 4 bytes: the strides the kernels take, the same for any source."""
+    E, N, nb = s.shape
+    return torch.empty(E, N, _pad4(nb), dtype=torch.uint8, device=s.device)[..., :nb].copy_(s)
+
+
+def _moe_scales(p: _MoEPath, s, E: int, N: int, K: int, name: str, who: str) -> torch.Tensor:
+    """The scales of a stacked weight [E, N, K] of a scaled path: fp32 [E, N], or e8m0 block bytes [E, N, K / 32] with strides the
+    kernels take (size-1 dimensions have no stride to speak of: such scales are copied to the padded layout)."""
+    if not p.block_scales:
+        return _moe_scale_w8(s, E, N, name, who)
+    s = _block_scales(s, (E, N), K // 32, f"{who}: {name}")
+    return _pad_block_scales(s) if 1 in (E, N) and s.stride() != (N * _pad4(K // 32), _pad4(K // 32), 1) else s
+
+
 def moe_up_w8(x, route: MoERoute, w8_up, s_up, act: str = "swiglu", w8_gate=None, s_gate=None, b_up=None, b_gate=None, out=None):
     """moe_up on weight-only FP8 expert weights (mio_moe_up_w8): x [T, d] bf16 / fp16, w8_up (and w8_gate for swiglu) [E, I, d]
     torch.float8_e4m3fn with d % 16 == 0, s_up / s_gate fp32 [E, I] (quantize_expert_weights_w8 makes both) -> h [T k, I] by sorted
@@ -2420,6 +2568,53 @@ def moe_mlp_w8(x, route: MoERoute, w8_up, s_up, w8_down, s_down, act: str = "swi
     """moe_mlp on weight-only FP8 expert weights: moe_up_w8, then moe_down_w8.  x, h, the biases, the residual and y stay bf16 /
     fp16; nothing synchronises, so the call can be captured in a graph."""
     return moe_down_w8(moe_up_w8(x, route, w8_up, s_up, act, w8_gate, s_gate, b_up, b_gate), route, w8_down, s_down, b_down, residual,
+                       out)
+
+
+# ---- the same on MXFP4 expert weights (mio_moe_up_w4, mio_moe_down_w4; DESIGN 4.2h) ---------------------------------------------------
+def quantize_expert_weights_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One-time preparation of a stacked bf16 / fp16 expert weight [E, N, K] (K % 32 == 0) for moe_up_w4 / moe_down_w4: (w4
+    [E, N, K / 2] uint8, scale [E, N, K / 32] uint8 e8m0).  It is quantize_weight_mxfp4 on the [E N, K] view (a block reads itself
+    alone), so expert e's part equals quantize_weight_mxfp4(w[e]) byte for byte."""
+    if not isinstance(w, torch.Tensor) or w.dim() != 3:
+        raise ValueError(f"quantize_expert_weights_mxfp4 takes a stacked weight [E, N, K], got {getattr(w, 'shape', None)}")
+    E, N, K = w.shape
+    w4, scale = quantize_weight_mxfp4(w.reshape(E * N, K))
+    return w4.view(E, N, K // 2), scale.unflatten(0, (E, N))
+
+
+def moe_up_w4_splits(T: int, top_k: int, E: int, I: int, d: int, activation: str = "swiglu") -> int:
+    """The slices of K = d a moe_up_w4 call of this shape runs (1: one launch, no workspace).  Host-only; ValueError where the
+    call would be refused."""
+    return _moe_splits(lib.mio_moe_up_w4_splits, T, top_k, E, I, d, _moe_act(activation))
+
+
+def moe_down_w4_splits(T: int, top_k: int, E: int, d: int, I: int) -> int:
+    """The slices of K = I a moe_down_w4 call of this shape runs.  Host-only; ValueError where the call would be refused."""
+    return _moe_splits(lib.mio_moe_down_w4_splits, T, top_k, E, d, I)
+
+
+def moe_up_w4(x, route: MoERoute, w4_up, s_up, act: str = "swiglu", w4_gate=None, s_gate=None, b_up=None, b_gate=None, out=None):
+    """moe_up on MXFP4 expert weights (mio_moe_up_w4): x [T, d] bf16 (fp16 is refused), w4_up (and w4_gate for swiglu) [E, I, d / 2]
+    uint8 e2m1 nibbles with d % 32 == 0, s_up / s_gate [E, I, d / 32] uint8 e8m0 (quantize_expert_weights_mxfp4 makes both) -> h
+    [T k, I] by sorted position: row p is act(x[t] deq_e^T + b_up[e]) (swiglu: silu of the gate's, times that).  Weights whose
+    strides are multiples of 16 bytes go to the launch as they are; scales of any row stride are taken, and where a stride is no
+    multiple of 4 bytes or the base is not 4-byte aligned a copy with padded rows is made.  Nothing synchronises with the host."""
+    return _moe_up_core(_MOE_DECODE_W4, x, route, w4_up, act, w4_gate, b_up, b_gate, out, s_up, s_gate)
+
+
+def moe_down_w4(h, route: MoERoute, w4_down, s_down, b_down=None, residual=None, out=None):
+    """moe_down on MXFP4 expert weights (mio_moe_down_w4): h [T k, I] by sorted position, w4_down [E, d, I / 2] uint8 with
+    I % 32 == 0, s_down [E, d, I / 32] uint8 e8m0 -> y [T, d] = sum_j weights[t, j] (h[row_pos[t k + j]] deq_e^T + b_down[e])
+    (+ residual[t]), e = ids[t, j]: the slots in slot order, rounded once.  Scales are prepared as moe_up_w4 says."""
+    return _moe_down_core(_MOE_DECODE_W4, h, route, w4_down, b_down, residual, out, s_down)
+
+
+def moe_mlp_w4(x, route: MoERoute, w4_up, s_up, w4_down, s_down, act: str = "swiglu", w4_gate=None, s_gate=None, b_up=None,
+               b_gate=None, b_down=None, residual=None, out=None):
+    """moe_mlp on MXFP4 expert weights: moe_up_w4, then moe_down_w4.  x, h, the biases, the residual and y are bf16; nothing
+    synchronises, so the call can be captured in a graph."""
+    return moe_down_w4(moe_up_w4(x, route, w4_up, s_up, act, w4_gate, s_gate, b_up, b_gate), route, w4_down, s_down, b_down, residual,
                        out)
 
 
