@@ -1119,6 +1119,45 @@ int mio_moe_prefill_down(const void* h, const void* w_down, const void* b_down, 
                          int32_t d, int32_t I, int64_t ldh, int64_t ldw, int64_t expert_stride, int64_t ldy,
                          int64_t ldr, int32_t dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The same two tiled grouped GEMMs on MXFP4 expert weights (csrc/moe_prefill_w4.hip).
+ * The route and its tile map are mio_moe_prefill_route's; shapes, limits, the meaning of h and y,
+ * the slot order, the workspace (mio_moe_prefill_down_workspace_bytes, the same fp32 rows), the
+ * ownership rules, the determinism and graph capture are those stated for mio_moe_prefill_up /
+ * _down above.  The arguments are theirs with each weight's scales behind it and lds,
+ * scale_expert_stride behind expert_stride, the way mio_moe_up_w4 extends mio_moe_up.
+ *
+ * Weights.  The storage form of mio_moe_up_w4 / mio_moe_down_w4 exactly: nibbles [E][N, K / 2]
+ * (element 2 i in the low nibble of byte i), ldw and expert_stride in BYTES, multiples of 16, ldw
+ * >= K / 2; e8m0 scale bytes [E][N, K / 32], lds and scale_expert_stride in BYTES, multiples of 4,
+ * lds >= K / 32, base 4-byte aligned.  K (d for up, I for down) must be a multiple of 32.  x, h,
+ * the biases, the residual and y are bf16 only.
+ *
+ * Arithmetic.  Weight-only: deq_e[n, k] = e2m1 * 2^(scale byte - 127) is formed exactly in bf16
+ * (scale bytes 2 .. 252) on the way into LDS and multiplied on the bf16 MFMA with fp32
+ * accumulation, every accumulator taking its 32-k steps in ascending order: both entry points
+ * equal mio_moe_prefill_up / _down on the bf16 tensor deq bit for bit, and see the effective
+ * weights the decode entry points see.  No scale is left for an epilogue.  The nibbles, the scale
+ * bytes and the biases of an expert with no routed row are never read; nor is a block at k >= K.
+ * Refused (< 0, mio_last_error() names the entry point) before any launch: everything
+ * mio_moe_prefill_up / _down refuse, with K a multiple of 32, ldw against K / 2 and in multiples
+ * of 16 bytes, the scale stride rules above, MIO_FP16, null scales, and gate nibbles and gate
+ * scales that do not come together iff SWIGLU.  T == 0 or N == 0 returns 0 and launches nothing.
+ * ------------------------------------------------------------------------------------------ */
+int mio_moe_prefill_up_w4(const void* x, const void* w4_up, const void* s_up, const void* b_up, const void* w4_gate,
+                          const void* s_gate, const void* b_gate, const int32_t* expert_offsets,
+                          const int32_t* sorted_rows, const int32_t* tile_expert, const int32_t* tile_row0,
+                          const int32_t* num_tiles, void* h, int32_t T, int32_t top_k, int32_t E, int32_t I,
+                          int32_t d, int64_t ldx, int64_t ldw, int64_t expert_stride, int64_t lds,
+                          int64_t scale_expert_stride, int64_t ldh, int32_t act, int32_t dtype, void* stream);
+int mio_moe_prefill_down_w4(const void* h, const void* w4_down, const void* s_down, const void* b_down,
+                            const int32_t* ids, const float* weights, const int32_t* expert_offsets,
+                            const int32_t* row_pos, const int32_t* tile_expert, const int32_t* tile_row0,
+                            const int32_t* num_tiles, const void* residual, void* y, void* workspace, int32_t T,
+                            int32_t top_k, int32_t E, int32_t d, int32_t I, int64_t ldh, int64_t ldw,
+                            int64_t expert_stride, int64_t lds, int64_t scale_expert_stride, int64_t ldy,
+                            int64_t ldr, int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

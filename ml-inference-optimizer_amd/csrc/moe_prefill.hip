@@ -27,8 +27,7 @@
 // Up's epilogue is the decode units' skinny_finish (bias, activation, one rounding) into h by sorted position; down stores fp32
 // rows by sorted position into the workspace and moe_common.h's moe_down_finish_kernel, at one slice, is where a token's slots
 // meet.
-#include "moe_common.h"
-#include "moe_prefill_plan.h"
+#include "moe_prefill_common.h"
 
 // ---- router ------------------------------------------------------------------------------------------------------------------
 struct MoePfRouteDev {
@@ -141,86 +140,44 @@ __global__ __launch_bounds__(MOE_PF_RT_NT) void moe_prefill_place_kernel(const M
 }
 
 // ---- grouped GEMM -------------------------------------------------------------------------------------------------------------
-struct MoePfDev {
-  const void* x;     // up: the tokens [T, ldx]; down: h by sorted position [T k, ldx]
-  const void* w;     // [E][N, ldw], experts expert_stride elements apart
-  const void* wg;    // SwiGLU: the gate weight, same strides
-  const void* bias;  // up: [E, N] or null
-  const void* bias_g;
-  void* y;           // up: h [T k, ldy]
-  float* ws;         // down: fp32 rows [T k][N] by sorted position
-  const int32_t* offsets;
-  const int32_t* sorted_rows;
-  const int32_t* tile_expert;
-  const int32_t* tile_row0;
-  const int32_t* num_tiles;
-  int64_t ldx, ldw, estride, ldy;
-  int T, topk, E, rows, N, K, act, max_tiles;
-};
-
-constexpr int MOE_PF_ROWB = MOE_PF_BK * 2;                    // bytes of a tile row in LDS
-constexpr int MOE_PF_PPT = MOE_PF_BM * 8 / MOE_PF_NT;         // 16-byte pieces of one operand's chunk per thread
-static_assert(MOE_PF_ROWB == 128 && MOE_PF_PPT == 4 && MOE_PF_NT / 8 * MOE_PF_PPT == MOE_PF_BM, "staging pattern: thread -> (row, piece)");
-
+// (the launch's arguments, the tile, the x staging, a chunk's MFMAs and the read-out: moe_prefill_common.h, shared with the MXFP4 unit)
 template <typename T, bool GLU, bool GATHER>
 __global__ __launch_bounds__(MOE_PF_NT, 2) void moe_prefill_gemm_kernel(const MoePfDev p) {
-  using X8 = typename DT<T>::x8;
   __shared__ __attribute__((aligned(16))) unsigned char lds[MOE_PF_LDS_BYTES];
   // the tile: BM sorted positions of one expert.  Past the map: nothing else is read and no barrier is met, all threads alike.
-  const int tile = blockIdx.x;
-  if (tile >= min(*p.num_tiles, p.max_tiles)) return;
-  const int e = min(max(p.tile_expert[tile], 0), p.E - 1);
-  const int row0 = min(max(p.tile_row0[tile], 0), p.rows);
-  const int cnt = min(MOE_PF_BM, min(p.offsets[e + 1], p.rows) - row0);
-  if (cnt <= 0) return;
+  MoePfTile t;
+  if (!moe_pf_tile(p, t)) return;
   constexpr int BN = GLU ? MOE_PF_BN_GLU : MOE_PF_BN;
-  constexpr int WN = BN / 2;  // output columns of a wave
   const int n0 = blockIdx.y * BN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = lane & 15, q = lane >> 4, wm = wave & 1, wn = wave >> 1;
 
-  // staging: piece i of this thread is (row srow + 32 i, k 8 (tid & 7) .. + 7) of both tiles; the swizzle does not depend on i
-  const int srow = tid >> 3, spk = (tid & 7) * 8;
-  const int soff = srow * MOE_PF_ROWB + (((tid & 7) ^ ((srow >> 1) & 7)) * 16);
+  // staging: piece i of this thread is (row srow + 32 i, k 8 (tid & 7) .. + 7) of both tiles
+  const MoePfStage st = moe_pf_stage(tid);
   const T* xsrc[MOE_PF_PPT];  // null: a row past the tile's count / a column past N, zeros
   const T* wsrc[MOE_PF_PPT];
+  moe_pf_x_sources<T, GATHER>(p, t, st, xsrc);
 #pragma unroll
   for (int i = 0; i < MOE_PF_PPT; ++i) {
-    const int row = srow + 32 * i;
-    xsrc[i] = nullptr;
-    if (row < cnt) {
-      const int pos = row0 + row;
-      const int src = GATHER ? min(max(p.sorted_rows[pos] / p.topk, 0), p.T - 1) : pos;
-      xsrc[i] = (const T*)p.x + (int64_t)src * p.ldx + spk;
-    }
     // weight tile row: column n0 + row; SwiGLU: rows 0 .. 63 the up weight's columns n0 .., rows 64 .. 127 the gate weight's
+    const int row = st.srow + 32 * i;
     const int n = n0 + (GLU ? (row & (MOE_PF_BN_GLU - 1)) : row);
     const T* wb = (const T*)((GLU && row >= MOE_PF_BN_GLU) ? p.wg : p.w);
-    wsrc[i] = n < p.N ? wb + (int64_t)e * p.estride + (int64_t)n * p.ldw + spk : nullptr;
+    wsrc[i] = n < p.N ? wb + (int64_t)t.e * p.estride + (int64_t)n * p.ldw + st.spk : nullptr;
   }
 
   u32x4_t rx[MOE_PF_PPT], rw[MOE_PF_PPT];
-  const auto fetch = [&](int k0) {  // K % 8 == 0: a piece lies inside [0, K) or past it
-    const bool kin = k0 + spk < p.K;
-#pragma unroll
-    for (int i = 0; i < MOE_PF_PPT; ++i) {
-      rx[i] = (u32x4_t){0u, 0u, 0u, 0u};
-      rw[i] = (u32x4_t){0u, 0u, 0u, 0u};
-      if (kin && xsrc[i]) rx[i] = *(const u32x4_t*)(xsrc[i] + k0);
-      if (kin && wsrc[i]) rw[i] = *(const u32x4_t*)(wsrc[i] + k0);
-    }
+  const auto fetch = [&](int k0) {
+    const bool kin = k0 + st.spk < p.K;
+    moe_pf_fetch<T>(xsrc, k0, kin, rx);
+    moe_pf_fetch<T>(wsrc, k0, kin, rw);
   };
   const auto stash = [&](int buf) {
-    unsigned char* xt = lds + buf * 2 * MOE_PF_TILE_BYTES + soff;
-#pragma unroll
-    for (int i = 0; i < MOE_PF_PPT; ++i) {
-      *(u32x4_t*)(xt + i * 32 * MOE_PF_ROWB) = rx[i];
-      *(u32x4_t*)(xt + MOE_PF_TILE_BYTES + i * 32 * MOE_PF_ROWB) = rw[i];
-    }
+    unsigned char* xt = lds + buf * 2 * MOE_PF_TILE_BYTES;
+    moe_pf_stash(xt, st, rx);
+    moe_pf_stash(xt + MOE_PF_TILE_BYTES, st, rw);
   };
 
-  // fragments: x rows wm 64 + 16 i + c; weight tile rows wrow(j) + c (plain: wn 64 + 16 j; SwiGLU: j < 2 up, j >= 2 gate)
-  const auto wrow = [&](int j) { return GLU ? (j >> 1) * MOE_PF_BN_GLU + wn * WN + 16 * (j & 1) : wn * WN + 16 * j; };
   f32x4_t acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -237,63 +194,11 @@ __global__ __launch_bounds__(MOE_PF_NT, 2) void moe_prefill_gemm_kernel(const Mo
     const bool more = ch + 1 < nchunks;
     if (more) fetch((ch + 1) * MOE_PF_BK);
     const unsigned char* xt = lds + (ch & 1) * 2 * MOE_PF_TILE_BYTES;
-    const unsigned char* wt = xt + MOE_PF_TILE_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int lro = c * MOE_PF_ROWB + (((ks * 4 + q) ^ (c >> 1)) * 16);
-      X8 a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) b[i] = __builtin_bit_cast(X8, *(const u32x4_t*)(xt + (wm * 64 + 16 * i) * MOE_PF_ROWB + lro));
-#pragma unroll
-      for (int j = 0; j < 4; ++j) a[j] = __builtin_bit_cast(X8, *(const u32x4_t*)(wt + wrow(j) * MOE_PF_ROWB + lro));
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = DT<T>::mfma16(a[j], b[i], acc[i][j]);
-    }
+    moe_pf_mma_chunk<T, GLU>(xt, xt + MOE_PF_TILE_BYTES, wm, wn, c, q, acc);
     if (more) stash((ch + 1) & 1);  // (the buffer chunk ch - 1 was read from, a barrier ago)
     __syncthreads();
   }
-
-  // lane (c, q): rows wm 64 + 16 i + c of the tile, i.e. sorted positions row0 + that, columns n .. n + 3
-  SkinnyFinish f = {};
-  if constexpr (GATHER) {
-    f.bias = p.bias ? (const char*)p.bias + (int64_t)e * p.N * 2 : nullptr;
-    f.bias_g = p.bias_g ? (const char*)p.bias_g + (int64_t)e * p.N * 2 : nullptr;
-    f.y = p.y;
-    f.ldy = p.ldy;
-    f.N = p.N;
-    f.act = p.act;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = wm * 64 + 16 * i + c;
-    if (m >= cnt) continue;
-    const int pos = row0 + m;
-#pragma unroll
-    for (int j = 0; j < (GLU ? 2 : 4); ++j) {
-      const int n = n0 + wn * WN + 16 * j + 4 * q;
-      if (n >= p.N) continue;
-      if constexpr (GATHER) {
-        const float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-        float g[4] = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (GLU) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) g[u] = acc[i][j + 2][u];
-        }
-        skinny_finish<T, GLU, false>(f, pos, n, v, g);
-      } else {
-        float* dst = p.ws + (int64_t)pos * p.N + n;
-        if ((p.N & 3) == 0) {  // (n + 3 < N then, and the rows are 16-byte aligned)
-          *(f32x4_t*)dst = acc[i][j];
-        } else {
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-            if (n + u < p.N) dst[u] = acc[i][j][u];
-        }
-      }
-    }
-  }
+  moe_pf_read_out<T, GLU, GATHER>(p, t, n0, wm, wn, c, q, acc);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
@@ -303,8 +208,6 @@ static const MoePfKernel MOE_PF_TABLE[2][3] = {
     {moe_prefill_gemm_kernel<__bf16, true, true>, moe_prefill_gemm_kernel<__bf16, false, true>, moe_prefill_gemm_kernel<__bf16, false, false>},
     {moe_prefill_gemm_kernel<_Float16, true, true>, moe_prefill_gemm_kernel<_Float16, false, true>,
      moe_prefill_gemm_kernel<_Float16, false, false>}};
-
-static inline bool moe_pf_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 extern "C" int mio_moe_prefill_max_tiles(int32_t T, int32_t top_k, int32_t E) {
   std::string err;
@@ -364,16 +267,12 @@ static int moe_pf_gemm_checks(const std::string& fn, int64_t T, int32_t k, int32
   return 0;
 }
 
-static MoePfDev moe_pf_args(const void* x, const void* w, const int32_t* offsets, const int32_t* sorted_rows, const int32_t* tile_expert,
-                            const int32_t* tile_row0, const int32_t* num_tiles, int64_t ldx, int64_t ldw, int64_t estride, int32_t T,
-                            int32_t k, int32_t E, int32_t N, int32_t K) {
-  MoePfDev p = {};
-  p.x = x; p.w = w;
-  p.offsets = offsets; p.sorted_rows = sorted_rows; p.tile_expert = tile_expert; p.tile_row0 = tile_row0; p.num_tiles = num_tiles;
-  p.ldx = ldx; p.ldw = ldw; p.estride = estride;
-  p.T = T; p.topk = k; p.E = E; p.rows = T * k; p.N = N; p.K = K; p.act = MIO_ACT_NONE;
-  p.max_tiles = (int)moe_prefill_max_tiles(T, k, E);
-  return p;
+void moe_pf_launch_down_finish(int32_t dtype, const MoePfDev& p, const void* b_down, const int32_t* ids, const float* weights,
+                               const int32_t* row_pos, const void* residual, void* y, int64_t ldy, int64_t ldr, hipStream_t st) {
+  const MoeDownDev f = {p.ws, nullptr, b_down, residual, y, ids, weights, row_pos, ldy, ldr, p.T, p.topk, p.E, p.rows, p.N, 1};
+  const int64_t threads = (int64_t)p.T * ((p.N + 3) / 4);
+  if (dtype == MIO_BF16) hipLaunchKernelGGL((moe_down_finish_kernel<__bf16, 1>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, f);
+  else hipLaunchKernelGGL((moe_down_finish_kernel<_Float16, 1>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, f);
 }
 
 extern "C" int mio_moe_prefill_up(const void* x, const void* w_up, const void* b_up, const void* w_gate, const void* b_gate,
@@ -385,13 +284,9 @@ extern "C" int mio_moe_prefill_up(const void* x, const void* w_up, const void* b
   if (int rc = moe_pf_gemm_checks(fn, T, top_k, E, I, d, act, dtype, ldx, ldw, expert_stride, ldh)) return rc;
   const bool glu = act == MIO_ACT_SWIGLU;
   MIO_CHECK(glu == (w_gate != nullptr), fn + ": w_gate is required iff act == SWIGLU");
-  MIO_CHECK(glu || b_gate == nullptr, fn + ": b_gate belongs to act == SWIGLU");
-  MIO_CHECK(w_up && (T == 0 || (x && h && expert_offsets && sorted_rows && tile_expert && tile_row0 && num_tiles)),
-            fn + ": x, w_up, h, expert_offsets, sorted_rows and the tile map must be non-null");
-  MIO_CHECK(mio_aligned16(x) && mio_aligned16(w_up) && mio_aligned16(w_gate) && mio_aligned16(b_up) && mio_aligned16(b_gate) &&
-                mio_aligned16(h) && moe_pf_aligned4(expert_offsets) && moe_pf_aligned4(sorted_rows) && moe_pf_aligned4(tile_expert) &&
-                moe_pf_aligned4(tile_row0) && moe_pf_aligned4(num_tiles),
-            fn + ": pointers must be 16-byte aligned (the route's arrays: 4-byte)");
+  if (int rc = moe_pf_up_pointer_checks(fn, x, w_up, b_up, w_gate, b_gate, expert_offsets, sorted_rows, tile_expert, tile_row0, num_tiles, h,
+                                        T, glu, ": x, w_up, h, expert_offsets, sorted_rows and the tile map must be non-null"))
+    return rc;
   if (T == 0 || I == 0) return 0;
   MoePfDev p = moe_pf_args(x, w_up, expert_offsets, sorted_rows, tile_expert, tile_row0, num_tiles, ldx, ldw, expert_stride, T, top_k, E, I, d);
   p.wg = w_gate; p.bias = b_up; p.bias_g = b_gate; p.y = h; p.ldy = ldh; p.act = act;
@@ -410,24 +305,18 @@ extern "C" int mio_moe_prefill_down(const void* h, const void* w_down, const voi
                                     int64_t expert_stride, int64_t ldy, int64_t ldr, int32_t dtype, void* stream) {
   const std::string fn = "mio_moe_prefill_down";
   if (int rc = moe_pf_gemm_checks(fn, T, top_k, E, d, I, MIO_ACT_NONE, dtype, ldh, ldw, expert_stride, ldy)) return rc;
-  MIO_CHECK(!residual || (ldr % 8 == 0 && ldr >= d), fn + ": ldr must be a multiple of 8 elements and at least d");
-  MIO_CHECK(w_down && (T == 0 || (h && y && ids && weights && expert_offsets && row_pos && tile_expert && tile_row0 && num_tiles)),
-            fn + ": h, w_down, y, ids, weights, expert_offsets, row_pos and the tile map must be non-null");
-  MIO_CHECK(mio_aligned16(h) && mio_aligned16(w_down) && mio_aligned16(b_down) && mio_aligned16(residual) && mio_aligned16(y) &&
-                mio_aligned16(workspace) && moe_pf_aligned4(ids) && moe_pf_aligned4(weights) && moe_pf_aligned4(expert_offsets) &&
-                moe_pf_aligned4(row_pos) && moe_pf_aligned4(tile_expert) && moe_pf_aligned4(tile_row0) && moe_pf_aligned4(num_tiles),
-            fn + ": pointers must be 16-byte aligned (the route's arrays: 4-byte)");
+  if (int rc = moe_pf_down_pointer_checks(fn, h, w_down, b_down, ids, weights, expert_offsets, row_pos, tile_expert, tile_row0, num_tiles,
+                                          residual, y, workspace, T, d, ldr,
+                                          ": h, w_down, y, ids, weights, expert_offsets, row_pos and the tile map must be non-null"))
+    return rc;
   if (T == 0 || d == 0) return 0;
   MIO_CHECK(workspace != nullptr, fn + ": workspace required (mio_moe_prefill_down_workspace_bytes)");
   MoePfDev p = moe_pf_args(h, w_down, expert_offsets, nullptr, tile_expert, tile_row0, num_tiles, ldh, ldw, expert_stride, T, top_k, E, d, I);
   p.ws = (float*)workspace;
-  const MoeDownDev f = {(const float*)workspace, nullptr, b_down, residual, y, ids, weights, row_pos, ldy, ldr, T, top_k, E, p.rows, d, 1};
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(MOE_PF_TABLE[dtype == MIO_BF16 ? 0 : 1][2], dim3((unsigned)p.max_tiles, (unsigned)((d + MOE_PF_BN - 1) / MOE_PF_BN)),
                      dim3(MOE_PF_NT), 0, st, p);
-  const int64_t threads = (int64_t)T * ((d + 3) / 4);
-  if (dtype == MIO_BF16) hipLaunchKernelGGL((moe_down_finish_kernel<__bf16, 1>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, f);
-  else hipLaunchKernelGGL((moe_down_finish_kernel<_Float16, 1>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, f);
+  moe_pf_launch_down_finish(dtype, p, b_down, ids, weights, row_pos, residual, y, ldy, ldr, st);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mio_fail(fn + " launch: " + hipGetErrorString(e));
   return 0;

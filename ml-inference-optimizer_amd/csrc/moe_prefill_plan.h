@@ -53,6 +53,21 @@ static inline bool moe_prefill_shape_ok(const char* who, int64_t T, int32_t k, i
   return false;
 }
 
+// The MXFP4 unit (moe_prefill_w4.hip): the same tile over e2m1 nibbles [E][N, K / 2] with one e8m0 scale byte per row and 32 k.  A
+// chunk of a weight tile row is MOE_PF_W4_BLOCKS MX blocks, each 16 bytes of nibbles and one scale byte, and the tile's (row,
+// block) pairs are one per thread.  The shape rule is the 16-bit one with whole MX blocks, under the decode form's words.
+constexpr int MOE_PF_W4_BLOCKS = MOE_PF_BK / 32;
+static_assert(MOE_PF_BN * MOE_PF_W4_BLOCKS == MOE_PF_NT, "MXFP4 weight staging: one (row, block) per thread");
+
+static inline bool moe_prefill_w4_shape_ok(const char* who, int64_t T, int32_t k, int32_t E, int32_t N, int32_t K, int32_t act,
+                                           std::string& err) {
+  // (K rounded to 8: the 16-bit rule on K has nothing to say, the one below says it in the half-byte form's words)
+  if (!moe_prefill_shape_ok(who, T, k, E, N, K - K % 8, act, err)) return false;
+  if (K % SKINNY_W4.k_multiple == 0) return true;
+  err = std::string(who) + SKINNY_W4.k_multiple_text;
+  return false;
+}
+
 // down: fp32 rows [T k][N] by sorted position, the decode path's partials layout with one slice
 static inline size_t moe_prefill_down_workspace_bytes(int64_t T, int32_t k, int32_t N) {
   return (size_t)(T * k) * (size_t)N * sizeof(float);

@@ -183,6 +183,8 @@ EXPORTS = (
     "mio_moe_prefill_up",
     "mio_moe_prefill_down_workspace_bytes",
     "mio_moe_prefill_down",
+    "mio_moe_prefill_up_w4",
+    "mio_moe_prefill_down_w4",
 )
 
 
@@ -507,6 +509,11 @@ def _load() -> C.CDLL:
     # E, d, I, ldh, ldw, expert_stride, ldy, ldr, dtype, stream
     lib.mio_moe_prefill_down.argtypes = [vp] * 13 + [i32] * 5 + [i64] * 5 + [i32, vp]
     lib.mio_moe_prefill_down.restype = i32
+    # the same pair on MXFP4 expert weights: each weight's scales behind it, lds and scale_expert_stride (bytes) behind expert_stride
+    lib.mio_moe_prefill_up_w4.argtypes = [vp] * 13 + [i32] * 5 + [i64] * 6 + [i32, i32, vp]
+    lib.mio_moe_prefill_up_w4.restype = i32
+    lib.mio_moe_prefill_down_w4.argtypes = [vp] * 14 + [i32] * 5 + [i64] * 7 + [i32, vp]
+    lib.mio_moe_prefill_down_w4.restype = i32
     return lib
 
 

@@ -4,7 +4,8 @@ MoEMLP replaces the MLP of a Mixtral / Qwen-MoE / OLMoE class block: a router (o
 top_k experts of every token, and the weighted sum of those experts' MLPs.  forward() is the router GEMM, ops.moe_route and
 ops.moe_mlp (the grouped up projection, then the grouped down projection with the combine): four to six launches whatever E is,
 the routing device data from start to end, so a step can be captured in a graph.  MoEConfig selects the FP8 copies of the expert
-weights (ops.moe_mlp_w8) or, for more than 64 rows, the tiled path (ops.moe_route_prefill, ops.moe_mlp_prefill).  There is no
+weights (ops.moe_mlp_w8) or, for more than 64 rows, the tiled path (ops.moe_route_prefill, ops.moe_mlp_prefill; on loaded MXFP4 bytes
+ops.moe_mlp_prefill_w4).  There is no
 PyTorch path: CPU tensors raise ValueError as the other modules do.
 """
 from __future__ import annotations
@@ -34,7 +35,9 @@ class MoEConfig:
     expert_weights_mxfp4: the same with MXFP4 copies (ops.quantize_expert_weights_mxfp4: e2m1 nibbles, one e8m0 scale byte per 32
     k) through ops.moe_mlp_w4: a quarter of the 16-bit weight bytes plus 1/32 for the scales per step.  Exclusive with
     expert_weights_fp8; hidden_size and intermediate_size must be multiples of 32; dtype must be bf16.  The router GEMM and
-    grouped_prefill stay 16-bit.  Off by default (profiles/moe_w4.md)."""
+    grouped_prefill stay 16-bit: the module holds the 16-bit parameters, and its tall inputs read them.  A module whose experts
+    were loaded as MXFP4 bytes (MoEMLP.load_mxfp4_experts) holds nothing else, and its grouped_prefill runs the tiled grouped
+    GEMMs on those bytes (ops.moe_mlp_prefill_w4, profiles/moe_prefill_w4.md).  Off by default (profiles/moe_w4.md)."""
     activation: str = "swiglu"
     renormalize: bool = True
     dtype: torch.dtype = torch.bfloat16
@@ -110,7 +113,8 @@ class MoEMLP(nn.Module):
         without host synchronisation, but every chunk streams its experts' weights again -- unless config.grouped_prefill is on:
         then T > 64 is one router GEMM, one ops.moe_route_prefill and one ops.moe_mlp_prefill per 8192 rows.  With
         config.expert_weights_fp8 the decode path (T <= 64 and the row chunks) reads the FP8 copies of the expert weights; the
-        grouped prefill path reads the 16-bit weights."""
+        grouped prefill path reads the 16-bit weights -- or, after load_mxfp4_experts, the loaded bytes through
+        ops.moe_mlp_prefill_w4."""
         if not hidden_states.is_cuda:
             raise ValueError("Input tensor must be on a CUDA device for the HIP kernels")
         d = self.hidden_size
@@ -125,9 +129,11 @@ class MoEMLP(nn.Module):
         out = ops.empty_rows8(T, d, dt, x.device)
         # the path, chosen once on the whole T (a short last chunk of a tall input stays on the prefill ops): its chunk length,
         # its route and MLP ops, and the weights under the names that MLP op takes them by
-        prefill = self.config.grouped_prefill and T > ops.MOE_MAX_TOKENS and not self._mxfp4
+        prefill = self.config.grouped_prefill and T > ops.MOE_MAX_TOKENS
         if self._mxfp4 or (self.config.expert_weights_mxfp4 and not prefill):
-            chunk, route_op, mlp_op = ops.MOE_MAX_TOKENS, ops.moe_route, ops.moe_mlp_w4
+            # (loaded MXFP4 bytes are the only expert weights there are: their tall inputs run the tiled path on those bytes)
+            chunk, route_op, mlp_op = ((ops.MOE_PREFILL_MAX_TOKENS, ops.moe_route_prefill, ops.moe_mlp_prefill_w4) if prefill
+                                       else (ops.MOE_MAX_TOKENS, ops.moe_route, ops.moe_mlp_w4))
             if dt != torch.bfloat16:
                 raise ValueError("MXFP4 expert weights need dtype bf16")
             if self._mxfp4:
@@ -157,8 +163,9 @@ class MoEMLP(nn.Module):
         """Take pre-quantised MXFP4 expert weights as they are: blocks uint8 [E, N, K / 2] (or [E, N, K / 32, 16], taken by view),
         e2m1 nibbles with element 2 i in the low nibble of byte i, and scales uint8 e8m0 [E, N, K / 32]; N, K = I, d for up and
         gate, d, I for down; the gate pair is None where the activation is not swiglu.  The module then holds no 16-bit expert
-        weights (w_up, w_gate and w_down become None): the decode path on these bytes is its only one, T > 64 goes in row chunks
-        of 64, and config.dtype must be bf16.  The tensors are kept, not copied, where the kernels can take them as they lie, as
+        weights (w_up, w_gate and w_down become None): T <= 64 is the decode path on these bytes (ops.moe_mlp_w4); T > 64 goes
+        through it in row chunks of 64, or with config.grouped_prefill through the tiled path on the same bytes
+        (ops.moe_route_prefill, ops.moe_mlp_prefill_w4) per 8192 rows; config.dtype must be bf16.  The tensors are kept, not copied, where the kernels can take them as they lie, as
         non-persistent buffers mxfp4_w4_up, mxfp4_s_up, ...: module.to(device) moves them, state_dict() does not hold them (a
         checkpoint of such a module is the bytes it was loaded from), and load_from_expert_state_dict is refused afterwards."""
         E, I, d = self.num_experts, self.intermediate_size, self.hidden_size

@@ -35,6 +35,8 @@ same exception types for the same conditions):
   moe_route_prefill / moe_up_prefill / moe_down_prefill / moe_mlp_prefill
                                the same for tall inputs (T <= 8192): a tile map built on the device, 128 x 128 x 64 tiled grouped
                                GEMMs, one pass over the active experts' weights
+  moe_up_prefill_w4 / moe_down_prefill_w4 / moe_mlp_prefill_w4
+                               the tiled grouped GEMMs on MXFP4 expert weights, widened to bf16 on the way into LDS, bf16 only
 There is no fallback path: a non-zero return from the library raises RuntimeError.
 """
 from __future__ import annotations
@@ -2113,9 +2115,9 @@ def sampling_probs(logits, temperature, top_k=None, top_p=None, min_p=None):
 
 
 # ------------------------------------------------------------------------------------------------
-# mixture-of-experts MLP: router, grouped up projection, grouped down projection + combine.  Three paths -- decode steps on
-# 16-bit experts, decode steps on FP8 experts, tall inputs (prefill) over a tile map -- each a _MoEPath record; route, up and
-# down are stated once (_moe_route_core, _moe_up_core, _moe_down_core) and the public ops hand them their path
+# mixture-of-experts MLP: router, grouped up projection, grouped down projection + combine.  Five paths -- decode steps on
+# 16-bit, FP8 and MXFP4 experts, tall inputs (prefill) over a tile map on 16-bit and MXFP4 experts -- each a _MoEPath record; route,
+# up and down are stated once (_moe_route_core, _moe_up_core, _moe_down_core) and the public ops hand them their path
 # ------------------------------------------------------------------------------------------------
 MOE_MAX_TOKENS, MOE_MAX_EXPERTS, MOE_MAX_TOP_K = 64, 256, 8
 MOE_PREFILL_MAX_TOKENS = 8192
@@ -2254,6 +2256,10 @@ _MOE_PREFILL = _MOE_DECODE._replace(
     route_ok=_moe_prefill_route_ok, max_tokens=MOE_PREFILL_MAX_TOKENS, cap_note="", tiled=True,
     route_entry=lib.mio_moe_prefill_route, up_entry=lib.mio_moe_prefill_up, up_workspace_bytes=None,
     down_entry=lib.mio_moe_prefill_down, down_workspace_bytes=lib.mio_moe_prefill_down_workspace_bytes)
+# (the tall-input route and workspace over the MXFP4 record's weights)
+_MOE_PREFILL_W4 = _MOE_PREFILL._replace(
+    up_op="moe_up_prefill_w4", down_op="moe_down_prefill_w4", up_entry=lib.mio_moe_prefill_up_w4, down_entry=lib.mio_moe_prefill_down_w4,
+    **{f: getattr(_MOE_DECODE_W4, f) for f in ("w_dtype", "w_multiple", "k_multiple", "pre", "scaled", "block_scales", "k_per_elem")})
 
 
 def moe_route(router_logits, top_k: int, renormalize: bool = True, out: Optional[MoERoute] = None) -> MoERoute:
@@ -2648,6 +2654,32 @@ def moe_mlp_prefill(x, route: MoEPrefillRoute, w_up, w_down, act: str = "swiglu"
     w_gate [E, I, d], w_down [E, d, I], biases [E, I] / [E, d].  h and the workspace come from torch's allocator; nothing
     synchronises, so the call can be captured in a graph."""
     return moe_down_prefill(moe_up_prefill(x, route, w_up, act, w_gate, b_up, b_gate), route, w_down, b_down, residual, out)
+
+
+# ---- the same on MXFP4 expert weights (mio_moe_prefill_up_w4 / _down_w4; DESIGN 4.2i): moe_route_prefill's route, moe_up_w4's bytes
+def moe_up_prefill_w4(x, route: MoEPrefillRoute, w4_up, s_up, act: str = "swiglu", w4_gate=None, s_gate=None, b_up=None, b_gate=None,
+                      out=None):
+    """moe_up_prefill on MXFP4 expert weights (mio_moe_prefill_up_w4): x [T, d] bf16 (fp16 is refused), w4_up / w4_gate
+    [E, I, d / 2] uint8 and s_up / s_gate [E, I, d / 32] uint8 e8m0 exactly as moe_up_w4 takes them -> h [T k, I] by sorted
+    position.  The nibbles are widened to bf16 with their block scales on the way into LDS, exactly, so h equals moe_up_prefill on
+    the bf16 dequantisation bit for bit; a weight tile's bytes are read once per 128 rows of its expert."""
+    return _moe_up_core(_MOE_PREFILL_W4, x, route, w4_up, act, w4_gate, b_up, b_gate, out, s_up, s_gate)
+
+
+def moe_down_prefill_w4(h, route: MoEPrefillRoute, w4_down, s_down, b_down=None, residual=None, out=None, workspace=None):
+    """moe_down_prefill on MXFP4 expert weights (mio_moe_prefill_down_w4): h [T k, I] bf16 by sorted position, w4_down [E, d, I / 2]
+    uint8 with s_down [E, d, I / 32] uint8 e8m0 as moe_down_w4 takes them -> y [T, d] as moe_down states it on the dequantised
+    weight.  workspace: as moe_down_prefill's, the same T k d fp32 elements."""
+    return _moe_down_core(_MOE_PREFILL_W4, h, route, w4_down, b_down, residual, out, s_down, workspace=workspace)
+
+
+def moe_mlp_prefill_w4(x, route: MoEPrefillRoute, w4_up, s_up, w4_down, s_down, act: str = "swiglu", w4_gate=None, s_gate=None,
+                       b_up=None, b_gate=None, b_down=None, residual=None, out=None):
+    """The experts' MLP of a tall input on MXFP4 expert weights under a moe_route_prefill routing: moe_up_prefill_w4, then
+    moe_down_prefill_w4.  x [T, d] bf16 (T <= 8192); weights and scales as moe_mlp_w4 takes them.  Nothing synchronises, so the
+    call can be captured in a graph and replays under any routing."""
+    return moe_down_prefill_w4(moe_up_prefill_w4(x, route, w4_up, s_up, act, w4_gate, s_gate, b_up, b_gate), route, w4_down, s_down,
+                               b_down, residual, out)
 
 
 # ------------------------------------------------------------------------------------------------
